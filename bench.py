@@ -12,6 +12,7 @@ batch of synthetic input already resident in HBM.
 `value` = ODE steps integrated per second by the whole job = n_gpus * 50 * K / T.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs bench_outputs   # + the last timed step's outputs as bench_outputs/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --steps K --warmup W        # the same: starts its own N ranks (one fresh process per GPU);
@@ -803,8 +804,14 @@ def main():
     ap.add_argument("--batched", type=int, default=8,
                     help="N=1 only: after the BASELINE measurement, also time this many trajectories per GPU as one batched "
                          "graph (reported under 'batched', never in 'value'); 0 = skip")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed on rank 0 as DIR/<name>.npy (float32, ~8 MB): "
+                         "u(T), du0, the parameter gradients dw1 db1 dw2 db2 and the parameters w1 b1 w2 b2 after its Adam update "
+                         "(weights [in][out], states [node][feature]); the inputs are seeded, so two builds compare output for output")
     ap.add_argument("--child-layer", default=None, help=argparse.SUPPRESS)   # (internal: one layer leg in a loop, for the rocprofv3 child pass)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.child_layer:
         child_layer(args.child_layer)
         return
@@ -951,6 +958,12 @@ def main():
         fence()
         elapsed = time.perf_counter() - t0
         job.step_ms = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(n_steps))
+        if traj == 1 and args.dump_outputs:
+            # what the last timed step handed its caller (outside the timed region; the split below solves again with the
+            # parameters the last Adam step wrote, so it would not be the timed step's output any more)
+            job.outputs = {"uT": uT, "du0": du0, "dw1": dw1.view(D, D), "db1": db1, "dw2": dw2.view(D, D), "db2": db2,
+                           "w1": w1.view(D, D), "b1": b1, "w2": w2.view(D, D), "b2": b2}
+            job.outputs = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in job.outputs.items()}
         if dist is not None:
             tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -1017,6 +1030,10 @@ def main():
         return (time.perf_counter() - t0) / n_steps
 
     elapsed, ms_fwd, ms_bwd, plan = job(1, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in job.outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     api_s = api_job(args.steps, args.warmup) if world == 1 else None
     step_ms = list(job.step_ms)      # this rank's per-step device times of the timed region (`value` stays K steps / wall time)
 
