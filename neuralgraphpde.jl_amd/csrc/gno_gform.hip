@@ -119,7 +119,9 @@ __global__ __launch_bounds__(256, 3) void gno_gform_fwd_kernel(const GFormArgs p
       const int r = rh + GG::RG * ps;
       const float4 v = hreg[ps];
       if (p.hsum) {   // uniform
-        if (full) hpart = f4_add(hpart, v);
+        // (unmasked only where the passes cover exactly the chunk: with RG > GC -- in = 32 at 16-edge chunks -- rows GC .. RG - 1 are
+        // clamped copies of the chunk's last edge even in a full chunk)
+        if (GG::HP * GG::RG == kGC && full) hpart = f4_add(hpart, v);
         else hpart = f4_fma(r < nb ? 1.0f : 0.0f, v, hpart);
       }
       if (GG::HP * GG::RG == kGC || r < kGC) *reinterpret_cast<float4 *>(&ldsH[r * GG::HS + 4 * c4h]) = v;
@@ -253,7 +255,7 @@ int32_t ngpde_gno_gform_preferred(int64_t n_nodes, int64_t n_edges, int32_t in_c
   // config 5) that this form's forward must win back on the edges: it does from about 64 edges per node (radius 0.1, 117 per node:
   // forward + backward 0.895 -> 0.861 ms; radius 0.05, 34 per node: 0.623 -> 0.657 ms, so not there).
   if (ngpde_gno_gform_supported(in_chs, kdim) != 1 || cout % 4 != 0 || n_edges <= 0) return 0;
-  if ((uint64_t)n_nodes * (uint64_t)in_chs * 4u >= (1ull << 32)) return 0;
+  if ((uint64_t)n_nodes * (uint64_t)std::max(in_chs, kGK) * 4u >= (1ull << 32)) return 0;   // (h and Q rows: 32-bit byte offsets)
   return (!training || n_edges >= 64 * n_nodes) ? 1 : 0;
 }
 
@@ -275,8 +277,8 @@ int32_t ngpde_gno_gform_aggregate(const ngpde_graph_t *g, int32_t in_chs, int32_
   NGPDE_REQUIRE(act1 >= NGPDE_ACT_IDENTITY && act1 <= NGPDE_ACT_SOFTPLUS, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_gform_aggregate: unknown activation %d", act1);
   if (g->n_nodes == 0) return NGPDE_OK;
   NGPDE_REQUIRE(h && gout && (p_target || q_source || e_term), NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_gform_aggregate: NULL argument");
-  NGPDE_REQUIRE((uint64_t)g->n_nodes * (uint64_t)in_chs * 4u < (1ull << 32), NGPDE_ERR_UNSUPPORTED,
-                "ngpde_gno_gform_aggregate: h beyond 4 GB (rows are fetched with 32-bit offsets)");
+  NGPDE_REQUIRE((uint64_t)g->n_nodes * (uint64_t)std::max(in_chs, kGK) * 4u < (1ull << 32), NGPDE_ERR_UNSUPPORTED,
+                "ngpde_gno_gform_aggregate: h or Q beyond 4 GB (rows are fetched with 32-bit offsets)");
   NGPDE_REQUIRE(((reinterpret_cast<uintptr_t>(p_target) | reinterpret_cast<uintptr_t>(q_source) | reinterpret_cast<uintptr_t>(e_term) | reinterpret_cast<uintptr_t>(h) |
                   reinterpret_cast<uintptr_t>(gout) | reinterpret_cast<uintptr_t>(hsum) | reinterpret_cast<uintptr_t>(z_out)) & 15) == 0,
                 NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_gform_aggregate: every array must be 16-byte aligned");
@@ -285,7 +287,9 @@ int32_t ngpde_gno_gform_aggregate(const ngpde_graph_t *g, int32_t in_chs, int32_
   a.P = p_target; a.Q = q_source; a.Et = e_term; a.h = h; a.G = gout; a.hsum = hsum; a.z_out = z_out; a.act1 = act1; a.mean = mean ? 1 : 0;
   const dim3 grid((unsigned)g->n_nodes), block(256);
   hipStream_t s = (hipStream_t)stream;
-  static const int chunk = [] { const char *e = std::getenv("NGPDE_GNO_GFORM_CHUNK"); return e ? std::atoi(e) : 32; }();   // (A/B runs: 16 or 32)
+  // edges per chunk (A/B runs): NGPDE_GNO_GFORM_CHUNK=16; unset or any other value means 32.  Read per call, as the other switches.
+  const char *chunk_env = std::getenv("NGPDE_GNO_GFORM_CHUNK");
+  const int chunk = chunk_env && std::atoi(chunk_env) == 16 ? 16 : 32;
 #define NGPDE_GF2(CC, AA)                                                                         \
   do {                                                                                            \
     if (chunk == 16) hipLaunchKernelGGL((gno_gform_fwd_kernel<CC, 16, AA>), grid, block, 0, s, a); \

@@ -5,7 +5,7 @@ at all), node counts across partial tiles, state as a matrix or a NamedTuple, ex
 depths 1 - 5 and widths 1 - 72 (64 => 64 tails reach the specialised message kernels), activations, aggregations + / mean / max / min / *.
 The entry's plan (fused message launch or primitives, one-launch pullback or saved pre-activations, chain / pair Dense launches, the
 three GNO message forms) is whatever make_plan decides for the case.  With ORACLE=1 the entry's output, input gradient and phi's
-gradients of every ExplicitEdgeConv / VMHConv / MPPDEConv case with a matrix state are also compared with
+gradients of every ExplicitEdgeConv / VMHConv / MPPDEConv / GNOConv case with a matrix state are also compared with
 the float64 oracle (oracle/ngpde_oracle.py) at the suite's tolerances (1e-4 / 5e-4 of the largest value).
 usage: [ORACLE=1] python3 tools/fuzz_layer_entries.py [cases=60] [seed=1] [verbose=0]      exit code 1 when a case differs"""
 import os
@@ -184,7 +184,7 @@ def off(a, ref, rtol, atol):
 
 def against_oracle(layer, x, seed):
     """[] or the list of quantities beyond tolerance; None when the case is not one the oracle leg covers"""
-    if isinstance(x, dict) or isinstance(layer, ng.GNOConv):
+    if isinstance(x, dict):
         return None
     g = layer.initialgraph()
     s, t = g.edge_index(0)
@@ -207,9 +207,15 @@ def against_oracle(layer, x, seed):
     elif isinstance(layer, ng.VMHConv):
         yo, c = O.vmh_conv(x64, omlp(layer.ϕ, ps["ϕ"]), omlp(layer.γ, ps["γ"]), og, aggr=layer.aggr)
         gr, sub = O.vmh_conv_backward(c, R), ps["ϕ"]
-    else:
+    elif isinstance(layer, ng.MPPDEConv):
         yo, c = O.mppde_conv(x64, omlp(layer.ϕ, ps["ϕ"]), omlp(layer.ψ, ps["ψ"]), og, aggr=layer.aggr)
         gr, sub = O.mppde_conv_backward(c, R), ps["ϕ"]
+    else:
+        lin = ps["linear"]
+        yo, c = O.gno_conv(x64, omlp(layer.ϕ, ps["ϕ"]), lin["weight"].detach().cpu().double().numpy(),
+                           lin["bias"].detach().cpu().double().numpy() if "bias" in lin else None, og, layer.in_chs, layer.out_chs,
+                           layer.linear.activation, layer.aggr)
+        gr, sub = O.gno_conv_backward(c, R), ps["ϕ"]
     if isinstance(layer, ng.ExplicitEdgeConv) and layer.aggr in ("max", "min"):
         yo = np.where(np.isfinite(yo), yo, 0.0)
     if not np.isfinite(yo).all() or np.abs(yo).max() > 1e6:
