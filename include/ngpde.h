@@ -455,8 +455,9 @@ int32_t ngpde_node_expect_generation(const ngpde_node_t *plan, uint64_t generati
  * this returns the number of kernel launches one forward (+ backward) solve enqueues. */
 int32_t ngpde_node_launch_count(const ngpde_node_t *plan, int32_t *forward, int32_t *backward);
 /* which internal forms the plan chose: bit 0 = pre-scaled arrays (rows held as c .* x, halo rows staged by LDS-DMA),
- * bit 1 = relu sign-bit masks instead of saved layer outputs, bit 2 = eager launches (no HIP-graph replay), bits 3 / 4 = the
- * forward solve / the adjoint run as ONE persistent launch each, tiles synchronised inside the launch by per-tile phase flags:
+ * bit 1 = relu sign-bit masks instead of saved layer outputs, bit 2 = reserved (never set), bits 3 / 4 = the forward solve / the
+ * adjoint run as ONE persistent launch each (a plan is persistent in every direction it has or in none: bit 4 is set exactly when
+ * bit 3 is and the plan has a backward), tiles synchronised inside the launch by per-tile phase flags:
  * graphs whose tiles fit the LDS halo, d = 64 (d = 16 / 32 zero-padded onto it, bit 7), any activation; up to 2 tiles per
  * co-resident workgroup in registers (bit 5), up to 8 taking turns (bit 6); graphs with edge weights on the turn-taking form with
  * the slot weights in LDS (up to 3 tiles per workgroup); graphs with hubs of at most one tile per CU in the hub geometry (bit 8).  d = 128,
@@ -464,7 +465,7 @@ int32_t ngpde_node_launch_count(const ngpde_node_t *plan, int32_t *forward, int3
  * needs all its workgroups resident at once: run one such solve at a time per device (NGPDE_NO_PERSISTENT=1 selects the
  * replayed plan otherwise).  Its waits are bounded; a launch that gives up writes NaN outputs and raises the plan's fault
  * flag, which ngpde_node_fault reads (synchronises `stream`). */
-enum { NGPDE_NODE_PRESCALED = 1, NGPDE_NODE_SIGN_MASKS = 2, NGPDE_NODE_EAGER = 4, NGPDE_NODE_PERSISTENT_FWD = 8,
+enum { NGPDE_NODE_PRESCALED = 1, NGPDE_NODE_SIGN_MASKS = 2, /* 4: reserved, never set (was NGPDE_NODE_EAGER) */ NGPDE_NODE_PERSISTENT_FWD = 8,
        NGPDE_NODE_PERSISTENT_BWD = 16, NGPDE_NODE_TILE_PAIRS = 32 /* persistent launches with two tiles per workgroup */,
        NGPDE_NODE_TILE_ROUNDS = 64 /* persistent launches with k tiles per workgroup taking turns (larger graphs) */,
        NGPDE_NODE_WIDENED = 128 /* d = 16 / 32 run zero-padded on the 64-wide persistent kernels (NGPDE_NO_WIDEN=1 turns it off) */,
@@ -472,8 +473,8 @@ enum { NGPDE_NODE_PRESCALED = 1, NGPDE_NODE_SIGN_MASKS = 2, NGPDE_NODE_EAGER = 4
                                         beyond the 96-row halo / 32-entry rows (a Cora-shaped graph, docs/src/tutorials/graph_node.md:14-23):
                                         256-row halos, variable-length rows, hub rows summed by all lane groups of the workgroup */,
        NGPDE_NODE_OWN_FIRST = 512 /* the plan reads its own slot tables (by-target lists): each row's own-tile neighbours first, which the
-                                     one-tile forward launch sums while it waits for the neighbouring tiles; every kernel of the plan
-                                     sums in that order (graphs of at most two tiles per CU; NGPDE_NO_OWN_FIRST=1 at create keeps the handle's order) */ };
+                                     one-tile forward launch sums while it waits for the neighbouring tiles; every forward kernel of
+                                     the plan sums in that order (graphs of at most two tiles per CU; NGPDE_NO_OWN_FIRST=1 at create keeps the handle's order) */ };
 int32_t ngpde_node_flags(const ngpde_node_t *plan, int32_t *flags);
 /* Host only, no device call: the node numbering of a block-diagonal batch (Flux.batch / MLUtils.batch of single graphs,
  * /root/reference/test/runtests.jl:89-102, docs/src/tutorials/VMH.md:120-134) whose members are padded to whole 32-row tiles, so

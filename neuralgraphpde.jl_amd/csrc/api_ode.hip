@@ -73,11 +73,14 @@ int32_t ngpde_ode_create(const ngpde_graph_t *g, const ngpde_ode_desc_t *d, ngpd
       if (d->members > 1)
         st = ngpde_node_gat_create_batch(g, d->members, d->heads, d->head_width, d->negative_slope, d->act, d->tableau, d->n_steps, d->dt, d->with_backward, &o->gat);
       else st = ngpde_node_gat_create(g, d->heads, d->head_width, d->negative_slope, d->act, d->tableau, d->n_steps, d->dt, d->with_backward, &o->gat);
-      fl = NGPDE_NODE_PERSISTENT_FWD | NGPDE_NODE_PERSISTENT_BWD;
+      fl = NGPDE_NODE_PERSISTENT_FWD | (d->with_backward ? NGPDE_NODE_PERSISTENT_BWD : 0);
       break;
     }
     case NGPDE_RHS_VMH: {
-      NGPDE_REQUIRE(d->members == 1, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_create: a batch of point clouds is ONE block-diagonal graph to the VMH plan (members = 1)");
+      if (d->members != 1) {
+        st = fail(NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_create: a batch of point clouds is ONE block-diagonal graph to the VMH plan (members = 1)");
+        break;
+      }
       const int hd = d->width;
       if ((st = check_mlp_chain("phi", d->n_phi, d->phi_dims, d->phi_acts, 2 * hd + d->pos_width, -1))) break;
       if ((st = check_mlp_chain("gamma", d->n_gamma, d->gamma_dims, d->gamma_acts, hd + d->phi_dims[d->n_phi], hd))) break;
@@ -89,7 +92,7 @@ int32_t ngpde_ode_create(const ngpde_graph_t *g, const ngpde_ode_desc_t *d, ngpd
       }
       st = ngpde_node_vmh_create(g, hd, d->pos_width, d->pos, d->n_phi, d->phi_dims, d->phi_acts, d->n_gamma, d->gamma_dims, d->gamma_acts, d->aggr, d->tableau,
                                  d->n_steps, d->dt, d->with_backward, &o->vmh);
-      fl = NGPDE_NODE_PERSISTENT_FWD | NGPDE_NODE_PERSISTENT_BWD;
+      fl = NGPDE_NODE_PERSISTENT_FWD | (d->with_backward ? NGPDE_NODE_PERSISTENT_BWD : 0);
       break;
     }
     default: st = fail(NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_create: unknown right-hand side %d", d->rhs);

@@ -168,7 +168,6 @@ struct FusedBwdArgs {
   const float *z = nullptr;      // [N][d] saved pre-activation (or y for relu/identity); unused when mask is given
   const uint8_t *mask = nullptr; // sign bits written by the forward launch (same tile / thread layout), relu only
   bool pre = false;              // pre-scaled pipeline: g_in holds c .* G, T is dL/d(c .* x), g_out is written as c .* G
-  const OwnFirst *of = nullptr;  // as in FusedFwdArgs (the by-source tables)
   const float *saved_agg = nullptr;  // [N][d]
   const float *wt = nullptr;     // [d][d]
   float *g_out = nullptr;        // [N][d]  dZ * W
@@ -187,18 +186,18 @@ int32_t launch_zero(void *ptr, size_t bytes, hipStream_t stream);   // graph-cap
 // ---- persistent solver launches (node_persistent.hip): the whole forward solve / adjoint of the 2 x GCNConv(64 => 64) plan as
 // ONE launch each, tiles synchronised by per-tile phase flags
 // Own-first slot tables of a solver plan over GCNConv layers (node_persistent.hip: own_first_tables_build).  A 32-row tile's own rows
-// are in LDS when a phase of the persistent solver starts; what it waits for are the rows of other tiles.  Per direction the plan
-// holds a COPY of the handle's slot bytes in which every row lists the slots of its tile's own rows first, padded with the all-zero
-// row to a whole number of 4-slot rounds common to the four rows of a wave, then the slots of foreign rows -- and the schedule
-// entries with the padded length in place of the degree, so that every kernel of the plan (persistent in all its forms, replayed)
-// walks the same rounds in the same order and the results stay bitwise comparable -- plus, per wave, the number of own rounds,
-// which the one-tile persistent kernels sum BEFORE they wait for their neighbours.  The handle's own lists are untouched (the
-// edge-function, GAT and VMH kernels index per-edge arrays by a row's CSR position).
+// are in LDS when a phase of the persistent solver starts; what it waits for are the rows of other tiles.  For the forward direction
+// (by target) the plan holds a COPY of the handle's slot bytes in which every row lists the slots of its tile's own rows first, padded
+// with the all-zero row to a whole number of 4-slot rounds common to the four rows of a wave, then the slots of foreign rows -- and the
+// schedule entries with the padded length in place of the degree, so that every forward kernel of the plan (persistent in all its
+// forms, replayed) walks the same rounds in the same order and the results stay bitwise comparable -- plus, per wave, the number of
+// own rounds, which the one-tile persistent kernels sum BEFORE they wait for their neighbours.  The handle's own lists are untouched
+// (the adjoint, edge-function, GAT and VMH kernels read them; the latter index per-edge arrays by a row's CSR position).
 struct OwnFirst {
-  uint8_t *slots[2] = {nullptr, nullptr};   // [n_sched][kSlotWidth]            (0: by target, 1: by source)
-  int4 *sched[2] = {nullptr, nullptr};      // [n_sched] {node, row start, PADDED length, bits of c}
-  float *slot_w[2] = {nullptr, nullptr};    // [n_sched][kSlotWidth] or NULL (unweighted)
-  uint8_t *pre[2] = {nullptr, nullptr};     // [n_tiles][8] own rounds of wave w's rows 4 w .. 4 w + 3 (0: that wave keeps the handle's order)
+  uint8_t *slots = nullptr;   // [n_sched][kSlotWidth]
+  int4 *sched = nullptr;      // [n_sched] {node, row start, PADDED length, bits of c}
+  float *slot_w = nullptr;    // [n_sched][kSlotWidth] or NULL (unweighted)
+  uint8_t *pre = nullptr;     // [n_tiles][8] own rounds of wave w's rows 4 w .. 4 w + 3 (0: that wave keeps the handle's order)
 };
 int32_t own_first_tables_build(const ngpde_graph *g, OwnFirst *of, hipStream_t stream);
 void own_first_tables_free(OwnFirst *of);
@@ -260,7 +259,6 @@ struct NodePersistBwd {
   float *ubar = nullptr;
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   bool no_latch = false;       // the caller latches the fault word in its next kernel (node.hip: the slab reduction)
-  const OwnFirst *of = nullptr;   // the plan's own-first slot tables, or NULL (the handle's lists)
 };
 const unsigned *node_persistent_abort_word(const NodePersist *ps);   // the abort word of the plan's persistent launches
 bool node_persistent_interleave_env();

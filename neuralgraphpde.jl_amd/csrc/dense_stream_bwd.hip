@@ -43,7 +43,6 @@ struct DenseBwdK {
   int nwidth[kMaxNarrow], ndiv[kMaxNarrow], nfeat[kMaxNarrow];
   const float *wt, *z, *dy;
   float *partial;          // [gridDim.x][din + 1][64]
-  int dephase;
 };
 
 template <int S, int N, class F>
@@ -233,7 +232,6 @@ __global__ __launch_bounds__(kBT, 2) void dense_stream64_bwd_kernel(const DenseB
     }
   };
 
-  dephase_second_half(p.dephase);
   int tile = blockIdx.x;
   int b0 = 0, b1 = 1, bf = NMAIN;   // buffers of X_0, X_1 (NMAIN = 2) and the free one
   if (tile < p.n_tiles) {
@@ -338,7 +336,6 @@ struct DensePairBwdK {
   const float *nx[2][kMaxNarrow];
   int nwidth[2][kMaxNarrow], ndiv[2][kMaxNarrow], nfeat[2][kMaxNarrow];
   float *partial[2];   // [gridDim.x][din_s + 1][64]
-  int dephase;
 #ifdef NGPDE_STAMPS
   unsigned long long *stamps;   // diagnostic build only (tools/stamps_pair_bwd.py): [gridDim.x][16], the workgroup's 4th tile
 #endif
@@ -499,7 +496,6 @@ __global__ __launch_bounds__(kBT, 2) void dense_pair64_bwd_kernel(const DensePai
   // Per tile: the tile's dy rows and narrow values (registers, loaded a tile ago) -> LDS; then, with the next tile's loads
   // and X image in flight, the products; the loads are collected BEFORE this tile's dX stores are issued (vmcnt counts stores
   // too: collected at the top of the next tile they would cost a store latency per tile).
-  dephase_second_half(p.dephase);
   int tile = blockIdx.x, it = 0;
   if (tile < p.n_tiles) {
     fetch(tile);
@@ -594,10 +590,6 @@ __global__ __launch_bounds__(kBT, 2) void dense_pair64_bwd_kernel(const DensePai
   }
 }
 
-int dephase_cycles() {
-  static const int v = [] { const char *e = std::getenv("NGPDE_DENSE_DEPHASE"); return e ? std::atoi(e) : 0; }();
-  return v;
-}
 bool env_on(const char *name) {
   const char *e = std::getenv(name);
   return e && e[0] == '1';
@@ -632,7 +624,7 @@ int32_t launch_dense_stream_bwd(int64_t n, const SegTable &t, int din, int act, 
                                 float *const *dseg, float *dwt, float *dbias, float *slabs, int grid, hipStream_t stream) {
   DenseBwdK k{};
   k.n = n; k.n_tiles = (int)((n + kTR - 1) / kTR); k.din = din; k.act = act;
-  k.wt = wt; k.z = (act == NGPDE_ACT_IDENTITY) ? nullptr : z; k.dy = dy; k.partial = slabs; k.dephase = dephase_cycles();
+  k.wt = wt; k.z = (act == NGPDE_ACT_IDENTITY) ? nullptr : z; k.dy = dy; k.partial = slabs;
   int n_main = 0;
   for (int b = 0; b < t.n; ++b) {
     const bool grad = dseg && dseg[b] && t.row_div[b] == 1;
@@ -678,7 +670,7 @@ int32_t launch_dense_pair_bwd(int64_t n, const SegTable &ta, int dina, const flo
                               const SegTable &tb, int dinb, const float *wtb, const float *dyb, float *dwtb, float *dbb, float *dx,
                               const float *dx_add, void *workspace, int grid, hipStream_t stream) {
   DensePairBwdK k{};
-  k.n = n; k.n_tiles = (int)((n + kTR - 1) / kTR); k.x = ta.ptr[0]; k.dx = dx; k.dx_add = dx_add; k.dephase = dephase_cycles();
+  k.n = n; k.n_tiles = (int)((n + kTR - 1) / kTR); k.x = ta.ptr[0]; k.dx = dx; k.dx_add = dx_add;
 #ifdef NGPDE_STAMPS
   k.stamps = g_pair_bwd_stamps;
 #endif

@@ -838,9 +838,8 @@ int32_t launch_edge_mlp64_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hipStr
   k.stamps = g_edge64_stamps;
 #endif
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kW * kTS + 2 * (size_t)kChunk4 * kTS) * sizeof(float);
-  int per_xcd = std::max(1, std::min(lds + 4096 <= 80 * 1024 ? 64 : 32, (k.n_tiles + 7) / 8));
-  if (const char *e = std::getenv("NGPDE_EDGE64_WGS_PER_XCD")) per_xcd = std::max(1, std::min(per_xcd, atoi(e)));   // diagnostic: fewer resident workgroups   // two persistent workgroups per CU (one when the halo
-                                                                                                   // region is large), a multiple of the 8 XCDs
+  // two persistent workgroups per CU (one when the halo region is large), a multiple of the 8 XCDs
+  const int per_xcd = std::max(1, std::min(lds + 4096 <= 80 * 1024 ? 64 : 32, (k.n_tiles + 7) / 8));
   const dim3 grid(8 * per_xcd), block(kT4);
   auto launch = [&](auto kernel) -> hipError_t {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -915,8 +914,7 @@ int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hip
   k.dqpart = dq ? reinterpret_cast<float *>(reinterpret_cast<char *>(a.workspace) + edge64_slab_bytes(g)) : nullptr;
   k.dQ = dq ? a.dQ : nullptr;
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kChunk4 * kTS + 2 * (size_t)kW * kTS) * sizeof(float);
-  int grid = (lds + 4096 <= 80 * 1024) ? edge64_bwd_grid(g) : std::max(8, edge64_bwd_grid(g) / 2);
-  if (const char *e = std::getenv("NGPDE_EDGE64_WGS_PER_XCD")) grid = std::max(8, std::min(grid, 8 * atoi(e)));   // diagnostic: fewer resident workgroups
+  const int grid = (lds + 4096 <= 80 * 1024) ? edge64_bwd_grid(g) : std::max(8, edge64_bwd_grid(g) / 2);
   auto launch = [&](auto kernel) -> hipError_t {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

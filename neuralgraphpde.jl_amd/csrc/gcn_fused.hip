@@ -345,9 +345,6 @@ struct FwdK {
   CombDev comb;
   float *comb_out;
   uint8_t *save_mask;
-  int order;   // bit 0: W fetched after the aggregation, bit 1: stage terms fetched after the aggregation.  Both on by default:
-               // everything issued at kernel start competes in the memory system with the halo rows the workgroup waits for
-               // (measured at C2: layer-1 5.98 -> 5.85 us, layer-2 + stage 7.46 -> 7.06 us)
   NGPDE_STAMP_FIELD
 };
 
@@ -387,22 +384,6 @@ __global__ __launch_bounds__(kThreads, (D <= 64 ? 4 : 2)) void gcn_fused_fwd_ker
     tile_prologue<D>(h_sched, p.ell, p.ent, X4, tile, grp, q, active, sc, ecol, ecf, selfv);
   }
   __builtin_amdgcn_sched_barrier(0);
-  // W: B[k = in][j = out] = wt[in][out], stored transposed in LDS: 4 dword loads down a column
-  // (coalesced across lanes) -> one ds_write_b128
-  float4 wreg[G::NPASS];
-  auto load_w = [&]() {
-    const int j = tid % D, kg0 = tid / D;
-#pragma unroll
-    for (int ps = 0; ps < G::NPASS; ++ps) {
-      const int kg = kg0 + ps * G::KGP;
-      wreg[ps] = f4_zero();
-      if (kg < D / 4) {
-        const float *w = p.wt + (size_t)(4 * kg) * D + j;
-        wreg[ps] = make_float4(w[0], w[D], w[2 * D], w[3 * D]);
-      }
-    }
-  };
-  if (!(p.order & 1)) load_w();
   const float4 b4 = p.bias ? reinterpret_cast<const float4 *>(p.bias)[q] : f4_zero();   // uniform condition
   __builtin_amdgcn_sched_barrier(0);
   // ---- round 2: addresses from round 1 -- the tile's distinct rows, then the node-local stage terms
@@ -410,11 +391,6 @@ __global__ __launch_bounds__(kThreads, (D <= 64 ? 4 : 2)) void gcn_fused_fwd_ker
     NGPDE_USE(hr.he[0].x);
     NGPDE_SUBSTAMP(NGPDE_STAMP_PTR(p), 0);   // round-1 data arrived
     halo_round2<D, PRE>(X4, q, grp, ldsXh, hr);
-  }
-  float4 cterm[G::R][8];
-  if (HALO && active && p.has_comb && !(p.order & 2)) {
-#pragma unroll
-    for (int r = 0; r < G::R; ++r) comb_prefetch(p.comb, (size_t)max(sc[r].x, 0) * G::LPR + q, cterm[r]);
   }
   __builtin_amdgcn_sched_barrier(0);
   float4 acc[G::R];
@@ -430,12 +406,26 @@ __global__ __launch_bounds__(kThreads, (D <= 64 ? 4 : 2)) void gcn_fused_fwd_ker
     coop_add<G::LPR, G::R>(sc, grp, q, reinterpret_cast<const float4 *>(ldsZ), acc);
   }
   NGPDE_STAMP(1);
-  if (p.order & 1) load_w();
-  if (HALO && active && p.has_comb && (p.order & 2)) {
+  // W and the stage terms are fetched only after the aggregation: everything issued at kernel start competes in the memory system
+  // with the halo rows the workgroup waits for (measured at C2: layer-1 5.98 -> 5.85 us, layer-2 + stage 7.46 -> 7.06 us), and the
+  // per-row gather keeps 16 rows in flight.
+  // W: B[k = in][j = out] = wt[in][out], stored transposed in LDS: 4 dword loads down a column
+  // (coalesced across lanes) -> one ds_write_b128
+  float4 wreg[G::NPASS];
+  {
+    const int j = tid % D, kg0 = tid / D;
 #pragma unroll
-    for (int r = 0; r < G::R; ++r) comb_prefetch(p.comb, (size_t)max(sc[r].x, 0) * G::LPR + q, cterm[r]);
+    for (int ps = 0; ps < G::NPASS; ++ps) {
+      const int kg = kg0 + ps * G::KGP;
+      wreg[ps] = f4_zero();
+      if (kg < D / 4) {
+        const float *w = p.wt + (size_t)(4 * kg) * D + j;
+        wreg[ps] = make_float4(w[0], w[D], w[2 * D], w[3 * D]);
+      }
+    }
   }
-  if (!HALO && active && p.has_comb) {   // the per-row gather keeps 16 rows in flight: stage terms only afterwards
+  float4 cterm[G::R][8];
+  if (active && p.has_comb) {
 #pragma unroll
     for (int r = 0; r < G::R; ++r) comb_prefetch(p.comb, (size_t)max(sc[r].x, 0) * G::LPR + q, cterm[r]);
   }
@@ -495,7 +485,7 @@ struct BwdK {
   CombDev comb;
   float *store_t, *store_v;
   float v_scale;
-  int do_dense, tape_late, order;
+  int do_dense, tape_late;
   const float *z, *saved_agg, *wt;
   const uint8_t *mask;
   float *g_out, *slab_dw, *slab_db;
@@ -518,11 +508,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
     const float *__restrict__ h_x, const float *__restrict__ h_slot_w, int h_n_tiles, const BwdK p) {
   using G = Geo<D>;
   static_assert(!PRE || !AGG || HALO, "the pre-scaled form exists for the LDS-staged aggregation only");
-#ifdef NGPDE_PRE_NO_BWD_DMA
-  constexpr bool DMA = false;
-#else
   constexpr bool DMA = PRE && AGG && HALO;
-#endif
   constexpr int kXZ = (AGG && HALO && G::XH > kTM * G::TS) ? G::XH : kTM * G::TS;
   constexpr int kRegion = kXZ + kTM * G::TS * 2 + D * G::TS;
   __shared__ __attribute__((aligned(16))) float lds_all[(PAIR ? 2 : 1) * kRegion];
@@ -593,7 +579,6 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
       }
     }
   };
-  if (!DMA && !(p.order & 1)) load_w();
   auto load_slab = [&]() {   // consumed only after the dW MFMAs
     if (p.do_dense) {
 #pragma unroll
@@ -604,7 +589,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
       if (dbpart == 0 && half == 0) dbv = p.slab_db[(size_t)blockIdx.x * D + dbc];
     }
   };
-  if (!DMA && !(p.order & 2)) load_slab();
+  if (!DMA) load_slab();
   float4 zrow[G::R], xrow[G::R], cterm[G::R][8];
   auto load_tape = [&]() {   // saved activations of this thread's rows (node-local, HBM-resident tape)
     if (active && p.do_dense) {
@@ -626,7 +611,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
     if constexpr (DMA) {
       halo_finish<D, true, false>(hr, h_slot_w != nullptr, p.self_loops, grp, q, ldsXh, sc, t, nullptr, [&]() {
         load_mask();
-        if (!(p.order & 2)) load_slab();
+        load_slab();
         load_tape();
       });
     } else {
@@ -647,8 +632,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
   }
   NGPDE_STAMP(1);
   if (!DMA && p.tape_late) load_tape();
-  if (DMA || (p.order & 1)) load_w();
-  if (p.order & 2) load_slab();
+  load_w();   // after the aggregation, as in the forward kernel
   if (active && p.has_comb) {   // adjoint stage terms: one batch of independent node-local loads
 #pragma unroll
     for (int r = 0; r < G::R; ++r) comb_prefetch(p.comb, (size_t)max(sc[r].x, 0) * G::LPR + q, cterm[r]);
@@ -897,11 +881,8 @@ inline bool no_halo_env() {
   return v;
 }
 
-// paired workgroups for the backward kernels (D <= 64: two 60 KB regions fit the CU's LDS); NGPDE_NO_PAIR=1 for A/B runs
-inline bool fused_bwd_pairs(int d) {
-  static const bool off = [] { const char *e = std::getenv("NGPDE_NO_PAIR"); return e && e[0] == '1'; }();
-  return d <= 64 && !off;
-}
+// paired workgroups for the backward kernels (D <= 64: two 60 KB regions fit the CU's LDS)
+inline bool fused_bwd_pairs(int d) { return d <= 64; }
 
 // activations with a compiled-in fast path; everything else takes the runtime switch (ACT = -1)
 inline int act_template(int act) { return (act == NGPDE_ACT_RELU || act == NGPDE_ACT_IDENTITY) ? act : -1; }
@@ -946,18 +927,14 @@ int32_t launch_fused_fwd(const FusedFwdArgs &a, hipStream_t stream) {
   FwdK k;
   k.x = a.x; k.sched = g->by_t.sched; k.ent = g->by_t.ent; k.ell = g->by_t.ell;
   k.halo = g->by_t.halo; k.tile_info = g->by_t.tile_info; k.slots = g->by_t.slots; k.slot_w = g->by_t.slot_w;
-  if (a.of && a.of->slots[0] && g->by_t.halo_ok && !no_halo_env()) {   // a solver plan's own-first tables (LDS-staged aggregation only:
-    k.slots = a.of->slots[0]; k.sched = a.of->sched[0];                 // the same rows in another order, padded lengths in the schedule)
-    if (k.slot_w) k.slot_w = a.of->slot_w[0];
+  if (a.of && a.of->slots && g->by_t.halo_ok && !no_halo_env()) {   // a solver plan's own-first tables (LDS-staged aggregation only:
+    k.slots = a.of->slots; k.sched = a.of->sched;                   // the same rows in another order, padded lengths in the schedule)
+    if (k.slot_w) k.slot_w = a.of->slot_w;
   }
   k.self_loops = g->self_loops; k.n_tiles = fused_num_blocks(g->n_nodes); k.act = a.act;
   k.wt = a.wt; k.bias = a.bias; k.y = a.y; k.save_agg = a.save_agg; k.save_z = a.save_z;
   k.has_comb = a.has_comb ? 1 : 0; k.comb = to_dev(a.comb); k.comb_out = a.comb_out;
   k.save_mask = a.save_mask;
-  {   // default 3; NGPDE_FWD_ORDER=0..3 for A/B runs of the load placement
-    static const int ord = [] { const char *e = std::getenv("NGPDE_FWD_ORDER"); return e ? atoi(e) : 3; }();
-    k.order = ord;
-  }
   NGPDE_STAMP_SET(k, k.n_tiles)
   const bool use_halo = g->by_t.halo_ok && !no_halo_env();
   NGPDE_REQUIRE(!a.pre || fused_prescaled_supported(g, a.d), NGPDE_ERR_UNSUPPORTED,
@@ -1002,10 +979,6 @@ int32_t launch_fused_bwd(const FusedBwdArgs &a, hipStream_t stream) {
   BwdK k;
   k.g_in = a.g_in; k.sched = g->by_s.sched; k.ent = g->by_s.ent; k.ell = g->by_s.ell;
   k.halo = g->by_s.halo; k.tile_info = g->by_s.tile_info; k.slots = g->by_s.slots; k.slot_w = g->by_s.slot_w;
-  if (a.of && a.of->slots[1] && g->by_s.halo_ok && !no_halo_env()) {
-    k.slots = a.of->slots[1]; k.sched = a.of->sched[1];
-    if (k.slot_w) k.slot_w = a.of->slot_w[1];
-  }
   k.self_loops = g->self_loops; k.n_tiles = fused_num_blocks(g->n_nodes); k.act = a.act;
   k.has_comb = a.has_comb ? 1 : 0; k.comb = to_dev(a.comb);
   k.store_t = a.store_t; k.store_v = a.store_v; k.v_scale = a.v_scale;
@@ -1013,24 +986,18 @@ int32_t launch_fused_bwd(const FusedBwdArgs &a, hipStream_t stream) {
   k.mask = a.mask;
   NGPDE_REQUIRE(!a.mask || a.act == NGPDE_ACT_RELU, NGPDE_ERR_INVALID_ARGUMENT, "sign-bit masks carry relu' only");
   k.tape_late = a.has_comb ? 0 : 1;
-  {
-    static const int ord = [] { const char *e = std::getenv("NGPDE_BWD_ORDER"); return e ? atoi(e) : 1; }();
-    k.order = ord;
-    if (ord & 4) k.tape_late = 1;
-  }
   k.g_out = a.g_out; k.slab_dw = a.slab_dw; k.slab_db = a.slab_db;
   NGPDE_STAMP_SET(k, k.n_tiles)
   const bool use_halo = g->by_s.halo_ok && !no_halo_env();
   NGPDE_REQUIRE(!a.pre || fused_prescaled_supported(g, a.d), NGPDE_ERR_UNSUPPORTED,
                 "the pre-scaled form needs self loops and tiles that fit the LDS halo in both directions");
-  const bool pair = fused_bwd_pairs(a.d);
+  const bool pair = fused_bwd_pairs(a.d);   // (D <= 64: the launches below instantiate the paired kernel only)
   const dim3 grid(pair ? (k.n_tiles + 1) / 2 : k.n_tiles), block(pair ? 2 * kThreads : kThreads);
 #define NGPDE_BWD_LAUNCH3(DD, AG, AA, HH, PP, SS)                                                                 \
   if (a.ev_start) hipExtLaunchKernelGGL((gcn_fused_bwd_kernel<DD, AG, AA, HH, PP, SS>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, \
                                         k.halo, k.slots, k.sched, k.g_in, k.slot_w, k.n_tiles, k);                    \
   else hipLaunchKernelGGL((gcn_fused_bwd_kernel<DD, AG, AA, HH, PP, SS>), grid, block, 0, stream, k.halo, k.slots, k.sched, k.g_in, k.slot_w, k.n_tiles, k);
-#define NGPDE_BWD_LAUNCH2(DD, AG, AA, HH, SS)                                                                     \
-  if (DD <= 64 && pair) { NGPDE_BWD_LAUNCH3(DD, AG, AA, HH, (DD <= 64), SS) } else { NGPDE_BWD_LAUNCH3(DD, AG, AA, HH, false, SS) }
+#define NGPDE_BWD_LAUNCH2(DD, AG, AA, HH, SS) NGPDE_BWD_LAUNCH3(DD, AG, AA, HH, (DD <= 64), SS)
 #define NGPDE_BWD_LAUNCH(DD, AG, AA)                                                                              \
   if (Geo<DD>::HALO && a.pre) { NGPDE_BWD_LAUNCH2(DD, AG, AA, (AG && Geo<DD>::HALO), (Geo<DD>::HALO)) }            \
   else if (AG && Geo<DD>::HALO && use_halo) { NGPDE_BWD_LAUNCH2(DD, AG, AA, (AG && Geo<DD>::HALO), false) }        \

@@ -12,7 +12,6 @@
 //              dt*sum_j a_ji U-bar_j (or the lambda update at the step boundary) and runs layer 2's
 //              dense backward for that next stage.
 #include <cstdlib>
-#include <cstring>
 #include <new>
 #include <vector>
 
@@ -200,7 +199,7 @@ struct ngpde_node {
   // same floor); padded columns of u stay decoupled from the real ones because the padded rows AND columns of W are zero
   int du = 0;
   float dt = 0.f;
-  bool with_bwd = false, needs_z = false, eager = false;
+  bool with_bwd = false, needs_z = false;
   Tableau tb;
   int64_t n = 0;
   size_t row_elems = 0;  // n * d
@@ -233,8 +232,9 @@ struct ngpde_node {
 
   // Persistent form (node_persistent.hip): the whole forward solve / the whole adjoint as ONE launch each, tiles
   // synchronised by per-tile phase flags.  Chosen when the graph is one co-resident wave of tiles (<= 2 per CU), d = 64,
-  // relu (adjoint), unweighted, pre-scaled form available; NGPDE_NO_PERSISTENT=1 or NGPDE_PERSISTENT=fwd|bwd restrict it.
-  bool persist_fwd = false, persist_bwd = false;
+  // relu (adjoint), unweighted, pre-scaled form available; NGPDE_NO_PERSISTENT=1 turns it off.  A plan is persistent in every
+  // direction it has, or in none.
+  bool persistent = false;
   bool hub = false;          // ... in the hub geometry (graphs whose tiles do not fit the handle's halo lists)
   // persistent adjoint of an activation other than relu: the tape holds the aggregated inputs (first half) and the pre-activations
   // (second half, `ztape`), two rows per stage evaluation each, indexed like the relu plan's tape
@@ -358,7 +358,6 @@ int32_t enqueue_forward(ngpde_node *p, hipStream_t stream, int *launches, Prof *
 void fill_dense(const ngpde_node *p, FusedBwdArgs &a, int layer, int step, int stage) {
   a.do_dense = true;
   a.pre = p->pre;
-  a.of = p->has_of ? &p->of : nullptr;
   if (p->mask_mode) a.mask = p->mask_slot(step, stage, layer);
   if (layer == 2) {
     a.z = p->needs_z ? p->slot(step, stage, 5) : p->slot(step, stage, 3);
@@ -428,7 +427,6 @@ int32_t enqueue_backward(ngpde_node *p, hipStream_t stream, int *launches, Prof 
         } else {
           e.do_dense = false;
           e.pre = p->pre;
-          e.of = p->has_of ? &p->of : nullptr;
         }
       }
       if (prof && e.do_dense) prof->want(3, &e.ev_start, &e.ev_stop);
@@ -476,7 +474,6 @@ int32_t enqueue_backward_persistent(ngpde_node *p, hipStream_t stream, hipEvent_
   a.tape = p->tape; a.masks = p->masks; a.row_elems = p->row_elems; a.mask_bytes = p->mask_bytes; a.ztape = p->ztape;
   a.slab_dw1 = p->slab_dw1; a.slab_db1 = p->slab_db1; a.slab_dw2 = p->slab_dw2; a.slab_db2 = p->slab_db2;
   a.interleave = p->interleave; a.pair = p->pair; a.ubar = p->pubar; a.k_tiles = p->ktiles;
-  a.of = p->has_of ? &p->of : nullptr;
   a.ev_start = ev0; a.ev_stop = ev1;
   int32_t st;
   if ((st = launch_node_bwd_persistent(a, stream))) return st;
@@ -608,9 +605,7 @@ static int32_t node_create(const ngpde_graph_t *g, int32_t members, int32_t d, i
   const int S = p->tb.S;
   int32_t st = NGPDE_OK;
   if (want_persist) {
-    const char *only = std::getenv("NGPDE_PERSISTENT");
-    p->persist_fwd = !(only && std::strcmp(only, "bwd") == 0);
-    p->persist_bwd = p->with_bwd && !(only && std::strcmp(only, "fwd") == 0);
+    p->persistent = true;
     // stage-indexed coefficient tables (device memory): forward cf[i][j], adjoint dtb[j], cu[i][j]
     float coef[90] = {0};   // forward: cf[i][j] (j < i) at i * 6 + j, self weights at 36 + i; adjoint: dt b at 42 + j,
                             // cu[i][j] (j > i >= 1) at 48 + i * 6 + j, self weights at 84 + i  (node_persistent.hip)
@@ -628,22 +623,15 @@ static int32_t node_create(const ngpde_graph_t *g, int32_t members, int32_t d, i
     st = node_persistent_setup(g, coef, &p->persist, p->pair, hub);
     if (st == NGPDE_ERR_UNSUPPORTED) {   // a wait list too long for one polling wave (or neighbouring tile pairs): the replayed plan
       st = NGPDE_OK;
-      p->persist_fwd = p->persist_bwd = false;
+      p->persistent = false;
     }
-    if (p->pair && !(p->persist_fwd && (p->persist_bwd || !p->with_bwd))) {   // tile pairs: both directions or none
-      p->persist_fwd = p->persist_bwd = false;
-    }
-    if (!p->persist_fwd) p->pair = false;
-    if (p->ktiles > 0) {   // tile rounds: both directions or none; the grid is ceil(tiles / K)
-      if (p->persist_fwd && (p->persist_bwd || !p->with_bwd)) p->persist.pair_wgs = (p->persist.n_tiles + p->ktiles - 1) / p->ktiles;
-      else { p->persist_fwd = p->persist_bwd = false; p->ktiles = 0; }
-    }
+    if (p->persistent && p->ktiles > 0) p->persist.pair_wgs = (p->persist.n_tiles + p->ktiles - 1) / p->ktiles;   // tile rounds: the grid is ceil(tiles / K)
   }
-  if (!p->persist_fwd) p->ktiles = 0;
-  // activations other than relu: the persistent pair needs BOTH directions persistent (the tapes' layouts differ from the replayed plan's)
-  if (p->with_bwd && !p->mask_mode && !(p->persist_fwd && p->persist_bwd)) p->persist_fwd = p->persist_bwd = false;
-  if (hub && !(p->persist_fwd && (p->persist_bwd || !p->with_bwd))) {   // hub geometry refused (a cap, NGPDE_PERSISTENT=fwd / bwd): the unscaled replayed plan
-    p->persist_fwd = p->persist_bwd = false;
+  if (!p->persistent) {
+    p->pair = false;
+    p->ktiles = 0;
+  }
+  if (hub && !p->persistent) {   // hub geometry refused (a cap): the unscaled replayed plan
     p->pre = false;
     hub = false;
     node_persistent_free(&p->persist);
@@ -665,11 +653,10 @@ static int32_t node_create(const ngpde_graph_t *g, int32_t members, int32_t d, i
       p->has_of = st == NGPDE_OK;
     }
   }
-  p->ztape_mode = p->with_bwd && !p->mask_mode && p->persist_fwd && p->persist_bwd;
+  // activations other than relu: the persistent adjoint reads the pre-activations from a tape of its own layout
+  p->ztape_mode = p->with_bwd && !p->mask_mode && p->persistent;
   p->slots = p->mask_mode ? 2 : (p->ztape_mode ? 4 : (p->with_bwd ? (p->needs_z ? 6 : 4) : 4));
   p->mask_bytes = p->mask_mode ? fused_mask_bytes(p->n, d) : 0;
-  const char *eager = std::getenv("NGPDE_NODE_EAGER");
-  p->eager = eager && eager[0] == '1';
   p->interleave = members > 1 && !hub && node_persistent_interleave_env();   // (hub geometry: the members one after the other)
   const size_t xslots = p->interleave ? 2 : 1;   // [N][d] arrays per exchanged buffer
   auto A = [&](float **ptr, size_t elems) {
@@ -713,23 +700,22 @@ static int32_t node_create(const ngpde_graph_t *g, int32_t members, int32_t d, i
     }
     A(&p->dw1, dd); A(&p->db1, d); A(&p->dw2, dd); A(&p->db2, d);
   }
-  if (st == NGPDE_OK && p->persist_fwd) A(&p->pbuf, xslots * p->row_elems);
+  if (st == NGPDE_OK && p->persistent) A(&p->pbuf, xslots * p->row_elems);
   if (st == NGPDE_OK && p->ktiles) A(&p->kstate, 7 * p->row_elems);
   if (st == NGPDE_OK && p->ztape_mode) p->ztape = p->tape + (size_t)n_steps * S * 2 * p->all_elems;
-  if (st == NGPDE_OK && members > 1 && !(p->persist_fwd && (p->persist_bwd || !p->with_bwd)))
+  if (st == NGPDE_OK && members > 1 && !p->persistent)
     st = fail(NGPDE_ERR_UNSUPPORTED, "ngpde_node_gcn2_create_batch: the member-by-member solve exists for the persistent plan only "
                                      "(d = 64, relu, unweighted, at most two 32-row tiles per CU); batch the graphs into one handle instead");
-  if (st == NGPDE_OK && !p->eager && !(p->persist_fwd && (p->persist_bwd || !p->with_bwd))) {
+  if (st == NGPDE_OK && !p->persistent) {
     hipError_t e = hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking);
     if (e != hipSuccess) st = fail(NGPDE_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-    if (st == NGPDE_OK && !p->persist_fwd) st = capture(p, false);
-    if (st == NGPDE_OK && p->with_bwd && !p->persist_bwd) st = capture(p, true);
-  } else if (st == NGPDE_OK) {
-    p->fwd_launches = 2 * S * n_steps;
-    p->bwd_launches = p->with_bwd ? 1 + 2 * S * n_steps + 4 : 0;
+    if (st == NGPDE_OK) st = capture(p, false);
+    if (st == NGPDE_OK && p->with_bwd) st = capture(p, true);
   }
-  if (p->persist_fwd) p->fwd_launches = 2;                    // flag reset, the solve (the fault latch rides on the exit scaling)
-  if (p->persist_bwd) p->bwd_launches = 3;                    // flag reset, the adjoint, ONE reduction of the four slab sets (it latches too)
+  if (p->persistent) {
+    p->fwd_launches = 2;                          // flag reset, the solve (the fault latch rides on the exit scaling)
+    p->bwd_launches = p->with_bwd ? 3 : 0;        // flag reset, the adjoint, ONE reduction of the four slab sets (it latches too)
+  }
   if (st != NGPDE_OK) {
     std::string keep = last_error();
     ngpde_node_destroy(p);
@@ -749,7 +735,7 @@ int32_t ngpde_node_gcn2_create_batch(const ngpde_graph_t *g, int32_t members, in
       (node_persistent_mode(g, 64, act, with_backward != 0) != 0 || node_persistent_hub_possible(g, 64))) {
     ngpde_node_t *w = nullptr;
     if (node_create(g, members, 64, d, act, tableau, n_steps, dt, with_backward, &w) == NGPDE_OK) {
-      if (w->persist_fwd && (w->persist_bwd || !w->with_bwd)) {
+      if (w->persistent) {
         *out = w;
         return NGPDE_OK;
       }
@@ -772,8 +758,8 @@ int32_t ngpde_node_launch_count(const ngpde_node_t *p, int32_t *forward, int32_t
 int32_t ngpde_node_flags(const ngpde_node_t *p, int32_t *flags) {
   NGPDE_RANGE();
   NGPDE_REQUIRE(p != nullptr && flags != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_node_flags: NULL argument");
-  *flags = (p->pre ? NGPDE_NODE_PRESCALED : 0) | (p->mask_mode ? NGPDE_NODE_SIGN_MASKS : 0) | (p->eager ? NGPDE_NODE_EAGER : 0) |
-           (p->persist_fwd ? NGPDE_NODE_PERSISTENT_FWD : 0) | (p->persist_bwd ? NGPDE_NODE_PERSISTENT_BWD : 0) |
+  *flags = (p->pre ? NGPDE_NODE_PRESCALED : 0) | (p->mask_mode ? NGPDE_NODE_SIGN_MASKS : 0) |
+           (p->persistent ? NGPDE_NODE_PERSISTENT_FWD : 0) | (p->persistent && p->with_bwd ? NGPDE_NODE_PERSISTENT_BWD : 0) |
            (p->pair ? NGPDE_NODE_TILE_PAIRS : 0) | (p->ktiles ? NGPDE_NODE_TILE_ROUNDS : 0) | (p->du != p->d ? NGPDE_NODE_WIDENED : 0) |
            (p->hub ? NGPDE_NODE_HUB_GEOMETRY : 0) | (p->has_of ? NGPDE_NODE_OWN_FIRST : 0);
   return NGPDE_OK;
@@ -835,12 +821,9 @@ int32_t ngpde_node_gcn2_forward(ngpde_node_t *p, const float *u0, const float *w
     int32_t st = launch_pack_params(w1, b1, w2, b2, p->du, p->d, p->w1, p->b1, p->w2, p->b2, stream);
     if (st) return st;
   }
-  const bool fold_latch = p->persist_fwd && p->pre;   // (the exit scaling latches the launch's fault word)
-  if (p->persist_fwd) {
+  const bool fold_latch = p->persistent && p->pre;   // (the exit scaling latches the launch's fault word)
+  if (p->persistent) {
     int32_t st = enqueue_forward_persistent(p, stream, nullptr, nullptr, fold_latch);
-    if (st) return st;
-  } else if (p->eager) {
-    int32_t st = enqueue_forward(p, stream, nullptr);
     if (st) return st;
   } else {
     NGPDE_HIP_CHECK(hipGraphLaunch(p->fwd_exec, stream));
@@ -895,12 +878,9 @@ int32_t ngpde_node_gcn2_backward(ngpde_node_t *p, const float *duT, float *du0, 
   } else {
     NGPDE_HIP_CHECK(hipMemcpyAsync(p->lam, duT, p->all_elems * sizeof(float), hipMemcpyDeviceToDevice, stream));
   }
-  if (p->persist_bwd) {   // (its one reduction launch writes the four gradients where the caller wants them)
+  if (p->persistent) {   // (its one reduction launch writes the four gradients where the caller wants them)
     float *const outs[4] = {dw1, db1, dw2, db2};
     int32_t st = enqueue_backward_persistent(p, stream, nullptr, nullptr, outs);
-    if (st) return st;
-  } else if (p->eager) {
-    int32_t st = enqueue_backward(p, stream, nullptr);
     if (st) return st;
   } else {
     NGPDE_HIP_CHECK(hipGraphLaunch(p->bwd_exec, stream));
@@ -912,7 +892,7 @@ int32_t ngpde_node_gcn2_backward(ngpde_node_t *p, const float *duT, float *du0, 
     NGPDE_HIP_CHECK(hipMemcpyAsync(du0, p->lam, p->all_elems * sizeof(float), hipMemcpyDeviceToDevice, stream));
   }
   p->backward_pending = false;
-  if (p->persist_bwd) return NGPDE_OK;
+  if (p->persistent) return NGPDE_OK;
   if (p->du != p->d) {
     int32_t st;
     if (dw1 && (st = copy_block(dw1, p->du, p->dw1, p->d, p->du, p->du, stream))) return st;
@@ -942,7 +922,7 @@ int32_t ngpde_node_profile(ngpde_node_t *p, int32_t stride, float *out_us, int32
     NGPDE_HIP_CHECK(hipMemcpyAsync(p->u, p->u0keep, p->all_elems * sizeof(float), hipMemcpyDeviceToDevice, stream));
   }
   hipEvent_t pe[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (p->persist_fwd) {
+  if (p->persistent) {
     prof.want(0, &pe[0], &pe[1]);
     if ((st = enqueue_forward_persistent(p, stream, pe[0], pe[1]))) return st;
   } else if ((st = enqueue_forward(p, stream, nullptr, &prof))) return st;
@@ -951,7 +931,7 @@ int32_t ngpde_node_profile(ngpde_node_t *p, int32_t stride, float *out_us, int32
     std::vector<float> ones(p->all_elems, 1.0f);
     NGPDE_HIP_CHECK(hipMemcpyAsync(p->lam, ones.data(), p->all_elems * sizeof(float), hipMemcpyHostToDevice, stream));
     NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
-    if (p->persist_bwd) {
+    if (p->persistent) {
       prof.counter = 0;
       prof.want(2, &pe[2], &pe[3]);
       if ((st = enqueue_backward_persistent(p, stream, pe[2], pe[3]))) return st;

@@ -321,16 +321,11 @@ __device__ __forceinline__ float4 tile_aggregate_weighted(const TileCtx &c, cons
   }
   return f4_add(a, Xh4[c.grp * PG::LPR + c.q]);
 }
-template <bool WGT>
-__device__ __forceinline__ float4 tile_aggregate_rounds(const TileCtx &c, const float *ldsXh) {
-  if constexpr (WGT) return tile_aggregate_weighted(c, ldsXh);
-  else return tile_aggregate_lean(c, ldsXh);
-}
 
 
 // ---- own-first aggregation (round 6; the plan's OwnFirst tables, common.h) ------------------------------------------------------------
-// The slot bytes a plan's kernels read list every row's own-tile slots first (padded to the wave's number of own rounds), then the
-// foreign ones; TileMeta::of_pre names the own rounds per wave.  The one-tile kernels sum those rounds BEFORE they wait for their
+// The slot bytes a plan's forward kernels read list every row's own-tile slots first (padded to the wave's number of own rounds), then the
+// foreign ones; TileMeta::of_pre names the own rounds per wave.  The one-tile forward kernels sum those rounds BEFORE they wait for their
 // neighbours' flags -- a tile's own rows are in LDS since its last epilogue -- and only the foreign rounds behind the gather.  Measured
 // with an in-kernel re-ordering of the same kind (profiles/r06_a_own_first.txt): forward launch 2.301 -> 2.234 ms.
 // rounds [r0, r1) of the row's slot words from LDS, same association as tile_aggregate
@@ -768,10 +763,11 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
 // all K tiles).  No gather-ahead pipeline is needed: by the time a tile's turn comes again the workgroup has spent K - 1 turns on
 // its other tiles, and the neighbours' rows and flags of the previous phase have long arrived (what the GAT solver's batch kernels
 // showed, gat_fused.hip).  A workgroup's own tiles may even be neighbours: turn s of phase ph needs the others' phase ph - 1 only.
-// Arithmetic per tile is node_fwd_persistent_kernel's, operation for operation.
-template <int ACT, bool TAPE, bool WGT = false>
+// Arithmetic per tile is node_fwd_persistent_kernel's, operation for operation.  Weighted graphs only: each tile's slot weights
+// take the LDS of the pipelined kernel below, which runs the unweighted ones.
+template <int ACT, bool TAPE>
 __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentK_kernel(const PFwdK p) {
-  constexpr int kMS = meta_stride<WGT>(), kMT = meta_tiles<WGT>();
+  constexpr int kMS = meta_stride<true>(), kMT = meta_tiles<true>();
   __shared__ __attribute__((aligned(16))) float lds[kXhF + 2 * kTileF + kWF + 2 * PD + kMT * kMS + 48 + 4];
   static_assert(sizeof(lds) <= 80 * 1024 - 64, "two workgroups per CU");
   float *ldsXh = lds, *ldsT = lds + kXhF, *ldsZ = ldsT + kTileF, *ldsW = ldsZ + kTileF, *ldsB = ldsW + kWF;
@@ -788,7 +784,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentK_kernel(const
   const int W = p.pair_wgs, K = min(p.k_tiles, kMT);
   const int t0 = xcd_tile(blockIdx.x, W);
   const unsigned rowb = (unsigned)(p.row_elems * sizeof(float));
-  for (int s = 0; s < K && t0 + s * W < p.m.n_tiles; ++s) tile_tables_to_lds<WGT>(p.m, t0 + s * W, ldsMeta + s * kMS);
+  for (int s = 0; s < K && t0 + s * W < p.m.n_tiles; ++s) tile_tables_to_lds<true>(p.m, t0 + s * W, ldsMeta + s * kMS);
   __syncthreads();
   const float4 bias1 = reinterpret_cast<const float4 *>(ldsB)[q], bias2 = reinterpret_cast<const float4 *>(ldsB + PD)[q];
   bool ok = true;
@@ -806,7 +802,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentK_kernel(const
           const int tile = t0 + s * W;
           if (tile >= p.m.n_tiles) break;   // uniform
           TileCtx c;
-          tile_ctx_from_lds<WGT>(c, tile, ldsMeta + s * kMS);
+          tile_ctx_from_lds<true>(c, tile, ldsMeta + s * kMS);
           const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
           if (!tile_wait(p.m, c, ph, s_ok)) { ok = false; break; }
           halo_fill_all(c, X, ldsXh);
@@ -822,7 +818,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentK_kernel(const
           }
           wait_vmcnt0();
           __syncthreads();   // halo rows landed (and the phase's W is in LDS)
-          float4 acc = f4_scale(c.ci, tile_aggregate_rounds<WGT>(c, ldsXh));
+          float4 acc = f4_scale(c.ci, tile_aggregate_weighted(c, ldsXh));
           *reinterpret_cast<float4 *>(&ldsT[c.grp * PG::TS + 4 * c.q]) = acc;
           if (TAPE && c.valid) st4_stream_g(p.tape + ev * p.row_elems, own, acc);
           __syncthreads();
@@ -879,7 +875,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentK_kernel(const
 //   T2  if they were all there: the next turn's rows go out by LDS-DMA and travel under the product and the epilogue; product; barrier
 //   T5  bias, activation, stage combination, row / state stores (not drained); then the next turn's state rows are fetched into the
 //       registers this turn has just finished with
-// A next turn whose flags were not there takes the blocking path at its T0.  Arithmetic per tile is the tile-round kernel's.
+// A next turn whose flags were not there takes the blocking path at its T0.  Arithmetic per tile is node_fwd_persistent_kernel's.
 template <int ACT, bool TAPE>
 __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(const PFwdK p) {
   constexpr int kMS = meta_stride<false>(), kMT = meta_tiles<false>();
@@ -1314,10 +1310,6 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
   float db1 = 0.f, db2 = 0.f;
   const int dbc = c.tid / PG::DBP, dbpart = c.tid % PG::DBP;
   const int S = p.S;
-  int of_pre = 0;   // own rounds of this wave's rows (the plan's own-first tables): summed before the wait
-  if constexpr (!HUB && !WGT) {
-    if (p.m.of_pre) of_pre = __builtin_amdgcn_readfirstlane((int)p.m.of_pre[(size_t)c.tile * 8 + c.wave_u]);
-  }
   __syncthreads();
 
   // the dense half of a phase: dL/dy = c .* K-bar, relu' by the sign bits, G = dZ W^T -> c .* G stored for the next gather,
@@ -1448,13 +1440,11 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
         } else {
           unsigned sw[8];
           tile_slot_words(c, sw);
-          float4 a = tile_aggregate_rounds_range(c, sw, ldsXh, f4_zero(), 0, of_pre);   // own rows (in LDS since the last publish): under the wait
           if (!tile_wait_primed(p.m, c, ph, s_ok, p.m.flags, f_next)) { ok = false; break; }
           NGPDE_PST(p.m, ph, 1);
           tile_gather_foreign(c, p.g2, ldsXh);
           NGPDE_PST(p.m, ph, 2);
-          a = tile_aggregate_rounds_range(c, sw, ldsXh, a, of_pre, (c.wmax + 3) >> 2);
-          t = f4_add(a, Xh4[c.grp * PG::LPR + c.q]);
+          t = f4_add(tile_aggregate_rounds_range(c, sw, ldsXh, f4_zero(), 0, (c.wmax + 3) >> 2), Xh4[c.grp * PG::LPR + c.q]);
         }
         dense(ph, ldsW1, dw1, db1, t, mk, xrow, p.g1, !last_next, ev_next);
       }
@@ -1484,13 +1474,11 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
         } else {
           unsigned sw[8];
           tile_slot_words(c, sw);
-          float4 a = tile_aggregate_rounds_range(c, sw, ldsXh, f4_zero(), 0, of_pre);   // own rows (in LDS since the last publish): under the wait
           if (!tile_wait_primed(p.m, c, ph, s_ok, p.m.flags, f_next)) { ok = false; break; }
           NGPDE_PST(p.m, ph, 1);
           tile_gather_foreign(c, p.g1, ldsXh);
           NGPDE_PST(p.m, ph, 2);
-          a = tile_aggregate_rounds_range(c, sw, ldsXh, a, of_pre, (c.wmax + 3) >> 2);
-          t = f4_add(a, Xh4[c.grp * PG::LPR + c.q]);
+          t = f4_add(tile_aggregate_rounds_range(c, sw, ldsXh, f4_zero(), 0, (c.wmax + 3) >> 2), Xh4[c.grp * PG::LPR + c.q]);
         }
         float4 kbar;
         if (i >= 1) {
@@ -1853,13 +1841,14 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
 // ---------------------------------------------------------------------------------------------------------------------
 // adjoint, K tiles per workgroup taking turns (see node_fwd_persistentK_kernel): lambda and the stage adjoints are own rows of
 // p.lam / p.ubar (zero at launch where the one-tile kernel starts from zero registers), one layer's W in LDS at a time, the
-// parameter-gradient accumulators in registers over all tiles and phases (one slab per WORKGROUP at the end).
+// parameter-gradient accumulators in registers over all tiles and phases (one slab per WORKGROUP at the end).  Weighted graphs
+// only, as in the forward (unweighted: node_bwd_persistentKP_kernel).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int ACT, bool WGT = false>
+template <int ACT>
 __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const PBwdK p) {
   constexpr bool RELU = (ACT == NGPDE_ACT_RELU);
   using Aux = typename std::conditional<RELU, unsigned, float4>::type;
-  constexpr int kMS = meta_stride<WGT>(), kMT = meta_tiles<WGT>();
+  constexpr int kMS = meta_stride<true>(), kMT = meta_tiles<true>();
   __shared__ __attribute__((aligned(16))) float lds[kXhF + 2 * kTileF + kWF + kMT * kMS + 48 + 4];
   static_assert(sizeof(lds) <= 80 * 1024 - 64, "two workgroups per CU");
   float *ldsXh = lds, *ldsG = lds, *ldsDZ = lds + kXhF, *ldsX = ldsDZ + kTileF, *ldsW = ldsX + kTileF;
@@ -1880,7 +1869,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
   const int S = p.S, W = p.pair_wgs, K = min(p.k_tiles, kMT);
   const int t0 = xcd_tile(blockIdx.x, W);
   const unsigned rowb = (unsigned)(p.row_elems * sizeof(float));
-  for (int s = 0; s < K && t0 + s * W < p.m.n_tiles; ++s) tile_tables_to_lds<WGT>(p.m, t0 + s * W, ldsMeta + s * kMS);
+  for (int s = 0; s < K && t0 + s * W < p.m.n_tiles; ++s) tile_tables_to_lds<true>(p.m, t0 + s * W, ldsMeta + s * kMS);
   __syncthreads();
 
   // the dense half of a turn (node_bwd_persistent_kernel's, with the tile context as an argument)
@@ -1960,7 +1949,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
       const int tile = t0 + s * W;
       if (tile >= p.m.n_tiles) break;
       TileCtx c;
-      tile_ctx_from_lds<WGT>(c, tile, ldsMeta + s * kMS);
+      tile_ctx_from_lds<true>(c, tile, ldsMeta + s * kMS);
       const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
       __syncthreads();   // (the phase's W is in LDS; the previous turn's products are done with the operand tiles)
       const float4 lam = f4_sel(c.valid, ld4_g(p.lam, own), f4_zero());
@@ -1982,7 +1971,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
           const int tile = t0 + s * W;
           if (tile >= p.m.n_tiles) break;
           TileCtx c;
-          tile_ctx_from_lds<WGT>(c, tile, ldsMeta + s * kMS);
+          tile_ctx_from_lds<true>(c, tile, ldsMeta + s * kMS);
           const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
           const Aux mk = mk_n;
           const float4 xrow = xrow_n;
@@ -1990,7 +1979,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
           halo_fill_all(c, p.g2, ldsXh);
           wait_vmcnt0();
           __syncthreads();
-          const float4 t = tile_aggregate_rounds<WGT>(c, ldsXh);
+          const float4 t = tile_aggregate_weighted(c, ldsXh);
           __syncthreads();   // every thread has its sum: the region becomes the product's result tile
           // next: the workgroup's next tile, or layer 2 of the stage evaluated before this one (the very last phase asks for nothing)
           const bool more = s + 1 < Kv;
@@ -2009,7 +1998,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
           const int tile = t0 + s * W;
           if (tile >= p.m.n_tiles) break;
           TileCtx c;
-          tile_ctx_from_lds<WGT>(c, tile, ldsMeta + s * kMS);
+          tile_ctx_from_lds<true>(c, tile, ldsMeta + s * kMS);
           const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
           const Aux mk = mk_n;        // (the last phase runs no dense half: nothing was asked for)
           const float4 xrow = xrow_n;
@@ -2023,7 +2012,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
                        lb5 = (i < 5 && S > 5) ? ld4_g(p.ubar, own + 4 * rowb) : f4_zero();
           wait_vmcnt0();
           __syncthreads();
-          const float4 t = tile_aggregate_rounds<WGT>(c, ldsXh);
+          const float4 t = tile_aggregate_weighted(c, ldsXh);
           __syncthreads();
           const float4 ub1 = i == 1 ? t : lb1, ub2 = i == 2 ? t : lb2, ub3 = i == 3 ? t : lb3, ub4 = i == 4 ? t : lb4,
                        ub5 = i == 5 ? t : lb5;   // U-bar_i is t itself
@@ -2093,7 +2082,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
 //       region is the product's result tile); row stores (not drained)
 // A next turn whose flags were not there (the first tile of the next phase, mostly: its neighbours are in THIS phase) takes the
 // blocking path at its T0, which publishes what is pending first -- so a workgroup never spins in front of its own publish.
-// Arithmetic per tile is the tile-round kernel's, operation for operation: du0 bitwise equal, NGPDE_NO_TILE_PIPE=1 selects it.
+// Arithmetic per tile is node_bwd_persistent_kernel's, operation for operation: du0 bitwise equal to the replayed plan's.
 template <int ACT>
 __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(const PBwdK p) {
   constexpr bool RELU = (ACT == NGPDE_ACT_RELU);
@@ -2459,16 +2448,13 @@ int node_persistent_rounds(const ngpde_graph *g) {   // K of mode 3: tiles per w
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, kThreads, 0) != hipSuccess) o = 0;
     occ = std::min(occ, o);
   };
-  take(node_fwd_persistentK_kernel<NGPDE_ACT_RELU, true>); take(node_fwd_persistentK_kernel<NGPDE_ACT_RELU, false>);
-  take(node_fwd_persistentK_kernel<-1, true>); take(node_fwd_persistentK_kernel<-1, false>);
   take(node_fwd_persistentKP_kernel<NGPDE_ACT_RELU, true>); take(node_fwd_persistentKP_kernel<NGPDE_ACT_RELU, false>);
   take(node_fwd_persistentKP_kernel<-1, true>); take(node_fwd_persistentKP_kernel<-1, false>);
-  take(node_bwd_persistentK_kernel<NGPDE_ACT_RELU>); take(node_bwd_persistentK_kernel<-1>);
   take(node_bwd_persistentKP_kernel<NGPDE_ACT_RELU>); take(node_bwd_persistentKP_kernel<-1>);
-  if (g->by_t.slot_w) {
-    take(node_fwd_persistentK_kernel<NGPDE_ACT_RELU, true, true>); take(node_fwd_persistentK_kernel<NGPDE_ACT_RELU, false, true>);
-    take(node_fwd_persistentK_kernel<-1, true, true>); take(node_fwd_persistentK_kernel<-1, false, true>);
-    take(node_bwd_persistentK_kernel<NGPDE_ACT_RELU, true>); take(node_bwd_persistentK_kernel<-1, true>);
+  if (g->by_t.slot_w) {   // (weighted graphs: the K kernels)
+    take(node_fwd_persistentK_kernel<NGPDE_ACT_RELU, true>); take(node_fwd_persistentK_kernel<NGPDE_ACT_RELU, false>);
+    take(node_fwd_persistentK_kernel<-1, true>); take(node_fwd_persistentK_kernel<-1, false>);
+    take(node_bwd_persistentK_kernel<NGPDE_ACT_RELU>); take(node_bwd_persistentK_kernel<-1>);
   }
   const int nt = g->n_sched / kTileRows, resident = cus * occ;
   if (resident < 1) return 0;
@@ -2733,21 +2719,17 @@ __global__ __launch_bounds__(64) void own_first_tables_kernel(int n_tiles, const
 
 int32_t own_first_tables_build(const ngpde_graph *g, OwnFirst *of, hipStream_t stream) {
   const int nt = g->n_sched / kTileRows;
-  const Csr *cs[2] = {&g->by_t, &g->by_s};
   // the by-target lists only: the adjoint's tiles reach their wait with the flags already set (its parameter-gradient products sit
-  // between publish and wait), so there the padding rounds cost more than the early sums win (2.913 -> 2.925 ms, profiles/r06_l_own_first.txt);
-  // NGPDE_OWN_FIRST_ADJOINT=1 builds both (A/B runs)
-  const char *adj = std::getenv("NGPDE_OWN_FIRST_ADJOINT");
-  const int n_dir = (adj && adj[0] == '1') ? 2 : 1;
-  for (int dir = 0; dir < n_dir; ++dir) {
-    const Csr &c = *cs[dir];
-    if (!c.halo_ok || !c.slots || !c.sched) continue;
-    NGPDE_HIP_CHECK(hipMalloc((void **)&of->slots[dir], (size_t)g->n_sched * kSlotWidth));
-    NGPDE_HIP_CHECK(hipMalloc((void **)&of->sched[dir], (size_t)g->n_sched * sizeof(int4)));
-    NGPDE_HIP_CHECK(hipMalloc((void **)&of->pre[dir], (size_t)nt * 8));
-    if (c.slot_w) NGPDE_HIP_CHECK(hipMalloc((void **)&of->slot_w[dir], (size_t)g->n_sched * kSlotWidth * sizeof(float)));
-    hipLaunchKernelGGL(own_first_tables_kernel, dim3(nt), dim3(64), 0, stream, nt, c.slots, c.sched, c.slot_w, of->slots[dir], of->sched[dir],
-                       of->slot_w[dir], of->pre[dir]);
+  // between publish and wait), so there the padding rounds cost more than the early sums win (measured with by-source tables too:
+  // 2.913 -> 2.925 ms, profiles/r06_l_own_first.txt)
+  const Csr &c = g->by_t;
+  if (c.halo_ok && c.slots && c.sched) {
+    NGPDE_HIP_CHECK(hipMalloc((void **)&of->slots, (size_t)g->n_sched * kSlotWidth));
+    NGPDE_HIP_CHECK(hipMalloc((void **)&of->sched, (size_t)g->n_sched * sizeof(int4)));
+    NGPDE_HIP_CHECK(hipMalloc((void **)&of->pre, (size_t)nt * 8));
+    if (c.slot_w) NGPDE_HIP_CHECK(hipMalloc((void **)&of->slot_w, (size_t)g->n_sched * kSlotWidth * sizeof(float)));
+    hipLaunchKernelGGL(own_first_tables_kernel, dim3(nt), dim3(64), 0, stream, nt, c.slots, c.sched, c.slot_w, of->slots, of->sched,
+                       of->slot_w, of->pre);
     NGPDE_LAUNCH_CHECK("own_first_tables_kernel");
   }
   NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
@@ -2755,12 +2737,10 @@ int32_t own_first_tables_build(const ngpde_graph *g, OwnFirst *of, hipStream_t s
 }
 
 void own_first_tables_free(OwnFirst *of) {
-  for (int dir = 0; dir < 2; ++dir) {
-    if (of->slots[dir]) (void)hipFree(of->slots[dir]);
-    if (of->sched[dir]) (void)hipFree(of->sched[dir]);
-    if (of->slot_w[dir]) (void)hipFree(of->slot_w[dir]);
-    if (of->pre[dir]) (void)hipFree(of->pre[dir]);
-  }
+  if (of->slots) (void)hipFree(of->slots);
+  if (of->sched) (void)hipFree(of->sched);
+  if (of->slot_w) (void)hipFree(of->slot_w);
+  if (of->pre) (void)hipFree(of->pre);
   *of = OwnFirst();
 }
 
@@ -2911,13 +2891,14 @@ __global__ void latch_fault_kernel(const unsigned *abort_word, unsigned *fault) 
 }  // namespace
 const unsigned *node_persistent_abort_word(const NodePersist *ps) { return ps->sync ? ps->sync + (size_t)ps->n_tiles * 64 : nullptr; }
 namespace {
-TileMeta make_meta(const Csr &c, const NodePersist &ps, int dir, const OwnFirst *of) {
+// of: the plan's own-first tables (forward only, dir 0), or NULL
+TileMeta make_meta(const Csr &c, const NodePersist &ps, int dir, const OwnFirst *of = nullptr) {
   TileMeta m;
   m.halo = c.halo; m.slots = c.slots; m.sched = c.sched; m.tile_info = c.tile_info; m.nbr = ps.nbr; m.slot_w = c.slot_w;
   m.of_pre = nullptr;
-  if (of && of->slots[dir] && !ps.hub) {   // the plan's own-first tables: the same rows in another order, padded lengths in the schedule
-    m.slots = of->slots[dir]; m.sched = of->sched[dir]; m.of_pre = of->pre[dir];
-    if (m.slot_w) m.slot_w = of->slot_w[dir];
+  if (of && of->slots && !ps.hub) {   // the plan's own-first tables: the same rows in another order, padded lengths in the schedule
+    m.slots = of->slots; m.sched = of->sched; m.of_pre = of->pre;
+    if (m.slot_w) m.slot_w = of->slot_w;
   }
   const NodePersist::HubLists &L = ps.hub_lists[dir];
   m.hub_halo = L.halo; m.hub_slots = L.slots; m.hub_rows = L.rows; m.hub_info = L.info; m.hub_long = L.longs; m.hub_sched = L.sched;
@@ -3019,15 +3000,11 @@ int32_t launch_node_fwd_persistent(const NodePersistFwd &a, hipStream_t stream) 
     if ((st = launch_zero(a.state + a.row_elems, 6 * a.row_elems * sizeof(float), stream))) return st;   // k_0 .. k_5 start from zero
     const dim3 gridk(ps.pair_wgs), blockk(kThreads);
     NGPDE_REQUIRE(!k.m.slot_w || a.k_tiles <= kMaxTileRoundsW, NGPDE_ERR_STATE, "weighted tile rounds: at most %d tiles per workgroup", kMaxTileRoundsW);
-    const char *nopipe = std::getenv("NGPDE_NO_TILE_PIPE");
-    const bool pipe = !k.m.slot_w && !(nopipe && nopipe[0] == '1');
+    // unweighted: the pipelined kernel; weighted: the plain tile-round kernel (the slot weights leave no LDS for the pipeline)
 #define NGPDE_PFK_LAUNCH(AA, TT)                                                                                                  \
-    if (pipe) {                                                                                                                   \
+    if (!k.m.slot_w) {                                                                                                            \
       if (a.ev_start) hipExtLaunchKernelGGL((node_fwd_persistentKP_kernel<AA, TT>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
       else hipLaunchKernelGGL((node_fwd_persistentKP_kernel<AA, TT>), gridk, blockk, 0, stream, k);                                \
-    } else if (k.m.slot_w) {                                                                                                             \
-      if (a.ev_start) hipExtLaunchKernelGGL((node_fwd_persistentK_kernel<AA, TT, true>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
-      else hipLaunchKernelGGL((node_fwd_persistentK_kernel<AA, TT, true>), gridk, blockk, 0, stream, k);                           \
     } else if (a.ev_start) hipExtLaunchKernelGGL((node_fwd_persistentK_kernel<AA, TT>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
     else hipLaunchKernelGGL((node_fwd_persistentK_kernel<AA, TT>), gridk, blockk, 0, stream, k);
     if (a.tape && a.act == NGPDE_ACT_RELU) { NGPDE_PFK_LAUNCH(NGPDE_ACT_RELU, true) }
@@ -3101,7 +3078,7 @@ int32_t launch_node_bwd_persistent(const NodePersistBwd &a, hipStream_t stream) 
   if ((st = turn.enter(stream))) return st;
   if ((st = launch_zero(ps.sync, ps.sync_bytes, stream))) return st;
   PBwdK k;
-  k.m = make_meta(g->by_s, ps, 1, a.of);
+  k.m = make_meta(g->by_s, ps, 1);
   k.n_steps = a.n_steps; k.S = a.S; k.n_members = a.n_members; k.act = a.act; k.ztape = a.ztape;
   k.lam = a.lam; k.g1 = a.g1; k.g2 = a.g2; k.w1 = a.w1; k.w2 = a.w2;
   k.tape = a.tape; k.masks = a.masks; k.row_elems = a.row_elems; k.mask_bytes = a.mask_bytes;
@@ -3121,17 +3098,12 @@ int32_t launch_node_bwd_persistent(const NodePersistBwd &a, hipStream_t stream) 
     if ((st = launch_zero(a.ubar, 5 * a.row_elems * sizeof(float), stream))) return st;   // the stage adjoints start from zero
     const dim3 gridk(ps.pair_wgs), blockk(kThreads);
     NGPDE_REQUIRE(!k.m.slot_w || a.k_tiles <= kMaxTileRoundsW, NGPDE_ERR_STATE, "weighted tile rounds: at most %d tiles per workgroup", kMaxTileRoundsW);
-    const char *nopipe_b = std::getenv("NGPDE_NO_TILE_PIPE");
-    const bool piped_b = !k.m.slot_w && !(nopipe_b && nopipe_b[0] == '1');
 #define NGPDE_PBK_LAUNCH(AA)                                                                                                      \
-    if (piped_b) {                                                                                                                \
+    if (!k.m.slot_w) {                                                                                                            \
       if (a.ev_start) hipExtLaunchKernelGGL((node_bwd_persistentKP_kernel<AA>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
       else hipLaunchKernelGGL((node_bwd_persistentKP_kernel<AA>), gridk, blockk, 0, stream, k);                                    \
-    } else if (k.m.slot_w) {                                                                                                      \
-      if (a.ev_start) hipExtLaunchKernelGGL((node_bwd_persistentK_kernel<AA, true>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
-      else hipLaunchKernelGGL((node_bwd_persistentK_kernel<AA, true>), gridk, blockk, 0, stream, k);                               \
-    } else if (a.ev_start) hipExtLaunchKernelGGL((node_bwd_persistentK_kernel<AA, false>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
-    else hipLaunchKernelGGL((node_bwd_persistentK_kernel<AA, false>), gridk, blockk, 0, stream, k);
+    } else if (a.ev_start) hipExtLaunchKernelGGL((node_bwd_persistentK_kernel<AA>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
+    else hipLaunchKernelGGL((node_bwd_persistentK_kernel<AA>), gridk, blockk, 0, stream, k);
     if (a.act == NGPDE_ACT_RELU) { NGPDE_PBK_LAUNCH(NGPDE_ACT_RELU) }
     else { NGPDE_PBK_LAUNCH(-1) }
 #undef NGPDE_PBK_LAUNCH

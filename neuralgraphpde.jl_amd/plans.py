@@ -146,7 +146,7 @@ class _NodeGCN2Fn(torch.autograd.Function):
         return du0, dw1, db1, dw2, db2, None
 
 
-_FLAG_NAMES = ((1, "prescaled"), (2, "sign_masks"), (4, "eager"), (8, "persistent_fwd"), (16, "persistent_bwd"), (32, "tile_pairs"),
+_FLAG_NAMES = ((1, "prescaled"), (2, "sign_masks"), (8, "persistent_fwd"), (16, "persistent_bwd"), (32, "tile_pairs"),
                (64, "tile_rounds"), (128, "widened"), (256, "hub_geometry"), (512, "own_first"))
 
 

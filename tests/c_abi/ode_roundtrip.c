@@ -135,7 +135,9 @@ int main(void) {
     ngpde_ode_desc_t de = d;
     de.tableau = NGPDE_TABLEAU_EULER; de.n_steps = 1; de.dt = 0.1; de.with_backward = 0; de.pos = pos_d;
     ngpde_ode_t *oe = NULL;
-    CHECK_NG(ngpde_ode_create(g, &de, &oe, NULL));
+    int32_t fe = 0;
+    CHECK_NG(ngpde_ode_create(g, &de, &oe, &fe));
+    EXPECT((fe & NGPDE_NODE_PERSISTENT_FWD) && !(fe & NGPDE_NODE_PERSISTENT_BWD), "VMH without backward: persistent forward, no persistent adjoint flag");
     CHECK_NG(ngpde_ode_forward(oe, u0_d, &prm, 0, 0, uT_a, NULL));
     CHECK_HIP(hipDeviceSynchronize());
     float *got = malloc(sizeof(float) * n);
@@ -192,6 +194,8 @@ int main(void) {
     EXPECT(ngpde_ode_create(g, &bad, &ob, NULL) == NGPDE_ERR_DIMENSION_MISMATCH, "VMH: gamma must return the state's width (DimensionMismatch)");
     bad = d; bad.rhs = NGPDE_RHS_GAT; bad.width = 48; bad.heads = 3; bad.head_width = 16;
     EXPECT(ngpde_ode_create(g, &bad, &ob, NULL) == NGPDE_ERR_UNSUPPORTED && ob == NULL, "GAT 48 => 3 x 16: no device-resident plan (ERR_UNSUPPORTED: the host steps it)");
+    bad = d; bad.pos = pos_d; bad.members = 2;
+    EXPECT(ngpde_ode_create(g, &bad, &ob, NULL) == NGPDE_ERR_INVALID_ARGUMENT && ob == NULL, "VMH: a batch is one graph to the plan (members = 1)");
     bad = d; bad.rhs = 9;
     EXPECT(ngpde_ode_create(g, &bad, &ob, NULL) == NGPDE_ERR_INVALID_ARGUMENT, "unknown right-hand side (ERR_INVALID_ARGUMENT)");
   }

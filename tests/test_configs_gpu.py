@@ -791,7 +791,7 @@ def test_graph_node_tutorial_training_loop(graph_kind):
         l, yhat = loss_fn()
         acc = float((yhat.T[~mask].argmax(1) == y[~mask]).double().mean())
     plan = next(iter(node._plans.values()))[0]
-    switched = any(os.environ.get(v) for v in ("NGPDE_NO_PERSISTENT", "NGPDE_NO_WIDEN", "NGPDE_NO_HALO", "NGPDE_PERSISTENT", "NGPDE_NO_PRESCALE", "NGPDE_NO_MASK"))
+    switched = any(os.environ.get(v) for v in ("NGPDE_NO_PERSISTENT", "NGPDE_NO_WIDEN", "NGPDE_NO_HALO", "NGPDE_NO_PRESCALE", "NGPDE_NO_MASK"))
     assert switched or "persistent_fwd" in plan.flags(), plan.flags()
     assert switched or ("hub_geometry" in plan.flags()) == (graph_kind == "citation"), plan.flags()
     assert not plan.fault()

@@ -513,8 +513,8 @@ def _oracle_node_with_seed(params, og, u0, seed, tableau, dt, nsteps, act="relu"
     return uT, du0, acc
 
 
-PLAN_SWITCHES = ("NGPDE_NO_PERSISTENT", "NGPDE_PERSISTENT", "NGPDE_NO_WIDEN", "NGPDE_NO_TILE_PAIRS", "NGPDE_TILE_ROUNDS", "NGPDE_NO_INTERLEAVE",
-                 "NGPDE_WEIGHTED_TILE_ROUNDS", "NGPDE_NO_TILE_PIPE", "NGPDE_NO_PRESCALE", "NGPDE_NO_MASK", "NGPDE_NO_OWN_FIRST", "NGPDE_OWN_FIRST_ADJOINT")
+PLAN_SWITCHES = ("NGPDE_NO_PERSISTENT", "NGPDE_NO_WIDEN", "NGPDE_NO_TILE_PAIRS", "NGPDE_TILE_ROUNDS", "NGPDE_NO_INTERLEAVE",
+                 "NGPDE_WEIGHTED_TILE_ROUNDS", "NGPDE_NO_PRESCALE", "NGPDE_NO_MASK", "NGPDE_NO_OWN_FIRST")
 
 
 def needs_persistent_plan(monkeypatch=None):

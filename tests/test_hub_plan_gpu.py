@@ -15,7 +15,7 @@ from oracle import ngpde_oracle as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SWITCHES = ("NGPDE_NO_PERSISTENT", "NGPDE_NO_HALO", "NGPDE_PERSISTENT", "NGPDE_NO_PRESCALE", "NGPDE_NO_MASK", "NGPDE_NO_WIDEN")
+SWITCHES = ("NGPDE_NO_PERSISTENT", "NGPDE_NO_HALO", "NGPDE_NO_PRESCALE", "NGPDE_NO_MASK", "NGPDE_NO_WIDEN")
 
 
 def hub_plan_expected():

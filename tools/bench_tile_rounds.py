@@ -1,6 +1,6 @@
 """Solve + discrete adjoint of the C2 right-hand side on graphs of 2x / 4x / 8x the bench's size (tile pairs, tile rounds), through the
 C ABI: ms per direction by the plan's own dispatch events, and the fraction of the HBM bound of SURVEY 8(d)'s algorithmic bytes.
-  python3 tools/bench_tile_rounds.py [factors...]      (NGPDE_NO_TILE_PIPE=1: the plain tile-round kernels)"""
+  python3 tools/bench_tile_rounds.py [factors...]"""
 import ctypes as C, json, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

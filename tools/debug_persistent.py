@@ -1,5 +1,5 @@
 """Persistent solver plan vs the replayed plan, output by output, on the bench workload cut to STEPS steps (env: STEPS, TAB,
-N, PAIRS, MIX=fwd|bwd to run only one direction persistently)."""
+N, PAIRS)."""
 import ctypes as C
 import os
 import sys
@@ -30,8 +30,6 @@ stream = torch.cuda.current_stream().cuda_stream
 def run(persistent):
     if persistent:
         os.environ.pop("NGPDE_NO_PERSISTENT", None)
-        if os.environ.get("MIX"):
-            os.environ["NGPDE_PERSISTENT"] = os.environ["MIX"]
     else:
         os.environ["NGPDE_NO_PERSISTENT"] = "1"
     plan = _Plan(g.handle((True, None, False)), D, _lib.ACT["relu"], TAB, STEPS, 1.0 / 50, True)

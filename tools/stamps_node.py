@@ -1,7 +1,6 @@
-"""Diagnostic: per-workgroup phase timestamps of every kernel of one Tsit5 step (libngpde_diag.so, eager)."""
+"""Diagnostic: per-workgroup phase timestamps of every kernel of one Tsit5 step (libngpde_diag.so)."""
 import ctypes as C
 import os, sys
-os.environ["NGPDE_NODE_EAGER"] = "1"
 import numpy as np
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
