@@ -874,9 +874,11 @@ __global__ __launch_bounds__(256) void edge64_dq_combine_kernel(int n_listed, co
 
 // ---- pullback launch.  Same conditions as the forward specialisation (the activation pairs instantiated below); workspace =
 // one [65][64] slab per workgroup (edge_mlp64_bwd_grid).
-static int edge64_bwd_grid(const ngpde_graph *g) {
+// The kernel splits the tiles into 8 per-XCD ranges and lets gridDim.x / 8 workgroups walk each: the grid has to be a multiple of 8,
+// or the workgroups beyond the last multiple walk tiles of their XCD a second time (and add their dW2 / db2 twice).
+static int edge64_bwd_grid(const ngpde_graph *g, int per_xcd_cap = 64) {
   const int n_tiles = (int)(g->n_sched / kTileRows);
-  return 8 * std::max(1, std::min(64, (n_tiles + 7) / 8));   // two persistent workgroups per CU, a multiple of the 8 XCDs
+  return 8 * std::max(1, std::min(per_xcd_cap, (n_tiles + 7) / 8));   // persistent workgroups, a multiple of the 8 XCDs
 }
 bool edge_mlp64_bwd_applicable(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
   if (env_off("NGPDE_NO_EDGE64")) return false;
@@ -914,7 +916,8 @@ int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hip
   k.dqpart = dq ? reinterpret_cast<float *>(reinterpret_cast<char *>(a.workspace) + edge64_slab_bytes(g)) : nullptr;
   k.dQ = dq ? a.dQ : nullptr;
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kChunk4 * kTS + 2 * (size_t)kW * kTS) * sizeof(float);
-  const int grid = (lds + 4096 <= 80 * 1024) ? edge64_bwd_grid(g) : std::max(8, edge64_bwd_grid(g) / 2);
+  // two workgroups per CU, or one when the halo region is large (the workspace holds slabs for the larger grid)
+  const int grid = edge64_bwd_grid(g, lds + 4096 <= 80 * 1024 ? 64 : 32);
   auto launch = [&](auto kernel) -> hipError_t {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
