@@ -1346,7 +1346,7 @@ int32_t launch_dense_multi_fwd(int count, const int64_t *n, const SegTable *segs
 // the contraction is long; every split gets a multiple of BK features
 int dense_fwd_splits(int64_t n, int din, int dout) {
   const int64_t tiles = ((n + BM - 1) / BM) * ((dout + BN - 1) / BN);
-  if (tiles >= 256 || din < 256) return 1;
+  if (tiles == 0 || tiles >= 256 || din < 256) return 1;   // (no rows: nothing to split, and no division by zero tiles)
   const int64_t want = (512 + tiles - 1) / tiles;
   return (int)std::max<int64_t>(1, std::min<int64_t>(want, din / 64));
 }
@@ -1426,7 +1426,7 @@ __global__ void add_partials_kernel(int64_t count, int nparts, size_t stride, co
 // splits of the input pullback over the output features (see dense_mfma_bwd_input_kernel): 1 = none
 int dense_bwd_input_splits(int64_t n, int din, int dout) {
   const int64_t tiles = ((n + BM2 - 1) / BM2) * ((din + BN - 1) / BN);
-  if (tiles >= 256 || dout < 512) return 1;
+  if (tiles == 0 || tiles >= 256 || dout < 512) return 1;   // (ngpde_dense_workspace_bytes asks for n = 0 too)
   // enough workgroups for a few rounds of the chip, each still with a dozen or more K steps (the partial slabs cost a pass too)
   return (int)std::max<int64_t>(1, std::min<int64_t>((2048 + tiles - 1) / tiles, dout / 256));
 }
