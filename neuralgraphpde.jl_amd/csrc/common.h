@@ -273,16 +273,20 @@ int32_t node_persistent_setup(const ngpde_graph *g, const float *coef_host /* [9
 void node_persistent_free(NodePersist *ps);
 int32_t launch_node_fwd_persistent(const NodePersistFwd &a, hipStream_t stream);
 int32_t launch_node_bwd_persistent(const NodePersistBwd &a, hipStream_t stream);
-// Persistent launches of one process take turns per device (node_persistent.hip): enter() takes the device's turnstile lock and makes
-// `stream` wait for the previous persistent launch on the device, leave() records this one and releases the lock; the lock is
-// held from enter to leave, so two host threads cannot both pass the wait and then launch side by side.  The destructor releases
-// a lock that an error path left behind.  On a stream that is being captured into a HIP graph the event wait / record is skipped
-// (a captured event would poison later eager launches): ordering inside the captured graph is the capture's own.
+// The bracket of every persistent launch (node_persistent.hip): enter, launch, latch, leave.  Persistent launches of one process
+// take turns per device: enter() takes the device's turnstile lock and makes `stream` wait for the previous persistent launch on the
+// device, then zeroes the plan's sync arena and, under NGPDE_DEBUG_FORCE_ABORT=1 (tests only), sets its abort word; latch() enqueues
+// fault |= abort word (skipped by a caller that latches in its own next kernel); leave() records this launch and releases the lock.
+// The lock is held from enter to leave, so two host threads cannot both pass the wait and then launch side by side.  The destructor
+// releases a lock that an error path left behind.  On a stream that is being captured into a HIP graph the event wait / record is
+// skipped (a captured event would poison later eager launches): ordering inside the captured graph is the capture's own.
 struct PersistentTurn {
   int dev = -1;
   bool held = false;
   hipStream_t stream = nullptr;
-  int32_t enter(hipStream_t s);
+  const NodePersist *ps = nullptr;
+  int32_t enter(const NodePersist &p, hipStream_t s);
+  int32_t latch();
   int32_t leave();
   ~PersistentTurn();
   PersistentTurn() = default;

@@ -17,7 +17,6 @@
 // dal_j a_l + dar_j a_r (dar_j = sum of dscore over the outgoing edges), dx = dWx W^T and dW += x^T dWx on MFMA with the
 // accumulators of a workgroup's tiles kept in registers, u_l = sum_j dal_j x_j, u_r likewise;  (3) slabs -> dW, db, and
 // da_l,k = W_k u_l,k.  No atomics: every output has one writer and a fixed summation order.
-#include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <cstdlib>
@@ -25,6 +24,8 @@
 #include "common.h"
 #include "device_utils.h"
 #include "gcn_tile.h"
+#include "persistent_mem.h"
+#include "persistent_sync.h"
 
 namespace ngpde {
 
@@ -378,13 +379,6 @@ struct GatBwdTK {
   float *dz, *dscore, *dal, *slab_db;
 };
 
-// write-through store (see node_persistent.hip: store_sc1 -- the s_nop 4 covers an SGPR base re-materialised by a spill reload right
-// in front of the asm, the s_nop 1 the rewrite of the data registers): rows / entries another workgroup of the SAME launch reads
-typedef float gat_f4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void gat_store_sc1(float *base, unsigned byte_off, float4 v) {
-  gat_f4v t = {v.x, v.y, v.z, v.w};
-  asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(byte_off), "v"(t), "s"(base) : "memory");
-}
 // agent-scope (sc1) loads of four consecutive floats written by another workgroup of the same launch
 __device__ __forceinline__ float4 gat_load4_sc1(const float *ptr) {
   float4 v;
@@ -539,7 +533,7 @@ __device__ __forceinline__ float gat_bwd_target_compute(const GatBwdTK &p, const
     if (q + 16 * s < deg) {
       const float4 v4 = make_float4(dsc[s][0], H > 1 ? dsc[s][1] : 0.f, H > 2 ? dsc[s][2] : 0.f, H > 2 ? dsc[s][3] : 0.f);
       if constexpr (PAD) {
-        gat_store_sc1(p.dscore, (unsigned)((((size_t)tile * kTM + grp) * kSlotWidth + q + 16 * s) * 4 * sizeof(float)), v4);
+        store_sc1(p.dscore, (unsigned)((((size_t)tile * kTM + grp) * kSlotWidth + q + 16 * s) * 4 * sizeof(float)), v4);
       } else {
         float *dst = p.dscore + (size_t)(m.sc.y + q + 16 * s) * H;
         if (H == 4) *reinterpret_cast<float4 *>(dst) = v4;
@@ -885,7 +879,6 @@ __global__ __launch_bounds__(1024) void gat_layer_reduce_kernel(const float *__r
 //     the neighbours' publish of the SAME phase; by-source half -> U-bar_i = dx.  One hand-off per right-hand side.
 //     dW / u / db accumulate in registers over the whole adjoint; one slab per tile at the end, reduced by gat_layer_reduce_kernel.
 // ---------------------------------------------------------------------------------------------------
-constexpr int kGatNbrStride = 64;   // = node_persistent.hip's wait-list stride (node_persistent_setup builds the lists)
 struct GatSync {
   const int *nbr;        // [n_tiles][64] wait lists, -1 padded
   unsigned *flags;       // one 128-byte line per tile: the last published phase
@@ -921,19 +914,6 @@ __device__ __forceinline__ void gat_publish(const GatSync &s, const GatThread &t
   wait_vmcnt0();
   __syncthreads();
   if (t.tid == 0) __hip_atomic_store(s.flags + 32 * tile, ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-#define NGPDE_GAT_GLOBAL __attribute__((address_space(1)))
-__device__ __forceinline__ float4 gat_ld4(const float *base, unsigned byte_off) {
-  const gat_f4v v = *reinterpret_cast<NGPDE_GAT_GLOBAL const gat_f4v *>(reinterpret_cast<uintptr_t>(base) + byte_off);
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void gat_st4(float *base, unsigned byte_off, float4 v) {
-  const gat_f4v w = {v.x, v.y, v.z, v.w};
-  *reinterpret_cast<NGPDE_GAT_GLOBAL gat_f4v *>(reinterpret_cast<uintptr_t>(base) + byte_off) = w;
-}
-__device__ __forceinline__ float4 gat_nan4() {
-  const float n = __int_as_float(0x7fc00000);
-  return make_float4(n, n, n, n);
 }
 
 struct GatNodeFwdK {
@@ -979,7 +959,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_batch_ker
   gat_fwd_consts<H>(p.l, L, t, breg, b4);
   if (t.tid < 64) ldsC[t.tid] = p.cf[t.tid];
   if (t.tid == 0) s_ok = 1;
-  const int my_nbr = p.s.nbr[(size_t)tile * kGatNbrStride + t.lane];
+  const int my_nbr = p.s.nbr[(size_t)tile * kNbrStride + t.lane];
   const bool ok = m.sc.x >= 0;
   const unsigned own = (unsigned)max(m.sc.x, 0) * (unsigned)(GD * 4) + (unsigned)(t.q * 16);
   const int S = p.S;
@@ -991,7 +971,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_batch_ker
   for (int mb = 0; mb < p.n_members && !dead; mb += 2, ph0 += P) {
     const int nsl = min(2, p.n_members - mb);
     for (int sl = 0; sl < nsl; ++sl)   // u of the slot's member -> row 6 of the slot's scratch
-      if (ok) gat_st4(p.kbuf + (size_t)(sl * 7 + 6) * p.row_elems, own, gat_ld4(p.u_in + (size_t)(mb + sl) * p.row_elems, own));
+      if (ok) st4_g(p.kbuf + (size_t)(sl * 7 + 6) * p.row_elems, own, ld4_g(p.u_in + (size_t)(mb + sl) * p.row_elems, own));
     for (int n = 0; n < p.n_steps && !dead; ++n) {
       for (int i = 0; i < S && !dead; ++i) {
         const unsigned lp = (unsigned)(n * S + i) + 1, ph = ph0 + lp;
@@ -1008,15 +988,15 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_batch_ker
           l.alpha = p.alpha ? p.alpha + (size_t)(mb + sl) * p.alpha_stride + e * p.alpha_elems : nullptr;
           const float4 z = gat_fwd_compute<H>(l, L, t, m, tile, breg, b4);
           const float4 y = f4_act(l.act, z);
-          if (p.yz && ok) gat_st4(p.yz + (size_t)(mb + sl) * p.yz_stride + e * p.row_elems, own, l.act == NGPDE_ACT_RELU ? y : z);
-          float4 v = f4_scale(1.0f, gat_ld4(kb + (size_t)6 * p.row_elems, own));
-          for (int j = 0; j < i; ++j) v = f4_fma(ldsC[row * 8 + j], gat_ld4(kb + (size_t)j * p.row_elems, own), v);
+          if (p.yz && ok) st4_g(p.yz + (size_t)(mb + sl) * p.yz_stride + e * p.row_elems, own, l.act == NGPDE_ACT_RELU ? y : z);
+          float4 v = f4_scale(1.0f, ld4_g(kb + (size_t)6 * p.row_elems, own));
+          for (int j = 0; j < i; ++j) v = f4_fma(ldsC[row * 8 + j], ld4_g(kb + (size_t)j * p.row_elems, own), v);
           v = f4_fma(ldsC[row * 8 + i], y, v);
           if (ok) {
-            if (i + 1 < S) gat_st4(kb + (size_t)i * p.row_elems, own, y);
-            else gat_st4(kb + (size_t)6 * p.row_elems, own, v);
-            if (last) gat_st4(p.u_out + (size_t)(mb + sl) * p.row_elems, own, v);
-            else gat_store_sc1(xs + (p.taped ? e + 1 : ((e + 1) & 1)) * p.row_elems, own, v);
+            if (i + 1 < S) st4_g(kb + (size_t)i * p.row_elems, own, y);
+            else st4_g(kb + (size_t)6 * p.row_elems, own, v);
+            if (last) st4_g(p.u_out + (size_t)(mb + sl) * p.row_elems, own, v);
+            else store_sc1(xs + (p.taped ? e + 1 : ((e + 1) & 1)) * p.row_elems, own, v);
           }
           if (!last) gat_publish(ys, t, tile, ph);
           else __syncthreads();   // (the other slot's DMA must not land in rows this slot's waves still read)
@@ -1025,7 +1005,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_batch_ker
     }
   }
   if (dead && ok)
-    for (int mb = 0; mb < p.n_members; ++mb) gat_st4(p.u_out + (size_t)mb * p.row_elems, own, gat_nan4());
+    for (int mb = 0; mb < p.n_members; ++mb) st4_g(p.u_out + (size_t)mb * p.row_elems, own, f4_nan());
 }
 
 template <int H>
@@ -1049,10 +1029,10 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_kernel(co
   gat_fwd_consts<H>(p.l, L, t, breg, b4);
   if (t.tid < 64) ldsC[t.tid] = p.cf[t.tid];
   if (t.tid == 0) s_ok = 1;
-  const int my_nbr = p.s.nbr[(size_t)tile * kGatNbrStride + t.lane];
+  const int my_nbr = p.s.nbr[(size_t)tile * kNbrStride + t.lane];
   const bool ok = m.sc.x >= 0;
   const unsigned own = (unsigned)max(m.sc.x, 0) * (unsigned)(GD * 4) + (unsigned)(t.q * 16);
-  float4 u = ok ? gat_ld4(p.u_in, own) : f4_zero();
+  float4 u = ok ? ld4_g(p.u_in, own) : f4_zero();
   const int S = p.S;
   GatFwdK l = p.l;
   bool dead = false;
@@ -1072,23 +1052,23 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_kernel(co
       l.alpha = p.alpha ? p.alpha + e * p.alpha_elems : nullptr;
       const float4 z = gat_fwd_compute<H>(l, L, t, m, tile, breg, b4);
       const float4 y = f4_act(l.act, z);
-      if (p.yz && ok) gat_st4(p.yz + e * p.row_elems, own, l.act == NGPDE_ACT_RELU ? y : z);
+      if (p.yz && ok) st4_g(p.yz + e * p.row_elems, own, l.act == NGPDE_ACT_RELU ? y : z);
       float4 v = f4_scale(1.0f, u);
-      for (int j = 0; j < i; ++j) v = f4_fma(ldsC[row * 8 + j], gat_ld4(p.kbuf + (size_t)j * p.row_elems, own), v);
+      for (int j = 0; j < i; ++j) v = f4_fma(ldsC[row * 8 + j], ld4_g(p.kbuf + (size_t)j * p.row_elems, own), v);
       v = f4_fma(ldsC[row * 8 + i], y, v);
-      if (i + 1 < S && ok) gat_st4(p.kbuf + (size_t)i * p.row_elems, own, y);   // (a padding row's thread addresses node 0)
+      if (i + 1 < S && ok) st4_g(p.kbuf + (size_t)i * p.row_elems, own, y);   // (a padding row's thread addresses node 0)
       else u = v;
       const bool last = (n == p.n_steps - 1 && i == S - 1);
       if (ok) {
-        if (last) gat_st4(p.u_out, own, v);
-        else gat_store_sc1(p.xs + (p.taped ? e + 1 : ((e + 1) & 1)) * p.row_elems, own, v);
+        if (last) st4_g(p.u_out, own, v);
+        else store_sc1(p.xs + (p.taped ? e + 1 : ((e + 1) & 1)) * p.row_elems, own, v);
       }
       NGPDE_GSTP(NGPDE_GSTP_OF(l), 14);
       if (!last) gat_publish(p.s, t, tile, ph);
       NGPDE_GSTP(NGPDE_GSTP_OF(l), 15);
     }
   }
-  if (dead && ok) gat_st4(p.u_out, own, gat_nan4());
+  if (dead && ok) st4_g(p.u_out, own, f4_nan());
 }
 
 struct GatNodeBwdK {
@@ -1129,7 +1109,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_batch_ker
   const int tile = xcd_tile(blockIdx.x, p.t.n_tiles);
   if (t.tid < 64) ldsC[t.tid] = p.cb[t.tid];
   if (t.tid == 0) s_ok = 1;
-  const int my_nbr = p.y.nbr[(size_t)tile * kGatNbrStride + t.lane];
+  const int my_nbr = p.y.nbr[(size_t)tile * kNbrStride + t.lane];
   const int hq = (4 * t.q) / C;
   const float4 al4 = *reinterpret_cast<const float4 *>(p.s.a + (size_t)hq * 2 * C + (4 * t.q) % C);
   const float4 ar4 = *reinterpret_cast<const float4 *>(p.s.a + (size_t)hq * 2 * C + C + (4 * t.q) % C);
@@ -1152,7 +1132,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_batch_ker
   for (int mb = 0; mb < p.n_members && !dead; mb += 2, ph0 += P) {
     const int nsl = min(2, p.n_members - mb);
     for (int sl = 0; sl < nsl; ++sl)
-      if (ok) gat_st4(p.lam + (size_t)(mb + sl) * p.row_elems, own, gat_ld4(p.duT + (size_t)(mb + sl) * p.row_elems, own));
+      if (ok) st4_g(p.lam + (size_t)(mb + sl) * p.row_elems, own, ld4_g(p.duT + (size_t)(mb + sl) * p.row_elems, own));
     unsigned lp = 0;
     for (int n = p.n_steps - 1; n >= 0 && !dead; --n) {
       for (int i = S - 1; i >= 0 && !dead; --i) {
@@ -1169,15 +1149,15 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_batch_ker
           tk.alpha = p.alpha + (size_t)(mb + sl) * p.alpha_stride + e * p.alpha_elems;
           tk.dscore = p.dscore + (size_t)(sl * 2 + (ph & 1)) * p.dscore_elems;
           tk.dal = p.t.dal + (size_t)sl * p.dal_stride;
-          const float4 lamv = gat_ld4(lam, own);
+          const float4 lamv = ld4_g(lam, own);
           float4 yzv = f4_zero();
-          if (p.yz) yzv = gat_ld4(p.yz + (size_t)(mb + sl) * p.yz_stride + e * p.row_elems, own);
+          if (p.yz) yzv = ld4_g(p.yz + (size_t)(mb + sl) * p.yz_stride + e * p.row_elems, own);
           float4 v = f4_scale(ldsC[i * 8 + i], ok ? lamv : f4_zero());
-          for (int j = i + 1; j < S; ++j) v = f4_fma(ldsC[i * 8 + j], gat_ld4(ub + (size_t)j * p.row_elems, own), v);
+          for (int j = i + 1; j < S; ++j) v = f4_fma(ldsC[i * 8 + j], ld4_g(ub + (size_t)j * p.row_elems, own), v);
           if (p.yz) v = f4_mul(v, f4_dact(tk.act, yzv));
           if (!ok) v = f4_zero();
           float *dzb = p.dzbuf + (size_t)(sl * 2 + (ph & 1)) * p.row_elems;
-          if (ok) gat_store_sc1(dzb, own, v);
+          if (ok) store_sc1(dzb, own, v);
           dbacc += gat_bwd_target_compute<H, true>(tk, LT, t, mt, tile, v);
           gat_publish(ys, t, tile, ph);
         }
@@ -1202,25 +1182,25 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_batch_ker
           halo_round2<GD, true, 16>(reinterpret_cast<const float4 *>(dzb), t.q, t.grp, ldsXh, hrs);
           const float4 dxv = gat_bwd_source_core<H, true>(sk, LS, t, ms, al4, ar4, dw, uacc, spre);
           if (i > 0) {
-            if (ok) gat_st4(ub + (size_t)i * p.row_elems, own, dxv);
+            if (ok) st4_g(ub + (size_t)i * p.row_elems, own, dxv);
           } else {
-            float4 w = f4_scale(1.0f, ok ? gat_ld4(lam, own) : f4_zero());
+            float4 w = f4_scale(1.0f, ok ? ld4_g(lam, own) : f4_zero());
             w = f4_fma(1.0f, dxv, w);
-            for (int j = 1; j < S; ++j) w = f4_fma(1.0f, gat_ld4(ub + (size_t)j * p.row_elems, own), w);
-            if (ok) gat_st4(lam, own, w);
+            for (int j = 1; j < S; ++j) w = f4_fma(1.0f, ld4_g(ub + (size_t)j * p.row_elems, own), w);
+            if (ok) st4_g(lam, own, w);
           }
         }
       }
     }
   }
   if (ok && dead)
-    for (int mb = 0; mb < p.n_members; ++mb) gat_st4(p.lam + (size_t)mb * p.row_elems, own, gat_nan4());
+    for (int mb = 0; mb < p.n_members; ++mb) st4_g(p.lam + (size_t)mb * p.row_elems, own, f4_nan());
   const float bad = __int_as_float(0x7fc00000);
   float4 *slab4 = reinterpret_cast<float4 *>(p.s.slab_dw + (size_t)tile * GD * GD);
 #pragma unroll
   for (int mm = 0; mm < GG::DWT; ++mm) {
     const int t2 = t.wave_u + GG::WAVES * mm;
-    if (t2 < NT) slab4[t2 * 64 + t.lane] = dead ? gat_nan4() : make_float4(dw[mm][0], dw[mm][1], dw[mm][2], dw[mm][3]);
+    if (t2 < NT) slab4[t2 * 64 + t.lane] = dead ? f4_nan() : make_float4(dw[mm][0], dw[mm][1], dw[mm][2], dw[mm][3]);
   }
   if (t.tid % GG::DBP == 0) p.slab_db[(size_t)tile * GD + t.tid / GG::DBP] = dead ? bad : dbacc;
   __syncthreads();
@@ -1246,7 +1226,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
   const int tile = xcd_tile(blockIdx.x, p.t.n_tiles);
   if (t.tid < 64) ldsC[t.tid] = p.cb[t.tid];
   if (t.tid == 0) s_ok = 1;
-  const int my_nbr = p.y.nbr[(size_t)tile * kGatNbrStride + t.lane];
+  const int my_nbr = p.y.nbr[(size_t)tile * kNbrStride + t.lane];
   const int hq = (4 * t.q) / C;
   const float4 al4 = *reinterpret_cast<const float4 *>(p.s.a + (size_t)hq * 2 * C + (4 * t.q) % C);
   const float4 ar4 = *reinterpret_cast<const float4 *>(p.s.a + (size_t)hq * 2 * C + C + (4 * t.q) % C);
@@ -1258,7 +1238,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
   const int node = p.t.sched[(size_t)tile * kTM + t.grp].x;   // (the same node in both directions' schedules: checked by the host)
   const bool ok = node >= 0;
   const unsigned own = (unsigned)max(node, 0) * (unsigned)(GD * 4) + (unsigned)(t.q * 16);
-  float4 lam = ok ? gat_ld4(p.duT, own) : f4_zero();
+  float4 lam = ok ? ld4_g(p.duT, own) : f4_zero();
   const int S = p.S;
   GatBwdTK tk = p.t;
   GatBwdSK sk = p.s;
@@ -1278,13 +1258,13 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
       tk.alpha = p.alpha + e * p.alpha_elems;
       tk.dscore = p.dscore + (size_t)(ph & 1) * p.dscore_elems;
       float4 yzv = f4_zero();
-      if (p.yz) yzv = gat_ld4(p.yz + e * p.row_elems, own);
+      if (p.yz) yzv = ld4_g(p.yz + e * p.row_elems, own);
       float4 v = f4_scale(ldsC[i * 8 + i], lam);
-      for (int j = i + 1; j < S; ++j) v = f4_fma(ldsC[i * 8 + j], gat_ld4(p.ubar + (size_t)j * p.row_elems, own), v);
+      for (int j = i + 1; j < S; ++j) v = f4_fma(ldsC[i * 8 + j], ld4_g(p.ubar + (size_t)j * p.row_elems, own), v);
       if (p.yz) v = f4_mul(v, f4_dact(tk.act, yzv));
       if (!ok) v = f4_zero();
       float *dzb = p.dzbuf + (size_t)(ph & 1) * p.row_elems;
-      if (ok) gat_store_sc1(dzb, own, v);
+      if (ok) store_sc1(dzb, own, v);
       NGPDE_GSTP(NGPDE_GSTP_OF(p), 1);
       dbacc += gat_bwd_target_compute<H, true>(tk, LT, t, mt, tile, v);
       NGPDE_GSTP(NGPDE_GSTP_OF(p), 2);
@@ -1308,22 +1288,22 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
       const float4 dxv = gat_bwd_source_core<H, true>(sk, LS, t, ms, al4, ar4, dw, uacc, spre);
       NGPDE_GSTP(NGPDE_GSTP_OF(p), 6);
       if (i > 0) {
-        if (ok) gat_st4(p.ubar + (size_t)i * p.row_elems, own, dxv);
+        if (ok) st4_g(p.ubar + (size_t)i * p.row_elems, own, dxv);
       } else {   // lambda of the step before: 1 * lambda + sum_j 1 * U-bar_j, j ascending
         float4 w = f4_scale(1.0f, lam);
         w = f4_fma(1.0f, dxv, w);
-        for (int j = 1; j < S; ++j) w = f4_fma(1.0f, gat_ld4(p.ubar + (size_t)j * p.row_elems, own), w);
+        for (int j = 1; j < S; ++j) w = f4_fma(1.0f, ld4_g(p.ubar + (size_t)j * p.row_elems, own), w);
         lam = ok ? w : f4_zero();
       }
     }
   }
-  if (ok) gat_st4(p.lam, own, dead ? gat_nan4() : lam);
+  if (ok) st4_g(p.lam, own, dead ? f4_nan() : lam);
   const float bad = __int_as_float(0x7fc00000);
   float4 *slab4 = reinterpret_cast<float4 *>(p.s.slab_dw + (size_t)tile * GD * GD);
 #pragma unroll
   for (int mm = 0; mm < GG::DWT; ++mm) {
     const int t2 = t.wave_u + GG::WAVES * mm;
-    if (t2 < NT) slab4[t2 * 64 + t.lane] = dead ? gat_nan4() : make_float4(dw[mm][0], dw[mm][1], dw[mm][2], dw[mm][3]);
+    if (t2 < NT) slab4[t2 * 64 + t.lane] = dead ? f4_nan() : make_float4(dw[mm][0], dw[mm][1], dw[mm][2], dw[mm][3]);
   }
   if (t.tid % GG::DBP == 0) p.slab_db[(size_t)tile * GD + t.tid / GG::DBP] = dead ? bad : dbacc;
   __syncthreads();
@@ -1455,15 +1435,9 @@ __global__ void gat_sched_same_kernel(const int4 *__restrict__ a, const int4 *__
   const int pos = blockIdx.x * blockDim.x + threadIdx.x;
   if (pos < n && a[pos].x != b[pos].x) *bad = 1u;
 }
-__global__ void gat_set_word_kernel(unsigned *w, unsigned v) {
-  if (threadIdx.x == 0) *w = v;
-}
-__global__ void gat_latch_fault_kernel(const unsigned *abort_word, unsigned *fault) {
-  if (threadIdx.x == 0 && *abort_word != 0) *fault = 1u;
-}
 inline GatSync gat_sync(const NodePersist &ps) {
   GatSync y;
-  y.nbr = ps.nbr; y.flags = ps.sync; y.abort_word = ps.sync + (size_t)ps.n_tiles * 64;   // node_persistent_setup's layout
+  y.nbr = ps.nbr; y.flags = ps.sync; y.abort_word = sync_abort_word(ps.sync, ps.n_tiles);
   return y;
 }
 }  // namespace
@@ -1519,8 +1493,7 @@ int32_t launch_gat_node_fwd(const GatNodeFwd &a, hipStream_t stream) {
   const NodePersist &ps = *a.ps;
   int32_t st;
   PersistentTurn turn;
-  if ((st = turn.enter(stream))) return st;
-  if ((st = launch_zero(ps.sync, ps.sync_bytes, stream))) return st;
+  if ((st = turn.enter(ps, stream))) return st;
   GatNodeFwdK k;
   k.l.x = nullptr; k.l.wt = a.wt; k.l.a = a.a; k.l.bias = a.bias; k.l.sched = g->by_t.sched; k.l.halo = g->by_t.halo;
   k.l.tile_info = g->by_t.tile_info;
@@ -1528,19 +1501,13 @@ int32_t launch_gat_node_fwd(const GatNodeFwd &a, hipStream_t stream) {
   k.l.save_z = nullptr;
   NGPDE_GST_SET(k.l)
   k.s = gat_sync(ps);
-  {
-    const char *fa = std::getenv("NGPDE_DEBUG_FORCE_ABORT");
-    if (fa && fa[0] == '1') hipLaunchKernelGGL(gat_set_word_kernel, dim3(1), dim3(64), 0, stream, k.s.abort_word, 1u);
-  }
   k.n_steps = a.n_steps; k.S = a.S; k.taped = a.taped ? 1 : 0; k.u_in = a.u_in; k.u_out = a.u_out; k.xs = a.xs; k.yz = a.yz;
   k.alpha = a.alpha; k.kbuf = a.kbuf; k.row_elems = (size_t)g->n_nodes * GD; k.alpha_elems = (size_t)std::max<int64_t>(g->n_edges, 1) * a.heads;
   k.cf = a.cf;
-  k.n_members = a.n_members; k.flag_stride = (size_t)ps.n_tiles * 32; k.xs_stride = a.xs_stride; k.yz_stride = a.yz_stride;
+  k.n_members = a.n_members; k.flag_stride = sync_slot_stride(ps.n_tiles); k.xs_stride = a.xs_stride; k.yz_stride = a.yz_stride;
   k.alpha_stride = a.alpha_stride;
   const dim3 grid(ps.n_tiles), block(kThreads);
-#define NGPDE_GN_LAUNCH(KERNEL)                                                                                   \
-  if (a.ev_start) hipExtLaunchKernelGGL(KERNEL, grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k);              \
-  else hipLaunchKernelGGL(KERNEL, grid, block, 0, stream, k);
+#define NGPDE_GN_LAUNCH(KERNEL) launch_timed(KERNEL, grid, block, 0, stream, a.ev_start, a.ev_stop, k);
   if (a.n_members > 1) {
     switch (a.heads) {
       case 1: NGPDE_GN_LAUNCH(gat_node_fwd_persistent_batch_kernel<1>) break;
@@ -1555,8 +1522,7 @@ int32_t launch_gat_node_fwd(const GatNodeFwd &a, hipStream_t stream) {
     }
   }
   NGPDE_LAUNCH_CHECK("gat_node_fwd_persistent_kernel");
-  hipLaunchKernelGGL(gat_latch_fault_kernel, dim3(1), dim3(64), 0, stream, k.s.abort_word, ps.fault);
-  NGPDE_LAUNCH_CHECK("gat_latch_fault_kernel");
+  if ((st = turn.latch())) return st;
   return turn.leave();
 }
 
@@ -1565,8 +1531,7 @@ int32_t launch_gat_node_bwd(const GatNodeBwd &a, hipStream_t stream) {
   const NodePersist &ps = *a.ps;
   int32_t st;
   PersistentTurn turn;
-  if ((st = turn.enter(stream))) return st;
-  if ((st = launch_zero(ps.sync, ps.sync_bytes, stream))) return st;
+  if ((st = turn.enter(ps, stream))) return st;
   GatNodeBwdK k;
   const bool ident = a.act == NGPDE_ACT_IDENTITY;
   k.t.x = nullptr; k.t.wt = a.wt; k.t.dy = nullptr; k.t.yz = nullptr; k.t.alpha = nullptr; k.t.sched = g->by_t.sched; k.t.halo = g->by_t.halo;
@@ -1580,14 +1545,10 @@ int32_t launch_gat_node_bwd(const GatNodeBwd &a, hipStream_t stream) {
   NGPDE_GST_SET(k)
   NGPDE_GST_SET(k.t)
   NGPDE_GST_SET(k.s)
-  {
-    const char *fa = std::getenv("NGPDE_DEBUG_FORCE_ABORT");
-    if (fa && fa[0] == '1') hipLaunchKernelGGL(gat_set_word_kernel, dim3(1), dim3(64), 0, stream, k.y.abort_word, 1u);
-  }
   k.n_steps = a.n_steps; k.S = a.S; k.xs = a.xs; k.yz = ident ? nullptr : a.yz; k.alpha = a.alpha; k.duT = a.duT; k.lam = a.lam;
   k.ubar = a.ubar; k.dzbuf = a.dzbuf; k.dscore = a.dscore; k.slab_db = a.slab_db; k.row_elems = (size_t)g->n_nodes * GD;
   k.alpha_elems = (size_t)std::max<int64_t>(g->n_edges, 1) * a.heads; k.dscore_elems = gat_node_dscore_elems(g); k.cb = a.cb;
-  k.n_members = a.n_members; k.flag_stride = (size_t)ps.n_tiles * 32; k.xs_stride = a.xs_stride; k.yz_stride = a.yz_stride;
+  k.n_members = a.n_members; k.flag_stride = sync_slot_stride(ps.n_tiles); k.xs_stride = a.xs_stride; k.yz_stride = a.yz_stride;
   k.alpha_stride = a.alpha_stride; k.dal_stride = (size_t)g->n_nodes * a.heads;
   NGPDE_REQUIRE(ident || a.yz, NGPDE_ERR_INVALID_ARGUMENT, "persistent GAT adjoint: the saved y / z rows are missing");
   const dim3 grid(ps.n_tiles), block(kThreads);
@@ -1606,7 +1567,7 @@ int32_t launch_gat_node_bwd(const GatNodeBwd &a, hipStream_t stream) {
   }
 #undef NGPDE_GN_LAUNCH
   NGPDE_LAUNCH_CHECK("gat_node_bwd_persistent_kernel");
-  hipLaunchKernelGGL(gat_latch_fault_kernel, dim3(1), dim3(64), 0, stream, k.y.abort_word, ps.fault);
+  if ((st = turn.latch())) return st;
   hipLaunchKernelGGL(gat_layer_reduce_kernel, dim3(67), dim3(1024), 0, stream, a.slab_dw, ps.n_tiles, a.slab_db, ps.n_tiles, a.slab_u, a.dwt,
                      a.db, a.da);
   NGPDE_LAUNCH_CHECK("gat_layer_reduce_kernel");

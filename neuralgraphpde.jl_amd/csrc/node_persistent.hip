@@ -26,7 +26,6 @@
 //
 // Arithmetic is that of the pre-scaled replayed plan (gcn_fused.hip, PRE = true) operation for operation: same aggregation
 // order (slot bytes, then the own row), same fp32 MFMA products, same stage combinations in the same order.
-#include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <cstdlib>
@@ -38,6 +37,7 @@
 #include "device_utils.h"
 #include "gcn_tile.h"
 #include "persistent_mem.h"
+#include "persistent_sync.h"
 
 namespace ngpde {
 
@@ -50,8 +50,6 @@ constexpr int kXhF = (kHaloCap + 1) * PD;   // halo region (floats), +1: the all
 constexpr int kTileF = kTM * PG::TS;        // one 32-row MFMA operand / result tile
 constexpr int kWF = PD * PG::TS;            // one transposed weight matrix
 constexpr int kMaxTileRounds = 8;            // tile rounds: at most this many tiles per workgroup
-constexpr int kNbrStride = 64;              // wait-list stride per tile; at most 63 entries (one lane of the polling wave each,
-                                            // lane 63 watches the abort word)
 
 #ifdef NGPDE_STAMPS
 // diagnostic build only (tools/stamps_persistent.py): shader-clock stamps of thread 0 at 8 points of the first g_pst_max phases
@@ -2880,16 +2878,16 @@ void node_persistent_free(NodePersist *ps) {
 }
 
 namespace {
-// fault |= abort word of the launch that just ran (sticky, read by ngpde_node_fault)
 // NGPDE_DEBUG_FORCE_ABORT=1 (tests only): the launch starts with its abort word set, i.e. every workgroup gives up at its first wait
 __global__ void set_word_kernel(unsigned *w, unsigned v) {
   if (threadIdx.x == 0) *w = v;
 }
+// fault |= abort word of the launch that just ran (sticky, read by ngpde_node_fault)
 __global__ void latch_fault_kernel(const unsigned *abort_word, unsigned *fault) {
   if (threadIdx.x == 0 && *abort_word != 0) *fault = 1u;
 }
 }  // namespace
-const unsigned *node_persistent_abort_word(const NodePersist *ps) { return ps->sync ? ps->sync + (size_t)ps->n_tiles * 64 : nullptr; }
+const unsigned *node_persistent_abort_word(const NodePersist *ps) { return ps->sync ? sync_abort_word(ps->sync, ps->n_tiles) : nullptr; }
 namespace {
 // of: the plan's own-first tables (forward only, dir 0), or NULL
 TileMeta make_meta(const Csr &c, const NodePersist &ps, int dir, const OwnFirst *of = nullptr) {
@@ -2904,7 +2902,7 @@ TileMeta make_meta(const Csr &c, const NodePersist &ps, int dir, const OwnFirst 
   m.hub_halo = L.halo; m.hub_slots = L.slots; m.hub_rows = L.rows; m.hub_info = L.info; m.hub_long = L.longs; m.hub_sched = L.sched;
   m.hub_w = L.w;
   if (ps.hub) m.slot_w = nullptr;   // (the hub geometry reads its own weight lists)
-  m.flags = ps.sync; m.abort_word = ps.sync + (size_t)ps.n_tiles * 64; m.n_tiles = ps.n_tiles;   // [slot 0 | slot 1 | abort]
+  m.flags = ps.sync; m.abort_word = sync_abort_word(ps.sync, ps.n_tiles); m.n_tiles = ps.n_tiles;
   m.stats = ps.stats;
 #ifdef NGPDE_STAMPS
   m.stamps = g_pst_base; m.stamps_max = g_pst_max;
@@ -2937,16 +2935,27 @@ Turnstile &turnstile() {
 }
 }  // namespace
 
-int32_t PersistentTurn::enter(hipStream_t s) {
+int32_t PersistentTurn::enter(const NodePersist &p, hipStream_t s) {
+  ps = &p;
   stream = s;
   NGPDE_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16) return NGPDE_OK;
-  Turnstile &t = turnstile();
-  t.mu.lock();
-  held = true;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
-  if (cs == hipStreamCaptureStatusNone && t.used[dev]) NGPDE_HIP_CHECK(hipStreamWaitEvent(stream, t.last[dev], 0));
+  if (dev >= 0 && dev < 16) {
+    Turnstile &t = turnstile();
+    t.mu.lock();
+    held = true;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
+    if (cs == hipStreamCaptureStatusNone && t.used[dev]) NGPDE_HIP_CHECK(hipStreamWaitEvent(stream, t.last[dev], 0));
+  }
+  int32_t st;
+  if ((st = launch_zero(p.sync, p.sync_bytes, stream))) return st;
+  const char *fa = std::getenv("NGPDE_DEBUG_FORCE_ABORT");   // (read at every launch: the tests set it around one call)
+  if (fa && fa[0] == '1') hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(64), 0, stream, sync_abort_word(p.sync, p.n_tiles), 1u);
+  return NGPDE_OK;
+}
+int32_t PersistentTurn::latch() {
+  hipLaunchKernelGGL(latch_fault_kernel, dim3(1), dim3(64), 0, stream, sync_abort_word(ps->sync, ps->n_tiles), ps->fault);
+  NGPDE_LAUNCH_CHECK("latch_fault_kernel");
   return NGPDE_OK;
 }
 int32_t PersistentTurn::leave() {
@@ -2976,80 +2985,58 @@ int32_t launch_node_fwd_persistent(const NodePersistFwd &a, hipStream_t stream) 
   const NodePersist &ps = *a.ps;
   int32_t st;
   PersistentTurn turn;
-  if ((st = turn.enter(stream))) return st;
-  if ((st = launch_zero(ps.sync, ps.sync_bytes, stream))) return st;
+  if ((st = turn.enter(ps, stream))) return st;
   PFwdK k;
   k.m = make_meta(g->by_t, ps, 0, a.of);
-  {
-    const char *fa = std::getenv("NGPDE_DEBUG_FORCE_ABORT");
-    if (fa && fa[0] == '1') hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(64), 0, stream, k.m.abort_word, 1u);
-  }
   k.n_steps = a.n_steps; k.S = a.S; k.act = a.act; k.n_members = a.n_members;
   k.u_in = a.u_in; k.u_out = a.u_out; k.bufA = a.bufA; k.bufB = a.bufB;
   k.w1 = a.w1; k.b1 = a.b1; k.w2 = a.w2; k.b2 = a.b2;
   k.tape = a.tape; k.masks = a.masks; k.row_elems = a.row_elems; k.mask_bytes = a.mask_bytes;
-  k.flag_stride = (size_t)ps.n_tiles * 32;
+  k.flag_stride = sync_slot_stride(ps.n_tiles);
   k.pair_wgs = a.pair ? ps.pair_wgs : 0;
   k.cf = ps.coef;
   NGPDE_REQUIRE(!a.pair || (ps.pair_wgs > 0 && !a.interleave && a.n_members == 1), NGPDE_ERR_STATE, "tile-pair launch without its setup");
   k.k_tiles = a.k_tiles; k.state = a.state;
+  const auto launch = [&](auto kernel, dim3 grid) { launch_timed(kernel, grid, dim3(kThreads), 0, stream, a.ev_start, a.ev_stop, k); };
   if (a.k_tiles > 0) {   // tile rounds: K tiles per workgroup, state in memory
     NGPDE_REQUIRE(ps.pair_wgs > 0 && a.n_members == 1 && a.state, NGPDE_ERR_STATE, "tile-round launch without its setup");
     NGPDE_REQUIRE(a.k_tiles <= kMaxTileRounds, NGPDE_ERR_STATE, "tile rounds: at most %d tiles per workgroup", kMaxTileRounds);
     k.pair_wgs = ps.pair_wgs; k.ztape = a.ztape;
     if ((st = launch_zero(a.state + a.row_elems, 6 * a.row_elems * sizeof(float), stream))) return st;   // k_0 .. k_5 start from zero
-    const dim3 gridk(ps.pair_wgs), blockk(kThreads);
+    const dim3 gridk(ps.pair_wgs);
     NGPDE_REQUIRE(!k.m.slot_w || a.k_tiles <= kMaxTileRoundsW, NGPDE_ERR_STATE, "weighted tile rounds: at most %d tiles per workgroup", kMaxTileRoundsW);
     // unweighted: the pipelined kernel; weighted: the plain tile-round kernel (the slot weights leave no LDS for the pipeline)
-#define NGPDE_PFK_LAUNCH(AA, TT)                                                                                                  \
-    if (!k.m.slot_w) {                                                                                                            \
-      if (a.ev_start) hipExtLaunchKernelGGL((node_fwd_persistentKP_kernel<AA, TT>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
-      else hipLaunchKernelGGL((node_fwd_persistentKP_kernel<AA, TT>), gridk, blockk, 0, stream, k);                                \
-    } else if (a.ev_start) hipExtLaunchKernelGGL((node_fwd_persistentK_kernel<AA, TT>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
-    else hipLaunchKernelGGL((node_fwd_persistentK_kernel<AA, TT>), gridk, blockk, 0, stream, k);
+#define NGPDE_PFK_LAUNCH(AA, TT) \
+    launch(k.m.slot_w ? node_fwd_persistentK_kernel<AA, TT> : node_fwd_persistentKP_kernel<AA, TT>, gridk);
     if (a.tape && a.act == NGPDE_ACT_RELU) { NGPDE_PFK_LAUNCH(NGPDE_ACT_RELU, true) }
     else if (a.tape) { NGPDE_PFK_LAUNCH(-1, true) }
     else if (a.act == NGPDE_ACT_RELU) { NGPDE_PFK_LAUNCH(NGPDE_ACT_RELU, false) }
     else { NGPDE_PFK_LAUNCH(-1, false) }
 #undef NGPDE_PFK_LAUNCH
     NGPDE_LAUNCH_CHECK("node_fwd_persistentK_kernel");
-    if (!a.no_latch) hipLaunchKernelGGL(latch_fault_kernel, dim3(1), dim3(64), 0, stream, k.m.abort_word, ps.fault);
-    NGPDE_LAUNCH_CHECK("latch_fault_kernel");
+    if (!a.no_latch && (st = turn.latch())) return st;
     return turn.leave();
   }
   NGPDE_REQUIRE(!k.m.slot_w || (!a.pair && !a.interleave && a.n_members == 1), NGPDE_ERR_STATE,
                 "weighted graphs: one tile per workgroup or tile rounds, one member");
-  const dim3 grid(a.pair ? ps.pair_wgs : ps.n_tiles), block(kThreads);
+  const dim3 grid(a.pair ? ps.pair_wgs : ps.n_tiles);
   if (ps.hub) {   // hub geometry: one tile per workgroup and CU
     NGPDE_REQUIRE(!a.pair && !a.interleave, NGPDE_ERR_STATE, "hub geometry: one tile per workgroup, the members of a batch one after the other");
     k.ztape = a.ztape;
     NGPDE_REQUIRE(!a.tape || (a.act == NGPDE_ACT_RELU ? a.masks != nullptr : a.ztape != nullptr), NGPDE_ERR_INVALID_ARGUMENT,
                   "persistent forward with a tape needs the sign-bit masks (relu) or the pre-activation tape");
-#define NGPDE_PFH_LAUNCH(AA, TT)                                                                                                   \
-    if (a.ev_start) hipExtLaunchKernelGGL((node_fwd_persistent_kernel<AA, TT, false, true>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k); \
-    else hipLaunchKernelGGL((node_fwd_persistent_kernel<AA, TT, false, true>), grid, block, 0, stream, k);
-    if (a.tape && a.act == NGPDE_ACT_RELU) { NGPDE_PFH_LAUNCH(NGPDE_ACT_RELU, true) }
-    else if (a.tape) { NGPDE_PFH_LAUNCH(-1, true) }
-    else if (a.act == NGPDE_ACT_RELU) { NGPDE_PFH_LAUNCH(NGPDE_ACT_RELU, false) }
-    else { NGPDE_PFH_LAUNCH(-1, false) }
-#undef NGPDE_PFH_LAUNCH
+    if (a.tape && a.act == NGPDE_ACT_RELU) launch(node_fwd_persistent_kernel<NGPDE_ACT_RELU, true, false, true>, grid);
+    else if (a.tape) launch(node_fwd_persistent_kernel<-1, true, false, true>, grid);
+    else if (a.act == NGPDE_ACT_RELU) launch(node_fwd_persistent_kernel<NGPDE_ACT_RELU, false, false, true>, grid);
+    else launch(node_fwd_persistent_kernel<-1, false, false, true>, grid);
     NGPDE_LAUNCH_CHECK("node_fwd_persistent_kernel (hub geometry)");
-    if (!a.no_latch) hipLaunchKernelGGL(latch_fault_kernel, dim3(1), dim3(64), 0, stream, k.m.abort_word, ps.fault);
-    NGPDE_LAUNCH_CHECK("latch_fault_kernel");
+    if (!a.no_latch && (st = turn.latch())) return st;
     return turn.leave();
   }
-#define NGPDE_PF_LAUNCH(AA, TT)                                                                                              \
-  if (k.m.slot_w) {                                                                                                          \
-    if (a.ev_start) hipExtLaunchKernelGGL((node_fwd_persistent_kernel<AA, TT, true>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k); \
-    else hipLaunchKernelGGL((node_fwd_persistent_kernel<AA, TT, true>), grid, block, 0, stream, k);                           \
-  } else if (a.pair) {                                                                                                              \
-    if (a.ev_start) hipExtLaunchKernelGGL((node_fwd_persistent2_kernel<AA, TT, true>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k); \
-    else hipLaunchKernelGGL((node_fwd_persistent2_kernel<AA, TT, true>), grid, block, 0, stream, k);                          \
-  } else if (a.interleave) {                                                                                                 \
-    if (a.ev_start) hipExtLaunchKernelGGL((node_fwd_persistent2_kernel<AA, TT, false>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k); \
-    else hipLaunchKernelGGL((node_fwd_persistent2_kernel<AA, TT, false>), grid, block, 0, stream, k);                         \
-  } else if (a.ev_start) hipExtLaunchKernelGGL((node_fwd_persistent_kernel<AA, TT>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k); \
-  else hipLaunchKernelGGL((node_fwd_persistent_kernel<AA, TT>), grid, block, 0, stream, k);
+#define NGPDE_PF_LAUNCH(AA, TT)                                                                                  \
+  launch(k.m.slot_w ? node_fwd_persistent_kernel<AA, TT, true>                                                   \
+         : a.pair ? node_fwd_persistent2_kernel<AA, TT, true>                                                    \
+         : a.interleave ? node_fwd_persistent2_kernel<AA, TT, false> : node_fwd_persistent_kernel<AA, TT>, grid);
   k.ztape = a.ztape;
   if (a.tape && a.act == NGPDE_ACT_RELU) {
     NGPDE_REQUIRE(a.masks != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "persistent forward with a relu tape needs the sign-bit masks");
@@ -3065,8 +3052,7 @@ int32_t launch_node_fwd_persistent(const NodePersistFwd &a, hipStream_t stream) 
   }
 #undef NGPDE_PF_LAUNCH
   NGPDE_LAUNCH_CHECK("node_fwd_persistent_kernel");
-  if (!a.no_latch) hipLaunchKernelGGL(latch_fault_kernel, dim3(1), dim3(64), 0, stream, k.m.abort_word, ps.fault);
-  NGPDE_LAUNCH_CHECK("latch_fault_kernel");
+  if (!a.no_latch && (st = turn.latch())) return st;
   return turn.leave();
 }
 
@@ -3075,8 +3061,7 @@ int32_t launch_node_bwd_persistent(const NodePersistBwd &a, hipStream_t stream) 
   const NodePersist &ps = *a.ps;
   int32_t st;
   PersistentTurn turn;
-  if ((st = turn.enter(stream))) return st;
-  if ((st = launch_zero(ps.sync, ps.sync_bytes, stream))) return st;
+  if ((st = turn.enter(ps, stream))) return st;
   PBwdK k;
   k.m = make_meta(g->by_s, ps, 1);
   k.n_steps = a.n_steps; k.S = a.S; k.n_members = a.n_members; k.act = a.act; k.ztape = a.ztape;
@@ -3084,73 +3069,51 @@ int32_t launch_node_bwd_persistent(const NodePersistBwd &a, hipStream_t stream) 
   k.tape = a.tape; k.masks = a.masks; k.row_elems = a.row_elems; k.mask_bytes = a.mask_bytes;
   k.slab_dw1 = a.slab_dw1; k.slab_db1 = a.slab_db1; k.slab_dw2 = a.slab_dw2; k.slab_db2 = a.slab_db2;
   k.cb = ps.coef + 42;
-  k.flag_stride = (size_t)ps.n_tiles * 32;
+  k.flag_stride = sync_slot_stride(ps.n_tiles);
   k.pair_wgs = a.pair ? ps.pair_wgs : 0;
   k.ubar = a.ubar;
   NGPDE_REQUIRE(!a.pair || (ps.pair_wgs > 0 && !a.interleave && a.n_members == 1 && a.act == NGPDE_ACT_RELU), NGPDE_ERR_STATE,
                 "tile-pair launch without its setup");
   k.k_tiles = a.k_tiles;
+  const auto launch = [&](auto kernel, dim3 grid) { launch_timed(kernel, grid, dim3(kThreads), 0, stream, a.ev_start, a.ev_stop, k); };
   if (a.k_tiles > 0) {   // tile rounds
     NGPDE_REQUIRE(ps.pair_wgs > 0 && a.n_members == 1 && a.ubar, NGPDE_ERR_STATE, "tile-round launch without its setup");
     NGPDE_REQUIRE(a.k_tiles <= kMaxTileRounds, NGPDE_ERR_STATE, "tile rounds: at most %d tiles per workgroup", kMaxTileRounds);
     NGPDE_REQUIRE(a.act == NGPDE_ACT_RELU || a.ztape, NGPDE_ERR_INVALID_ARGUMENT, "persistent adjoint: activations other than relu need the saved pre-activations");
     k.pair_wgs = ps.pair_wgs;
     if ((st = launch_zero(a.ubar, 5 * a.row_elems * sizeof(float), stream))) return st;   // the stage adjoints start from zero
-    const dim3 gridk(ps.pair_wgs), blockk(kThreads);
+    const dim3 gridk(ps.pair_wgs);
     NGPDE_REQUIRE(!k.m.slot_w || a.k_tiles <= kMaxTileRoundsW, NGPDE_ERR_STATE, "weighted tile rounds: at most %d tiles per workgroup", kMaxTileRoundsW);
-#define NGPDE_PBK_LAUNCH(AA)                                                                                                      \
-    if (!k.m.slot_w) {                                                                                                            \
-      if (a.ev_start) hipExtLaunchKernelGGL((node_bwd_persistentKP_kernel<AA>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
-      else hipLaunchKernelGGL((node_bwd_persistentKP_kernel<AA>), gridk, blockk, 0, stream, k);                                    \
-    } else if (a.ev_start) hipExtLaunchKernelGGL((node_bwd_persistentK_kernel<AA>), gridk, blockk, 0, stream, a.ev_start, a.ev_stop, 0, k);  \
-    else hipLaunchKernelGGL((node_bwd_persistentK_kernel<AA>), gridk, blockk, 0, stream, k);
-    if (a.act == NGPDE_ACT_RELU) { NGPDE_PBK_LAUNCH(NGPDE_ACT_RELU) }
-    else { NGPDE_PBK_LAUNCH(-1) }
-#undef NGPDE_PBK_LAUNCH
+    if (a.act == NGPDE_ACT_RELU) launch(k.m.slot_w ? node_bwd_persistentK_kernel<NGPDE_ACT_RELU> : node_bwd_persistentKP_kernel<NGPDE_ACT_RELU>, gridk);
+    else launch(k.m.slot_w ? node_bwd_persistentK_kernel<-1> : node_bwd_persistentKP_kernel<-1>, gridk);
     NGPDE_LAUNCH_CHECK("node_bwd_persistentK_kernel");
-    if (!a.no_latch) hipLaunchKernelGGL(latch_fault_kernel, dim3(1), dim3(64), 0, stream, k.m.abort_word, ps.fault);
-    NGPDE_LAUNCH_CHECK("latch_fault_kernel");
+    if (!a.no_latch && (st = turn.latch())) return st;
     return turn.leave();
   }
   NGPDE_REQUIRE(!k.m.slot_w || (!a.pair && !a.interleave && a.n_members == 1), NGPDE_ERR_STATE,
                 "weighted graphs: one tile per workgroup or tile rounds, one member");
-  const dim3 grid(a.pair ? ps.pair_wgs : ps.n_tiles), block(kThreads);
+  const dim3 grid(a.pair ? ps.pair_wgs : ps.n_tiles);
   if (ps.hub) {
     NGPDE_REQUIRE(!a.pair && !a.interleave, NGPDE_ERR_STATE, "hub geometry: one tile per workgroup, the members of a batch one after the other");
     NGPDE_REQUIRE(a.act == NGPDE_ACT_RELU || a.ztape, NGPDE_ERR_INVALID_ARGUMENT, "persistent adjoint: activations other than relu need the saved pre-activations");
-    if (a.act == NGPDE_ACT_RELU) {
-      if (a.ev_start) hipExtLaunchKernelGGL((node_bwd_persistent_kernel<NGPDE_ACT_RELU, false, true>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k);
-      else hipLaunchKernelGGL((node_bwd_persistent_kernel<NGPDE_ACT_RELU, false, true>), grid, block, 0, stream, k);
-    } else {
-      if (a.ev_start) hipExtLaunchKernelGGL((node_bwd_persistent_kernel<-1, false, true>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k);
-      else hipLaunchKernelGGL((node_bwd_persistent_kernel<-1, false, true>), grid, block, 0, stream, k);
-    }
+    launch(a.act == NGPDE_ACT_RELU ? node_bwd_persistent_kernel<NGPDE_ACT_RELU, false, true> : node_bwd_persistent_kernel<-1, false, true>, grid);
   } else if (k.m.slot_w) {
     NGPDE_REQUIRE(a.act == NGPDE_ACT_RELU || a.ztape, NGPDE_ERR_INVALID_ARGUMENT, "persistent adjoint: activations other than relu need the saved pre-activations");
-    if (a.act == NGPDE_ACT_RELU) {
-      if (a.ev_start) hipExtLaunchKernelGGL((node_bwd_persistent_kernel<NGPDE_ACT_RELU, true>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k);
-      else hipLaunchKernelGGL((node_bwd_persistent_kernel<NGPDE_ACT_RELU, true>), grid, block, 0, stream, k);
-    } else {
-      if (a.ev_start) hipExtLaunchKernelGGL((node_bwd_persistent_kernel<-1, true>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k);
-      else hipLaunchKernelGGL((node_bwd_persistent_kernel<-1, true>), grid, block, 0, stream, k);
-    }
+    launch(a.act == NGPDE_ACT_RELU ? node_bwd_persistent_kernel<NGPDE_ACT_RELU, true> : node_bwd_persistent_kernel<-1, true>, grid);
   } else if (a.pair) {
     NGPDE_REQUIRE(a.ubar != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "tile-pair persistent adjoint without its stage-adjoint scratch");
-    if (a.ev_start) hipExtLaunchKernelGGL(node_bwd_persistent2_kernel<true>, grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k);
-    else hipLaunchKernelGGL(node_bwd_persistent2_kernel<true>, grid, block, 0, stream, k);
+    launch(node_bwd_persistent2_kernel<true>, grid);
   } else if (a.interleave) {
     NGPDE_REQUIRE(a.ubar != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "interleaved persistent adjoint without its stage-adjoint scratch");
-    if (a.ev_start) hipExtLaunchKernelGGL(node_bwd_persistent2_kernel<false>, grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k);
-    else hipLaunchKernelGGL(node_bwd_persistent2_kernel<false>, grid, block, 0, stream, k);
+    launch(node_bwd_persistent2_kernel<false>, grid);
   } else if (a.act != NGPDE_ACT_RELU) {
     NGPDE_REQUIRE(a.ztape != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "persistent adjoint: activations other than relu need the saved pre-activations");
-    if (a.ev_start) hipExtLaunchKernelGGL(node_bwd_persistent_kernel<-1>, grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k);
-    else hipLaunchKernelGGL(node_bwd_persistent_kernel<-1>, grid, block, 0, stream, k);
-  } else if (a.ev_start) hipExtLaunchKernelGGL(node_bwd_persistent_kernel<NGPDE_ACT_RELU>, grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k);
-  else hipLaunchKernelGGL(node_bwd_persistent_kernel<NGPDE_ACT_RELU>, grid, block, 0, stream, k);
+    launch(node_bwd_persistent_kernel<-1>, grid);
+  } else {
+    launch(node_bwd_persistent_kernel<NGPDE_ACT_RELU>, grid);
+  }
   NGPDE_LAUNCH_CHECK("node_bwd_persistent_kernel");
-  if (!a.no_latch) hipLaunchKernelGGL(latch_fault_kernel, dim3(1), dim3(64), 0, stream, k.m.abort_word, ps.fault);
-  NGPDE_LAUNCH_CHECK("latch_fault_kernel");
+  if (!a.no_latch && (st = turn.latch())) return st;
   return turn.leave();
 }
 

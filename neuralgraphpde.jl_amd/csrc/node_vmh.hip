@@ -28,7 +28,6 @@
 //     the second half of phase ph - 1 and at once the first half of phase ph.
 // State width 1 (a scalar field, as in the tutorial), positions of 1-3 coordinates, MLPs of 2-4 layers up to 64 wide with
 // identity output layers; up to kVmhMaxTurns tiles per resident workgroup.  Anything else keeps the generic solver.
-#include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <cstdlib>
@@ -40,6 +39,7 @@
 #include "common.h"
 #include "device_utils.h"
 #include "persistent_mem.h"
+#include "persistent_sync.h"
 
 namespace ngpde {
 
@@ -367,10 +367,6 @@ __device__ __forceinline__ void vmh_publish(const VmhMeta &m, const VCtx &c, int
   if (whole_tile && c.tid == 1) __hip_atomic_store(m.flags + 32 * (c.wg + 1), (unsigned)ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ float4 ld4_nt(const float *p) {   // a tape row: read once
-  const f4v v = __builtin_nontemporal_load(reinterpret_cast<const NGPDE_GLOBAL_AS f4v *>(reinterpret_cast<uintptr_t>(p)));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
 __device__ __forceinline__ float ld_sc1(const float *p) {
   return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
@@ -810,14 +806,14 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_bwd_kernel(const VmhBwdK p) {
     const int n_mt = (m.phi_dout[l] + 15) >> 4;
     const float *yrow = p.tape_phi + (((size_t)(l + 1) * m.evals + ev) * E + pe1) * VW + 4 * kq;
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) y[mt] = (valid1 && mt < n_mt) ? ld4_nt(yrow + 16 * mt) : f4_zero();
+    for (int mt = 0; mt < 4; ++mt) y[mt] = (valid1 && mt < n_mt) ? ld4_stream_g(yrow + 16 * mt, 0) : f4_zero();
   };
   auto fetch_phase = [&](size_t ev) {
 #pragma unroll
     for (int l = 0; l < kVmhMaxL - 1; ++l) {
       yg[l] = f4_zero();
       if (l + 1 < m.n_gam && c.row_valid && 4 * c.q < 16 * ((m.gam_dout[l] + 15) >> 4))
-        yg[l] = ld4_nt(p.tape_gam + (((size_t)(l + 1) * m.evals + ev) * N + c.node) * VW + 4 * c.q);
+        yg[l] = ld4_stream_g(p.tape_gam + (((size_t)(l + 1) * m.evals + ev) * N + c.node) * VW + 4 * c.q, 0);
     }
     if (one_round && m.n_phi >= 2) fetch_phi(m.n_phi - 2, ev, ytop);
   };
@@ -890,7 +886,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_bwd_kernel(const VmhBwdK p) {
     const int n_mt = (m.phi_dout[l] + 15) >> 4;
     const float *yrow = p.tape_phi + (((size_t)(l + 1) * m.evals + ev) * E + pe) * VW + 4 * kq;
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) yall[l][mt] = (valid && mt < n_mt) ? ld4_nt(yrow + 16 * mt) : f4_zero();
+    for (int mt = 0; mt < 4; ++mt) yall[l][mt] = (valid && mt < n_mt) ? ld4_stream_g(yrow + 16 * mt, 0) : f4_zero();
   };
   for (int ph = 1; ph <= n_sweeps && ok; ++ph) {
     {
@@ -1141,12 +1137,6 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_bwd_kernel(const VmhBwdK p) {
   if (my_node >= 0) p.lam[my_node] = ok ? lam : __int_as_float(0x7fc00000);
 }
 
-__global__ void vmh_set_word_kernel(unsigned *w, unsigned v) {
-  if (threadIdx.x == 0) *w = v;
-}
-__global__ void vmh_latch_fault_kernel(const unsigned *abort_word, unsigned *fault) {
-  if (threadIdx.x == 0 && *abort_word != 0) *fault = 1u;
-}
 __global__ void vmh_copy_block_kernel(const float *src, int sp, float *dst, int dp, int rows, int cols) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx < rows * cols) dst[(idx / cols) * dp + idx % cols] = src[(idx / cols) * sp + idx % cols];
@@ -1246,7 +1236,7 @@ static void fill_meta(VmhMeta &m, const VmhLaunch &a) {
   m.rowptr_s = g->by_s.rowptr; m.xpos_s = g->by_s.xpos;
   m.nbr = a.ps->nbr;
   m.n_tiles = g->n_sched / kTileRows;
-  m.flags = a.ps->sync; m.abort_word = a.ps->sync + (size_t)(2 * m.n_tiles) * 32;
+  m.flags = a.ps->sync; m.abort_word = sync_abort_word(a.ps->sync, a.ps->n_tiles);
   m.n_nodes = (int)g->n_nodes; m.pos = a.pos; m.pd = a.shape.pd; m.aggr = a.shape.aggr;
   m.n_phi = a.shape.n_phi; m.n_gam = a.shape.n_gam;
   for (int l = 0; l < kVmhMaxL; ++l) {
@@ -1269,14 +1259,9 @@ int32_t launch_node_vmh_fwd(const VmhLaunch &a, hipStream_t stream) {
   const NodePersist &ps = *a.ps;
   int32_t st;
   PersistentTurn turn;
-  if ((st = turn.enter(stream))) return st;
-  if ((st = launch_zero(ps.sync, ps.sync_bytes, stream))) return st;
+  if ((st = turn.enter(ps, stream))) return st;
   VmhFwdK k;
   fill_meta(k.m, a);
-  {
-    const char *fa = std::getenv("NGPDE_DEBUG_FORCE_ABORT");
-    if (fa && fa[0] == '1') hipLaunchKernelGGL(vmh_set_word_kernel, dim3(1), dim3(64), 0, stream, k.m.abort_word, 1u);
-  }
   k.n_steps = a.n_steps; k.S = a.S; k.u_in = a.u_in; k.u_out = a.u_out; k.x0 = a.x0; k.x1 = a.x1;
   k.save = a.save; k.save_every = a.save_every; k.save_off = a.save_off;
   k.state = a.state;
@@ -1293,8 +1278,7 @@ int32_t launch_node_vmh_fwd(const VmhLaunch &a, hipStream_t stream) {
     hipLaunchKernelGGL(node_vmh_fwd_kernel<false>, dim3(geo.grid), dim3(VT), geo.lds, stream, k);
   }
   NGPDE_LAUNCH_CHECK("node_vmh_fwd_kernel");
-  hipLaunchKernelGGL(vmh_latch_fault_kernel, dim3(1), dim3(64), 0, stream, k.m.abort_word, ps.fault);
-  NGPDE_LAUNCH_CHECK("latch_fault_kernel");
+  if ((st = turn.latch())) return st;
   return turn.leave();
 }
 
@@ -1302,8 +1286,7 @@ int32_t launch_node_vmh_bwd(const VmhLaunch &a, hipStream_t stream) {
   const NodePersist &ps = *a.ps;
   int32_t st;
   PersistentTurn turn;
-  if ((st = turn.enter(stream))) return st;
-  if ((st = launch_zero(ps.sync, ps.sync_bytes, stream))) return st;
+  if ((st = turn.enter(ps, stream))) return st;
   VmhBwdK k;
   fill_meta(k.m, a);
   k.dsave = a.dsave; k.save_every = a.save_every; k.save_off = a.save_off;
@@ -1321,8 +1304,7 @@ int32_t launch_node_vmh_bwd(const VmhLaunch &a, hipStream_t stream) {
     hipLaunchKernelGGL(node_vmh_bwd_kernel<false>, dim3(geo.grid), dim3(VT), geo.lds, stream, k);
   }
   NGPDE_LAUNCH_CHECK("node_vmh_bwd_kernel");
-  hipLaunchKernelGGL(vmh_latch_fault_kernel, dim3(1), dim3(64), 0, stream, k.m.abort_word, ps.fault);
-  NGPDE_LAUNCH_CHECK("latch_fault_kernel");
+  if ((st = turn.latch())) return st;
   return turn.leave();
 }
 
