@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "stamps.h"
 
 namespace ngpde {
 
@@ -750,6 +751,7 @@ struct StreamOut {
   int din_all, dout, act;
   const float *wt, *bias;
   float *y, *save_z;
+  NGPDE_STAMP_FIELD   // (dense_pair_fwd_kernel: a's)
 };
 
 __device__ __forceinline__ void load_wfrag(const float *__restrict__ wt, int dout, int k0, int col, int kq, f32x4 (&breg)[4]) {
@@ -901,19 +903,8 @@ __device__ __forceinline__ void stream_epilogue(const StreamOut &o, int n_narrow
 // Both kernels double-buffer the input images: the DMA of tile t + 1 is issued at the top of tile t into the buffer tile t - 1
 // left behind, and collected at the top of tile t + 1 -- a whole tile of arithmetic later.
 constexpr int kPairTR = 64;
-#ifdef NGPDE_STAMPS
-extern unsigned long long *g_pair_stamps;
-unsigned long long *g_pair_stamps = nullptr;   // diagnostic build only (tools/stamps_pair.py): [n_blocks][16], the workgroup's 4th tile
-#define PAIR_STAMP(k) do { if (threadIdx.x == 0 && stamps && it == 3) stamps[(size_t)blockIdx.x * 16 + (k)] = clock64(); } while (0)
-#else
-#define PAIR_STAMP(k)
-#endif
 __global__ __launch_bounds__(kStreamThreads, 4) void dense_pair_fwd_kernel(int64_t n, int n_tiles, const float *__restrict__ x,
-                                                                           const StreamOut a, const StreamOut b
-#ifdef NGPDE_STAMPS
-                                                                           , unsigned long long *stamps
-#endif
-                                                                           ) {
+                                                                           const StreamOut a, const StreamOut b) {
   constexpr int TR = kPairTR;
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   // dyn: two buffers [TR][OS2], each the X image of a tile, then each output on its way out
@@ -947,35 +938,35 @@ __global__ __launch_bounds__(kStreamThreads, 4) void dense_pair_fwd_kernel(int64
   for (; t < n_tiles; t += G, ++it) {
     const int64_t row0 = (int64_t)t * TR;
     float *cur = dyn + (it & 1) * (TR * OS2), *nxt = dyn + ((it + 1) & 1) * (TR * OS2);
-    PAIR_STAMP(0);
+    if (it == 3) NGPDE_STAMP(a.stamps, 16, 0, memtime);
     if (it == 0) wait_vmcnt0();
     __syncthreads();   // this tile's image has landed (collected below, a tile ago); the previous tile's outputs have left LDS
-    PAIR_STAMP(1);
+    if (it == 3) NGPDE_STAMP(a.stamps, 16, 1, memtime);
     // narrow features of this tile's rows, then the next tile's image
     const float xv = narrow_fetch(nq, row0 + nr, n);
     f32x4 acca[TR / 32], accb[TR / 32];
 #pragma unroll
     for (int rt = 0; rt < TR / 32; ++rt) acca[rt] = accb[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     products_beside_dma<TR, 1, 2>(cur, nxt, 0, t + G < n_tiles, x, nullptr, (int64_t)(t + G) * TR, n, wave, lane, half, wa, wb, acca, accb);
-    PAIR_STAMP(2);
+    if (it == 3) NGPDE_STAMP(a.stamps, 16, 2, memtime);
     // collect the next tile's image HERE, behind the products and before this tile's stores are issued: a wait at the top of the
     // next tile would also wait for those stores (vmcnt counts them) -- a full store latency per tile
     wait_vmcnt0();
-    PAIR_STAMP(3);
+    if (it == 3) NGPDE_STAMP(a.stamps, 16, 3, memtime);
     xn[nr * kNarrowAll + nf] = xv;
     __syncthreads();
-    PAIR_STAMP(4);
+    if (it == 3) NGPDE_STAMP(a.stamps, 16, 4, memtime);
     stage_cols<TR>(cur, half, ct, lane, acca);
     __syncthreads();
-    PAIR_STAMP(5);
+    if (it == 3) NGPDE_STAMP(a.stamps, 16, 5, memtime);
     stream_epilogue<TR, false>(a, na, xn, wn, cur, row0, n, tid, ba);
-    PAIR_STAMP(6);
+    if (it == 3) NGPDE_STAMP(a.stamps, 16, 6, memtime);
     __syncthreads();
     stage_cols<TR>(cur, half, ct, lane, accb);
     __syncthreads();
-    PAIR_STAMP(7);
+    if (it == 3) NGPDE_STAMP(a.stamps, 16, 7, memtime);
     stream_epilogue<TR, false>(b, nb, xn + 4, wn + kNarrow * 64, cur, row0, n, tid, bb);
-    PAIR_STAMP(8);
+    if (it == 3) NGPDE_STAMP(a.stamps, 16, 8, memtime);
   }
 }
 
@@ -1548,11 +1539,8 @@ int32_t launch_dense_pair_fwd(int64_t n, const SegTable &ta, int dina, int douta
   static int cap = 0;   // resident workgroups of this kernel on this device (one occupancy query per process)
   if (!cap) cap = stream_grid(reinterpret_cast<const void *>(dense_pair_fwd_kernel), lds, 1 << 30);
   const int grid = std::min(n_tiles, cap);
-#ifdef NGPDE_STAMPS
-  hipLaunchKernelGGL(dense_pair_fwd_kernel, dim3((unsigned)grid), dim3(kStreamThreads), lds, stream, n, n_tiles, ta.ptr[0], a, b, g_pair_stamps);
-#else
+  NGPDE_STAMP_SET(a, kStampPair, 0);
   hipLaunchKernelGGL(dense_pair_fwd_kernel, dim3((unsigned)grid), dim3(kStreamThreads), lds, stream, n, n_tiles, ta.ptr[0], a, b);
-#endif
   NGPDE_LAUNCH_CHECK("dense_pair_fwd_kernel");
   return NGPDE_OK;
 }
@@ -1587,10 +1575,3 @@ int32_t launch_dense_chain_fwd(int64_t n, const SegTable &t1, int din1, int act1
 }
 
 }  // namespace ngpde
-
-#ifdef NGPDE_STAMPS
-extern "C" int32_t ngpde_debug_set_pair_stamps(unsigned long long *buf) {
-  ngpde::g_pair_stamps = buf;
-  return 0;
-}
-#endif

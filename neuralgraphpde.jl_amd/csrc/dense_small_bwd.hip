@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "stamps.h"
 
 namespace ngpde {
 
@@ -30,20 +31,9 @@ constexpr int kT = 256, kR = 64, kW = 64;
 constexpr int kSZ = kW + 4;    // dz and W tiles: 16-byte rows, conflict-free row reads (16 rows x one 16-byte chunk)
 constexpr int kSX = kW + 16;   // X tile: read only transposed (rows 4 s + kq, 16 consecutive columns): stride 80 spreads kq over the banks
 
-// diagnostic build only (tools/stamps_small_dense.py): wall-clock stamps (100 MHz) of thread 0 of every workgroup, [n_blocks][8]
-#ifdef NGPDE_STAMPS
-unsigned long long *g_small_stamps = nullptr;
-#define NGPDE_SST_FIELD unsigned long long *stamps;
-#define NGPDE_SST(p, k) do { if (threadIdx.x == 0 && (p).stamps) (p).stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define NGPDE_SST_SET(kk) kk.stamps = g_small_stamps;
-#else
-#define NGPDE_SST_FIELD
-#define NGPDE_SST(p, k)
-#define NGPDE_SST_SET(kk)
-#endif
 
 struct SmallBwdK {
-  NGPDE_SST_FIELD
+  NGPDE_STAMP_FIELD
   int64_t n;
   int n_tiles, din, dout, act;
   SegTable segs;
@@ -115,7 +105,7 @@ __global__ __launch_bounds__(kT) void dense_small_bwd_kernel(const SmallBwdK p) 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i16 = lane & 15, kq = lane >> 4;
   const int din = p.din, dout = p.dout;
-  NGPDE_SST(p, 0);
+  NGPDE_STAMP(p.stamps, 8, 0, memrealtime);
   // W for the input pullback: B[k = o][j = in] = wt[in][o]  ->  Bt[j = in][k = o] = wt[in][o], a straight (zero-padded) copy.  Its loads
   // go out here, the first tile's loads right behind them, and only then the LDS writes: one round trip for both (a W copy completed
   // first cost a second one: 4-5 us before the first product instead of 2.5)
@@ -193,7 +183,7 @@ __global__ __launch_bounds__(kT) void dense_small_bwd_kernel(const SmallBwdK p) 
     const int64_t row0 = (int64_t)tile * kR;
     if (tile != (int)blockIdx.x) load_tile(tile);
     if (p.z) { NGPDE_ACT_DISPATCH(p.act, dz16, dv, zv) }   // (rows / columns beyond the problem: dv = 0)
-    NGPDE_SST(p, 1);   // loads landed, dz formed
+    NGPDE_STAMP(p.stamps, 8, 1, memrealtime);   // loads landed, dz formed
     __syncthreads();   // the previous tile's products are done with the LDS tiles (and W is in LDS)
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
@@ -203,7 +193,7 @@ __global__ __launch_bounds__(kT) void dense_small_bwd_kernel(const SmallBwdK p) 
       ldsX[(rq + 4 * s) * kSX + c] = xv[s];
     }
     __syncthreads();
-    NGPDE_SST(p, 2);   // tiles in LDS
+    NGPDE_STAMP(p.stamps, 8, 2, memrealtime);   // tiles in LDS
     // ---- dX rows 16 wave .. + 15 = dz x W^T: contraction over the outputs
     {
       f32x4 acc[4];
@@ -232,7 +222,7 @@ __global__ __launch_bounds__(kT) void dense_small_bwd_kernel(const SmallBwdK p) 
         }
       }
     }
-    NGPDE_SST(p, 3);   // dX product + stores issued
+    NGPDE_STAMP(p.stamps, 8, 3, memrealtime);   // dX product + stores issued
     // ---- dW rows (input features) 16 wave .. + 15 += X^T dz: contraction over the tile's rows
 #pragma unroll
     for (int ks = 0; ks < kR / 4; ++ks) {
@@ -241,7 +231,7 @@ __global__ __launch_bounds__(kT) void dense_small_bwd_kernel(const SmallBwdK p) 
       for (int nt = 0; nt < 4; ++nt) accW[nt] = mfma16(a, ldsDZ[(4 * ks + kq) * kSZ + nt * 16 + i16], accW[nt]);
     }
   }
-  NGPDE_SST(p, 4);   // dW product
+  NGPDE_STAMP(p.stamps, 8, 4, memrealtime);   // dW product
   // ---- slab of this workgroup
   float *slab = p.partial + (size_t)blockIdx.x * (din + 1) * dout;
 #pragma unroll
@@ -256,7 +246,7 @@ __global__ __launch_bounds__(kT) void dense_small_bwd_kernel(const SmallBwdK p) 
   ldsDb[rq][c] = dbacc;
   __syncthreads();
   if (tid < kW && tid < dout) slab[(size_t)din * dout + tid] = (ldsDb[0][tid] + ldsDb[1][tid]) + (ldsDb[2][tid] + ldsDb[3][tid]);
-  NGPDE_SST(p, 5);   // slab stores issued
+  NGPDE_STAMP(p.stamps, 8, 5, memrealtime);   // slab stores issued
 }
 
 // ---- forward of the same shapes: y = act(X W + b) with the whole contraction in one pass -----------------------------------------
@@ -407,17 +397,10 @@ int32_t launch_dense_small_bwd(int64_t n, const SegTable &t, int din, int dout, 
   }
   for (int b = 0; b <= 4; ++b) k.grads.offset[b] = t.offset[b];
   k.wt = wt; k.z = (act == NGPDE_ACT_IDENTITY) ? nullptr : z; k.dy = dy; k.partial = slabs;
-  NGPDE_SST_SET(k)
+  NGPDE_STAMP_SET(k, kStampSmallDense, 0);
   hipLaunchKernelGGL(dense_small_bwd_kernel, dim3(grid), dim3(kT), 0, stream, k);
   NGPDE_LAUNCH_CHECK("dense_small_bwd_kernel");
   return launch_dense_weight_reduce(grid, din, dout, slabs, dwt, dbias, stream);
 }
 
 }  // namespace ngpde
-
-#ifdef NGPDE_STAMPS
-extern "C" int32_t ngpde_debug_set_small_dense_stamps(unsigned long long *dev_buf) {   // [n_blocks][8] or NULL
-  ngpde::g_small_stamps = dev_buf;
-  return NGPDE_OK;
-}
-#endif

@@ -17,7 +17,7 @@
 // (rows 4s .. 4s + 3 x 16 consecutive columns).  These launches are bound by instruction ISSUE on the SIMD (a wave's MFMAs, VALU
 // and waits are one in-order stream and two waves share a SIMD), not by memory: every LDS address of the product loops is a
 // register set up once per launch plus an immediate, and the reads of a product group are issued in the middle of the group before
-// (PairBwdAddr, stream_bwd_dw / stream_bwd_dx / pair_bwd_products; DESIGN 5.4, tools/stamps_pair_bwd.py).
+// (PairBwdAddr, stream_bwd_dw / stream_bwd_dx / pair_bwd_products; DESIGN 5.4, tools/stamps.py pair-bwd).
 // Per-workgroup dW / db slabs are summed by dense_weight_reduce_kernel in a fixed order: no atomics, reproducible.
 #include <algorithm>
 #include <cstdlib>
@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "stamps.h"
 
 namespace ngpde {
 
@@ -77,7 +78,7 @@ __device__ __forceinline__ void dma_x_tile(const float *x, uint32_t row0, uint32
 // (j, c) resp. kh and an immediate per m resp. rt.  Written as sw_addr(4 s + kq, ..) in the loop the compiler either keeps ~ 100 addresses
 // in registers across the tile loop or (behind an opaque zero, as both kernels did until round 5) recomputes them per slice: ~ 80 VALU
 // instructions per 10 MFMAs, and VALU issue does not overlap a wave's own MFMAs -- the products phase of a tile took 20 k cycles for
-// 9.2 k cycles of MFMA (tools/stamps_pair_bwd.py).
+// 9.2 k cycles of MFMA (tools/stamps.py pair-bwd).
 struct PairBwdAddr {
   int a[4][4];   // [j][ob]: dy columns 16 ob + i of row slice j (mod 4)
   int aw[4];     // [j]: column 16 wave + i (the X image's and the narrow products' column block)
@@ -336,16 +337,8 @@ struct DensePairBwdK {
   const float *nx[2][kMaxNarrow];
   int nwidth[2][kMaxNarrow], ndiv[2][kMaxNarrow], nfeat[2][kMaxNarrow];
   float *partial[2];   // [gridDim.x][din_s + 1][64]
-#ifdef NGPDE_STAMPS
-  unsigned long long *stamps;   // diagnostic build only (tools/stamps_pair_bwd.py): [gridDim.x][16], the workgroup's 4th tile
-#endif
+  NGPDE_STAMP_FIELD
 };
-#ifdef NGPDE_STAMPS
-unsigned long long *g_pair_bwd_stamps = nullptr;
-#define PBWD_STAMP(k) do { if (threadIdx.x == 0 && p.stamps && it == 3) p.stamps[(size_t)blockIdx.x * 16 + (k)] = clock64(); } while (0)
-#else
-#define PBWD_STAMP(k)
-#endif
 
 // The products of one tile of dense_pair64_bwd_kernel with the NEXT tile's X image on its way by LDS-DMA.  The pointers are
 // __restrict__ so that the DMA and the LDS reads carry no-alias information: without it the compiler puts s_waitcnt vmcnt(0) in
@@ -355,9 +348,9 @@ __device__ __forceinline__ void pair_bwd_products(const float *__restrict__ ximg
                                                   const float *__restrict__ dz1, const float *__restrict__ nblk, bool has_next,
                                                   const float *x, uint32_t next_row0, uint32_t n, int wave, int lane, const PairBwdAddr &q,
                                                   const f32x4 (&wf)[2][4], f32x4 (&accW)[2][4], f32x4 (&accN)[2], f32x4 (&accX)[4],
-                                                  unsigned long long *st = nullptr) {   // (st: diagnostic build)
+                                                  const StampSink *st = nullptr) {
   if (has_next) dma_x_tile(x, next_row0, n, xnext, wave, lane);
-  if (st) st[12] = clock64();
+  NGPDE_STAMP(st, 16, 12, memtime);
   // ---- dW_s += X^T dy_s: this wave's 16 input features x 64 outputs, both sides from one read of X; the narrow block
   // (features + ones) x this wave's 16 outputs.  The 13 LDS words of row slice s + 1 are asked for in the MIDDLE of the 10 products
   // of slice s (two register sets, scheduling fences): written as "read, then multiply" the compiler emits read -> s_waitcnt
@@ -416,7 +409,7 @@ __device__ __forceinline__ void pair_bwd_products(const float *__restrict__ ximg
     __builtin_amdgcn_sched_barrier(0);
     wmul(fs[s & 1], 1);
   });
-  if (st) st[13] = clock64();
+  NGPDE_STAMP(st, 16, 13, memtime);
   // ---- dX[:, 16 w .. + 15] = dy_a Wa^T + dy_b Wb^T: all 64 rows, this wave's 16 columns, weights from registers; same pipeline
   static_for<0, 16>([&](auto gc) {
     constexpr int g = decltype(gc)::value, rt = g >> 2, kh = g & 3;
@@ -505,9 +498,9 @@ __global__ __launch_bounds__(kBT, 2) void dense_pair64_bwd_kernel(const DensePai
   for (; tile < p.n_tiles; tile += gridDim.x, ++it) {
     const int64_t row0 = (int64_t)tile * kTR;
     float *cur = (it & 1) ? ldsX1 : ldsX0, *nxt = (it & 1) ? ldsX0 : ldsX1;
-    PBWD_STAMP(0);
+    if (it == 3) NGPDE_STAMP(p.stamps, 16, 0, memtime);
     __syncthreads();   // the previous tile's dz tiles and outgoing dX are consumed
-    PBWD_STAMP(1);
+    if (it == 3) NGPDE_STAMP(p.stamps, 16, 1, memtime);
 #pragma unroll
     for (int pp = 0; pp < 4; ++pp) {
       const int r = rg + 16 * pp;
@@ -516,23 +509,19 @@ __global__ __launch_bounds__(kBT, 2) void dense_pair64_bwd_kernel(const DensePai
     }
     *reinterpret_cast<float2 *>(&ldsN[(nsd * kTR + nrow) * 16 + nf]) = make_float2(nv0, nv1);
     __syncthreads();
-    PBWD_STAMP(2);
+    if (it == 3) NGPDE_STAMP(p.stamps, 16, 2, memtime);
     const int tnext = tile + gridDim.x;
     if (tnext < p.n_tiles) fetch(tnext);
-    PBWD_STAMP(3);
+    if (it == 3) NGPDE_STAMP(p.stamps, 16, 3, memtime);
     f32x4 accX[4];
     pair_bwd_products(cur, nxt, ldsDz0, ldsDz1, ldsN, tnext < p.n_tiles, p.x, (uint32_t)tnext * kTR, (uint32_t)p.n, wave, lane, addr, wf,
-                      accW, accN, accX
-#ifdef NGPDE_STAMPS
-                      , (threadIdx.x == 0 && p.stamps && it == 3) ? p.stamps + (size_t)blockIdx.x * 16 : nullptr
-#endif
-                      );
-    PBWD_STAMP(4);
+                      accW, accN, accX, it == 3 ? NGPDE_STAMP_SINK(p) : nullptr);
+    if (it == 3) NGPDE_STAMP(p.stamps, 16, 4, memtime);
     wait_vmcnt0();   // (tracked by the compiler: behind an asm wait it would drain vmcnt again at the next barrier, with the addend
                      // loads below in flight)
     // the addend's rows: in flight while dX is staged.  Inline loads: written as C++ loads the compiler sinks each of them
     // into the guarded store below -- load, wait (for the previous store with it), add, store, four times in a row
-    PBWD_STAMP(5);
+    if (it == 3) NGPDE_STAMP(p.stamps, 16, 5, memtime);
     f32x4 addv[4];
 #pragma unroll
     for (int pp = 0; pp < 4; ++pp) addv[pp] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -544,15 +533,15 @@ __global__ __launch_bounds__(kBT, 2) void dense_pair64_bwd_kernel(const DensePai
       }
     }
     __syncthreads();   // every wave is done with the X image
-    PBWD_STAMP(6);
+    if (it == 3) NGPDE_STAMP(p.stamps, 16, 6, memtime);
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) cur[(16 * rt + 4 * kq + reg) * kPS + 16 * wave + i] = accX[rt][reg];
     __syncthreads();
-    PBWD_STAMP(7);
+    if (it == 3) NGPDE_STAMP(p.stamps, 16, 7, memtime);
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(addv[0]), "+v"(addv[1]), "+v"(addv[2]), "+v"(addv[3]) : : "memory");
-    PBWD_STAMP(8);
+    if (it == 3) NGPDE_STAMP(p.stamps, 16, 8, memtime);
 #pragma unroll
     for (int pp = 0; pp < 4; ++pp) {
       const int r = rg + 16 * pp;
@@ -561,16 +550,11 @@ __global__ __launch_bounds__(kBT, 2) void dense_pair64_bwd_kernel(const DensePai
         *reinterpret_cast<float4 *>(p.dx + (row0 + r) * kD + 4 * qc) = make_float4(v.x + addv[pp][0], v.y + addv[pp][1], v.z + addv[pp][2], v.w + addv[pp][3]);
       }
     }
-    PBWD_STAMP(9);
-#ifdef NGPDE_STAMPS
-    if (threadIdx.x == 0 && p.stamps && it == 3) {   // which CU / XCD the workgroup runs on: who shares a CU with whom
-      unsigned hw, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      p.stamps[(size_t)blockIdx.x * 16 + 10] = hw;
-      p.stamps[(size_t)blockIdx.x * 16 + 11] = xcc;
+    if (it == 3) NGPDE_STAMP(p.stamps, 16, 9, memtime);
+    if (it == 3) {   // which CU / XCD the workgroup runs on: who shares a CU with whom
+      NGPDE_STAMP(p.stamps, 16, 10, hw_id);
+      NGPDE_STAMP(p.stamps, 16, 11, xcc_id);
     }
-#endif
   }
 
   // ---- slabs of both sides: the accumulators directly (row 4 of the narrow block = the bias gradient)
@@ -671,9 +655,7 @@ int32_t launch_dense_pair_bwd(int64_t n, const SegTable &ta, int dina, const flo
                               const float *dx_add, void *workspace, int grid, hipStream_t stream) {
   DensePairBwdK k{};
   k.n = n; k.n_tiles = (int)((n + kTR - 1) / kTR); k.x = ta.ptr[0]; k.dx = dx; k.dx_add = dx_add;
-#ifdef NGPDE_STAMPS
-  k.stamps = g_pair_bwd_stamps;
-#endif
+  NGPDE_STAMP_SET(k, kStampPairBwd, 0);
   const SegTable *ts[2] = {&ta, &tb};
   const int dins[2] = {dina, dinb};
   const float *wts[2] = {wta, wtb}, *dys[2] = {dya, dyb};
@@ -703,10 +685,3 @@ int32_t launch_dense_pair_bwd(int64_t n, const SegTable &ta, int dina, const flo
 }
 
 }  // namespace ngpde
-
-#ifdef NGPDE_STAMPS
-extern "C" int32_t ngpde_debug_set_pair_bwd_stamps(unsigned long long *buf) {
-  ngpde::g_pair_bwd_stamps = buf;
-  return 0;
-}
-#endif

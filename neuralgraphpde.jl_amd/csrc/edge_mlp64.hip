@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "stamps.h"
 
 namespace ngpde {
 
@@ -47,19 +48,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kT4 = 256, kW = 64, kTS = kW + 4, kSlice = 16, kChunk4 = 64, kRows = 32;
 
-#ifdef NGPDE_STAMPS
-// diagnostic build only (tools/stamps_edge64.py): phase timestamps of one steady-state tile per workgroup, [n_blocks][16] words
-unsigned long long *g_edge64_stamps = nullptr;
-#define E64_STAMP(k)                                                                                          \
-  do {                                                                                                        \
-    if (threadIdx.x == 0 && p.stamps && stamp_tile) {                                                         \
-      p.stamps[(size_t)blockIdx.x * 16 + (k)] = clock64();                                                    \
-      if ((k) == 0 || (k) == 13) p.stamps[(size_t)blockIdx.x * 16 + 14 + ((k) ? 1 : 0)] = wall_clock64();     \
-    }                                                                                                         \
-  } while (0)
-#else
-#define E64_STAMP(k)
-#endif
 
 struct EdgeMlp64K {
   const int4 *sched;
@@ -68,9 +56,7 @@ struct EdgeMlp64K {
   int n_tiles, halo_rows, aggr;
   const float *P, *Q, *wt, *bias;
   float *out;
-#ifdef NGPDE_STAMPS
-  unsigned long long *stamps;
-#endif
+  NGPDE_STAMP_FIELD
 };
 
 struct Meta64 {
@@ -322,10 +308,8 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_fwd_kernel(const EdgeMlp64K
   }
 
   for (; jt < range_len; jt += wgs_per_xcd) {
-#ifdef NGPDE_STAMPS
     const bool stamp_tile = (jt == wg_in_xcd + 4 * wgs_per_xcd);   // a tile in steady state (the fifth of the workgroup)
-#endif
-    E64_STAMP(0);
+    if (stamp_tile) { NGPDE_STAMP(p.stamps, 16, 0, memtime); NGPDE_STAMP(p.stamps, 16, 14, memrealtime); }
     // ---- stage this tile (fetched under the previous tile's arithmetic)
     const int4 sc0 = meta.sc0, sc1 = meta.sc1;
 #pragma unroll
@@ -371,7 +355,7 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_fwd_kernel(const EdgeMlp64K
     float4 racc0 = f4_zero(), racc1 = f4_zero();
     __syncthreads();
 
-    E64_STAMP(1);
+    if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 1, memtime);
     const int n_it = (total + kChunk4 - 1) / kChunk4;
     auto reduce = [&](int it) {   // lane group g16 sums the messages of rows g16 and g16 + 16 that lie in chunk `it`, edge order
       const int c0 = it * kChunk4;
@@ -392,29 +376,29 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_fwd_kernel(const EdgeMlp64K
     if (n_it > 0) {
       f32x4 a[4], accp[4];
       block(no, no, yes, 0, total, ldsMsg0, a, accp);          // a1 of slice 0
-      E64_STAMP(2);
+      if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 2, memtime);
       block(yes, no, yes, 1, total, ldsMsg0, a, accp);         // products of slice 0 | a1 of slice 1
-      E64_STAMP(3);
+      if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 3, memtime);
       if (has_next) fetch_rows(meta, rows);           // the next tile's rows: in flight across this tile's remaining arithmetic
-      E64_STAMP(4);
+      if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 4, memtime);
       for (int it = 1; it < n_it; ++it) {
         // products of slice it | messages of slice it - 1 (-> buffer (it - 1) & 1) | a1 of slice it + 1
         block(yes, yes, yes, it + 1, total, ldsMsg0 + ((it - 1) & 1) * (kChunk4 * kTS), a, accp);
-        if (it == 1) E64_STAMP(5);
+        if (it == 1 && stamp_tile) NGPDE_STAMP(p.stamps, 16, 5, memtime);
         __syncthreads();
-        if (it == 1) E64_STAMP(6);
+        if (it == 1 && stamp_tile) NGPDE_STAMP(p.stamps, 16, 6, memtime);
         reduce(it - 1);   // (no second barrier: the next block writes the other buffer)
-        if (it == 1) E64_STAMP(7);
-        if (it == 1) E64_STAMP(8);
-        if (it == 2) E64_STAMP(9);
+        if (it == 1 && stamp_tile) NGPDE_STAMP(p.stamps, 16, 7, memtime);
+        if (it == 1 && stamp_tile) NGPDE_STAMP(p.stamps, 16, 8, memtime);
+        if (it == 2 && stamp_tile) NGPDE_STAMP(p.stamps, 16, 9, memtime);
       }
-      E64_STAMP(10);
+      if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 10, memtime);
       block(no, yes, no, 0, total, ldsMsg0 + ((n_it - 1) & 1) * (kChunk4 * kTS), a, accp);   // messages of the last slice
-      E64_STAMP(11);
+      if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 11, memtime);
       __syncthreads();
       reduce(n_it - 1);
       __syncthreads();
-      E64_STAMP(12);
+      if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 12, memtime);
     } else if (has_next) {
       fetch_rows(meta, rows);
     }
@@ -428,7 +412,7 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_fwd_kernel(const EdgeMlp64K
       if (p.aggr == NGPDE_AGGR_MEAN) racc1 = deg > 0 ? f4_scale(1.0f / (float)deg, racc1) : f4_zero();
       *reinterpret_cast<float4 *>(p.out + (size_t)sc1.x * kW + 4 * q) = racc1;
     }
-    E64_STAMP(13);
+    if (stamp_tile) { NGPDE_STAMP(p.stamps, 16, 13, memtime); NGPDE_STAMP(p.stamps, 16, 15, memrealtime); }
   }
 }
 
@@ -834,9 +818,7 @@ int32_t launch_edge_mlp64_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hipStr
   k.n_tiles = (int)(g->n_sched / kTileRows); k.aggr = a.aggr;
   k.halo_rows = std::max<int>(kTileRows, std::min<int>(kHaloCap, g->by_t.max_halo));
   k.P = a.P; k.Q = a.Q; k.wt = a.wt[0]; k.bias = a.bias[0]; k.out = a.out;
-#ifdef NGPDE_STAMPS
-  k.stamps = g_edge64_stamps;
-#endif
+  NGPDE_STAMP_SET(k, kStampEdge64, 0);
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kW * kTS + 2 * (size_t)kChunk4 * kTS) * sizeof(float);
   // two persistent workgroups per CU (one when the halo region is large), a multiple of the 8 XCDs
   const int per_xcd = std::max(1, std::min(lds + 4096 <= 80 * 1024 ? 64 : 32, (k.n_tiles + 7) / 8));
@@ -951,10 +933,3 @@ int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hip
 }
 
 }  // namespace ngpde
-
-#ifdef NGPDE_STAMPS
-extern "C" int32_t ngpde_debug_set_edge64_stamps(unsigned long long *buf) {
-  ngpde::g_edge64_stamps = buf;
-  return 0;
-}
-#endif

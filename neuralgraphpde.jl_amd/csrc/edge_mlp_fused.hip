@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "stamps.h"
 
 namespace ngpde {
 
@@ -20,19 +21,6 @@ namespace {
 
 constexpr int kT = 512, kW = 64, kTS = kW + 4, kChunk = 128, kGroups = 32;   // kChunk = 8 waves x 16 edges
 
-#ifdef NGPDE_STAMPS
-// diagnostic build only (tools/stamps_edge.py): phase timestamps of each workgroup's FIRST tile, [n_blocks][16] words
-unsigned long long *g_edge_stamps = nullptr;
-#define EDGE_STAMP(k)                                                                                     \
-  do {                                                                                                    \
-    if (threadIdx.x == 0 && p.stamps && first_tile) {                                                     \
-      p.stamps[(size_t)blockIdx.x * 16 + (k)] = clock64();                                                \
-      if ((k) == 0 || (k) == 7) p.stamps[(size_t)blockIdx.x * 16 + 8 + ((k) ? 1 : 0)] = wall_clock64();  \
-    }                                                                                                     \
-  } while (0)
-#else
-#define EDGE_STAMP(k)
-#endif
 
 struct EdgeMlpK {
   const int4 *sched;
@@ -45,9 +33,7 @@ struct EdgeMlpK {
   const float *wt[3], *bias[3];
   float *out;
   float *save_z[4];   // [0]: z1 [E][h1]; [k]: pre-activation of tail layer k [E][dout_k]; nullable
-#ifdef NGPDE_STAMPS
-  unsigned long long *stamps;
-#endif
+  NGPDE_STAMP_FIELD
 };
 
 __device__ __forceinline__ int xcd_tile(int b, int nb) {
@@ -161,10 +147,8 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
   const int last_w = (NTAIL > 0) ? p.dout[NTAIL - 1] : h1;
 
   for (; jt < range_len; jt += wgs_per_xcd) {
-#ifdef NGPDE_STAMPS
     const bool first_tile = (jt == wg_in_xcd + 4 * wgs_per_xcd);   // a tile in steady state (the fifth of the workgroup)
-#endif
-    EDGE_STAMP(0);
+    if (first_tile) { NGPDE_STAMP(p.stamps, 16, 0, memtime); NGPDE_STAMP(p.stamps, 16, 8, memrealtime); }
     // ---- stage this tile (fetched under the previous tile's arithmetic)
     const int4 sc = meta.sc;
 #pragma unroll
@@ -210,7 +194,7 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
     else if (p.aggr == NGPDE_AGGR_MUL) racc = make_float4(1.f, 1.f, 1.f, 1.f);   // scatter(*): the neutral element (an empty neighbourhood gives 1)
     else racc = f4_zero();
     __syncthreads();
-    EDGE_STAMP(1);
+    if (first_tile) NGPDE_STAMP(p.stamps, 16, 1, memtime);
 
     bool rows_fetched = false;
     for (int c0 = 0; c0 < total; c0 += kChunk) {
@@ -242,7 +226,7 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
       for (int ct = 0; ct < 4; ++ct)
         if (!(valid && 16 * ct + 4 * kq < h1)) a[ct] = f4_zero();
       }
-      if (c0 == 0) EDGE_STAMP(2);
+      if (c0 == 0 && first_tile) NGPDE_STAMP(p.stamps, 16, 2, memtime);
       if (has_next && !rows_fetched) {   // the next tile's rows: in flight across this tile's MFMAs
         fetch_rows(meta, rows);
         rows_fetched = true;
@@ -285,13 +269,13 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
           if (!(valid && 16 * mt + 4 * kq < dw)) a[mt] = f4_zero();
       }
       }
-      if (c0 == 0) EDGE_STAMP(3);
+      if (c0 == 0 && first_tile) NGPDE_STAMP(p.stamps, 16, 3, memtime);
       // ---- messages of the chunk -> LDS, then lane group g sums the messages of row g in edge order
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
         *reinterpret_cast<float4 *>(&ldsMsg[(wave * 16 + ei) * kTS + 16 * mt + 4 * kq]) = a[mt];
       __syncthreads();
-      if (c0 == 0) EDGE_STAMP(4);
+      if (c0 == 0 && first_tile) NGPDE_STAMP(p.stamps, 16, 4, memtime);
       {
         const int lo = max(my_lo, c0), hi = min(my_hi, c0 + kChunk);
         for (int kk = lo; kk < hi; ++kk) {
@@ -303,16 +287,16 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
         }
       }
       __syncthreads();
-      if (c0 == 0) EDGE_STAMP(5);
+      if (c0 == 0 && first_tile) NGPDE_STAMP(p.stamps, 16, 5, memtime);
     }
-    EDGE_STAMP(6);
+    if (first_tile) NGPDE_STAMP(p.stamps, 16, 6, memtime);
     if (has_next && !rows_fetched) fetch_rows(meta, rows);   // a tile without edges
     if (sc.x >= 0 && 4 * q < last_w) {
       const int deg = my_hi - my_lo;
       if (p.aggr == NGPDE_AGGR_MEAN) racc = deg > 0 ? f4_scale(1.0f / (float)deg, racc) : f4_zero();
       *reinterpret_cast<float4 *>(p.out + (size_t)sc.x * last_w + 4 * q) = racc;
     }
-    EDGE_STAMP(7);
+    if (first_tile) { NGPDE_STAMP(p.stamps, 16, 7, memtime); NGPDE_STAMP(p.stamps, 16, 9, memrealtime); }
   }
 }
 
@@ -757,9 +741,7 @@ int32_t launch_edge_mlp_fused_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hi
   }
   k.out = a.out;
   for (int l = 0; l < 4; ++l) k.save_z[l] = a.save_z[l];
-#ifdef NGPDE_STAMPS
-  k.stamps = g_edge_stamps;
-#endif
+  NGPDE_STAMP_SET(k, kStampEdge, 0);
   // LDS: the halo region is sized by the largest halo of this graph's tiles; persistent workgroups, a multiple of the 8 XCDs
   k.halo_rows = std::max<int>(kTileRows, std::min<int>(kHaloCap, g->by_t.max_halo));
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kGroups * kTS + (size_t)a.n_tail * kW * kTS + (size_t)kChunk * kTS) * sizeof(float);
@@ -784,15 +766,6 @@ int32_t launch_edge_mlp_fused_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hi
   NGPDE_LAUNCH_CHECK("edge_mlp_fused_fwd_kernel");
   return NGPDE_OK;
 }
-
-#ifdef NGPDE_STAMPS
-}  // namespace ngpde
-extern "C" int32_t ngpde_debug_set_edge_stamps(unsigned long long *buf) {
-  ngpde::g_edge_stamps = buf;
-  return 0;
-}
-namespace ngpde {
-#endif
 
 static int edge_bwd_grid(const ngpde_graph *g) {
   const int n_tiles = (int)(g->n_sched / kTileRows);

@@ -26,6 +26,7 @@
 #include "gcn_tile.h"
 #include "persistent_mem.h"
 #include "persistent_sync.h"
+#include "stamps.h"
 
 namespace ngpde {
 
@@ -113,24 +114,9 @@ __device__ __forceinline__ f32x4 mfma_block(const float *pa, const float *pb) {
 // ---------------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------------
-#ifdef NGPDE_STAMPS
-// diagnostic build only (tools/stamps_gat.py): shader-clock stamps of thread 0 of every workgroup
-unsigned long long *g_gat_stamps = nullptr;
-#define NGPDE_GST(k) do { if (threadIdx.x == 0 && p.stamps) { p.stamps[(size_t)blockIdx.x * 16 + (k)] = clock64(); if ((k) == 0 || (k) == 10) p.stamps[(size_t)blockIdx.x * 16 + 11 + (k) / 10] = wall_clock64(); } } while (0)
-#define NGPDE_GST_FIELD unsigned long long *stamps;
-#define NGPDE_GST_SET(kk) kk.stamps = g_gat_stamps;
-#define NGPDE_GSTP(ptr, k) do { if (threadIdx.x == 0 && (ptr)) (ptr)[(size_t)blockIdx.x * 16 + (k)] = clock64(); } while (0)
-#define NGPDE_GSTP_OF(kk) (kk).stamps
-#else
-#define NGPDE_GST(k)
-#define NGPDE_GST_FIELD
-#define NGPDE_GST_SET(kk)
-#define NGPDE_GSTP(ptr, k)
-#define NGPDE_GSTP_OF(kk) nullptr
-#endif
 
 struct GatFwdK {
-  NGPDE_GST_FIELD
+  NGPDE_STAMP_FIELD
   const float *x, *wt, *a, *bias;
   const int4 *sched;
   const int2 *halo;
@@ -216,9 +202,9 @@ __device__ __forceinline__ float4 gat_fwd_compute(const GatFwdK &p, const GatFwd
   const float4 al4 = *reinterpret_cast<const float4 *>(p.a + (size_t)hq * 2 * C + (4 * q) % C);
   const float4 ar4 = *reinterpret_cast<const float4 *>(p.a + (size_t)hq * 2 * C + C + (4 * q) % C);
   const int hc = __builtin_amdgcn_readfirstlane(p.tile_info[tile].x);            // rows staged (own rows first)
-  NGPDE_GST(1);
+  NGPDE_STAMP(p.stamps, 16, 1, memtime);
   __syncthreads();   // staged rows (DMA) visible
-  NGPDE_GST(2);
+  NGPDE_STAMP(p.stamps, 16, 2, memtime);
   // ---- WX[hh][o] = sum_j x_hh[j] W[j][o]: <= 6 row tiles x 4 column tiles, wave w: column tile w & 3, row tiles (w >> 2), + 2, + 4
   {
     const int ct = wave_u & 3, i = lane & 15, kq = lane >> 4;
@@ -241,9 +227,9 @@ __device__ __forceinline__ float4 gat_fwd_compute(const GatFwdK &p, const GatFwd
     }
     if (grp == 0) *reinterpret_cast<float4 *>(&ldsWX[kHaloCap * GG::TS + 4 * q]) = f4_zero();   // the all-zero row's product
   }
-  NGPDE_GST(3);
+  NGPDE_STAMP(p.stamps, 16, 3, memtime);
   __syncthreads();
-  NGPDE_GST(4);
+  NGPDE_STAMP(p.stamps, 16, 4, memtime);
   // ---- score halves: ar of every staged row (one lane per head writes it), al of the own row
   float al[4] = {0.f, 0.f, 0.f, 0.f};
   {
@@ -319,7 +305,7 @@ __device__ __forceinline__ float4 gat_fwd_compute(const GatFwdK &p, const GatFwd
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-  NGPDE_GST(5);
+  NGPDE_STAMP(p.stamps, 16, 5, memtime);
   // ---- aggregation of the entries' W x rows, this lane's head
   float4 acc = f4_zero();
   {
@@ -335,7 +321,7 @@ __device__ __forceinline__ float4 gat_fwd_compute(const GatFwdK &p, const GatFwd
       }
     }
   }
-  NGPDE_GST(9);
+  NGPDE_STAMP(p.stamps, 16, 9, memtime);
   return f4_add(acc, b4);
 }
 
@@ -349,7 +335,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_layer_fwd_kernel(const GatFwd
   const GatFwdLds L = {ldsXh, ldsS, ldsA, ldsAr, ldsV};
   const GatThread t = gat_thread();
   const int tile = xcd_tile(blockIdx.x, p.n_tiles);
-  NGPDE_GST(0);
+  NGPDE_STAMP(p.stamps, 16, 0, memtime); NGPDE_STAMP(p.stamps, 16, 11, memrealtime);
   TileMeta m;
   tile_meta(p.halo, p.slots, p.sched, p.x, tile, t.grp, t.q, ldsXh, m);
   float breg[4][4];
@@ -361,14 +347,14 @@ __global__ __launch_bounds__(kThreads, 4) void gat_layer_fwd_kernel(const GatFwd
     if (p.save_z) reinterpret_cast<float4 *>(p.save_z)[idx4] = z;
     reinterpret_cast<float4 *>(p.y)[idx4] = f4_act(p.act, z);
   }
-  NGPDE_GST(10);
+  NGPDE_STAMP(p.stamps, 16, 10, memtime); NGPDE_STAMP(p.stamps, 16, 12, memrealtime);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // pullback, by target:  dz, d alpha, softmax / leakyrelu pullback -> dscore, dal, db slabs
 // ---------------------------------------------------------------------------------------------------
 struct GatBwdTK {
-  NGPDE_GST_FIELD
+  NGPDE_STAMP_FIELD
   const float *x, *wt, *dy, *yz, *alpha;
   const int4 *sched;
   const int2 *halo;
@@ -442,7 +428,7 @@ __device__ __forceinline__ float gat_bwd_target_compute(const GatBwdTK &p, const
   if (grp == 0) Xh4[kHaloCap * GG::LPR + q] = f4_zero();
   *reinterpret_cast<float4 *>(&ldsDZ[grp * GG::TS + 4 * q]) = dz;
   __syncthreads();
-  NGPDE_GSTP(NGPDE_GSTP_OF(p), 7);
+  NGPDE_STAMP(p.stamps, 16, 7, memtime);
   float db_part;
   {   // db partial: column sums of the dz tile (8 adjacent lanes hold row-partials of one column)
     const int dbc = tid / GG::DBP, dbpart = tid % GG::DBP;
@@ -477,7 +463,7 @@ __device__ __forceinline__ float gat_bwd_target_compute(const GatBwdTK &p, const
     if (grp == 0) *reinterpret_cast<float4 *>(&ldsWX[kHaloCap * GG::TS + 4 * q]) = f4_zero();   // the all-zero row's product
   }
   __syncthreads();
-  NGPDE_GSTP(NGPDE_GSTP_OF(p), 8);
+  NGPDE_STAMP(p.stamps, 16, 8, memtime);
   // d alpha of every entry of the row: lane q holds features 4q .. 4q + 3 of its row's dz, i.e. of head 4q / C; partial dot with the
   // entry's W x row, summed over the C / 4 lanes of the head (quad permutes, then half-row / row mirrors); one lane per head
   // writes it to the (row, entry, head) table, the lane that owns the entry reads its heads back
@@ -515,7 +501,7 @@ __device__ __forceinline__ float gat_bwd_target_compute(const GatBwdTK &p, const
       }
     }
   }
-  NGPDE_GSTP(NGPDE_GSTP_OF(p), 9);
+  NGPDE_STAMP(p.stamps, 16, 9, memtime);
   // softmax pullback: dlogit = alpha (d alpha - sum alpha d alpha); leakyrelu' by the saved sign
   float dsc[2][4], dalv[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -570,7 +556,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_layer_bwd_target_kernel(const
 // pullback, by source:  dWx = sum alpha dz[t] + dal a_l + dar a_r;  dx = dWx W^T;  dW, u_l, u_r slabs
 // ---------------------------------------------------------------------------------------------------
 struct GatBwdSK {
-  NGPDE_GST_FIELD
+  NGPDE_STAMP_FIELD
   const float *gz, *x, *wt, *a, *alpha, *dscore, *dal;
   const int4 *sched;
   const int2 *halo;
@@ -706,9 +692,9 @@ __device__ __forceinline__ float4 gat_bwd_source_core(const GatBwdSK &p, const G
   float dalv[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) dalv[k] = __shfl(dalq, k, GG::LPR);
-  NGPDE_GSTP(NGPDE_GSTP_OF(p), 10);
+  NGPDE_STAMP(p.stamps, 16, 10, memtime);
   __syncthreads();   // staged dz rows visible (coefficients are group-private, same wave)
-  NGPDE_GSTP(NGPDE_GSTP_OF(p), 11);
+  NGPDE_STAMP(p.stamps, 16, 11, memtime);
   float4 g = f4_zero();
   {
     const int wmax = wave_max_deg(deg);
@@ -730,9 +716,9 @@ __device__ __forceinline__ float4 gat_bwd_source_core(const GatBwdSK &p, const G
   *reinterpret_cast<float4 *>(&ldsXT[grp * GG::TS + 4 * q]) = xo;
   if (q < 4) ldsDD[grp * 8 + q] = ok ? sel4(dalv, q) : 0.f;
   else if (q < 8) ldsDD[grp * 8 + q] = ok ? sel4(darv, q - 4) : 0.f;
-  NGPDE_GSTP(NGPDE_GSTP_OF(p), 12);
+  NGPDE_STAMP(p.stamps, 16, 12, memtime);
   __syncthreads();   // tiles complete, staged rows dead
-  NGPDE_GSTP(NGPDE_GSTP_OF(p), 13);
+  NGPDE_STAMP(p.stamps, 16, 13, memtime);
   mfma_rows_times_bt<GD>(ldsDWX, ldsBt, ldsXh, wave_u, lane);
   {   // dWt[i][o] += sum_n x[n][i] dWx[n][o]
     const int i = lane & 15, kq = lane >> 4;
@@ -747,7 +733,7 @@ __device__ __forceinline__ float4 gat_bwd_source_core(const GatBwdSK &p, const G
       }
     }
   }
-  NGPDE_GSTP(NGPDE_GSTP_OF(p), 14);
+  NGPDE_STAMP(p.stamps, 16, 14, memtime);
   {   // u_which,k[i] += sum_n (dal | dar)[n][k] x[n][i]
     const int which = tid >> 8, hk = (tid >> 6) & 3, i = tid & 63;
 #pragma unroll 8
@@ -1041,13 +1027,13 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_kernel(co
   for (int n = 0; n < p.n_steps && !dead; ++n) {
     for (int i = 0; i < S; ++i) {
       ++ph;
-      NGPDE_GSTP(NGPDE_GSTP_OF(l), 0);
+      NGPDE_STAMP(l.stamps, 16, 0, memtime);
       const size_t e = ph - 1;
       const float *X = p.xs + (p.taped ? e : (e & 1)) * p.row_elems;
       // the input of the next stage / the step update, as ngpde_rk_stage_combine forms it: 1 * u, then the k_j in order
       const int row = (i + 1 < S) ? i + 1 : S;
       if (!gat_wait(p.s, t, my_nbr, ph - 1, &s_ok)) { dead = true; break; }
-      NGPDE_GSTP(NGPDE_GSTP_OF(l), 13);
+      NGPDE_STAMP(l.stamps, 16, 13, memtime);
       halo_round2<GD, true, 16>(reinterpret_cast<const float4 *>(X), t.q, t.grp, ldsXh, hr);
       l.alpha = p.alpha ? p.alpha + e * p.alpha_elems : nullptr;
       const float4 z = gat_fwd_compute<H>(l, L, t, m, tile, breg, b4);
@@ -1063,16 +1049,16 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_kernel(co
         if (last) st4_g(p.u_out, own, v);
         else store_sc1(p.xs + (p.taped ? e + 1 : ((e + 1) & 1)) * p.row_elems, own, v);
       }
-      NGPDE_GSTP(NGPDE_GSTP_OF(l), 14);
+      NGPDE_STAMP(l.stamps, 16, 14, memtime);
       if (!last) gat_publish(p.s, t, tile, ph);
-      NGPDE_GSTP(NGPDE_GSTP_OF(l), 15);
+      NGPDE_STAMP(l.stamps, 16, 15, memtime);
     }
   }
   if (dead && ok) st4_g(p.u_out, own, f4_nan());
 }
 
 struct GatNodeBwdK {
-  NGPDE_GST_FIELD
+  NGPDE_STAMP_FIELD
   GatBwdTK t;           // wt, lists by target, n_tiles, act, slope, dal (x, alpha, dscore per phase; dy, yz, dz, slab_db unused)
   GatBwdSK s;           // wt, a, dal, lists by source, xpos, xpad, n_tiles, slab_dw, slab_u (gz, x, alpha, dscore per phase; dx unused)
   GatSync y;
@@ -1249,7 +1235,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
   for (int n = p.n_steps - 1; n >= 0 && !dead; --n) {
     for (int i = S - 1; i >= 0; --i) {
       ++ph;
-      NGPDE_GSTP(NGPDE_GSTP_OF(p), 0);
+      NGPDE_STAMP(p.stamps, 16, 0, memtime);
       const size_t e = (size_t)n * S + i;
       const float *X = p.xs + e * p.row_elems;
       // ---- by target.  K-bar_i = (dt b_i) lambda + sum_{j > i} (dt a_ji) U-bar_j, in ngpde_rk_stage_combine's order
@@ -1265,11 +1251,11 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
       if (!ok) v = f4_zero();
       float *dzb = p.dzbuf + (size_t)(ph & 1) * p.row_elems;
       if (ok) store_sc1(dzb, own, v);
-      NGPDE_GSTP(NGPDE_GSTP_OF(p), 1);
+      NGPDE_STAMP(p.stamps, 16, 1, memtime);
       dbacc += gat_bwd_target_compute<H, true>(tk, LT, t, mt, tile, v);
-      NGPDE_GSTP(NGPDE_GSTP_OF(p), 2);
+      NGPDE_STAMP(p.stamps, 16, 2, memtime);
       gat_publish(p.y, t, tile, ph);
-      NGPDE_GSTP(NGPDE_GSTP_OF(p), 3);
+      NGPDE_STAMP(p.stamps, 16, 3, memtime);
       // ---- by source
       TileMeta ms;
       HaloRegs<GD> hrs;
@@ -1281,12 +1267,12 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
       sk.dscore = tk.dscore;
       gat_bwd_source_indices<true>(sk, t, ms.sc, spre);
       gat_bwd_source_prefetch<H>(sk, t, ms.sc, spre);   // the tape's share of the half's loads: under the wait
-      NGPDE_GSTP(NGPDE_GSTP_OF(p), 4);
+      NGPDE_STAMP(p.stamps, 16, 4, memtime);
       if (!gat_wait(p.y, t, my_nbr, ph, &s_ok)) { dead = true; break; }
-      NGPDE_GSTP(NGPDE_GSTP_OF(p), 5);
+      NGPDE_STAMP(p.stamps, 16, 5, memtime);
       halo_round2<GD, true, 16>(reinterpret_cast<const float4 *>(dzb), t.q, t.grp, ldsXh, hrs);
       const float4 dxv = gat_bwd_source_core<H, true>(sk, LS, t, ms, al4, ar4, dw, uacc, spre);
-      NGPDE_GSTP(NGPDE_GSTP_OF(p), 6);
+      NGPDE_STAMP(p.stamps, 16, 6, memtime);
       if (i > 0) {
         if (ok) st4_g(p.ubar + (size_t)i * p.row_elems, own, dxv);
       } else {   // lambda of the step before: 1 * lambda + sum_j 1 * U-bar_j, j ascending
@@ -1338,13 +1324,6 @@ inline GatWs gat_ws(const ngpde_graph *g, int heads) {
 
 }  // namespace
 
-#ifdef NGPDE_STAMPS
-extern "C" int32_t ngpde_debug_set_gat_stamps(unsigned long long *dev_buf) {   // [n_tiles][16] or NULL
-  g_gat_stamps = dev_buf;
-  return NGPDE_OK;
-}
-#endif
-
 bool gat_layer_fused_supported(const ngpde_graph *g, int din, int heads, int c) {
   return g && g->has_norm && g->n_edges > 0 && g->by_t.halo_ok && g->by_s.halo_ok && din == GD && heads * c == GD &&
          (heads == 1 || heads == 2 || heads == 4) && (uint64_t)g->n_nodes * GD * 4 < (1ull << 32) && !no_fused_gat_layer_env();
@@ -1359,7 +1338,7 @@ int32_t launch_gat_layer_fwd(const ngpde_graph *g, int heads, float slope, int a
   k.x = x; k.wt = wt; k.a = a; k.bias = bias; k.sched = g->by_t.sched; k.halo = g->by_t.halo; k.slots = g->by_t.slots;
   k.tile_info = g->by_t.tile_info;
   k.n_tiles = fused_num_blocks(g->n_nodes); k.act = act; k.slope = slope; k.y = y; k.alpha = alpha; k.save_z = save_z;
-  NGPDE_GST_SET(k)
+  NGPDE_STAMP_SET(k, kStampGat, 0);
   const dim3 grid(k.n_tiles), block(kThreads);
   switch (heads) {
     case 1: hipLaunchKernelGGL(gat_layer_fwd_kernel<1>, grid, block, 0, stream, k); break;
@@ -1388,12 +1367,12 @@ int32_t launch_gat_layer_bwd(const ngpde_graph *g, int heads, float slope, int a
     t.tile_info = g->by_t.tile_info;
     t.slots = g->by_t.slots; t.n_tiles = n_tiles; t.act = act; t.slope = slope; t.dz = ident ? nullptr : dz; t.dscore = dscore;
     t.dal = dal; t.slab_db = slab_db;
-    NGPDE_GST_SET(t)
+    NGPDE_STAMP_SET(t, kStampGat, 0);
     GatBwdSK s;
     s.gz = ident ? dy : dz; s.x = x; s.wt = wt; s.a = a; s.alpha = alpha; s.dscore = dscore; s.dal = dal; s.sched = g->by_s.sched;
     s.halo = g->by_s.halo; s.slots = g->by_s.slots; s.xpos = g->by_s.xpos; s.n_tiles = n_tiles; s.n_edges = (int)g->n_edges; s.dx = dx; s.slab_dw = slab_dw;
     s.slab_u = slab_u; s.xpad = nullptr;
-    NGPDE_GST_SET(s)
+    NGPDE_STAMP_SET(s, kStampGat, 0);
     const dim3 block(kThreads);
     switch (heads) {
       case 1:
@@ -1499,7 +1478,7 @@ int32_t launch_gat_node_fwd(const GatNodeFwd &a, hipStream_t stream) {
   k.l.tile_info = g->by_t.tile_info;
   k.l.slots = g->by_t.slots; k.l.n_tiles = ps.n_tiles; k.l.act = a.act; k.l.slope = a.slope; k.l.y = nullptr; k.l.alpha = nullptr;
   k.l.save_z = nullptr;
-  NGPDE_GST_SET(k.l)
+  NGPDE_STAMP_SET(k.l, kStampGat, 0);
   k.s = gat_sync(ps);
   k.n_steps = a.n_steps; k.S = a.S; k.taped = a.taped ? 1 : 0; k.u_in = a.u_in; k.u_out = a.u_out; k.xs = a.xs; k.yz = a.yz;
   k.alpha = a.alpha; k.kbuf = a.kbuf; k.row_elems = (size_t)g->n_nodes * GD; k.alpha_elems = (size_t)std::max<int64_t>(g->n_edges, 1) * a.heads;
@@ -1542,9 +1521,9 @@ int32_t launch_gat_node_bwd(const GatNodeBwd &a, hipStream_t stream) {
   k.s.sched = g->by_s.sched; k.s.halo = g->by_s.halo; k.s.slots = g->by_s.slots; k.s.xpos = g->by_s.xpos; k.s.xpad = a.xpad; k.s.n_edges = (int)g->n_edges;
   k.s.n_tiles = ps.n_tiles; k.s.dx = nullptr; k.s.slab_dw = a.slab_dw; k.s.slab_u = a.slab_u;
   k.y = gat_sync(ps);
-  NGPDE_GST_SET(k)
-  NGPDE_GST_SET(k.t)
-  NGPDE_GST_SET(k.s)
+  NGPDE_STAMP_SET(k, kStampGat, 0);
+  NGPDE_STAMP_SET(k.t, kStampGat, 0);
+  NGPDE_STAMP_SET(k.s, kStampGat, 0);
   k.n_steps = a.n_steps; k.S = a.S; k.xs = a.xs; k.yz = ident ? nullptr : a.yz; k.alpha = a.alpha; k.duT = a.duT; k.lam = a.lam;
   k.ubar = a.ubar; k.dzbuf = a.dzbuf; k.dscore = a.dscore; k.slab_db = a.slab_db; k.row_elems = (size_t)g->n_nodes * GD;
   k.alpha_elems = (size_t)std::max<int64_t>(g->n_edges, 1) * a.heads; k.dscore_elems = gat_node_dscore_elems(g); k.cb = a.cb;

@@ -22,41 +22,11 @@
 #include "common.h"
 #include "device_utils.h"
 #include "gcn_tile.h"
+#include "stamps.h"
 
 namespace ngpde {
 
 namespace {
-
-#ifdef NGPDE_STAMPS
-// diagnostic build only (tools/): per-workgroup phase timestamps, one slot of [n_blocks][16] words per
-// launch; never compiled into the product library
-unsigned long long *g_stamps_base = nullptr;
-int g_stamps_max = 0, g_stamps_next = 0;
-#define NGPDE_STAMP_FIELD unsigned long long *stamps;
-#define NGPDE_STAMP(k)                                                              \
-  do {                                                                              \
-    if (threadIdx.x == 0 && p.stamps) {                                             \
-      p.stamps[(size_t)blockIdx.x * 16 + 2 * (k)] = clock64();                      \
-      p.stamps[(size_t)blockIdx.x * 16 + 2 * (k) + 1] = wall_clock64();             \
-    }                                                                               \
-  } while (0)
-#define NGPDE_STAMP_SET(kk, nb)                                                     \
-  kk.stamps = nullptr;                                                              \
-  if (g_stamps_base && g_stamps_next < g_stamps_max) kk.stamps = g_stamps_base + (size_t)(g_stamps_next++) * (nb) * 16;
-#define NGPDE_SUBSTAMP(ptr, k)                                                      \
-  do {                                                                              \
-    if (threadIdx.x == 0 && (ptr)) (ptr)[(size_t)blockIdx.x * 16 + 10 + (k)] = clock64(); \
-  } while (0)
-#define NGPDE_USE(v) asm volatile("" ::"v"(v))
-#define NGPDE_STAMP_PTR(p) (p).stamps
-#else
-#define NGPDE_STAMP_FIELD
-#define NGPDE_STAMP(k)
-#define NGPDE_STAMP_SET(kk, nb)
-#define NGPDE_SUBSTAMP(ptr, k)
-#define NGPDE_USE(v)
-#define NGPDE_STAMP_PTR(p) nullptr
-#endif
 
 struct CombDev {
   int n;
@@ -274,12 +244,12 @@ struct NoHook { __device__ __forceinline__ void operator()() const {} };
 template <int D, bool DMA = false, bool POST = true, class Hook = NoHook, bool SCALE = true>
 __device__ __forceinline__ void halo_finish(const HaloRegs<D> &h, bool weighted, int self_loops, int grp, int q,
                                             float *ldsXh, const int4 (&sc)[Geo<D>::R], float4 (&acc)[Geo<D>::R],
-                                            unsigned long long *dbg = nullptr, Hook &&after_barrier = NoHook()) {
+                                            const StampSink *dbg = nullptr, Hook &&after_barrier = NoHook()) {
   using G = Geo<D>;
   float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
   if constexpr (!DMA) {
-    NGPDE_USE(h.hv[0].x); NGPDE_USE(h.hv[G::HI - 1].x);
-    NGPDE_SUBSTAMP(dbg, 1);   // halo rows arrived
+    NGPDE_STAMP_AFTER(h.hv[0].x); NGPDE_STAMP_AFTER(h.hv[G::HI - 1].x);
+    NGPDE_STAMP(dbg, 16, 11, memtime);   // halo rows arrived
 #pragma unroll
     for (int k = 0; k < G::HI; ++k) {
       const int hh = grp + k * G::GROUPS;
@@ -298,9 +268,9 @@ __device__ __forceinline__ void halo_finish(const HaloRegs<D> &h, bool weighted,
     wmax = max(wmax, __shfl_xor(wmax, 4));
   }
   wmax = __builtin_amdgcn_readfirstlane(wmax);
-  NGPDE_SUBSTAMP(dbg, 2);   // LDS written
+  NGPDE_STAMP(dbg, 16, 12, memtime);   // LDS written
   __syncthreads();
-  NGPDE_SUBSTAMP(dbg, 3);   // barrier passed
+  NGPDE_STAMP(dbg, 16, 13, memtime);   // barrier passed
   after_barrier();
 #pragma unroll
   for (int r = 0; r < G::R; ++r) {
@@ -325,8 +295,8 @@ __device__ __forceinline__ void halo_finish(const HaloRegs<D> &h, bool weighted,
     if (self_loops) a = f4_add(a, Xh4[min(grp * G::R + r, kTM - 1) * G::LPR + q]);   // own row = slot (position in tile)
     acc[r] = POST ? f4_scale(ci, a) : a;
   }
-  NGPDE_USE(acc[0].x);
-  NGPDE_SUBSTAMP(dbg, 4);   // LDS aggregation done
+  NGPDE_STAMP_AFTER(acc[0].x);
+  NGPDE_STAMP(dbg, 16, 14, memtime);   // LDS aggregation done
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -369,7 +339,7 @@ __global__ __launch_bounds__(kThreads, (D <= 64 ? 4 : 2)) void gcn_fused_fwd_ker
   const int act = ACT >= 0 ? ACT : p.act;
   const bool active = grp * G::R < kTM;
   const float4 *X4 = reinterpret_cast<const float4 *>(h_x);
-  NGPDE_STAMP(0);
+  NGPDE_STAMP(p.stamps, 16, 0, memtime); NGPDE_STAMP(p.stamps, 16, 1, memrealtime);
 
   // ---- round 1: every load whose address depends on nothing loaded; the gather chain first, pinned in this order
   int4 sc[G::R];
@@ -388,14 +358,14 @@ __global__ __launch_bounds__(kThreads, (D <= 64 ? 4 : 2)) void gcn_fused_fwd_ker
   __builtin_amdgcn_sched_barrier(0);
   // ---- round 2: addresses from round 1 -- the tile's distinct rows, then the node-local stage terms
   if (HALO) {
-    NGPDE_USE(hr.he[0].x);
-    NGPDE_SUBSTAMP(NGPDE_STAMP_PTR(p), 0);   // round-1 data arrived
+    NGPDE_STAMP_AFTER(hr.he[0].x);
+    NGPDE_STAMP(p.stamps, 16, 10, memtime);   // round-1 data arrived
     halo_round2<D, PRE>(X4, q, grp, ldsXh, hr);
   }
   __builtin_amdgcn_sched_barrier(0);
   float4 acc[G::R];
   if (HALO) {
-    halo_finish<D, PRE, true>(hr, h_slot_w != nullptr, p.self_loops, grp, q, ldsXh, sc, acc, NGPDE_STAMP_PTR(p));
+    halo_finish<D, PRE, true>(hr, h_slot_w != nullptr, p.self_loops, grp, q, ldsXh, sc, acc, NGPDE_STAMP_SINK(p));
   } else {
     // (LDS: the product's operand tiles are not written yet -- W waits in registers, the row sums are what this forms)
     // counter + row list (20 words) in W's tile, partial sums in the row tile, the rows' sums in the result tile (kTM x D floats each)
@@ -405,7 +375,7 @@ __global__ __launch_bounds__(kThreads, (D <= 64 ? 4 : 2)) void gcn_fused_fwd_ker
     aggregate_rows<G::LPR, G::R, G::U>(X4, p.ent, p.self_loops, sc, q, ecol, ecf, selfv, acc);
     coop_add<G::LPR, G::R>(sc, grp, q, reinterpret_cast<const float4 *>(ldsZ), acc);
   }
-  NGPDE_STAMP(1);
+  NGPDE_STAMP(p.stamps, 16, 2, memtime); NGPDE_STAMP(p.stamps, 16, 3, memrealtime);
   // W and the stage terms are fetched only after the aggregation: everything issued at kernel start competes in the memory system
   // with the halo rows the workgroup waits for (measured at C2: layer-1 5.98 -> 5.85 us, layer-2 + stage 7.46 -> 7.06 us), and the
   // per-row gather keeps 16 rows in flight.
@@ -446,10 +416,10 @@ __global__ __launch_bounds__(kThreads, (D <= 64 ? 4 : 2)) void gcn_fused_fwd_ker
     }
   }
   __syncthreads();
-  NGPDE_STAMP(2);
+  NGPDE_STAMP(p.stamps, 16, 4, memtime); NGPDE_STAMP(p.stamps, 16, 5, memrealtime);
   mfma_rows_times_bt<D>(ldsT, ldsBt, ldsZ, wave_u, lane);
   __syncthreads();
-  NGPDE_STAMP(3);
+  NGPDE_STAMP(p.stamps, 16, 6, memtime); NGPDE_STAMP(p.stamps, 16, 7, memrealtime);
   if (active) {
 #pragma unroll
     for (int r = 0; r < G::R; ++r) {
@@ -468,7 +438,7 @@ __global__ __launch_bounds__(kThreads, (D <= 64 ? 4 : 2)) void gcn_fused_fwd_ker
       if (p.has_comb) reinterpret_cast<float4 *>(p.comb_out)[idx4] = comb_finish(p.comb, yv, cterm[r]);
     }
   }
-  NGPDE_STAMP(4);
+  NGPDE_STAMP(p.stamps, 16, 8, memtime); NGPDE_STAMP(p.stamps, 16, 9, memrealtime);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -531,7 +501,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
   const int act = ACT >= 0 ? ACT : p.act;
   const bool active = grp * G::R < kTM;
   const float4 *G4 = reinterpret_cast<const float4 *>(h_x);
-  NGPDE_STAMP(0);
+  NGPDE_STAMP(p.stamps, 16, 0, memtime); NGPDE_STAMP(p.stamps, 16, 1, memrealtime);
 
   // ---- round 1 / round 2 of the gather chain first (vmcnt retires in order: slower loads must not sit in front)
   int4 sc[G::R];
@@ -630,7 +600,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
 #pragma unroll
     for (int r = 0; r < G::R; ++r) t[r] = G4[(size_t)max(sc[r].x, 0) * G::LPR + q];
   }
-  NGPDE_STAMP(1);
+  NGPDE_STAMP(p.stamps, 16, 2, memtime); NGPDE_STAMP(p.stamps, 16, 3, memrealtime);
   if (!DMA && p.tape_late) load_tape();
   load_w();   // after the aggregation, as in the forward kernel
   if (active && p.has_comb) {   // adjoint stage terms: one batch of independent node-local loads
@@ -677,11 +647,11 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
     }
   }
   __syncthreads();
-  NGPDE_STAMP(2);
+  NGPDE_STAMP(p.stamps, 16, 4, memtime); NGPDE_STAMP(p.stamps, 16, 5, memrealtime);
   // G = dZ x Wt^T  (gradient w.r.t. the aggregated input)
   mfma_rows_times_bt<D>(ldsDZ, ldsBt, ldsG, wave_u, lane);
   __syncthreads();   // G complete in LDS; W^T no longer needed
-  NGPDE_STAMP(3);
+  NGPDE_STAMP(p.stamps, 16, 6, memtime); NGPDE_STAMP(p.stamps, 16, 7, memrealtime);
   // the product rows leave for memory now and drain under the dW product instead of at the end of the launch
   if (active) {
 #pragma unroll
@@ -692,7 +662,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
       store_stream4(&reinterpret_cast<float4 *>(p.g_out)[(size_t)sc[r].x * G::LPR + q], gv);   // gathered once by the next launch
     }
   }
-  NGPDE_STAMP(4);
+  NGPDE_STAMP(p.stamps, 16, 8, memtime); NGPDE_STAMP(p.stamps, 16, 9, memrealtime);
   // dWt[i][o] += sum_n X3[n][i] dZ[n][o]   (K = kTM rows of this tile)
   const int i = lane & 15, kq = lane >> 4;
 #pragma unroll
@@ -723,7 +693,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
     dbv += s;
     if (!PAIR && dbpart == 0) p.slab_db[(size_t)blockIdx.x * D + dbc] = dbv;
   }
-  NGPDE_STAMP(5);
+  NGPDE_STAMP(p.stamps, 16, 10, memtime); NGPDE_STAMP(p.stamps, 16, 11, memrealtime);
   if (PAIR) {
     // half 1 parks its dW tiles and db partials in its W^T region (idle since the barrier above), half 0 folds them in
     float *park = lds_all + 2 * kXZ + kRest + 2 * kTM * G::TS;   // [NT][64 lanes][4] + [D]
@@ -745,7 +715,7 @@ __global__ __launch_bounds__((PAIR ? 2 : 1) * kThreads, (PAIR || D <= 64 ? 4 : 2
       if (dbpart == 0) p.slab_db[(size_t)blockIdx.x * D + dbc] = dbv + park[NT * 256 + dbc];
     }
   }
-  NGPDE_STAMP(6);
+  NGPDE_STAMP(p.stamps, 16, 12, memtime); NGPDE_STAMP(p.stamps, 16, 13, memrealtime);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -889,15 +859,6 @@ inline int act_template(int act) { return (act == NGPDE_ACT_RELU || act == NGPDE
 
 }  // namespace
 
-#ifdef NGPDE_STAMPS
-extern "C" int32_t ngpde_debug_set_stamps(unsigned long long *dev_buf, int32_t max_launches) {
-  g_stamps_base = dev_buf;
-  g_stamps_max = max_launches;
-  g_stamps_next = 0;
-  return NGPDE_OK;
-}
-#endif
-
 // the pre-scaled pipeline (rows stored as c .* x, gathered raw by LDS-DMA): every tile staged from LDS in both directions,
 // and c finite and positive (self loops: degree >= 1)
 bool fused_prescaled_supported(const ngpde_graph *g, int d) {
@@ -935,7 +896,7 @@ int32_t launch_fused_fwd(const FusedFwdArgs &a, hipStream_t stream) {
   k.wt = a.wt; k.bias = a.bias; k.y = a.y; k.save_agg = a.save_agg; k.save_z = a.save_z;
   k.has_comb = a.has_comb ? 1 : 0; k.comb = to_dev(a.comb); k.comb_out = a.comb_out;
   k.save_mask = a.save_mask;
-  NGPDE_STAMP_SET(k, k.n_tiles)
+  NGPDE_STAMP_SET(k, kStampGcn, (int64_t)k.n_tiles * 16);
   const bool use_halo = g->by_t.halo_ok && !no_halo_env();
   NGPDE_REQUIRE(!a.pre || fused_prescaled_supported(g, a.d), NGPDE_ERR_UNSUPPORTED,
                 "the pre-scaled form needs self loops and tiles that fit the LDS halo in both directions");
@@ -987,7 +948,7 @@ int32_t launch_fused_bwd(const FusedBwdArgs &a, hipStream_t stream) {
   NGPDE_REQUIRE(!a.mask || a.act == NGPDE_ACT_RELU, NGPDE_ERR_INVALID_ARGUMENT, "sign-bit masks carry relu' only");
   k.tape_late = a.has_comb ? 0 : 1;
   k.g_out = a.g_out; k.slab_dw = a.slab_dw; k.slab_db = a.slab_db;
-  NGPDE_STAMP_SET(k, k.n_tiles)
+  NGPDE_STAMP_SET(k, kStampGcn, (int64_t)k.n_tiles * 16);
   const bool use_halo = g->by_s.halo_ok && !no_halo_env();
   NGPDE_REQUIRE(!a.pre || fused_prescaled_supported(g, a.d), NGPDE_ERR_UNSUPPORTED,
                 "the pre-scaled form needs self loops and tiles that fit the LDS halo in both directions");

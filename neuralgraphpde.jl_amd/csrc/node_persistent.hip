@@ -38,6 +38,7 @@
 #include "gcn_tile.h"
 #include "persistent_mem.h"
 #include "persistent_sync.h"
+#include "stamps.h"
 
 namespace ngpde {
 
@@ -50,21 +51,6 @@ constexpr int kXhF = (kHaloCap + 1) * PD;   // halo region (floats), +1: the all
 constexpr int kTileF = kTM * PG::TS;        // one 32-row MFMA operand / result tile
 constexpr int kWF = PD * PG::TS;            // one transposed weight matrix
 constexpr int kMaxTileRounds = 8;            // tile rounds: at most this many tiles per workgroup
-
-#ifdef NGPDE_STAMPS
-// diagnostic build only (tools/stamps_persistent.py): shader-clock stamps of thread 0 at 8 points of the first g_pst_max phases
-unsigned long long *g_pst_base = nullptr;
-int g_pst_max = 0;
-#define NGPDE_PST_FIELD unsigned long long *stamps; int stamps_max;
-#define NGPDE_PST(m, ph, k)                                                                                   \
-  do {                                                                                                        \
-    if (threadIdx.x == 0 && (m).stamps && (ph) <= (m).stamps_max)                                             \
-      (m).stamps[((size_t)blockIdx.x * (m).stamps_max + ((ph) - 1)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-#else
-#define NGPDE_PST_FIELD
-#define NGPDE_PST(m, ph, k)
-#endif
 
 struct TileCtx {
   int tid, lane, wave_u, grp, q, tile, node, hcount, wmax, my_nbr;
@@ -97,7 +83,7 @@ struct TileMeta {
   const int4 *hub_sched;      // [n_sched] {node or -1, 0, 0, bits of c[node]}: the hub geometry's OWN tile partition (see hub_partition)
   const uint8_t *hub_long;    // [n_tiles][kTileRows] rows (0 .. 31) with more than kSlotWidth entries
   const float *hub_w;         // [n_tiles][kHubList] edge weights of the entries, or NULL (unweighted)
-  NGPDE_PST_FIELD
+  NGPDE_STAMP_FIELD
 };
 
 __device__ __forceinline__ void tile_ctx_init(const TileMeta &m, TileCtx &c, float *lds_meta, int tile = -1) {
@@ -210,7 +196,7 @@ __device__ __forceinline__ bool tile_wait(const TileMeta &m, const TileCtx &c, i
 // The same wait with its first round of flag loads issued earlier by the caller (poll_issue: `f` holds wave 0's samples, in flight
 // under whatever the workgroup did in between).  A workgroup that is level with its neighbours finds the flags in that sample
 // and only meets at the barrier; one that runs ahead spins here exactly as long as it leads.  (Used by the interleaved adjoint,
-// whose slot-phase is long enough for the flags to be there.  What the stamps of tools/stamps_interleaved.py say about the hand-off:
+// whose slot-phase is long enough for the flags to be there.  What the stamps of tools/stamps.py interleaved say about the hand-off:
 // a flag store is seen by a poll from another XCD ~3-4 k cycles (1.2-1.5 us) after it was issued, a poll or a gather is a
 // ~1.5 k-cycle round trip, the drain in front of the flag ~1 k: with only two slots the ~2.4 us of hand-off exceed the ~1.7 us of
 // work the other slot offers in the forward kernel -- wherever the look is put, the difference is waited for.)
@@ -677,33 +663,33 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
       for (int layer = 0; layer < 2; ++layer) {
         ++ph;
         const float *X = layer == 0 ? ((n == 0 && i == 0) ? u_in : p.bufA) : p.bufB;
-        NGPDE_PST(p.m, ph, 0);
+        NGPDE_PHASE_STAMP(p.m.stamps, ph, 0);
         float4 agg;
         if constexpr (HUB) {
           unsigned sw[8];
           hub_slot_words(c, sw);
           if (!hub_wait(p.m, c, ph, s_ok)) { ok = false; break; }
-          NGPDE_PST(p.m, ph, 1);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
           hub_gather_foreign(c, X, ldsXh);
-          NGPDE_PST(p.m, ph, 2);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           agg = hub_aggregate(c, sw, ldsXh, ldsZ);   // (the product's output tile is free until this phase's product)
         } else if constexpr (!WGT) {
           unsigned sw[8];
           tile_slot_words(c, sw);
           float4 a = tile_aggregate_rounds_range(c, sw, ldsXh, f4_zero(), 0, of_pre);   // own rows: under the wait
           if (!tile_wait(p.m, c, ph, s_ok)) { ok = false; break; }
-          NGPDE_PST(p.m, ph, 1);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
           tile_gather_foreign(c, X, ldsXh);
-          NGPDE_PST(p.m, ph, 2);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           a = tile_aggregate_rounds_range(c, sw, ldsXh, a, of_pre, (c.wmax + 3) >> 2);
           agg = f4_add(a, Xh4[c.grp * PG::LPR + c.q]);
         } else {
           unsigned sw[8];
           tile_slot_words(c, sw);
           if (!tile_wait(p.m, c, ph, s_ok)) { ok = false; break; }
-          NGPDE_PST(p.m, ph, 1);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
           tile_gather_foreign(c, X, ldsXh);
-          NGPDE_PST(p.m, ph, 2);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           agg = tile_aggregate_weighted(c, ldsXh);
         }
         float4 acc = f4_scale(c.ci, agg);   // a_i = c_i * sum of the stored (pre-scaled) rows
@@ -711,11 +697,11 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
         const size_t ev = ev0 + (size_t)(n * p.S + i) * 2 + layer;
         if (TAPE && c.valid) st4_stream_g(p.tape + ev * p.row_elems, own, acc);
         __syncthreads();
-        NGPDE_PST(p.m, ph, 3);
+        NGPDE_PHASE_STAMP(p.m.stamps, ph, 3);
         if (WGT && layer == 0) mfma_rows_times_bfrag64(ldsT, bw1, ldsZ, c.wave_u, c.lane);
         else mfma_rows_times_bt<PD>(ldsT, layer == 0 ? ldsW1 : ldsW2, ldsZ, c.wave_u, c.lane);
         __syncthreads();
-        NGPDE_PST(p.m, ph, 4);
+        NGPDE_PHASE_STAMP(p.m.stamps, ph, 4);
         const float4 z = f4_add(*reinterpret_cast<const float4 *>(&ldsZ[c.grp * PG::TS + 4 * c.q]), layer == 0 ? bias1 : bias2);
         const uint8_t sign_bits = (uint8_t)((z.x > 0.f ? 1 : 0) | (z.y > 0.f ? 2 : 0) | (z.z > 0.f ? 4 : 0) | (z.w > 0.f ? 8 : 0));
         float4 yv = f4_sel(c.valid, f4_scale(c.ci, f4_act(act, z)), f4_zero());   // stored as c .* y
@@ -736,9 +722,9 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
           if (c.valid) store_sc1(p.bufA, own, v);
           Xh4[c.grp * PG::LPR + c.q] = v;
         }
-        NGPDE_PST(p.m, ph, 5);
+        NGPDE_PHASE_STAMP(p.m.stamps, ph, 5);
         tile_publish(p.m, c, ph);
-        NGPDE_PST(p.m, ph, 6);
+        NGPDE_PHASE_STAMP(p.m.stamps, ph, 6);
         // relu' for the adjoint (any other activation: the pre-activation itself): only the adjoint launch reads it, so it leaves
         // after the rows are published
         if constexpr (TAPE && ACT == NGPDE_ACT_RELU) stu8_g(p.masks + ev * p.mask_bytes + (size_t)c.tile * kThreads, (unsigned)c.tid, sign_bits);
@@ -937,10 +923,10 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
           const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
           // ---- T0
           [[maybe_unused]] const int turn = (ph - 1) * KT + s + 1;   // (stamps: one record per turn)
-          NGPDE_PST(p.m, turn, 0);
+          NGPDE_PHASE_STAMP(p.m.stamps, turn, 0);
           wait_vmcnt0();
           __syncthreads();
-          NGPDE_PST(p.m, turn, 1);
+          NGPDE_PHASE_STAMP(p.m.stamps, turn, 1);
           n_ahead += pre ? 1 : 0;
           if (pend_flags && tid == 0) __hip_atomic_store(pend_flags, (unsigned)pend_ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           pend_flags = nullptr;
@@ -951,7 +937,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
             wait_vmcnt0();
             __syncthreads();
           }
-          NGPDE_PST(p.m, turn, 2);
+          NGPDE_PHASE_STAMP(p.m.stamps, turn, 2);
           // ---- the turn after this one: the next tile of this phase, or this workgroup's first tile in the next phase
           const bool same_phase = s + 1 < KT;
           const int ns = same_phase ? s + 1 : 0, nph = same_phase ? ph : ph + 1, nlayer = same_phase ? layer : 1 - layer;
@@ -978,7 +964,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
           }
           __syncthreads();
           // ---- T2: the halo region is free; the next turn's rows travel under the product and the epilogue
-          NGPDE_PST(p.m, turn, 3);
+          NGPDE_PHASE_STAMP(p.m.stamps, turn, 3);
           pre = *s_pre != 0;
           TileCtx cn;
           unsigned ownn = 0;
@@ -987,11 +973,11 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
             ownn = (unsigned)cn.node * (unsigned)(PD * 4) + (unsigned)(cn.q * 16);
             halo_fill_all(cn, nX, ldsXh);
           }
-          NGPDE_PST(p.m, turn, 4);
+          NGPDE_PHASE_STAMP(p.m.stamps, turn, 4);
           if (layer == 0) mfma_rows_times_bfrag64(ldsT, bw1, ldsZ, wave_u, lane);
           else mfma_rows_times_bt<PD>(ldsT, ldsW, ldsZ, wave_u, lane);
           __syncthreads();
-          NGPDE_PST(p.m, turn, 5);
+          NGPDE_PHASE_STAMP(p.m.stamps, turn, 5);
           // ---- T5
           const float4 z = f4_add(*reinterpret_cast<const float4 *>(&ldsZ[c.grp * PG::TS + 4 * c.q]), layer == 0 ? bias1 : bias2);
           const float cself = ldsC[36 + i], cf0 = ldsC[i * 6 + 0], cf1 = ldsC[i * 6 + 1], cf2 = ldsC[i * 6 + 2], cf3 = ldsC[i * 6 + 3],
@@ -1018,7 +1004,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
           pend_ph = ph;
           if constexpr (TAPE && ACT == NGPDE_ACT_RELU) stu8_g(p.masks + ev * p.mask_bytes + (size_t)tile * kThreads, (unsigned)tid, sign_bits);
           else if (TAPE && c.valid) st4_stream_g(p.ztape + ev * p.row_elems, own, z);
-          NGPDE_PST(p.m, turn, 6);
+          NGPDE_PHASE_STAMP(p.m.stamps, turn, 6);
         }
       }
     }
@@ -1086,7 +1072,7 @@ __device__ __forceinline__ bool fwd_slot_phase(const PFwdK &p, const TileCtx &c,
   float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
   float *bufA = p.bufA + (PAIR ? 0 : (size_t)sl * p.row_elems), *bufB = p.bufB + (PAIR ? 0 : (size_t)sl * p.row_elems);
   unsigned *flags = p.m.flags + (PAIR ? 0 : (size_t)sl * p.flag_stride);
-  NGPDE_PST(p.m, ph, 0);
+  NGPDE_PHASE_STAMP(p.m.stamps, ph, 0);
   // T0
   wait_vmcnt0();
   __syncthreads();
@@ -1098,10 +1084,10 @@ __device__ __forceinline__ bool fwd_slot_phase(const PFwdK &p, const TileCtx &c,
   if (!pre) {
     Xh4[c.grp * PG::LPR + c.q] = S.xown;   // (behind the barrier: nobody is still aggregating from the halo region)
     if (!tile_wait(p.m, c, ph, s_ok, flags)) return false;
-    NGPDE_PST(p.m, ph, 1);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
     tile_gather_foreign(c, X, ldsXh);
   }
-  NGPDE_PST(p.m, ph, 2);
+  NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
   // T1
   float4 acc = f4_scale(c.ci, tile_aggregate(c, sw, ldsXh));
   *reinterpret_cast<float4 *>(&ldsT[c.grp * PG::TS + 4 * c.q]) = acc;
@@ -1111,7 +1097,7 @@ __device__ __forceinline__ bool fwd_slot_phase(const PFwdK &p, const TileCtx &c,
   __syncthreads();
   unsigned f1 = 0;
   if (nx.exists && c.wave_u == 0) f1 = poll_issue(p.m, cn, nx.flags);
-  NGPDE_PST(p.m, ph, 3);
+  NGPDE_PHASE_STAMP(p.m.stamps, ph, 3);
   // T3
   mfma_rows_times_bt<PD>(ldsT, ldsW, ldsZ, c.wave_u, c.lane);
   // T4.  (A workgroup that runs AHEAD of its neighbours looks too early -- their flags of the phase before are published at the
@@ -1123,7 +1109,7 @@ __device__ __forceinline__ bool fwd_slot_phase(const PFwdK &p, const TileCtx &c,
     if (c.lane == 0) *s_pre = hit ? 1 : 0;
   }
   __syncthreads();
-  NGPDE_PST(p.m, ph, 4);
+  NGPDE_PHASE_STAMP(p.m.stamps, ph, 4);
   // T5.  Every LDS read of the epilogue comes BEFORE a DMA is issued (see halo_fill_ahead)
   pre = *s_pre != 0;
   const float4 z = f4_add(*reinterpret_cast<const float4 *>(&ldsZ[c.grp * PG::TS + 4 * c.q]), reinterpret_cast<const float4 *>(ldsBias)[c.q]);
@@ -1150,11 +1136,11 @@ __device__ __forceinline__ bool fwd_slot_phase(const PFwdK &p, const TileCtx &c,
     if (c.valid) store_sc1(bufA, own, v);
     S.xown = v;
   }
-  NGPDE_PST(p.m, ph, 5);
+  NGPDE_PHASE_STAMP(p.m.stamps, ph, 5);
   pend_flags = flags + 32 * c.tile;     // published at the next T0 (or behind the loops)
   pend_ph = ph;
   if (TAPE) stu8_g(p.masks + ev * p.mask_bytes + (size_t)c.tile * kThreads, (unsigned)c.tid, sign_bits);
-  NGPDE_PST(p.m, ph, 6);
+  NGPDE_PHASE_STAMP(p.m.stamps, ph, 6);
   return true;
 }
 
@@ -1344,16 +1330,16 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
     *reinterpret_cast<float4 *>(&ldsDZ[c.grp * PG::TS + 4 * c.q]) = dz;
     *reinterpret_cast<float4 *>(&ldsX[c.grp * PG::TS + 4 * c.q]) = f4_sel(c.valid, xrow, f4_zero());
     __syncthreads();
-    NGPDE_PST(p.m, ph, 3);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 3);
     if (WGT && ldsW == ldsW1) mfma_rows_times_bswz64(ldsDZ, ldsW, ldsG, c.wave_u, c.lane);   // (layer 1 of a weighted graph: the unpadded, swizzled W1)
     else mfma_rows_times_bt<PD>(ldsDZ, ldsW, ldsG, c.wave_u, c.lane);
     __syncthreads();
-    NGPDE_PST(p.m, ph, 4);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 4);
     const float4 gv = f4_sel(c.valid, f4_scale(c.ci, *reinterpret_cast<const float4 *>(&ldsG[c.grp * PG::TS + 4 * c.q])), f4_zero());
     if (c.valid) store_sc1(gout, own, gv);
-    NGPDE_PST(p.m, ph, 5);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 5);
     tile_publish(p.m, c, ph);
-    NGPDE_PST(p.m, ph, 6);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 6);
     Xh4[c.grp * PG::LPR + c.q] = gv;   // behind the barrier: every thread has read its row of G (same LDS region)
     if constexpr (!HUB) {
       if (c.wave_u == 0) f_next = poll_issue(p.m, c, p.m.flags);
@@ -1393,7 +1379,7 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
       for (int o = 1; o < PG::DBP; o <<= 1) s += __shfl_xor(s, o);
       dbl += s;
     }
-    NGPDE_PST(p.m, ph, 7);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 7);
   };
 
   bool ok = true;
@@ -1414,7 +1400,7 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
     for (int i = S - 1; i >= 0 && ok; --i) {
       {   // layer 1 of stage i: dL/dy1 = A^T g2
         ++ph;
-        NGPDE_PST(p.m, ph, 0);
+        NGPDE_PHASE_STAMP(p.m.stamps, ph, 0);
         const Aux mk = mk_n;                      // asked for behind the publish of the phase before
         const float4 xrow = xrow_n;
         // next: layer 2 of the stage evaluated before this one (none in the very last phase of the member)
@@ -1425,23 +1411,23 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
           unsigned sw[8];
           hub_slot_words(c, sw);
           if (!hub_wait(p.m, c, ph, s_ok)) { ok = false; break; }
-          NGPDE_PST(p.m, ph, 1);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
           hub_gather_foreign(c, p.g2, ldsXh);
-          NGPDE_PST(p.m, ph, 2);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           t = hub_aggregate(c, sw, ldsXh, ldsDZ);   // (the operand tiles of the previous phase's products are dead: that phase ended at this wait's barrier)
         } else if constexpr (WGT) {
           if (!tile_wait_primed(p.m, c, ph, s_ok, p.m.flags, f_next)) { ok = false; break; }
-          NGPDE_PST(p.m, ph, 1);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
           tile_gather_foreign(c, p.g2, ldsXh);
-          NGPDE_PST(p.m, ph, 2);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           t = tile_aggregate_weighted(c, ldsXh);
         } else {
           unsigned sw[8];
           tile_slot_words(c, sw);
           if (!tile_wait_primed(p.m, c, ph, s_ok, p.m.flags, f_next)) { ok = false; break; }
-          NGPDE_PST(p.m, ph, 1);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
           tile_gather_foreign(c, p.g2, ldsXh);
-          NGPDE_PST(p.m, ph, 2);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           t = f4_add(tile_aggregate_rounds_range(c, sw, ldsXh, f4_zero(), 0, (c.wmax + 3) >> 2), Xh4[c.grp * PG::LPR + c.q]);
         }
         dense(ph, ldsW1, dw1, db1, t, mk, xrow, p.g1, !last_next, ev_next);
@@ -1449,7 +1435,7 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
       {   // U-bar_i = A^T g1; K-bar of the stage evaluated before it (or the lambda update), layer 2's dense half
         ++ph;
         const bool last = (i == 0 && n == 0);
-        NGPDE_PST(p.m, ph, 0);
+        NGPDE_PHASE_STAMP(p.m.stamps, ph, 0);
         const Aux mk = mk_n;                      // (the last phase of a member runs no dense half: nothing was asked for)
         const float4 xrow = xrow_n;
         // next: layer 1 of stage i - 1, or of the last stage of the step before
@@ -1459,23 +1445,23 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
           unsigned sw[8];
           hub_slot_words(c, sw);
           if (!hub_wait(p.m, c, ph, s_ok)) { ok = false; break; }
-          NGPDE_PST(p.m, ph, 1);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
           hub_gather_foreign(c, p.g1, ldsXh);
-          NGPDE_PST(p.m, ph, 2);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           t = hub_aggregate(c, sw, ldsXh, ldsDZ);   // (the operand tiles of the previous phase's products are dead: that phase ended at this wait's barrier)
         } else if constexpr (WGT) {
           if (!tile_wait_primed(p.m, c, ph, s_ok, p.m.flags, f_next)) { ok = false; break; }
-          NGPDE_PST(p.m, ph, 1);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
           tile_gather_foreign(c, p.g1, ldsXh);
-          NGPDE_PST(p.m, ph, 2);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           t = tile_aggregate_weighted(c, ldsXh);
         } else {
           unsigned sw[8];
           tile_slot_words(c, sw);
           if (!tile_wait_primed(p.m, c, ph, s_ok, p.m.flags, f_next)) { ok = false; break; }
-          NGPDE_PST(p.m, ph, 1);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
           tile_gather_foreign(c, p.g1, ldsXh);
-          NGPDE_PST(p.m, ph, 2);
+          NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           t = f4_add(tile_aggregate_rounds_range(c, sw, ldsXh, f4_zero(), 0, (c.wmax + 3) >> 2), Xh4[c.grp * PG::LPR + c.q]);
         }
         float4 kbar;
@@ -1636,7 +1622,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
       pf_mk = ldu8_g(p.masks + nx.ev * p.mask_bytes + (size_t)cn.tile * kThreads, (unsigned)c.tid);
       pf_x = ld4_stream_g(p.tape + nx.ev * p.row_elems, ownn);
     }
-    NGPDE_PST(p.m, ph, 3);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 3);
     // T3: both matrix products of the phase back to back (no barrier between them: they read the same operand tiles and write
     // different things): G = dZ W^T into the halo region (free since T2), then dW += A^T dZ, db.  Wave 0 fetches the next
     // slot-phase's flags between the two -- as late as it can be done with the answer still there when the products end
@@ -1660,14 +1646,14 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
       __syncthreads();
       pre = false;
     }
-    NGPDE_PST(p.m, ph, 4);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 4);
     const float4 gv = f4_sel(c.valid, f4_scale(c.ci, *reinterpret_cast<const float4 *>(&ldsG[c.grp * PG::TS + 4 * c.q])), f4_zero());
     if (pre) {   // uniform
       __syncthreads();   // every thread has read its row of G: the region is the halo again
       halo_fill_all(cn, nx.X, ldsXh);
     }
     if (c.valid) store_sc1(gout, own, gv);
-    NGPDE_PST(p.m, ph, 5);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 5);
     pend_flags = flags + 32 * c.tile;
     pend_ph = ph;
   };
@@ -1678,12 +1664,12 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
     n_ahead += pre ? 1 : 0;
     if (!pre) {
       if (!tile_wait(p.m, c, ph, s_ok, flags)) return false;
-      NGPDE_PST(p.m, ph, 1);
+      NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
       halo_fill_all(c, X, ldsXh);
       wait_vmcnt0();
       __syncthreads();
     }
-    NGPDE_PST(p.m, ph, 2);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
     return true;
   };
 
@@ -1691,7 +1677,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
   auto phase_l1 = [&](const TileCtx &c, const TileCtx &cn, unsigned own, unsigned ownn, int sl, int ph, const BNext &nx) -> bool {
     float *g1 = p.g1 + (PAIR ? 0 : (size_t)sl * p.row_elems), *g2 = p.g2 + (PAIR ? 0 : (size_t)sl * p.row_elems);
     unsigned *flags = p.m.flags + (PAIR ? 0 : (size_t)sl * p.flag_stride);
-    NGPDE_PST(p.m, ph, 0);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 0);
     const unsigned mk = pf_mk;
     const float4 xrow = pf_x;
     if (!top(c, flags, ph, g2)) return false;
@@ -1707,7 +1693,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
     float *g1 = p.g1 + (PAIR ? 0 : (size_t)sl * p.row_elems), *g2 = p.g2 + (PAIR ? 0 : (size_t)sl * p.row_elems);
     float *ubar = p.ubar + (PAIR ? 0 : (size_t)sl * 5 * p.row_elems);   // (tile pairs: the rows of one member)
     unsigned *flags = p.m.flags + (PAIR ? 0 : (size_t)sl * p.flag_stride);
-    NGPDE_PST(p.m, ph, 0);
+    NGPDE_PHASE_STAMP(p.m.stamps, ph, 0);
     const unsigned mk = pf_mk;
     const float4 xrow = pf_x;
     if (!top(c, flags, ph, g1)) return false;
@@ -2904,20 +2890,10 @@ TileMeta make_meta(const Csr &c, const NodePersist &ps, int dir, const OwnFirst 
   if (ps.hub) m.slot_w = nullptr;   // (the hub geometry reads its own weight lists)
   m.flags = ps.sync; m.abort_word = sync_abort_word(ps.sync, ps.n_tiles); m.n_tiles = ps.n_tiles;
   m.stats = ps.stats;
-#ifdef NGPDE_STAMPS
-  m.stamps = g_pst_base; m.stamps_max = g_pst_max;
-#endif
+  NGPDE_STAMP_SET(m, kStampPersistent, 0);
   return m;
 }
 }  // namespace
-
-#ifdef NGPDE_STAMPS
-extern "C" int32_t ngpde_debug_set_persistent_stamps(unsigned long long *dev_buf, int32_t max_phases) {
-  g_pst_base = dev_buf;   // [n_tiles][max_phases][8], or NULL
-  g_pst_max = max_phases;
-  return NGPDE_OK;
-}
-#endif
 
 // A persistent launch needs ALL its workgroups resident, and two of them in flight on one device (two plans on two streams) can
 // starve each other of residency until both time out.  Inside one process they are therefore made to take turns: every persistent

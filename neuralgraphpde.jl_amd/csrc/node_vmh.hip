@@ -40,6 +40,7 @@
 #include "device_utils.h"
 #include "persistent_mem.h"
 #include "persistent_sync.h"
+#include "stamps.h"
 
 namespace ngpde {
 
@@ -52,21 +53,6 @@ constexpr int VR = 16;                // target rows of a half tile (the unit of
 constexpr int VTS = VW + 4;           // staging tile stride
 constexpr int VNbr = 64;
 constexpr int kVmhMaxTurns = 64;       // tile rounds: tiles per workgroup (64 x 256 CUs x 32 rows = 524 288 nodes)
-
-#ifdef NGPDE_STAMPS
-// diagnostic build only (tools/stamps_vmh.py): shader-clock stamps of thread 0 at 8 points of the first g_vst_max phases
-unsigned long long *g_vst_base = nullptr;
-int g_vst_max = 0;
-#define NGPDE_VST_FIELD unsigned long long *stamps; int stamps_max;
-#define NGPDE_VST(m, ph, k)                                                                                   \
-  do {                                                                                                        \
-    if (threadIdx.x == 0 && (m).stamps && (ph) <= (m).stamps_max)                                             \
-      (m).stamps[((size_t)blockIdx.x * (m).stamps_max + ((ph) - 1)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-#else
-#define NGPDE_VST_FIELD
-#define NGPDE_VST(m, ph, k)
-#endif
 
 struct VmhMeta {
   const int4 *sched_t;
@@ -86,7 +72,7 @@ struct VmhMeta {
   const int *srcpos, *srcdeg;        // by schedule row: positions of the node's out-edges in the by-target order, their count (launch_vmh_srcpos)
   int evals;                         // right-hand-side evaluations of a solve: the tapes are [layer][evals][rows][64] (a layer's rows contiguous)
   int s_rows;                        // rows of the staging tile: 64, 96 or 128 (what the LDS left by the weights allows)
-  NGPDE_VST_FIELD
+  NGPDE_STAMP_FIELD
 };
 
 // derivative of an activation from its OUTPUT y = act(z)
@@ -482,12 +468,12 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_fwd_kernel(const VmhFwdK p) {
         pre_h = (hn != h && pre_ph <= last_ph) ? hn : -1;      // (a workgroup's only tile keeps its state in registers: nothing to fetch)
         if (pre_h >= 0) vctx_fetch_a<VRT>(m, pre_h, pre, false);
       }
-      NGPDE_VST(m, ph, 0);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 0);
       if (!vmh_wait(m, c, ph - 1, t.s_ok)) { ok = false; break; }
-      NGPDE_VST(m, ph, 1);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 1);
       if (c.tid < c.hcount) t.hh[c.tid] = ph == 1 ? X[t.hnode[c.tid]] : ld_sc1(X + t.hnode[c.tid]);
       __syncthreads();
-      NGPDE_VST(m, ph, 2);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 2);
       // ---- message MLP per 16-edge wave slice, messages summed per target through the staging tile
       float4 racc = f4_zero();
       const int lo = t.off[rg], hi = has_row ? t.off[rg + 1] : t.off[rg];
@@ -553,7 +539,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_fwd_kernel(const VmhFwdK p) {
             }
           }
         }
-        NGPDE_VST(m, ph, 3);
+        NGPDE_PHASE_STAMP(m.stamps, ph, 3);
         // messages through the staging tile, as many waves at a time as it has 16-row blocks (all, when the LDS left by the
         // weights allows); lane group r sums the rows of target r in edge order
         const int sw = m.s_rows >> 4;
@@ -566,7 +552,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_fwd_kernel(const VmhFwdK p) {
             for (int mt = 0; mt < 4; ++mt) *reinterpret_cast<float4 *>(&mine[ei * VTS + 16 * mt + 4 * kq]) = msg[mt];
           }
           __syncthreads();
-          if (rd == 0 && w0 == 0) NGPDE_VST(m, ph, 7);   // (diagnostic build: every wave's messages of the first step are staged)
+          if (rd == 0 && w0 == 0) NGPDE_PHASE_STAMP(m.stamps, ph, 7);   // (diagnostic build: every wave's messages of the first step are staged)
           {
             const float *base = t.S + 4 * c.q - cs * VTS;
             const int ce = min(cs + 16 * sw, c0 + VROUND);   // (the last wave group of a round may be a partial one)
@@ -575,7 +561,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_fwd_kernel(const VmhFwdK p) {
           __syncthreads();
         }
       }
-      NGPDE_VST(m, ph, 4);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 4);
       if constexpr (ROUNDS) {   // part B of the next turn's prefetch: the halo nodes' positions and the rows' state (part A has landed by now)
         if (pre_h >= 0) {
           vctx_fetch_px(m, pre);
@@ -647,7 +633,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_fwd_kernel(const VmhFwdK p) {
         if (g_on) *reinterpret_cast<float4 *>(&tout[(16 * rgp + ei) * VTS + 16 * mt + 4 * kq]) = zo;
         __syncthreads();
       }
-      NGPDE_VST(m, ph, 5);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 5);
       // ---- stage derivative k_i = gamma's output (column 0); the next stage input (or the step update) of the own nodes
       const float *tfin = (m.n_gam & 1) ? tB : tA;
       if (c.tid < VRT) {
@@ -664,7 +650,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_fwd_kernel(const VmhFwdK p) {
         if (my_node >= 0) st_sc1(Xn + my_node, v);
       }
       vmh_publish(m, c, ph, ROUNDS);
-      NGPDE_VST(m, ph, 6);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 6);
       if (ROUNDS && my_node >= 0) {
         p.state[my_node] = su; p.state[N + my_node] = sk0; p.state[2 * N + my_node] = sk1; p.state[3 * N + my_node] = sk2;
         p.state[4 * N + my_node] = sk3; p.state[5 * N + my_node] = sk4;
@@ -834,7 +820,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_bwd_kernel(const VmhBwdK p) {
   // the second half of a phase: the by-source gather behind the hand-off, the stage adjoint (false: the wait gave up)
   auto pass2 = [&](int ph2, int i2, const float *dsrc2) -> bool {
     if (!vmh_wait(m, c, ph2, t.s_ok)) return false;
-    NGPDE_VST(m, ph2, 6);
+    NGPDE_PHASE_STAMP(m.stamps, ph2, 6);
     {   // the by-source sum: the out-edges of row g16 (16 lanes, two entries each), then a fixed-order lane reduction
       const int dg = has_row ? s_srcdeg[rg] : 0;
       float a = 0.f;
@@ -900,7 +886,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_bwd_kernel(const VmhBwdK p) {
       if constexpr (ROUNDS) {
         const int h = blockIdx.x + s * G;
         if (h >= nh) break;
-        NGPDE_VST(m, ph, 7);
+        NGPDE_PHASE_STAMP(m.stamps, ph, 7);
         float own_sum = 0.f;
         if (pre_h == h) {      // tables, by-source positions and the rows' state from what the turn before asked for
           vctx_commit<VRT>(m, c, t, h, pre);
@@ -934,7 +920,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_bwd_kernel(const VmhBwdK p) {
 #pragma unroll
           for (int l = 0; l < kVmhMaxL - 1; ++l) fetch_y(l, ev, 0);   // (the first round's; a later round's rows are asked for a round ahead)
         }
-        NGPDE_VST(m, ph, 5);
+        NGPDE_PHASE_STAMP(m.stamps, ph, 5);
         if (ph > 1) {
           if (my_node >= 0) s_row[VRT + c.tid] = own_sum;
           __syncthreads();
@@ -952,7 +938,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_bwd_kernel(const VmhBwdK p) {
       // a state saved after step n + 1 hands its cotangent to lambda before step n + 1 is walked back
       if (i == S - 1 && p.dsave && n + 1 < p.n_steps && (n + 1) % p.save_every == 0 && my_node >= 0)
         lam += p.dsave[(size_t)((n + 1) / p.save_every - 1 + p.save_off) * N + my_node];
-      NGPDE_VST(m, ph, 0);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 0);
       // ---- K-bar_i of the own nodes -> the gradient of gamma's output (column 0 of tile A)
       if (c.tid < VRT) {
         float kbar = t.misc[i * 8 + i] * lam;
@@ -1014,7 +1000,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_bwd_kernel(const VmhBwdK p) {
       }
       // d(gamma's input) = [dh_i; dm_i]: tile tgin, row r; the message gradient is scaled by 1 / deg (mean)
       const float *tgin = (m.n_gam & 1) ? tB : tA;
-      NGPDE_VST(m, ph, 1);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 1);
       // ---- phi backwards per 16-edge wave slice
       for (int k = c.tid; k < c.total; k += VT) s_es[k] = 0.f;
       __syncthreads();
@@ -1090,17 +1076,17 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_bwd_kernel(const VmhBwdK p) {
           }
         }
       }
-      NGPDE_VST(m, ph, 2);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 2);
       if constexpr (ROUNDS) fetch_b();   // (part A of the next turn's prefetch has landed by now)
       __syncthreads();
-      NGPDE_VST(m, ph, 3);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 3);
       if (c.tid < VRT) {   // what the own rows get from their own edges and from gamma
         float a = tgin[c.tid * VTS];
         for (int k = t.off[c.tid]; k < t.off[c.tid + 1]; ++k) a += s_es[k];
         s_row[VRT + c.tid] = a;
       }
       vmh_publish(m, c, ph, ROUNDS);
-      NGPDE_VST(m, ph, 4);
+      NGPDE_PHASE_STAMP(m.stamps, ph, 4);
       if constexpr (ROUNDS) {
         store_state();
         if (my_node >= 0) p.state[(size_t)7 * N + my_node] = s_row[VRT + c.tid];          // the rows' own sums wait for the next sweep
@@ -1112,7 +1098,7 @@ __global__ __launch_bounds__(VT, 1) void node_vmh_bwd_kernel(const VmhBwdK p) {
         have_prev = true;
         ev_prev = ev;
         if (ev > 0) fetch_phase(ev - 1);
-        NGPDE_VST(m, ph, 5);
+        NGPDE_PHASE_STAMP(m.stamps, ph, 5);
         if (!pass2(ph, i, dsrc)) { ok = false; break; }
       }
     }
@@ -1250,9 +1236,7 @@ static void fill_meta(VmhMeta &m, const VmhLaunch &a) {
   m.n_edges = (size_t)g->n_edges;
   m.srcpos = a.srcpos; m.srcdeg = a.srcdeg;
   m.evals = a.n_steps * a.S;
-#ifdef NGPDE_STAMPS
-  m.stamps = g_vst_base; m.stamps_max = g_vst_max;
-#endif
+  NGPDE_STAMP_SET(m, kStampVmh, 0);
 }
 
 int32_t launch_node_vmh_fwd(const VmhLaunch &a, hipStream_t stream) {
@@ -1334,11 +1318,3 @@ int32_t launch_vmh_copy_block(const float *src, int sp, float *dst, int dp, int 
 }
 
 }  // namespace ngpde
-
-#ifdef NGPDE_STAMPS
-extern "C" int32_t ngpde_debug_set_vmh_stamps(unsigned long long *dev_buf, int32_t max_phases) {
-  ngpde::g_vst_base = dev_buf;
-  ngpde::g_vst_max = max_phases;
-  return 0;
-}
-#endif

@@ -1,4 +1,4 @@
-"""Summarise the round-3 counter passes of tools/profile_round3.sh: per persistent launch (one-member kernel, two-member
+"""Summarise the round-3 counter passes (profiles/r03_a_*): per persistent launch (one-member kernel, two-member
 interleaved kernel, tile-pair kernel) HBM bytes (FETCH_SIZE x 2 + WRITE_SIZE, KiB units, the gfx950 correction of
 tools/pmc_summary.py), matrix-pipe busy share of the SIMD cycles and LDS bank-conflict share of the LDS-active cycles.
 

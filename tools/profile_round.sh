@@ -36,12 +36,12 @@ STEPS=20 TAB=tsit5 REPS=5 timeout 200 python3 tools/debug_vmh_node.py > $O/vmh_n
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/vmh_stats -o k -- python3 $R/tools/debug_vmh_node.py > $O/vmh_stats.log 2>&1
 cd $R
-[ -f neuralgraphpde.jl_amd/libngpde_diag.so ] && timeout 200 python3 tools/stamps_vmh.py > $O/vmh_stamps.txt 2>/dev/null
+[ -f neuralgraphpde.jl_amd/libngpde_diag.so ] && timeout 200 python3 tools/stamps.py vmh > $O/vmh_stamps.txt 2>/dev/null
 python3 tools/hbm_rw_probe.py > $O/hbm_rw_probe.jsonl 2>/dev/null
-[ -f neuralgraphpde.jl_amd/libngpde_diag.so ] && timeout 200 python3 tools/stamps_pair.py > $O/pair_stamps.txt 2>/dev/null
+[ -f neuralgraphpde.jl_amd/libngpde_diag.so ] && timeout 200 python3 tools/stamps.py pair > $O/pair_stamps.txt 2>/dev/null
 # does the fp32 matrix instruction run beside the VALU?
 hipcc --offload-arch=gfx950 -O3 tools/mfma_valu_overlap.hip -o /tmp/ovl 2>/dev/null && timeout 120 /tmp/ovl > $O/mfma_valu_overlap.jsonl 2>/dev/null
-[ -f neuralgraphpde.jl_amd/libngpde_diag.so ] && timeout 200 python3 tools/stamps_edge64.py 64 > $O/edge64_stamps.txt 2>/dev/null
+[ -f neuralgraphpde.jl_amd/libngpde_diag.so ] && timeout 200 python3 tools/stamps.py edge64 64 > $O/edge64_stamps.txt 2>/dev/null
 python3 tools/bench_gcn_anywidth.py > $O/gcn_anywidth.jsonl 2>/dev/null
 python3 tools/trace_generic_node.py 50 > $O/generic_node.jsonl 2>/dev/null
 python3 tools/trace_generic_node.py 50 capture >> $O/generic_node.jsonl 2>/dev/null

@@ -1,5 +1,5 @@
-"""Which tiles set the pace of the persistent solver?  Reads the per-workgroup stamp segments that `DUMP=1 python3 tools/stamps_persistent.py`
-leaves in gpurun_out/stamps_{fwd,bwd}.npy (diagnostic build) and relates a workgroup's own work per phase (everything but the wait) to its
+"""Which tiles set the pace of the persistent solver?  Reads the per-workgroup stamp segments that `DUMP=1 python3 tools/stamps.py persistent`
+leaves in stamps_{fwd,bwd}.npy (diagnostic build; read from the directory given as the first argument, else the current one) and relates a workgroup's own work per phase (everything but the wait) to its
 tile: referenced rows, sum and maximum of the degrees, aggregation rounds of its slowest wave, and the XCD it runs on.  Finding of round 5
 (DESIGN 5.2): the phase period is the cycle through two neighbouring tiles -- the mean of their own work plus one hand-off; own work spreads 5.1 k - 6.8 k cycles (5 - 95 %) in
 the forward with correlations of only 0.2 - 0.3 to any tile property (+ ~150 cycles per aggregation round); the workgroups of XCD 2 are
@@ -7,6 +7,7 @@ the forward with correlations of only 0.2 - 0.3 to any tile property (+ ~150 cyc
 import os, sys, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
+DIR = sys.argv[1] if len(sys.argv) > 1 else "."
 import ngpde_amd as ng
 from ngpde_amd import _lib, synth as S
 N, PAIRS = 16384, 65536
@@ -31,7 +32,7 @@ tile_max, tile_sum = td.max(1), td.sum(1)
 wave_max = td.reshape(nt, 8, 4).max(2)
 rounds = np.ceil(wave_max / 4).max(1)
 for which in ("fwd", "bwd"):
-    a = np.load(f"gpurun_out/stamps_{which}.npy")
+    a = np.load(os.path.join(DIR, f"stamps_{which}.npy"))
     b = np.arange(nt)
     tile_of_b = (b % 8) * (nt // 8) + b // 8
     own = a[:, 1:].sum(1)
@@ -42,7 +43,7 @@ for which in ("fwd", "bwd"):
         sel = b % 8 == x
         print(f"  xcd {x}: halo {hc[tile_of_b][sel].mean():.1f} sum deg {tile_sum[tile_of_b][sel].mean():.0f} max deg {tile_max[tile_of_b][sel].mean():.1f} | own {own[sel].mean():.0f} agg {agg[sel].mean():.0f}")
 for which in ("fwd", "bwd"):
-    a = np.load(f"gpurun_out/stamps_{which}.npy")
+    a = np.load(os.path.join(DIR, f"stamps_{which}.npy"))
     b = np.arange(nt)
     tile_of_b = (b % 8) * (nt // 8) + b // 8
     own = a[:, 1:].sum(1); agg = a[:, 2]
