@@ -597,6 +597,67 @@ int32_t ngpde_rk_stage_combine(int64_t count, float c_self, const float *base, i
  * ngpde_rk_stage_combine(count, 1, acc, 1, {g}, {1}, acc) per array: fma(1, g, 1 * acc)).  acc / g / counts are HOST arrays. */
 int32_t ngpde_accumulate_many(int32_t n_arrays, float *const *acc, const float *const *g, const int64_t *counts, ngpde_stream_t stream);
 
+/* ---- adaptive Tsit5 for right-hand sides evaluated by arbitrary layers ---------------------------------------------------------
+ * The reference's tutorials solve with adaptive Tsit5: docs/src/tutorials/graph_node.md:80-81 `NeuralODE(node_chain; save_everystep =
+ * false, reltol = 1e-3, abstol = 1e-3, save_start = false)` and VMH.md:87 `NeuralODE(gnn, tspan, Tsit5(); saveat = dt_train, reltol =
+ * 1e-9, abstol = 1e-3)`.  The caller forms the stages as for a fixed step (ngpde_rk_stage_combine), evaluates f(u_new) as the seventh
+ * stage (FSAL: the next step's first), gets EEst from ngpde_rk_error_norm, reads it back and asks ngpde_rk_control_step what to do.
+ * The pullback is the discrete adjoint of the ACCEPTED steps with their step sizes held fixed (rejected attempts contribute nothing,
+ * the step sizes are not differentiated through the controller); the reference's InterpolatingAdjoint is a continuous adjoint, the
+ * two gradients differ by O(tol).
+ *
+ * Scaled RMS norm (OrdinaryDiffEq calculate_residuals + its default internalnorm), written to the DEVICE double *out:
+ *   out = sqrt( (1/count) sum_i ( e_i / (abstol + reltol max(|u_prev_i|, |u_new_i|)) )^2 ),  e_i = sum_j coefs[j] terms[j][i]
+ * e_i is formed as ngpde_rk_stage_combine forms it (base NULL: the fmaf chain in term order), the rest in double.  With the seven Tsit5
+ * stages and coefs = float(dt btilde_j) (formed in double) it is Tsit5's EEst; one term with u_prev = u_new = u0 gives |u0/sk| and
+ * |f0/sk| of the starting-step heuristic, two terms with coefficients +1, -1 give |(f1 - f0)/sk|.  count >= 1, 1 <= n_terms <= 8;
+ * terms / coefs are HOST arrays as in ngpde_rk_stage_combine.  Two launches (per-block partials, then one block adds them in a fixed
+ * order): no atomics, bitwise reproducible, no allocation or synchronisation -- graph-capture safe.  `workspace` holds
+ * ngpde_rk_error_norm_workspace_bytes(count) bytes (at most 16 KiB). */
+size_t ngpde_rk_error_norm_workspace_bytes(int64_t count);
+int32_t ngpde_rk_error_norm(int64_t count, int32_t n_terms, const float *const *terms, const float *coefs, const float *u_prev,
+                            const float *u_new, double abstol, double reltol, void *workspace, double *out /* device */,
+                            ngpde_stream_t stream);
+
+/* Step-size controller, host only (no device call), caller-owned state.  OrdinaryDiffEq's PI controller with the Tsit5 defaults
+ * beta1 = 7/50, beta2 = 2/25, gamma = 9/10, qmin = 1/5, qmax = 10, qsteady = [1, 1], qoldinit = 1e-4:
+ *   q11 = EEst^beta1, q = clamp(q11 / qold^beta2 / gamma, 1/qmax, 1/qmin) (q = 1/qmax when EEst == 0);
+ *   accept when EEst <= 1: qold = max(EEst, qoldinit), dt_next = dt / q;  reject otherwise: dt_next = dt / min(1/qmin, q11/gamma);
+ *   a non-finite EEst is a reject with dt_next = dt qmin.
+ * The next attempt takes min(dt_next, dtmax), cut to land exactly on the next stop (t_end and, with saveat > 0, every save point
+ * t0 + k saveat, as tstops make DiffEq land): on landing t becomes the stop itself.  A step whose proposal falls below dtmin (or is
+ * NaN), and the attempt after `maxiters` attempts (rejected ones included), fail with NGPDE_ERR_STATE naming dtmin / maxiters and t;
+ * the state then refuses further steps.
+ *   init:        dt > 0 is the first attempt's step (capped by dtmax, cut to the first stop); dt <= 0: chosen by the two calls below.
+ *                dtmax <= 0: t_end - t0; maxiters <= 0: 100 000 (DiffEq's default); saveat 0: no save points, otherwise it must
+ *                divide tspan (NGPDE_ERR_INVALID_ARGUMENT).  dtmin = 1e-12 (t_end - t0); the caller may change it after init.
+ *   trial_dt:    Hairer-Norsett-Wanner's starting step as ode_determine_initdt applies it (order 5), first half: with d0 = |u0/sk|,
+ *                d1 = |f0/sk|, sk = abstol + reltol |u0|: dt0 = 1e-6 if d0 < 1e-5 or d1 < 1e-5, else 0.01 d0 / d1; capped by dtmax.
+ *                The caller evaluates f1 = f(u0 + dt0 f0).
+ *   initial_dt:  second half, with norm_df = |(f1 - f0)/sk|: d2 = norm_df / dt0; dt1 = max(1e-6, 1e-3 dt0) if max(d1, d2) <= 1e-15,
+ *                else (0.01 / max(d1, d2))^(1/5); the first step is min(100 dt0, dt1, dtmax), cut to the first stop.  Non-finite
+ *                norms: NGPDE_ERR_STATE.
+ *   step:        EEst of the attempt just made -> *action: NGPDE_RK_REJECT (retry from t with the new dt), NGPDE_RK_ACCEPT (t
+ *                advanced; `saved` says the step ended on a save point), NGPDE_RK_DONE (accepted, t = t_end). */
+typedef enum { NGPDE_RK_REJECT = 0, NGPDE_RK_ACCEPT = 1, NGPDE_RK_DONE = 2 } ngpde_rk_action_t;
+typedef struct ngpde_rk_control {
+  double t0, t, t_end;
+  double dt;                   /* step of the next attempt */
+  double dtmax, dtmin;
+  double saveat;               /* 0: no save points */
+  double qold, q11, eest;      /* PI controller memory; eest: the last attempt's EEst */
+  int64_t maxiters, naccept, nreject, nattempt;
+  int64_t n_save, next_save;   /* save points t0 + k saveat, k = 1 .. n_save (the last is t_end); the next one's k */
+  int32_t lands;               /* dt reaches the next stop */
+  int32_t saved;               /* the last accepted step ended on a save point */
+  int32_t done;                /* 1: t_end reached; -1: failed */
+  int32_t reserved;
+} ngpde_rk_control_t;
+int32_t ngpde_rk_control_init(ngpde_rk_control_t *state, double t0, double t_end, double dt, double dtmax, double saveat, int64_t maxiters);
+int32_t ngpde_rk_control_trial_dt(const ngpde_rk_control_t *state, double d0, double d1, double *dt0);
+int32_t ngpde_rk_control_initial_dt(ngpde_rk_control_t *state, double d0, double d1, double norm_df);
+int32_t ngpde_rk_control_step(ngpde_rk_control_t *state, double eest, int32_t *action);
+
 /* Optimiser step on the flat parameter vector, one launch behind the gradient all-reduce on the same stream
  * [UPSTREAM Optimisers.jl Adam / Rprop; reference call sites docs/src/tutorials/graph_node.md:90,122-129, VMH.md:97].
  * grad_scale multiplies the (reduced) gradient first: 1/world_size for a mean over data-parallel ranks.

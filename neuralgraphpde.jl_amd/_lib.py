@@ -79,6 +79,17 @@ class OdeDesc(C.Structure):
                 ("n_gamma", _i32), ("gamma_dims", _i32 * (MLP_MAX_LAYERS + 1)), ("gamma_acts", _i32 * MLP_MAX_LAYERS)]
 
 
+class RkControl(C.Structure):
+    """ngpde_rk_control_t: the state of the adaptive step-size controller (ngpde_rk_control_*)"""
+    _fields_ = [("t0", C.c_double), ("t", C.c_double), ("t_end", C.c_double), ("dt", C.c_double), ("dtmax", C.c_double),
+                ("dtmin", C.c_double), ("saveat", C.c_double), ("qold", C.c_double), ("q11", C.c_double), ("eest", C.c_double),
+                ("maxiters", _i64), ("naccept", _i64), ("nreject", _i64), ("nattempt", _i64), ("n_save", _i64), ("next_save", _i64),
+                ("lands", _i32), ("saved", _i32), ("done", _i32), ("reserved", _i32)]
+
+
+RK_REJECT, RK_ACCEPT, RK_DONE = 0, 1, 2
+
+
 class OdeWb(C.Structure):
     """ngpde_ode_wb_t"""
     _fields_ = [("weight", _vp * MLP_MAX_LAYERS), ("bias", _vp * MLP_MAX_LAYERS)]
@@ -169,6 +180,12 @@ SIGNATURES = {
     "ngpde_gat_backward": (_i32, [_vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_rk_stage_combine": (_i32, [_i64, _f32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_accumulate_many": (_i32, [_i32, _vp, _vp, _vp, _vp]),
+    "ngpde_rk_error_norm_workspace_bytes": (_sz, [_i64]),
+    "ngpde_rk_error_norm": (_i32, [_i64, _i32, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "ngpde_rk_control_init": (_i32, [C.POINTER(RkControl), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i64]),
+    "ngpde_rk_control_trial_dt": (_i32, [C.POINTER(RkControl), C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "ngpde_rk_control_initial_dt": (_i32, [C.POINTER(RkControl), C.c_double, C.c_double, C.c_double]),
+    "ngpde_rk_control_step": (_i32, [C.POINTER(RkControl), C.c_double, C.POINTER(_i32)]),
     "ngpde_gno_message_supported": (_i32, [_i32, _i32]),
     "ngpde_gno_message_backward_from_nodes": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ngpde_gno_message_forward": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -102,6 +102,85 @@ void launch_rk_combine(int n_terms, int64_t count, float c_self, const float *ba
   }
 }
 
+// Scaled RMS norm of an embedded error estimate (OrdinaryDiffEq calculate_residuals + the default internalnorm):
+//   out = sqrt( (1/count) sum_i ( e_i / (abstol + reltol max(|u_prev_i|, |u_new_i|)) )^2 ),  e_i = sum_j coef[j] term[j][i]
+// e_i is formed exactly as rk_combine_kernel forms it with base = NULL (all loads first, then the fmaf chain in term order); the
+// residual and its square are taken in double.  Two passes, no atomics: pass 1 writes one partial per block (thread sums in
+// grid-stride order, a 64-lane shuffle tree per wave, the four waves' sums added in wave order), pass 2 is one block that adds the
+// partials in the same fixed order.  Same inputs, same launch geometry (it depends on count only): the same bits.
+constexpr int kNormThreads = 256;
+constexpr int kNormMaxBlocks = 2048;
+
+__device__ __forceinline__ double block_sum_256(double v) {
+  __shared__ double wave_sum[kNormThreads / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];     // (read by thread 0 only)
+}
+
+__device__ __forceinline__ double scaled_sq(float e, float up, float un, double abstol, double reltol) {
+  const double r = (double)e / (abstol + reltol * (double)fmaxf(fabsf(up), fabsf(un)));
+  return r * r;
+}
+
+template <int N, class T>
+__global__ void __launch_bounds__(kNormThreads) rk_error_norm_partial_kernel(int64_t count, const CombK k, const T *u_prev,
+                                                                             const T *u_new, double abstol, double reltol,
+                                                                             double *__restrict__ partial) {
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+    T t[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) t[j] = reinterpret_cast<const T *>(k.term[j])[i];   // all loads first
+    const T up = u_prev[i], un = u_new[i];
+    if constexpr (sizeof(T) == 16) {
+      float4 e = f4_zero();
+#pragma unroll
+      for (int j = 0; j < N; ++j) e = f4_fma(k.coef[j], t[j], e);
+      acc += scaled_sq(e.x, up.x, un.x, abstol, reltol);
+      acc += scaled_sq(e.y, up.y, un.y, abstol, reltol);
+      acc += scaled_sq(e.z, up.z, un.z, abstol, reltol);
+      acc += scaled_sq(e.w, up.w, un.w, abstol, reltol);
+    } else {
+      float e = 0.f;
+#pragma unroll
+      for (int j = 0; j < N; ++j) e = fmaf(k.coef[j], t[j], e);
+      acc += scaled_sq(e, up, un, abstol, reltol);
+    }
+  }
+  const double s = block_sum_256(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(kNormThreads) rk_error_norm_final_kernel(int n_partial, int64_t count, const double *__restrict__ partial,
+                                                                           double *__restrict__ out) {
+  double acc = 0.0;
+  for (int b = threadIdx.x; b < n_partial; b += kNormThreads) acc += partial[b];
+  const double s = block_sum_256(acc);
+  if (threadIdx.x == 0) *out = sqrt(s / (double)count);
+}
+
+int norm_blocks(int64_t count) { return (int)std::min<int64_t>((count + kNormThreads - 1) / kNormThreads, kNormMaxBlocks); }
+
+template <class T>
+void launch_rk_error_norm(int n_terms, int64_t count, const CombK &k, const float *u_prev, const float *u_new, double abstol, double reltol,
+                          int blocks, double *partial, hipStream_t stream) {
+  const T *up = reinterpret_cast<const T *>(u_prev), *un = reinterpret_cast<const T *>(u_new);
+  const dim3 grid((unsigned)blocks), block(kNormThreads);
+  switch (n_terms) {
+    case 1: hipLaunchKernelGGL((rk_error_norm_partial_kernel<1, T>), grid, block, 0, stream, count, k, up, un, abstol, reltol, partial); break;
+    case 2: hipLaunchKernelGGL((rk_error_norm_partial_kernel<2, T>), grid, block, 0, stream, count, k, up, un, abstol, reltol, partial); break;
+    case 3: hipLaunchKernelGGL((rk_error_norm_partial_kernel<3, T>), grid, block, 0, stream, count, k, up, un, abstol, reltol, partial); break;
+    case 4: hipLaunchKernelGGL((rk_error_norm_partial_kernel<4, T>), grid, block, 0, stream, count, k, up, un, abstol, reltol, partial); break;
+    case 5: hipLaunchKernelGGL((rk_error_norm_partial_kernel<5, T>), grid, block, 0, stream, count, k, up, un, abstol, reltol, partial); break;
+    case 6: hipLaunchKernelGGL((rk_error_norm_partial_kernel<6, T>), grid, block, 0, stream, count, k, up, un, abstol, reltol, partial); break;
+    case 7: hipLaunchKernelGGL((rk_error_norm_partial_kernel<7, T>), grid, block, 0, stream, count, k, up, un, abstol, reltol, partial); break;
+    default: hipLaunchKernelGGL((rk_error_norm_partial_kernel<8, T>), grid, block, 0, stream, count, k, up, un, abstol, reltol, partial); break;
+  }
+}
+
 }  // namespace
 }  // namespace ngpde
 
@@ -127,6 +206,38 @@ int32_t ngpde_rk_stage_combine(int64_t count, float c_self, const float *base, i
   if (count % 4 == 0 && (bits & 15) == 0) launch_rk_combine<float4>(n_terms, count / 4, c_self, base, k, out, (hipStream_t)stream);
   else launch_rk_combine<float>(n_terms, count, c_self, base, k, out, (hipStream_t)stream);
   NGPDE_LAUNCH_CHECK("rk_combine_kernel");
+  return NGPDE_OK;
+}
+
+size_t ngpde_rk_error_norm_workspace_bytes(int64_t count) {
+  return count > 0 ? (size_t)norm_blocks(count) * sizeof(double) : 0;
+}
+
+int32_t ngpde_rk_error_norm(int64_t count, int32_t n_terms, const float *const *terms, const float *coefs, const float *u_prev,
+                            const float *u_new, double abstol, double reltol, void *workspace, double *out, ngpde_stream_t stream) {
+  NGPDE_RANGE();
+  NGPDE_REQUIRE(count > 0 && n_terms >= 1 && n_terms <= 8, NGPDE_ERR_INVALID_ARGUMENT,
+                "ngpde_rk_error_norm: count >= 1 and 1 <= n_terms <= 8 required (got %lld, %d)", (long long)count, n_terms);
+  NGPDE_REQUIRE(terms && coefs && u_prev && u_new && workspace && out, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_error_norm: NULL argument");
+  NGPDE_REQUIRE(abstol >= 0.0 && reltol >= 0.0 && abstol + reltol > 0.0, NGPDE_ERR_INVALID_ARGUMENT,
+                "ngpde_rk_error_norm: abstol, reltol >= 0, not both 0, required (got %g, %g)", abstol, reltol);
+  CombK k;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(u_prev) | reinterpret_cast<uintptr_t>(u_new);
+  for (int j = 0; j < 8; ++j) {
+    k.term[j] = j < n_terms ? terms[j] : nullptr;
+    k.coef[j] = j < n_terms ? coefs[j] : 0.f;
+    NGPDE_REQUIRE(j >= n_terms || terms[j], NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_error_norm: term %d is NULL", j);
+    bits |= reinterpret_cast<uintptr_t>(k.term[j]);
+  }
+  const int blocks = norm_blocks(count);
+  double *partial = static_cast<double *>(workspace);
+  if (count % 4 == 0 && (bits & 15) == 0)
+    launch_rk_error_norm<float4>(n_terms, count / 4, k, u_prev, u_new, abstol, reltol, blocks, partial, (hipStream_t)stream);
+  else
+    launch_rk_error_norm<float>(n_terms, count, k, u_prev, u_new, abstol, reltol, blocks, partial, (hipStream_t)stream);
+  NGPDE_LAUNCH_CHECK("rk_error_norm_partial_kernel");
+  hipLaunchKernelGGL(rk_error_norm_final_kernel, dim3(1), dim3(kNormThreads), 0, (hipStream_t)stream, blocks, count, partial, out);
+  NGPDE_LAUNCH_CHECK("rk_error_norm_final_kernel");
   return NGPDE_OK;
 }
 

@@ -1,7 +1,8 @@
 """NeuralODE -- the caller of the hot path in the reference's tutorial
 (/root/reference/docs/src/tutorials/graph_node.md:44-66): `dudt(u, p, t) = model(u, p, st)` integrated
-by an explicit Runge-Kutta scheme.  BASELINE configs fix the step count (Euler x 10, Tsit5 x 50), so
-this integrator is fixed-step and its pullback is the discrete adjoint.
+by an explicit Runge-Kutta scheme.  BASELINE configs fix the step count (Euler x 10, Tsit5 x 50); the tutorials themselves
+solve with adaptive Tsit5 (graph_node.md:80-81, VMH.md:87), which NeuralODE(..., adaptive=True) runs on the generic path below.
+The pullback is the discrete adjoint of the steps taken.
 
 When the right-hand side is Chain(GCNConv(d => d, act), GCNConv(d => d, act)) on one graph (the
 tutorial's `node_chain`, graph_node.md:78) the whole solve and its adjoint run device-resident from
@@ -13,6 +14,8 @@ launch (_NodeGenericFn): no torch element-wise kernel on the path.
 from __future__ import annotations
 
 import ctypes as C
+import math
+import numbers
 
 import torch
 
@@ -34,6 +37,10 @@ _TSIT5_A = [
 _TSIT5_B = [0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081,
             2.324710524099774]
 TABLEAUS = {"euler": ([[]], [1.0]), "tsit5": (_TSIT5_A, _TSIT5_B)}
+# Tsit5's embedded error weights (OrdinaryDiffEq's btilde1..7; the seventh stage is f(u_new), FSAL): utilde = dt sum_j btilde_j k_j
+# is the difference of the 5th- and 4th-order solutions, so sum_j btilde_j c_j^(q-1) = 0 for q = 1..4 and not for q = 5
+_TSIT5_BTILDE = [-0.00178001105222577714, -0.0008164344596567469, 0.007880878010261995, -0.1447110071732629, 0.5823571654525552,
+                 -0.45808210592918697, 1.0 / 66.0]
 
 
 # ---- any right-hand side: explicit RK stepping with every combination as ONE library launch ---------------------------------
@@ -88,43 +95,132 @@ def _rebuild(tree, it):
     return {k: (_rebuild(v, it) if isinstance(v, dict) else next(it)) for k, v in tree.items()}
 
 
+def _fixed_schedule(node):
+    """(dts, saved) of the fixed-step solve: n_steps steps of node.dt, every save_every-th one ending on a save point"""
+    k = node.save_every
+    return [node.dt] * node.n_steps, [bool(k) and (n + 1) % k == 0 for n in range(node.n_steps)]
+
+
+def _error_norm(terms, coefs, u_prev, u_new, abstol, reltol, ws, out):
+    """the scaled RMS norm of sum_j coefs[j] terms[j] (ngpde_rk_error_norm), read back: one device-to-host synchronisation"""
+    arr = (C.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
+    cf = (C.c_float * len(coefs))(*[float(c) for c in coefs])
+    _lib.check(_lib.load().ngpde_rk_error_norm(u_prev.numel(), len(terms), arr, cf, u_prev.data_ptr(), u_new.data_ptr(), float(abstol),
+                                               float(reltol), ws.data_ptr(), out.data_ptr(), _lib.current_stream()))
+    return float(out.item())
+
+
+class _Control:
+    """the library's step-size controller (ngpde_rk_control_*) for one adaptive solve"""
+
+    def __init__(self, node):
+        self.state = _lib.RkControl()
+        t0, t1 = node.tspan
+        _lib.check(_lib.load().ngpde_rk_control_init(C.byref(self.state), float(t0), float(t1), float(node.dt or 0.0),
+                                                     float(node.dtmax or 0.0), float(node.saveat or 0.0), int(node.maxiters)))
+
+    def trial_dt(self, d0, d1):
+        dt0 = C.c_double()
+        _lib.check(_lib.load().ngpde_rk_control_trial_dt(C.byref(self.state), d0, d1, C.byref(dt0)))
+        return dt0.value
+
+    def initial_dt(self, d0, d1, norm_df):
+        _lib.check(_lib.load().ngpde_rk_control_initial_dt(C.byref(self.state), d0, d1, norm_df))
+
+    def step(self, eest):
+        action = C.c_int32()
+        _lib.check(_lib.load().ngpde_rk_control_step(C.byref(self.state), eest, C.byref(action)))
+        return action.value
+
+
 def _rk_forward(node, u, ps_in, st, needs, fresh=False):
-    """u(T) of the fixed-step solve; with `needs` also the tape: per step and stage the (stage input, stage output) pair whose
-    autograd closure is the layers' pullback.  fresh: the stage inputs get version counters of their own (a captured solve
-    refills its static input buffer before every replay; the closures are only ever run at capture time)"""
+    """u(T) (or the saved states) of the solve; with `needs` also the tape: per step and stage the (stage input, stage output) pair
+    whose autograd closure is the layers' pullback.  The last item is the schedule (dts, saved) of the steps taken: fixed, or the
+    accepted steps of an adaptive solve.  fresh: the stage inputs get version counters of their own (a captured solve refills its
+    static input buffer before every replay; the closures are only ever run at capture time)"""
     a, b = TABLEAUS[node.solver]
-    dt, S = node.dt, len(b)
+    S = len(b)
     ucur, tape, st_out = u, [], st
-    k_save = node.save_every
-    saves = [ucur] if (k_save and node.save_start) else []      # saveat: the states at t0 (+ j saveat), as DiffEq's sol.u
+    saving = node.saving
+    saves = [ucur] if (saving and node.save_start) else []      # saveat: the states at t0 (+ j saveat), as DiffEq's sol.u
+
+    def stage(U):
+        nonlocal st_out
+        if needs:
+            U = (U.data if fresh else U.detach()).requires_grad_(True)
+        k, st_out = node.model(U.T, ps_in, st_out)
+        k = rows_of(k)
+        if k.shape != ucur.shape:
+            raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
+                                         f"DimensionMismatch: the right-hand side maps {tuple(ucur.shape[::-1])} to "
+                                         f"{tuple(k.shape[::-1])}; du/dt must have the shape of u")
+        return U, k
+
+    dts, saved = ([], []) if node.adaptive else _fixed_schedule(node)
+    ctl, first, nf, eests, init_norms = None, None, 0, [], None
     with (torch.enable_grad() if needs else torch.no_grad()):
-        for n_step in range(node.n_steps):
+        if node.adaptive:
+            ctl = _Control(node)
+            ws = torch.empty(max(int(_lib.load().ngpde_rk_error_norm_workspace_bytes(ucur.numel())), 8), dtype=torch.uint8, device=ucur.device)
+            eout = torch.empty(1, dtype=torch.float64, device=ucur.device)
+            tol = (node.abstol, node.reltol)
+            first = stage(ucur)                      # f0: the first step's first stage
+            nf = 1
+            if node.dt is None:                      # Hairer-Norsett-Wanner's starting step (ode_determine_initdt, order 5)
+                f0 = first[1].detach()
+                d0 = _error_norm([ucur], [1.0], ucur, ucur, *tol, ws, eout)
+                d1 = _error_norm([f0], [1.0], ucur, ucur, *tol, ws, eout)
+                dt0 = ctl.trial_dt(d0, d1)
+                with torch.no_grad():
+                    f1 = rows_of(node.model(_combine(ucur, 1.0, [f0], [dt0]).T, ps_in, st_out)[0])
+                nf += 1
+                init_norms = (d0, d1, _error_norm([f1, f0], [1.0, -1.0], ucur, ucur, *tol, ws, eout))
+                ctl.initial_dt(*init_norms)
+                del f1
+        n_step = 0
+        while ctl is not None or n_step < len(dts):
+            dt = ctl.state.dt if ctl is not None else dts[n_step]
             ks, pairs = [], []
             for i in range(S):
-                terms = [ks[j] for j in range(i) if a[i][j] != 0.0]
-                coefs = [dt * a[i][j] for j in range(i) if a[i][j] != 0.0]
-                U = _combine(ucur, 1.0, terms, coefs) if terms else ucur
-                if needs:
-                    U = (U.data if fresh else U.detach()).requires_grad_(True)
-                k, st_out = node.model(U.T, ps_in, st_out)
-                k = rows_of(k)
-                if k.shape != ucur.shape:
-                    raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
-                                                 f"DimensionMismatch: the right-hand side maps {tuple(ucur.shape[::-1])} to "
-                                                 f"{tuple(k.shape[::-1])}; du/dt must have the shape of u")
+                if i == 0 and first is not None:      # FSAL: f(u_new) of the last accepted step, or f0
+                    U, k = first
+                else:
+                    terms = [ks[j] for j in range(i) if a[i][j] != 0.0]
+                    coefs = [dt * a[i][j] for j in range(i) if a[i][j] != 0.0]
+                    U, k = stage(_combine(ucur, 1.0, terms, coefs) if terms else ucur)
                 ks.append(k.detach())
                 pairs.append((U, k))
-            ucur = _combine(ucur, 1.0, ks, [dt * bi for bi in b])
+            unew = _combine(ucur, 1.0, ks, [dt * bi for bi in b])
+            if ctl is not None:
+                last = stage(unew)                   # the seventh stage: the embedded estimate's, and the next step's first
+                nf += S
+                eest = _error_norm(ks + [last[1].detach()], [dt * bt for bt in _TSIT5_BTILDE], ucur, unew, *tol, ws, eout)
+                eests.append(eest)
+                action = ctl.step(eest)              # (raises NgpdeError(ERR_STATE) when maxiters / dtmin end the solve)
+                if action == _lib.RK_REJECT:
+                    first = pairs[0]                 # the attempt's other stages are dropped
+                    continue
+                first = last
+                dts.append(dt)
+                saved.append(bool(ctl.state.saved))
+            ucur = unew
             if needs:
                 tape.append(pairs)
-            if k_save and (n_step + 1) % k_save == 0:
+            if saved[n_step]:
                 saves.append(ucur)
-    if k_save:      # [T][N][D]: the memory layout of the reference's (D x N x T) array; rows written by library launches
+            n_step += 1
+            if ctl is not None and action == _lib.RK_DONE:
+                break
+    if ctl is not None:
+        c = ctl.state
+        node.stats = dict(naccept=int(c.naccept), nreject=int(c.nreject), nf=nf, dts=list(dts), t=float(c.t), eests=eests,
+                          init_norms=init_norms)
+    if saving:      # [T][N][D]: the memory layout of the reference's (D x N x T) array; rows written by library launches
         out = torch.empty((len(saves),) + tuple(ucur.shape), dtype=ucur.dtype, device=ucur.device)
         for j, s_ in enumerate(saves):
             _combine(s_, 1.0, [], [], out=out[j])
         ucur = out
-    return ucur, tape, st_out
+    return ucur, tape, st_out, (dts, saved)
 
 
 def _accumulate_many(pairs):
@@ -141,15 +237,22 @@ def _accumulate_many(pairs):
     _lib.check(_lib.load().ngpde_accumulate_many(n, accs, gs, cnt, _lib.current_stream()))
 
 
-def _rk_backward(node, tape, duT, params, retain=False):
-    """discrete adjoint of _rk_forward: (du0, cotangents of `params`)"""
+def _rk_backward(node, tape, duT, params, schedule, retain=False):
+    """discrete adjoint of _rk_forward over the steps of `schedule` (dts, saved), their sizes held fixed: (du0, cotangents of `params`)"""
     a, b = TABLEAUS[node.solver]
-    dt, S = node.dt, len(b)
+    S = len(b)
+    dts, saved = schedule
     acc = [None] * len(params)
-    k_save = node.save_every
-    off = 0 if node.save_start else -1           # saved state j is u after (j - off') steps: index of u_n is n / k_save + off
-    lam = duT[node.n_steps // k_save + off] if k_save else duT
+    saving = node.saving
+    # slot of duT holding the cotangent of u_n, the state at the start of step n (None: not saved)
+    n_saved = 1 if node.save_start else 0
+    slot, start_slot = (0 if node.save_start else None), []
+    for n in range(len(dts)):
+        start_slot.append(slot)
+        slot, n_saved = (n_saved, n_saved + 1) if saved[n] else (None, n_saved)
+    lam = duT[n_saved - 1] if saving else duT     # (a solve with saveat ends on its last save point)
     for n_step, pairs in zip(range(len(tape) - 1, -1, -1), reversed(tape)):
+        dt = dts[n_step]
         ubar = [None] * S
         for i in reversed(range(S)):
             terms = [ubar[j] for j in range(i + 1, S) if a[j][i] != 0.0 and ubar[j] is not None]
@@ -176,8 +279,8 @@ def _rk_backward(node, tape, duT, params, retain=False):
                     pairs_ag.append((_dense(acc[n]), _dense(g.contiguous() if acc[n].is_contiguous() else g.T.contiguous().T)))
             _accumulate_many(pairs_ag)      # ONE launch for all parameters of this stage (sixteen arrays in the VMH tutorial's model)
         live = [x for x in ubar if x is not None]
-        if k_save and n_step % k_save == 0 and n_step // k_save + off >= 0:
-            live.append(duT[n_step // k_save + off])          # lambda(t_n) also carries the cotangent of the state saved there
+        if saving and start_slot[n_step] is not None:
+            live.append(duT[start_slot[n_step]])              # lambda(t_n) also carries the cotangent of the state saved there
         if live:
             lam = _combine(lam, 1.0, live, [1.0] * len(live))
     return lam, acc
@@ -191,8 +294,8 @@ def _inner_params(ps, leaves, fresh=False):
 
 
 class _NodeGenericFn(torch.autograd.Function):
-    """Fixed-step explicit Runge-Kutta solve of du/dt = model(u) for ANY model made of this package's layers, and its discrete
-    adjoint.  Forward: the stage inputs u + dt sum_j a_ij k_j and the step update are one ngpde_rk_stage_combine launch each,
+    """Explicit Runge-Kutta solve of du/dt = model(u) for ANY model made of this package's layers -- fixed-step, or adaptive Tsit5 --
+    and its discrete adjoint.  Forward: the stage inputs u + dt sum_j a_ij k_j and the step update are one ngpde_rk_stage_combine launch each,
     the stages are the layers' own kernels; every stage keeps its (input, output) pair with the layer's pullback closure.
     Backward: per stage, in reverse, K-bar_i = dt b_i lambda + dt sum_{j>i} a_ji U-bar_j (one launch), U-bar_i and the parameter
     cotangents from the stage's pullback (the layers' backward kernels), parameter gradients accumulated by one launch each,
@@ -203,14 +306,14 @@ class _NodeGenericFn(torch.autograd.Function):
     def forward(ctx, u, node, ps, st, *leaves):
         needs = any(ctx.needs_input_grad)
         inner, ps_in = _inner_params(ps, leaves) if needs else (list(leaves), ps)
-        uT, tape, _ = _rk_forward(node, u.detach().contiguous(), ps_in, st, needs)
-        ctx.node, ctx.tape, ctx.inner = node, tape if needs else None, inner
+        uT, tape, _, schedule = _rk_forward(node, u.detach().contiguous(), ps_in, st, needs)
+        ctx.node, ctx.tape, ctx.inner, ctx.schedule = node, tape if needs else None, inner, schedule
         return uT
 
     @staticmethod
     def backward(ctx, duT):
         params = [p for p in ctx.inner if isinstance(p, torch.Tensor) and p.requires_grad]
-        lam, acc = _rk_backward(ctx.node, ctx.tape, duT.contiguous(), params)
+        lam, acc = _rk_backward(ctx.node, ctx.tape, duT.contiguous(), params, ctx.schedule)
         ctx.tape = None
         it = iter(acc)
         out = [next(it) if (isinstance(p, torch.Tensor) and p.requires_grad) else None for p in ctx.inner]
@@ -258,7 +361,7 @@ class _CapturedSolve:
         self.fwd_graph = torch.cuda.CUDAGraph()
         # (relaxed: a finaliser that frees device memory in the middle of the capture must not invalidate it)
         with _NoCyclicGC(), torch.cuda.graph(self.fwd_graph, capture_error_mode="relaxed"):
-            self.uT_static, self.tape, _ = _rk_forward(node, self.u_static, self.ps_in, st, needs, fresh=True)
+            self.uT_static, self.tape, _, self.schedule = _rk_forward(node, self.u_static, self.ps_in, st, needs, fresh=True)
         self.bwd_graph = None
         self.generation = 0                                # forward replays so far: the single static tape belongs to the last one
 
@@ -278,7 +381,8 @@ class _CapturedSolve:
             self.duT_static = duT.detach().clone()
             self.bwd_graph = torch.cuda.CUDAGraph()
             with _NoCyclicGC(), torch.cuda.graph(self.bwd_graph, pool=self.fwd_graph.pool(), capture_error_mode="relaxed"):
-                self.lam_static, self.acc_static = _rk_backward(self.node, self.tape, self.duT_static, self.params, retain=True)
+                self.lam_static, self.acc_static = _rk_backward(self.node, self.tape, self.duT_static, self.params, self.schedule,
+                                                                retain=True)
         else:
             self.duT_static.copy_(duT)
         self.bwd_graph.replay()
@@ -309,13 +413,30 @@ class NeuralODE(AbstractExplicitLayer):
     dt = (tspan[1] - tspan[0]) / n_steps unless given.  capture=True (an extension, for right-hand sides other than the
     two-GCNConv chain, which is always device-resident): the whole solve and its adjoint are captured into HIP graphs at
     the first call and replayed afterwards (_CapturedSolve).
+
+    adaptive=True (graph_node.md:80-81, VMH.md:87): Tsit5 with step-size control, DiffEq's names and defaults -- reltol=1e-3,
+    abstol=1e-6 (scalars), dtmax=None (t_end - t0), maxiters=100_000 (attempts, rejected ones included); dt is the first step
+    (None: Hairer-Norsett-Wanner's choice) and n_steps is ignored.  Every attempt forms the stages as the fixed step does, evaluates
+    f(u_new) (the next step's first stage), gets EEst from one ngpde_rk_error_norm launch pair and reads it back (one synchronisation
+    per attempt); the library's controller (ngpde_rk_control_step, OrdinaryDiffEq's PI controller) accepts or rejects.  Steps land
+    on the save points of saveat exactly (no dense output).  It always runs the generic path (the device-resident plans are
+    fixed-step), and capture=True is refused: the step count depends on the data.  The pullback is the discrete adjoint of the
+    accepted steps with their sizes held fixed -- rejected attempts contribute nothing and the controller is not differentiated; the
+    reference's InterpolatingAdjoint is a continuous adjoint, so the gradients differ by O(tol).  NeuralODE.stats holds the last
+    solve's naccept, nreject, nf, accepted step sizes (dts) and final t, as DiffEq's sol.stats (and every attempt's EEst, and the
+    starting step's three norms when it was chosen).
     """
 
-    def __init__(self, model, *, solver="tsit5", tspan=(0.0, 1.0), n_steps=10, dt=None, capture=False, saveat=None, save_start=True):
+    def __init__(self, model, *, solver="tsit5", tspan=(0.0, 1.0), n_steps=10, dt=None, capture=False, saveat=None, save_start=True,
+                 adaptive=False, reltol=1e-3, abstol=1e-6, dtmax=None, maxiters=100_000):
         solver = solver.lower()
         if solver not in TABLEAUS:
             raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, f"unknown solver {solver!r}; one of {list(TABLEAUS)}")
         self.model, self.solver, self.tspan, self.n_steps = model, solver, tuple(tspan), int(n_steps)
+        self.adaptive, self.saveat, self.stats = bool(adaptive), None, None
+        if self.adaptive:
+            self._init_adaptive(dt, capture, saveat, save_start, reltol, abstol, dtmax, maxiters)
+            return
         self.dt = float(dt) if dt is not None else (self.tspan[1] - self.tspan[0]) / self.n_steps
         # saveat (VMH.md:85 `NeuralODE(gnn, tspan, Tsit5(); saveat=dt_train)`): the output is the solution at t0, t0 + saveat, ..., T --
         # a (D x N x T) array -- instead of u(T).  The step is fixed, so saveat must be a whole number of steps.
@@ -331,6 +452,37 @@ class NeuralODE(AbstractExplicitLayer):
         self.capture = bool(capture)      # generic right-hand sides: replay the whole solve / adjoint from HIP graphs
         self._captured = {}
         self._gat_ok = {}                 # (id(graph handle), heads) -> (handle, does the device-resident GAT solver take it?)
+
+    def _init_adaptive(self, dt, capture, saveat, save_start, reltol, abstol, dtmax, maxiters):
+        def bad(msg):
+            return _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, f"NeuralODE(adaptive=True): {msg}")
+        if self.solver != "tsit5":
+            raise bad(f"solver {self.solver!r} has no embedded error estimate; adaptive stepping takes \"tsit5\"")
+        if capture:
+            raise bad("capture=True needs a fixed step count (one captured graph); an adaptive solve's depends on the data")
+        for name, v in (("reltol", reltol), ("abstol", abstol)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0:
+                raise bad(f"{name} must be a finite scalar >= 0 (vector tolerances are not supported), got {v!r}")
+        if reltol == 0 and abstol == 0:
+            raise bad("reltol and abstol are both 0")
+        for name, v in (("dt", dt), ("dtmax", dtmax)):
+            if v is not None and not (isinstance(v, numbers.Real) and math.isfinite(v) and v > 0):
+                raise bad(f"{name} must be a finite step > 0 or None, got {v!r}")
+        if int(maxiters) < 1:
+            raise bad(f"maxiters must be >= 1, got {maxiters!r}")
+        self.reltol, self.abstol = float(reltol), float(abstol)
+        self.dt = float(dt) if dt is not None else None
+        self.dtmax = float(dtmax) if dtmax is not None else None
+        self.maxiters = int(maxiters)
+        self.saveat, self.save_every, self.save_start = (float(saveat) if saveat is not None else None), 0, bool(save_start)
+        _Control(self)        # the library checks tspan and that saveat divides it (ArgumentError)
+        self.capture = False
+        self._plans, self._no_member_plan, self._captured, self._gat_ok = {}, False, {}, {}
+
+    @property
+    def saving(self):
+        """does the solve return the states at the save points (saveat) rather than u(T)?"""
+        return bool(self.save_every) or self.saveat is not None
 
     def initialparameters(self, rng):
         return self.model.initialparameters(rng)
@@ -560,7 +712,11 @@ class NeuralODE(AbstractExplicitLayer):
         u = rows_of(x)
         needs_grad = torch.is_grad_enabled() and (u.requires_grad or any(
             isinstance(v, torch.Tensor) and v.requires_grad for v in _leaves(ps)))      # (parameter trees of any depth: VMHConv's phi / gamma chains)
-        plan = self.plan_for(ps, st, needs_grad) if not self.save_every else None
+        if not self.adaptive:      # (an adaptive solve's statistics are set by the solve itself)
+            self.stats = dict(naccept=self.n_steps, nreject=0, nf=len(TABLEAUS[self.solver][1]) * self.n_steps, dts=[self.dt] * self.n_steps,
+                              t=float(self.tspan[1]))
+        # adaptive stepping: always the generic path (the device-resident plans are fixed-step by construction)
+        plan = self.plan_for(ps, st, needs_grad) if not (self.save_every or self.adaptive) else None
         if plan is not None:
             if not u.is_cuda:
                 raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, "NeuralODE: inputs must live on the GPU (no CPU fallback)")
@@ -576,7 +732,7 @@ class NeuralODE(AbstractExplicitLayer):
                                [("layer_1.bias", b1, d), ("layer_2.bias", b2, d)])
             uT = _NodeGCN2Fn.apply(u, w1, b1, w2, b2, plan)
             return uT.T, st
-        gplan = self.gat_plan_for(ps, st, u) if not self.save_every else None
+        gplan = self.gat_plan_for(ps, st, u) if not (self.save_every or self.adaptive) else None
         if gplan is not None:
             gps = ps["layer_1"] if isinstance(self.model, Chain) else ps
             gm = self.model.chain[0] if isinstance(self.model, Chain) else self.model
@@ -588,7 +744,7 @@ class NeuralODE(AbstractExplicitLayer):
                                              f"{a.numel()} entries, expected 2 x {gm.out_chs} x {gm.heads}")
             uT = _NodeOdeFn.apply(u, gplan, None, a, w, b)
             return uT.T, st
-        vplan = self.vmh_plan_for(ps, st, u, needs_grad)
+        vplan = self.vmh_plan_for(ps, st, u, needs_grad) if not self.adaptive else None
         if vplan is not None:
             plan_v, wb, index = vplan
             # a state whose node count is not the plan's graph's (a forgotten updategraph in the minibatch loop): the reference's
@@ -629,4 +785,4 @@ class NeuralODE(AbstractExplicitLayer):
             uT = _NodeCapturedFn.apply(u, solve, *leaves)
             return (uT.permute(2, 1, 0) if self.save_every else uT.T), st
         uT = _NodeGenericFn.apply(u, self, ps, st, *leaves)
-        return (uT.permute(2, 1, 0) if self.save_every else uT.T), st      # saveat: (D x N x T), the reference's array of the solution
+        return (uT.permute(2, 1, 0) if self.saving else uT.T), st      # saveat: (D x N x T), the reference's array of the solution
