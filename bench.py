@@ -13,6 +13,7 @@ batch of synthetic input already resident in HBM.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
     python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs bench_outputs   # + the last timed step's outputs as bench_outputs/*.npy
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full     # + every other leg (see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --steps K --warmup W        # the same: starts its own N ranks (one fresh process per GPU);
@@ -20,6 +21,11 @@ batch of synthetic input already resident in HBM.
 
 Multi-GPU is data parallel over independent trajectories (different u0 per rank, same graph and
 parameters): per-GPU work is fixed ("weak"), one all-reduce(sum) of the 8320-float gradient per step.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line.  Everything else runs
+only with --full, after the timed steps: the forward / backward split of one solve, the same step through the public API,
+the per-kernel roofline (launch events, a rocprofv3 child pass), the batched / larger-graph / d = 16, 32 / weighted solves,
+the CPU baseline and the `secondary` layer and solver legs (N > 1: the data-parallel C4 step).
 """
 import argparse
 import ctypes as C
@@ -677,7 +683,8 @@ def rocprof_roofline(out, role, algo_bytes):
     try:
         env = dict(os.environ, TMPDIR="/tmp")
         cmd = [exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "k", "--", sys.executable,
-               os.path.abspath(__file__), "--steps", str(ROCPROF_CHILD_STEPS), "--warmup", "3", "--no-cpu-baseline", "--batched", "0", "--no-secondary"]
+               os.path.abspath(__file__), "--steps", str(ROCPROF_CHILD_STEPS), "--warmup", "3", "--full", "--no-cpu-baseline", "--batched", "0",
+               "--no-secondary"]
         subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=300, check=True)
         found = None
         for base, _, files in os.walk(tmp):
@@ -692,7 +699,7 @@ def rocprof_roofline(out, role, algo_bytes):
         achieved = algo_bytes / (us * 1e-6) / 1e9
         r["achieved"], r["frac"], r["avg_launch_us"] = round(achieved, 1), round(achieved / HBM_PEAK_GBS, 4), round(us, 3)
         r["avg_launch_source"] = (f"rocprofv3 --kernel-trace --stats AverageNs over {calls} launches of {want}, collected by a child run of "
-                                  f"this script (--steps {ROCPROF_CHILD_STEPS} --warmup 3, the command of tools/profile_round.sh: a device that was idle runs its first four or "
+                                  f"this script (--steps {ROCPROF_CHILD_STEPS} --warmup 3 --full, the command of tools/profile_round.sh: a device that was idle runs its first four or "
                                   "five launches 3 - 20 % slower, so a pass of 3 steps read 5 % above the timed region's launches); *_events: " + events)
     except Exception as e:  # noqa: BLE001 -- the bench line must still come out
         r["avg_launch_source"] = events + f"; the rocprofv3 child pass failed ({type(e).__name__}: {e})"
@@ -796,14 +803,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C3 / C4 / C5 layer measurements ('secondary')")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg: forward / backward split, public-API step, per-kernel "
+                         "roofline, batched / larger-graph / variant solves, CPU baseline, 'secondary' (the four options below "
+                         "trim it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the C3 / C4 / C5 layer measurements ('secondary')")
     ap.add_argument("--no-rocprof", action="store_true",
-                    help="N=1: do not re-run a short headline pass under rocprofv3 --kernel-trace --stats for roofline.frac "
+                    help="with --full, N=1: do not re-run a short headline pass under rocprofv3 --kernel-trace --stats for roofline.frac "
                          "(implied by --no-secondary; the fraction then comes from the library's dispatch events)")
     ap.add_argument("--batched", type=int, default=8,
-                    help="N=1 only: after the BASELINE measurement, also time this many trajectories per GPU as one batched "
-                         "graph (reported under 'batched', never in 'value'); 0 = skip")
+                    help="with --full, N=1 only: after the BASELINE measurement, also time this many trajectories per GPU as one "
+                         "batched graph (reported under 'batched', never in 'value'); 0 = skip")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last one computed on rank 0 as DIR/<name>.npy (float32, ~8 MB): "
                          "u(T), du0, the parameter gradients dw1 db1 dw2 db2 and the parameters w1 b1 w2 b2 after its Adam update "
@@ -907,9 +918,10 @@ def main():
                 self.f.close()
             return False
 
-    def job(traj, n_steps, n_warmup):
+    def job(traj, n_steps, n_warmup, split=True):
         """`traj` independent trajectories on this GPU as ONE block-diagonal batched graph (traj = 1: the BASELINE workload).
-        Returns (elapsed seconds of n_steps bench steps, max over ranks; forward / backward ms of one solve; plan)."""
+        Returns (elapsed seconds of n_steps bench steps, max over ranks; forward / backward ms of one solve, or None when not
+        `split`; plan)."""
         # traj > 1: a block-diagonal batch of `traj` graphs with ONE structure.  The persistent plan solves its members one
         # after the other on the member's handle; where it is not available the batch becomes one big derived graph.
         try:
@@ -968,6 +980,8 @@ def main():
             tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
+        if not split:
+            return elapsed, None, None, plan
         # forward / backward split of one solve, by HIP events on the launch stream (outside the timed region)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         with device_turn():
@@ -1029,12 +1043,12 @@ def main():
         fence()
         return (time.perf_counter() - t0) / n_steps
 
-    elapsed, ms_fwd, ms_bwd, plan = job(1, args.steps, args.warmup)
+    elapsed, ms_fwd, ms_bwd, plan = job(1, args.steps, args.warmup, split=args.full)
     if args.dump_outputs and rank == 0:
         os.makedirs(args.dump_outputs, exist_ok=True)
         for name, a in job.outputs.items():
             np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
-    api_s = api_job(args.steps, args.warmup) if world == 1 else None
+    api_s = api_job(args.steps, args.warmup) if args.full and world == 1 else None
     step_ms = list(job.step_ms)      # this rank's per-step device times of the timed region (`value` stays K steps / wall time)
 
     def role_table(plan, traj):
@@ -1058,16 +1072,18 @@ def main():
 
     out = None
     if rank == 0:
-        roles, algo, us, kernels, dom = role_table(plan, 1)
-        achieved = algo[dom] / (float(us[dom]) * 1e-6) / 1e9
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")   # PMC-derived HBM bytes per launch, if collected
-        if os.path.exists(tpath):
-            try:
-                traffic = json.load(open(tpath)).get(roles[dom])
-            except Exception:
-                traffic = None
+        if args.full:
+            roles, algo, us, kernels, dom = role_table(plan, 1)
+            achieved = algo[dom] / (float(us[dom]) * 1e-6) / 1e9
+            traffic = None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")   # PMC-derived HBM bytes per launch, if collected
+            if os.path.exists(tpath):
+                try:
+                    traffic = json.load(open(tpath)).get(roles[dom])
+                except Exception:
+                    traffic = None
         fl, bl = plan.launch_count()
+        split_ms = {"ms_forward_solve": round(ms_fwd, 3), "ms_backward_solve": round(ms_bwd, 3)} if args.full else {}
         value = world * ODE_STEPS * args.steps / elapsed
         out = {
             "metric": "ODE-steps/sec (fwd+bwd) on 16k-node graph, 64-d feats",
@@ -1082,28 +1098,28 @@ def main():
                                    "forward + discrete adjoint of sum(u(T))",
                        "bench_step": "one full solve forward + backward (+ gradient all-reduce when N > 1) + fused Adam step",
                        "ode_steps_per_solve": ODE_STEPS, "rhs_evals_per_ode_step": 6,
-                       "launches_per_solve": {"forward": fl, "backward": bl},
-                       "ms_forward_solve": round(ms_fwd, 3), "ms_backward_solve": round(ms_bwd, 3),
+                       "launches_per_solve": {"forward": fl, "backward": bl}, **split_ms,
                        "tape_GB": round(plan.tape_bytes() / 1e9, 3),
                        "parallelism": f"dp{world} (independent trajectories, all-reduce of 8320-float grads)",
                        "collective": comm_record if comm_record is not None else {"impl": "none (one rank)", "world": 1}},
-            "roofline": {"bound": "hbm", "kernel": roles[dom], "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "traffic_source": "static: profiles/traffic.json, the rocprofv3 --pmc passes of tools/profile_round.sh "
-                                           "(FETCH_SIZE x 2 + WRITE_SIZE per launch), not collected in this run",
-                         "algorithmic_MB_per_launch": round(algo[dom] / 1e6, 2),
-                         "avg_launch_us": round(float(us[dom]), 3),
-                         "avg_launch_source": "the library's own dispatch events (hipExtLaunchKernelGGL start / stop, median of five passes); "
-                                              "rocprofv3 --kernel-trace reads ~1-4.5 % longer for the same launch (profiles/r05_k_kernel_stats.csv: 2.953 ms, frac 0.444)"},
-            "kernels": kernels,
-            "plan": sorted(plan.flags()), "fault": bool(plan.fault()),
         }
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "kernel": roles[dom], "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                               "traffic_source": "static: profiles/traffic.json, the rocprofv3 --pmc passes of tools/profile_round.sh "
+                                                 "(FETCH_SIZE x 2 + WRITE_SIZE per launch), not collected in this run",
+                               "algorithmic_MB_per_launch": round(algo[dom] / 1e6, 2),
+                               "avg_launch_us": round(float(us[dom]), 3),
+                               "avg_launch_source": "the library's own dispatch events (hipExtLaunchKernelGGL start / stop, median of five passes); "
+                                                    "rocprofv3 --kernel-trace reads ~1-4.5 % longer for the same launch (profiles/r05_k_kernel_stats.csv: 2.953 ms, frac 0.444)"}
+            out["kernels"] = kernels
+        out["plan"], out["fault"] = sorted(plan.flags()), bool(plan.fault())
         if api_s is not None:
             # the headline drives the C ABI directly (the call sequence a Julia shim would make); this is the same step through
             # the Python mirror of the reference's API -- plan pool, autograd, tensor allocation and loss included
             out["api_ms_per_step"] = round(1000.0 * api_s, 4)
             out["api_value"] = round(ODE_STEPS / api_s, 2)
-        if world == 1 and args.batched > 1:
+        if args.full and world == 1 and args.batched > 1:
             # Secondary: the same kernels when a launch is no longer ONE wave of workgroups.  `traj` trajectories of the
             # BASELINE workload on this GPU as one block-diagonal batched GNNGraph (test/runtests.jl:89-102); each launch
             # then processes traj x the algorithmic bytes.  Not the headline: `value` above is one trajectory per GPU.
@@ -1124,7 +1140,7 @@ def main():
                 "pipeline": pipeline_stats(planb),
             }
             planb = None
-        if world == 1 and args.batched > 1:
+        if args.full and world == 1 and args.batched > 1:
             # The same solve on a graph of TWICE the size (32 768 nodes / 262 144 edges, 1 024 tiles: more than the 512 workgroups
             # that can be resident): the persistent launches with two tiles per workgroup.  Not the headline; here to show what a
             # graph that is not the bench's own size runs at.
@@ -1190,15 +1206,15 @@ def main():
                                   "ms_per_solve_forward_backward": round(msv, 3), "plan": sorted(planv.flags()), "fault": bool(planv.fault())}
                 planv = None
             out["variants"] = variants
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, outs = cpu_baseline(s, t, u0_h, w1_h, b1_h, w2_h, b2_h)
             out["cpu_baseline"] = cb
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
     plan = None
-    if out is not None and world == 1 and not (args.no_rocprof or args.no_secondary):
+    if out is not None and args.full and world == 1 and not (args.no_rocprof or args.no_secondary):
         rocprof_roofline(out, roles[dom], algo[dom])
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         sec = secondary(dev, world, rank, dist, rocprof=(world == 1 and not args.no_rocprof))          # every rank takes part (N > 1: the data-parallel C4 step)
         if out is not None:
             out["secondary"] = sec

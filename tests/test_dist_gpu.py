@@ -75,14 +75,15 @@ def test_bench_n2_path_end_to_end_with_torchrun_and_gloo():
     # the driver's N > 1 launch line (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     # --master-port P bench.py --gpus N ...) rehearsed with two ranks sharing this box's one GPU: NGPDE_BENCH_BACKEND=gloo carries
     # the collectives through the host (the measured configuration is nccl = RCCL, one rank per GPU).  Rendezvous, per-rank plans,
-    # gradient all-reduce, barrier + max over ranks, the C4 / C5 data-parallel legs and ONE JSON line from rank 0.
+    # gradient all-reduce, barrier + max over ranks, the C4 data-parallel leg of --full and ONE JSON line from rank 0.
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NGPDE_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -107,6 +108,25 @@ def _run_bench(extra_env, *argv, timeout=900):
                        timeout=timeout)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     return r, [json.loads(l) for l in lines]
+
+
+def test_bench_plain_run_prints_the_headline_only(tmp_path):
+    # without --full the run is set-up, warm-up, the timed steps, --dump-outputs and the line: the headline's fields, none of the
+    # legs that --full adds (their own solves, child passes and CPU runs), and the last timed step's outputs on disk
+    r, recs = _run_bench({}, "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(recs) == 1, r.stdout[-2000:]
+    d = recs[0]
+    assert d["metric"] == "ODE-steps/sec (fwd+bwd) on 16k-node graph, 64-d feats" and d["unit"] == "ODE-steps/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] == pytest.approx(50 * 2 / (d["ms_per_step"] * 1e-3 * 2), rel=1e-3)
+    assert d["fault"] is False and "persistent_fwd" in d["plan"]
+    full_only = {"roofline", "kernels", "api_value", "batched", "larger_graph", "variants", "cpu_baseline", "secondary"}
+    assert not full_only & set(d) and "ms_forward_solve" not in d["config"]
+    outs = {"uT", "du0", "dw1", "db1", "dw2", "db2", "w1", "b1", "w2", "b2"}
+    assert {p.stem for p in tmp_path.glob("*.npy")} == outs
+    uT, dw1 = np.load(tmp_path / "uT.npy"), np.load(tmp_path / "dw1.npy")
+    assert uT.shape == (16384, 64) and dw1.shape == (64, 64) and np.isfinite(uT).all() and np.isfinite(dw1).all()
 
 
 def test_bench_plain_launch_spawns_its_ranks():

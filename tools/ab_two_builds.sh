@@ -7,7 +7,7 @@ for v in base noslp; do
   cp $L/ab_$v.so $L/libngpde_hip.so
   echo "== $v pass $rep"
   python3 tools/bench_layers.py --only c4 --traj 64 --reps 30 2>/dev/null | cut -c80-170
-  python3 bench.py --no-rocprof --steps 10 2>/dev/null | python3 -c "
+  python3 bench.py --full --no-rocprof --steps 10 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s=d['secondary']
