@@ -658,6 +658,29 @@ int32_t ngpde_rk_control_trial_dt(const ngpde_rk_control_t *state, double d0, do
 int32_t ngpde_rk_control_initial_dt(ngpde_rk_control_t *state, double d0, double d1, double norm_df);
 int32_t ngpde_rk_control_step(ngpde_rk_control_t *state, double eest, int32_t *action);
 
+/* Dense output (DiffEq's `saveat` semantics: the save points do not change the steps taken).  Tsit5's free 4th-order interpolant
+ * (Tsitouras 2011, as OrdinaryDiffEq's Tsit5 evaluates it) over an accepted step [t_n, t_n + dt]:
+ *   u(t_n + theta dt) = u_n + dt sum_{i=1..7} b_i(theta) k_i,   b_i(theta) = r_i1 theta + r_i2 theta^2 + r_i3 theta^3 + r_i4 theta^4,
+ * k_7 = f(u_{n+1}) (the seventh stage of the attempt, FSAL).  b_i(0) = 0 and b_i(1) = Tsit5's b_i (b_7 = 0).
+ *   tsit5_interp_coefs:  host only; coefs[i] = dt b_i(theta) in double, i < 7.  0 <= theta <= 1 and a finite dt, else
+ *                        NGPDE_ERR_INVALID_ARGUMENT.
+ *   dense_output:        out_j = u_prev + sum_i coefs[j n_stages + i] k_i for j < n_out in one pass over u_prev and the stages (one
+ *                        launch per 16 outputs).  out_j is BITWISE ngpde_rk_stage_combine(count, 1, u_prev, n_stages, k, coefs + j
+ *                        n_stages, out_j): 1 * u_prev, then the fmaf chain in stage order.  1 <= n_stages <= 8; k / coefs / outs are
+ *                        HOST arrays (of device pointers / floats [n_out][n_stages] / device pointers); the outputs must not alias the
+ *                        inputs.
+ *   dense_output_pullback: its adjoint.  kbar_i = sum_j coefs[j n_stages + i] douts[j] (written) and, when ubar is not NULL,
+ *                        ubar += sum_j douts[j].  BITWISE the fmaf chain in j order that ngpde_rk_stage_combine forms (kbar_i: base
+ *                        NULL, coefficients coefs[.][i]; ubar: c_self = 1, coefficients 1), chained through calls with the previous
+ *                        partial as base (c_self 1) beyond 8 terms -- 1 * v is exact, so the split does not change the bits.  Each
+ *                        cotangent is read once per launch of up to 16; n_out >= 1.
+ * Both: element-wise, float4 when count % 4 == 0 and every pointer is 16-byte aligned; no atomics, no allocation, graph-capture safe. */
+int32_t ngpde_rk_tsit5_interp_coefs(double theta, double dt, double *coefs /* [7] */);
+int32_t ngpde_rk_dense_output(int64_t count, const float *u_prev, int32_t n_stages, const float *const *k, int32_t n_out,
+                              const float *coefs, float *const *outs, ngpde_stream_t stream);
+int32_t ngpde_rk_dense_output_pullback(int64_t count, int32_t n_out, const float *const *douts, int32_t n_stages, const float *coefs,
+                                       float *ubar, float *const *kbar, ngpde_stream_t stream);
+
 /* Optimiser step on the flat parameter vector, one launch behind the gradient all-reduce on the same stream
  * [UPSTREAM Optimisers.jl Adam / Rprop; reference call sites docs/src/tutorials/graph_node.md:90,122-129, VMH.md:97].
  * grad_scale multiplies the (reduced) gradient first: 1/world_size for a mean over data-parallel ranks.

@@ -186,6 +186,9 @@ SIGNATURES = {
     "ngpde_rk_control_trial_dt": (_i32, [C.POINTER(RkControl), C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "ngpde_rk_control_initial_dt": (_i32, [C.POINTER(RkControl), C.c_double, C.c_double, C.c_double]),
     "ngpde_rk_control_step": (_i32, [C.POINTER(RkControl), C.c_double, C.POINTER(_i32)]),
+    "ngpde_rk_tsit5_interp_coefs": (_i32, [C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "ngpde_rk_dense_output": (_i32, [_i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "ngpde_rk_dense_output_pullback": (_i32, [_i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_gno_message_supported": (_i32, [_i32, _i32]),
     "ngpde_gno_message_backward_from_nodes": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ngpde_gno_message_forward": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

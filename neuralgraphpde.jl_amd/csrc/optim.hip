@@ -102,6 +102,121 @@ void launch_rk_combine(int n_terms, int64_t count, float c_self, const float *ba
   }
 }
 
+// Dense output of one accepted step at up to kDenseMax save times: out[j] = 1 * u_prev + sum_i coef[j][i] k[i] (Tsit5's free
+// interpolant with coef[j][i] = dt b_i(theta_j)).  u_prev and the stages are read once for all outputs; every output is the fmaf chain
+// rk_combine_kernel forms with c_self = 1 (all loads first, then the chain in stage order), so it is bitwise one stage-combine call.
+// The j loop is unrolled against the constant bound with a uniform early exit: the kernel-argument arrays are only ever indexed by
+// constants.
+constexpr int kDenseMax = 16;
+struct DenseK {
+  const float *k[8];
+  float *out[kDenseMax];
+  float coef[kDenseMax][8];
+  int n_out;
+};
+template <int N, class T>
+__global__ void rk_dense_output_kernel(int64_t count, const T *u_prev, const DenseK d) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+    T t[N];
+#pragma unroll
+    for (int s = 0; s < N; ++s) t[s] = reinterpret_cast<const T *>(d.k[s])[i];     // all loads first
+    const T u = u_prev[i];
+#pragma unroll
+    for (int j = 0; j < kDenseMax; ++j) {
+      if (j >= d.n_out) break;
+      T v;
+      if constexpr (sizeof(T) == 16) {
+        v = f4_scale(1.0f, u);
+#pragma unroll
+        for (int s = 0; s < N; ++s) v = f4_fma(d.coef[j][s], t[s], v);
+      } else {
+        v = 1.0f * u;
+#pragma unroll
+        for (int s = 0; s < N; ++s) v = fmaf(d.coef[j][s], t[s], v);
+      }
+      reinterpret_cast<T *>(d.out[j])[i] = v;
+    }
+  }
+}
+
+// Its adjoint over up to kDenseMax cotangents: kbar[s] = (first ? 0 : 1 * kbar[s]) + sum_j coef[j][s] dout[j] (the fmaf chain in j
+// order) and, when ubar is given, ubar = 1 * ubar + sum_j 1 * dout[j].  Each cotangent is read once; a later launch of a longer list
+// continues the chains from the partial sums (first = 0), as chained stage-combine calls would.
+struct DensePullK {
+  const float *dout[kDenseMax];
+  float *kbar[8];
+  float coef[kDenseMax][8];
+  int n_out;
+  int first;
+};
+template <int N, class T>
+__global__ void __launch_bounds__(256) rk_dense_output_pullback_kernel(int64_t count, T *ubar, const DensePullK d) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+    // every load before the first store: a load behind a store to an array that may alias it would wait for that store
+    T g[kDenseMax], v[N], w;
+#pragma unroll
+    for (int j = 0; j < kDenseMax; ++j)
+      if (j < d.n_out) g[j] = reinterpret_cast<const T *>(d.dout[j])[i];
+    if constexpr (sizeof(T) == 16) {
+#pragma unroll
+      for (int s = 0; s < N; ++s) v[s] = d.first ? f4_zero() : f4_scale(1.0f, reinterpret_cast<const T *>(d.kbar[s])[i]);
+      w = ubar ? f4_scale(1.0f, ubar[i]) : f4_zero();
+#pragma unroll
+      for (int s = 0; s < N; ++s) {
+#pragma unroll
+        for (int j = 0; j < kDenseMax; ++j)
+          if (j < d.n_out) v[s] = f4_fma(d.coef[j][s], g[j], v[s]);
+      }
+#pragma unroll
+      for (int j = 0; j < kDenseMax; ++j)
+        if (j < d.n_out) w = f4_fma(1.0f, g[j], w);
+    } else {
+#pragma unroll
+      for (int s = 0; s < N; ++s) v[s] = d.first ? 0.f : 1.0f * reinterpret_cast<const T *>(d.kbar[s])[i];
+      w = ubar ? 1.0f * ubar[i] : 0.f;
+#pragma unroll
+      for (int s = 0; s < N; ++s) {
+#pragma unroll
+        for (int j = 0; j < kDenseMax; ++j)
+          if (j < d.n_out) v[s] = fmaf(d.coef[j][s], g[j], v[s]);
+      }
+#pragma unroll
+      for (int j = 0; j < kDenseMax; ++j)
+        if (j < d.n_out) w = fmaf(1.0f, g[j], w);
+    }
+#pragma unroll
+    for (int s = 0; s < N; ++s) reinterpret_cast<T *>(d.kbar[s])[i] = v[s];
+    if (ubar) ubar[i] = w;
+  }
+}
+
+#define NGPDE_STAGE_SWITCH(n, KERNEL, ...)                                                      \
+  switch (n) {                                                                                  \
+    case 1: hipLaunchKernelGGL((KERNEL<1, T>), __VA_ARGS__); break;                             \
+    case 2: hipLaunchKernelGGL((KERNEL<2, T>), __VA_ARGS__); break;                             \
+    case 3: hipLaunchKernelGGL((KERNEL<3, T>), __VA_ARGS__); break;                             \
+    case 4: hipLaunchKernelGGL((KERNEL<4, T>), __VA_ARGS__); break;                             \
+    case 5: hipLaunchKernelGGL((KERNEL<5, T>), __VA_ARGS__); break;                             \
+    case 6: hipLaunchKernelGGL((KERNEL<6, T>), __VA_ARGS__); break;                             \
+    case 7: hipLaunchKernelGGL((KERNEL<7, T>), __VA_ARGS__); break;                             \
+    default: hipLaunchKernelGGL((KERNEL<8, T>), __VA_ARGS__); break;                            \
+  }
+
+template <class T>
+void launch_rk_dense_output(int n_stages, int64_t count, const float *u_prev, const DenseK &d, hipStream_t stream) {
+  const dim3 grid((unsigned)std::min<int64_t>((count + 255) / 256, 4096)), block(256);
+  const T *u = reinterpret_cast<const T *>(u_prev);
+  NGPDE_STAGE_SWITCH(n_stages, rk_dense_output_kernel, grid, block, 0, stream, count, u, d)
+}
+
+template <class T>
+void launch_rk_dense_output_pullback(int n_stages, int64_t count, float *ubar, const DensePullK &d, hipStream_t stream) {
+  const dim3 grid((unsigned)std::min<int64_t>((count + 255) / 256, 4096)), block(256);
+  T *ub = reinterpret_cast<T *>(ubar);
+  NGPDE_STAGE_SWITCH(n_stages, rk_dense_output_pullback_kernel, grid, block, 0, stream, count, ub, d)
+}
+#undef NGPDE_STAGE_SWITCH
+
 // Scaled RMS norm of an embedded error estimate (OrdinaryDiffEq calculate_residuals + the default internalnorm):
 //   out = sqrt( (1/count) sum_i ( e_i / (abstol + reltol max(|u_prev_i|, |u_new_i|)) )^2 ),  e_i = sum_j coef[j] term[j][i]
 // e_i is formed exactly as rk_combine_kernel forms it with base = NULL (all loads first, then the fmaf chain in term order); the
@@ -206,6 +321,70 @@ int32_t ngpde_rk_stage_combine(int64_t count, float c_self, const float *base, i
   if (count % 4 == 0 && (bits & 15) == 0) launch_rk_combine<float4>(n_terms, count / 4, c_self, base, k, out, (hipStream_t)stream);
   else launch_rk_combine<float>(n_terms, count, c_self, base, k, out, (hipStream_t)stream);
   NGPDE_LAUNCH_CHECK("rk_combine_kernel");
+  return NGPDE_OK;
+}
+
+int32_t ngpde_rk_dense_output(int64_t count, const float *u_prev, int32_t n_stages, const float *const *k, int32_t n_out,
+                              const float *coefs, float *const *outs, ngpde_stream_t stream) {
+  NGPDE_RANGE();
+  NGPDE_REQUIRE(count >= 0 && n_stages >= 1 && n_stages <= 8 && n_out >= 0, NGPDE_ERR_INVALID_ARGUMENT,
+                "ngpde_rk_dense_output: count >= 0, 1 <= n_stages <= 8 and n_out >= 0 required (got %lld, %d, %d)", (long long)count,
+                n_stages, n_out);
+  if (count == 0 || n_out == 0) return NGPDE_OK;
+  NGPDE_REQUIRE(u_prev && k && coefs && outs, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_dense_output: NULL argument");
+  uintptr_t kbits = reinterpret_cast<uintptr_t>(u_prev);
+  for (int s = 0; s < n_stages; ++s) {
+    NGPDE_REQUIRE(k[s], NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_dense_output: stage %d is NULL", s);
+    kbits |= reinterpret_cast<uintptr_t>(k[s]);
+  }
+  for (int j = 0; j < n_out; ++j) NGPDE_REQUIRE(outs[j], NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_dense_output: output %d is NULL", j);
+  for (int j0 = 0; j0 < n_out; j0 += kDenseMax) {
+    DenseK d{};
+    d.n_out = std::min(kDenseMax, n_out - j0);
+    uintptr_t bits = kbits;
+    for (int s = 0; s < n_stages; ++s) d.k[s] = k[s];
+    for (int j = 0; j < d.n_out; ++j) {
+      d.out[j] = outs[j0 + j];
+      bits |= reinterpret_cast<uintptr_t>(d.out[j]);
+      for (int s = 0; s < n_stages; ++s) d.coef[j][s] = coefs[(size_t)(j0 + j) * n_stages + s];
+    }
+    if (count % 4 == 0 && (bits & 15) == 0) launch_rk_dense_output<float4>(n_stages, count / 4, u_prev, d, (hipStream_t)stream);
+    else launch_rk_dense_output<float>(n_stages, count, u_prev, d, (hipStream_t)stream);
+    NGPDE_LAUNCH_CHECK("rk_dense_output_kernel");
+  }
+  return NGPDE_OK;
+}
+
+int32_t ngpde_rk_dense_output_pullback(int64_t count, int32_t n_out, const float *const *douts, int32_t n_stages, const float *coefs,
+                                       float *ubar, float *const *kbar, ngpde_stream_t stream) {
+  NGPDE_RANGE();
+  NGPDE_REQUIRE(count >= 0 && n_stages >= 1 && n_stages <= 8 && n_out >= 1, NGPDE_ERR_INVALID_ARGUMENT,
+                "ngpde_rk_dense_output_pullback: count >= 0, 1 <= n_stages <= 8 and n_out >= 1 required (got %lld, %d, %d)",
+                (long long)count, n_stages, n_out);
+  if (count == 0) return NGPDE_OK;
+  NGPDE_REQUIRE(douts && coefs && kbar, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_dense_output_pullback: NULL argument");
+  uintptr_t kbits = reinterpret_cast<uintptr_t>(ubar);
+  for (int s = 0; s < n_stages; ++s) {
+    NGPDE_REQUIRE(kbar[s], NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_dense_output_pullback: stage cotangent %d is NULL", s);
+    kbits |= reinterpret_cast<uintptr_t>(kbar[s]);
+  }
+  for (int j = 0; j < n_out; ++j)
+    NGPDE_REQUIRE(douts[j], NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_dense_output_pullback: cotangent %d is NULL", j);
+  for (int j0 = 0; j0 < n_out; j0 += kDenseMax) {
+    DensePullK d{};
+    d.n_out = std::min(kDenseMax, n_out - j0);
+    d.first = j0 == 0;
+    uintptr_t bits = kbits;
+    for (int s = 0; s < n_stages; ++s) d.kbar[s] = kbar[s];
+    for (int j = 0; j < d.n_out; ++j) {
+      d.dout[j] = douts[j0 + j];
+      bits |= reinterpret_cast<uintptr_t>(d.dout[j]);
+      for (int s = 0; s < n_stages; ++s) d.coef[j][s] = coefs[(size_t)(j0 + j) * n_stages + s];
+    }
+    if (count % 4 == 0 && (bits & 15) == 0) launch_rk_dense_output_pullback<float4>(n_stages, count / 4, ubar, d, (hipStream_t)stream);
+    else launch_rk_dense_output_pullback<float>(n_stages, count, ubar, d, (hipStream_t)stream);
+    NGPDE_LAUNCH_CHECK("rk_dense_output_pullback_kernel");
+  }
   return NGPDE_OK;
 }
 

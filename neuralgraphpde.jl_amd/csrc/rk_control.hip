@@ -35,12 +35,36 @@ int32_t propose(ngpde_rk_control_t *s, double dt_next) {
   return NGPDE_OK;
 }
 
+// Tsit5's free 4th-order interpolant (Tsitouras 2011, the form OrdinaryDiffEq's Tsit5 dense output uses):
+// b_i(theta) = r_i1 theta + r_i2 theta^2 + r_i3 theta^3 + r_i4 theta^4 over the seven stages, the seventh being f(u_new)
+constexpr double kTsit5Interp[7][4] = {
+    {1.0, -2.763706197274826, 2.9132554618219126, -1.0530884977290216},
+    {0.0, 0.13169999999999998, -0.2234, 0.1017},
+    {0.0, 3.9302962368947516, -5.941033872131505, 2.490627285651253},
+    {0.0, -12.411077166933676, 30.33818863028232, -16.548102889244902},
+    {0.0, 37.50931341651104, -88.1789048947664, 47.37952196281928},
+    {0.0, -27.896526289197286, 65.09189467479366, -34.87065786149661},
+    {0.0, 1.5, -4.0, 2.5},
+};
+
 }  // namespace
 }  // namespace ngpde
 
 using namespace ngpde;
 
 extern "C" {
+
+int32_t ngpde_rk_tsit5_interp_coefs(double theta, double dt, double *coefs) {
+  NGPDE_REQUIRE(coefs, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_tsit5_interp_coefs: NULL argument");
+  NGPDE_REQUIRE(theta >= 0.0 && theta <= 1.0, NGPDE_ERR_INVALID_ARGUMENT,
+                "ngpde_rk_tsit5_interp_coefs: 0 <= theta <= 1 required (got %g)", theta);
+  NGPDE_REQUIRE(std::isfinite(dt), NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_tsit5_interp_coefs: dt must be finite (got %g)", dt);
+  for (int i = 0; i < 7; ++i) {
+    const double *r = kTsit5Interp[i];
+    coefs[i] = dt * (theta * (r[0] + theta * (r[1] + theta * (r[2] + theta * r[3]))));
+  }
+  return NGPDE_OK;
+}
 
 int32_t ngpde_rk_control_init(ngpde_rk_control_t *s, double t0, double t_end, double dt, double dtmax, double saveat, int64_t maxiters) {
   NGPDE_REQUIRE(s, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rk_control_init: NULL state");

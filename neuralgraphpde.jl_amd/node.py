@@ -2,6 +2,8 @@
 (/root/reference/docs/src/tutorials/graph_node.md:44-66): `dudt(u, p, t) = model(u, p, st)` integrated
 by an explicit Runge-Kutta scheme.  BASELINE configs fix the step count (Euler x 10, Tsit5 x 50); the tutorials themselves
 solve with adaptive Tsit5 (graph_node.md:80-81, VMH.md:87), which NeuralODE(..., adaptive=True) runs on the generic path below.
+Its saveat either cuts the steps to land on the save points (a scalar, by default) or, as DiffEq does, leaves the steps alone and
+evaluates Tsit5's free interpolant at them (interpolate_saveat=True, or a vector of save times).
 The pullback is the discrete adjoint of the steps taken.
 
 When the right-hand side is Chain(GCNConv(d => d, act), GCNConv(d => d, act)) on one graph (the
@@ -110,14 +112,84 @@ def _error_norm(terms, coefs, u_prev, u_new, abstol, reltol, ws, out):
     return float(out.item())
 
 
+def _zero(ref):
+    """a float32 array of ref's size holding zeros (ngpde_rk_stage_combine with no base and no terms)"""
+    out = torch.empty_like(ref, memory_format=torch.contiguous_format)
+    _lib.check(_lib.load().ngpde_rk_stage_combine(out.numel(), 0.0, None, 0, None, None, out.data_ptr(), _lib.current_stream()))
+    return out
+
+
+def tsit5_interp_coefs(theta, dt):
+    """dt b_i(theta), i = 1..7: Tsit5's free interpolant over a step of size dt (ngpde_rk_tsit5_interp_coefs, in double)"""
+    out = (C.c_double * 7)()
+    _lib.check(_lib.load().ngpde_rk_tsit5_interp_coefs(float(theta), float(dt), out))
+    return list(out)
+
+
+def _dense_output(u_prev, ks, rows, outs):
+    """outs[j] = u_prev + sum_i rows[j][i] ks[i] for every j (ngpde_rk_dense_output: one pass over u_prev and the stages)"""
+    karr = (C.c_void_p * len(ks))(*[k.data_ptr() for k in ks])
+    cf = (C.c_float * (len(rows) * len(ks)))(*[float(c) for r in rows for c in r])
+    oarr = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+    _lib.check(_lib.load().ngpde_rk_dense_output(u_prev.numel(), u_prev.data_ptr(), len(ks), karr, len(outs), cf, oarr,
+                                                  _lib.current_stream()))
+
+
+def _dense_output_pullback(douts, rows, n_stages, ubar):
+    """the stage cotangents sum_j rows[j][i] douts[j], i < n_stages, and ubar += sum_j douts[j] (ngpde_rk_dense_output_pullback)"""
+    kbar = [torch.empty_like(douts[0]) for _ in range(n_stages)]
+    darr = (C.c_void_p * len(douts))(*[d.data_ptr() for d in douts])
+    cf = (C.c_float * (len(rows) * n_stages))(*[float(c) for r in rows for c in r])
+    karr = (C.c_void_p * n_stages)(*[k.data_ptr() for k in kbar])
+    _lib.check(_lib.load().ngpde_rk_dense_output_pullback(douts[0].numel(), len(douts), darr, n_stages, cf, _lib.ptr(ubar), karr,
+                                                           _lib.current_stream()))
+    return kbar
+
+
+def _is_vector(saveat):
+    return isinstance(saveat, (list, tuple)) or getattr(saveat, "ndim", 0) >= 1
+
+
+def dense_save_times(tspan, saveat, save_start):
+    """the save times of an interpolating solve (DiffEq's saveat): a scalar gives t0 (with save_start), t0 + k saveat for every
+    k >= 1 below t_end, and t_end, a point within 1e-12 (t_end - t0) of t_end counting as t_end; a vector gives its own times, t0
+    dropped when save_start is False"""
+    t0, t1 = float(tspan[0]), float(tspan[1])
+    if _is_vector(saveat):
+        times = [float(s) for s in saveat]
+        return times[1:] if (times and times[0] == t0 and not save_start) else times
+    saveat, span = float(saveat), t1 - t0
+    times = [t0] if save_start else []
+    k = 1
+    while t0 + k * saveat < t1 - 1e-12 * span:
+        times.append(t0 + k * saveat)
+        k += 1
+    return times + [t1]
+
+
+def saves_in_step(times, j, t_n, t_next, dt):
+    """the save times of the accepted step [t_n, t_next] of size dt, from times[j] on: (interior [(slot, theta)] with t_n < s <
+    t_next and theta = (s - t_n) / dt, the slot of s == t_next or None, the next j).  A time equal to the step's end is the step's
+    state itself (DiffEq's curt == t); theta is clamped to [0, 1] against the last bit of t_n + dt."""
+    interior = []
+    while j < len(times) and times[j] < t_next:
+        interior.append((j, min(max((times[j] - t_n) / dt, 0.0), 1.0)))
+        j += 1
+    end = None
+    if j < len(times) and times[j] == t_next:
+        end, j = j, j + 1
+    return interior, end, j
+
+
 class _Control:
-    """the library's step-size controller (ngpde_rk_control_*) for one adaptive solve"""
+    """the library's step-size controller (ngpde_rk_control_*) for one adaptive solve (an interpolating solve stops at t_end only)"""
 
     def __init__(self, node):
         self.state = _lib.RkControl()
         t0, t1 = node.tspan
+        saveat = 0.0 if node.save_times is not None else float(node.saveat or 0.0)
         _lib.check(_lib.load().ngpde_rk_control_init(C.byref(self.state), float(t0), float(t1), float(node.dt or 0.0),
-                                                     float(node.dtmax or 0.0), float(node.saveat or 0.0), int(node.maxiters)))
+                                                     float(node.dtmax or 0.0), saveat, int(node.maxiters)))
 
     def trial_dt(self, d0, d1):
         dt0 = C.c_double()
@@ -136,13 +208,25 @@ class _Control:
 def _rk_forward(node, u, ps_in, st, needs, fresh=False):
     """u(T) (or the saved states) of the solve; with `needs` also the tape: per step and stage the (stage input, stage output) pair
     whose autograd closure is the layers' pullback.  The last item is the schedule (dts, saved) of the steps taken: fixed, or the
-    accepted steps of an adaptive solve.  fresh: the stage inputs get version counters of their own (a captured solve refills its
+    accepted steps of an adaptive solve -- an interpolating one (node.save_times) adds a third item, its record of the saves: the
+    slot of t0, per step the slot its end fills and its interpolated (slots, coefficient rows), the final step's seventh-stage
+    pair when that step interpolates.  fresh: the stage inputs get version counters of their own (a captured solve refills its
     static input buffer before every replay; the closures are only ever run at capture time)"""
     a, b = TABLEAUS[node.solver]
     S = len(b)
     ucur, tape, st_out = u, [], st
     saving = node.saving
     saves = [ucur] if (saving and node.save_start) else []      # saveat: the states at t0 (+ j saveat), as DiffEq's sol.u
+    times = node.save_times if node.adaptive else None
+    dense = None
+    if times is not None:    # interpolating saveat: the output is filled step by step (the steps are the solve's own)
+        saves = []
+        out = torch.empty((len(times),) + tuple(ucur.shape), dtype=ucur.dtype, device=ucur.device)
+        dense = dict(t0=None, end=[], interp=[], last=None)
+        jt = 0
+        if times and times[0] == float(node.tspan[0]):
+            dense["t0"], jt = 0, 1
+            _combine(ucur, 1.0, [], [], out=out[0])
 
     def stage(U):
         nonlocal st_out
@@ -196,6 +280,7 @@ def _rk_forward(node, u, ps_in, st, needs, fresh=False):
                 nf += S
                 eest = _error_norm(ks + [last[1].detach()], [dt * bt for bt in _TSIT5_BTILDE], ucur, unew, *tol, ws, eout)
                 eests.append(eest)
+                t_n = ctl.state.t
                 action = ctl.step(eest)              # (raises NgpdeError(ERR_STATE) when maxiters / dtmin end the solve)
                 if action == _lib.RK_REJECT:
                     first = pairs[0]                 # the attempt's other stages are dropped
@@ -203,6 +288,19 @@ def _rk_forward(node, u, ps_in, st, needs, fresh=False):
                 first = last
                 dts.append(dt)
                 saved.append(bool(ctl.state.saved))
+                if dense is not None:
+                    # Tsit5's free interpolant over [t_n, t_n + dt] at the step's interior save times, k_7 = f(u_new): one launch
+                    # writing into the output; a save time on the step's end is u_new itself
+                    interior, end, jt = saves_in_step(times, jt, t_n, ctl.state.t, dt)
+                    rows = [tsit5_interp_coefs(th, dt) for _, th in interior]
+                    if interior:
+                        _dense_output(ucur, ks + [last[1].detach()], rows, [out[sl] for sl, _ in interior])
+                        if needs and action == _lib.RK_DONE:
+                            dense["last"] = last     # the final step's seventh stage: its pullback carries g_7 (no step n+1 does)
+                    if end is not None:
+                        _combine(unew, 1.0, [], [], out=out[end])
+                    dense["end"].append(end)
+                    dense["interp"].append(([sl for sl, _ in interior], rows) if interior else None)
             ucur = unew
             if needs:
                 tape.append(pairs)
@@ -215,6 +313,11 @@ def _rk_forward(node, u, ps_in, st, needs, fresh=False):
         c = ctl.state
         node.stats = dict(naccept=int(c.naccept), nreject=int(c.nreject), nf=nf, dts=list(dts), t=float(c.t), eests=eests,
                           init_norms=init_norms)
+        if dense is not None:
+            assert jt == len(times)
+            node.stats.update(save_times=list(times), ninterp=sum(len(r[0]) for r in dense["interp"] if r is not None))
+    if dense is not None:
+        return out, tape, st_out, (dts, saved, dense)
     if saving:      # [T][N][D]: the memory layout of the reference's (D x N x T) array; rows written by library launches
         out = torch.empty((len(saves),) + tuple(ucur.shape), dtype=ucur.dtype, device=ucur.device)
         for j, s_ in enumerate(saves):
@@ -238,25 +341,73 @@ def _accumulate_many(pairs):
 
 
 def _rk_backward(node, tape, duT, params, schedule, retain=False):
-    """discrete adjoint of _rk_forward over the steps of `schedule` (dts, saved), their sizes held fixed: (du0, cotangents of `params`)"""
+    """discrete adjoint of _rk_forward over the steps of `schedule` (dts, saved[, dense]), their sizes held fixed: (du0, cotangents
+    of `params`).  An interpolating solve's saves inside step n are pulled back by one ngpde_rk_dense_output_pullback launch into g_1..g_7
+    and a cotangent of u_n: g_i joins stage i's K-bar, g_7 -- the cotangent of f(u_{n+1}) -- joins the first stage's K-bar of step n + 1
+    (the same evaluation, FSAL), or for the final step the taped seventh stage's pullback before the reverse sweep starts."""
     a, b = TABLEAUS[node.solver]
     S = len(b)
-    dts, saved = schedule
+    dts, saved = schedule[:2]
+    dense = schedule[2] if len(schedule) > 2 else None
     acc = [None] * len(params)
     saving = node.saving
-    # slot of duT holding the cotangent of u_n, the state at the start of step n (None: not saved)
-    n_saved = 1 if node.save_start else 0
-    slot, start_slot = (0 if node.save_start else None), []
-    for n in range(len(dts)):
-        start_slot.append(slot)
-        slot, n_saved = (n_saved, n_saved + 1) if saved[n] else (None, n_saved)
-    lam = duT[n_saved - 1] if saving else duT     # (a solve with saveat ends on its last save point)
+
+    def absorb(grads):
+        pairs_ag = []
+        for n, g in enumerate(grads):
+            if g is None:
+                continue
+            if acc[n] is None:
+                # own the accumulator in a layout _dense can view without a copy (an expanded / strided cotangent would make
+                # _dense return a temporary, and the sum written into it would be lost)
+                acc[n] = g if (g.is_contiguous() or (g.dim() == 2 and g.T.is_contiguous())) else g.contiguous()
+            elif acc[n].stride() == g.stride():
+                # same layout for every stage's cotangent of one parameter: add in memory order
+                pairs_ag.append((_dense(acc[n]), _dense(g)))
+            else:       # layouts differ (one transposed, one not): index-wise sum in the accumulator's own layout
+                pairs_ag.append((_dense(acc[n]), _dense(g.contiguous() if acc[n].is_contiguous() else g.T.contiguous().T)))
+        _accumulate_many(pairs_ag)      # ONE launch for all parameters of this stage (sixteen arrays in the VMH tutorial's model)
+
+    if dense is None:
+        # slot of duT holding the cotangent of u_n, the state at the start of step n (None: not saved)
+        n_saved = 1 if node.save_start else 0
+        slot, start_slot = (0 if node.save_start else None), []
+        for n in range(len(dts)):
+            start_slot.append(slot)
+            slot, n_saved = (n_saved, n_saved + 1) if saved[n] else (None, n_saved)
+        lam = duT[n_saved - 1] if saving else duT     # (a solve with saveat ends on its last save point)
+    else:
+        start_slot = [dense["t0"]] + dense["end"][:-1]
+        lam = duT[dense["end"][-1]] if dense["end"][-1] is not None else _zero(duT[0])
+    pulled = {}      # step -> (g_1..g_7, the cotangent of u_n) of its interpolated saves
+
+    def pull(n):
+        if dense is not None and n >= 0 and dense["interp"][n] is not None:
+            slots, rows = dense["interp"][n]
+            h = _zero(duT[0])
+            pulled[n] = (_dense_output_pullback([duT[sl] for sl in slots], rows, S + 1, h), h)
+
+    if dense is not None:
+        pull(len(dts) - 1)
+        if len(dts) - 1 in pulled:         # the final step's seventh stage f(u_N): its taped pair, K-bar = g_7
+            U, k = dense["last"]
+            grads = torch.autograd.grad(k, [U] + params, pulled[len(dts) - 1][0][S], allow_unused=True, retain_graph=retain)
+            absorb(grads[1:])
+            if grads[0] is not None:
+                lam = _combine(lam, 1.0, [grads[0].contiguous()], [1.0])
     for n_step, pairs in zip(range(len(tape) - 1, -1, -1), reversed(tape)):
         dt = dts[n_step]
+        pull(n_step - 1)                   # step n - 1's g_7 is a cotangent of this step's first stage
         ubar = [None] * S
         for i in reversed(range(S)):
             terms = [ubar[j] for j in range(i + 1, S) if a[j][i] != 0.0 and ubar[j] is not None]
             coefs = [dt * a[j][i] for j in range(i + 1, S) if a[j][i] != 0.0 and ubar[j] is not None]
+            if n_step in pulled:
+                terms.append(pulled[n_step][0][i])
+                coefs.append(1.0)
+            if i == 0 and n_step - 1 in pulled:
+                terms.append(pulled[n_step - 1][0][S])
+                coefs.append(1.0)
             if b[i] == 0.0 and not terms:
                 continue
             kbar = _combine(lam, dt * b[i], terms, coefs)
@@ -264,23 +415,12 @@ def _rk_backward(node, tape, duT, params, schedule, retain=False):
             grads = torch.autograd.grad(k, [U] + params, kbar, allow_unused=True, retain_graph=retain)
             if grads[0] is not None:
                 ubar[i] = grads[0].contiguous()
-            pairs_ag = []
-            for n, g in enumerate(grads[1:]):
-                if g is None:
-                    continue
-                if acc[n] is None:
-                    # own the accumulator in a layout _dense can view without a copy (an expanded / strided cotangent would make
-                    # _dense return a temporary, and the sum written into it would be lost)
-                    acc[n] = g if (g.is_contiguous() or (g.dim() == 2 and g.T.is_contiguous())) else g.contiguous()
-                elif acc[n].stride() == g.stride():
-                    # same layout for every stage's cotangent of one parameter: add in memory order
-                    pairs_ag.append((_dense(acc[n]), _dense(g)))
-                else:       # layouts differ (one transposed, one not): index-wise sum in the accumulator's own layout
-                    pairs_ag.append((_dense(acc[n]), _dense(g.contiguous() if acc[n].is_contiguous() else g.T.contiguous().T)))
-            _accumulate_many(pairs_ag)      # ONE launch for all parameters of this stage (sixteen arrays in the VMH tutorial's model)
+            absorb(grads[1:])
         live = [x for x in ubar if x is not None]
         if saving and start_slot[n_step] is not None:
             live.append(duT[start_slot[n_step]])              # lambda(t_n) also carries the cotangent of the state saved there
+        if n_step in pulled:
+            live.append(pulled.pop(n_step)[1])                # ... and that of u_n in the step's interpolated saves
         if live:
             lam = _combine(lam, 1.0, live, [1.0] * len(live))
     return lam, acc
@@ -418,25 +558,34 @@ class NeuralODE(AbstractExplicitLayer):
     abstol=1e-6 (scalars), dtmax=None (t_end - t0), maxiters=100_000 (attempts, rejected ones included); dt is the first step
     (None: Hairer-Norsett-Wanner's choice) and n_steps is ignored.  Every attempt forms the stages as the fixed step does, evaluates
     f(u_new) (the next step's first stage), gets EEst from one ngpde_rk_error_norm launch pair and reads it back (one synchronisation
-    per attempt); the library's controller (ngpde_rk_control_step, OrdinaryDiffEq's PI controller) accepts or rejects.  Steps land
-    on the save points of saveat exactly (no dense output).  It always runs the generic path (the device-resident plans are
+    per attempt); the library's controller (ngpde_rk_control_step, OrdinaryDiffEq's PI controller) accepts or rejects.  saveat has
+    two meanings here.  Landing (a scalar saveat, interpolate_saveat=None or False): the steps are cut to end on t0 + k saveat, which
+    must divide tspan.  Interpolating (interpolate_saveat=True, or a 1-D sequence of strictly increasing times in tspan, which always
+    interpolates), DiffEq's own: the steps are those of the same solve without saveat, and a save time inside an accepted step is
+    Tsit5's free 4th-order interpolant there (ngpde_rk_dense_output, no extra right-hand-side evaluation); a save time on a step's
+    end is that step's state.  A scalar gives t0 + k saveat below t_end and t_end (it need not divide tspan), a vector its own times
+    (t0 and t_end only when listed); save_start=False drops t0.  It always runs the generic path (the device-resident plans are
     fixed-step), and capture=True is refused: the step count depends on the data.  The pullback is the discrete adjoint of the
     accepted steps with their sizes held fixed -- rejected attempts contribute nothing and the controller is not differentiated; the
     reference's InterpolatingAdjoint is a continuous adjoint, so the gradients differ by O(tol).  NeuralODE.stats holds the last
     solve's naccept, nreject, nf, accepted step sizes (dts) and final t, as DiffEq's sol.stats (and every attempt's EEst, and the
-    starting step's three norms when it was chosen).
+    starting step's three norms when it was chosen; an interpolating solve adds its save_times and ninterp, the saves interpolated).
     """
 
     def __init__(self, model, *, solver="tsit5", tspan=(0.0, 1.0), n_steps=10, dt=None, capture=False, saveat=None, save_start=True,
-                 adaptive=False, reltol=1e-3, abstol=1e-6, dtmax=None, maxiters=100_000):
+                 adaptive=False, reltol=1e-3, abstol=1e-6, dtmax=None, maxiters=100_000, interpolate_saveat=None):
         solver = solver.lower()
         if solver not in TABLEAUS:
             raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, f"unknown solver {solver!r}; one of {list(TABLEAUS)}")
         self.model, self.solver, self.tspan, self.n_steps = model, solver, tuple(tspan), int(n_steps)
         self.adaptive, self.saveat, self.stats = bool(adaptive), None, None
+        self.save_times, self.interpolate_saveat = None, False     # (an interpolating adaptive solve's save times)
         if self.adaptive:
-            self._init_adaptive(dt, capture, saveat, save_start, reltol, abstol, dtmax, maxiters)
+            self._init_adaptive(dt, capture, saveat, save_start, reltol, abstol, dtmax, maxiters, interpolate_saveat)
             return
+        if interpolate_saveat is not None or _is_vector(saveat):
+            raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, "NeuralODE: a vector saveat and interpolate_saveat need adaptive=True "
+                                                                "(a fixed-step solve lands on its save points)")
         self.dt = float(dt) if dt is not None else (self.tspan[1] - self.tspan[0]) / self.n_steps
         # saveat (VMH.md:85 `NeuralODE(gnn, tspan, Tsit5(); saveat=dt_train)`): the output is the solution at t0, t0 + saveat, ..., T --
         # a (D x N x T) array -- instead of u(T).  The step is fixed, so saveat must be a whole number of steps.
@@ -453,7 +602,7 @@ class NeuralODE(AbstractExplicitLayer):
         self._captured = {}
         self._gat_ok = {}                 # (id(graph handle), heads) -> (handle, does the device-resident GAT solver take it?)
 
-    def _init_adaptive(self, dt, capture, saveat, save_start, reltol, abstol, dtmax, maxiters):
+    def _init_adaptive(self, dt, capture, saveat, save_start, reltol, abstol, dtmax, maxiters, interpolate_saveat):
         def bad(msg):
             return _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, f"NeuralODE(adaptive=True): {msg}")
         if self.solver != "tsit5":
@@ -474,8 +623,40 @@ class NeuralODE(AbstractExplicitLayer):
         self.dt = float(dt) if dt is not None else None
         self.dtmax = float(dtmax) if dtmax is not None else None
         self.maxiters = int(maxiters)
-        self.saveat, self.save_every, self.save_start = (float(saveat) if saveat is not None else None), 0, bool(save_start)
-        _Control(self)        # the library checks tspan and that saveat divides it (ArgumentError)
+        if interpolate_saveat is not None and not isinstance(interpolate_saveat, bool):
+            raise bad(f"interpolate_saveat must be None, True or False, got {interpolate_saveat!r}")
+        vector = _is_vector(saveat)
+        if vector:
+            if interpolate_saveat is False:
+                raise bad("a vector saveat is always interpolated (the steps cannot land on arbitrary times); interpolate_saveat=False "
+                          "takes a scalar saveat")
+            if getattr(saveat, "ndim", 1) != 1:
+                raise bad(f"saveat must be a scalar or a 1-D sequence of times, got {getattr(saveat, 'ndim', '?')} dimensions")
+            times = list(saveat.tolist() if hasattr(saveat, "tolist") else saveat)
+            if not all(isinstance(v, numbers.Real) and not isinstance(v, bool) for v in times):
+                raise bad(f"saveat must be a scalar or a 1-D sequence of times, got {saveat!r}")
+            times = [float(v) for v in times]
+            t0, t1 = float(self.tspan[0]), float(self.tspan[1])
+            if not times:
+                raise bad("saveat is an empty vector")
+            if not all(math.isfinite(v) and t0 <= v <= t1 for v in times):
+                raise bad(f"every saveat time must lie in tspan [{t0}, {t1}], got {times!r}")
+            if any(b_ <= a_ for a_, b_ in zip(times, times[1:])):
+                raise bad(f"saveat times must be strictly increasing, got {times!r}")
+            saveat = tuple(times)
+        elif interpolate_saveat:
+            if saveat is None:
+                raise bad("interpolate_saveat=True without saveat")
+            if isinstance(saveat, bool) or not isinstance(saveat, numbers.Real) or not math.isfinite(saveat) or saveat <= 0:
+                raise bad(f"saveat must be a finite spacing > 0, got {saveat!r}")
+            if (self.tspan[1] - self.tspan[0]) / float(saveat) > 1e7:
+                raise bad(f"saveat = {saveat} makes more than 1e7 save points")
+        self.saveat = saveat if vector else (float(saveat) if saveat is not None else None)
+        self.save_every, self.save_start = 0, bool(save_start)
+        self.interpolate_saveat = vector or bool(interpolate_saveat)
+        if self.interpolate_saveat:
+            self.save_times = dense_save_times(self.tspan, self.saveat, self.save_start)
+        _Control(self)        # the library checks tspan and, when the steps land on them, that saveat divides it (ArgumentError)
         self.capture = False
         self._plans, self._no_member_plan, self._captured, self._gat_ok = {}, False, {}, {}
 
