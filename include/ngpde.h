@@ -267,6 +267,47 @@ int32_t ngpde_segment_reduce_forward(const ngpde_graph_t *g, int32_t d, int32_t 
 int32_t ngpde_segment_reduce_backward(const ngpde_graph_t *g, int32_t d, int32_t aggr, const float *m, const float *out,
                                       const float *dout, float *dm, ngpde_stream_t stream);
 
+/* ---- the public message-passing API (src/NeuralGraphPDE.jl:5-11 re-exports propagate, apply_edges, aggregate_neighbors,
+ * softmax_edge_neighbors, copy_xj, copy_xi, xi_dot_xj, e_mul_xj, w_mul_xj; docs/src/devdoc.md:47-52 builds user layers on
+ * propagate(message, g, aggr; xi, xj, e)).  Atomic-free, bitwise reproducible, no workspace.  Checked before any device call, in
+ * this order: a negative width (NGPDE_ERR_DIMENSION_MISMATCH), an aggregation the entry does not take (NGPDE_ERR_INVALID_ARGUMENT),
+ * a NULL graph (NGPDE_ERR_INVALID_ARGUMENT). */
+
+/* The gather half of propagate (src/NeuralGraphPDE.jl:5-11, docs/src/devdoc.md:47-52): for the n <= 4 node arrays x[k] ([N][width[k]])
+ * xi[k][p] = x[k][t_p] and xj[k][p] = x[k][s_p], [E][width[k]] in p order, in ONE launch; xi / xj (the tables or their entries)
+ * nullable.  The pullback, one launch: dx[k][i] = sum over the incoming p of dxi[k][p] + sum over the outgoing p of dxj[k][p]
+ * (dxi / dxj nullable: that side contributes nothing). */
+int32_t ngpde_gather_forward(const ngpde_graph_t *g, int32_t n, const float *const *x, const int32_t *width, float *const *xi,
+                             float *const *xj, ngpde_stream_t stream);
+int32_t ngpde_gather_backward(const ngpde_graph_t *g, int32_t n, const int32_t *width, const float *const *dxi, const float *const *dxj,
+                              float *const *dx, ngpde_stream_t stream);
+
+/* propagate(e_mul_xj | w_mul_xj | copy_xj, g, + | mean; xj = x, e) fused (src/NeuralGraphPDE.jl:5-11, docs/src/devdoc.md:47-52; the
+ * weighted form of src/layers.jl:228-232): out[i] = aggr over the incoming e of e_e .* x[s_e], no [E][d] message array.  e: [E][e_width]
+ * in COO order with e_width 1 (a scalar per edge: w_mul_xj's edge weights) or d, or e_width 0 and e NULL (copy_xj).  aggr
+ * NGPDE_AGGR_SUM or NGPDE_AGGR_MEAN (an empty neighbourhood gives 0).  The pullback: dx [N][d] (nullable) summed over each source's
+ * outgoing edges; de [E][e_width] in COO order (nullable): the elementwise dout[t_e] .* x[s_e] for e_width d, the dot product
+ * <dout[t_e], x[s_e]> for e_width 1 (/ deg t_e under mean).  ngpde_propagate_copy_xj is unchanged. */
+int32_t ngpde_propagate_emul_forward(const ngpde_graph_t *g, int32_t d, int32_t e_width, int32_t aggr, const float *x, const float *e,
+                                     float *out, ngpde_stream_t stream);
+int32_t ngpde_propagate_emul_backward(const ngpde_graph_t *g, int32_t d, int32_t e_width, int32_t aggr, const float *x, const float *e,
+                                      const float *dout, float *dx, float *de, ngpde_stream_t stream);
+
+/* apply_edges(xi_dot_xj, g; xi, xj) (src/NeuralGraphPDE.jl:5-11, docs/src/devdoc.md:47-52): out[e] = <xi[t_e], xj[s_e]>, [E] in COO
+ * order; xi, xj [N][d] (may be different arrays).  The pullback: dxi[i] = sum over the incoming e of dout_e xj[s_e], dxj[j] = sum
+ * over the outgoing e of dout_e xi[t_e] (each nullable). */
+int32_t ngpde_apply_edges_dot_forward(const ngpde_graph_t *g, int32_t d, const float *xi, const float *xj, float *out,
+                                      ngpde_stream_t stream);
+int32_t ngpde_apply_edges_dot_backward(const ngpde_graph_t *g, int32_t d, const float *xi, const float *xj, const float *dout, float *dxi,
+                                       float *dxj, ngpde_stream_t stream);
+
+/* softmax_edge_neighbors(g, e) (src/NeuralGraphPDE.jl:5-11, docs/src/devdoc.md:47-52): per target, a softmax over its incoming edges
+ * with the row maximum subtracted; e, y [E][h] in COO order, any h >= 1.  The pullback de = y .* (dy - sum over the row of y .* dy).
+ * One launch each. */
+int32_t ngpde_softmax_edge_neighbors_forward(const ngpde_graph_t *g, int32_t h, const float *e, float *y, ngpde_stream_t stream);
+int32_t ngpde_softmax_edge_neighbors_backward(const ngpde_graph_t *g, int32_t h, const float *y, const float *dy, float *de,
+                                              ngpde_stream_t stream);
+
 /* GNOConv message (src/layers.jl:527-530): K_e = reshape(phi_out[:, e], cout, cin) column-major,
  * m_e = K_e * h[:, s_e].  k: [E][cin*cout] p order (element o + cout*i), h: [N][cin], m: [E][cout]. */
 int32_t ngpde_gno_contract_forward(const ngpde_graph_t *g, int32_t cin, int32_t cout, const float *k, const float *h,

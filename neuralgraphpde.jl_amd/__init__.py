@@ -12,6 +12,8 @@ from .layers import (AbstractExplicitLayer, AbstractGNNContainerLayer, AbstractG
                      GCNConv, apply, glorot_normal, glorot_uniform, setup, to_device, zeros32)
 from .node import NeuralODE
 from .layers_mp import ExplicitEdgeConv, GATConv, GNOConv, MPPDEConv, SpectralConv, VMHConv
+from .msgpass import (aggregate_neighbors, apply_edges, copy_xi, copy_xj, e_mul_xj, propagate, softmax_edge_neighbors, w_mul_xj,
+                      xi_dot_xj)
 from . import dist, optim, synth
 
 
@@ -26,4 +28,5 @@ __all__ = [
     "ExplicitEdgeConv", "VMHConv", "MPPDEConv", "GNOConv", "SpectralConv", "GATConv",
     "setup", "apply", "to_device", "updategraph", "wrapgraph", "drop", "GNNGraph", "EMPTYGRAPH", "rand_graph",
     "batch", "radius_graph", "knn_graph", "glorot_uniform", "glorot_normal", "zeros32", "NgpdeError", "DimensionMismatch", "ArgumentError",
+    "propagate", "apply_edges", "aggregate_neighbors", "softmax_edge_neighbors", "copy_xj", "copy_xi", "xi_dot_xj", "e_mul_xj", "w_mul_xj",
 ]

@@ -170,6 +170,14 @@ SIGNATURES = {
     "ngpde_edge_combine_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ngpde_segment_reduce_forward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "ngpde_segment_reduce_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_gather_forward": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_gather_backward": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_propagate_emul_forward": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ngpde_propagate_emul_backward": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_apply_edges_dot_forward": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "ngpde_apply_edges_dot_backward": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_softmax_edge_neighbors_forward": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+    "ngpde_softmax_edge_neighbors_backward": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_gno_contract_forward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_gno_contract_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_gno_apply_supported": (_i32, [_i32, _i32]),
