@@ -168,8 +168,10 @@ __device__ __forceinline__ void tile_ctx_from_lds(TileCtx &c, int tile, const fl
 // word on lane 63, ONE load per lane and round (a second dependent load per round would double the polling period, which is
 // the granularity a published flag is seen with); everybody meets at the barrier.  Returns false when the solve was aborted.
 // Bounded: after ~2 s of the 100 MHz counter (the whole solve takes ~6 ms) the wave raises the abort word itself.
-__device__ __forceinline__ bool tile_wait(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags) {
-  if (ph <= 1) return true;
+// (tile_wait_arrive: the wait without the look at its verdict -- *s_ok, valid behind the barrier -- for callers that read it later, see
+// tile_gather_foreign_checked)
+__device__ __forceinline__ void tile_wait_arrive(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags) {
+  if (ph <= 1) return;
   if (c.wave_u == 0) {
     const unsigned need = (unsigned)(ph - 1);
     const unsigned *addr = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? flags + 32 * c.my_nbr : nullptr);
@@ -190,6 +192,10 @@ __device__ __forceinline__ bool tile_wait(const TileMeta &m, const TileCtx &c, i
     if (c.lane == 0) *s_ok = ok ? 1 : 0;
   }
   __syncthreads();
+}
+__device__ __forceinline__ bool tile_wait(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags) {
+  if (ph <= 1) return true;
+  tile_wait_arrive(m, c, ph, s_ok, flags);
   return *s_ok != 0;
 }
 __device__ __forceinline__ bool tile_wait(const TileMeta &m, const TileCtx &c, int ph, int *s_ok) { return tile_wait(m, c, ph, s_ok, m.flags); }
@@ -200,7 +206,7 @@ __device__ __forceinline__ bool tile_wait(const TileMeta &m, const TileCtx &c, i
 // a flag store is seen by a poll from another XCD ~3-4 k cycles (1.2-1.5 us) after it was issued, a poll or a gather is a
 // ~1.5 k-cycle round trip, the drain in front of the flag ~1 k: with only two slots the ~2.4 us of hand-off exceed the ~1.7 us of
 // work the other slot offers in the forward kernel -- wherever the look is put, the difference is waited for.)
-__device__ __forceinline__ bool tile_wait_primed(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags, unsigned f) {
+__device__ __forceinline__ void tile_wait_primed_arrive(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags, unsigned f) {
   if (c.wave_u == 0) {
     const unsigned need = (unsigned)(ph - 1);
     const unsigned *addr = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? flags + 32 * c.my_nbr : nullptr);
@@ -221,6 +227,9 @@ __device__ __forceinline__ bool tile_wait_primed(const TileMeta &m, const TileCt
     if (c.lane == 0) *s_ok = ok ? 1 : 0;
   }
   __syncthreads();
+}
+__device__ __forceinline__ bool tile_wait_primed(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags, unsigned f) {
+  tile_wait_primed_arrive(m, c, ph, s_ok, flags, f);
   return *s_ok != 0;
 }
 
@@ -248,6 +257,30 @@ __device__ __forceinline__ void tile_gather_foreign(const TileCtx &c, const floa
   __syncthreads();
 }
 
+// The same gather with the byte offsets of the foreign rows formed by the caller BEFORE the wait (tile_gather_offsets): read behind the
+// wait, every halo index is an LDS round trip between "the flags were seen" and the DMA it addresses, paid by all waves in step.
+__device__ __forceinline__ void tile_gather_offsets(const TileCtx &c, unsigned (&off)[2]) {
+#pragma unroll
+  for (int k = 0; k < 2; ++k) off[k] = (unsigned)c.lds_hnode[c.grp + 32 * k] * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
+}
+// ... and with the wait's verdict (*s_ok, written in front of the wait's barrier) read under the DMAs instead of between the wait and the
+// gather, where it is one more LDS round trip in everybody's way.  A gather that an aborted solve issues reads valid rows and is drained
+// here before anybody leaves.  Returns false when the solve was aborted.
+__device__ __forceinline__ bool tile_gather_foreign_checked(const TileCtx &c, const float *X, float *ldsXh, const unsigned (&off)[2], const int *s_ok) {
+  float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    if (4 * c.wave_u + 32 * (k + 1) < c.hcount) {   // wave-uniform: a wave's four groups stage four consecutive slots
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(reinterpret_cast<const char *>(X) + off[k]),
+                                       (__attribute__((address_space(3))) void *)(Xh4 + (c.grp + 32 * (k + 1)) * PG::LPR + c.q), 16, 0, 16);
+    }
+  }
+  const int verdict = *s_ok;
+  wait_vmcnt0();
+  __syncthreads();
+  return verdict != 0;
+}
+
 // sum of the row's neighbours (slot bytes, in CSR order) + its own row (self loop), all from LDS
 // (plain adds on purpose: this file is built without SLP packing, and written as v_pk_add_f32 -- f4_add_pk -- these sums cost the
 // headline 2 %: they run beside the CU's other workgroup's MFMAs, where packed f32 VALU is slow; profiles/r05_x_ab_slp.txt)
@@ -258,6 +291,65 @@ __device__ __forceinline__ void tile_slot_words(const TileCtx &c, unsigned (&w)[
   w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
 }
 
+// the four rows a slot word names (one ds_read_b128 each)
+__device__ __forceinline__ void tile_round_rows(const float4 *Xh4, unsigned w, int q, float4 (&v)[4]) {
+#pragma unroll
+  for (int jb = 0; jb < 4; ++jb) v[jb] = Xh4[((w >> (8 * jb)) & 0xff) * PG::LPR + q];
+}
+// Rounds 0 .. n - 1 (n wave-uniform, 0 .. 8) of the slot words w added to a: a + ((v0 + v1) + (v2 + v3)) per round, rounds in order.
+// Software-pipelined: the four rows of round r + 1 are asked for BEFORE round r is summed, so a round costs the issue of its reads and
+// adds and not an LDS round trip of its own (one basic block per round behind a wave-uniform `if`, as this sum was written before,
+// exposes the full latency in every round of a wave).  The exit test sits in front of the prefetch, never between a round's prefetch
+// and the adds it covers; the last round is a peeled epilogue (adds only).  Worth <= 1 % of the headline: the tile's other waves already
+// covered most of that latency, the sums are bound by VALU issue (profiles/r07_a_pipelined_sums.txt).
+__device__ __forceinline__ float4 tile_aggregate_rounds(const TileCtx &c, const unsigned (&w)[8], const float *ldsXh, float4 a, int n) {
+  const float4 *Xh4 = reinterpret_cast<const float4 *>(ldsXh);
+  if (n <= 0) return a;   // wave-uniform
+  float4 v[4];
+  tile_round_rows(Xh4, w[0], c.q, v);
+#pragma unroll
+  for (int jw = 0; jw < 8; ++jw) {
+    if (jw == 7 || jw + 1 >= n) {   // wave-uniform
+      a = f4_add(a, f4_add(f4_add(v[0], v[1]), f4_add(v[2], v[3])));
+      break;
+    }
+    float4 nx[4];
+    tile_round_rows(Xh4, w[jw + 1], c.q, nx);
+    __builtin_amdgcn_sched_barrier(0);   // the reads first: left alone, the scheduler starts every other round with the adds that wait
+    a = f4_add(a, f4_add(f4_add(v[0], v[1]), f4_add(v[2], v[3])));
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) v[jb] = nx[jb];
+  }
+  return a;
+}
+// The same sum without the second buffer of rows, for the adjoint (16 more registers across its sums spill there): the two halves of
+// a round roll through their own registers -- rows 0, 1 of round r + 1 are asked for as soon as v0 + v1 of round r is formed, rows
+// 2, 3 as soon as v2 + v3 is -- so half a round's reads are always in flight under the other half's adds.  Same additions, same order.
+__device__ __forceinline__ float4 tile_aggregate_rounds_rolling(const TileCtx &c, const unsigned (&w)[8], const float *ldsXh, float4 a, int n) {
+  const float4 *Xh4 = reinterpret_cast<const float4 *>(ldsXh);
+  if (n <= 0) return a;   // wave-uniform
+  auto row = [&](unsigned wd, int jb) { return Xh4[((wd >> (8 * jb)) & 0xff) * PG::LPR + c.q]; };
+  float4 v0 = row(w[0], 0), v1 = row(w[0], 1), v2 = row(w[0], 2), v3 = row(w[0], 3);
+#pragma unroll
+  for (int jw = 0; jw < 8; ++jw) {
+    if (jw == 7 || jw + 1 >= n) {   // wave-uniform
+      a = f4_add(a, f4_add(f4_add(v0, v1), f4_add(v2, v3)));
+      break;
+    }
+    const float4 p = f4_add(v0, v1);
+    __builtin_amdgcn_sched_barrier(0);
+    v0 = row(w[jw + 1], 0); v1 = row(w[jw + 1], 1);
+    __builtin_amdgcn_sched_barrier(0);
+    const float4 s2 = f4_add(v2, v3);
+    __builtin_amdgcn_sched_barrier(0);
+    v2 = row(w[jw + 1], 2); v3 = row(w[jw + 1], 3);
+    __builtin_amdgcn_sched_barrier(0);
+    a = f4_add(a, f4_add(p, s2));
+  }
+  return a;
+}
+
+// (the two-slot kernels' form, one basic block per round: the tile-pair kernels have no 16 registers for a second buffer of rows)
 __device__ __forceinline__ float4 tile_aggregate(const TileCtx &c, const unsigned (&sw)[8], const float *ldsXh) {
   const float4 *Xh4 = reinterpret_cast<const float4 *>(ldsXh);
   float4 a = f4_zero();
@@ -312,20 +404,12 @@ __device__ __forceinline__ float4 tile_aggregate_weighted(const TileCtx &c, cons
 // foreign ones; TileMeta::of_pre names the own rounds per wave.  The one-tile forward kernels sum those rounds BEFORE they wait for their
 // neighbours' flags -- a tile's own rows are in LDS since its last epilogue -- and only the foreign rounds behind the gather.  Measured
 // with an in-kernel re-ordering of the same kind (profiles/r06_a_own_first.txt): forward launch 2.301 -> 2.234 ms.
-// rounds [r0, r1) of the row's slot words from LDS, same association as tile_aggregate
-__device__ __forceinline__ float4 tile_aggregate_rounds_range(const TileCtx &c, const unsigned (&sw)[8], const float *ldsXh, float4 a, int r0, int r1) {
-  const float4 *Xh4 = reinterpret_cast<const float4 *>(ldsXh);
+// The foreign rounds start at a wave-uniform round r0 = of_pre: their slot words are fetched a second time, shifted, so that the pipelined
+// sum (tile_aggregate_rounds) indexes its words from 0 with constants: w[k] = the row's word min(r0 + k, 7).  Fetched with the own
+// rounds' words BEFORE the wait; the own rounds' words are dead by then, so no more registers cross the wait than before.
+__device__ __forceinline__ void tile_slot_words_from(const TileCtx &c, int r0, unsigned (&w)[8]) {
 #pragma unroll
-  for (int jw = 0; jw < 8; ++jw) {
-    if (jw >= r0 && jw < r1) {   // wave-uniform
-      const unsigned w = sw[jw];
-      float4 v[4];
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) v[jb] = Xh4[((w >> (8 * jb)) & 0xff) * PG::LPR + c.q];
-      a = f4_add(a, f4_add(f4_add(v[0], v[1]), f4_add(v[2], v[3])));
-    }
-  }
-  return a;
+  for (int k = 0; k < 8; ++k) w[k] = c.lds_slots[c.grp * 8 + min(r0 + k, 7)];
 }
 // ---- hub geometry (graphs whose tiles do not fit the 96-row halo / 32-entry rows: BASELINE config 1's Cora-shaped graph) --------
 // One workgroup per CU and tile; per tile and direction (lists built by node_persistent_setup, not part of the graph handle):
@@ -674,15 +758,19 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
           NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           agg = hub_aggregate(c, sw, ldsXh, ldsZ);   // (the product's output tile is free until this phase's product)
         } else if constexpr (!WGT) {
-          unsigned sw[8];
+          unsigned sw[8], swf[8];
           tile_slot_words(c, sw);
-          float4 a = tile_aggregate_rounds_range(c, sw, ldsXh, f4_zero(), 0, of_pre);   // own rows: under the wait
-          if (!tile_wait(p.m, c, ph, s_ok)) { ok = false; break; }
+          tile_slot_words_from(c, of_pre, swf);
+          unsigned goff[2];
+          tile_gather_offsets(c, goff);
+          const float4 self = Xh4[c.grp * PG::LPR + c.q];   // (this thread's own store of the last epilogue)
+          float4 a = tile_aggregate_rounds(c, sw, ldsXh, f4_zero(), of_pre);   // own rows: under the wait
+          tile_wait_arrive(p.m, c, ph, s_ok, p.m.flags);
           NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
-          tile_gather_foreign(c, X, ldsXh);
+          if (!tile_gather_foreign_checked(c, X, ldsXh, goff, s_ok)) { ok = false; break; }
           NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
-          a = tile_aggregate_rounds_range(c, sw, ldsXh, a, of_pre, (c.wmax + 3) >> 2);
-          agg = f4_add(a, Xh4[c.grp * PG::LPR + c.q]);
+          a = tile_aggregate_rounds(c, swf, ldsXh, a, ((c.wmax + 3) >> 2) - of_pre);
+          agg = f4_add(a, self);
         } else {
           unsigned sw[8];
           tile_slot_words(c, sw);
@@ -695,7 +783,6 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
         float4 acc = f4_scale(c.ci, agg);   // a_i = c_i * sum of the stored (pre-scaled) rows
         *reinterpret_cast<float4 *>(&ldsT[c.grp * PG::TS + 4 * c.q]) = acc;
         const size_t ev = ev0 + (size_t)(n * p.S + i) * 2 + layer;
-        if (TAPE && c.valid) st4_stream_g(p.tape + ev * p.row_elems, own, acc);
         __syncthreads();
         NGPDE_PHASE_STAMP(p.m.stamps, ph, 3);
         if (WGT && layer == 0) mfma_rows_times_bfrag64(ldsT, bw1, ldsZ, c.wave_u, c.lane);
@@ -729,6 +816,9 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
         // after the rows are published
         if constexpr (TAPE && ACT == NGPDE_ACT_RELU) stu8_g(p.masks + ev * p.mask_bytes + (size_t)c.tile * kThreads, (unsigned)c.tid, sign_bits);
         else if (TAPE && c.valid) st4_stream_g(p.ztape + ev * p.row_elems, own, z);
+        // the tape row likewise: the aggregated row stays in ldsT until this thread overwrites it in the next phase, so its 64-bit address
+        // arithmetic, its issue and its share of the publish's drain are out of the chain between "flags seen" and "flag published"
+        if (TAPE && c.valid) st4_stream_g(p.tape + ev * p.row_elems, own, *reinterpret_cast<const float4 *>(&ldsT[c.grp * PG::TS + 4 * c.q]));
       }
     }
   }
@@ -1328,7 +1418,6 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
       dz = f4_sel(c.valid, f4_mul(kbar, f4_dact(p.act, mk)), f4_zero());
     }
     *reinterpret_cast<float4 *>(&ldsDZ[c.grp * PG::TS + 4 * c.q]) = dz;
-    *reinterpret_cast<float4 *>(&ldsX[c.grp * PG::TS + 4 * c.q]) = f4_sel(c.valid, xrow, f4_zero());
     __syncthreads();
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 3);
     if (WGT && ldsW == ldsW1) mfma_rows_times_bswz64(ldsDZ, ldsW, ldsG, c.wave_u, c.lane);   // (layer 1 of a weighted graph: the unpadded, swizzled W1)
@@ -1337,6 +1426,9 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 4);
     const float4 gv = f4_sel(c.valid, f4_scale(c.ci, *reinterpret_cast<const float4 *>(&ldsG[c.grp * PG::TS + 4 * c.q])), f4_zero());
     if (c.valid) store_sc1(gout, own, gv);
+    // the tape row for the parameter-gradient products, which run behind the publish: written under the drain of the row stores, in
+    // front of the publish's barrier (its readers of the phase before are two barriers back)
+    *reinterpret_cast<float4 *>(&ldsX[c.grp * PG::TS + 4 * c.q]) = f4_sel(c.valid, xrow, f4_zero());
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 5);
     tile_publish(p.m, c, ph);
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 6);
@@ -1422,13 +1514,24 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
           NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           t = tile_aggregate_weighted(c, ldsXh);
         } else {
-          unsigned sw[8];
+          unsigned sw[8], goff[2];
           tile_slot_words(c, sw);
-          if (!tile_wait_primed(p.m, c, ph, s_ok, p.m.flags, f_next)) { ok = false; break; }
-          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
-          tile_gather_foreign(c, p.g2, ldsXh);
+          if constexpr (RELU) tile_gather_offsets(c, goff);   // (with a row of pre-activations in flight as well, the two offsets spill)
+          if constexpr (RELU) {
+            tile_wait_primed_arrive(p.m, c, ph, s_ok, p.m.flags, f_next);
+            NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
+            if (!tile_gather_foreign_checked(c, p.g2, ldsXh, goff, s_ok)) { ok = false; break; }
+          } else {
+            if (!tile_wait_primed(p.m, c, ph, s_ok, p.m.flags, f_next)) { ok = false; break; }
+            NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
+            tile_gather_foreign(c, p.g2, ldsXh);
+          }
           NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
-          t = f4_add(tile_aggregate_rounds_range(c, sw, ldsXh, f4_zero(), 0, (c.wmax + 3) >> 2), Xh4[c.grp * PG::LPR + c.q]);
+          float4 self;
+          if constexpr (RELU) self = Xh4[c.grp * PG::LPR + c.q];   // asked for in front of the rounds: LDS reads return in order
+          t = tile_aggregate_rounds_rolling(c, sw, ldsXh, f4_zero(), (c.wmax + 3) >> 2);
+          if constexpr (!RELU) self = Xh4[c.grp * PG::LPR + c.q];
+          t = f4_add(t, self);
         }
         dense(ph, ldsW1, dw1, db1, t, mk, xrow, p.g1, !last_next, ev_next);
       }
@@ -1456,13 +1559,24 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
           NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
           t = tile_aggregate_weighted(c, ldsXh);
         } else {
-          unsigned sw[8];
+          unsigned sw[8], goff[2];
           tile_slot_words(c, sw);
-          if (!tile_wait_primed(p.m, c, ph, s_ok, p.m.flags, f_next)) { ok = false; break; }
-          NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
-          tile_gather_foreign(c, p.g1, ldsXh);
+          if constexpr (RELU) tile_gather_offsets(c, goff);   // (with a row of pre-activations in flight as well, the two offsets spill)
+          if constexpr (RELU) {
+            tile_wait_primed_arrive(p.m, c, ph, s_ok, p.m.flags, f_next);
+            NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
+            if (!tile_gather_foreign_checked(c, p.g1, ldsXh, goff, s_ok)) { ok = false; break; }
+          } else {
+            if (!tile_wait_primed(p.m, c, ph, s_ok, p.m.flags, f_next)) { ok = false; break; }
+            NGPDE_PHASE_STAMP(p.m.stamps, ph, 1);
+            tile_gather_foreign(c, p.g1, ldsXh);
+          }
           NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
-          t = f4_add(tile_aggregate_rounds_range(c, sw, ldsXh, f4_zero(), 0, (c.wmax + 3) >> 2), Xh4[c.grp * PG::LPR + c.q]);
+          float4 self;
+          if constexpr (RELU) self = Xh4[c.grp * PG::LPR + c.q];   // asked for in front of the rounds: LDS reads return in order
+          t = tile_aggregate_rounds_rolling(c, sw, ldsXh, f4_zero(), (c.wmax + 3) >> 2);
+          if constexpr (!RELU) self = Xh4[c.grp * PG::LPR + c.q];
+          t = f4_add(t, self);
         }
         float4 kbar;
         if (i >= 1) {
