@@ -308,6 +308,56 @@ int32_t ngpde_softmax_edge_neighbors_forward(const ngpde_graph_t *g, int32_t h, 
 int32_t ngpde_softmax_edge_neighbors_backward(const ngpde_graph_t *g, int32_t h, const float *y, const float *dy, float *de,
                                               ngpde_stream_t stream);
 
+/* ---- the per-graph readouts (src/NeuralGraphPDE.jl:5-7 re-exports reduce_nodes, reduce_edges, softmax_nodes, softmax_edges,
+ * broadcast_nodes, broadcast_edges): one row per graph of a block-diagonal batch out of its nodes' or edges' rows, and back.
+ * A readout is 1 to a few hundred segments of 10^3 to 10^5 rows each -- the opposite shape of a neighbourhood -- so it has kernels
+ * of its own: a PLAN cuts every segment into chunks of at most chunk_rows rows, one workgroup reduces a chunk, and one wave per
+ * segment folds the chunks' partial rows in chunk order.  Atomic-free; the chunking is the plan's alone, so every result is bitwise
+ * equal from run to run.  Nothing is allocated after create: the caller provides the workspace, and every entry can be captured
+ * into a HIP graph.  Checked before any device call, in this order: a negative width (NGPDE_ERR_DIMENSION_MISMATCH), an aggregation
+ * other than NGPDE_AGGR_SUM / MEAN / MAX / MIN (NGPDE_ERR_INVALID_ARGUMENT), a NULL plan (NGPDE_ERR_INVALID_ARGUMENT), a workspace
+ * smaller than ngpde_readout_workspace_bytes (NGPDE_ERR_WORKSPACE). */
+typedef struct ngpde_readout ngpde_readout_t;
+
+/* The plan depends on the map from items to segments alone: segment of item i = id[index ? index[i] : i] - id_base; id NULL: one
+ * segment.  id, index: device int32; index entries address id.  Nodes: (N, indicator, NULL); edges: (E, indicator, the sources in COO
+ * order).  n_items <= 2^31 - 1, n_segments >= 1 (n_segments > 1 needs id: both refused without touching the device); an id outside
+ * id_base : id_base + n_segments - 1 is NGPDE_ERR_INVALID_ARGUMENT.  Non-decreasing ids (every batch) make the plan `contiguous`:
+ * rows are addressed directly; otherwise through a stable permutation of the items by segment.  Synchronises the stream.
+ * PRECONDITION, NOT CHECKED: every index[i] lies inside id.  The entry is not told id's length, so an index entry outside it is an
+ * out-of-bounds device read, not an error status; pass the sources of a graph whose edges were validated (ngpde_graph_create). */
+int32_t ngpde_readout_create(int64_t n_items, const int32_t *id, const int32_t *index, int32_t id_base, int32_t n_segments,
+                             ngpde_stream_t stream, ngpde_readout_t **out);
+int32_t ngpde_readout_destroy(ngpde_readout_t *r);
+/* every output nullable */
+int32_t ngpde_readout_info(const ngpde_readout_t *r, int64_t *n_items, int32_t *n_segments, int32_t *contiguous, int64_t *n_chunks,
+                           int32_t *chunk_rows);
+/* bytes that cover every entry below at width d (0 for a NULL plan or d <= 0) */
+size_t ngpde_readout_workspace_bytes(const ngpde_readout_t *r, int32_t d);
+
+/* reduce_nodes / reduce_edges(aggr, g, x): out[s] = aggr over the items of segment s of x[i]; x [n][d], out [S][d].  An empty
+ * segment gives 0 for sum and mean, -inf / +inf for max / min (the conventions of ngpde_segment_reduce_forward).  One launch when
+ * every segment is a single chunk, two otherwise.  The pullback (one launch, no workspace): dx[i] = dout[s_i], / count for mean, and
+ * where x[i] == out[s_i] for max / min (every tied entry, as NNlib's); x and out are read for max / min only. */
+int32_t ngpde_readout_reduce_forward(const ngpde_readout_t *r, int32_t d, int32_t aggr, const float *x, float *out, void *workspace,
+                                     size_t workspace_bytes, ngpde_stream_t stream);
+int32_t ngpde_readout_reduce_backward(const ngpde_readout_t *r, int32_t d, int32_t aggr, const float *x, const float *out,
+                                      const float *dout, float *dx, ngpde_stream_t stream);
+
+/* softmax_nodes / softmax_edges(g, x): per segment and column, the softmax over the segment's items with the maximum subtracted;
+ * x, y [n][d].  The maximum and the sum of exponentials are found in ONE pass over x (two launches when every segment is a single
+ * chunk, three otherwise).  The pullback dx = y .* (dy - sum over the segment of y .* dy), the same launch counts. */
+int32_t ngpde_readout_softmax_forward(const ngpde_readout_t *r, int32_t d, const float *x, float *y, void *workspace,
+                                      size_t workspace_bytes, ngpde_stream_t stream);
+int32_t ngpde_readout_softmax_backward(const ngpde_readout_t *r, int32_t d, const float *y, const float *dy, float *dx, void *workspace,
+                                       size_t workspace_bytes, ngpde_stream_t stream);
+
+/* broadcast_nodes / broadcast_edges(g, u): out[i] = u[s_i]; u [S][d], out [n][d].  The pullback du[s] = the sum of dout over the
+ * segment (the reduce with NGPDE_AGGR_SUM). */
+int32_t ngpde_readout_broadcast_forward(const ngpde_readout_t *r, int32_t d, const float *u, float *out, ngpde_stream_t stream);
+int32_t ngpde_readout_broadcast_backward(const ngpde_readout_t *r, int32_t d, const float *dout, float *du, void *workspace,
+                                         size_t workspace_bytes, ngpde_stream_t stream);
+
 /* GNOConv message (src/layers.jl:527-530): K_e = reshape(phi_out[:, e], cout, cin) column-major,
  * m_e = K_e * h[:, s_e].  k: [E][cin*cout] p order (element o + cout*i), h: [N][cin], m: [E][cout]. */
 int32_t ngpde_gno_contract_forward(const ngpde_graph_t *g, int32_t cin, int32_t cout, const float *k, const float *h,

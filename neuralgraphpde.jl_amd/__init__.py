@@ -14,6 +14,7 @@ from .node import NeuralODE
 from .layers_mp import ExplicitEdgeConv, GATConv, GNOConv, MPPDEConv, SpectralConv, VMHConv
 from .msgpass import (aggregate_neighbors, apply_edges, copy_xi, copy_xj, e_mul_xj, propagate, softmax_edge_neighbors, w_mul_xj,
                       xi_dot_xj)
+from .readout import (broadcast_edges, broadcast_nodes, graph_indicator, reduce_edges, reduce_nodes, softmax_edges, softmax_nodes)
 from . import dist, optim, synth
 
 
@@ -29,4 +30,5 @@ __all__ = [
     "setup", "apply", "to_device", "updategraph", "wrapgraph", "drop", "GNNGraph", "EMPTYGRAPH", "rand_graph",
     "batch", "radius_graph", "knn_graph", "glorot_uniform", "glorot_normal", "zeros32", "NgpdeError", "DimensionMismatch", "ArgumentError",
     "propagate", "apply_edges", "aggregate_neighbors", "softmax_edge_neighbors", "copy_xj", "copy_xi", "xi_dot_xj", "e_mul_xj", "w_mul_xj",
+    "reduce_nodes", "reduce_edges", "softmax_nodes", "softmax_edges", "broadcast_nodes", "broadcast_edges", "graph_indicator",
 ]

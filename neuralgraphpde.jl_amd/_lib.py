@@ -178,6 +178,16 @@ SIGNATURES = {
     "ngpde_apply_edges_dot_backward": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ngpde_softmax_edge_neighbors_forward": (_i32, [_vp, _i32, _vp, _vp, _vp]),
     "ngpde_softmax_edge_neighbors_backward": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "ngpde_readout_create": (_i32, [_i64, _vp, _vp, _i32, _i32, _vp, C.POINTER(_vp)]),
+    "ngpde_readout_destroy": (_i32, [_vp]),
+    "ngpde_readout_info": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32)]),
+    "ngpde_readout_workspace_bytes": (_sz, [_vp, _i32]),
+    "ngpde_readout_reduce_forward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ngpde_readout_reduce_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_readout_softmax_forward": (_i32, [_vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ngpde_readout_softmax_backward": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ngpde_readout_broadcast_forward": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+    "ngpde_readout_broadcast_backward": (_i32, [_vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_gno_contract_forward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_gno_contract_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_gno_apply_supported": (_i32, [_i32, _i32]),
@@ -345,6 +355,6 @@ def flush_destroy():
 
 
 def destroy_later(fn, ptr):
-    """fn: "ngpde_graph_destroy" | "ngpde_node_destroy" | "ngpde_ode_destroy"; ptr: the handle"""
+    """fn: "ngpde_graph_destroy" | "ngpde_node_destroy" | "ngpde_ode_destroy" | "ngpde_readout_destroy"; ptr: the handle"""
     _pending_destroy.append((fn, ptr))
     flush_destroy()

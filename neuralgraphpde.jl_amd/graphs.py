@@ -128,15 +128,20 @@ class GNNGraph:
 
     GNNGraph(s, t; num_nodes, ndata, edata, gdata)        -- as test/runtests.jl:11-13
     GNNGraph(g; ndata=..., edata=..., gdata=...)          -- copy with data replaced (:28, :58, :145)
+
+    `graph_indicator` (keyword, in `index_base` like s and t; also what batch / radius_graph / knn_graph record): the graph each node
+    belongs to.  Kept as the attribute `graph_indicator`, an int32 array of length N, 0-based, or None for a single graph; the
+    per-graph readouts (readout.py) read it.
     """
 
     def __init__(self, s=None, t=None, *, num_nodes=None, ndata=None, edata=None, gdata=None,
-                 num_graphs=None, edge_weight=None, index_base=1):
+                 num_graphs=None, edge_weight=None, index_base=1, graph_indicator=None):
         if isinstance(s, GNNGraph):
             g = s
             self._s0, self._t0 = g._s0, g._t0
             self.num_nodes, self.num_edges = g.num_nodes, g.num_edges
             self.num_graphs = g.num_graphs if num_graphs is None else num_graphs
+            self.graph_indicator = g.graph_indicator
             self.edge_weight = g.edge_weight if edge_weight is None else edge_weight
             self._handles = g._handles          # same structure -> share the native handles
             self._shared = g._shared            # ... the device copy of the COO list and the locality order
@@ -158,7 +163,19 @@ class GNNGraph:
                                          f"DimensionMismatch: edge index outside 1:{num_nodes}")
         self._s0, self._t0 = s0, t0
         self.num_nodes, self.num_edges = int(num_nodes), int(s0.size)
+        gi0 = None
+        if graph_indicator is not None:
+            gi0 = _to_numpy(graph_indicator).reshape(-1).astype(np.int64) - index_base
+            if gi0.size != self.num_nodes:
+                raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
+                                             f"DimensionMismatch: graph_indicator has {gi0.size} entries for {self.num_nodes} nodes")
+            if num_graphs is None:
+                num_graphs = int(gi0.max(initial=0)) + 1
+            if gi0.size and (gi0.min() < 0 or gi0.max() >= int(num_graphs)):
+                raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT,
+                                         f"graph_indicator holds an id outside {index_base}:{index_base + int(num_graphs) - 1}")
         self.num_graphs = 1 if num_graphs is None else int(num_graphs)
+        self.graph_indicator = gi0.astype(np.int32) if (gi0 is not None and self.num_graphs > 1) else None
         self.edge_weight = edge_weight
         self.ndata = _normalize(ndata, "x", self.num_nodes, "node")
         self.edata = _normalize(edata, "e", self.num_edges, "edge")
@@ -323,7 +340,8 @@ def _device_indicator(graph_indicator, n, dev):
 
 
 def _graph_from_device_coo(s, t, n, num_graphs, dev, pts, gi, locality):
-    g = GNNGraph(s.cpu().numpy(), t.cpu().numpy(), num_nodes=n, index_base=0, num_graphs=num_graphs)
+    g = GNNGraph(s.cpu().numpy(), t.cpu().numpy(), num_nodes=n, index_base=0, num_graphs=num_graphs,
+                 graph_indicator=None if gi is None else gi.cpu().numpy() - 1)
     g._shared[("coo", str(dev))] = (s, t)            # the handle builder takes the device lists as they are
     if locality == "spatial" and n:
         order = torch.empty(n, dtype=torch.int32, device=dev)
@@ -397,8 +415,20 @@ def batch(graphs):
             out[k] = torch.cat(parts, dim=-1)
         return out
 
+    # the members' indicators, each offset by the number of graphs before it (a member may itself be a batch)
+    gis, goff = [], 0
+    for g in graphs:
+        if g.num_graphs == 1:
+            gis.append(np.full(g.num_nodes, goff, dtype=np.int32))
+        elif g.graph_indicator is not None:
+            gis.append(g.graph_indicator + np.int32(goff))
+        else:
+            gis = None       # a member of several graphs that does not know its nodes' graphs: neither does the batch
+            break
+        goff += g.num_graphs
     out = GNNGraph(np.concatenate(ss) if ss else [], np.concatenate(tt) if tt else [], num_nodes=off,
-                   index_base=0, num_graphs=sum(g.num_graphs for g in graphs))
+                   index_base=0, num_graphs=sum(g.num_graphs for g in graphs),
+                   graph_indicator=np.concatenate(gis) if gis else None)
     out.ndata = cat([g.ndata for g in graphs], lambda g: g.num_nodes)
     out.edata = cat([g.edata for g in graphs], lambda g: g.num_edges)
     out.gdata = cat([g.gdata for g in graphs], lambda g: g.num_graphs, gdata=True)
