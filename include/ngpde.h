@@ -358,6 +358,80 @@ int32_t ngpde_readout_broadcast_forward(const ngpde_readout_t *r, int32_t d, con
 int32_t ngpde_readout_broadcast_backward(const ngpde_readout_t *r, int32_t d, const float *dout, float *du, void *workspace,
                                          size_t workspace_bytes, ngpde_stream_t stream);
 
+/* ---- graph queries and transforms on a device COO list (src/NeuralGraphPDE.jl:4 re-exports GNNGraphs: degree, has_self_loops,
+ * has_multi_edges, is_bidirected, add_self_loops, remove_self_loops, remove_multi_edges, to_bidirected, getgraph, unbatch): what a
+ * user does to a graph between making it (ngpde_radius_graph / ngpde_knn_graph write such lists) and ngpde_graph_create_device.
+ *   s, t         device int32[n_edges] with `index_base` added, as the neighbour search writes them; outputs carry the same base
+ *   n_nodes      <= 2^31 - 1; n_edges (2 * n_edges when symmetrising) <= 2^31 - 1, refused beyond (NGPDE_ERR_INVALID_ARGUMENT)
+ * Checked before any device call: NULL and negative arguments (NGPDE_ERR_INVALID_ARGUMENT).  An edge end outside the node range is
+ * NGPDE_ERR_DIMENSION_MISMATCH from the entries that index by node or build a sort key; no kernel reads or writes through such an end.
+ * MEMORY: temporary storage (sort buffers, flags, scans: a few arrays of n_edges or n_nodes words) is allocated with hipMalloc inside
+ * the call and freed before it returns, as ngpde_graph_create_device does; these entries are therefore not capturable into a HIP graph.
+ * The group reduce below allocates nothing and is.
+ * SYNCHRONISATION: ngpde_coo_flags, ngpde_coo_compact and ngpde_coo_coalesce return a data-dependent count or flags through HOST
+ * pointers and synchronise `stream` before they return, as ngpde_radius_graph does; their device outputs are sized by the caller to
+ * the upper bound given with each.  Nothing here uses float atomics: every result is bitwise equal from run to run. */
+enum { NGPDE_DIR_OUT = 0, NGPDE_DIR_IN = 1, NGPDE_DIR_BOTH = 2 };
+
+/* degree(g, dir; edge_weight): exactly one of out_counts / out_sums is given (the other NULL) and selects the form.  out_counts
+ * int32[n_nodes] = the number of edges leaving (OUT) / entering (IN) a node, BOTH = the sum of the two; w is not read.  out_sums
+ * float[n_nodes] = the sum of w (device float[n_edges], required unless n_edges == 0) over those edges, added in COO order from 0.0f
+ * (a stable sort of the COO positions by node, then one thread per node: the order of norm_kernel in graph_device.hip); BOTH = the OUT
+ * sum + the IN sum. */
+int32_t ngpde_coo_degree(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t dir,
+                         const float *w, int32_t *out_counts, float *out_sums, ngpde_stream_t stream);
+
+/* The three predicates from one call (host outputs, each nullable): has_self_loops = some s == t; has_multi_edges = some (s, t) pair
+ * occurs twice; is_bidirected = for every pair the multiplicity of (s, t) equals that of (t, s) (the sorted 64-bit keys s*n + t and
+ * t*n + s are the same sequence).  Synchronises. */
+int32_t ngpde_coo_flags(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t *has_self_loops,
+                        int32_t *has_multi_edges, int32_t *is_bidirected, ngpde_stream_t stream);
+
+/* Stable compaction.  An edge is kept iff (drop_self_loops == 0 or s != t) and, with `nodes`, both ends are listed.
+ *   nodes        device int64[n_keep], 0-based, or NULL: the induced subgraph -- node nodes[k] becomes node k, every other node is
+ *                dropped (a relabel table, -1 = dropped, is built in front of the compaction).  An entry outside 0 : n_nodes - 1 or a
+ *                repeated one is NGPDE_ERR_INVALID_ARGUMENT, detected on the device and read back with the count.
+ *   s_out, t_out device int32[n_edges] (upper bound): the kept edges in COO order, renumbered under `nodes`
+ *   kept         device int64[n_edges] (upper bound): the COO position (0-based) of every kept edge, ascending -- the index list
+ *                ngpde_rows_index takes to move the edge features
+ *   n_out        host: the number of kept edges.  Synchronises. */
+int32_t ngpde_coo_compact(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int64_t n_keep,
+                          const int64_t *nodes, int32_t drop_self_loops, int32_t *s_out, int32_t *t_out, int64_t *kept, int64_t *n_out,
+                          ngpde_stream_t stream);
+
+/* Coalesce: one edge per distinct (s, t), ORDERED BY SOURCE, THEN TARGET.  M = n_edges copies, or with symmetrize != 0 the M = 2 * n_edges
+ * copies of [s; t], [t; s] (copy e < n_edges is edge e, copy e >= n_edges is edge e - n_edges reversed; the 2E list is never written).
+ * The copies are sorted stably by the 64-BIT key s*n_nodes + t (rocPRIM radix sort; a 32-bit key overflows from n = 65 536 on); a copy
+ * whose key differs from its predecessor's heads a group.  Outputs, all device int32, sized by the caller to M (group_ptr: M + 1):
+ *   s_out, t_out   [n_out]      the distinct pairs
+ *   group_ptr      [n_out + 1]  group g holds the sorted copies group_ptr[g] .. group_ptr[g + 1] - 1
+ *   member         [M]          the source-edge ROW of every sorted copy (copy e >= n_edges names row e - n_edges), ascending by copy
+ *                               -- hence by COO position -- inside a group
+ *   group_of       [M]          the inverse: the group that copy e fell into (what the pullback of the group reduce reads)
+ *   n_out          host: the number of groups.  Synchronises. */
+int32_t ngpde_coo_coalesce(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t symmetrize,
+                           int32_t *s_out, int32_t *t_out, int32_t *group_ptr, int32_t *member, int32_t *group_of, int64_t *n_out,
+                           ngpde_stream_t stream);
+
+/* The features of coalesced edges: out[g][:] = aggr over the members of group g of src[member][:], rows of d floats, src [n_rows][d],
+ * out [n_groups][d]; aggr NGPDE_AGGR_SUM (a plain float sum in member order from the first member), MEAN (that sum divided by the
+ * member count), MAX / MIN (exact).  One launch, a lane per (group, 4 columns) with float4 rows where d % 4 == 0 and the arrays are
+ * 16-byte aligned, a lane per (group, column) otherwise; a group of any length is walked by its lane.
+ * Pullback, one launch, atomic-free: source row r occurs in exactly `copies` groups (1, or 2 after symmetrize: group_of[r] and
+ * group_of[r + n_rows]); dsrc[r] = the sum in copy order of dout[g] (SUM), dout[g] / count(g) (MEAN), dout[g] where src[r] == out[g]
+ * else 0 (MAX / MIN: every extremal member, as ngpde_segment_reduce_backward); src and out are read for MAX / MIN only.
+ * PRECONDITION, NOT CHECKED: group_ptr, member and group_of are those ngpde_coo_coalesce wrote for n_rows edges. */
+int32_t ngpde_group_reduce_forward(int64_t n_groups, int64_t n_rows, int32_t d, int32_t aggr, const int32_t *group_ptr,
+                                   const int32_t *member, const float *src, float *out, ngpde_stream_t stream);
+int32_t ngpde_group_reduce_backward(int64_t n_groups, int64_t n_rows, int32_t copies, int32_t d, int32_t aggr, const int32_t *group_ptr,
+                                    const int32_t *group_of, const float *src, const float *out, const float *dout, float *dsrc,
+                                    ngpde_stream_t stream);
+
+/* add_self_loops: s_out, t_out int32[n_edges + n_nodes] = the old edges in order, then (i, i) for i = 0 .. n_nodes - 1; w_out (nullable,
+ * with w) float[n_edges + n_nodes] = w, then n_nodes ones.  Concatenation and iota in one launch; existing loops are not looked for. */
+int32_t ngpde_coo_add_self_loops(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, const float *w,
+                                 int32_t *s_out, int32_t *t_out, float *w_out, ngpde_stream_t stream);
+
 /* GNOConv message (src/layers.jl:527-530): K_e = reshape(phi_out[:, e], cout, cin) column-major,
  * m_e = K_e * h[:, s_e].  k: [E][cin*cout] p order (element o + cout*i), h: [N][cin], m: [E][cout]. */
 int32_t ngpde_gno_contract_forward(const ngpde_graph_t *g, int32_t cin, int32_t cout, const float *k, const float *h,

@@ -188,6 +188,13 @@ SIGNATURES = {
     "ngpde_readout_softmax_backward": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_readout_broadcast_forward": (_i32, [_vp, _i32, _vp, _vp, _vp]),
     "ngpde_readout_broadcast_backward": (_i32, [_vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ngpde_coo_degree": (_i32, [_i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ngpde_coo_flags": (_i32, [_i64, _i64, _vp, _vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp]),
+    "ngpde_coo_compact": (_i32, [_i64, _i64, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_coo_coalesce": (_i32, [_i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_group_reduce_forward": (_i32, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_group_reduce_backward": (_i32, [_i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_coo_add_self_loops": (_i32, [_i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ngpde_gno_contract_forward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_gno_contract_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_gno_apply_supported": (_i32, [_i32, _i32]),
