@@ -93,6 +93,7 @@ int32_t ngpde_ode_create(const ngpde_graph_t *g, const ngpde_ode_desc_t *d, ngpd
       st = ngpde_node_vmh_create(g, hd, d->pos_width, d->pos, d->n_phi, d->phi_dims, d->phi_acts, d->n_gamma, d->gamma_dims, d->gamma_acts, d->aggr, d->tableau,
                                  d->n_steps, d->dt, d->with_backward, &o->vmh);
       fl = NGPDE_NODE_PERSISTENT_FWD | (d->with_backward ? NGPDE_NODE_PERSISTENT_BWD : 0);
+      if (st == NGPDE_OK && node_vmh_plan_tile_rounds(o->vmh)) fl |= NGPDE_NODE_TILE_ROUNDS;
       break;
     }
     default: st = fail(NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_create: unknown right-hand side %d", d->rhs);

@@ -104,6 +104,7 @@ struct ngpde_graph {
   // derived on first use, under lazy_mu (the handle stays shareable between host threads)
   mutable std::mutex lazy_mu;
   mutable int sched_same = -1;   // do the by-target and by-source schedules name the same node at every position? (-1: not asked yet; gat_fused.hip)
+  mutable int wait_lists_fit = -1;   // does every tile neighbour at most 63 tiles? (-1: not asked yet; node_wait_lists_fit)
   mutable ngpde::HaloInverse halo_inv;
 };
 
@@ -270,6 +271,9 @@ int node_persistent_mode(const ngpde_graph *g, int d, int act, bool with_bwd);  
 bool node_persistent_hub_possible(const ngpde_graph *g, int d);
 int node_persistent_rounds(const ngpde_graph *g);                               // mode 3: tiles per workgroup
 int32_t node_persistent_setup(const ngpde_graph *g, const float *coef_host /* [90] */, NodePersist *ps, bool pair = false, bool hub = false);
+// does node_persistent_setup(g, ..., hub = false) find room for every tile's wait list?  What a plan's `supported` query must say
+// before its `create` runs into the bound.  Asked of the device once per handle (blocking copies of the halo lists).
+bool node_wait_lists_fit(const ngpde_graph *g);
 void node_persistent_free(NodePersist *ps);
 int32_t launch_node_fwd_persistent(const NodePersistFwd &a, hipStream_t stream);
 int32_t launch_node_bwd_persistent(const NodePersistBwd &a, hipStream_t stream);
@@ -355,6 +359,8 @@ struct VmhLaunch {
   int save_every = 0, save_off = 0;
 };
 bool node_vmh_supported(const ngpde_graph *g, const VmhShape &s);
+bool node_vmh_tile_rounds(const ngpde_graph *g, const VmhShape &s);   // a supported shape: does the plan run in tile rounds?
+bool node_vmh_plan_tile_rounds(const ngpde_node_vmh_t *plan);          // ... of a plan (node.hip)
 int32_t launch_node_vmh_fwd(const VmhLaunch &a, hipStream_t stream);
 int32_t launch_node_vmh_bwd(const VmhLaunch &a, hipStream_t stream);
 int32_t launch_vmh_copy_block(const float *src, int sp, float *dst, int dp, int rows, int cols, hipStream_t stream);

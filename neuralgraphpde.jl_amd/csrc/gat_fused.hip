@@ -1443,6 +1443,7 @@ bool gat_node_persistent_supported(const ngpde_graph *g, int heads, int c) {
   }
   const int nt = g->n_sched / kTileRows;
   if (nt < 1 || nt > cus * occ) return false;
+  if (!node_wait_lists_fit(g)) return false;   // (node_persistent_setup refuses a tile that neighbours more than 63 others)
   // both directions' schedules must name the same node at every position (the solver keeps per-thread state across the halves):
   // compared on the device ONCE per handle (a launch on the NULL stream and a blocking copy -- not something to repeat per solve)
   std::lock_guard<std::mutex> lock(g->lazy_mu);

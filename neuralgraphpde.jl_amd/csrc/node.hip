@@ -1211,6 +1211,8 @@ static void node_vmh_free(ngpde_node_vmh *p) {
   delete p;
 }
 
+bool ngpde::node_vmh_plan_tile_rounds(const ngpde_node_vmh_t *p) { return p && node_vmh_tile_rounds(p->g, p->shape); }
+
 static int32_t vmh_shape(int32_t hd, int32_t pd, int32_t n_phi, const int32_t *phi_dims, const int32_t *phi_acts, int32_t n_gamma,
                          const int32_t *gamma_dims, const int32_t *gamma_acts, int32_t aggr, VmhShape *s) {
   NGPDE_REQUIRE(phi_dims && phi_acts && gamma_dims && gamma_acts, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_node_vmh: NULL layer table");
@@ -1247,7 +1249,7 @@ int32_t ngpde_node_vmh_create(const ngpde_graph_t *g, int32_t hd, int32_t pd, co
   NGPDE_REQUIRE(node_vmh_supported(g, shape), NGPDE_ERR_UNSUPPORTED,
                 "ngpde_node_vmh_create: needs a scalar state, 1-3 position coordinates, MLPs of 2-4 Dense layers up to 64 wide with identity / relu / "
                 "tanh / sigmoid hidden and identity output layers, + or mean aggregation, tiles that fit the LDS halo in both directions and "
-                "at most one 16-row half tile per CU (use the generic solver otherwise)");
+                "neighbour at most 63 other tiles each, and at most 64 tiles per resident workgroup (use the generic solver otherwise)");
   ngpde_node_vmh *p = new (std::nothrow) ngpde_node_vmh();
   NGPDE_REQUIRE(p != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_node_vmh_create: out of host memory");
   p->g = g; p->shape = shape; p->n_steps = n_steps; p->with_bwd = with_backward != 0;

@@ -2481,6 +2481,16 @@ static bool build_wait_lists(const ngpde_graph *g, std::vector<int> &out) {
   return true;
 }
 
+bool node_wait_lists_fit(const ngpde_graph *g) {
+  if (!g) return false;
+  std::lock_guard<std::mutex> lock(g->lazy_mu);
+  if (g->wait_lists_fit < 0) {
+    std::vector<int> lists;
+    g->wait_lists_fit = build_wait_lists(g, lists) ? 1 : 0;
+  }
+  return g->wait_lists_fit == 1;
+}
+
 // Can the plan run as two persistent launches?  (same conditions as the pre-scaled replayed plan, plus: d = 64, unweighted, ALL
 // workgroups co-resident.)  0: no.  1: one tile per workgroup (graphs of at most CUs x occupancy tiles).  2: two tiles per
 // workgroup through the two-slot kernels (up to twice as many tiles; relu when a backward is asked for).

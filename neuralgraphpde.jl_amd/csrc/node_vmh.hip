@@ -1213,7 +1213,12 @@ bool node_vmh_supported(const ngpde_graph *g, const VmhShape &s) {
     if (!act_ok(s.gam_act[l])) return false;
   if (s.phi_act[s.n_phi - 1] != NGPDE_ACT_IDENTITY || s.gam_act[s.n_gam - 1] != NGPDE_ACT_IDENTITY) return false;   // (output layers)
   if (g->max_in_degree > kSlotWidth || g->max_out_degree > kSlotWidth) return false;
-  return vmh_geo(s.n_phi + s.n_gam, g->n_sched / kTileRows).grid > 0;
+  if (vmh_geo(s.n_phi + s.n_gam, g->n_sched / kTileRows).grid <= 0) return false;
+  return node_wait_lists_fit(g);   // (node_persistent_setup refuses a tile that neighbours more than 63 others)
+}
+
+bool node_vmh_tile_rounds(const ngpde_graph *g, const VmhShape &s) {
+  return g && vmh_geo(s.n_phi + s.n_gam, g->n_sched / kTileRows).rounds;
 }
 
 static void fill_meta(VmhMeta &m, const VmhLaunch &a) {

@@ -881,7 +881,8 @@ class NeuralODE(AbstractExplicitLayer):
             # the tapes of a solve -- every layer's input rows and dz rows of every right-hand-side evaluation, 64 floats wide -- did not
             # fit the device (the library parks and re-uses the tapes of plans that went away, and frees them before it gives up): the
             # generic solver, which keeps O(stages) arrays, takes the solve
-            if e.code != _lib.ERR_HIP:
+            # ... or the library found, while building the plan, that the graph is not the plan's after all: the same way out
+            if e.code not in (_lib.ERR_HIP, _lib.ERR_UNSUPPORTED):
                 raise
             if not pool:
                 self._plans.pop(key, None)

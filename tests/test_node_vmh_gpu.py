@@ -35,11 +35,11 @@ def plan_flags(node):
     return sorted({f for pool in node._plans.values() for p in pool for f in p.flags()})
 
 
-def oracle_solve(phi, gam, ps, og, u0, tab_name, dt, n_steps, R, aggr="mean"):
-    ophi, ogam = omlp(phi, ps["ϕ"]), omlp(gam, ps["γ"])
-    tab = O.TABLEAUS[tab_name]
-    gphi = [dict(weight=np.zeros_like(L["weight"]), bias=np.zeros_like(L["bias"])) for L in ophi]
-    ggam = [dict(weight=np.zeros_like(L["weight"]), bias=np.zeros_like(L["bias"])) for L in ogam]
+def grad_accumulators(ophi, ogam):
+    """zeroed parameter gradients of two oracle layer lists ({weight, bias, act}; a bias may be None: no entry then) and the
+    (vjp, accumulate) pair rk_adjoint takes"""
+    zeros = lambda layers: [{k: np.zeros_like(L[k]) for k in ("weight", "bias") if L.get(k) is not None} for L in layers]
+    gphi, ggam = zeros(ophi), zeros(ogam)
 
     def vjp(cache, kbar):
         gr = O.vmh_conv_backward(cache, kbar)
@@ -49,10 +49,22 @@ def oracle_solve(phi, gam, ps, og, u0, tab_name, dt, n_steps, R, aggr="mean"):
         for dst, src in ((gphi, gr["phi"]), (ggam, gr["gamma"])):
             for d_, s_ in zip(dst, src):
                 d_["weight"] += s_["weight"]
-                d_["bias"] += np.asarray(s_["bias"]).reshape(d_["bias"].shape)
+                if "bias" in d_:
+                    d_["bias"] += np.asarray(s_["bias"]).reshape(d_["bias"].shape)
+    return gphi, ggam, vjp, accumulate
+
+
+def oracle_solve_layers(ophi, ogam, og, u0, tab_name, dt, n_steps, R, aggr="mean"):
+    """u(T), du0 and the parameter gradients of loss = sum(R .* u(T)) in float64; ophi / ogam: plain lists of {weight, bias, act}"""
+    tab = O.TABLEAUS[tab_name]
+    gphi, ggam, vjp, accumulate = grad_accumulators(ophi, ogam)
     uT, tape = O.rk_solve(lambda u: O.vmh_conv(u, ophi, ogam, og, aggr=aggr), u0.astype(np.float64), tab, dt, n_steps)
     du0 = O.rk_adjoint(vjp, tape, R, tab, dt, accumulate)
     return uT, du0, gphi, ggam
+
+
+def oracle_solve(phi, gam, ps, og, u0, tab_name, dt, n_steps, R, aggr="mean"):
+    return oracle_solve_layers(omlp(phi, ps["ϕ"]), omlp(gam, ps["γ"]), og, u0, tab_name, dt, n_steps, R, aggr=aggr)
 
 
 @pytest.mark.parametrize("solver,n_steps,act,aggr,depth,pd,N", [
