@@ -34,657 +34,16 @@
 #include <type_traits>
 
 #include "common.h"
-#include "device_utils.h"
-#include "gcn_tile.h"
-#include "persistent_mem.h"
-#include "persistent_sync.h"
+#include "persistent_gcn_tile.h"
 #include "stamps.h"
 
 namespace ngpde {
 
 namespace {
 
-constexpr int PD = 64;
-using PG = Geo<PD>;
-static_assert(PG::R == 1 && PG::GROUPS == kTM && PG::LPR == 16, "one 16-lane group per tile row");
-constexpr int kXhF = (kHaloCap + 1) * PD;   // halo region (floats), +1: the all-zero row
-constexpr int kTileF = kTM * PG::TS;        // one 32-row MFMA operand / result tile
-constexpr int kWF = PD * PG::TS;            // one transposed weight matrix
-constexpr int kMaxTileRounds = 8;            // tile rounds: at most this many tiles per workgroup
-
-struct TileCtx {
-  int tid, lane, wave_u, grp, q, tile, node, hcount, wmax, my_nbr;
-  bool valid;
-  float ci;
-  // kept in LDS, not in registers (the 16 lanes of a group would each hold the same 8 words): the 32 slot bytes of every row
-  // [32][8] and the node ids of the 64 foreign halo slots
-  const unsigned *lds_slots;
-  const int *lds_hnode;
-  const float *lds_w;   // weighted graphs (tile rounds only): the tile's slot weights [32][32], else unused
-};
-constexpr int kMetaF = kTM * 8 + 2 * kTM;   // floats of LDS the two tables take
-
-struct TileMeta {
-  const int2 *halo;
-  const uint8_t *slots;
-  const int4 *sched;
-  const int2 *tile_info;
-  const int *nbr;
-  const float *slot_w;   // [n_sched][kSlotWidth] edge weights in slot order, or NULL (unweighted)
-  unsigned *flags, *abort_word;
-  int n_tiles;
-  const uint8_t *of_pre;   // [n_tiles][8] own rounds per wave when slots / sched are a plan's own-first tables, else NULL
-  int *stats;   // [n_tiles][2] (forward, adjoint): slot-phases of the last launch whose halo rows were gathered ahead of time
-  // hub geometry (HUB kernels only; then `nbr` is [n_tiles][kHubNbr])
-  const int *hub_halo;        // [n_tiles][kHubHalo] node ids, own rows first
-  const uint8_t *hub_slots;   // [n_tiles][kHubList]
-  const int2 *hub_rows;       // [n_sched] {start, length} of the row's list inside its tile's slot bytes
-  const int4 *hub_info;       // [n_tiles] {halo count, list bytes, long rows, 0}
-  const int4 *hub_sched;      // [n_sched] {node or -1, 0, 0, bits of c[node]}: the hub geometry's OWN tile partition (see hub_partition)
-  const uint8_t *hub_long;    // [n_tiles][kTileRows] rows (0 .. 31) with more than kSlotWidth entries
-  const float *hub_w;         // [n_tiles][kHubList] edge weights of the entries, or NULL (unweighted)
-  NGPDE_STAMP_FIELD
-};
-
-__device__ __forceinline__ void tile_ctx_init(const TileMeta &m, TileCtx &c, float *lds_meta, int tile = -1) {
-  c.tid = threadIdx.x;
-  c.lane = c.tid & 63;
-  c.wave_u = __builtin_amdgcn_readfirstlane(c.tid >> 6);
-  c.grp = c.tid >> 4;
-  c.q = c.tid & 15;
-  c.tile = tile >= 0 ? tile : xcd_tile(blockIdx.x, m.n_tiles);
-  const size_t pos = (size_t)c.tile * kTM + c.grp;
-  const int4 sc = m.sched[pos];
-  c.valid = sc.x >= 0;
-  c.node = max(sc.x, 0);
-  c.ci = c.valid ? __int_as_float(sc.w) : 0.f;
-  unsigned *ls = reinterpret_cast<unsigned *>(lds_meta);
-  int *lh = reinterpret_cast<int *>(lds_meta + kTM * 8);
-  if (c.q < 8) ls[c.grp * 8 + c.q] = reinterpret_cast<const unsigned *>(m.slots)[pos * 8 + c.q];
-  if (c.q >= 8 && c.q < 10) lh[c.grp + 32 * (c.q - 8)] = m.halo[(size_t)c.tile * kHaloCap + c.grp + 32 * (c.q - 7)].x;
-  c.lds_slots = ls;
-  c.lds_hnode = lh;
-  c.hcount = __builtin_amdgcn_readfirstlane(m.tile_info[c.tile].x);
-  int wm = c.valid ? sc.z : 0;
-  wm = max(wm, __shfl_xor(wm, 16));
-  wm = max(wm, __shfl_xor(wm, 32));
-  c.wmax = __builtin_amdgcn_readfirstlane(wm);
-  c.my_nbr = m.nbr[(size_t)c.tile * kNbrStride + c.lane];
-}
-
-// Tile rounds (node_*_persistentK_kernel): the tables of ALL the workgroup's tiles stay in LDS for the whole launch -- slot words,
-// halo node ids, schedule entries, wait list, halo count per tile -- so that a turn sets its context up from LDS instead of
-// re-reading five arrays from memory (one round trip and a barrier per turn).
-constexpr int kMetaKF = kMetaF + kTM * 4 + kNbrStride + 4;   // floats per tile
-// Weighted graphs (GCNConv's edge_weight, src/layers.jl:206-231) run on the tile-round kernels only: those keep ONE layer's W in LDS,
-// which leaves room for the 4 KB of slot weights per tile behind the tile's tables -- for at most kMaxTileRoundsW tiles per workgroup.
-constexpr int kMaxTileRoundsW = 3;
-constexpr int kSlotWF = kTM * kSlotWidth;
-template <bool WGT> constexpr int meta_stride() { return kMetaKF + (WGT ? kSlotWF : 0); }
-template <bool WGT> constexpr int meta_tiles() { return WGT ? kMaxTileRoundsW : kMaxTileRounds; }
-template <bool WGT = false>
-__device__ __forceinline__ void tile_tables_to_lds(const TileMeta &m, int tile, float *base) {
-  const int tid = threadIdx.x, grp = tid >> 4, q = tid & 15;
-  const size_t pos = (size_t)tile * kTM + grp;
-  unsigned *ls = reinterpret_cast<unsigned *>(base);
-  int *lh = reinterpret_cast<int *>(base + kTM * 8);
-  int4 *lsc = reinterpret_cast<int4 *>(base + kMetaF);
-  int *ln = reinterpret_cast<int *>(base + kMetaF + kTM * 4);
-  if (q < 8) ls[grp * 8 + q] = reinterpret_cast<const unsigned *>(m.slots)[pos * 8 + q];
-  if (q >= 8 && q < 10) lh[grp + 32 * (q - 8)] = m.halo[(size_t)tile * kHaloCap + grp + 32 * (q - 7)].x;
-  if (q == 10) lsc[grp] = m.sched[pos];
-  if (tid < kNbrStride) ln[tid] = m.nbr[(size_t)tile * kNbrStride + tid];
-  if (tid == kNbrStride) ln[kNbrStride] = m.tile_info[tile].x;
-  if constexpr (WGT) {
-    float2 *lw = reinterpret_cast<float2 *>(base + kMetaKF);
-    lw[tid] = reinterpret_cast<const float2 *>(m.slot_w + (size_t)tile * kSlotWF)[tid];   // 512 threads x 2 floats = [32][32]
-  }
-}
-template <bool WGT = false>
-__device__ __forceinline__ void tile_ctx_from_lds(TileCtx &c, int tile, const float *base) {
-  c.tid = threadIdx.x;
-  c.lane = c.tid & 63;
-  c.wave_u = __builtin_amdgcn_readfirstlane(c.tid >> 6);
-  c.grp = c.tid >> 4;
-  c.q = c.tid & 15;
-  c.tile = tile;
-  const int4 sc = reinterpret_cast<const int4 *>(base + kMetaF)[c.grp];
-  const int *ln = reinterpret_cast<const int *>(base + kMetaF + kTM * 4);
-  c.valid = sc.x >= 0;
-  c.node = max(sc.x, 0);
-  c.ci = c.valid ? __int_as_float(sc.w) : 0.f;
-  c.lds_slots = reinterpret_cast<const unsigned *>(base);
-  c.lds_hnode = reinterpret_cast<const int *>(base + kTM * 8);
-  c.hcount = __builtin_amdgcn_readfirstlane(ln[kNbrStride]);
-  int wm = c.valid ? sc.z : 0;
-  wm = max(wm, __shfl_xor(wm, 16));
-  wm = max(wm, __shfl_xor(wm, 32));
-  c.wmax = __builtin_amdgcn_readfirstlane(wm);
-  c.my_nbr = ln[c.lane];
-  c.lds_w = WGT ? base + kMetaKF : nullptr;
-}
-
-// Wait until every tile of the wait list has finished phase ph - 1: wave 0 polls, one flag per lane (lanes 0..62) and the abort
-// word on lane 63, ONE load per lane and round (a second dependent load per round would double the polling period, which is
-// the granularity a published flag is seen with); everybody meets at the barrier.  Returns false when the solve was aborted.
-// Bounded: after ~2 s of the 100 MHz counter (the whole solve takes ~6 ms) the wave raises the abort word itself.
-// (tile_wait_arrive: the wait without the look at its verdict -- *s_ok, valid behind the barrier -- for callers that read it later, see
-// tile_gather_foreign_checked)
-__device__ __forceinline__ void tile_wait_arrive(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags) {
-  if (ph <= 1) return;
-  if (c.wave_u == 0) {
-    const unsigned need = (unsigned)(ph - 1);
-    const unsigned *addr = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? flags + 32 * c.my_nbr : nullptr);
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    bool ok = true;
-    for (unsigned it = 1;; ++it) {
-      unsigned f = need;
-      if (addr) f = __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__any((int)(c.lane == 63 && f != 0))) { ok = false; break; }              // somebody gave up
-      if (__all((int)(c.lane == 63 || f >= need))) break;
-      if ((it & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {
-        if (c.lane == 0) __hip_atomic_store(m.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = false;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);   // (2 / 4 / 8 measured: no difference beyond run-to-run noise; the polling period is not what a phase waits for)
-    }
-    if (c.lane == 0) *s_ok = ok ? 1 : 0;
-  }
-  __syncthreads();
-}
-__device__ __forceinline__ bool tile_wait(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags) {
-  if (ph <= 1) return true;
-  tile_wait_arrive(m, c, ph, s_ok, flags);
-  return *s_ok != 0;
-}
-__device__ __forceinline__ bool tile_wait(const TileMeta &m, const TileCtx &c, int ph, int *s_ok) { return tile_wait(m, c, ph, s_ok, m.flags); }
-// The same wait with its first round of flag loads issued earlier by the caller (poll_issue: `f` holds wave 0's samples, in flight
-// under whatever the workgroup did in between).  A workgroup that is level with its neighbours finds the flags in that sample
-// and only meets at the barrier; one that runs ahead spins here exactly as long as it leads.  (Used by the interleaved adjoint,
-// whose slot-phase is long enough for the flags to be there.  What the stamps of tools/stamps.py interleaved say about the hand-off:
-// a flag store is seen by a poll from another XCD ~3-4 k cycles (1.2-1.5 us) after it was issued, a poll or a gather is a
-// ~1.5 k-cycle round trip, the drain in front of the flag ~1 k: with only two slots the ~2.4 us of hand-off exceed the ~1.7 us of
-// work the other slot offers in the forward kernel -- wherever the look is put, the difference is waited for.)
-__device__ __forceinline__ void tile_wait_primed_arrive(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags, unsigned f) {
-  if (c.wave_u == 0) {
-    const unsigned need = (unsigned)(ph - 1);
-    const unsigned *addr = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? flags + 32 * c.my_nbr : nullptr);
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    bool ok = true;
-    for (unsigned it = 1;; ++it) {
-      if (__any((int)(c.lane == 63 && f != 0))) { ok = false; break; }
-      if (__all((int)(c.lane == 63 || f >= need))) break;
-      if ((it & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {
-        if (c.lane == 0) __hip_atomic_store(m.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = false;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-      f = (c.lane == 63) ? 0u : need;
-      if (addr) f = __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (c.lane == 0) *s_ok = ok ? 1 : 0;
-  }
-  __syncthreads();
-}
-__device__ __forceinline__ bool tile_wait_primed(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags, unsigned f) {
-  tile_wait_primed_arrive(m, c, ph, s_ok, flags, f);
-  return *s_ok != 0;
-}
-
-// every storing wave drains, the workgroup meets, ONE lane publishes (Guideline 16, R1)
-__device__ __forceinline__ void tile_publish(const TileCtx &c, int ph, unsigned *flags) {
-  wait_vmcnt0();
-  __syncthreads();
-  if (c.tid == 0) __hip_atomic_store(flags + 32 * c.tile, (unsigned)ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void tile_publish(const TileMeta &m, const TileCtx &c, int ph) { tile_publish(c, ph, m.flags); }
-
-// the rows of OTHER tiles this tile's halo references: memory -> LDS slots 32.., sc1 (the producers stored them write-through
-// in the previous phase; sc1 loads bypass this CU's L1, which may hold the same addresses from two phases ago)
-__device__ __forceinline__ void tile_gather_foreign(const TileCtx &c, const float *X, float *ldsXh) {
-  float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    if (4 * c.wave_u + 32 * (k + 1) < c.hcount) {   // wave-uniform: a wave's four groups stage four consecutive slots
-      const unsigned off = (unsigned)c.lds_hnode[c.grp + 32 * k] * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(reinterpret_cast<const char *>(X) + off),
-                                       (__attribute__((address_space(3))) void *)(Xh4 + (c.grp + 32 * (k + 1)) * PG::LPR + c.q), 16, 0, 16);
-    }
-  }
-  wait_vmcnt0();
-  __syncthreads();
-}
-
-// The same gather with the byte offsets of the foreign rows formed by the caller BEFORE the wait (tile_gather_offsets): read behind the
-// wait, every halo index is an LDS round trip between "the flags were seen" and the DMA it addresses, paid by all waves in step.
-__device__ __forceinline__ void tile_gather_offsets(const TileCtx &c, unsigned (&off)[2]) {
-#pragma unroll
-  for (int k = 0; k < 2; ++k) off[k] = (unsigned)c.lds_hnode[c.grp + 32 * k] * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
-}
-// ... and with the wait's verdict (*s_ok, written in front of the wait's barrier) read under the DMAs instead of between the wait and the
-// gather, where it is one more LDS round trip in everybody's way.  A gather that an aborted solve issues reads valid rows and is drained
-// here before anybody leaves.  Returns false when the solve was aborted.
-__device__ __forceinline__ bool tile_gather_foreign_checked(const TileCtx &c, const float *X, float *ldsXh, const unsigned (&off)[2], const int *s_ok) {
-  float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    if (4 * c.wave_u + 32 * (k + 1) < c.hcount) {   // wave-uniform: a wave's four groups stage four consecutive slots
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(reinterpret_cast<const char *>(X) + off[k]),
-                                       (__attribute__((address_space(3))) void *)(Xh4 + (c.grp + 32 * (k + 1)) * PG::LPR + c.q), 16, 0, 16);
-    }
-  }
-  const int verdict = *s_ok;
-  wait_vmcnt0();
-  __syncthreads();
-  return verdict != 0;
-}
-
-// sum of the row's neighbours (slot bytes, in CSR order) + its own row (self loop), all from LDS
-// (plain adds on purpose: this file is built without SLP packing, and written as v_pk_add_f32 -- f4_add_pk -- these sums cost the
-// headline 2 %: they run beside the CU's other workgroup's MFMAs, where packed f32 VALU is slow; profiles/r05_x_ab_slp.txt)
-// the row's 32 slot bytes, fetched from LDS BEFORE the wait (one address per 16-lane group: broadcast reads): they are live
-// only across the wait and the gather, where registers are plentiful, and the aggregation does not start with a dependent read
-__device__ __forceinline__ void tile_slot_words(const TileCtx &c, unsigned (&w)[8]) {
-  const uint4 a = reinterpret_cast<const uint4 *>(c.lds_slots)[c.grp * 2], b = reinterpret_cast<const uint4 *>(c.lds_slots)[c.grp * 2 + 1];
-  w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-
-// the four rows a slot word names (one ds_read_b128 each)
-__device__ __forceinline__ void tile_round_rows(const float4 *Xh4, unsigned w, int q, float4 (&v)[4]) {
-#pragma unroll
-  for (int jb = 0; jb < 4; ++jb) v[jb] = Xh4[((w >> (8 * jb)) & 0xff) * PG::LPR + q];
-}
-// Rounds 0 .. n - 1 (n wave-uniform, 0 .. 8) of the slot words w added to a: a + ((v0 + v1) + (v2 + v3)) per round, rounds in order.
-// Software-pipelined: the four rows of round r + 1 are asked for BEFORE round r is summed, so a round costs the issue of its reads and
-// adds and not an LDS round trip of its own (one basic block per round behind a wave-uniform `if`, as this sum was written before,
-// exposes the full latency in every round of a wave).  The exit test sits in front of the prefetch, never between a round's prefetch
-// and the adds it covers; the last round is a peeled epilogue (adds only).  Worth <= 1 % of the headline: the tile's other waves already
-// covered most of that latency, the sums are bound by VALU issue (profiles/r07_a_pipelined_sums.txt).
-__device__ __forceinline__ float4 tile_aggregate_rounds(const TileCtx &c, const unsigned (&w)[8], const float *ldsXh, float4 a, int n) {
-  const float4 *Xh4 = reinterpret_cast<const float4 *>(ldsXh);
-  if (n <= 0) return a;   // wave-uniform
-  float4 v[4];
-  tile_round_rows(Xh4, w[0], c.q, v);
-#pragma unroll
-  for (int jw = 0; jw < 8; ++jw) {
-    if (jw == 7 || jw + 1 >= n) {   // wave-uniform
-      a = f4_add(a, f4_add(f4_add(v[0], v[1]), f4_add(v[2], v[3])));
-      break;
-    }
-    float4 nx[4];
-    tile_round_rows(Xh4, w[jw + 1], c.q, nx);
-    __builtin_amdgcn_sched_barrier(0);   // the reads first: left alone, the scheduler starts every other round with the adds that wait
-    a = f4_add(a, f4_add(f4_add(v[0], v[1]), f4_add(v[2], v[3])));
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb) v[jb] = nx[jb];
-  }
-  return a;
-}
-// The same sum without the second buffer of rows, for the adjoint (16 more registers across its sums spill there): the two halves of
-// a round roll through their own registers -- rows 0, 1 of round r + 1 are asked for as soon as v0 + v1 of round r is formed, rows
-// 2, 3 as soon as v2 + v3 is -- so half a round's reads are always in flight under the other half's adds.  Same additions, same order.
-__device__ __forceinline__ float4 tile_aggregate_rounds_rolling(const TileCtx &c, const unsigned (&w)[8], const float *ldsXh, float4 a, int n) {
-  const float4 *Xh4 = reinterpret_cast<const float4 *>(ldsXh);
-  if (n <= 0) return a;   // wave-uniform
-  auto row = [&](unsigned wd, int jb) { return Xh4[((wd >> (8 * jb)) & 0xff) * PG::LPR + c.q]; };
-  float4 v0 = row(w[0], 0), v1 = row(w[0], 1), v2 = row(w[0], 2), v3 = row(w[0], 3);
-#pragma unroll
-  for (int jw = 0; jw < 8; ++jw) {
-    if (jw == 7 || jw + 1 >= n) {   // wave-uniform
-      a = f4_add(a, f4_add(f4_add(v0, v1), f4_add(v2, v3)));
-      break;
-    }
-    const float4 p = f4_add(v0, v1);
-    __builtin_amdgcn_sched_barrier(0);
-    v0 = row(w[jw + 1], 0); v1 = row(w[jw + 1], 1);
-    __builtin_amdgcn_sched_barrier(0);
-    const float4 s2 = f4_add(v2, v3);
-    __builtin_amdgcn_sched_barrier(0);
-    v2 = row(w[jw + 1], 2); v3 = row(w[jw + 1], 3);
-    __builtin_amdgcn_sched_barrier(0);
-    a = f4_add(a, f4_add(p, s2));
-  }
-  return a;
-}
-
-// (the two-slot kernels' form, one basic block per round: the tile-pair kernels have no 16 registers for a second buffer of rows)
-__device__ __forceinline__ float4 tile_aggregate(const TileCtx &c, const unsigned (&sw)[8], const float *ldsXh) {
-  const float4 *Xh4 = reinterpret_cast<const float4 *>(ldsXh);
-  float4 a = f4_zero();
-#pragma unroll
-  for (int jw = 0; jw < 8; ++jw) {
-    if (jw * 4 < c.wmax) {   // wave-uniform
-      const unsigned w = sw[jw];
-      float4 v[4];
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) v[jb] = Xh4[((w >> (8 * jb)) & 0xff) * PG::LPR + c.q];
-      a = f4_add(a, f4_add(f4_add(v[0], v[1]), f4_add(v[2], v[3])));
-    }
-  }
-  return f4_add(a, Xh4[c.grp * PG::LPR + c.q]);
-}
-// the same sums in the same order with the slot words read from LDS round by round (8 fewer registers across the rounds; for the
-// interleaved adjoint, which is at the 128-register edge)
-__device__ __forceinline__ float4 tile_aggregate_lean(const TileCtx &c, const float *ldsXh) {
-  const float4 *Xh4 = reinterpret_cast<const float4 *>(ldsXh);
-  float4 a = f4_zero();
-#pragma unroll 1
-  for (int jw = 0; jw * 4 < c.wmax; ++jw) {   // wave-uniform
-    const unsigned w = c.lds_slots[c.grp * 8 + jw];
-    float4 v[4];
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb) v[jb] = Xh4[((w >> (8 * jb)) & 0xff) * PG::LPR + c.q];
-    a = f4_add(a, f4_add(f4_add(v[0], v[1]), f4_add(v[2], v[3])));
-  }
-  return f4_add(a, Xh4[c.grp * PG::LPR + c.q]);
-}
-
-// weighted rows: the replayed plan's order of operations (halo_finish, gcn_fused.hip: one fma per slot, in slot order); the four
-// weights of a round are one 16-byte LDS read that the row's 16 lanes share
-__device__ __forceinline__ float4 tile_aggregate_weighted(const TileCtx &c, const float *ldsXh) {
-  const float4 *Xh4 = reinterpret_cast<const float4 *>(ldsXh);
-  float4 a = f4_zero();
-#pragma unroll 1
-  for (int jw = 0; jw * 4 < c.wmax; ++jw) {   // wave-uniform
-    const unsigned w = c.lds_slots[c.grp * 8 + jw];
-    const float4 wv = *reinterpret_cast<const float4 *>(c.lds_w + c.grp * kSlotWidth + 4 * jw);
-    float4 v[4];
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb) v[jb] = Xh4[((w >> (8 * jb)) & 0xff) * PG::LPR + c.q];
-    a = f4_fma(wv.x, v[0], a); a = f4_fma(wv.y, v[1], a); a = f4_fma(wv.z, v[2], a); a = f4_fma(wv.w, v[3], a);
-  }
-  return f4_add(a, Xh4[c.grp * PG::LPR + c.q]);
-}
-
-
-// ---- own-first aggregation (round 6; the plan's OwnFirst tables, common.h) ------------------------------------------------------------
-// The slot bytes a plan's forward kernels read list every row's own-tile slots first (padded to the wave's number of own rounds), then the
-// foreign ones; TileMeta::of_pre names the own rounds per wave.  The one-tile forward kernels sum those rounds BEFORE they wait for their
-// neighbours' flags -- a tile's own rows are in LDS since its last epilogue -- and only the foreign rounds behind the gather.  Measured
-// with an in-kernel re-ordering of the same kind (profiles/r06_a_own_first.txt): forward launch 2.301 -> 2.234 ms.
-// The foreign rounds start at a wave-uniform round r0 = of_pre: their slot words are fetched a second time, shifted, so that the pipelined
-// sum (tile_aggregate_rounds) indexes its words from 0 with constants: w[k] = the row's word min(r0 + k, 7).  Fetched with the own
-// rounds' words BEFORE the wait; the own rounds' words are dead by then, so no more registers cross the wait than before.
-__device__ __forceinline__ void tile_slot_words_from(const TileCtx &c, int r0, unsigned (&w)[8]) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) w[k] = c.lds_slots[c.grp * 8 + min(r0 + k, 7)];
-}
-// ---- hub geometry (graphs whose tiles do not fit the 96-row halo / 32-entry rows: BASELINE config 1's Cora-shaped graph) --------
-// One workgroup per CU and tile; per tile and direction (lists built by node_persistent_setup, not part of the graph handle):
-//   * a halo of up to kHubHalo = 256 distinct rows (own rows first), 64 KB of LDS -- the reach of an LDS-DMA destination;
-//   * per row a VARIABLE-length list of slot bytes in CSR order (start aligned to 4, {start, length} per row), at most kHubList bytes
-//     per tile; no zero row: the tail of a list is masked, not padded;
-//   * rows longer than kSlotWidth entries ("long rows", the hubs) are summed by all 32 lane groups together: group g takes entries
-//     g, g + 32, ..., the 32 partial rows meet in LDS and the row's own group adds them in group order;
-//   * a wait list of up to 255 tiles: four flags per lane of the polling wave (position 63 of the list is the abort word's lane).
-// Arithmetic per row otherwise as in the 96-row geometry (groups of four slots, then the own row).
-constexpr int kHubHalo = 256;
-constexpr int kHubList = 4096;
-constexpr int kHubNbr = 256;
-constexpr int kHubXhF = kHubHalo * PD;
-constexpr int kHubMetaF = kHubList / 4 + (kHubHalo - kTM) + 2 * kTM + kTM / 4 + kHubList;   // slot bytes, foreign node ids, {start, length} per row, long-row indices, entry weights
-
-struct HubCtx : TileCtx {
-  const uint8_t *hs;         // LDS: the tile's slot bytes
-  const int2 *hrows;         // LDS: {start, length} of every row's list
-  const uint8_t *hlong;      // LDS: rows with more than kSlotWidth entries
-  const float *hw;           // LDS: the entries' edge weights (same positions as the slot bytes), or NULL: unweighted graph
-  int start, len;            // this row's list (len = 0 for a long row: it is summed cooperatively)
-  int n_long;
-  int nb1, nb2, nb3;         // wave 0: wait-list entries lane + 64, + 128, + 192 (my_nbr = entry lane)
-};
-
-__device__ __forceinline__ void hub_ctx_init(const TileMeta &m, HubCtx &c, float *lds_meta) {
-  c.tid = threadIdx.x;
-  c.lane = c.tid & 63;
-  c.wave_u = __builtin_amdgcn_readfirstlane(c.tid >> 6);
-  c.grp = c.tid >> 4;
-  c.q = c.tid & 15;
-  c.tile = xcd_tile(blockIdx.x, m.n_tiles);
-  const size_t pos = (size_t)c.tile * kTM + c.grp;
-  const int4 sc = m.hub_sched[pos];
-  c.valid = sc.x >= 0;
-  c.node = max(sc.x, 0);
-  c.ci = c.valid ? __int_as_float(sc.w) : 0.f;
-  const int4 info = m.hub_info[c.tile];   // {halo count, list bytes (multiple of 16), long rows, -}
-  uint4 *ls = reinterpret_cast<uint4 *>(lds_meta);
-  int *lh = reinterpret_cast<int *>(lds_meta + kHubList / 4);
-  int2 *lr = reinterpret_cast<int2 *>(lds_meta + kHubList / 4 + (kHubHalo - kTM));
-  unsigned *ll = reinterpret_cast<unsigned *>(lds_meta + kHubList / 4 + (kHubHalo - kTM) + 2 * kTM);
-  if (c.tid * 16 < info.y) ls[c.tid] = reinterpret_cast<const uint4 *>(m.hub_slots + (size_t)c.tile * kHubList)[c.tid];
-  if (c.tid < kHubHalo - kTM) lh[c.tid] = m.hub_halo[(size_t)c.tile * kHubHalo + kTM + c.tid];
-  if (c.tid >= 256 && c.tid < 256 + kTM) lr[c.tid - 256] = m.hub_rows[(size_t)c.tile * kTM + (c.tid - 256)];
-  if (c.tid >= 320 && c.tid < 320 + kTM / 4) ll[c.tid - 320] = reinterpret_cast<const unsigned *>(m.hub_long + (size_t)c.tile * kTM)[c.tid - 320];
-  c.hs = reinterpret_cast<const uint8_t *>(ls);
-  c.lds_hnode = lh;
-  c.lds_slots = nullptr;
-  c.lds_w = nullptr;
-  c.hrows = lr;
-  c.hlong = reinterpret_cast<const uint8_t *>(ll);
-  c.hw = nullptr;
-  if (m.hub_w) {   // (uniform) edge weights (src/layers.jl:206-231): one float beside every slot byte
-    float4 *lw = reinterpret_cast<float4 *>(lds_meta + kHubList / 4 + (kHubHalo - kTM) + 2 * kTM + kTM / 4);
-    const float4 *gw = reinterpret_cast<const float4 *>(m.hub_w + (size_t)c.tile * kHubList);
-#pragma unroll
-    for (int k = 0; k < kHubList / 4 / kThreads; ++k)
-      if ((c.tid + k * kThreads) * 4 < info.y) lw[c.tid + k * kThreads] = gw[c.tid + k * kThreads];
-    c.hw = reinterpret_cast<const float *>(lw);
-  }
-  c.hcount = __builtin_amdgcn_readfirstlane(info.x);
-  c.n_long = __builtin_amdgcn_readfirstlane(info.z);
-  const int2 mine = m.hub_rows[pos];
-  c.start = mine.x;
-  c.len = (c.valid && mine.y <= kSlotWidth) ? mine.y : 0;
-  int wm = c.len;
-  wm = max(wm, __shfl_xor(wm, 16));
-  wm = max(wm, __shfl_xor(wm, 32));
-  c.wmax = __builtin_amdgcn_readfirstlane(wm);
-  const int *nb = m.nbr + (size_t)c.tile * kHubNbr;
-  c.my_nbr = nb[c.lane]; c.nb1 = nb[c.lane + 64]; c.nb2 = nb[c.lane + 128]; c.nb3 = nb[c.lane + 192];
-}
-
-// tile_wait for a wait list of up to 255 tiles: four independent flag loads per lane and round
-__device__ __forceinline__ bool hub_wait(const TileMeta &m, const HubCtx &c, int ph, int *s_ok) {
-  if (ph <= 1) return true;
-  if (c.wave_u == 0) {
-    const unsigned need = (unsigned)(ph - 1);
-    const unsigned *a0 = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? m.flags + 32 * c.my_nbr : nullptr);
-    const unsigned *a1 = c.nb1 >= 0 ? m.flags + 32 * c.nb1 : nullptr, *a2 = c.nb2 >= 0 ? m.flags + 32 * c.nb2 : nullptr,
-                   *a3 = c.nb3 >= 0 ? m.flags + 32 * c.nb3 : nullptr;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    bool ok = true;
-    for (unsigned it = 1;; ++it) {
-      unsigned f0 = need, f1 = need, f2 = need, f3 = need;
-      if (a0) f0 = __hip_atomic_load(a0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a1) f1 = __hip_atomic_load(a1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a2) f2 = __hip_atomic_load(a2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a3) f3 = __hip_atomic_load(a3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__any((int)(c.lane == 63 && f0 != 0))) { ok = false; break; }              // somebody gave up
-      if (__all((int)((c.lane == 63 || f0 >= need) && f1 >= need && f2 >= need && f3 >= need))) break;
-      if ((it & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {
-        if (c.lane == 0) __hip_atomic_store(m.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = false;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    if (c.lane == 0) *s_ok = ok ? 1 : 0;
-  }
-  __syncthreads();
-  return *s_ok != 0;
-}
-
-// tile_gather_foreign for up to 224 foreign rows (halo slots 32 .. 255)
-__device__ __forceinline__ void hub_gather_foreign(const HubCtx &c, const float *X, float *ldsXh) {
-  float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
-#pragma unroll
-  for (int k = 0; k < (kHubHalo - kTM) / kTM; ++k) {
-    if (4 * c.wave_u + 32 * (k + 1) < c.hcount) {   // wave-uniform: a wave's four groups stage four consecutive slots
-      const unsigned off = (unsigned)c.lds_hnode[c.grp + 32 * k] * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(reinterpret_cast<const char *>(X) + off),
-                                       (__attribute__((address_space(3))) void *)(Xh4 + (c.grp + 32 * (k + 1)) * PG::LPR + c.q), 16, 0, 16);
-    }
-  }
-  wait_vmcnt0();
-  __syncthreads();
-}
-
-// the row's first 32 slot bytes, fetched from LDS BEFORE the wait (as tile_slot_words; words beyond the row's list hold other rows'
-// bytes or table words -- valid LDS, masked at use)
-__device__ __forceinline__ void hub_slot_words(const HubCtx &c, unsigned (&w)[8]) {
-  const unsigned *s4 = reinterpret_cast<const unsigned *>(c.hs + c.start);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) w[k] = s4[k];
-}
-
-// sum of the row's neighbours + its own row; `part` = 32 x 64 floats of LDS that nobody else uses during the aggregation.
-// (Measured and not kept: the long row's partial rows formed first, eight masked entries per group unrolled with their slot bytes
-// fetched together -- 8 + 8 LDS reads per lane whatever the row's length: the hub tile's aggregation 3.8 k -> 4.7 k cycles.)
-// Weighted graphs (c.hw): one fma per entry in list order, as the 96-row geometry's weighted rows (tile_aggregate_weighted); a long
-// row's groups fold weight * row into their partial sums.
-__device__ __forceinline__ float4 hub_aggregate(const HubCtx &c, const unsigned (&sw)[8], const float *ldsXh, float *part) {
-  const float4 *Xh4 = reinterpret_cast<const float4 *>(ldsXh);
-  float4 a = f4_zero();
-  if (c.hw) {   // (uniform)
-#pragma unroll 1
-    for (int jw = 0; jw * 4 < c.wmax; ++jw) {   // wave-uniform
-      const unsigned w = sw[jw];
-      const float4 wv = *reinterpret_cast<const float4 *>(c.hw + c.start + 4 * jw);   // (list starts are multiples of four: 16-byte aligned)
-      const float ww[4] = {wv.x, wv.y, wv.z, wv.w};
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        const float4 v = f4_sel(4 * jw + jb < c.len, Xh4[((w >> (8 * jb)) & 0xff) * PG::LPR + c.q], f4_zero());
-        a = f4_fma(4 * jw + jb < c.len ? ww[jb] : 0.f, v, a);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int jw = 0; jw < 8; ++jw) {
-      if (jw * 4 < c.wmax) {   // wave-uniform
-        const unsigned w = sw[jw];
-        float4 v[4];
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb) v[jb] = f4_sel(4 * jw + jb < c.len, Xh4[((w >> (8 * jb)) & 0xff) * PG::LPR + c.q], f4_zero());
-        a = f4_add_pk(a, f4_add_pk(f4_add_pk(v[0], v[1]), f4_add_pk(v[2], v[3])));
-      }
-    }
-  }
-  for (int li = 0; li < c.n_long; ++li) {   // uniform
-    const int r = c.hlong[li];
-    const int2 rl = c.hrows[r];
-    float4 p = f4_zero();
-    if (c.hw) {
-      for (int j = c.grp; j < rl.y; j += kTM) p = f4_fma(c.hw[rl.x + j], Xh4[(unsigned)c.hs[rl.x + j] * PG::LPR + c.q], p);
-    } else {
-      for (int j = c.grp; j < rl.y; j += kTM) p = f4_add_pk(p, Xh4[(unsigned)c.hs[rl.x + j] * PG::LPR + c.q]);
-    }
-    reinterpret_cast<float4 *>(part)[c.grp * PG::LPR + c.q] = p;
-    __syncthreads();
-    if (c.wave_u == (r >> 2)) {   // the wave of the row's group: each of its four groups adds eight partial rows, two exchanges fold them
-      const int g4 = c.grp & 3;
-      float4 t = reinterpret_cast<const float4 *>(part)[g4 * PG::LPR + c.q];
-#pragma unroll
-      for (int k = 1; k < kTM / 4; ++k) t = f4_add_pk(t, reinterpret_cast<const float4 *>(part)[(g4 + 4 * k) * PG::LPR + c.q]);
-      t.x += __shfl_xor(t.x, 16); t.y += __shfl_xor(t.y, 16); t.z += __shfl_xor(t.z, 16); t.w += __shfl_xor(t.w, 16);
-      t.x += __shfl_xor(t.x, 32); t.y += __shfl_xor(t.y, 32); t.z += __shfl_xor(t.z, 32); t.w += __shfl_xor(t.w, 32);
-      if (c.grp == r) a = f4_add_pk(a, t);
-    }
-    __syncthreads();   // (the buffer is written again: by the next long row, or by the caller -- the adjoint's dz tile)
-  }
-  return f4_add_pk(a, Xh4[c.grp * PG::LPR + c.q]);
-}
-
-// W (row-major [in][out]) -> LDS, transposed (forward: B[k = in][j = out], stored Bt[j][k]) or straight (pullback: Bt[j = in][k = out])
-__device__ __forceinline__ void load_weight_lds(const float *wt, float *ldsBt, int tid, bool transpose) {
-  if (transpose) {
-    const int j = tid % PD, kg0 = tid / PD;
-#pragma unroll
-    for (int ps = 0; ps < PG::NPASS; ++ps) {
-      const int kg = kg0 + ps * PG::KGP;
-      if (kg < PD / 4) {
-        const float *w = wt + (size_t)(4 * kg) * PD + j;
-        *reinterpret_cast<float4 *>(&ldsBt[j * PG::TS + 4 * kg]) = make_float4(w[0], w[PD], w[2 * PD], w[3 * PD]);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < PG::W4; ++k) {
-      const int idx = tid + k * kThreads;
-      if (idx < PD * PD / 4) {
-        const int wi = (idx * 4) / PD, wo = (idx * 4) % PD;
-        *reinterpret_cast<float4 *>(&ldsBt[wi * PG::TS + wo]) = reinterpret_cast<const float4 *>(wt)[idx];
-      }
-    }
-  }
-}
-
-// ---- pieces of the interleaved kernels' software pipeline -------------------------------------------------------------------
-// wave 0: one flag load per lane of the wait list (lane 63: the abort word), NOT waited for
-__device__ __forceinline__ unsigned poll_issue(const TileMeta &m, const TileCtx &c, const unsigned *flags) {
-  const unsigned *addr = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? flags + 32 * c.my_nbr : nullptr);
-  unsigned f = (c.lane == 63) ? 0u : 0xffffffffu;
-  if (addr) f = __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return f;
-}
-// wave 0: did every tile of the wait list show phase ph - 1 (and nobody give up)?
-__device__ __forceinline__ bool poll_ready(const TileCtx &c, unsigned f, int ph) {
-  const unsigned need = (unsigned)(ph - 1);
-  return __all((int)(c.lane == 63 ? f == 0u : f >= need)) != 0;
-}
-// a slot's own rows into halo slots 0..31 and the LDS-DMA of the foreign rows (tile_gather_foreign without its wait).  `halo`
-// is __restrict__ so that LDS reads of OTHER regions issued behind it are not made to wait for the DMA (see dense_mfma.hip,
-// products_beside_dma: behind a global_load_lds the wait-count pass otherwise drains vmcnt in front of every LDS access)
-__device__ __forceinline__ void halo_fill_ahead(const TileCtx &c, const float *X, float *__restrict__ halo, float4 xown) {
-  float4 *Xh4 = reinterpret_cast<float4 *>(halo);
-  Xh4[c.grp * PG::LPR + c.q] = xown;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    if (4 * c.wave_u + 32 * (k + 1) < c.hcount) {   // wave-uniform
-      const unsigned off = (unsigned)c.lds_hnode[c.grp + 32 * k] * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(reinterpret_cast<const char *>(X) + off),
-                                       (__attribute__((address_space(3))) void *)(Xh4 + (c.grp + 32 * (k + 1)) * PG::LPR + c.q), 16, 0, 16);
-    }
-  }
-}
-// the same with the slot's OWN rows fetched as well (halo slots 0..31 = the tile's rows: one more DMA per wave; they were stored
-// write-through at least a slot-phase earlier).  For kernels that keep no copy of them in registers.
-__device__ __forceinline__ void halo_fill_all(const TileCtx &c, const float *X, float *__restrict__ halo) {
-  float4 *Xh4 = reinterpret_cast<float4 *>(halo);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    if (k == 0 || 4 * c.wave_u + 32 * k < c.hcount) {   // wave-uniform
-      const unsigned row = k == 0 ? (unsigned)c.node : (unsigned)c.lds_hnode[c.grp + 32 * (k - 1)];
-      const unsigned off = row * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(reinterpret_cast<const char *>(X) + off),
-                                       (__attribute__((address_space(3))) void *)(Xh4 + (c.grp + 32 * k) * PG::LPR + c.q), 16, 0, 16);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // forward solve
 // ---------------------------------------------------------------------------------------------------------------------
-struct PFwdK {
-  TileMeta m;          // lists by TARGET
-  int n_steps, S, act;
-  int n_members;       // trajectories solved one after the other on the same structure (a block-diagonal batch of identical graphs)
-  const float *u_in;   // [n_members][N][64]  c .* u0
-  float *u_out;        // [n_members][N][64]  c .* u(T)
-  float *bufA, *bufB;  // exchanged arrays: stage input (A), layer-1 output (B)
-  const float *w1, *b1, *w2, *b2;
-  float *tape;         // [n_members][n_steps][S][2][N][64] aggregated layer inputs, or null (forward-only plan)
-  uint8_t *masks;      // [n_members][n_steps][S][2][mask_bytes] relu sign bits
-  float *ztape;        // same shape as tape: the pre-activations, kept instead of the sign bits when the activation is not relu
-  size_t row_elems, mask_bytes;
-  size_t flag_stride;  // two-slot kernels: slot s uses bufA / bufB + s * row_elems and the flag words m.flags + s * flag_stride
-  int pair_wgs;        // tile-pair mode of the two-slot kernels (PAIR): the grid; workgroup b holds tiles t and t + pair_wgs of ONE member
-  int k_tiles;         // tile-round mode (node_fwd_persistentK_kernel): workgroup b holds tiles t, t + pair_wgs, ..., k_tiles of them
-  float *state;        // ... and keeps their state in memory: [7][N][64] own rows -- u, k_0 .. k_5 (k rows zero at launch)
-  const float *cf;     // device table [36 + 6]: cf[i * 6 + j], j < i: coefficient of k_j in the array written after stage i (next
-                       // stage input / step update), 0 elsewhere; cf[36 + i]: coefficient of k_i itself.  Copied to LDS.
-};
 
 // WGT (edge weights, src/layers.jl:206-231): the 4 KB of slot weights of the tile need LDS that two resident W^T do not leave, so layer 1's
 // W^T is B fragments in registers for the whole launch (16 per lane; the forward kernel has them to spare) and only W2^T is in LDS
@@ -702,7 +61,7 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
   typename std::conditional<HUB, HubCtx, TileCtx>::type c;
   if constexpr (HUB) hub_ctx_init(p.m, c, ldsMeta);
   else tile_ctx_init(p.m, c, ldsMeta);
-  if (c.tid < 42) ldsC[c.tid] = p.cf[c.tid];
+  coef_to_lds(ldsC, p.cf, 42, c.tid);
   const int act = ACT >= 0 ? ACT : p.act;
   float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
   float bw1[16];
@@ -718,11 +77,10 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
     load_weight_lds(p.w1, ldsW1, c.tid, true);
   }
   load_weight_lds(p.w2, ldsW2, c.tid, true);
-  if (c.tid < PD) ldsB[c.tid] = p.b1 ? p.b1[c.tid] : 0.f;
-  else if (c.tid < 2 * PD) ldsB[c.tid] = p.b2 ? p.b2[c.tid - PD] : 0.f;
-  if (!HUB && c.grp == 0) Xh4[kHaloCap * PG::LPR + c.q] = f4_zero();
+  biases_to_lds(ldsB, p.b1, p.b2, c.tid);
+  if (!HUB) zero_halo_row(ldsXh, c.grp == 0, c.q);
   if (c.tid == 0) *s_ok = 1;
-  const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);   // byte offset of this thread's 16 bytes in a [N][64] array
+  const unsigned own = own_row_offset(c);   // byte offset of this thread's 16 bytes in a [N][64] array
   __syncthreads();
   // own rounds of this wave's rows (the plan's own-first tables; 0: everything is summed behind the gather, as without them)
   int of_pre = 0;
@@ -781,7 +139,7 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
           agg = tile_aggregate_weighted(c, ldsXh);
         }
         float4 acc = f4_scale(c.ci, agg);   // a_i = c_i * sum of the stored (pre-scaled) rows
-        *reinterpret_cast<float4 *>(&ldsT[c.grp * PG::TS + 4 * c.q]) = acc;
+        tile_row_store(ldsT, c, acc);
         const size_t ev = ev0 + (size_t)(n * p.S + i) * 2 + layer;
         __syncthreads();
         NGPDE_PHASE_STAMP(p.m.stamps, ph, 3);
@@ -789,22 +147,17 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
         else mfma_rows_times_bt<PD>(ldsT, layer == 0 ? ldsW1 : ldsW2, ldsZ, c.wave_u, c.lane);
         __syncthreads();
         NGPDE_PHASE_STAMP(p.m.stamps, ph, 4);
-        const float4 z = f4_add(*reinterpret_cast<const float4 *>(&ldsZ[c.grp * PG::TS + 4 * c.q]), layer == 0 ? bias1 : bias2);
-        const uint8_t sign_bits = (uint8_t)((z.x > 0.f ? 1 : 0) | (z.y > 0.f ? 2 : 0) | (z.z > 0.f ? 4 : 0) | (z.w > 0.f ? 8 : 0));
-        float4 yv = f4_sel(c.valid, f4_scale(c.ci, f4_act(act, z)), f4_zero());   // stored as c .* y
+        const float4 z = fwd_preact(ldsZ, c, layer == 0 ? bias1 : bias2);
+        const uint8_t sign_bits = relu_sign_bits(z);
+        float4 yv = fwd_output(c, act, z);
         if (layer == 0) {
           if (c.valid) store_sc1(p.bufB, own, yv);
           Xh4[c.grp * PG::LPR + c.q] = yv;
         } else {
-          // k_i = yv; next stage input (or the step update) = u + sum_j cf[i][j] k_j -- same order as the replayed plan:
-          // coef_self * k_i first, then u, then k_0 .. k_{i-1}
+          // k_i = yv, kept in its register; then the next stage input (or the step update)
           k0 = f4_sel(i == 0, yv, k0); k1 = f4_sel(i == 1, yv, k1); k2 = f4_sel(i == 2, yv, k2);
           k3 = f4_sel(i == 3, yv, k3); k4 = f4_sel(i == 4, yv, k4); k5 = f4_sel(i == 5, yv, k5);
-          // (terms with a zero coefficient add an exact zero: k_j is finite, stale values of later stages included)
-          float4 v = f4_scale(ldsC[36 + i], yv);
-          v = f4_fma(1.0f, u, v);
-          v = f4_fma(ldsC[i * 6 + 0], k0, v); v = f4_fma(ldsC[i * 6 + 1], k1, v); v = f4_fma(ldsC[i * 6 + 2], k2, v);
-          v = f4_fma(ldsC[i * 6 + 3], k3, v); v = f4_fma(ldsC[i * 6 + 4], k4, v);
+          const float4 v = rk_combine<false>(RkCoefInPlace{ldsC, i}, i, yv, u, k0, k1, k2, k3, k4);
           if (i == p.S - 1) u = v;
           if (c.valid) store_sc1(p.bufA, own, v);
           Xh4[c.grp * PG::LPR + c.q] = v;
@@ -818,7 +171,7 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_fwd_persistent_ker
         else if (TAPE && c.valid) st4_stream_g(p.ztape + ev * p.row_elems, own, z);
         // the tape row likewise: the aggregated row stays in ldsT until this thread overwrites it in the next phase, so its 64-bit address
         // arithmetic, its issue and its share of the publish's drain are out of the chain between "flags seen" and "flag published"
-        if (TAPE && c.valid) st4_stream_g(p.tape + ev * p.row_elems, own, *reinterpret_cast<const float4 *>(&ldsT[c.grp * PG::TS + 4 * c.q]));
+        if (TAPE && c.valid) st4_stream_g(p.tape + ev * p.row_elems, own, tile_row(ldsT, c));
       }
     }
   }
@@ -848,17 +201,16 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentK_kernel(const
   float *ldsMeta = ldsB + 2 * PD, *ldsC = ldsMeta + kMT * kMS;
   int *s_ok = reinterpret_cast<int *>(ldsC + 48);
   const int tid = threadIdx.x, q = tid & 15;
-  if (tid < 42) ldsC[tid] = p.cf[tid];
+  coef_to_lds(ldsC, p.cf, 42, tid);
   const int act = ACT >= 0 ? ACT : p.act;
-  float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
-  if (tid < PD) ldsB[tid] = p.b1 ? p.b1[tid] : 0.f;
-  else if (tid < 2 * PD) ldsB[tid] = p.b2 ? p.b2[tid - PD] : 0.f;
-  if (tid < PG::LPR) Xh4[kHaloCap * PG::LPR + tid] = f4_zero();
+  biases_to_lds(ldsB, p.b1, p.b2, tid);
+  zero_halo_row(ldsXh, tid < PG::LPR, tid & 15);
   if (tid == 0) *s_ok = 1;
   const int W = p.pair_wgs, K = min(p.k_tiles, kMT);
   const int t0 = xcd_tile(blockIdx.x, W);
   const unsigned rowb = (unsigned)(p.row_elems * sizeof(float));
-  for (int s = 0; s < K && t0 + s * W < p.m.n_tiles; ++s) tile_tables_to_lds<true>(p.m, t0 + s * W, ldsMeta + s * kMS);
+  tile_round_tables<true>(p.m, t0, W, K, ldsMeta);
+  const int KT = tile_round_count(p.m, t0, W, K);   // tiles this workgroup really holds
   __syncthreads();
   const float4 bias1 = reinterpret_cast<const float4 *>(ldsB)[q], bias2 = reinterpret_cast<const float4 *>(ldsB + PD)[q];
   bool ok = true;
@@ -877,7 +229,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentK_kernel(const
           if (tile >= p.m.n_tiles) break;   // uniform
           TileCtx c;
           tile_ctx_from_lds<true>(c, tile, ldsMeta + s * kMS);
-          const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
+          const unsigned own = own_row_offset(c);
           if (!tile_wait(p.m, c, ph, s_ok)) { ok = false; break; }
           halo_fill_all(c, X, ldsXh);
           // own rows of the state, in flight under the gather and the product: 0 = u, 1 + j = k_j (zero at launch, like the
@@ -893,22 +245,19 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentK_kernel(const
           wait_vmcnt0();
           __syncthreads();   // halo rows landed (and the phase's W is in LDS)
           float4 acc = f4_scale(c.ci, tile_aggregate_weighted(c, ldsXh));
-          *reinterpret_cast<float4 *>(&ldsT[c.grp * PG::TS + 4 * c.q]) = acc;
+          tile_row_store(ldsT, c, acc);
           if (TAPE && c.valid) st4_stream_g(p.tape + ev * p.row_elems, own, acc);
           __syncthreads();
           mfma_rows_times_bt<PD>(ldsT, ldsW, ldsZ, c.wave_u, c.lane);
           __syncthreads();
-          const float4 z = f4_add(*reinterpret_cast<const float4 *>(&ldsZ[c.grp * PG::TS + 4 * c.q]), layer == 0 ? bias1 : bias2);
-          const uint8_t sign_bits = (uint8_t)((z.x > 0.f ? 1 : 0) | (z.y > 0.f ? 2 : 0) | (z.z > 0.f ? 4 : 0) | (z.w > 0.f ? 8 : 0));
-          const float4 yv = f4_sel(c.valid, f4_scale(c.ci, f4_act(act, z)), f4_zero());
+          const float4 z = fwd_preact(ldsZ, c, layer == 0 ? bias1 : bias2);
+          const uint8_t sign_bits = relu_sign_bits(z);
+          const float4 yv = fwd_output(c, act, z);
           if (layer == 0) {
             if (c.valid) store_sc1(p.bufB, own, yv);
           } else {
             const float4 k0 = i == 0 ? yv : sk0, k1 = i == 1 ? yv : sk1, k2 = i == 2 ? yv : sk2, k3 = i == 3 ? yv : sk3, k4 = i == 4 ? yv : sk4;   // k_i is yv itself
-            float4 v = f4_scale(ldsC[36 + i], yv);
-            v = f4_fma(1.0f, su, v);
-            v = f4_fma(ldsC[i * 6 + 0], k0, v); v = f4_fma(ldsC[i * 6 + 1], k1, v); v = f4_fma(ldsC[i * 6 + 2], k2, v);
-            v = f4_fma(ldsC[i * 6 + 3], k3, v); v = f4_fma(ldsC[i * 6 + 4], k4, v);
+            const float4 v = rk_combine<false>(RkCoefInPlace{ldsC, i}, i, yv, su, k0, k1, k2, k3, k4);
             if (c.valid) {
               if (i < p.S - 1) st4_g(p.state, own + (unsigned)(1 + i) * rowb, yv);   // (the last stage's derivative is combined here and never read again)
               if (i == p.S - 1) st4_g(p.state, own, v);
@@ -925,12 +274,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentK_kernel(const
   }
   if (!ok) {   // a wait was aborted: poison every row this workgroup owns
     __syncthreads();
-    for (int s = 0; s < K; ++s) {
-      const int tile = t0 + s * W;
-      if (tile >= p.m.n_tiles) break;
-      const int4 sc = p.m.sched[(size_t)tile * kTM + (tid >> 4)];
-      if (sc.x >= 0) st4_g(p.u_out, (unsigned)sc.x * (unsigned)(PD * 4) + (unsigned)(q * 16), f4_nan());
-    }
+    poison_tile_rounds(p.m, p.u_out, t0, W, KT, tid);
   }
 }
 
@@ -960,18 +304,16 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
   int *s_ok = reinterpret_cast<int *>(ldsC + 48), *s_pre = s_ok + 1;
   const int tid = threadIdx.x, q = tid & 15;
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  if (tid < 42) ldsC[tid] = p.cf[tid];
+  coef_to_lds(ldsC, p.cf, 42, tid);
   const int act = ACT >= 0 ? ACT : p.act;
-  float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
-  if (tid < PD) ldsB[tid] = p.b1 ? p.b1[tid] : 0.f;
-  else if (tid < 2 * PD) ldsB[tid] = p.b2 ? p.b2[tid - PD] : 0.f;
-  if (tid < PG::LPR) Xh4[kHaloCap * PG::LPR + tid] = f4_zero();
+  biases_to_lds(ldsB, p.b1, p.b2, tid);
+  zero_halo_row(ldsXh, tid < PG::LPR, tid & 15);
   if (tid == 0) *s_ok = 1, *s_pre = 0;
   const int W = p.pair_wgs, K = min(p.k_tiles, kMT);
   const int t0 = xcd_tile(blockIdx.x, W);
   const unsigned rowb = (unsigned)(p.row_elems * sizeof(float));
-  int KT = 0;   // tiles this workgroup really holds (the last workgroups of a ragged grid hold one fewer)
-  for (int s = 0; s < K && t0 + s * W < p.m.n_tiles; ++s, ++KT) tile_tables_to_lds<false>(p.m, t0 + s * W, ldsMeta + s * kMS);
+  tile_round_tables<false>(p.m, t0, W, K, ldsMeta);
+  const int KT = tile_round_count(p.m, t0, W, K);   // tiles this workgroup really holds
   __syncthreads();
   const float4 bias1 = reinterpret_cast<const float4 *>(ldsB)[q], bias2 = reinterpret_cast<const float4 *>(ldsB + PD)[q];
   // no weight reload per phase (the tile-round kernel stages the phase's W^T in LDS every phase: ~1.2 k cycles per turn at four
@@ -1010,7 +352,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
           const int tile = t0 + s * W;
           TileCtx c;
           tile_ctx_from_lds<false>(c, tile, ldsMeta + s * kMS);
-          const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
+          const unsigned own = own_row_offset(c);
           // ---- T0
           [[maybe_unused]] const int turn = (ph - 1) * KT + s + 1;   // (stamps: one record per turn)
           NGPDE_PHASE_STAMP(p.m.stamps, turn, 0);
@@ -1045,7 +387,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
           }
           // ---- T1
           float4 acc = f4_scale(c.ci, tile_aggregate_lean(c, ldsXh));
-          *reinterpret_cast<float4 *>(&ldsT[c.grp * PG::TS + 4 * c.q]) = acc;
+          tile_row_store(ldsT, c, acc);
           if (TAPE && c.valid) st4_stream_g(p.tape + ev * p.row_elems, own, acc);
           if (wave_u == 0) {
             const unsigned need = (unsigned)(nph - 1);
@@ -1060,7 +402,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
           unsigned ownn = 0;
           if (pre) {
             tile_ctx_from_lds<false>(cn, t0 + ns * W, nmeta);
-            ownn = (unsigned)cn.node * (unsigned)(PD * 4) + (unsigned)(cn.q * 16);
+            ownn = own_row_offset(cn);
             halo_fill_all(cn, nX, ldsXh);
           }
           NGPDE_PHASE_STAMP(p.m.stamps, turn, 4);
@@ -1069,19 +411,15 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
           __syncthreads();
           NGPDE_PHASE_STAMP(p.m.stamps, turn, 5);
           // ---- T5
-          const float4 z = f4_add(*reinterpret_cast<const float4 *>(&ldsZ[c.grp * PG::TS + 4 * c.q]), layer == 0 ? bias1 : bias2);
-          const float cself = ldsC[36 + i], cf0 = ldsC[i * 6 + 0], cf1 = ldsC[i * 6 + 1], cf2 = ldsC[i * 6 + 2], cf3 = ldsC[i * 6 + 3],
-                      cf4 = ldsC[i * 6 + 4];
-          const uint8_t sign_bits = (uint8_t)((z.x > 0.f ? 1 : 0) | (z.y > 0.f ? 2 : 0) | (z.z > 0.f ? 4 : 0) | (z.w > 0.f ? 8 : 0));
-          const float4 yv = f4_sel(c.valid, f4_scale(c.ci, f4_act(act, z)), f4_zero());
+          const float4 z = fwd_preact(ldsZ, c, layer == 0 ? bias1 : bias2);
+          const RkCoef cf = rk_coef(ldsC, i);   // (read here: every LDS read of the epilogue in front of a DMA that may go out)
+          const uint8_t sign_bits = relu_sign_bits(z);
+          const float4 yv = fwd_output(c, act, z);
           if (layer == 0) {
             if (c.valid) store_sc1(p.bufB, own, yv);
           } else {
             const float4 k0 = i == 0 ? yv : sk0, k1 = i == 1 ? yv : sk1, k2 = i == 2 ? yv : sk2, k3 = i == 3 ? yv : sk3, k4 = i == 4 ? yv : sk4;
-            float4 v = f4_scale(cself, yv);
-            v = f4_fma(1.0f, su, v);
-            v = f4_fma(cf0, k0, v); v = f4_fma(cf1, k1, v); v = f4_fma(cf2, k2, v);
-            v = f4_fma(cf3, k3, v); v = f4_fma(cf4, k4, v);
+            const float4 v = rk_combine<false>(cf, i, yv, su, k0, k1, k2, k3, k4);
             if (c.valid) {
               if (i < p.S - 1) st4_g(p.state, own + (unsigned)(1 + i) * rowb, yv);   // (the last stage's derivative is combined here and never read again)
               if (i == p.S - 1) st4_g(p.state, own, v);
@@ -1104,10 +442,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
   if (ok && pend_flags && tid == 0) __hip_atomic_store(pend_flags, (unsigned)pend_ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (!ok) {   // a wait was aborted: poison every row this workgroup owns
     __syncthreads();
-    for (int s = 0; s < KT; ++s) {
-      const int4 sc = p.m.sched[(size_t)(t0 + s * W) * kTM + (tid >> 4)];
-      if (sc.x >= 0) st4_g(p.u_out, (unsigned)sc.x * (unsigned)(PD * 4) + (unsigned)(q * 16), f4_nan());
-    }
+    poison_tile_rounds(p.m, p.u_out, t0, W, KT, tid);
   }
   if (tid == 0 && p.m.stats) p.m.stats[2 * t0] = n_ahead;
 }
@@ -1180,7 +515,7 @@ __device__ __forceinline__ bool fwd_slot_phase(const PFwdK &p, const TileCtx &c,
   NGPDE_PHASE_STAMP(p.m.stamps, ph, 2);
   // T1
   float4 acc = f4_scale(c.ci, tile_aggregate(c, sw, ldsXh));
-  *reinterpret_cast<float4 *>(&ldsT[c.grp * PG::TS + 4 * c.q]) = acc;
+  tile_row_store(ldsT, c, acc);
   const size_t ev = ev0 + (size_t)(n * p.S + i) * 2 + layer;
   if (TAPE && c.valid) st4_stream_g(p.tape + ev * p.row_elems, own, acc);
   // T2
@@ -1202,20 +537,14 @@ __device__ __forceinline__ bool fwd_slot_phase(const PFwdK &p, const TileCtx &c,
   NGPDE_PHASE_STAMP(p.m.stamps, ph, 4);
   // T5.  Every LDS read of the epilogue comes BEFORE a DMA is issued (see halo_fill_ahead)
   pre = *s_pre != 0;
-  const float4 z = f4_add(*reinterpret_cast<const float4 *>(&ldsZ[c.grp * PG::TS + 4 * c.q]), reinterpret_cast<const float4 *>(ldsBias)[c.q]);
-  const float cself = ldsC[36 + i], cf0 = ldsC[i * 6 + 0], cf1 = ldsC[i * 6 + 1], cf2 = ldsC[i * 6 + 2], cf3 = ldsC[i * 6 + 3],
-              cf4 = ldsC[i * 6 + 4];
+  const float4 z = f4_add(tile_row(ldsZ, c), reinterpret_cast<const float4 *>(ldsBias)[c.q]);   // (fwd_preact with the bias row read from LDS, behind the product's)
+  const RkCoef cf = rk_coef(ldsC, i);
   if (pre) halo_fill_ahead(cn, nx.X, ldsXh, Snext.xown);
-  const uint8_t sign_bits = (uint8_t)((z.x > 0.f ? 1 : 0) | (z.y > 0.f ? 2 : 0) | (z.z > 0.f ? 4 : 0) | (z.w > 0.f ? 8 : 0));
-  const float4 yv = f4_sel(c.valid, f4_scale(c.ci, f4_act(act, z)), f4_zero());
+  const uint8_t sign_bits = relu_sign_bits(z);
+  const float4 yv = fwd_output(c, act, z);
   float4 v = f4_zero();
-  if (layer != 0) {
-    v = f4_scale(cself, yv);
-    v = f4_fma(1.0f, S.u, v);
-    // (k_i = yv enters with the zero weight cf[i][i], as in node_fwd_persistent_kernel, where it is assigned first)
-    v = f4_fma(cf0, f4_sel(i == 0, yv, S.k0), v); v = f4_fma(cf1, f4_sel(i == 1, yv, S.k1), v); v = f4_fma(cf2, f4_sel(i == 2, yv, S.k2), v);
-    v = f4_fma(cf3, f4_sel(i == 3, yv, S.k3), v); v = f4_fma(cf4, f4_sel(i == 4, yv, S.k4), v);
-  }
+  // (k_i = yv enters with the zero weight cf[i][i], as in node_fwd_persistent_kernel, where it is assigned first)
+  if (layer != 0) v = rk_combine<true>(cf, i, yv, S.u, S.k0, S.k1, S.k2, S.k3, S.k4);
   if (layer == 0) {
     if (c.valid) store_sc1(bufB, own, yv);
     S.xown = yv;
@@ -1245,17 +574,15 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistent2_kernel(const
   const bool has1 = !PAIR || c.tile + p.pair_wgs < p.m.n_tiles;   // (PAIR: an odd tile count leaves the last workgroups one tile)
   if (PAIR) tile_ctx_init(p.m, c1s, ldsMeta + kMetaF, has1 ? c.tile + p.pair_wgs : c.tile);
   const TileCtx &c1 = PAIR ? c1s : c;
-  if (c.tid < 42) ldsC[c.tid] = p.cf[c.tid];
+  coef_to_lds(ldsC, p.cf, 42, c.tid);
   const int act = ACT >= 0 ? ACT : p.act;
-  float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
   load_weight_lds(p.w1, ldsW1, c.tid, true);
   load_weight_lds(p.w2, ldsW2, c.tid, true);
-  if (c.tid < PD) ldsB[c.tid] = p.b1 ? p.b1[c.tid] : 0.f;
-  else if (c.tid < 2 * PD) ldsB[c.tid] = p.b2 ? p.b2[c.tid - PD] : 0.f;
-  if (c.grp == 0) Xh4[kHaloCap * PG::LPR + c.q] = f4_zero();
+  biases_to_lds(ldsB, p.b1, p.b2, c.tid);
+  zero_halo_row(ldsXh, c.grp == 0, c.q);
   if (c.tid == 0) *s_ok = 1, *s_pre = 0;
-  const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
-  const unsigned own1 = (unsigned)c1.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
+  const unsigned own = own_row_offset(c);
+  const unsigned own1 = row_offset(c1.node, c.q);
   __syncthreads();
   bool ok = true;
   int ph = 0;   // both slots run the same phase numbers; the count runs on across the pairs
@@ -1307,10 +634,8 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistent2_kernel(const
     if (PAIR) break;   // one member
   }
   if (!ok) {   // an aborted solve poisons every member's output
-    for (int mb = 0; mb < p.n_members; ++mb) {
-      if (c.valid) st4_g(p.u_out + (size_t)mb * p.row_elems, own, f4_nan());
-      if (PAIR && has1 && c1.valid) st4_g(p.u_out + (size_t)mb * p.row_elems, own1, f4_nan());
-    }
+    poison_members(p.u_out, p.n_members, p.row_elems, c.valid, own);
+    poison_members(p.u_out, p.n_members, p.row_elems, PAIR && has1 && c1.valid, own1);
   }
   if (c.tid == 0 && p.m.stats) p.m.stats[2 * c.tile] = n_ahead;
 }
@@ -1318,24 +643,6 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistent2_kernel(const
 // ---------------------------------------------------------------------------------------------------------------------
 // discrete adjoint
 // ---------------------------------------------------------------------------------------------------------------------
-struct PBwdK {
-  TileMeta m;          // lists by SOURCE
-  int n_steps, S, n_members, act;
-  const float *ztape;  // pre-activations (activations other than relu), or null
-  float *lam;          // [n_members][N][64] in: dL/du~(T) (adjoint seed ./ c); out: dL/du~0
-  float *g1, *g2;      // exchanged arrays: c .* (dZ1 W1^T), c .* (dZ2 W2^T)
-  const float *w1, *w2;
-  const float *tape;
-  const uint8_t *masks;
-  size_t row_elems, mask_bytes;
-  float *slab_dw1, *slab_db1, *slab_dw2, *slab_db2;   // [n_tiles][...] written ONCE, at the end
-  int pair_wgs;        // tile-pair mode (PAIR): the grid; workgroup b holds tiles t and t + pair_wgs of ONE member
-  int k_tiles;         // tile-round mode (node_bwd_persistentK_kernel): k_tiles tiles per workgroup, state in lam / ubar (zero at launch)
-  size_t flag_stride;  // two-slot kernel: slot s uses g1 / g2 + s * row_elems, the flag words m.flags + s * flag_stride and
-  float *ubar;         // the stage-adjoint scratch ubar + s * 5 * row_elems ([slot][5][N][64])
-  const float *cb;     // device table [6 + 36 + 6], copied to LDS: cb[j] = dt * b[j]; cb[6 + i * 6 + j], j > i >= 1: dt * a[j][i-1], the
-                       // weight of U-bar_j in K-bar_{i-1}, 0 elsewhere; cb[42 + i] = dt * a[i][i-1], the weight of U-bar_i itself
-};
 
 // ACT = NGPDE_ACT_RELU: relu' from the forward launch's sign bits; ACT = -1: any activation (p.act), act'(z) from the saved
 // pre-activations (one more tape row per phase)
@@ -1357,7 +664,7 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
   typename std::conditional<HUB, HubCtx, TileCtx>::type c;
   if constexpr (HUB) hub_ctx_init(p.m, c, ldsMeta);
   else tile_ctx_init(p.m, c, ldsMeta);
-  if (c.tid < 48) ldsC[c.tid] = p.cb[c.tid];
+  coef_to_lds(ldsC, p.cb, 48, c.tid);
   float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
   if constexpr (WGT) {
     reinterpret_cast<float2 *>(ldsSW)[c.tid] = reinterpret_cast<const float2 *>(p.m.slot_w + (size_t)c.tile * kSlotWF)[c.tid];
@@ -1374,10 +681,9 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
     load_weight_lds(p.w1, ldsW1, c.tid, false);
   }
   load_weight_lds(p.w2, ldsW2, c.tid, false);
-  if (!HUB && c.grp == 0) Xh4[kHaloCap * PG::LPR + c.q] = f4_zero();
+  if (!HUB) zero_halo_row(ldsXh, c.grp == 0, c.q);
   if (c.tid == 0) *s_ok = 1;
-  const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
-  constexpr int NT = PG::CT * PG::CT;
+  const unsigned own = own_row_offset(c);
   f32x4 dw1[PG::DWT], dw2[PG::DWT];
 #pragma unroll
   for (int mm = 0; mm < PG::DWT; ++mm) dw1[mm] = dw2[mm] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1409,26 +715,19 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
   // products, which then waits for the tape rows.)
   unsigned f_next = 0;
   auto dense = [&](int ph, const float *ldsW, f32x4 (&dwl)[PG::DWT], float &dbl, float4 kbar, Aux mk, float4 xrow, float *gout, bool pf, size_t ev_n) {
-    kbar = f4_scale(c.ci, kbar);
-    float4 dz;
-    if constexpr (RELU) {
-      dz = c.valid ? make_float4((mk & 1u) ? kbar.x : 0.f, (mk & 2u) ? kbar.y : 0.f, (mk & 4u) ? kbar.z : 0.f, (mk & 8u) ? kbar.w : 0.f)
-                   : f4_zero();
-    } else {
-      dz = f4_sel(c.valid, f4_mul(kbar, f4_dact(p.act, mk)), f4_zero());
-    }
-    *reinterpret_cast<float4 *>(&ldsDZ[c.grp * PG::TS + 4 * c.q]) = dz;
+    const float4 dz = adjoint_dz<RELU>(c, p.act, kbar, mk);
+    tile_row_store(ldsDZ, c, dz);
     __syncthreads();
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 3);
     if (WGT && ldsW == ldsW1) mfma_rows_times_bswz64(ldsDZ, ldsW, ldsG, c.wave_u, c.lane);   // (layer 1 of a weighted graph: the unpadded, swizzled W1)
     else mfma_rows_times_bt<PD>(ldsDZ, ldsW, ldsG, c.wave_u, c.lane);
     __syncthreads();
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 4);
-    const float4 gv = f4_sel(c.valid, f4_scale(c.ci, *reinterpret_cast<const float4 *>(&ldsG[c.grp * PG::TS + 4 * c.q])), f4_zero());
+    const float4 gv = adjoint_g_row(ldsG, c);
     if (c.valid) store_sc1(gout, own, gv);
     // the tape row for the parameter-gradient products, which run behind the publish: written under the drain of the row stores, in
     // front of the publish's barrier (its readers of the phase before are two barriers back)
-    *reinterpret_cast<float4 *>(&ldsX[c.grp * PG::TS + 4 * c.q]) = f4_sel(c.valid, xrow, f4_zero());
+    adjoint_x_store(ldsX, c, xrow);
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 5);
     tile_publish(p.m, c, ph);
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 6);
@@ -1440,37 +739,8 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
       mk_n = mask_of(ev_n);
       xrow_n = tape_row(ev_n);
     }
-    // The parameter-gradient products run AFTER the rows are published: nobody waits for them, so they fill the time the
-    // neighbours need to see the flag and this tile needs to see theirs.  (The operand tiles stay intact until the next
-    // phase's dense half, two barriers away.)
-    // dWt[i][o] += sum_n A[n][i] dZ[n][o] over the tile's 32 rows
-    const int i16 = c.lane & 15, kq = c.lane >> 4;
-#pragma unroll
-    for (int mm = 0; mm < PG::DWT; ++mm) {
-      const int tt = c.wave_u + PG::WAVES * mm;
-      if (tt < NT) {   // wave-uniform
-        const int mt = tt / PG::CT, nt = tt % PG::CT;
-#pragma unroll
-        for (int kh = 0; kh < 2; ++kh) {   // two halves of the 32-row contraction: 8 operand registers live instead of 16
-          float a[kTM / 8], b[kTM / 8];
-#pragma unroll
-          for (int ks = 0; ks < kTM / 8; ++ks) {
-            a[ks] = ldsX[(4 * (ks + 4 * kh) + kq) * PG::TS + mt * 16 + i16];
-            b[ks] = ldsDZ[(4 * (ks + 4 * kh) + kq) * PG::TS + nt * 16 + i16];
-          }
-#pragma unroll
-          for (int ks = 0; ks < kTM / 8; ++ks) dwl[mm] = mfma16(a[ks], b[ks], dwl[mm]);
-        }
-      }
-    }
-    {
-      float s = 0.f;
-#pragma unroll
-      for (int nn = dbpart; nn < kTM; nn += PG::DBP) s += ldsDZ[nn * PG::TS + dbc];
-#pragma unroll
-      for (int o = 1; o < PG::DBP; o <<= 1) s += __shfl_xor(s, o);
-      dbl += s;
-    }
+    // behind the publish (the operand tiles stay intact until the next phase's dense half, two barriers away)
+    param_grad_products(ldsX, ldsDZ, c.wave_u, c.lane, dbc, dbpart, dwl, dbl);
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 7);
   };
 
@@ -1485,7 +755,7 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
               // g2 was last read two phases ago, so no wait either)
     ++ph;
     const size_t ev = ev0 + (size_t)((p.n_steps - 1) * S + (S - 1)) * 2 + 1;
-    dense(ph, ldsW2, dw2, db2, f4_scale(ldsC[S - 1], lam), mask_of(ev), tape_row(ev), p.g2, true,
+    dense(ph, ldsW2, dw2, db2, adjoint_kbar_last(ldsC, S, lam), mask_of(ev), tape_row(ev), p.g2, true,
           ev0 + (size_t)((p.n_steps - 1) * S + (S - 1)) * 2);   // (next: layer 1 of the last stage of the last step)
   }
   for (int n = p.n_steps - 1; n >= 0 && ok; --n) {
@@ -1580,21 +850,13 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
         }
         float4 kbar;
         if (i >= 1) {
-          // same order as the replayed plan: coef_self * t, then lambda, then U-bar_{i+1} ..
           ub1 = f4_sel(i == 1, t, ub1); ub2 = f4_sel(i == 2, t, ub2); ub3 = f4_sel(i == 3, t, ub3);
           ub4 = f4_sel(i == 4, t, ub4); ub5 = f4_sel(i == 5, t, ub5);
-          float4 v = f4_scale(ldsC[42 + i], t);
-          v = f4_fma(ldsC[i - 1], lam, v);
-          v = f4_fma(ldsC[6 + i * 6 + 2], ub2, v); v = f4_fma(ldsC[6 + i * 6 + 3], ub3, v);   // zero weights add an exact zero
-          v = f4_fma(ldsC[6 + i * 6 + 4], ub4, v); v = f4_fma(ldsC[6 + i * 6 + 5], ub5, v);
-          kbar = v;
+          kbar = adjoint_kbar_stage(ldsC, i, t, lam, ub2, ub3, ub4, ub5);
         } else {
-          float4 v = f4_scale(1.0f, t);
-          v = f4_fma(1.0f, lam, v);
-          v = f4_fma(1.0f, ub1, v); v = f4_fma(1.0f, ub2, v); v = f4_fma(1.0f, ub3, v);   // stage adjoints beyond S stay zero
-          v = f4_fma(1.0f, ub4, v); v = f4_fma(1.0f, ub5, v);
+          const float4 v = adjoint_lambda_update(t, lam, ub1, ub2, ub3, ub4, ub5);
           lam = v;
-          kbar = f4_scale(ldsC[S - 1], v);
+          kbar = adjoint_kbar_last(ldsC, S, v);
         }
         if (last) break;   // (this phase writes nothing other tiles read: no flag; the next member's first phase publishes ph + 1)
         dense(ph, ldsW2, dw2, db2, kbar, mk, xrow, p.g2, true, ev_next);
@@ -1604,18 +866,8 @@ __global__ __launch_bounds__(kThreads, HUB ? 2 : 4) void node_bwd_persistent_ker
   if (c.valid) st4_g(lam_g, own, f4_sel(ok, lam, f4_nan()));
   }
   // the tile's contribution to the parameter gradients: one slab per tile, summed by reduce_slabs_kernel
-  const float bad = __int_as_float(0x7fc00000);
-  auto write_slab = [&](const f32x4 (&dwl)[PG::DWT], float dbl, float *slab_dw, float *slab_db) {
-    float4 *slab4 = reinterpret_cast<float4 *>(slab_dw + (size_t)blockIdx.x * PD * PD);
-#pragma unroll
-    for (int mm = 0; mm < PG::DWT; ++mm) {
-      const int tt = c.wave_u + PG::WAVES * mm;
-      if (tt < NT) slab4[tt * 64 + c.lane] = f4_sel(ok, make_float4(dwl[mm][0], dwl[mm][1], dwl[mm][2], dwl[mm][3]), f4_nan());
-    }
-    if (dbpart == 0) slab_db[(size_t)blockIdx.x * PD + dbc] = ok ? dbl : bad;
-  };
-  write_slab(dw1, db1, p.slab_dw1, p.slab_db1);
-  write_slab(dw2, db2, p.slab_dw2, p.slab_db2);
+  write_slab(dw1, db1, p.slab_dw1, p.slab_db1, c.wave_u, c.lane, dbc, dbpart, ok);
+  write_slab(dw2, db2, p.slab_dw2, p.slab_db2, c.wave_u, c.lane, dbc, dbpart, ok);
 }
 
 
@@ -1654,15 +906,13 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
   const bool has1 = !PAIR || c.tile + p.pair_wgs < p.m.n_tiles;
   if (PAIR) tile_ctx_init(p.m, c1s, ldsMeta + kMetaF, has1 ? c.tile + p.pair_wgs : c.tile);
   const TileCtx &c1 = PAIR ? c1s : c;
-  if (c.tid < 48) ldsC[c.tid] = p.cb[c.tid];
-  float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
+  coef_to_lds(ldsC, p.cb, 48, c.tid);
   load_weight_lds(p.w1, ldsW1, c.tid, false);
   load_weight_lds(p.w2, ldsW2, c.tid, false);
-  if (c.grp == 0) Xh4[kHaloCap * PG::LPR + c.q] = f4_zero();
+  zero_halo_row(ldsXh, c.grp == 0, c.q);
   if (c.tid == 0) *s_ok = 1, *s_pre = 0;
-  const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
-  const unsigned own1 = (unsigned)c1.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
-  constexpr int NT = PG::CT * PG::CT;
+  const unsigned own = own_row_offset(c);
+  const unsigned own1 = row_offset(c1.node, c.q);
   f32x4 dw1[PG::DWT], dw2[PG::DWT];
 #pragma unroll
   for (int mm = 0; mm < PG::DWT; ++mm) dw1[mm] = dw2[mm] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1689,34 +939,10 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
     pend_flags = nullptr;
   };
 
-  // dWt[i][o] += sum_n A[n][i] dZ[n][o] over the tile's 32 rows; db += column sums of dZ.  The operand tiles are __restrict__ so that
-  // these LDS reads do not wait for a DMA issued just before them into the halo region (halo_fill_ahead)
+  // the operand tiles are __restrict__ so that the products' LDS reads do not wait for a DMA issued just before them into the halo
+  // region (halo_fill_ahead); wave and lane are the kernel's own, whichever slot's context the dense half runs with
   auto dw_products = [&](const float *__restrict__ tX, const float *__restrict__ tDZ, f32x4 (&dwl)[PG::DWT], float &dbl) {
-    const int i16 = c.lane & 15, kq = c.lane >> 4;
-#pragma unroll
-    for (int mm = 0; mm < PG::DWT; ++mm) {
-      const int tt = c.wave_u + PG::WAVES * mm;
-      if (tt < NT) {   // wave-uniform
-        const int mt = tt / PG::CT, nt = tt % PG::CT;
-#pragma unroll
-        for (int kh = 0; kh < 2; ++kh) {   // two halves of the 32-row contraction: 8 operand registers live instead of 16
-          float a[kTM / 8], b[kTM / 8];
-#pragma unroll
-          for (int ks = 0; ks < kTM / 8; ++ks) {
-            a[ks] = tX[(4 * (ks + 4 * kh) + kq) * PG::TS + mt * 16 + i16];
-            b[ks] = tDZ[(4 * (ks + 4 * kh) + kq) * PG::TS + nt * 16 + i16];
-          }
-#pragma unroll
-          for (int ks = 0; ks < kTM / 8; ++ks) dwl[mm] = mfma16(a[ks], b[ks], dwl[mm]);
-        }
-      }
-    }
-    float sdb = 0.f;
-#pragma unroll
-    for (int nn = dbpart; nn < kTM; nn += PG::DBP) sdb += tDZ[nn * PG::TS + dbc];
-#pragma unroll
-    for (int o = 1; o < PG::DBP; o <<= 1) sdb += __shfl_xor(sdb, o);
-    dbl += sdb;
+    param_grad_products(tX, tDZ, c.wave_u, c.lane, dbc, dbpart, dwl, dbl);
   };
 
   // the dense half of a slot-phase (T1's tail .. T5): dL/dy = c .* K-bar, relu' by the sign bits, G = dZ W^T -> c .* G stored for the
@@ -1725,12 +951,9 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
   // (c, own: this slot's tile; cn, ownn: the next slot-phase's)
   auto dense = [&](const TileCtx &c, const TileCtx &cn, unsigned own, unsigned ownn, unsigned *flags, int ph, const float *ldsW,
                    f32x4 (&dwl)[PG::DWT], float &dbl, float4 kbar, unsigned mk, float4 xrow, float *gout, const BNext &nx) {
-    kbar = f4_scale(c.ci, kbar);
-    const float4 dz = c.valid ? make_float4((mk & 1u) ? kbar.x : 0.f, (mk & 2u) ? kbar.y : 0.f, (mk & 4u) ? kbar.z : 0.f,
-                                            (mk & 8u) ? kbar.w : 0.f)
-                              : f4_zero();
-    *reinterpret_cast<float4 *>(&ldsDZ[c.grp * PG::TS + 4 * c.q]) = dz;
-    *reinterpret_cast<float4 *>(&ldsX[c.grp * PG::TS + 4 * c.q]) = f4_sel(c.valid, xrow, f4_zero());
+    const float4 dz = adjoint_dz<true>(c, NGPDE_ACT_RELU, kbar, mk);
+    tile_row_store(ldsDZ, c, dz);
+    adjoint_x_store(ldsX, c, xrow);
     __syncthreads();   // T2
     if (nx.tape) {     // the next slot-phase's tape row and sign bits: a slot-phase ahead, so that they are there at its T0
       pf_mk = ldu8_g(p.masks + nx.ev * p.mask_bytes + (size_t)cn.tile * kThreads, (unsigned)c.tid);
@@ -1761,7 +984,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
       pre = false;
     }
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 4);
-    const float4 gv = f4_sel(c.valid, f4_scale(c.ci, *reinterpret_cast<const float4 *>(&ldsG[c.grp * PG::TS + 4 * c.q])), f4_zero());
+    const float4 gv = adjoint_g_row(ldsG, c);
     if (pre) {   // uniform
       __syncthreads();   // every thread has read its row of G: the region is the halo again
       halo_fill_all(cn, nx.X, ldsXh);
@@ -1829,18 +1052,11 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
     float4 kbar;
     if (i >= 1) {
       if (c.valid) st4_g(ubar, uo + (unsigned)(i - 1) * rowb, t);   // U-bar_i
-      float4 v = f4_scale(ldsC[42 + i], t);
-      v = f4_fma(ldsC[i - 1], lam, v);
-      v = f4_fma(ldsC[6 + i * 6 + 2], ub2, v); v = f4_fma(ldsC[6 + i * 6 + 3], ub3, v);
-      v = f4_fma(ldsC[6 + i * 6 + 4], ub4, v); v = f4_fma(ldsC[6 + i * 6 + 5], ub5, v);
-      kbar = v;
+      kbar = adjoint_kbar_stage(ldsC, i, t, lam, ub2, ub3, ub4, ub5);
     } else {
-      float4 v = f4_scale(1.0f, t);
-      v = f4_fma(1.0f, lam, v);
-      v = f4_fma(1.0f, ub1, v); v = f4_fma(1.0f, ub2, v); v = f4_fma(1.0f, ub3, v);
-      v = f4_fma(1.0f, ub4, v); v = f4_fma(1.0f, ub5, v);
+      const float4 v = adjoint_lambda_update(t, lam, ub1, ub2, ub3, ub4, ub5);
       if (c.valid) st4_g(lam_g, uo, v);   // lambda of the step before (the member's dL/du~0 at the end)
-      kbar = f4_scale(ldsC[S - 1], v);
+      kbar = adjoint_kbar_last(ldsC, S, v);
     }
     if (!last) dense(c, cn, own, ownn, flags, ph, ldsW2, dw2, db2, kbar, mk, xrow, g2, nx);
     else pre = false;
@@ -1870,7 +1086,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
         // before this one's is published -- only its tape row is fetched)
         nx.gather = false; nx.ph = ph + 1; nx.X = p.g2; nx.flags = flags0; nx.tape = !two; nx.ev = ev00 + e1_first;
         const float4 lam = f4_sel(c.valid, ld4_g(lam_g0, own), f4_zero());
-        dense(c, two ? c1 : c, own, two ? own1 : own, flags0, ph, ldsW2, dw2, db2, f4_scale(ldsC[S - 1], lam), mk, xrow, p.g2, nx);
+        dense(c, two ? c1 : c, own, two ? own1 : own, flags0, ph, ldsW2, dw2, db2, adjoint_kbar_last(ldsC, S, lam), mk, xrow, p.g2, nx);
         if (dead) ok = false;
       }
       if (two && ok) {
@@ -1879,7 +1095,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
         const float4 xrow = ld4_stream_g(p.tape + (ev01 + e) * p.row_elems, own1);
         nx.gather = true; nx.ph = ph + 1; nx.X = p.g2; nx.flags = flags0; nx.tape = true; nx.ev = ev00 + e1_first;
         const float4 lam = f4_sel(c1.valid, ld4_g(lam_g1, own1), f4_zero());
-        dense(c1, c, own1, own, flags1, ph, ldsW2, dw2, db2, f4_scale(ldsC[S - 1], lam), mk, xrow, p.g2 + goff1, nx);
+        dense(c1, c, own1, own, flags1, ph, ldsW2, dw2, db2, adjoint_kbar_last(ldsC, S, lam), mk, xrow, p.g2 + goff1, nx);
         if (dead) ok = false;
       }
     }
@@ -1916,23 +1132,11 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
     if (PAIR) break;   // one member
   }
   if (!ok) {
-    for (int mb = 0; mb < p.n_members; ++mb) {
-      if (c.valid) st4_g(p.lam + (size_t)mb * p.row_elems, own, f4_nan());
-      if (PAIR && has1 && c1.valid) st4_g(p.lam + (size_t)mb * p.row_elems, own1, f4_nan());
-    }
+    poison_members(p.lam, p.n_members, p.row_elems, c.valid, own);
+    poison_members(p.lam, p.n_members, p.row_elems, PAIR && has1 && c1.valid, own1);
   }
-  const float bad = __int_as_float(0x7fc00000);
-  auto write_slab = [&](const f32x4 (&dwl)[PG::DWT], float dbl, float *slab_dw, float *slab_db) {
-    float4 *slab4 = reinterpret_cast<float4 *>(slab_dw + (size_t)blockIdx.x * PD * PD);
-#pragma unroll
-    for (int mm = 0; mm < PG::DWT; ++mm) {
-      const int tt = c.wave_u + PG::WAVES * mm;
-      if (tt < NT) slab4[tt * 64 + c.lane] = f4_sel(ok, make_float4(dwl[mm][0], dwl[mm][1], dwl[mm][2], dwl[mm][3]), f4_nan());
-    }
-    if (dbpart == 0) slab_db[(size_t)blockIdx.x * PD + dbc] = ok ? dbl : bad;
-  };
-  write_slab(dw1, db1, p.slab_dw1, p.slab_db1);
-  write_slab(dw2, db2, p.slab_dw2, p.slab_db2);
+  write_slab(dw1, db1, p.slab_dw1, p.slab_db1, c.wave_u, c.lane, dbc, dbpart, ok);
+  write_slab(dw2, db2, p.slab_dw2, p.slab_db2, c.wave_u, c.lane, dbc, dbpart, ok);
   if (c.tid == 0 && p.m.stats) p.m.stats[2 * c.tile + 1] = n_ahead;
 }
 
@@ -1954,11 +1158,9 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
   int *s_ok = reinterpret_cast<int *>(ldsC + 48);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (tid < 48) ldsC[tid] = p.cb[tid];
-  float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
-  if (tid < PG::LPR) Xh4[kHaloCap * PG::LPR + tid] = f4_zero();
+  coef_to_lds(ldsC, p.cb, 48, tid);
+  zero_halo_row(ldsXh, tid < PG::LPR, tid & 15);
   if (tid == 0) *s_ok = 1;
-  constexpr int NT = PG::CT * PG::CT;
   f32x4 dw1[PG::DWT], dw2[PG::DWT];
 #pragma unroll
   for (int mm = 0; mm < PG::DWT; ++mm) dw1[mm] = dw2[mm] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1967,7 +1169,8 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
   const int S = p.S, W = p.pair_wgs, K = min(p.k_tiles, kMT);
   const int t0 = xcd_tile(blockIdx.x, W);
   const unsigned rowb = (unsigned)(p.row_elems * sizeof(float));
-  for (int s = 0; s < K && t0 + s * W < p.m.n_tiles; ++s) tile_tables_to_lds<true>(p.m, t0 + s * W, ldsMeta + s * kMS);
+  tile_round_tables<true>(p.m, t0, W, K, ldsMeta);
+  const int Kv = tile_round_count(p.m, t0, W, K);   // tiles this workgroup really holds
   __syncthreads();
 
   // the dense half of a turn (node_bwd_persistent_kernel's, with the tile context as an argument)
@@ -1979,61 +1182,26 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
   // latency: a wave's loads return in order.)
   Aux mk_n{};
   float4 xrow_n = f4_zero();
-  int Kv = 0;
-  for (int s = 0; s < K && t0 + s * W < p.m.n_tiles; ++s) Kv = s + 1;
   auto fetch = [&](size_t ev, int s) {
     const int node = max(reinterpret_cast<const int4 *>(ldsMeta + s * kMS + kMetaF)[tid >> 4].x, 0);
-    const unsigned own = (unsigned)node * (unsigned)(PD * 4) + (unsigned)((tid & 15) * 16);
+    const unsigned own = row_offset(node, tid & 15);
     if constexpr (RELU) mk_n = ldu8_g(p.masks + ev * p.mask_bytes + (size_t)(t0 + s * W) * kThreads, (unsigned)tid);
     else mk_n = ld4_stream_g(p.ztape + ev * p.row_elems, own);
     xrow_n = ld4_stream_g(p.tape + ev * p.row_elems, own);
   };
   auto dense = [&](const TileCtx &c, unsigned own, int ph, f32x4 (&dwl)[PG::DWT], float &dbl, float4 kbar, Aux mk, float4 xrow, float *gout,
                    bool pf, size_t ev_n, int s_n) {
-    kbar = f4_scale(c.ci, kbar);
-    float4 dz;
-    if constexpr (RELU) {
-      dz = c.valid ? make_float4((mk & 1u) ? kbar.x : 0.f, (mk & 2u) ? kbar.y : 0.f, (mk & 4u) ? kbar.z : 0.f, (mk & 8u) ? kbar.w : 0.f)
-                   : f4_zero();
-    } else {
-      dz = f4_sel(c.valid, f4_mul(kbar, f4_dact(p.act, mk)), f4_zero());
-    }
-    *reinterpret_cast<float4 *>(&ldsDZ[c.grp * PG::TS + 4 * c.q]) = dz;
-    *reinterpret_cast<float4 *>(&ldsX[c.grp * PG::TS + 4 * c.q]) = f4_sel(c.valid, xrow, f4_zero());
+    const float4 dz = adjoint_dz<RELU>(c, p.act, kbar, mk);
+    tile_row_store(ldsDZ, c, dz);
+    adjoint_x_store(ldsX, c, xrow);
     if (pf) fetch(ev_n, s_n);
     __syncthreads();
     mfma_rows_times_bt<PD>(ldsDZ, ldsW, ldsG, c.wave_u, c.lane);
     __syncthreads();
-    const float4 gv = f4_sel(c.valid, f4_scale(c.ci, *reinterpret_cast<const float4 *>(&ldsG[c.grp * PG::TS + 4 * c.q])), f4_zero());
+    const float4 gv = adjoint_g_row(ldsG, c);
     if (c.valid) store_sc1(gout, own, gv);
     tile_publish(p.m, c, ph);
-    const int i16 = c.lane & 15, kq = c.lane >> 4;
-#pragma unroll
-    for (int mm = 0; mm < PG::DWT; ++mm) {
-      const int tt = c.wave_u + PG::WAVES * mm;
-      if (tt < NT) {   // wave-uniform
-        const int mt = tt / PG::CT, nt = tt % PG::CT;
-#pragma unroll
-        for (int kh = 0; kh < 2; ++kh) {
-          float a[kTM / 8], b[kTM / 8];
-#pragma unroll
-          for (int ks = 0; ks < kTM / 8; ++ks) {
-            a[ks] = ldsX[(4 * (ks + 4 * kh) + kq) * PG::TS + mt * 16 + i16];
-            b[ks] = ldsDZ[(4 * (ks + 4 * kh) + kq) * PG::TS + nt * 16 + i16];
-          }
-#pragma unroll
-          for (int ks = 0; ks < kTM / 8; ++ks) dwl[mm] = mfma16(a[ks], b[ks], dwl[mm]);
-        }
-      }
-    }
-    {
-      float s = 0.f;
-#pragma unroll
-      for (int nn = dbpart; nn < kTM; nn += PG::DBP) s += ldsDZ[nn * PG::TS + dbc];
-#pragma unroll
-      for (int o = 1; o < PG::DBP; o <<= 1) s += __shfl_xor(s, o);
-      dbl += s;
-    }
+    param_grad_products(ldsX, ldsDZ, c.wave_u, c.lane, dbc, dbpart, dwl, dbl);
   };
 
   bool ok = true;
@@ -2048,13 +1216,13 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
       if (tile >= p.m.n_tiles) break;
       TileCtx c;
       tile_ctx_from_lds<true>(c, tile, ldsMeta + s * kMS);
-      const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
+      const unsigned own = own_row_offset(c);
       __syncthreads();   // (the phase's W is in LDS; the previous turn's products are done with the operand tiles)
       const float4 lam = f4_sel(c.valid, ld4_g(p.lam, own), f4_zero());
       const Aux mk = mk_n;
       const float4 xrow = xrow_n;
       const bool more = s + 1 < Kv;   // next: the workgroup's next tile, or layer 1 of the last stage of the last step on its first one
-      dense(c, own, ph, dw2, db2, f4_scale(ldsC[S - 1], lam), mk, xrow, p.g2, true,
+      dense(c, own, ph, dw2, db2, adjoint_kbar_last(ldsC, S, lam), mk, xrow, p.g2, true,
             more ? ev : (size_t)((p.n_steps - 1) * S + (S - 1)) * 2, more ? s + 1 : 0);
     }
   }
@@ -2070,7 +1238,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
           if (tile >= p.m.n_tiles) break;
           TileCtx c;
           tile_ctx_from_lds<true>(c, tile, ldsMeta + s * kMS);
-          const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
+          const unsigned own = own_row_offset(c);
           const Aux mk = mk_n;
           const float4 xrow = xrow_n;
           if (!tile_wait(p.m, c, ph, s_ok)) { ok = false; break; }
@@ -2097,7 +1265,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
           if (tile >= p.m.n_tiles) break;
           TileCtx c;
           tile_ctx_from_lds<true>(c, tile, ldsMeta + s * kMS);
-          const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
+          const unsigned own = own_row_offset(c);
           const Aux mk = mk_n;        // (the last phase runs no dense half: nothing was asked for)
           const float4 xrow = xrow_n;
           if (!tile_wait(p.m, c, ph, s_ok)) { ok = false; break; }
@@ -2117,18 +1285,11 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
           float4 kbar;
           if (i >= 1) {
             if (c.valid) st4_g(p.ubar, own + (unsigned)(i - 1) * rowb, t);
-            float4 v = f4_scale(ldsC[42 + i], t);
-            v = f4_fma(ldsC[i - 1], lam, v);
-            v = f4_fma(ldsC[6 + i * 6 + 2], ub2, v); v = f4_fma(ldsC[6 + i * 6 + 3], ub3, v);
-            v = f4_fma(ldsC[6 + i * 6 + 4], ub4, v); v = f4_fma(ldsC[6 + i * 6 + 5], ub5, v);
-            kbar = v;
+            kbar = adjoint_kbar_stage(ldsC, i, t, lam, ub2, ub3, ub4, ub5);
           } else {
-            float4 v = f4_scale(1.0f, t);
-            v = f4_fma(1.0f, lam, v);
-            v = f4_fma(1.0f, ub1, v); v = f4_fma(1.0f, ub2, v); v = f4_fma(1.0f, ub3, v);
-            v = f4_fma(1.0f, ub4, v); v = f4_fma(1.0f, ub5, v);
+            const float4 v = adjoint_lambda_update(t, lam, ub1, ub2, ub3, ub4, ub5);
             if (c.valid) st4_g(p.lam, own, v);
-            kbar = f4_scale(ldsC[S - 1], v);
+            kbar = adjoint_kbar_last(ldsC, S, v);
           }
           if (!last) {   // next: the workgroup's next tile, or layer 1 of stage i - 1 / of the last stage of the step before
             const bool more = s + 1 < Kv;
@@ -2144,25 +1305,10 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentK_kernel(const
   }
   if (!ok) {
     __syncthreads();
-    for (int s = 0; s < K; ++s) {
-      const int tile = t0 + s * W;
-      if (tile >= p.m.n_tiles) break;
-      const int4 sc = p.m.sched[(size_t)tile * kTM + (tid >> 4)];
-      if (sc.x >= 0) st4_g(p.lam, (unsigned)sc.x * (unsigned)(PD * 4) + (unsigned)((tid & 15) * 16), f4_nan());
-    }
+    poison_tile_rounds(p.m, p.lam, t0, W, Kv, tid);
   }
-  const float bad = __int_as_float(0x7fc00000);
-  auto write_slab = [&](const f32x4 (&dwl)[PG::DWT], float dbl, float *slab_dw, float *slab_db) {
-    float4 *slab4 = reinterpret_cast<float4 *>(slab_dw + (size_t)blockIdx.x * PD * PD);
-#pragma unroll
-    for (int mm = 0; mm < PG::DWT; ++mm) {
-      const int tt = wave_u + PG::WAVES * mm;
-      if (tt < NT) slab4[tt * 64 + lane] = f4_sel(ok, make_float4(dwl[mm][0], dwl[mm][1], dwl[mm][2], dwl[mm][3]), f4_nan());
-    }
-    if (dbpart == 0) slab_db[(size_t)blockIdx.x * PD + dbc] = ok ? dbl : bad;
-  };
-  write_slab(dw1, db1, p.slab_dw1, p.slab_db1);
-  write_slab(dw2, db2, p.slab_dw2, p.slab_db2);
+  write_slab(dw1, db1, p.slab_dw1, p.slab_db1, wave_u, lane, dbc, dbpart, ok);
+  write_slab(dw2, db2, p.slab_dw2, p.slab_db2, wave_u, lane, dbc, dbpart, ok);
 }
 
 
@@ -2193,11 +1339,9 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
   int *s_ok = reinterpret_cast<int *>(ldsC + 48), *s_pre = s_ok + 1;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (tid < 48) ldsC[tid] = p.cb[tid];
-  float4 *Xh4 = reinterpret_cast<float4 *>(ldsXh);
-  if (tid < PG::LPR) Xh4[kHaloCap * PG::LPR + tid] = f4_zero();
+  coef_to_lds(ldsC, p.cb, 48, tid);
+  zero_halo_row(ldsXh, tid < PG::LPR, tid & 15);
   if (tid == 0) *s_ok = 1, *s_pre = 0;
-  constexpr int NT = PG::CT * PG::CT;
   f32x4 dw1[PG::DWT], dw2[PG::DWT];
 #pragma unroll
   for (int mm = 0; mm < PG::DWT; ++mm) dw1[mm] = dw2[mm] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -2206,8 +1350,8 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
   const int S = p.S, W = p.pair_wgs, K = min(p.k_tiles, kMT);
   const int t0 = xcd_tile(blockIdx.x, W);
   const unsigned rowb = (unsigned)(p.row_elems * sizeof(float));
-  int Kv = 0;   // tiles this workgroup really holds
-  for (int s = 0; s < K && t0 + s * W < p.m.n_tiles; ++s, ++Kv) tile_tables_to_lds<false>(p.m, t0 + s * W, ldsMeta + s * kMS);
+  tile_round_tables<false>(p.m, t0, W, K, ldsMeta);
+  const int Kv = tile_round_count(p.m, t0, W, K);   // tiles this workgroup really holds
   __syncthreads();
 
   bool pre = false, ok = true;
@@ -2224,7 +1368,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
   };
   auto fetch = [&](size_t ev, int s) {
     const int node = max(reinterpret_cast<const int4 *>(ldsMeta + s * kMS + kMetaF)[tid >> 4].x, 0);
-    const unsigned own = (unsigned)node * (unsigned)(PD * 4) + (unsigned)((tid & 15) * 16);
+    const unsigned own = row_offset(node, tid & 15);
     if constexpr (RELU) mk_n = ldu8_g(p.masks + ev * p.mask_bytes + (size_t)(t0 + s * W) * kThreads, (unsigned)tid);
     else mk_n = ld4_stream_g(p.ztape + ev * p.row_elems, own);
     xrow_n = ld4_stream_g(p.tape + ev * p.row_elems, own);
@@ -2247,46 +1391,11 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
     }
     return true;
   };
-  // (operand tiles __restrict__: these LDS reads must not wait for a DMA issued into the halo region)
-  auto dw_products = [&](const float *__restrict__ tX, const float *__restrict__ tDZ, f32x4 (&dwl)[PG::DWT], float &dbl) {
-    const int i16 = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int mm = 0; mm < PG::DWT; ++mm) {
-      const int tt = wave_u + PG::WAVES * mm;
-      if (tt < NT) {   // wave-uniform
-        const int mt = tt / PG::CT, nt = tt % PG::CT;
-#pragma unroll
-        for (int kh = 0; kh < 2; ++kh) {
-          float a[kTM / 8], b[kTM / 8];
-#pragma unroll
-          for (int ks = 0; ks < kTM / 8; ++ks) {
-            a[ks] = tX[(4 * (ks + 4 * kh) + kq) * PG::TS + mt * 16 + i16];
-            b[ks] = tDZ[(4 * (ks + 4 * kh) + kq) * PG::TS + nt * 16 + i16];
-          }
-#pragma unroll
-          for (int ks = 0; ks < kTM / 8; ++ks) dwl[mm] = mfma16(a[ks], b[ks], dwl[mm]);
-        }
-      }
-    }
-    float sdb = 0.f;
-#pragma unroll
-    for (int nn = dbpart; nn < kTM; nn += PG::DBP) sdb += tDZ[nn * PG::TS + dbc];
-#pragma unroll
-    for (int o = 1; o < PG::DBP; o <<= 1) sdb += __shfl_xor(sdb, o);
-    dbl += sdb;
-  };
   auto dense = [&](const TileCtx &c, unsigned own, int ph, f32x4 (&dwl)[PG::DWT], float &dbl, float4 kbar, Aux mk, float4 xrow, float *gout,
                    const Next &nx) {
-    kbar = f4_scale(c.ci, kbar);
-    float4 dz;
-    if constexpr (RELU) {
-      dz = c.valid ? make_float4((mk & 1u) ? kbar.x : 0.f, (mk & 2u) ? kbar.y : 0.f, (mk & 4u) ? kbar.z : 0.f, (mk & 8u) ? kbar.w : 0.f)
-                   : f4_zero();
-    } else {
-      dz = f4_sel(c.valid, f4_mul(kbar, f4_dact(p.act, mk)), f4_zero());
-    }
-    *reinterpret_cast<float4 *>(&ldsDZ[c.grp * PG::TS + 4 * c.q]) = dz;
-    *reinterpret_cast<float4 *>(&ldsX[c.grp * PG::TS + 4 * c.q]) = f4_sel(c.valid, xrow, f4_zero());
+    const float4 dz = adjoint_dz<RELU>(c, p.act, kbar, mk);
+    tile_row_store(ldsDZ, c, dz);
+    adjoint_x_store(ldsX, c, xrow);
     if (nx.tape) fetch(nx.ev, nx.s);
     __syncthreads();
     mfma_rows_times_bt<PD>(ldsDZ, ldsW, ldsG, wave_u, lane);
@@ -2296,7 +1405,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
       tile_ctx_from_lds<false>(cn, t0 + nx.s * W, ldsMeta + nx.s * kMS);
       if (wave_u == 0) f1 = poll_issue(p.m, cn, p.m.flags);
     }
-    dw_products(ldsX, ldsDZ, dwl, dbl);
+    param_grad_products_beside_dma(ldsX, ldsDZ, wave_u, lane, dbc, dbpart, dwl, dbl);
     if (nx.gather) {
       if (wave_u == 0) {
         const bool hit = poll_ready(cn, f1, nx.ph);
@@ -2308,7 +1417,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
       __syncthreads();
       pre = false;
     }
-    const float4 gv = f4_sel(c.valid, f4_scale(c.ci, *reinterpret_cast<const float4 *>(&ldsG[c.grp * PG::TS + 4 * c.q])), f4_zero());
+    const float4 gv = adjoint_g_row(ldsG, c);
     if (pre) {   // uniform
       __syncthreads();   // every thread has read its row of G: the region is the halo again
       halo_fill_all(cn, nx.X, ldsXh);
@@ -2328,7 +1437,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
     for (int s = 0; s < Kv; ++s) {
       TileCtx c;
       tile_ctx_from_lds<false>(c, t0 + s * W, ldsMeta + s * kMS);
-      const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
+      const unsigned own = own_row_offset(c);
       t0_publish();   // (the phase's W is in LDS; the previous turn's products are done with the operand tiles)
       const float4 lam = f4_sel(c.valid, ld4_g(p.lam, own), f4_zero());
       const Aux mk = mk_n;
@@ -2337,7 +1446,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
       Next nx;
       nx.gather = !more && multi; nx.ph = ph + 1; nx.s = more ? s + 1 : 0; nx.X = p.g2; nx.tape = true;
       nx.ev = more ? ev : (size_t)((p.n_steps - 1) * S + (S - 1)) * 2;
-      dense(c, own, ph, dw2, db2, f4_scale(ldsC[S - 1], lam), mk, xrow, p.g2, nx);
+      dense(c, own, ph, dw2, db2, adjoint_kbar_last(ldsC, S, lam), mk, xrow, p.g2, nx);
     }
   }
   for (int n = p.n_steps - 1; n >= 0 && ok; --n) {
@@ -2352,7 +1461,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
         for (int s = 0; s < Kv; ++s) {
           TileCtx c;
           tile_ctx_from_lds<false>(c, t0 + s * W, ldsMeta + s * kMS);
-          const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
+          const unsigned own = own_row_offset(c);
           const Aux mk = mk_n;
           const float4 xrow = xrow_n;
           if (!top(c, ph, p.g2)) { ok = false; break; }
@@ -2373,7 +1482,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
         for (int s = 0; s < Kv; ++s) {
           TileCtx c;
           tile_ctx_from_lds<false>(c, t0 + s * W, ldsMeta + s * kMS);
-          const unsigned own = (unsigned)c.node * (unsigned)(PD * 4) + (unsigned)(c.q * 16);
+          const unsigned own = own_row_offset(c);
           const Aux mk = mk_n;        // (the last phase runs no dense half: nothing was asked for)
           const float4 xrow = xrow_n;
           if (!top(c, ph, p.g1)) { ok = false; break; }
@@ -2389,18 +1498,11 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
           float4 kbar;
           if (i >= 1) {
             if (c.valid) st4_g(p.ubar, own + (unsigned)(i - 1) * rowb, t);
-            float4 v = f4_scale(ldsC[42 + i], t);
-            v = f4_fma(ldsC[i - 1], lam, v);
-            v = f4_fma(ldsC[6 + i * 6 + 2], ub2, v); v = f4_fma(ldsC[6 + i * 6 + 3], ub3, v);
-            v = f4_fma(ldsC[6 + i * 6 + 4], ub4, v); v = f4_fma(ldsC[6 + i * 6 + 5], ub5, v);
-            kbar = v;
+            kbar = adjoint_kbar_stage(ldsC, i, t, lam, ub2, ub3, ub4, ub5);
           } else {
-            float4 v = f4_scale(1.0f, t);
-            v = f4_fma(1.0f, lam, v);
-            v = f4_fma(1.0f, ub1, v); v = f4_fma(1.0f, ub2, v); v = f4_fma(1.0f, ub3, v);
-            v = f4_fma(1.0f, ub4, v); v = f4_fma(1.0f, ub5, v);
+            const float4 v = adjoint_lambda_update(t, lam, ub1, ub2, ub3, ub4, ub5);
             if (c.valid) st4_g(p.lam, own, v);
-            kbar = f4_scale(ldsC[S - 1], v);
+            kbar = adjoint_kbar_last(ldsC, S, v);
           }
           if (!last) {   // next: the workgroup's next tile, or layer 1 of stage i - 1 / of the last stage of the step before
             const bool more = s + 1 < Kv;
@@ -2420,23 +1522,12 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
   }
   if (!ok) {
     __syncthreads();
-    for (int s = 0; s < Kv; ++s) {
-      const int4 sc = p.m.sched[(size_t)(t0 + s * W) * kTM + (tid >> 4)];
-      if (sc.x >= 0) st4_g(p.lam, (unsigned)sc.x * (unsigned)(PD * 4) + (unsigned)((tid & 15) * 16), f4_nan());
-    }
+    poison_tile_rounds(p.m, p.lam, t0, W, Kv, tid);
   }
-  const float bad = __int_as_float(0x7fc00000);
-  auto write_slab = [&](const f32x4 (&dwl)[PG::DWT], float dbl, float *slab_dw, float *slab_db) {
-    float4 *slab4 = reinterpret_cast<float4 *>(slab_dw + (size_t)blockIdx.x * PD * PD);
-#pragma unroll
-    for (int mm = 0; mm < PG::DWT; ++mm) {
-      const int tt = wave_u + PG::WAVES * mm;
-      if (tt < NT) slab4[tt * 64 + lane] = f4_sel(ok, make_float4(dwl[mm][0], dwl[mm][1], dwl[mm][2], dwl[mm][3]), f4_nan());
-    }
-    if (dbpart == 0) slab_db[(size_t)blockIdx.x * PD + dbc] = ok ? dbl : bad;
-  };
-  write_slab(dw1, db1, p.slab_dw1, p.slab_db1);
-  write_slab(dw2, db2, p.slab_dw2, p.slab_db2);
+  // (as a captured lambda the call leaves this kernel's register allocation, and with it its scratch size, as it was)
+  auto slab = [&](const f32x4 (&dwl)[PG::DWT], float dbl, float *slab_dw, float *slab_db) { write_slab(dwl, dbl, slab_dw, slab_db, wave_u, lane, dbc, dbpart, ok); };
+  slab(dw1, db1, p.slab_dw1, p.slab_db1);
+  slab(dw2, db2, p.slab_dw2, p.slab_db2);
   if (tid == 0 && p.m.stats && Kv > 0) p.m.stats[2 * t0 + 1] = n_ahead;
 }
 
