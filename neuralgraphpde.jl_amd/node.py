@@ -27,6 +27,7 @@ from .layers import AbstractExplicitLayer, Chain, GCNConv, rows_of
 from .layers_mp import GATConv, VMHConv, _dense_stack, _node_data, _wt_b
 from .batches import _padded_batch, _canonical_batch
 from .plans import _rows_index, _check_plan_shapes, _Plan, _NodeGCN2Fn, _OdePlan, _ode_desc, _NodeOdeFn  # noqa: F401 (tools import _Plan from here)
+from .plans import _PlanPool, _Recent
 
 _TSIT5_A = [
     [],
@@ -91,6 +92,14 @@ def _graph_leaves(st):
             elif isinstance(v, dict):
                 out += _graph_leaves(v)
     return out
+
+
+def _shared_members(g):
+    """the members of a batch of graphs that share ONE structure (batch([g, g, ...]) or copies of g with other features), else None"""
+    members = getattr(g, "_members", None)
+    if members is not None and len(members) > 1 and all(m._handles is members[0]._handles for m in members):
+        return members
+    return None
 
 
 def _rebuild(tree, it):
@@ -580,6 +589,10 @@ class NeuralODE(AbstractExplicitLayer):
         self.model, self.solver, self.tspan, self.n_steps = model, solver, tuple(tspan), int(n_steps)
         self.adaptive, self.saveat, self.stats = bool(adaptive), None, None
         self.save_times, self.interpolate_saveat = None, False     # (an interpolating adaptive solve's save times)
+        self._plans, self._no_member_plan = _PlanPool(), False
+        self.capture = bool(capture)      # generic right-hand sides: replay the whole solve / adjoint from HIP graphs (adaptive: refused)
+        self._captured = _Recent()
+        self._gat_ok = _Recent()          # (id(graph handle), heads) -> (handle, does the device-resident GAT solver take it?)
         if self.adaptive:
             self._init_adaptive(dt, capture, saveat, save_start, reltol, abstol, dtmax, maxiters, interpolate_saveat)
             return
@@ -596,11 +609,6 @@ class NeuralODE(AbstractExplicitLayer):
                 raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, f"NeuralODE: saveat = {saveat} must be a whole number of steps "
                                                                   f"(dt = {self.dt}) that divides n_steps = {self.n_steps}")
             self.save_every = k
-        self._plans = {}
-        self._no_member_plan = False
-        self.capture = bool(capture)      # generic right-hand sides: replay the whole solve / adjoint from HIP graphs
-        self._captured = {}
-        self._gat_ok = {}                 # (id(graph handle), heads) -> (handle, does the device-resident GAT solver take it?)
 
     def _init_adaptive(self, dt, capture, saveat, save_start, reltol, abstol, dtmax, maxiters, interpolate_saveat):
         def bad(msg):
@@ -657,8 +665,6 @@ class NeuralODE(AbstractExplicitLayer):
         if self.interpolate_saveat:
             self.save_times = dense_save_times(self.tspan, self.saveat, self.save_start)
         _Control(self)        # the library checks tspan and, when the steps land on them, that saveat divides it (ArgumentError)
-        self.capture = False
-        self._plans, self._no_member_plan, self._captured, self._gat_ok = {}, False, {}, {}
 
     @property
     def saving(self):
@@ -705,86 +711,76 @@ class NeuralODE(AbstractExplicitLayer):
         # use_edge_weight=true: the graph's stored weights in the messages, the unweighted degree in the normalisation
         # (src/layers.jl:224 vs :230, as GCNConv.__call__ does); the plan's kernels read them from the handle's slot lists
         norm = (l1.add_self_loops, g.edge_weight if l1.use_edge_weight else None, False)
-        # a batch of graphs that share ONE structure (batch([g, g, ...]) or copies of g with other features): the plan is built on
-        # the member and solves the trajectories one after the other inside its persistent launches
-        members = getattr(g, "_members", None)
-        member_plan = (members is not None and len(members) > 1 and all(m._handles is members[0]._handles for m in members)
-                       and not self._no_member_plan and not l1.use_edge_weight)
-        handle = members[0].handle(norm) if member_plan else g.handle(norm)
-        key = (id(handle), d, l1.act, bool(with_backward), len(members) if member_plan else 1)
-        pool = self._plans.get(key)
-        if pool is None:
-            pool = self._plans[key] = []
-            while len(self._plans) > self.max_plans:        # a plan owns its tape (GBs): keep only the most recent ones
-                self._plans.pop(next(iter(self._plans)))     # (a training loop that swaps the graph every minibatch)
-        else:
-            self._plans[key] = self._plans.pop(key)          # most recently used last
-        # a plan holds ONE solve's tape: `y1 = node(u1); y2 = node(u2); (y1 + y2).backward()` needs two
-        for plan in pool:
-            if not (with_backward and plan.busy()):
-                return plan
-        if len(pool) >= self.max_outstanding:
-            raise _lib.NgpdeError(_lib.ERR_STATE, f"NeuralODE: {len(pool)} solves await their backward pass on this graph; "
-                                                  "each holds a tape -- run backward (or raise NeuralODE.max_outstanding)")
+        # a batch that shares ONE structure: the plan is built on the member and solves the trajectories one after the other inside
+        # its persistent launches
+        members = None if (self._no_member_plan or l1.use_edge_weight) else _shared_members(g)
+        handle = members[0].handle(norm) if members else g.handle(norm)
+        n_members = len(members) if members else 1
+        key = (id(handle), d, l1.act, bool(with_backward), n_members)
+        make = lambda: _Plan(handle, d, l1.act, self.solver, self.n_steps, self.dt, with_backward, members=n_members)
         try:
-            plan = _Plan(handle, d, l1.act, self.solver, self.n_steps, self.dt, with_backward,
-                         members=len(members) if member_plan else 1)
+            return self._plans.acquire(key, with_backward, make, self)
         except _lib.NgpdeError as e:
-            if not (member_plan and e.code == _lib.ERR_UNSUPPORTED):
+            if not (members and e.code == _lib.ERR_UNSUPPORTED):
                 raise
             self._no_member_plan = True     # not a case of the persistent plan: one handle for the whole batch instead
-            self._plans.pop(key, None)
             return self.plan_for(ps, st, with_backward)
-        pool.append(plan)
-        return plan
 
-    def gat_plan_for(self, ps, st, u):
-        """the device-resident plan when the right-hand side is ONE GAT-style layer in the one-launch shape (64 => heads x c = 64,
-        concat, tiles fit the LDS halo) and the library takes it (ngpde_node_gat_supported); None otherwise"""
+    def _solve_gcn2(self, u, ps, st, needs_grad):
+        """u(T) as (D x N) through the device-resident plan of the two-GCNConv chain; None when the right-hand side is not that chain"""
+        plan = self.plan_for(ps, st, needs_grad)
+        if plan is None:
+            return None
+        if not u.is_cuda:
+            raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, "NeuralODE: inputs must live on the GPU (no CPU fallback)")
+        p1, p2 = ps["layer_1"], ps["layer_2"]
+        b1 = p1["bias"].reshape(-1) if "bias" in p1 else None
+        b2 = p2["bias"].reshape(-1) if "bias" in p2 else None
+        w1, w2 = rows_of(p1["weight"]), rows_of(p2["weight"])
+        # the plan's entries take no sizes (they walk the handle's rows): what GCNConv.__call__ would have checked
+        # (check_num_nodes, the matrix product's own DimensionMismatch) is checked here, before any kernel runs
+        d = self.model.chain[0].in_chs
+        _check_plan_shapes("NeuralODE(GCNConv, GCNConv)", u, plan.n_nodes * plan.members, d,
+                           [("layer_1.weight", w1, (d, d)), ("layer_2.weight", w2, (d, d))],
+                           [("layer_1.bias", b1, d), ("layer_2.bias", b2, d)])
+        return _NodeGCN2Fn.apply(u, w1, b1, w2, b2, plan).T
+
+    def _solve_gat(self, u, ps, st, needs_grad):
+        """u(T) as (D x N) through the device-resident plan when the right-hand side is ONE GAT-style layer in the one-launch shape (64 =>
+        heads x c = 64, concat, tiles fit the LDS halo) and the library takes it (ngpde_node_gat_supported); None otherwise"""
         m = self.model
         if isinstance(m, Chain) and len(m.chain) == 1 and isinstance(m.chain[0], GATConv):    # Chain(GATConv(...)): the same solve
             m, ps, st = m.chain[0], ps["layer_1"], st["layer_1"]
         if not (isinstance(m, GATConv) and m.concat and u.is_cuda and m.in_chs == 64 and m.heads * m.out_chs == 64):
             return None
         g = st["graph"]
-        # a batch of graphs that share ONE structure: the plan is built on the member, two members per workgroup
-        members = getattr(g, "_members", None)
-        member_plan = members is not None and len(members) > 1 and all(mm._handles is members[0]._handles for mm in members)
-        handle = m._graph(members[0] if member_plan else g).handle()
-        with_backward = torch.is_grad_enabled() and (u.requires_grad or any(
-            isinstance(v, torch.Tensor) and v.requires_grad for v in ps.values()))
-        key = ("gat", id(handle), m.heads, m.act, m.negative_slope, bool(with_backward), len(members) if member_plan else 1)
-        pool = self._plans.get(key)
-        if pool is None:
+        members = _shared_members(g)      # the plan is built on the member, two members per workgroup
+        handle = m._graph(members[0] if members else g).handle()
+        n_members = len(members) if members else 1
+        key = ("gat", id(handle), m.heads, m.act, m.negative_slope, bool(needs_grad), n_members)
+        if key not in self._plans:
             # asked once per (graph handle, head count) of this NeuralODE: the check compares the two directions' schedules on the
             # device and synchronises (the entry keeps the handle alive, so its id cannot be recycled)
             ok = self._gat_ok.get((id(handle), m.heads))
             if ok is None:
-                ok = (handle, bool(_lib.load().ngpde_node_gat_supported(handle.ptr, 64, m.heads, m.out_chs)))
-                self._gat_ok[(id(handle), m.heads)] = ok
-                while len(self._gat_ok) > 8:
-                    self._gat_ok.pop(next(iter(self._gat_ok)))
+                ok = self._gat_ok.put((id(handle), m.heads),
+                                      (handle, bool(_lib.load().ngpde_node_gat_supported(handle.ptr, 64, m.heads, m.out_chs))), 8)
             if not ok[1]:
                 return None
-            pool = self._plans[key] = []
-            while len(self._plans) > self.max_plans:
-                self._plans.pop(next(iter(self._plans)))
-        else:
-            self._plans[key] = self._plans.pop(key)
-        for plan in pool:
-            if not (with_backward and plan.busy()):
-                return plan
-        if len(pool) >= self.max_outstanding:
-            raise _lib.NgpdeError(_lib.ERR_STATE, f"NeuralODE: {len(pool)} solves await their backward pass on this graph; "
-                                                  "each holds a tape -- run backward (or raise NeuralODE.max_outstanding)")
-        plan = _OdePlan(handle, _ode_desc(_lib.RHS_GAT, self.solver, self.n_steps, self.dt, with_backward, len(members) if member_plan else 1, width=64,
-                                          act=int(m.act), heads=int(m.heads), head_width=int(m.out_chs), negative_slope=float(m.negative_slope)), "gat")
-        pool.append(plan)
-        return plan
+        make = lambda: _OdePlan(handle, _ode_desc(_lib.RHS_GAT, self.solver, self.n_steps, self.dt, needs_grad, n_members, width=64, act=int(m.act),
+                                                  heads=int(m.heads), head_width=int(m.out_chs), negative_slope=float(m.negative_slope)), "gat")
+        plan = self._plans.acquire(key, needs_grad, make, self)      # (what the create raises goes to the caller)
+        b = ps["bias"].reshape(-1) if "bias" in ps else None
+        w, a = rows_of(ps["weight"]), rows_of(ps["a"])
+        _check_plan_shapes("NeuralODE(GATConv)", u, plan.n_nodes * plan.members, 64, [("weight", w, (64, 64))], [("bias", b, 64)])
+        if a.numel() != 2 * m.out_chs * m.heads:
+            raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH, f"DimensionMismatch: NeuralODE(GATConv): attention vector has "
+                                         f"{a.numel()} entries, expected 2 x {m.out_chs} x {m.heads}")
+        return _NodeOdeFn.apply(u, plan, None, a, w, b).T
 
-    def vmh_plan_for(self, ps, st, u, needs_grad):
+    def _vmh_plan(self, ps, st, u, needs_grad):
         """the device-resident plan when the right-hand side is VMHConv(phi, gamma) on a scalar state in the shapes the library takes
-        (ngpde_node_vmh_supported: docs/src/tutorials/VMH.md:75-89's model); (plan, weights and biases) or None"""
+        (ngpde_node_vmh_supported: docs/src/tutorials/VMH.md:75-89's model); (plan, weights and biases, a padded batch's index map) or None"""
         m = self.model
         if not (isinstance(m, VMHConv) and u.is_cuda and u.dim() == 2 and u.shape[1] == 1):
             return None
@@ -830,12 +826,12 @@ class NeuralODE(AbstractExplicitLayer):
                                                             ia(acts[1]), aggr)
         members = getattr(g, "_members", None)
         straddles = bool(members) and len(members) > 1 and any(mg.num_nodes % 32 for mg in members)
-        index, pool, key, handle = None, None, None, None
+        index, hit, key, handle = None, False, None, None
         if not straddles:      # (a batch whose clouds share tiles goes to its padded form at once: no handle of the unpadded union is built)
             handle = g.handle()
             key = ("vmh", id(handle), tuple(dims[0]), tuple(acts[0]), tuple(dims[1]), tuple(acts[1]), aggr, bool(needs_grad))
-            pool = self._plans.get(key)
-        if pool is None and (straddles or not supported(handle)):
+            hit = key in self._plans
+        if not hit and (straddles or not supported(handle)):
             # a batch of point clouds whose sizes are not multiples of the 32-row tile (VMH.md:120-134: 24 clouds of 3 000 points): a tile
             # that holds the end of one cloud and the start of the next stages two neighbourhoods and can overflow its halo, which takes
             # the persistent forms away from the whole handle.  The same batch with every cloud padded to whole tiles by isolated nodes
@@ -846,37 +842,28 @@ class NeuralODE(AbstractExplicitLayer):
             g, index = pad
             handle, pos = g.handle(), _node_data(g, u.device)
             key = ("vmh", id(handle), tuple(dims[0]), tuple(acts[0]), tuple(dims[1]), tuple(acts[1]), aggr, bool(needs_grad))
-            pool = self._plans.get(key)
-            if pool is None and not supported(handle):
+            hit = key in self._plans
+            if not hit and not supported(handle):
                 return None
-        if pool is None:
-            pool = self._plans[key] = []
-            while len(self._plans) > self.max_plans:
-                self._plans.pop(next(iter(self._plans)))
-        else:
-            self._plans[key] = self._plans.pop(key)
         if nodemap is not None:      # node of the given batch -> node of the earlier batch (-> its row among the padding nodes'), kept on the batch
             comp = getattr(g_given, "_vmh_comp", None)
             if comp is None or comp[0] is not index or comp[1] is not nodemap:
                 comp = g_given._vmh_comp = (index, nodemap, nodemap if index is None else index.index_select(0, nodemap))
             index = comp[2]
-        for plan in pool:
-            if not (needs_grad and plan.busy()):
-                return plan, wb, index
-        if len(pool) >= self.max_outstanding:
-            raise _lib.NgpdeError(_lib.ERR_STATE, f"NeuralODE: {len(pool)} solves await their backward pass on this graph; "
-                                                  "each holds a tape -- run backward (or raise NeuralODE.max_outstanding)")
-        # plans of this right-hand side on OTHER graphs are of no use any more (updategraph per minibatch, VMH.md:132-134): their tapes --
-        # tens of GB at the tutorial's batch size -- go back to the library's pool before the new plan asks for its own
-        # (only when THIS plan needs tapes, and only plans that hold tapes: a forward-only validation solve between training steps
-        # must not evict the training graph's plan and make the next step rebuild it)
-        if needs_grad:
-            for old_key in [k for k in self._plans if k[0] == "vmh" and k[1] != id(handle) and k[-1]]:
-                self._plans.pop(old_key)
-        try:
-            plan = _OdePlan(handle, _ode_desc(_lib.RHS_VMH, self.solver, self.n_steps, self.dt, needs_grad, width=1, pos_width=int(pd), aggr=int(aggr),
+
+        def make():
+            # plans of this right-hand side on OTHER graphs are of no use any more (updategraph per minibatch, VMH.md:132-134): their tapes --
+            # tens of GB at the tutorial's batch size -- go back to the library's pool before the new plan asks for its own
+            # (only when THIS plan needs tapes, and only plans that hold tapes: a forward-only validation solve between training steps
+            # must not evict the training graph's plan and make the next step rebuild it)
+            if needs_grad:
+                for old_key in [k for k in self._plans if k[0] == "vmh" and k[1] != id(handle) and k[-1]]:
+                    self._plans.pop(old_key)
+            return _OdePlan(handle, _ode_desc(_lib.RHS_VMH, self.solver, self.n_steps, self.dt, needs_grad, width=1, pos_width=int(pd), aggr=int(aggr),
                                               pos=pos.data_ptr(), n_phi=len(acts[0]), phi_dims=dims[0], phi_acts=acts[0], n_gamma=len(acts[1]),
                                               gamma_dims=dims[1], gamma_acts=acts[1]), "vmh")
+        try:
+            return self._plans.acquire(key, needs_grad, make, self), wb, index
         except _lib.NgpdeError as e:
             # the tapes of a solve -- every layer's input rows and dz rows of every right-hand-side evaluation, 64 floats wide -- did not
             # fit the device (the library parks and re-uses the tapes of plans that went away, and frees them before it gives up): the
@@ -884,11 +871,28 @@ class NeuralODE(AbstractExplicitLayer):
             # ... or the library found, while building the plan, that the graph is not the plan's after all: the same way out
             if e.code not in (_lib.ERR_HIP, _lib.ERR_UNSUPPORTED):
                 raise
-            if not pool:
-                self._plans.pop(key, None)
             return None
-        pool.append(plan)
-        return plan, wb, index
+
+    def _solve_vmh(self, u, ps, st, needs_grad):
+        """u(T) as (1 x N) -- with saveat the (1 x N x T) array of the solution at t0 (+ j saveat) -- through the device-resident
+        VMHConv plan; None when _vmh_plan finds none"""
+        found = self._vmh_plan(ps, st, u, needs_grad)
+        if found is None:
+            return None
+        plan, wb, index = found
+        # a state whose node count is not the plan's graph's (a forgotten updategraph in the minibatch loop): the reference's
+        # check_num_nodes DimensionMismatch, not N floats read and written through buffers of N'
+        n_expected = plan.n_nodes if index is None else int(index.numel())
+        if u.shape[0] != n_expected:
+            raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH, f"DimensionMismatch: NeuralODE(VMHConv): the state has {u.shape[0]} "
+                                         f"nodes, the graph in the layer's state has {n_expected}")
+        uin = u.reshape(-1)
+        if index is not None:      # (a padded batch: the real nodes' rows among the isolated padding nodes')
+            uin = _rows_index(uin, index, plan.n_nodes, True)
+        out = _NodeOdeFn.apply(uin, plan, (self.save_every, self.save_start) if self.save_every else None, None, *wb)
+        if index is not None:
+            out = _rows_index(out, index, plan.n_nodes, False)
+        return out.T.unsqueeze(0) if self.save_every else out.reshape(u.shape).T
 
     def __call__(self, x, ps, st):
         u = rows_of(x)
@@ -897,73 +901,25 @@ class NeuralODE(AbstractExplicitLayer):
         if not self.adaptive:      # (an adaptive solve's statistics are set by the solve itself)
             self.stats = dict(naccept=self.n_steps, nreject=0, nf=len(TABLEAUS[self.solver][1]) * self.n_steps, dts=[self.dt] * self.n_steps,
                               t=float(self.tspan[1]))
-        # adaptive stepping: always the generic path (the device-resident plans are fixed-step by construction)
-        plan = self.plan_for(ps, st, needs_grad) if not (self.save_every or self.adaptive) else None
-        if plan is not None:
-            if not u.is_cuda:
-                raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, "NeuralODE: inputs must live on the GPU (no CPU fallback)")
-            p1, p2 = ps["layer_1"], ps["layer_2"]
-            b1 = p1["bias"].reshape(-1) if "bias" in p1 else None
-            b2 = p2["bias"].reshape(-1) if "bias" in p2 else None
-            w1, w2 = rows_of(p1["weight"]), rows_of(p2["weight"])
-            # the plan's entries take no sizes (they walk the handle's rows): what GCNConv.__call__ would have checked
-            # (check_num_nodes, the matrix product's own DimensionMismatch) is checked here, before any kernel runs
-            d = self.model.chain[0].in_chs
-            _check_plan_shapes("NeuralODE(GCNConv, GCNConv)", u, plan.n_nodes * plan.members, d,
-                               [("layer_1.weight", w1, (d, d)), ("layer_2.weight", w2, (d, d))],
-                               [("layer_1.bias", b1, d), ("layer_2.bias", b2, d)])
-            uT = _NodeGCN2Fn.apply(u, w1, b1, w2, b2, plan)
-            return uT.T, st
-        gplan = self.gat_plan_for(ps, st, u) if not (self.save_every or self.adaptive) else None
-        if gplan is not None:
-            gps = ps["layer_1"] if isinstance(self.model, Chain) else ps
-            gm = self.model.chain[0] if isinstance(self.model, Chain) else self.model
-            b = gps["bias"].reshape(-1) if "bias" in gps else None
-            w, a = rows_of(gps["weight"]), rows_of(gps["a"])
-            _check_plan_shapes("NeuralODE(GATConv)", u, gplan.n_nodes * gplan.members, 64, [("weight", w, (64, 64))], [("bias", b, 64)])
-            if a.numel() != 2 * gm.out_chs * gm.heads:
-                raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH, f"DimensionMismatch: NeuralODE(GATConv): attention vector has "
-                                             f"{a.numel()} entries, expected 2 x {gm.out_chs} x {gm.heads}")
-            uT = _NodeOdeFn.apply(u, gplan, None, a, w, b)
-            return uT.T, st
-        vplan = self.vmh_plan_for(ps, st, u, needs_grad) if not self.adaptive else None
-        if vplan is not None:
-            plan_v, wb, index = vplan
-            # a state whose node count is not the plan's graph's (a forgotten updategraph in the minibatch loop): the reference's
-            # check_num_nodes DimensionMismatch, not N floats read and written through buffers of N'
-            n_expected = plan_v.n_nodes if index is None else int(index.numel())
-            if u.shape[0] != n_expected:
-                raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH, f"DimensionMismatch: NeuralODE(VMHConv): the state has {u.shape[0]} "
-                                             f"nodes, the graph in the layer's state has {n_expected}")
-            uin = u.reshape(-1)
-            if index is not None:      # (a padded batch: the real nodes' rows among the isolated padding nodes')
-                uin = _rows_index(uin, index, plan_v.n_nodes, True)
-            if self.save_every:      # saveat: the (1 x N x T) array of the solution at t0 (+ j saveat)
-                us = _NodeOdeFn.apply(uin, plan_v, (self.save_every, self.save_start), None, *wb)
-                if index is not None:
-                    us = _rows_index(us, index, plan_v.n_nodes, False)
-                return us.T.unsqueeze(0), st
-            uT = _NodeOdeFn.apply(uin, plan_v, None, None, *wb)
-            if index is not None:
-                uT = _rows_index(uT, index, plan_v.n_nodes, False)
-            return uT.reshape(u.shape).T, st
+            # the device-resident plans: fixed-step by construction (adaptive stepping is always the generic path), saveat in VMH's only
+            for solve in (self._solve_vmh,) if self.save_every else (self._solve_gcn2, self._solve_gat, self._solve_vmh):
+                out = solve(u, ps, st, needs_grad)
+                if out is not None:
+                    return out, st
         # any other right-hand side: explicit RK stepping through the layers' own kernels, every Runge-Kutta combination (and
         # every combination of the discrete adjoint) one library launch
         if not u.is_cuda:
             raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, "NeuralODE: inputs must live on the GPU (no CPU fallback)")
         leaves = _leaves(ps)
         if self.capture:
-            needs = torch.is_grad_enabled() and (u.requires_grad or any(isinstance(p, torch.Tensor) and p.requires_grad for p in leaves))
             # every GNNGraph leaf of the state tree (a container's graphs sit in st["layer_k"]["graph"]): the captures bake in
             # the addresses of their derived arrays.  The entry keeps `st` -- and with it the graphs -- alive, so an id cannot be
             # recycled while its key is cached.
-            key = (tuple(u.shape), needs, tuple(id(g) for g in _graph_leaves(st)),
+            key = (tuple(u.shape), needs_grad, tuple(id(g) for g in _graph_leaves(st)),
                    tuple(p.data_ptr() if isinstance(p, torch.Tensor) else id(p) for p in leaves))
             solve = self._captured.get(key)
             if solve is None:
-                solve = self._captured[key] = _CapturedSolve(self, u, ps, st, leaves, needs)
-                while len(self._captured) > self.max_plans:
-                    self._captured.pop(next(iter(self._captured)))
+                solve = self._captured.put(key, _CapturedSolve(self, u, ps, st, leaves, needs_grad), self.max_plans)
             uT = _NodeCapturedFn.apply(u, solve, *leaves)
             return (uT.permute(2, 1, 0) if self.save_every else uT.T), st
         uT = _NodeGenericFn.apply(u, self, ps, st, *leaves)

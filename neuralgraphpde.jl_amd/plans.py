@@ -1,7 +1,11 @@
-"""The device-resident solver plans behind NeuralODE (node.py): handles of the library's plan objects and the autograd functions that
-call their forward / adjoint entries.  `_Plan` = ngpde_node_gcn2_* (the two-GCNConv chain of graph_node.md:78, BASELINE's headline);
-`_OdePlan` = ngpde_ode_* (ONE create call: the library is given a description of the right-hand side and picks the plan -- a GAT-style
-layer, VMHConv(phi, gamma) or the GCN chain; csrc/api_ode.hip).  A plan holds the tape of ONE solve: `claim` / `busy` hand it out."""
+"""The device-resident solver plans behind NeuralODE (node.py): handles of the library's plan objects, the pool that hands them out and
+the autograd functions that call their forward / adjoint entries.
+`_ResidentPlan` is what every plan is on the host: the library object's pointer, the graph handle it was built on, and the token of the
+solve whose tape it holds (`claim` / `busy`: a plan holds the tape of ONE solve).  A subclass names its entries and says who remembers
+that a backward is outstanding: `_Plan` = ngpde_node_gcn2_* (the two-GCNConv chain of graph_node.md:78, BASELINE's headline; the library
+remembers), `_OdePlan` = ngpde_ode_* (ONE create call: the library is given a description of the right-hand side and picks the plan -- a
+GAT-style layer, VMHConv(phi, gamma) or the GCN chain; csrc/api_ode.hip; `_NodeOdeFn` remembers).
+`_PlanPool` is NeuralODE's key -> [plans] mapping: the most recent keys, per key one plan for every solve that still awaits its backward."""
 from __future__ import annotations
 
 import ctypes as C
@@ -53,24 +57,98 @@ def _check_plan_shapes(what, u, n_rows, d, weights, biases):
             raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH, f"DimensionMismatch: {what}: {name} has {b.numel()} entries, expected {n}")
 
 
-class _Plan:
-    def __init__(self, handle, d, act, tableau, n_steps, dt, with_backward, members=1):
-        """members > 1: `handle` is ONE member of a block-diagonal batch of `members` identical structures; the plan takes
-        [members * N][d] arrays and solves the members one after the other (ngpde_node_gcn2_create_batch; raises NgpdeError
-        with code ERR_UNSUPPORTED when the persistent plan does not cover the case)"""
+class _ResidentPlan:
+    """A plan object of the library with the tape of ONE solve.  A subclass sets `_entries` (the prefix of its tape_bytes / fault / destroy
+    entries), creates the object into `ptr` and answers `_backward_pending()`: has the last forward's backward not run yet?"""
+    _entries = None
+
+    def __init__(self, handle, members):
         self.lib = _lib.load()
         _lib.flush_destroy()            # plans whose finaliser ran inside a HIP-graph capture
         self.handle = handle            # keeps the graph handle alive
         self.ptr = None
         self.members = int(members)
         self.n_nodes = int(handle._n_nodes)     # rows of ONE member
+        self._token_ref = None
+
+    def tape_bytes(self):
+        return int(getattr(self.lib, self._entries + "_tape_bytes")(self.ptr))
+
+    def fault(self):
+        """True when a persistent launch of this plan gave up waiting (its outputs are NaN).  Synchronises."""
+        f = C.c_int32()
+        _lib.check(getattr(self.lib, self._entries + "_fault")(self.ptr, _lib.current_stream(), C.byref(f)))
+        return bool(f.value)
+
+    def claim(self):
+        """token held by the autograd node of the solve that now owns the tape; the plan is busy while that node is alive
+        and its backward has not run"""
+        token = _Token()
+        self._token_ref = weakref.ref(token)
+        return token
+
+    def busy(self):
+        ref = self._token_ref
+        return ref is not None and ref() is not None and self._backward_pending()
+
+    def __del__(self):
+        try:
+            if self.ptr:
+                _lib.destroy_later(self._entries + "_destroy", self.ptr)      # (not inside a HIP-graph capture: see _lib.destroy_later)
+                self.ptr = None
+        except Exception:
+            pass
+
+
+class _Recent(dict):
+    """a dictionary bounded by its callers: `put` inserts and drops the oldest keys beyond `limit`"""
+
+    def put(self, key, value, limit):
+        self[key] = value
+        while len(self) > limit:
+            del self[next(iter(self))]
+        return value
+
+
+class _PlanPool(_Recent):
+    """key -> the plans made for it, most recently used key last.  A plan owns its tape (GBs), so only the `max_plans` most recent keys
+    are kept (a training loop that swaps the graph every minibatch), and a key holds one plan per solve whose backward is outstanding:
+    `y1 = node(u1); y2 = node(u2); (y1 + y2).backward()` needs two."""
+
+    def acquire(self, key, with_backward, make, limits):
+        """the first plan of `key` that is free (any, when the solve keeps no tape), or a new one from make().  limits: whatever carries
+        max_plans and max_outstanding (the NeuralODE: read per call).  What make() raises is the caller's; a key it leaves empty goes."""
+        pool = self.get(key)
+        if pool is None:
+            pool = self.put(key, [], limits.max_plans)
+        else:
+            self[key] = self.pop(key)
+        for plan in pool:
+            if not (with_backward and plan.busy()):
+                return plan
+        if len(pool) >= limits.max_outstanding:
+            raise _lib.NgpdeError(_lib.ERR_STATE, f"NeuralODE: {len(pool)} solves await their backward pass on this graph; "
+                                                  "each holds a tape -- run backward (or raise NeuralODE.max_outstanding)")
+        try:
+            pool.append(make())
+        finally:
+            if not pool:      # make() raised on a fresh key
+                self.pop(key, None)
+        return pool[-1]
+
+
+class _Plan(_ResidentPlan):
+    _entries = "ngpde_node"
+
+    def __init__(self, handle, d, act, tableau, n_steps, dt, with_backward, members=1):
+        """members > 1: `handle` is ONE member of a block-diagonal batch of `members` identical structures; the plan takes
+        [members * N][d] arrays and solves the members one after the other (ngpde_node_gcn2_create_batch; raises NgpdeError
+        with code ERR_UNSUPPORTED when the persistent plan does not cover the case)"""
+        super().__init__(handle, members)
         out = C.c_void_p()
         _lib.check(self.lib.ngpde_node_gcn2_create_batch(handle.ptr, self.members, d, act, _lib.TABLEAU[tableau], n_steps, dt,
                                                          int(with_backward), C.byref(out)))
         self.ptr = out
-
-    def tape_bytes(self):
-        return int(self.lib.ngpde_node_tape_bytes(self.ptr))
 
     def launch_count(self):
         f, b = C.c_int32(), C.c_int32()
@@ -83,37 +161,14 @@ class _Plan:
         _lib.check(self.lib.ngpde_node_flags(self.ptr, C.byref(f)))
         return {name for bit, name in _FLAG_NAMES if f.value & bit}
 
-    def fault(self):
-        """True when a persistent launch of this plan gave up waiting (its outputs are NaN).  Synchronises."""
-        f = C.c_int32()
-        _lib.check(self.lib.ngpde_node_fault(self.ptr, _lib.current_stream(), C.byref(f)))
-        return bool(f.value)
-
-    def claim(self):
-        """token held by the autograd node of the solve that now owns the tape; the plan is busy while that node is alive
-        and its backward has not run"""
-        self._token = _Token()
-        self._token_ref = weakref.ref(self._token)
-        token, self._token = self._token, None
-        return token
-
-    def busy(self):
-        ref = getattr(self, "_token_ref", None)
-        return ref is not None and ref() is not None and self.generation()[1]
-
     def generation(self):
         """(generation of the last forward, is its backward still outstanding?) -- ngpde_node_generation"""
         gen, pend = C.c_uint64(), C.c_int32()
         _lib.check(self.lib.ngpde_node_generation(self.ptr, C.byref(gen), C.byref(pend)))
         return gen.value, bool(pend.value)
 
-    def __del__(self):
-        try:
-            if self.ptr:
-                _lib.destroy_later("ngpde_node_destroy", self.ptr)      # (not inside a HIP-graph capture: see _lib.destroy_later)
-                self.ptr = None
-        except Exception:
-            pass
+    def _backward_pending(self):
+        return self.generation()[1]
 
 
 class _NodeGCN2Fn(torch.autograd.Function):
@@ -150,54 +205,27 @@ _FLAG_NAMES = ((1, "prescaled"), (2, "sign_masks"), (8, "persistent_fwd"), (16, 
                (64, "tile_rounds"), (128, "widened"), (256, "hub_geometry"), (512, "own_first"))
 
 
-class _OdePlan:
+class _OdePlan(_ResidentPlan):
     """A device-resident solve + discrete adjoint chosen by the library's ONE create call (ngpde_ode_create: include/ngpde.h, csrc/api_ode.hip):
     the right-hand side is described, the library checks that its layers chain and picks the plan -- a GAT-style layer (ngpde_node_gat_*),
-    VMHConv(phi, gamma) (ngpde_node_vmh_*) or the two-GCNConv chain (ngpde_node_gcn2_*).  Holds the tape of ONE solve."""
+    VMHConv(phi, gamma) (ngpde_node_vmh_*) or the two-GCNConv chain (ngpde_node_gcn2_*).  `gen` counts its forwards and `_pending` says
+    that the last one's backward is outstanding: both kept by _NodeOdeFn."""
+    _entries = "ngpde_ode"
 
     def __init__(self, handle, desc, kind):
-        self.lib = _lib.load()
-        _lib.flush_destroy()
-        self.handle = handle
-        self.ptr = None
-        self.gen = 0
+        super().__init__(handle, desc.members)
+        self.gen, self._pending = 0, False
         self.kind = kind
-        self.members = int(desc.members)
-        self.n_nodes = int(handle._n_nodes)
         self.n_first, self.n_steps = int(desc.n_phi), int(desc.n_steps)
         out, fl = C.c_void_p(), C.c_int32()
         _lib.check(self.lib.ngpde_ode_create(handle.ptr, C.byref(desc), C.byref(out), C.byref(fl)))
         self.ptr, self._flags = out, fl.value
 
-    def tape_bytes(self):
-        return int(self.lib.ngpde_ode_tape_bytes(self.ptr))
-
     def flags(self):
         return {name for bit, name in _FLAG_NAMES if self._flags & bit} | {self.kind}
 
-    def fault(self):
-        f = C.c_int32()
-        _lib.check(self.lib.ngpde_ode_fault(self.ptr, _lib.current_stream(), C.byref(f)))
-        return bool(f.value)
-
-    def claim(self):
-        self._token = _Token()
-        self._token_ref = weakref.ref(self._token)
-        token, self._token = self._token, None
-        self._pending = True
-        return token
-
-    def busy(self):
-        ref = getattr(self, "_token_ref", None)
-        return ref is not None and ref() is not None and getattr(self, "_pending", False)
-
-    def __del__(self):
-        try:
-            if self.ptr:
-                _lib.destroy_later("ngpde_ode_destroy", self.ptr)
-                self.ptr = None
-        except Exception:
-            pass
+    def _backward_pending(self):
+        return self._pending
 
 
 def _ode_desc(rhs, tableau, n_steps, dt, with_backward, members=1, **kw):
@@ -234,7 +262,7 @@ class _NodeOdeFn(torch.autograd.Function):
         k, start = save if save is not None else (0, 0)
         out = torch.empty_like(u) if save is None else torch.empty((plan.n_steps // k + int(start), u.numel()), dtype=torch.float32, device=u.device)
         _lib.check(lib.ngpde_ode_forward(plan.ptr, _lib.ptr(u), C.byref(prm), int(k), int(start), _lib.ptr(out), _lib.current_stream()))
-        plan.gen += 1
+        plan.gen, plan._pending = plan.gen + 1, True
         ctx.plan, ctx.gen, ctx.token, ctx.save, ctx.nf = plan, plan.gen, plan.claim(), (int(k), int(start)), nf
         ctx.save_for_backward(*([att] if att is not None else []), *ws)
         ctx.has_att, ctx.has_bias, ctx.ushape = att is not None, [b is not None for b in bs], u.shape
