@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "edge_mlp_tile.h"
 #include "stamps.h"
 
 namespace ngpde {
@@ -46,27 +47,14 @@ __device__ __forceinline__ unsigned lds_addr(const void *ptr) { return (unsigned
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kT4 = 256, kW = 64, kTS = kW + 4, kSlice = 16, kChunk4 = 64, kRows = 32;
+constexpr int kT4 = 256, kSlice = 16, kChunk4 = 64;   // (kW, kTS, kRows: edge_mlp_tile.h)
+using Shape = TwoRowsPerGroup;
 
-
-struct EdgeMlp64K {
-  const int4 *sched;
-  const int2 *halo;
-  const uint8_t *slots;
-  int n_tiles, halo_rows, aggr;
+struct EdgeMlp64K : EdgeTileArgs {
+  int aggr;
   const float *P, *Q, *wt, *bias;
   float *out;
   NGPDE_STAMP_FIELD
-};
-
-struct Meta64 {
-  int4 sc0, sc1;       // schedule rows g16 and g16 + 16
-  unsigned sw0, sw1;   // slot word (q & 7) of those rows
-  int he[6];           // node ids of halo rows g16 + 16 k
-};
-struct Rows64 {
-  float px[8];   // P rows g16 and g16 + 16
-  float4 hv[6];
 };
 
 template <int ACT1, int ACT2>
@@ -88,41 +76,11 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_fwd_kernel(const EdgeMlp64K
   const int ei = lane & 15, kq = lane >> 4;         // MFMA role
   const int zero_slot = p.halo_rows;
 
-  const int xcd = blockIdx.x & 7, wg_in_xcd = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-  const int range_len = p.n_tiles / 8 + (xcd < p.n_tiles % 8 ? 1 : 0);
-  const int range_lo = xcd * (p.n_tiles / 8) + min(xcd, p.n_tiles % 8);
-
-  auto fetch_meta = [&](int tile, Meta64 &m) {
-    const size_t row = (size_t)tile * kTileRows + g16;
-    m.sc0 = p.sched[row];
-    m.sc1 = p.sched[row + 16];
-    m.sw0 = reinterpret_cast<const unsigned *>(p.slots)[row * 8 + (q & 7)];
-    m.sw1 = reinterpret_cast<const unsigned *>(p.slots)[(row + 16) * 8 + (q & 7)];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) m.he[k] = p.halo[(size_t)tile * kHaloCap + min(g16 + 16 * k, kHaloCap - 1)].x;
-  };
-  auto fetch_rows = [&](const Meta64 &m, Rows64 &r) {
-    const float4 p0 = *reinterpret_cast<const float4 *>(p.P + (size_t)max(m.sc0.x, 0) * kW + 4 * q);
-    const float4 p1 = *reinterpret_cast<const float4 *>(p.P + (size_t)max(m.sc1.x, 0) * kW + 4 * q);
-    r.px[0] = p0.x; r.px[1] = p0.y; r.px[2] = p0.z; r.px[3] = p0.w;
-    r.px[4] = p1.x; r.px[5] = p1.y; r.px[6] = p1.z; r.px[7] = p1.w;
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-      r.hv[k] = (g16 + 16 * k < p.halo_rows) ? *reinterpret_cast<const float4 *>(p.Q + (size_t)m.he[k] * kW + 4 * q) : f4_zero();
-  };
+  const EdgeTileRange tr(p.n_tiles);
 
   // ---- once per workgroup: W2^T rows (output j, contiguous inputs), bias, the all-zero halo row
-  {
-    const int j = tid & 63, kg0 = tid >> 6;   // output column j, input quads kg0 + 4 ps
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-      const int k = 4 * (kg0 + 4 * ps);
-      *reinterpret_cast<float4 *>(&ldsWt[j * kTS + k]) =
-          make_float4(p.wt[(size_t)k * kW + j], p.wt[(size_t)(k + 1) * kW + j], p.wt[(size_t)(k + 2) * kW + j], p.wt[(size_t)(k + 3) * kW + j]);
-    }
-    if (tid < kW) ldsBias[tid] = p.bias ? p.bias[tid] : 0.f;
-    if (g16 == 0) *reinterpret_cast<float4 *>(&ldsQ[zero_slot * kTS + 4 * q]) = f4_zero();
-  }
+  stage_weights<kT4, false, false>(p.wt, p.bias, kW, kW, tid, ldsWt, nullptr, ldsBias);
+  zero_halo_row(ldsQ, zero_slot, g16, q);
 
   // ---- the activation in stages: y = fin(x, tr2(mid(tr1(pre(x))))) with the two quarter-rate transcendentals (tr1, tr2) as
   // separate steps, so that the pipelined block below can put exactly one of them behind every MFMA; pre / mid / fin on pairs of
@@ -299,79 +257,38 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_fwd_kernel(const EdgeMlp64K
   const std::true_type yes{};
   const std::false_type no{};
 
-  Meta64 meta;
-  Rows64 rows;
-  int jt = wg_in_xcd;
-  if (jt < range_len) {
-    fetch_meta(range_lo + jt, meta);
-    fetch_rows(meta, rows);
+  TileMeta<Shape> meta;
+  TileRows<Shape> rows;
+  int jt = tr.wg_in_xcd;
+  if (jt < tr.range_len) {
+    fetch_meta(p, tr.range_lo + jt, g16, q, meta);
+    fetch_rows<false>(p.P, p.Q, kW, p.halo_rows, meta, g16, q, rows);
   }
 
-  for (; jt < range_len; jt += wgs_per_xcd) {
-    const bool stamp_tile = (jt == wg_in_xcd + 4 * wgs_per_xcd);   // a tile in steady state (the fifth of the workgroup)
+  for (; jt < tr.range_len; jt += tr.wgs_per_xcd) {
+    const bool stamp_tile = (jt == tr.wg_in_xcd + 4 * tr.wgs_per_xcd);   // a tile in steady state (the fifth of the workgroup)
     if (stamp_tile) { NGPDE_STAMP(p.stamps, 16, 0, memtime); NGPDE_STAMP(p.stamps, 16, 14, memrealtime); }
     // ---- stage this tile (fetched under the previous tile's arithmetic)
     const int4 sc0 = meta.sc0, sc1 = meta.sc1;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const int hh = g16 + 16 * k;
-      if (hh < p.halo_rows) *reinterpret_cast<float4 *>(&ldsQ[hh * kTS + 4 * q]) = rows.hv[k];
-    }
-    *reinterpret_cast<float4 *>(&ldsP[g16 * kTS + 4 * q]) = make_float4(rows.px[0], rows.px[1], rows.px[2], rows.px[3]);
-    *reinterpret_cast<float4 *>(&ldsP[(g16 + 16) * kTS + 4 * q]) = make_float4(rows.px[4], rows.px[5], rows.px[6], rows.px[7]);
-    if (q == 0) {
-      ldsOff[g16 + 1] = sc0.x >= 0 ? sc0.z : 0;
-      ldsOff[g16 + 17] = sc1.x >= 0 ? sc1.z : 0;
-      if (g16 == 0) ldsOff[0] = 0;
-    }
-    if (q < 8) {
-      ldsSlots[g16 * 8 + q] = meta.sw0;
-      ldsSlots[(g16 + 16) * 8 + q] = meta.sw1;
-    }
-    const int jn = jt + wgs_per_xcd;
-    const bool has_next = jn < range_len;       // workgroup-uniform
-    if (has_next) fetch_meta(range_lo + jn, meta);
+    stage_rows(rows, p.halo_rows, g16, q, ldsQ, ldsP);
+    stage_tile_degrees<false, false>(meta, g16, q, false, ldsOff, ldsSlots, nullptr, nullptr, nullptr);
+    const int jn = jt + tr.wgs_per_xcd;
+    const bool has_next = jn < tr.range_len;       // workgroup-uniform
+    if (has_next) fetch_meta(p, tr.range_lo + jn, g16, q, meta);
     __syncthreads();
-    if (tid < kRows) {   // inclusive scan of the 32 degrees inside wave 0
-      int v = ldsOff[tid + 1];
-#pragma unroll
-      for (int o = 1; o < kRows; o <<= 1) {
-        const int u = __shfl_up(v, o);
-        if (tid >= o) v += u;
-      }
-      ldsOff[tid + 1] = v;
-    }
+    scan_tile_degrees(ldsOff, tid);
     __syncthreads();
-    const int total = ldsOff[kRows];
-    const int lo0 = ldsOff[g16], hi0 = ldsOff[g16 + 1], lo1 = ldsOff[g16 + 16], hi1 = ldsOff[g16 + 17];
-    for (int k = lo0 + q; k < hi0; k += 16) {
-      const int j = k - lo0;
-      ldsEdge[k] = (uint16_t)(g16 | (((ldsSlots[g16 * 8 + (j >> 2)] >> (8 * (j & 3))) & 0xff) << 8));
-    }
-    for (int k = lo1 + q; k < hi1; k += 16) {
-      const int j = k - lo1;
-      ldsEdge[k] = (uint16_t)((g16 + 16) | (((ldsSlots[(g16 + 16) * 8 + (j >> 2)] >> (8 * (j & 3))) & 0xff) << 8));
-    }
+    int total, lo0, hi0, lo1, hi1;
+    expand_tile_edges(ldsOff, ldsSlots, ldsEdge, g16, q, total, lo0, hi0, lo1, hi1);
     float4 racc0 = f4_zero(), racc1 = f4_zero();
     __syncthreads();
 
     if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 1, memtime);
     const int n_it = (total + kChunk4 - 1) / kChunk4;
     auto reduce = [&](int it) {   // lane group g16 sums the messages of rows g16 and g16 + 16 that lie in chunk `it`, edge order
-      const int c0 = it * kChunk4;
-      const float *base = ldsMsg0 + (it & 1) * (kChunk4 * kTS) + 4 * q - c0 * kTS;
-      auto row_sum = [&](int lo, int hi, float4 &racc) {
-        int kk = max(lo, c0);
-        const int end = min(hi, c0 + kChunk4);
-        for (; kk + 4 <= end; kk += 4) {   // four independent LDS reads, added in edge order
-          const float4 m0 = *reinterpret_cast<const float4 *>(base + kk * kTS), m1 = *reinterpret_cast<const float4 *>(base + (kk + 1) * kTS);
-          const float4 m2 = *reinterpret_cast<const float4 *>(base + (kk + 2) * kTS), m3 = *reinterpret_cast<const float4 *>(base + (kk + 3) * kTS);
-          racc = f4_add(f4_add(f4_add(f4_add(racc, m0), m1), m2), m3);
-        }
-        for (; kk < end; ++kk) racc = f4_add(racc, *reinterpret_cast<const float4 *>(base + kk * kTS));
-      };
-      row_sum(lo0, hi0, racc0);
-      row_sum(lo1, hi1, racc1);
+      const float *chunk = ldsMsg0 + (it & 1) * (kChunk4 * kTS);
+      row_sum_chunk<4>(chunk, it * kChunk4, kChunk4, lo0, hi0, q, racc0);
+      row_sum_chunk<4>(chunk, it * kChunk4, kChunk4, lo1, hi1, q, racc1);
     };
     if (n_it > 0) {
       f32x4 a[4], accp[4];
@@ -379,7 +296,7 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_fwd_kernel(const EdgeMlp64K
       if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 2, memtime);
       block(yes, no, yes, 1, total, ldsMsg0, a, accp);         // products of slice 0 | a1 of slice 1
       if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 3, memtime);
-      if (has_next) fetch_rows(meta, rows);           // the next tile's rows: in flight across this tile's remaining arithmetic
+      if (has_next) fetch_rows<false>(p.P, p.Q, kW, p.halo_rows, meta, g16, q, rows);   // the next tile's rows: in flight across this tile's remaining arithmetic
       if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 4, memtime);
       for (int it = 1; it < n_it; ++it) {
         // products of slice it | messages of slice it - 1 (-> buffer (it - 1) & 1) | a1 of slice it + 1
@@ -400,7 +317,7 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_fwd_kernel(const EdgeMlp64K
       __syncthreads();
       if (stamp_tile) NGPDE_STAMP(p.stamps, 16, 12, memtime);
     } else if (has_next) {
-      fetch_rows(meta, rows);
+      fetch_rows<false>(p.P, p.Q, kW, p.halo_rows, meta, g16, q, rows);
     }
     if (sc0.x >= 0) {
       const int deg = hi0 - lo0;
@@ -425,11 +342,8 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_fwd_kernel(const EdgeMlp64K
 // apart (one's tile loads and reductions under the other's products), the incoming gradient rows read where they are used
 // instead of staged (that is what lets two workgroups fit the LDS), compile-time widths and activations, and one sigmoid per
 // value where activation and derivative both need it.
-struct EdgeMlp64BwdK {
-  const int4 *sched;
-  const int2 *halo;
-  const uint8_t *slots;
-  int n_tiles, halo_rows, aggr;
+struct EdgeMlp64BwdK : EdgeTileArgs {
+  int aggr;
   const float *P, *Q, *wt, *bias, *dout;
   float *dP, *dE, *partial;   // partial: [n_workgroups][65][64]  (row 64 = bias gradient)
   float *dqpart;              // DQ: [n_tiles][kDqStride][64] per-tile sums of dz1 by FOREIGN halo slot (the by-source sum, first half)
@@ -486,32 +400,10 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_bwd_kernel(const EdgeMlp64B
   const int ei = lane & 15, kq = lane >> 4;
   const int zero_slot = p.halo_rows;
 
-  const int xcd = blockIdx.x & 7, wg_in_xcd = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-  const int range_len = p.n_tiles / 8 + (xcd < p.n_tiles % 8 ? 1 : 0);
-  const int range_lo = xcd * (p.n_tiles / 8) + min(xcd, p.n_tiles % 8);
+  const EdgeTileRange tr(p.n_tiles);
 
-  auto fetch_meta = [&](int tile, Meta64 &m) {
-    const size_t row = (size_t)tile * kTileRows + g16;
-    m.sc0 = p.sched[row];
-    m.sc1 = p.sched[row + 16];
-    m.sw0 = reinterpret_cast<const unsigned *>(p.slots)[row * 8 + (q & 7)];
-    m.sw1 = reinterpret_cast<const unsigned *>(p.slots)[(row + 16) * 8 + (q & 7)];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) m.he[k] = p.halo[(size_t)tile * kHaloCap + min(g16 + 16 * k, kHaloCap - 1)].x;
-  };
-
-  {   // W2^T and W2 rows, bias, the all-zero halo row
-    const int j = tid & 63, kg0 = tid >> 6;
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-      const int k = 4 * (kg0 + 4 * ps);
-      *reinterpret_cast<float4 *>(&ldsWf[j * kTS + k]) =
-          make_float4(p.wt[(size_t)k * kW + j], p.wt[(size_t)(k + 1) * kW + j], p.wt[(size_t)(k + 2) * kW + j], p.wt[(size_t)(k + 3) * kW + j]);
-      *reinterpret_cast<float4 *>(&ldsWb[j * kTS + k]) = *reinterpret_cast<const float4 *>(p.wt + (size_t)j * kW + k);
-    }
-    if (tid < kW) ldsBias[tid] = p.bias ? p.bias[tid] : 0.f;
-    if (g16 == 0) *reinterpret_cast<float4 *>(&ldsQ[zero_slot * kTS + 4 * q]) = f4_zero();
-  }
+  stage_weights<kT4, false, true>(p.wt, p.bias, kW, kW, tid, ldsWf, ldsWb, ldsBias);   // W2^T and W2 rows, bias
+  zero_halo_row(ldsQ, zero_slot, g16, q);
 
   // dW2 accumulators of this wave: tile (ct, mt) <-> rows 16 ct .. + 15 (inputs) x columns 16 mt .. + 15 (outputs)
   f32x4 accW[4][4];
@@ -523,66 +415,32 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_bwd_kernel(const EdgeMlp64B
     for (int b = 0; b < 4; ++b) accW[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
 
-  Meta64 meta;
-  int jt = wg_in_xcd;
-  if (jt < range_len) fetch_meta(range_lo + jt, meta);
+  TileMeta<Shape> meta;
+  int jt = tr.wg_in_xcd;
+  if (jt < tr.range_len) fetch_meta(p, tr.range_lo + jt, g16, q, meta);
 
-  for (; jt < range_len; jt += wgs_per_xcd) {
+  for (; jt < tr.range_len; jt += tr.wgs_per_xcd) {
     const int4 sc0 = meta.sc0, sc1 = meta.sc1;
     {   // stage the tile: P rows and the distinct Q rows (the other workgroup of the CU computes meanwhile)
-      const float4 p0 = *reinterpret_cast<const float4 *>(p.P + (size_t)max(sc0.x, 0) * kW + 4 * q);
-      const float4 p1 = *reinterpret_cast<const float4 *>(p.P + (size_t)max(sc1.x, 0) * kW + 4 * q);
-      float4 hv[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k)
-        hv[k] = (g16 + 16 * k < p.halo_rows) ? *reinterpret_cast<const float4 *>(p.Q + (size_t)meta.he[k] * kW + 4 * q) : f4_zero();
+      TileRows<Shape> rows;
+      fetch_rows<false>(p.P, p.Q, kW, p.halo_rows, meta, g16, q, rows);
+      // (stored here, not through stage_rows: with the call the swish / swish instantiations spill a register)
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         const int hh = g16 + 16 * k;
-        if (hh < p.halo_rows) *reinterpret_cast<float4 *>(&ldsQ[hh * kTS + 4 * q]) = hv[k];
+        if (hh < p.halo_rows) *reinterpret_cast<float4 *>(&ldsQ[hh * kTS + 4 * q]) = rows.hv[k];
       }
-      *reinterpret_cast<float4 *>(&ldsP[g16 * kTS + 4 * q]) = p0;
-      *reinterpret_cast<float4 *>(&ldsP[(g16 + 16) * kTS + 4 * q]) = p1;
+      *reinterpret_cast<float4 *>(&ldsP[g16 * kTS + 4 * q]) = rows.prow[0];
+      *reinterpret_cast<float4 *>(&ldsP[(g16 + 16) * kTS + 4 * q]) = rows.prow[1];
     }
-    if (q == 0) {
-      const int d0 = sc0.x >= 0 ? sc0.z : 0, d1 = sc1.x >= 0 ? sc1.z : 0;
-      ldsOff[g16 + 1] = d0;
-      ldsOff[g16 + 17] = d1;
-      ldsRs[g16] = sc0.y;
-      ldsRs[g16 + 16] = sc1.y;
-      ldsNode[g16] = max(sc0.x, 0);
-      ldsNode[g16 + 16] = max(sc1.x, 0);
-      ldsInv[g16] = p.aggr == NGPDE_AGGR_MEAN ? (d0 > 0 ? 1.0f / (float)d0 : 0.f) : 1.0f;
-      ldsInv[g16 + 16] = p.aggr == NGPDE_AGGR_MEAN ? (d1 > 0 ? 1.0f / (float)d1 : 0.f) : 1.0f;
-      if (g16 == 0) ldsOff[0] = 0;
-    }
-    if (q < 8) {
-      ldsSlots[g16 * 8 + q] = meta.sw0;
-      ldsSlots[(g16 + 16) * 8 + q] = meta.sw1;
-    }
-    const int jn = jt + wgs_per_xcd;
-    if (jn < range_len) fetch_meta(range_lo + jn, meta);
+    stage_tile_degrees<true, true>(meta, g16, q, p.aggr == NGPDE_AGGR_MEAN, ldsOff, ldsSlots, ldsRs, ldsNode, ldsInv);
+    const int jn = jt + tr.wgs_per_xcd;
+    if (jn < tr.range_len) fetch_meta(p, tr.range_lo + jn, g16, q, meta);
     __syncthreads();
-    if (tid < kRows) {
-      int v = ldsOff[tid + 1];
-#pragma unroll
-      for (int o = 1; o < kRows; o <<= 1) {
-        const int u = __shfl_up(v, o);
-        if (tid >= o) v += u;
-      }
-      ldsOff[tid + 1] = v;
-    }
+    scan_tile_degrees(ldsOff, tid);
     __syncthreads();
-    const int total = ldsOff[kRows];
-    const int lo0 = ldsOff[g16], hi0 = ldsOff[g16 + 1], lo1 = ldsOff[g16 + 16], hi1 = ldsOff[g16 + 17];
-    for (int k = lo0 + q; k < hi0; k += 16) {
-      const int j = k - lo0;
-      ldsEdge[k] = (uint16_t)(g16 | (((ldsSlots[g16 * 8 + (j >> 2)] >> (8 * (j & 3))) & 0xff) << 8));
-    }
-    for (int k = lo1 + q; k < hi1; k += 16) {
-      const int j = k - lo1;
-      ldsEdge[k] = (uint16_t)((g16 + 16) | (((ldsSlots[(g16 + 16) * 8 + (j >> 2)] >> (8 * (j & 3))) & 0xff) << 8));
-    }
+    int total, lo0, hi0, lo1, hi1;
+    expand_tile_edges(ldsOff, ldsSlots, ldsEdge, g16, q, total, lo0, hi0, lo1, hi1);
     float4 racc0 = f4_zero(), racc1 = f4_zero();
     float4 qacc[kDqSlots];
 #pragma unroll
@@ -596,9 +454,9 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_bwd_kernel(const EdgeMlp64B
       float *mine = ldsS + (size_t)(wave * kSlice) * kTS;          // this wave's 16 rows of the staging tile
       float4 dz1[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
       if (wave_on) {
-        const unsigned ew = ldsEdge[valid ? k : 0];
-        const int r = ew & 0xff, slot = valid ? (int)(ew >> 8) : zero_slot;
-        const size_t pe = (size_t)(ldsRs[r] + (k - ldsOff[r]));
+        int r, slot;
+        size_t pe;
+        lane_edge(ldsEdge, ldsOff, ldsRs, k, valid, zero_slot, r, slot, pe);
         // incoming gradient rows of the edge's target (g = dout / deg for mean): issued now, used behind the first product
         // (kept raw until then: scaled at the load, the compiler loads them one after the other into one register
         // quad, each waited for before the next is issued -- three exposed round trips per slice)
@@ -649,26 +507,7 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_bwd_kernel(const EdgeMlp64B
             }
           }
         }
-        // ---- dW2 += a1^T dz2 over this wave's 16 edges: both operands transposed through the wave's LDS rows
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<float4 *>(&mine[ei * kTS + 16 * ct + 4 * kq]) = a1[ct];
-        float a1T[4][4];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-          for (int sI = 0; sI < 4; ++sI) a1T[ct][sI] = mine[(4 * sI + kq) * kTS + 16 * ct + ei];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) *reinterpret_cast<float4 *>(&mine[ei * kTS + 16 * mt + 4 * kq]) = gz[mt];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-          float dzT[4];
-#pragma unroll
-          for (int sI = 0; sI < 4; ++sI) dzT[sI] = mine[(4 * sI + kq) * kTS + 16 * mt + ei];
-#pragma unroll
-          for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int sI = 0; sI < 4; ++sI) accW[ct][mt] = mfma16(a1T[ct][sI], dzT[sI], accW[ct][mt]);
-        }
+        weight_grad_products<false>(mine, a1, gz, kW, kW, ei, kq, accW);   // dW2 += a1^T dz2
         // ---- da1 (transposed product with W2), dz1 = da1 . act1'(z1); fragments one group ahead as above
         {
           const float *wl0 = ldsWb + ei * kTS + 4 * kq;
@@ -701,11 +540,8 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_bwd_kernel(const EdgeMlp64B
         for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<float4 *>(&mine2[ei * kTS + 16 * ct + 4 * kq]) = dz1[ct];
       }
       __syncthreads();
-      {
-        const float *base = ldsS + 4 * q - c0 * kTS;
-        for (int kk = max(lo0, c0); kk < min(hi0, c0 + kChunk4); ++kk) racc0 = f4_add(racc0, *reinterpret_cast<const float4 *>(base + kk * kTS));
-        for (int kk = max(lo1, c0); kk < min(hi1, c0 + kChunk4); ++kk) racc1 = f4_add(racc1, *reinterpret_cast<const float4 *>(base + kk * kTS));
-      }
+      row_sum_chunk(ldsS, c0, kChunk4, lo0, hi0, q, racc0);
+      row_sum_chunk(ldsS, c0, kChunk4, lo1, hi1, q, racc1);
       if constexpr (DQ) {
         // lane q of a group looks at the slot ids of edges c0 + 16 i + q of the chunk; a ballot per i gives every group the 16 match
         // bits of its own slot; the set bits, lowest first, are the chunk's edges with that source in edge order
@@ -741,7 +577,7 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_bwd_kernel(const EdgeMlp64B
           const int node = j == 0 ? sc0.x : sc1.x;
           if (node >= 0) *reinterpret_cast<float4 *>(p.dQ + (size_t)node * kW + 4 * q) = qacc[j];
         } else if (sl < p.halo_rows) {
-          *reinterpret_cast<float4 *>(p.dqpart + ((size_t)(range_lo + jt) * kDqStride + sl) * kW + 4 * q) = qacc[j];
+          *reinterpret_cast<float4 *>(p.dqpart + ((size_t)(tr.range_lo + jt) * kDqStride + sl) * kW + 4 * q) = qacc[j];
         }
       }
     }
@@ -756,34 +592,11 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_bwd_kernel(const EdgeMlp64B
     float *slab = ldsS;                                            // [65][64] <= [64][kTS]
     __syncthreads();
     for (int idx = tid; idx < (kW + 1) * kW; idx += kT4) slab[idx] = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {   // db: sum the 16 edge lanes of each k-quarter inside the wave first
-      float v[4] = {dbacc[mt].x, dbacc[mt].y, dbacc[mt].z, dbacc[mt].w};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) v[c] += __shfl_xor(v[c], o);
-      }
-      dbacc[mt] = make_float4(v[0], v[1], v[2], v[3]);
-    }
+    fold_bias_lanes(dbacc);
     __syncthreads();
+#pragma unroll   // (as the compiler did on its own while the body was written out here)
     for (int w = 0; w < kT4 / 64; ++w) {
-      if (wave == w) {
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) slab[(16 * ct + 4 * kq + r) * kW + 16 * mt + ei] += accW[ct][mt][r];
-        if (ei == 0) {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            const int o = 16 * mt + 4 * kq;
-            slab[kW * kW + o] += dbacc[mt].x; slab[kW * kW + o + 1] += dbacc[mt].y;
-            slab[kW * kW + o + 2] += dbacc[mt].z; slab[kW * kW + o + 3] += dbacc[mt].w;
-          }
-        }
-      }
+      if (wave == w) fold_slab<false>(slab, kW, kW, accW, dbacc, ei, kq);
       __syncthreads();
     }
     float *dst = p.partial + (size_t)blockIdx.x * (kW + 1) * kW;
@@ -814,31 +627,20 @@ bool edge_mlp64_fwd_applicable(const ngpde_graph *g, const EdgeMlpArgs &a) {
 
 int32_t launch_edge_mlp64_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hipStream_t stream) {
   EdgeMlp64K k;
-  k.sched = g->by_t.sched; k.halo = g->by_t.halo; k.slots = g->by_t.slots;
-  k.n_tiles = (int)(g->n_sched / kTileRows); k.aggr = a.aggr;
-  k.halo_rows = std::max<int>(kTileRows, std::min<int>(kHaloCap, g->by_t.max_halo));
+  fill_tile_args(g, k);
+  k.aggr = a.aggr;
   k.P = a.P; k.Q = a.Q; k.wt = a.wt[0]; k.bias = a.bias[0]; k.out = a.out;
   NGPDE_STAMP_SET(k, kStampEdge64, 0);
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kW * kTS + 2 * (size_t)kChunk4 * kTS) * sizeof(float);
   // two persistent workgroups per CU (one when the halo region is large), a multiple of the 8 XCDs
-  const int per_xcd = std::max(1, std::min(lds + 4096 <= 80 * 1024 ? 64 : 32, (k.n_tiles + 7) / 8));
-  const dim3 grid(8 * per_xcd), block(kT4);
-  auto launch = [&](auto kernel) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, grid, block, lds, stream, k);
-    return hipSuccess;
-  };
-  hipError_t le;
+  const int grid = edge_persistent_grid(g, lds + 4096 <= 80 * 1024 ? 64 : 32);
+  auto launch = [&](auto kernel) { return launch_with_lds(kernel, grid, kT4, lds, stream, k, "edge_mlp64_fwd_kernel"); };
   const bool same = a.act[0] == a.act1;
   switch (a.act1) {
-    case NGPDE_ACT_SWISH: le = same ? launch(edge_mlp64_fwd_kernel<NGPDE_ACT_SWISH, NGPDE_ACT_SWISH>) : launch(edge_mlp64_fwd_kernel<NGPDE_ACT_SWISH, NGPDE_ACT_IDENTITY>); break;
-    case NGPDE_ACT_RELU: le = same ? launch(edge_mlp64_fwd_kernel<NGPDE_ACT_RELU, NGPDE_ACT_RELU>) : launch(edge_mlp64_fwd_kernel<NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY>); break;
-    default: le = same ? launch(edge_mlp64_fwd_kernel<NGPDE_ACT_TANH, NGPDE_ACT_TANH>) : launch(edge_mlp64_fwd_kernel<NGPDE_ACT_TANH, NGPDE_ACT_IDENTITY>); break;
+    case NGPDE_ACT_SWISH: return same ? launch(edge_mlp64_fwd_kernel<NGPDE_ACT_SWISH, NGPDE_ACT_SWISH>) : launch(edge_mlp64_fwd_kernel<NGPDE_ACT_SWISH, NGPDE_ACT_IDENTITY>);
+    case NGPDE_ACT_RELU: return same ? launch(edge_mlp64_fwd_kernel<NGPDE_ACT_RELU, NGPDE_ACT_RELU>) : launch(edge_mlp64_fwd_kernel<NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY>);
+    default: return same ? launch(edge_mlp64_fwd_kernel<NGPDE_ACT_TANH, NGPDE_ACT_TANH>) : launch(edge_mlp64_fwd_kernel<NGPDE_ACT_TANH, NGPDE_ACT_IDENTITY>);
   }
-  if (le != hipSuccess) return fail(NGPDE_ERR_HIP, "edge_mlp64_fwd_kernel: LDS request of %zu bytes refused: %s", lds, hipGetErrorString(le));
-  NGPDE_LAUNCH_CHECK("edge_mlp64_fwd_kernel");
-  return NGPDE_OK;
 }
 
 // dQ[node] += the partial rows of the OTHER tiles whose halo list holds the node (entries ascending by tile: fixed order); the node's
@@ -855,13 +657,7 @@ __global__ __launch_bounds__(256) void edge64_dq_combine_kernel(int n_listed, co
 }
 
 // ---- pullback launch.  Same conditions as the forward specialisation (the activation pairs instantiated below); workspace =
-// one [65][64] slab per workgroup (edge_mlp64_bwd_grid).
-// The kernel splits the tiles into 8 per-XCD ranges and lets gridDim.x / 8 workgroups walk each: the grid has to be a multiple of 8,
-// or the workgroups beyond the last multiple walk tiles of their XCD a second time (and add their dW2 / db2 twice).
-static int edge64_bwd_grid(const ngpde_graph *g, int per_xcd_cap = 64) {
-  const int n_tiles = (int)(g->n_sched / kTileRows);
-  return 8 * std::max(1, std::min(per_xcd_cap, (n_tiles + 7) / 8));   // persistent workgroups, a multiple of the 8 XCDs
-}
+// one [65][64] slab per workgroup of the larger grid (two workgroups per CU).
 bool edge_mlp64_bwd_applicable(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
   if (env_off("NGPDE_NO_EDGE64")) return false;
   if (!a.P || !a.Q || a.Eterm || a.h1 != kW || a.n_tail != 1 || a.dw != kW) return false;
@@ -870,7 +666,7 @@ bool edge_mlp64_bwd_applicable(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
   const bool a2 = a.act2 == a.act1 || a.act2 == NGPDE_ACT_IDENTITY;
   return a1 && a2;
 }
-static size_t edge64_slab_bytes(const ngpde_graph *g) { return ((size_t)edge64_bwd_grid(g) * (kW + 1) * kW * sizeof(float) + 255) / 256 * 256; }
+static size_t edge64_slab_bytes(const ngpde_graph *g) { return slab_bytes(edge_persistent_grid(g, 64), kW, kW); }
 // the by-source sum inside the launch (no [E][64] array): no per-edge term, every halo within kDqStride rows
 bool edge_mlp64_bwd_dq_in_launch(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
   if (env_off("NGPDE_EDGE64_NO_DQ")) return false;
@@ -883,9 +679,8 @@ size_t edge_mlp64_bwd_workspace(const ngpde_graph *g) {
 
 int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hipStream_t stream) {
   EdgeMlp64BwdK k;
-  k.sched = g->by_t.sched; k.halo = g->by_t.halo; k.slots = g->by_t.slots;
-  k.n_tiles = (int)(g->n_sched / kTileRows); k.aggr = a.aggr;
-  k.halo_rows = std::max<int>(kTileRows, std::min<int>(kHaloCap, g->by_t.max_halo));
+  fill_tile_args(g, k);
+  k.aggr = a.aggr;
   k.P = a.P; k.Q = a.Q; k.wt = a.wt; k.bias = a.bias; k.dout = a.dout;
   k.dP = a.dP; k.dE = a.dE; k.partial = (float *)a.workspace;
   const bool dq = edge_mlp64_bwd_dq_in_launch(g, a);
@@ -899,25 +694,18 @@ int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hip
   k.dQ = dq ? a.dQ : nullptr;
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kChunk4 * kTS + 2 * (size_t)kW * kTS) * sizeof(float);
   // two workgroups per CU, or one when the halo region is large (the workspace holds slabs for the larger grid)
-  const int grid = edge64_bwd_grid(g, lds + 4096 <= 80 * 1024 ? 64 : 32);
-  auto launch = [&](auto kernel) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kT4), lds, stream, k);
-    return hipSuccess;
-  };
-  hipError_t le;
+  const int grid = edge_persistent_grid(g, lds + 4096 <= 80 * 1024 ? 64 : 32);
+  auto launch = [&](auto kernel) { return launch_with_lds(kernel, grid, kT4, lds, stream, k, "edge_mlp64_bwd_kernel"); };
+  int32_t st;
   const bool same = a.act2 == a.act1;
 #define NGPDE_E64B(A1, A2) (dq ? launch(edge_mlp64_bwd_kernel<A1, A2, true>) : launch(edge_mlp64_bwd_kernel<A1, A2, false>))
   switch (a.act1) {
-    case NGPDE_ACT_SWISH: le = same ? NGPDE_E64B(NGPDE_ACT_SWISH, NGPDE_ACT_SWISH) : NGPDE_E64B(NGPDE_ACT_SWISH, NGPDE_ACT_IDENTITY); break;
-    case NGPDE_ACT_RELU: le = same ? NGPDE_E64B(NGPDE_ACT_RELU, NGPDE_ACT_RELU) : NGPDE_E64B(NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY); break;
-    default: le = same ? NGPDE_E64B(NGPDE_ACT_TANH, NGPDE_ACT_TANH) : NGPDE_E64B(NGPDE_ACT_TANH, NGPDE_ACT_IDENTITY); break;
+    case NGPDE_ACT_SWISH: st = same ? NGPDE_E64B(NGPDE_ACT_SWISH, NGPDE_ACT_SWISH) : NGPDE_E64B(NGPDE_ACT_SWISH, NGPDE_ACT_IDENTITY); break;
+    case NGPDE_ACT_RELU: st = same ? NGPDE_E64B(NGPDE_ACT_RELU, NGPDE_ACT_RELU) : NGPDE_E64B(NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY); break;
+    default: st = same ? NGPDE_E64B(NGPDE_ACT_TANH, NGPDE_ACT_TANH) : NGPDE_E64B(NGPDE_ACT_TANH, NGPDE_ACT_IDENTITY); break;
   }
 #undef NGPDE_E64B
-  if (le != hipSuccess) return fail(NGPDE_ERR_HIP, "edge_mlp64_bwd_kernel: LDS request of %zu bytes refused: %s", lds, hipGetErrorString(le));
-  NGPDE_LAUNCH_CHECK("edge_mlp64_bwd_kernel");
-  int32_t st;
+  if (st) return st;
   if ((st = launch_dense_weight_reduce(grid, kW, kW, k.partial, a.dwt, a.dbias, stream))) return st;
   if (dq) {
     if (hinv->n_listed > 0) {

@@ -13,20 +13,18 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "edge_mlp_tile.h"
 #include "stamps.h"
 
 namespace ngpde {
 
 namespace {
 
-constexpr int kT = 512, kW = 64, kTS = kW + 4, kChunk = 128, kGroups = 32;   // kChunk = 8 waves x 16 edges
+constexpr int kT = 512, kChunk = 128, kGroups = 32;   // kChunk = 8 waves x 16 edges (kW, kTS: edge_mlp_tile.h)
+using Shape = RowPerGroup;
 
-
-struct EdgeMlpK {
-  const int4 *sched;
-  const int2 *halo;
-  const uint8_t *slots;
-  int n_tiles, h1, act1, aggr, halo_rows;
+struct EdgeMlpK : EdgeTileArgs {
+  int h1, act1, aggr;
   const float *P, *Q, *Eterm;
   int n_tail;
   int din[3], dout[3], act[3];
@@ -34,27 +32,6 @@ struct EdgeMlpK {
   float *out;
   float *save_z[4];   // [0]: z1 [E][h1]; [k]: pre-activation of tail layer k [E][dout_k]; nullable
   NGPDE_STAMP_FIELD
-};
-
-__device__ __forceinline__ int xcd_tile(int b, int nb) {
-  const int x = b % 8, k = b / 8;
-  const int q = nb / 8, r = nb % 8;
-  return x * q + min(x, r) + k;
-}
-
-__device__ __forceinline__ float4 load4_guard(const float *base, size_t row, int width, int q) {
-  return (4 * q < width) ? *reinterpret_cast<const float4 *>(base + row * width + 4 * q) : f4_zero();
-}
-
-// tile metadata / rows of one tile held in registers between the moment they are fetched (under the previous tile's
-// arithmetic) and the moment they are staged into LDS
-struct TileMeta {
-  int4 sc;
-  uint4 s0, s1;
-  int2 he[3];
-};
-struct TileRows {
-  float4 prow, hv[3];
 };
 
 // Register-chained message MLP.  A wave owns 16 edges of the chunk; lane (i = lane & 15, kq = lane >> 4) holds, for edge i,
@@ -81,24 +58,7 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
   const int ei = lane & 15, kq = lane >> 4;         // MFMA role: edge ei of the wave's 16, k-quarter kq
   const int h1 = p.h1, zero_slot = p.halo_rows;
 
-  // persistent workgroup: XCD x = blockIdx % 8 owns a contiguous range of tiles; its workgroups stride through it
-  const int xcd = blockIdx.x & 7, wg_in_xcd = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-  const int range_len = p.n_tiles / 8 + (xcd < p.n_tiles % 8 ? 1 : 0);
-  const int range_lo = xcd * (p.n_tiles / 8) + min(xcd, p.n_tiles % 8);
-
-  auto fetch_meta = [&](int tile, TileMeta &m) {
-    m.sc = p.sched[(size_t)tile * kTileRows + grp];
-    m.s0 = reinterpret_cast<const uint4 *>(p.slots)[((size_t)tile * kTileRows + grp) * 2];
-    m.s1 = reinterpret_cast<const uint4 *>(p.slots)[((size_t)tile * kTileRows + grp) * 2 + 1];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) m.he[k] = p.halo[(size_t)tile * kHaloCap + min(grp + k * kGroups, kHaloCap - 1)];
-  };
-  auto fetch_rows = [&](const TileMeta &m, TileRows &r) {
-    r.prow = p.P ? load4_guard(p.P, max(m.sc.x, 0), h1, q) : f4_zero();
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      r.hv[k] = (p.Q && grp + k * kGroups < p.halo_rows) ? load4_guard(p.Q, m.he[k].x, h1, q) : f4_zero();
-  };
+  const EdgeTileRange tr(p.n_tiles);   // persistent workgroup: strides through its XCD's range of tiles
 
   // ---- once per workgroup: tail weights as W^T rows (output j, contiguous inputs) and biases in LDS
   // (all loads of all layers first, unconditional from clamped addresses, pinned, then selected and written: a `cond ? load : 0` is an
@@ -135,58 +95,33 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
       if (tid < kW) ldsBias[l * kW + tid] = (p.bias[l] && tid < doutl) ? p.bias[l][tid] : 0.f;
     }
   }
-  if (grp == 0) *reinterpret_cast<float4 *>(&ldsQ[zero_slot * kTS + 4 * q]) = f4_zero();   // the all-zero row
+  zero_halo_row(ldsQ, zero_slot, grp, q);
 
-  TileMeta meta;
-  TileRows rows;
-  int jt = wg_in_xcd;
-  if (jt < range_len) {
-    fetch_meta(range_lo + jt, meta);
-    fetch_rows(meta, rows);
+  TileMeta<Shape> meta;
+  TileRows<Shape> rows;
+  int jt = tr.wg_in_xcd;
+  if (jt < tr.range_len) {
+    fetch_meta(p, tr.range_lo + jt, grp, q, meta);
+    fetch_rows<true>(p.P, p.Q, h1, p.halo_rows, meta, grp, q, rows);
   }
   const int last_w = (NTAIL > 0) ? p.dout[NTAIL - 1] : h1;
 
-  for (; jt < range_len; jt += wgs_per_xcd) {
-    const bool first_tile = (jt == wg_in_xcd + 4 * wgs_per_xcd);   // a tile in steady state (the fifth of the workgroup)
+  for (; jt < tr.range_len; jt += tr.wgs_per_xcd) {
+    const bool first_tile = (jt == tr.wg_in_xcd + 4 * tr.wgs_per_xcd);   // a tile in steady state (the fifth of the workgroup)
     if (first_tile) { NGPDE_STAMP(p.stamps, 16, 0, memtime); NGPDE_STAMP(p.stamps, 16, 8, memrealtime); }
     // ---- stage this tile (fetched under the previous tile's arithmetic)
     const int4 sc = meta.sc;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int hh = grp + k * kGroups;
-      if (hh < p.halo_rows) *reinterpret_cast<float4 *>(&ldsQ[hh * kTS + 4 * q]) = rows.hv[k];
-    }
-    *reinterpret_cast<float4 *>(&ldsP[grp * kTS + 4 * q]) = rows.prow;
-    if (q == 0) {
-      ldsOff[grp + 1] = sc.x >= 0 ? sc.z : 0;   // degrees; turned into offsets below
-      ldsRs[grp] = sc.y;
-      if (grp == 0) ldsOff[0] = 0;
-    }
-    if (q < 8) {
-      const unsigned w[8] = {meta.s0.x, meta.s0.y, meta.s0.z, meta.s0.w, meta.s1.x, meta.s1.y, meta.s1.z, meta.s1.w};
-      unsigned v = 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v = (q == j) ? w[j] : v;
-      ldsSlots[grp * 8 + q] = v;
-    }
+    stage_rows(rows, p.halo_rows, grp, q, ldsQ, ldsP);
+    stage_tile_degrees<true>(meta, grp, q, ldsOff, ldsSlots, ldsRs);   // degrees; turned into offsets below
     // ---- next tile: metadata now (one L2 round trip, lands during the prefix sums), rows after the first chunk
-    const int jn = jt + wgs_per_xcd;
-    const bool has_next = jn < range_len;       // workgroup-uniform
-    if (has_next) fetch_meta(range_lo + jn, meta);
+    const int jn = jt + tr.wgs_per_xcd;
+    const bool has_next = jn < tr.range_len;       // workgroup-uniform
+    if (has_next) fetch_meta(p, tr.range_lo + jn, grp, q, meta);
     __syncthreads();
-    if (tid < kGroups) {   // inclusive scan of the 32 degrees inside wave 0 (DPP shuffles, no LDS round trips)
-      int v = ldsOff[tid + 1];
-#pragma unroll
-      for (int o = 1; o < kGroups; o <<= 1) {
-        const int u = __shfl_up(v, o);
-        if (tid >= o) v += u;
-      }
-      ldsOff[tid + 1] = v;
-    }
+    scan_tile_degrees(ldsOff, tid);
     __syncthreads();
-    const int total = ldsOff[kGroups];
-    const int my_lo = ldsOff[grp], my_hi = ldsOff[grp + 1];
-    for (int k = my_lo + q; k < my_hi; k += 16) ldsRowOf[k] = (uint8_t)grp;   // deg <= kSlotWidth: total <= 1024
+    int total, my_lo, my_hi;
+    expand_tile_edges(ldsOff, ldsRowOf, grp, q, total, my_lo, my_hi);
 
     float4 racc;
     if (p.aggr == NGPDE_AGGR_MAX) racc = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
@@ -202,14 +137,9 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
       const bool wave_on = c0 + wave * 16 < total;   // wave-uniform
       const int k = c0 + wave * 16 + ei;
       const bool valid = k < total;
-      int r = 0, slot = zero_slot;
-      size_t pe = 0;
-      if (valid) {
-        r = ldsRowOf[k];
-        const int j = k - ldsOff[r];
-        slot = (ldsSlots[r * 8 + (j >> 2)] >> (8 * (j & 3))) & 0xff;
-        pe = (size_t)(ldsRs[r] + j);
-      }
+      int r, slot;
+      size_t pe;
+      lane_edge(ldsRowOf, ldsOff, ldsSlots, ldsRs, k, valid, zero_slot, r, slot, pe);
       // ---- a1 = act1(P[t] + Q[s] + E), features 16 ct + 4 kq .. + 3
       float4 a[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
       if (wave_on) {
@@ -228,7 +158,7 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
       }
       if (c0 == 0 && first_tile) NGPDE_STAMP(p.stamps, 16, 2, memtime);
       if (has_next && !rows_fetched) {   // the next tile's rows: in flight across this tile's MFMAs
-        fetch_rows(meta, rows);
+        fetch_rows<true>(p.P, p.Q, h1, p.halo_rows, meta, grp, q, rows);
         rows_fetched = true;
       }
       // ---- remaining Dense layers, transposed product on MFMA, chained in registers
@@ -276,21 +206,17 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
         *reinterpret_cast<float4 *>(&ldsMsg[(wave * 16 + ei) * kTS + 16 * mt + 4 * kq]) = a[mt];
       __syncthreads();
       if (c0 == 0 && first_tile) NGPDE_STAMP(p.stamps, 16, 4, memtime);
-      {
-        const int lo = max(my_lo, c0), hi = min(my_hi, c0 + kChunk);
-        for (int kk = lo; kk < hi; ++kk) {
-          const float4 m = *reinterpret_cast<const float4 *>(&ldsMsg[(kk - c0) * kTS + 4 * q]);
-          if (p.aggr == NGPDE_AGGR_MAX) racc = make_float4(fmaxf(racc.x, m.x), fmaxf(racc.y, m.y), fmaxf(racc.z, m.z), fmaxf(racc.w, m.w));
-          else if (p.aggr == NGPDE_AGGR_MIN) racc = make_float4(fminf(racc.x, m.x), fminf(racc.y, m.y), fminf(racc.z, m.z), fminf(racc.w, m.w));
-          else if (p.aggr == NGPDE_AGGR_MUL) racc = f4_mul(racc, m);
-          else racc = f4_add(racc, m);
-        }
-      }
+      row_fold_chunk(ldsMsg, c0, kChunk, my_lo, my_hi, q, racc, [&](float4 acc, float4 m) {
+        if (p.aggr == NGPDE_AGGR_MAX) return make_float4(fmaxf(acc.x, m.x), fmaxf(acc.y, m.y), fmaxf(acc.z, m.z), fmaxf(acc.w, m.w));
+        if (p.aggr == NGPDE_AGGR_MIN) return make_float4(fminf(acc.x, m.x), fminf(acc.y, m.y), fminf(acc.z, m.z), fminf(acc.w, m.w));
+        if (p.aggr == NGPDE_AGGR_MUL) return f4_mul(acc, m);
+        return f4_add(acc, m);
+      });
       __syncthreads();
       if (c0 == 0 && first_tile) NGPDE_STAMP(p.stamps, 16, 5, memtime);
     }
     if (first_tile) NGPDE_STAMP(p.stamps, 16, 6, memtime);
-    if (has_next && !rows_fetched) fetch_rows(meta, rows);   // a tile without edges
+    if (has_next && !rows_fetched) fetch_rows<true>(p.P, p.Q, h1, p.halo_rows, meta, grp, q, rows);   // a tile without edges
     if (sc.x >= 0 && 4 * q < last_w) {
       const int deg = my_hi - my_lo;
       if (p.aggr == NGPDE_AGGR_MEAN) racc = deg > 0 ? f4_scale(1.0f / (float)deg, racc) : f4_zero();
@@ -310,11 +236,8 @@ __global__ __launch_bounds__(kT, (NTAIL <= 1 ? 4 : 2)) void edge_mlp_fused_fwd_k
 // dz1 goes to HBM once ([E][h1], p order: it is dE and the input of the by-source sum that gives dQ) and through LDS into
 // the in-tile segmented sum that gives dP.  At the end the 8 waves fold their dW2 / db2 accumulators into one slab per
 // workgroup in a fixed order; a reduce kernel sums the slabs.  No atomics.
-struct EdgeMlpBwdK {
-  const int4 *sched;
-  const int2 *halo;
-  const uint8_t *slots;
-  int n_tiles, h1, act1, aggr, halo_rows, n_tail, dw, act2;   // dw = width of the tail layer's output (NTAIL = 1)
+struct EdgeMlpBwdK : EdgeTileArgs {
+  int h1, act1, aggr, n_tail, dw, act2;   // dw = width of the tail layer's output (NTAIL = 1)
   const float *P, *Q, *Eterm, *wt, *bias, *dout;
   float *dP, *dE, *partial;   // partial: [n_workgroups][(h1 + 1)][dw]  (row h1 = bias gradient)
 };
@@ -341,141 +264,48 @@ __global__ __launch_bounds__(kT, 2) void edge_mlp_fused_bwd_kernel(const EdgeMlp
   const int ei = lane & 15, kq = lane >> 4;
   const int h1 = p.h1, zero_slot = p.halo_rows, dw = NTAIL ? p.dw : p.h1;
 
-  const int xcd = blockIdx.x & 7, wg_in_xcd = blockIdx.x >> 3, wgs_per_xcd = gridDim.x >> 3;
-  const int range_len = p.n_tiles / 8 + (xcd < p.n_tiles % 8 ? 1 : 0);
-  const int range_lo = xcd * (p.n_tiles / 8) + min(xcd, p.n_tiles % 8);
+  const EdgeTileRange tr(p.n_tiles);
 
-  auto fetch_meta = [&](int tile, TileMeta &m) {
-    m.sc = p.sched[(size_t)tile * kTileRows + grp];
-    m.s0 = reinterpret_cast<const uint4 *>(p.slots)[((size_t)tile * kTileRows + grp) * 2];
-    m.s1 = reinterpret_cast<const uint4 *>(p.slots)[((size_t)tile * kTileRows + grp) * 2 + 1];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) m.he[k] = p.halo[(size_t)tile * kHaloCap + min(grp + k * kGroups, kHaloCap - 1)];
-  };
-
-  if (NTAIL) {
-    const int j = tid % kW, kg0 = tid / kW;
-#pragma unroll
-    for (int ps = 0; ps < 2; ++ps) {
-      const int k = 4 * (kg0 + 8 * ps);
-      float t[4], u[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        t[r] = (k + r < h1 && j < dw) ? p.wt[(size_t)(k + r) * dw + j] : 0.f;        // W2^T row j (output), inputs k..k+3
-        u[r] = (j < h1 && k + r < dw) ? p.wt[(size_t)j * dw + k + r] : 0.f;          // W2 row j (input), outputs k..k+3
-      }
-      *reinterpret_cast<float4 *>(&ldsWf[j * kTS + k]) = make_float4(t[0], t[1], t[2], t[3]);
-      *reinterpret_cast<float4 *>(&ldsWb[j * kTS + k]) = make_float4(u[0], u[1], u[2], u[3]);
-    }
-    if (tid < kW) ldsBias[tid] = (p.bias && tid < dw) ? p.bias[tid] : 0.f;
-  }
-  if (grp == 0) *reinterpret_cast<float4 *>(&ldsQ[zero_slot * kTS + 4 * q]) = f4_zero();
+  if (NTAIL) stage_weights<kT, true, true>(p.wt, p.bias, h1, dw, tid, ldsWf, ldsWb, ldsBias);   // W2^T, W2, b2
+  zero_halo_row(ldsQ, zero_slot, grp, q);
 
   // dW2 accumulators of this wave: tile (ct, mt) <-> rows 16 ct .. + 15 (inputs) x columns 16 mt .. + 15 (outputs)
-  f32x4 accW[NTAIL ? 4 : 1][NTAIL ? 4 : 1];
-  float4 dbacc[NTAIL ? 4 : 1];
+  f32x4 accW[4][4];
+  float4 dbacc[4];
 #pragma unroll
-  for (int a = 0; a < (NTAIL ? 4 : 1); ++a) {
+  for (int a = 0; a < 4; ++a) {
     dbacc[a] = f4_zero();
 #pragma unroll
-    for (int b = 0; b < (NTAIL ? 4 : 1); ++b) accW[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < 4; ++b) accW[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
 
-  // the per-edge forward the pullback recomputes: z1 = P_i + Q_j + E_e, a1 = act1(z1) (zero on padded features / invalid edges) ...
-  auto first_layer = [&](int r, int slot, size_t pe, bool valid, float4 (&z1)[4], float4 (&a1)[4]) {
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-      const int f = 16 * ct + 4 * kq;
-      float4 z = f4_add(*reinterpret_cast<const float4 *>(&ldsP[r * kTS + f]), *reinterpret_cast<const float4 *>(&ldsQ[slot * kTS + f]));
-      if (p.Eterm && valid && f < h1) z = f4_add(z, *reinterpret_cast<const float4 *>(p.Eterm + pe * h1 + f));
-      z1[ct] = z;
-      a1[ct] = z;
-    }
-    f4n_act<4>(p.act1, a1);
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-      if (!(valid && 16 * ct + 4 * kq < h1)) a1[ct] = f4_zero();
-  };
-  // ... and z2 = W2^T a1 + b2 (transposed product: the D layout is the operand layout of the next product)
-  auto second_layer = [&](const float4 (&a1)[4], float4 (&z2)[4]) {
-    const int n_ct = (h1 + 15) >> 4, n_mt = (dw + 15) >> 4;   // uniform
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      z2[mt] = f4_zero();
-      if (mt < n_mt) {
-        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float *wl = ldsWf + (mt * 16 + ei) * kTS + 4 * kq;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-          if (ct < n_ct) {
-            const float4 w4 = *reinterpret_cast<const float4 *>(wl + 16 * ct);
-            acc = mfma16(w4.x, a1[ct].x, acc);
-            acc = mfma16(w4.y, a1[ct].y, acc);
-            acc = mfma16(w4.z, a1[ct].z, acc);
-            acc = mfma16(w4.w, a1[ct].w, acc);
-          }
-        }
-        const float4 b4 = *reinterpret_cast<const float4 *>(&ldsBias[16 * mt + 4 * kq]);
-        z2[mt] = make_float4(acc[0] + b4.x, acc[1] + b4.y, acc[2] + b4.z, acc[3] + b4.w);
-      }
-    }
-  };
   const bool mul = p.aggr == NGPDE_AGGR_MUL, ext = p.aggr == NGPDE_AGGR_MAX || p.aggr == NGPDE_AGGR_MIN, want_max = p.aggr == NGPDE_AGGR_MAX;
 
-  TileMeta meta;
-  int jt = wg_in_xcd;
-  if (jt < range_len) fetch_meta(range_lo + jt, meta);
+  TileMeta<Shape> meta;
+  int jt = tr.wg_in_xcd;
+  if (jt < tr.range_len) fetch_meta(p, tr.range_lo + jt, grp, q, meta);
 
-  for (; jt < range_len; jt += wgs_per_xcd) {
+  for (; jt < tr.range_len; jt += tr.wgs_per_xcd) {
     const int4 sc = meta.sc;
     // ---- stage the tile: Q halo rows, P rows, gradient rows (the loads of a tile are issued here; the next tile's metadata
     // is prefetched below)
     {
       const int node = max(sc.x, 0);
-      const float4 prow = (p.P && 4 * q < h1) ? *reinterpret_cast<const float4 *>(p.P + (size_t)node * h1 + 4 * q) : f4_zero();
-      float4 hv[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        hv[k] = (p.Q && grp + k * kGroups < p.halo_rows && 4 * q < h1)
-                    ? *reinterpret_cast<const float4 *>(p.Q + (size_t)meta.he[k].x * h1 + 4 * q) : f4_zero();
+      TileRows<Shape> rows;
+      fetch_rows<true>(p.P, p.Q, h1, p.halo_rows, meta, grp, q, rows);
       float4 grow = (sc.x >= 0 && 4 * q < dw) ? *reinterpret_cast<const float4 *>(p.dout + (size_t)node * dw + 4 * q) : f4_zero();
       if (p.aggr == NGPDE_AGGR_MEAN) grow = sc.z > 0 ? f4_scale(1.0f / (float)sc.z, grow) : f4_zero();
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int hh = grp + k * kGroups;
-        if (hh < p.halo_rows) *reinterpret_cast<float4 *>(&ldsQ[hh * kTS + 4 * q]) = hv[k];
-      }
-      *reinterpret_cast<float4 *>(&ldsP[grp * kTS + 4 * q]) = prow;
+      stage_rows(rows, p.halo_rows, grp, q, ldsQ, ldsP);
       *reinterpret_cast<float4 *>(&ldsG[grp * kTS + 4 * q]) = grow;
     }
-    if (q == 0) {
-      ldsOff[grp + 1] = sc.x >= 0 ? sc.z : 0;
-      ldsRs[grp] = sc.y;
-      if (grp == 0) ldsOff[0] = 0;
-    }
-    if (q < 8) {
-      const unsigned w[8] = {meta.s0.x, meta.s0.y, meta.s0.z, meta.s0.w, meta.s1.x, meta.s1.y, meta.s1.z, meta.s1.w};
-      unsigned v = 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v = (q == j) ? w[j] : v;
-      ldsSlots[grp * 8 + q] = v;
-    }
-    const int jn = jt + wgs_per_xcd;
-    if (jn < range_len) fetch_meta(range_lo + jn, meta);
+    stage_tile_degrees<true>(meta, grp, q, ldsOff, ldsSlots, ldsRs);
+    const int jn = jt + tr.wgs_per_xcd;
+    if (jn < tr.range_len) fetch_meta(p, tr.range_lo + jn, grp, q, meta);
     __syncthreads();
-    if (tid < kGroups) {
-      int v = ldsOff[tid + 1];
-#pragma unroll
-      for (int o = 1; o < kGroups; o <<= 1) {
-        const int u = __shfl_up(v, o);
-        if (tid >= o) v += u;
-      }
-      ldsOff[tid + 1] = v;
-    }
+    scan_tile_degrees(ldsOff, tid);
     __syncthreads();
-    const int total = ldsOff[kGroups];
-    const int my_lo = ldsOff[grp], my_hi = ldsOff[grp + 1];
-    for (int k = my_lo + q; k < my_hi; k += 16) ldsRowOf[k] = (uint8_t)grp;
+    int total, my_lo, my_hi;
+    expand_tile_edges(ldsOff, ldsRowOf, grp, q, total, my_lo, my_hi);
     float4 racc = f4_zero();
     __syncthreads();
 
@@ -490,21 +320,16 @@ __global__ __launch_bounds__(kT, 2) void edge_mlp_fused_bwd_kernel(const EdgeMlp
         const bool wave_on = c0 + wave * 16 < total;   // wave-uniform
         const int k = c0 + wave * 16 + ei;
         const bool valid = k < total;
-        int r = 0, slot = zero_slot;
-        size_t pe = 0;
-        if (valid) {
-          r = ldsRowOf[k];
-          const int j = k - ldsOff[r];
-          slot = (ldsSlots[r * 8 + (j >> 2)] >> (8 * (j & 3))) & 0xff;
-          pe = (size_t)(ldsRs[r] + j);
-        }
+        int r, slot;
+        size_t pe;
+        lane_edge(ldsRowOf, ldsOff, ldsSlots, ldsRs, k, valid, zero_slot, r, slot, pe);
         float *mine = ldsS + (size_t)(wave * 16) * kTS;
         float4 m[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
         if (wave_on) {
           float4 z1[4], a1[4];
-          first_layer(r, slot, pe, valid, z1, a1);
+          first_layer(ldsP, ldsQ, p.Eterm, h1, p.act1, r, slot, pe, valid, kq, z1, a1);   // the per-edge forward, recomputed
           if (NTAIL) {
-            second_layer(a1, m);
+            dense_transposed<true>(ldsWf, ldsBias, h1, dw, ei, kq, a1, m);
             f4n_act<4>(p.act2, m);
           } else {
 #pragma unroll
@@ -540,19 +365,14 @@ __global__ __launch_bounds__(kT, 2) void edge_mlp_fused_bwd_kernel(const EdgeMlp
       const bool wave_on = c0 + wave * 16 < total;   // wave-uniform
       const int k = c0 + wave * 16 + ei;
       const bool valid = k < total;
-      int r = 0, slot = zero_slot;
-      size_t pe = 0;
-      if (valid) {
-        r = ldsRowOf[k];
-        const int j = k - ldsOff[r];
-        slot = (ldsSlots[r * 8 + (j >> 2)] >> (8 * (j & 3))) & 0xff;
-        pe = (size_t)(ldsRs[r] + j);
-      }
+      int r, slot;
+      size_t pe;
+      lane_edge(ldsRowOf, ldsOff, ldsSlots, ldsRs, k, valid, zero_slot, r, slot, pe);
       float *mine = ldsS + (size_t)(wave * 16) * kTS;          // this wave's 16 rows of the staging tile
       float4 dz1[4] = {f4_zero(), f4_zero(), f4_zero(), f4_zero()};
       if (wave_on) {
         float4 z1[4], a1[4];
-        first_layer(r, slot, pe, valid, z1, a1);
+        first_layer(ldsP, ldsQ, p.Eterm, h1, p.act1, r, slot, pe, valid, kq, z1, a1);   // the per-edge forward, recomputed
         f4n_dact<4>(p.act1, z1);                       // z1 <- act1'(z1): only the derivative is needed from here on
         float4 gz[4];                                          // NTAIL = 0: g itself; NTAIL = 1: dz2 = g * act2'(z2)
 #pragma unroll
@@ -578,10 +398,9 @@ __global__ __launch_bounds__(kT, 2) void edge_mlp_fused_bwd_kernel(const EdgeMlp
         };
         if (!NTAIL && (mul || ext)) others(gz, a1);
         if (NTAIL) {
-          const int n_ct = (h1 + 15) >> 4, n_mt = (dw + 15) >> 4;   // uniform
           // ---- z2 (transposed product), dz2
           float4 z2[4];
-          second_layer(a1, z2);
+          dense_transposed<true>(ldsWf, ldsBias, h1, dw, ei, kq, a1, z2);
           if (mul || ext) {
             float4 m2[4] = {z2[0], z2[1], z2[2], z2[3]};
             f4n_act<4>(p.act2, m2);
@@ -593,50 +412,12 @@ __global__ __launch_bounds__(kT, 2) void edge_mlp_fused_bwd_kernel(const EdgeMlp
             gz[mt] = f4_mul(gz[mt], z2[mt]);                  // g is zero for invalid edges / padded features
             dbacc[mt] = f4_add(dbacc[mt], gz[mt]);
           }
-          // ---- dW2 += a1^T dz2 over this wave's 16 edges: both operands transposed through the wave's LDS rows
-#pragma unroll
-          for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<float4 *>(&mine[ei * kTS + 16 * ct + 4 * kq]) = a1[ct];
-          float a1T[4][4];
-#pragma unroll
-          for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int sI = 0; sI < 4; ++sI) a1T[ct][sI] = mine[(4 * sI + kq) * kTS + 16 * ct + ei];
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) *reinterpret_cast<float4 *>(&mine[ei * kTS + 16 * mt + 4 * kq]) = gz[mt];
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            if (mt < n_mt) {
-              float dzT[4];
-#pragma unroll
-              for (int sI = 0; sI < 4; ++sI) dzT[sI] = mine[(4 * sI + kq) * kTS + 16 * mt + ei];
-#pragma unroll
-              for (int ct = 0; ct < 4; ++ct) {
-                if (ct < n_ct) {
-#pragma unroll
-                  for (int sI = 0; sI < 4; ++sI) accW[ct][mt] = mfma16(a1T[ct][sI], dzT[sI], accW[ct][mt]);
-                }
-              }
-            }
-          }
+          weight_grad_products<true>(mine, a1, gz, h1, dw, ei, kq, accW);   // dW2 += a1^T dz2
           // ---- da1 (transposed product with W2), dz1
+          float4 da1[4];
+          dense_transposed<false>(ldsWb, nullptr, dw, h1, ei, kq, gz, da1);
 #pragma unroll
-          for (int ct = 0; ct < 4; ++ct) {
-            if (ct < n_ct) {
-              f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-              const float *wl = ldsWb + (ct * 16 + ei) * kTS + 4 * kq;
-#pragma unroll
-              for (int mt = 0; mt < 4; ++mt) {
-                if (mt < n_mt) {
-                  const float4 w4 = *reinterpret_cast<const float4 *>(wl + 16 * mt);
-                  acc = mfma16(w4.x, gz[mt].x, acc);
-                  acc = mfma16(w4.y, gz[mt].y, acc);
-                  acc = mfma16(w4.z, gz[mt].z, acc);
-                  acc = mfma16(w4.w, gz[mt].w, acc);
-                }
-              }
-              dz1[ct] = f4_mul(make_float4(acc[0], acc[1], acc[2], acc[3]), z1[ct]);
-            }
-          }
+          for (int ct = 0; ct < 4; ++ct) dz1[ct] = f4_mul(da1[ct], z1[ct]);
         } else {
 #pragma unroll
           for (int ct = 0; ct < 4; ++ct) dz1[ct] = f4_mul(gz[ct], z1[ct]);
@@ -652,10 +433,7 @@ __global__ __launch_bounds__(kT, 2) void edge_mlp_fused_bwd_kernel(const EdgeMlp
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<float4 *>(&mine[ei * kTS + 16 * ct + 4 * kq]) = dz1[ct];
       __syncthreads();
-      {
-        const int lo = max(my_lo, c0), hi = min(my_hi, c0 + kChunk);
-        for (int kk = lo; kk < hi; ++kk) racc = f4_add(racc, *reinterpret_cast<const float4 *>(&ldsS[(kk - c0) * kTS + 4 * q]));
-      }
+      row_sum_chunk(ldsS, c0, kChunk, my_lo, my_hi, q, racc);
       __syncthreads();
     }
     if (p.dP && sc.x >= 0 && 4 * q < h1) *reinterpret_cast<float4 *>(p.dP + (size_t)sc.x * h1 + 4 * q) = racc;
@@ -666,40 +444,10 @@ __global__ __launch_bounds__(kT, 2) void edge_mlp_fused_bwd_kernel(const EdgeMlp
     float *slab = ldsS;                                            // [(h1 + 1)][dw], needs 65 * 64 floats <= kChunk * kTS
     __syncthreads();
     for (int idx = tid; idx < (h1 + 1) * dw; idx += kT) slab[idx] = 0.f;
-    // db: sum the 16 edge lanes of each k-quarter inside the wave first
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      float v[4] = {dbacc[mt].x, dbacc[mt].y, dbacc[mt].z, dbacc[mt].w};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) v[c] += __shfl_xor(v[c], o);
-      }
-      dbacc[mt] = make_float4(v[0], v[1], v[2], v[3]);
-    }
+    fold_bias_lanes(dbacc);
     __syncthreads();
     for (int w = 0; w < kT / 64; ++w) {
-      if (wave == w) {
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int kin = 16 * ct + 4 * kq + r, o = 16 * mt + ei;
-              if (kin < h1 && o < dw) slab[kin * dw + o] += accW[ct][mt][r];
-            }
-        if (ei == 0) {
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            const int o = 16 * mt + 4 * kq;
-            if (o < dw) {
-              slab[h1 * dw + o] += dbacc[mt].x; slab[h1 * dw + o + 1] += dbacc[mt].y;
-              slab[h1 * dw + o + 2] += dbacc[mt].z; slab[h1 * dw + o + 3] += dbacc[mt].w;
-            }
-          }
-        }
-      }
+      if (wave == w) fold_slab<true>(slab, h1, dw, accW, dbacc, ei, kq);
       __syncthreads();
     }
     float *dst = p.partial + (size_t)blockIdx.x * (h1 + 1) * dw;
@@ -733,8 +481,8 @@ int32_t launch_edge_mlp_fused_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hi
   if (g->n_nodes == 0) return NGPDE_OK;
   if (edge_mlp64_fwd_applicable(g, a)) return launch_edge_mlp64_fwd(g, a, stream);
   EdgeMlpK k;
-  k.sched = g->by_t.sched; k.halo = g->by_t.halo; k.slots = g->by_t.slots;
-  k.n_tiles = (int)(g->n_sched / kTileRows); k.h1 = a.h1; k.act1 = a.act1; k.aggr = a.aggr;
+  fill_tile_args(g, k);   // (halo region sized by the largest halo of this graph's tiles)
+  k.h1 = a.h1; k.act1 = a.act1; k.aggr = a.aggr;
   k.P = a.P; k.Q = a.Q; k.Eterm = a.Eterm; k.n_tail = a.n_tail;
   for (int l = 0; l < 3; ++l) {
     k.din[l] = a.din[l]; k.dout[l] = a.dout[l]; k.act[l] = a.act[l]; k.wt[l] = a.wt[l]; k.bias[l] = a.bias[l];
@@ -742,35 +490,18 @@ int32_t launch_edge_mlp_fused_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hi
   k.out = a.out;
   for (int l = 0; l < 4; ++l) k.save_z[l] = a.save_z[l];
   NGPDE_STAMP_SET(k, kStampEdge, 0);
-  // LDS: the halo region is sized by the largest halo of this graph's tiles; persistent workgroups, a multiple of the 8 XCDs
-  k.halo_rows = std::max<int>(kTileRows, std::min<int>(kHaloCap, g->by_t.max_halo));
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kGroups * kTS + (size_t)a.n_tail * kW * kTS + (size_t)kChunk * kTS) * sizeof(float);
-  const int wgs_per_cu = (lds + 2048 <= 80 * 1024) ? 2 : 1;
-  const int per_xcd = std::max(1, std::min(32 * wgs_per_cu, (k.n_tiles + 7) / 8));
-  const dim3 grid(8 * per_xcd), block(kT);
-  auto launch = [&](auto kernel) -> hipError_t {
-    // more than 64 KB of dynamic LDS has to be requested explicitly
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, grid, block, lds, stream, k);
-    return hipSuccess;
-  };
-  hipError_t le;
+  const int grid = edge_persistent_grid(g, lds + 2048 <= 80 * 1024 ? 64 : 32);   // two workgroups per CU where the LDS allows
+  const char *name = "edge_mlp_fused_fwd_kernel";
   switch (a.n_tail) {
-    case 0: le = launch(edge_mlp_fused_fwd_kernel<0>); break;
-    case 1: le = launch(edge_mlp_fused_fwd_kernel<1>); break;
-    case 2: le = launch(edge_mlp_fused_fwd_kernel<2>); break;
-    default: le = launch(edge_mlp_fused_fwd_kernel<3>); break;
+    case 0: return launch_with_lds(edge_mlp_fused_fwd_kernel<0>, grid, kT, lds, stream, k, name);
+    case 1: return launch_with_lds(edge_mlp_fused_fwd_kernel<1>, grid, kT, lds, stream, k, name);
+    case 2: return launch_with_lds(edge_mlp_fused_fwd_kernel<2>, grid, kT, lds, stream, k, name);
+    default: return launch_with_lds(edge_mlp_fused_fwd_kernel<3>, grid, kT, lds, stream, k, name);
   }
-  if (le != hipSuccess) return fail(NGPDE_ERR_HIP, "edge_mlp_fused_fwd_kernel: LDS request of %zu bytes refused: %s", lds, hipGetErrorString(le));
-  NGPDE_LAUNCH_CHECK("edge_mlp_fused_fwd_kernel");
-  return NGPDE_OK;
 }
 
-static int edge_bwd_grid(const ngpde_graph *g) {
-  const int n_tiles = (int)(g->n_sched / kTileRows);
-  return 8 * std::max(1, std::min(32, (n_tiles + 7) / 8));   // one persistent workgroup per CU, a multiple of the 8 XCDs
-}
+static int edge_bwd_grid(const ngpde_graph *g) { return edge_persistent_grid(g, 32); }   // one persistent workgroup per CU
 
 bool edge_mlp_fused_bwd_supported(const ngpde_graph *g, int h1, int n_tail, int dw, int aggr) {
   if (!g || !g->has_norm || !g->by_t.halo_ok) return false;
@@ -796,26 +527,18 @@ int32_t launch_edge_mlp_fused_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a,
   if (edge_mlp64_bwd_applicable(g, a)) return launch_edge_mlp64_bwd(g, a, stream);   // (checks dE itself: not needed when it sums by source in the launch)
   NGPDE_REQUIRE(a.dE != nullptr || g->n_edges == 0, NGPDE_ERR_INVALID_ARGUMENT, "fused edge-MLP pullback: the [E][h1] buffer dE is required");
   EdgeMlpBwdK k;
-  k.sched = g->by_t.sched; k.halo = g->by_t.halo; k.slots = g->by_t.slots;
-  k.n_tiles = (int)(g->n_sched / kTileRows); k.h1 = a.h1; k.act1 = a.act1; k.aggr = a.aggr; k.n_tail = a.n_tail;
+  fill_tile_args(g, k);
+  k.h1 = a.h1; k.act1 = a.act1; k.aggr = a.aggr; k.n_tail = a.n_tail;
   k.dw = a.n_tail ? a.dw : a.h1; k.act2 = a.act2;
-  k.halo_rows = std::max<int>(kTileRows, std::min<int>(kHaloCap, g->by_t.max_halo));
   k.P = a.P; k.Q = a.Q; k.Eterm = a.Eterm; k.wt = a.wt; k.bias = a.bias; k.dout = a.dout;
   k.dP = a.dP; k.dE = a.dE; k.partial = (float *)a.workspace;
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + 2 * (size_t)kGroups * kTS + (size_t)kChunk * kTS + (a.n_tail ? 2 * (size_t)kW * kTS : 0) +
                       (a.aggr >= NGPDE_AGGR_MAX ? (size_t)kGroups * kTS : 0)) * sizeof(float);
-  const dim3 grid(edge_bwd_grid(g)), block(kT);
-  auto launch = [&](auto kernel) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, grid, block, lds, stream, k);
-    return hipSuccess;
-  };
-  const hipError_t le = a.n_tail ? launch(edge_mlp_fused_bwd_kernel<1>) : launch(edge_mlp_fused_bwd_kernel<0>);
-  if (le != hipSuccess) return fail(NGPDE_ERR_HIP, "edge_mlp_fused_bwd_kernel: LDS request of %zu bytes refused: %s", lds, hipGetErrorString(le));
-  NGPDE_LAUNCH_CHECK("edge_mlp_fused_bwd_kernel");
-  int32_t st;
-  if (a.n_tail && (st = launch_dense_weight_reduce((int)grid.x, a.h1, a.dw, k.partial, a.dwt, a.dbias, stream))) return st;
+  const int grid = edge_bwd_grid(g);
+  int32_t st = a.n_tail ? launch_with_lds(edge_mlp_fused_bwd_kernel<1>, grid, kT, lds, stream, k, "edge_mlp_fused_bwd_kernel")
+                        : launch_with_lds(edge_mlp_fused_bwd_kernel<0>, grid, kT, lds, stream, k, "edge_mlp_fused_bwd_kernel");
+  if (st) return st;
+  if (a.n_tail && (st = launch_dense_weight_reduce(grid, a.h1, a.dw, k.partial, a.dwt, a.dbias, stream))) return st;
   if (a.dQ && (st = launch_edge_sum_by_source(g, a.h1, a.dE, a.dQ, stream))) return st;
   return NGPDE_OK;
 }
