@@ -432,6 +432,65 @@ int32_t ngpde_group_reduce_backward(int64_t n_groups, int64_t n_rows, int32_t co
 int32_t ngpde_coo_add_self_loops(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, const float *w,
                                  int32_t *s_out, int32_t *t_out, float *w_out, ngpde_stream_t stream);
 
+/* ---- random graph sampling on a device COO list (src/NeuralGraphPDE.jl:4 re-exports GNNGraphs: sample_neighbors, rand_edge_split):
+ * a fresh sub-sample of every neighbourhood, or a random hold-out of the edges, per epoch, without the lists leaving the device.  The
+ * conventions are those of the block above: int32 lists with `index_base`, outputs sized by the caller to the upper bound given with
+ * each, n_nodes, n_edges and the number of draws <= 2^31 - 1 (refused beyond), NULL and negative arguments refused before any device
+ * call (NGPDE_ERR_INVALID_ARGUMENT), an edge end outside the node range NGPDE_ERR_DIMENSION_MISMATCH without a read or write through
+ * it, temporaries from hipMalloc inside the call (not capturable), the data-dependent count through a HOST pointer after one
+ * synchronisation of `stream`.  No float arithmetic and no racing writes: every result is bitwise equal from run to run.
+ * RANDOMNESS: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), stateless: a value is a
+ * pure function of (seed, stream, counter) -- key (lo32(seed), hi32(seed)), counter (c0, c1, stream, 0), the 64-bit draw
+ * out[0] | out[1] << 32 -- never of the thread, the launch geometry or the call order.  Streams: 1 = the neighbour keys, 2 = the draws
+ * with replacement, 3 = the split keys, so one seed gives the three operations independent values. */
+
+/* out[i] (device uint64[n]) = the draw at counter (lo32(first + i), c1, stream_id, 0): the generator's bits through the ABI, for tests.
+ * The samplers below evaluate the same device function in their kernels and write no keys they do not need. */
+int32_t ngpde_random_keys(uint64_t seed, uint32_t stream_id, uint32_t c1, uint64_t first, int64_t n, uint64_t *out, ngpde_stream_t stream);
+
+/* Rows longer than this are selected by a segmented sort instead of in LDS (below): 2048 keys of 8 bytes are the 16 KB of LDS a
+ * 256-thread workgroup stages, 9 workgroups per CU; rank counting is quadratic in the row, ~2 * 10^4 comparisons per thread here. */
+#define NGPDE_SAMPLE_LDS_ROW_MAX 2048
+
+/* sample_neighbors(g, nodes, K; dir, replace).  The ROW of a node is the list of COO positions of its inbound (dir NGPDE_DIR_IN) or
+ * outbound (NGPDE_DIR_OUT) edges in COO order (the stable grouping ngpde_coo_degree makes).  Only the rows of listed nodes take part.
+ *   nodes        device int64[n_listed], 0-based, distinct, or NULL (with n_listed 0): every node.  An entry outside 0 : n_nodes - 1
+ *                or a repeated one is NGPDE_ERR_INVALID_ARGUMENT, detected on the device and read back with the count.
+ *   k            -1: every edge of a listed row; 0: none; k < -1 refused
+ *   replace == 0 the edge at COO position e has the key draw(stream 1, counter (lo32(e), hi32(e))); a listed row keeps its min(k, deg)
+ *                edges with the smallest (key, e) -- a uniform k-subset, and since the key belongs to the edge, what a node gets does
+ *                not depend on which other nodes are listed.  A row with deg <= k is copied through without drawing; a longer one of
+ *                at most NGPDE_SAMPLE_LDS_ROW_MAX edges is selected in ONE launch for all rows by exact rank counting on keys drawn
+ *                in the kernel and staged in LDS (an edge is kept iff fewer than k edges of its row have a smaller (key, e)): a wave
+ *                per row of up to NGPDE_SAMPLE_LDS_ROW_MAX / 4 edges, the 256-thread workgroup per longer row; rows beyond the bound
+ *                go through rocprim::segmented_radix_sort_pairs of the keys, stable, so ties break by position there too (that sort
+ *                is enqueued whenever n_edges exceeds the bound, over empty segments if no row does: only the device knows).  The
+ *                kept edges are compacted in COO order.  Outputs hold up to n_edges entries.
+ *   replace != 0 (k >= 0): a listed node v with deg > 0 gets exactly k edges, draw j being entry (draw(stream 2, counter (v, j)) * deg)
+ *                >> 64 of its row; a node without edges gets none.  Output order: listed-node order (node order with nodes NULL),
+ *                then j.  Outputs hold up to n_listed * k (n_nodes * k with nodes NULL) entries.
+ *   s_out, t_out device int32: the sampled edges, with `index_base`;  eid_out device int64: their COO positions (0-based) in the input
+ *   n_out        host: the number of sampled edges.  Synchronises. */
+int32_t ngpde_coo_sample_neighbors(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t dir,
+                                   int64_t n_listed, const int64_t *nodes, int32_t k, int32_t replace, uint64_t seed, int32_t *s_out,
+                                   int32_t *t_out, int64_t *eid_out, int64_t *n_out, ngpde_stream_t stream);
+
+/* rand_edge_split(g, frac): a random partition of the edges into a first and a second part, n_first = round(frac * ...) made by the
+ * caller.  side_out device int32[n_edges]: 0 = first part, 1 = second; kept0 / kept1 device int64[n_edges] (upper bound each): the COO
+ * positions of the two parts, ascending; n0_out host: the size of the first part (the second has n_edges - n0).  Synchronises.
+ *   by_pair == 0 the key of edge e is draw(stream 3, counter (lo32(e), hi32(e))); the n_first edges with the smallest (key, e) -- one
+ *                stable 64-bit radix sort -- are the first part.  n_first <= n_edges.
+ *   by_pair != 0 for bidirected lists: the key is draw(stream 3, counter (min(s, t), max(s, t))), shared by both directions of a pair
+ *                and by parallel copies.  The RANKED edges are those with s <= t; n_first counts them (more than there are:
+ *                NGPDE_ERR_INVALID_ARGUMENT, read back with the count).  tau = the key of the ranked edge of rank n_first - 1; every
+ *                edge with key <= tau goes to the first part, so a pair is never torn (with parallel copies the first part may hold
+ *                more than n_first ranked edges); n_first == 0 sends everything to the second part.  The sort runs over all n_edges
+ *                keys and an inclusive scan of the ranked flags in sorted order finds the rank: the number of ranked edges never has
+ *                to reach the host. */
+int32_t ngpde_coo_rand_split(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int64_t n_first,
+                             int32_t by_pair, uint64_t seed, int32_t *side_out, int64_t *kept0, int64_t *kept1, int64_t *n0_out,
+                             ngpde_stream_t stream);
+
 /* GNOConv message (src/layers.jl:527-530): K_e = reshape(phi_out[:, e], cout, cin) column-major,
  * m_e = K_e * h[:, s_e].  k: [E][cin*cout] p order (element o + cout*i), h: [N][cin], m: [E][cout]. */
 int32_t ngpde_gno_contract_forward(const ngpde_graph_t *g, int32_t cin, int32_t cout, const float *k, const float *h,

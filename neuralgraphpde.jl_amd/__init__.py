@@ -17,6 +17,7 @@ from .msgpass import (aggregate_neighbors, apply_edges, copy_xi, copy_xj, e_mul_
 from .readout import (broadcast_edges, broadcast_nodes, graph_indicator, reduce_edges, reduce_nodes, softmax_edges, softmax_nodes)
 from .graphops import (add_self_loops, degree, getgraph, has_multi_edges, has_self_loops, induced_subgraph, is_bidirected,
                        remove_multi_edges, remove_self_loops, to_bidirected, unbatch)
+from .sampling import rand_edge_split, sample_neighbors
 from . import dist, optim, synth
 
 
@@ -34,5 +35,5 @@ __all__ = [
     "propagate", "apply_edges", "aggregate_neighbors", "softmax_edge_neighbors", "copy_xj", "copy_xi", "xi_dot_xj", "e_mul_xj", "w_mul_xj",
     "reduce_nodes", "reduce_edges", "softmax_nodes", "softmax_edges", "broadcast_nodes", "broadcast_edges", "graph_indicator",
     "degree", "has_self_loops", "has_multi_edges", "is_bidirected", "add_self_loops", "remove_self_loops", "remove_multi_edges",
-    "to_bidirected", "induced_subgraph", "getgraph", "unbatch",
+    "to_bidirected", "induced_subgraph", "getgraph", "unbatch", "sample_neighbors", "rand_edge_split",
 ]

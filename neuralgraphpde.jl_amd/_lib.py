@@ -39,6 +39,7 @@ TABLEAU = {"euler": 0, "tsit5": 1}
 _vp, _i32, _i64, _sz, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float
 
 MLP_MAX_LAYERS = 8
+SAMPLE_LDS_ROW_MAX = 2048          # NGPDE_SAMPLE_LDS_ROW_MAX
 
 
 class Mlp(C.Structure):
@@ -195,6 +196,10 @@ SIGNATURES = {
     "ngpde_group_reduce_forward": (_i32, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ngpde_group_reduce_backward": (_i32, [_i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ngpde_coo_add_self_loops": (_i32, [_i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_random_keys": (_i32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, _i64, _vp, _vp]),
+    "ngpde_coo_sample_neighbors": (_i32, [_i64, _i64, _vp, _vp, _i32, _i32, _i64, _vp, _i32, _i32, C.c_uint64, _vp, _vp, _vp,
+                                          C.POINTER(_i64), _vp]),
+    "ngpde_coo_rand_split": (_i32, [_i64, _i64, _vp, _vp, _i32, _i64, _i32, C.c_uint64, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
     "ngpde_gno_contract_forward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_gno_contract_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_gno_apply_supported": (_i32, [_i32, _i32]),
