@@ -875,32 +875,13 @@ struct GatSync {
 __device__ __forceinline__ bool gat_wait(const GatSync &s, const GatThread &t, int my_nbr, unsigned need, int *s_ok) {
   if (need == 0) return true;
   if (t.wave_u == 0) {
-    const unsigned *addr = (t.lane == 63) ? s.abort_word : (my_nbr >= 0 ? s.flags + 32 * my_nbr : nullptr);
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    bool ok = true;
-    for (unsigned it = 1;; ++it) {
-      unsigned f = need;
-      if (addr) f = __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__any((int)(t.lane == 63 && f != 0))) { ok = false; break; }              // somebody gave up
-      if (__all((int)(t.lane == 63 || f >= need))) break;
-      if ((it & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {   // ~2 s of the 100 MHz counter
-        if (t.lane == 0) __hip_atomic_store(s.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = false;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    if (t.lane == 0) *s_ok = ok ? 1 : 0;
+    const unsigned *const a[1] = {watch_first(s.abort_word, s.flags, t.lane, my_nbr)};
+    flag_poll<1>(a, s.abort_word, t.lane, need, s_ok);
   }
   __syncthreads();
   return *s_ok != 0;
 }
-// every storing wave drains, the workgroup meets, ONE lane publishes
-__device__ __forceinline__ void gat_publish(const GatSync &s, const GatThread &t, int tile, unsigned ph) {
-  wait_vmcnt0();
-  __syncthreads();
-  if (t.tid == 0) __hip_atomic_store(s.flags + 32 * tile, ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+__device__ __forceinline__ void gat_publish(const GatSync &s, const GatThread &t, int tile, unsigned ph) { flag_publish(s.flags, t.tid, ph, tile); }
 
 struct GatNodeFwdK {
   GatFwdK l;            // wt, a, bias, lists by target, n_tiles, act, slope (x, y, alpha, save_z are set per phase / unused)
@@ -921,6 +902,32 @@ struct GatNodeFwdK {
   size_t flag_stride, xs_stride, yz_stride, alpha_stride;
 };
 
+// What the two forward solver kernels set up before their first phase, once: the tile and its tables, the layer's constants, the
+// Runge-Kutta coefficients in LDS, the abort verdict, the lane's wait-list entry and the thread's own-row byte offset.
+struct GatNodeFwdFrame {
+  int tile, my_nbr;
+  TileMeta m;
+  HaloRegs<GD> hr;
+  float breg[4][4];
+  float4 b4;
+  bool ok;        // the thread's row is a node (not padding)
+  unsigned own;   // byte offset of the thread's 16 bytes of its own row
+};
+// (Kernel arguments by member, here and below: the whole block by reference has every member loaded at the kernel's entry -- more spills.)
+template <int H>
+__device__ __forceinline__ void gat_node_fwd_enter(const GatFwdK &l, const float *cf, const int *nbr, const GatFwdLds &L, const GatThread &t,
+                                                   float *ldsC, int *s_ok, GatNodeFwdFrame &f) {
+  f.tile = xcd_tile(blockIdx.x, l.n_tiles);
+  tile_meta_load(l.halo, l.slots, l.sched, f.tile, t.grp, t.q, f.hr, f.m);
+  tile_meta_words(f.hr, f.m);
+  gat_fwd_consts<H>(l, L, t, f.breg, f.b4);
+  if (t.tid < 64) ldsC[t.tid] = cf[t.tid];
+  if (t.tid == 0) *s_ok = 1;
+  f.my_nbr = nbr[(size_t)f.tile * kNbrStride + t.lane];
+  f.ok = f.m.sc.x >= 0;
+  f.own = (unsigned)max(f.m.sc.x, 0) * (unsigned)(GD * 4) + (unsigned)(t.q * 16);
+}
+
 // BATCH: a block-diagonal batch of identical structures (test/runtests.jl:89-102), two members at a time per workgroup: while one
 // member's rows and flag travel to the neighbours the workgroup computes the other member's phase (the idea of node_persistent.hip's
 // two-slot kernels; here nothing but the accumulators lives in registers across phases, so the slots simply take turns).
@@ -935,19 +942,8 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_batch_ker
   __shared__ int s_ok;
   const GatFwdLds L = {ldsXh, ldsS, ldsA, ldsAr, ldsV};
   const GatThread t = gat_thread();
-  const int tile = xcd_tile(blockIdx.x, p.l.n_tiles);
-  TileMeta m;
-  HaloRegs<GD> hr;
-  tile_meta_load(p.l.halo, p.l.slots, p.l.sched, tile, t.grp, t.q, hr, m);
-  tile_meta_words(hr, m);
-  float breg[4][4];
-  float4 b4;
-  gat_fwd_consts<H>(p.l, L, t, breg, b4);
-  if (t.tid < 64) ldsC[t.tid] = p.cf[t.tid];
-  if (t.tid == 0) s_ok = 1;
-  const int my_nbr = p.s.nbr[(size_t)tile * kNbrStride + t.lane];
-  const bool ok = m.sc.x >= 0;
-  const unsigned own = (unsigned)max(m.sc.x, 0) * (unsigned)(GD * 4) + (unsigned)(t.q * 16);
+  GatNodeFwdFrame f;
+  gat_node_fwd_enter<H>(p.l, p.cf, p.s.nbr, L, t, ldsC, &s_ok, f);
   const int S = p.S;
   const unsigned P = (unsigned)(p.n_steps * S);
   GatFwdK l = p.l;
@@ -957,7 +953,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_batch_ker
   for (int mb = 0; mb < p.n_members && !dead; mb += 2, ph0 += P) {
     const int nsl = min(2, p.n_members - mb);
     for (int sl = 0; sl < nsl; ++sl)   // u of the slot's member -> row 6 of the slot's scratch
-      if (ok) st4_g(p.kbuf + (size_t)(sl * 7 + 6) * p.row_elems, own, ld4_g(p.u_in + (size_t)(mb + sl) * p.row_elems, own));
+      if (f.ok) st4_g(p.kbuf + (size_t)(sl * 7 + 6) * p.row_elems, f.own, ld4_g(p.u_in + (size_t)(mb + sl) * p.row_elems, f.own));
     for (int n = 0; n < p.n_steps && !dead; ++n) {
       for (int i = 0; i < S && !dead; ++i) {
         const unsigned lp = (unsigned)(n * S + i) + 1, ph = ph0 + lp;
@@ -969,29 +965,29 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_batch_ker
           float *xs = p.xs + (size_t)(mb + sl) * p.xs_stride, *kb = p.kbuf + (size_t)sl * 7 * p.row_elems;
           const float *X = xs + (p.taped ? e : (e & 1)) * p.row_elems;
           const int row = (i + 1 < S) ? i + 1 : S;
-          if (!gat_wait(ys, t, my_nbr, lp > 1 ? ph - 1 : 0u, &s_ok)) { dead = true; break; }
-          halo_round2<GD, true, 16>(reinterpret_cast<const float4 *>(X), t.q, t.grp, ldsXh, hr);
+          if (!gat_wait(ys, t, f.my_nbr, lp > 1 ? ph - 1 : 0u, &s_ok)) { dead = true; break; }
+          halo_round2<GD, true, 16>(reinterpret_cast<const float4 *>(X), t.q, t.grp, ldsXh, f.hr);
           l.alpha = p.alpha ? p.alpha + (size_t)(mb + sl) * p.alpha_stride + e * p.alpha_elems : nullptr;
-          const float4 z = gat_fwd_compute<H>(l, L, t, m, tile, breg, b4);
+          const float4 z = gat_fwd_compute<H>(l, L, t, f.m, f.tile, f.breg, f.b4);
           const float4 y = f4_act(l.act, z);
-          if (p.yz && ok) st4_g(p.yz + (size_t)(mb + sl) * p.yz_stride + e * p.row_elems, own, l.act == NGPDE_ACT_RELU ? y : z);
-          float4 v = f4_scale(1.0f, ld4_g(kb + (size_t)6 * p.row_elems, own));
-          for (int j = 0; j < i; ++j) v = f4_fma(ldsC[row * 8 + j], ld4_g(kb + (size_t)j * p.row_elems, own), v);
+          if (p.yz && f.ok) st4_g(p.yz + (size_t)(mb + sl) * p.yz_stride + e * p.row_elems, f.own, l.act == NGPDE_ACT_RELU ? y : z);
+          float4 v = f4_scale(1.0f, ld4_g(kb + (size_t)6 * p.row_elems, f.own));
+          for (int j = 0; j < i; ++j) v = f4_fma(ldsC[row * 8 + j], ld4_g(kb + (size_t)j * p.row_elems, f.own), v);
           v = f4_fma(ldsC[row * 8 + i], y, v);
-          if (ok) {
-            if (i + 1 < S) st4_g(kb + (size_t)i * p.row_elems, own, y);
-            else st4_g(kb + (size_t)6 * p.row_elems, own, v);
-            if (last) st4_g(p.u_out + (size_t)(mb + sl) * p.row_elems, own, v);
-            else store_sc1(xs + (p.taped ? e + 1 : ((e + 1) & 1)) * p.row_elems, own, v);
+          if (f.ok) {
+            if (i + 1 < S) st4_g(kb + (size_t)i * p.row_elems, f.own, y);
+            else st4_g(kb + (size_t)6 * p.row_elems, f.own, v);
+            if (last) st4_g(p.u_out + (size_t)(mb + sl) * p.row_elems, f.own, v);
+            else store_sc1(xs + (p.taped ? e + 1 : ((e + 1) & 1)) * p.row_elems, f.own, v);
           }
-          if (!last) gat_publish(ys, t, tile, ph);
+          if (!last) gat_publish(ys, t, f.tile, ph);
           else __syncthreads();   // (the other slot's DMA must not land in rows this slot's waves still read)
         }
       }
     }
   }
-  if (dead && ok)
-    for (int mb = 0; mb < p.n_members; ++mb) st4_g(p.u_out + (size_t)mb * p.row_elems, own, f4_nan());
+  if (dead && f.ok)
+    for (int mb = 0; mb < p.n_members; ++mb) st4_g(p.u_out + (size_t)mb * p.row_elems, f.own, f4_nan());
 }
 
 template <int H>
@@ -1005,20 +1001,9 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_kernel(co
   __shared__ int s_ok;
   const GatFwdLds L = {ldsXh, ldsS, ldsA, ldsAr, ldsV};
   const GatThread t = gat_thread();
-  const int tile = xcd_tile(blockIdx.x, p.l.n_tiles);
-  TileMeta m;
-  HaloRegs<GD> hr;
-  tile_meta_load(p.l.halo, p.l.slots, p.l.sched, tile, t.grp, t.q, hr, m);
-  tile_meta_words(hr, m);
-  float breg[4][4];
-  float4 b4;
-  gat_fwd_consts<H>(p.l, L, t, breg, b4);
-  if (t.tid < 64) ldsC[t.tid] = p.cf[t.tid];
-  if (t.tid == 0) s_ok = 1;
-  const int my_nbr = p.s.nbr[(size_t)tile * kNbrStride + t.lane];
-  const bool ok = m.sc.x >= 0;
-  const unsigned own = (unsigned)max(m.sc.x, 0) * (unsigned)(GD * 4) + (unsigned)(t.q * 16);
-  float4 u = ok ? ld4_g(p.u_in, own) : f4_zero();
+  GatNodeFwdFrame f;
+  gat_node_fwd_enter<H>(p.l, p.cf, p.s.nbr, L, t, ldsC, &s_ok, f);
+  float4 u = f.ok ? ld4_g(p.u_in, f.own) : f4_zero();
   const int S = p.S;
   GatFwdK l = p.l;
   bool dead = false;
@@ -1032,29 +1017,29 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_fwd_persistent_kernel(co
       const float *X = p.xs + (p.taped ? e : (e & 1)) * p.row_elems;
       // the input of the next stage / the step update, as ngpde_rk_stage_combine forms it: 1 * u, then the k_j in order
       const int row = (i + 1 < S) ? i + 1 : S;
-      if (!gat_wait(p.s, t, my_nbr, ph - 1, &s_ok)) { dead = true; break; }
+      if (!gat_wait(p.s, t, f.my_nbr, ph - 1, &s_ok)) { dead = true; break; }
       NGPDE_STAMP(l.stamps, 16, 13, memtime);
-      halo_round2<GD, true, 16>(reinterpret_cast<const float4 *>(X), t.q, t.grp, ldsXh, hr);
+      halo_round2<GD, true, 16>(reinterpret_cast<const float4 *>(X), t.q, t.grp, ldsXh, f.hr);
       l.alpha = p.alpha ? p.alpha + e * p.alpha_elems : nullptr;
-      const float4 z = gat_fwd_compute<H>(l, L, t, m, tile, breg, b4);
+      const float4 z = gat_fwd_compute<H>(l, L, t, f.m, f.tile, f.breg, f.b4);
       const float4 y = f4_act(l.act, z);
-      if (p.yz && ok) st4_g(p.yz + e * p.row_elems, own, l.act == NGPDE_ACT_RELU ? y : z);
+      if (p.yz && f.ok) st4_g(p.yz + e * p.row_elems, f.own, l.act == NGPDE_ACT_RELU ? y : z);
       float4 v = f4_scale(1.0f, u);
-      for (int j = 0; j < i; ++j) v = f4_fma(ldsC[row * 8 + j], ld4_g(p.kbuf + (size_t)j * p.row_elems, own), v);
+      for (int j = 0; j < i; ++j) v = f4_fma(ldsC[row * 8 + j], ld4_g(p.kbuf + (size_t)j * p.row_elems, f.own), v);
       v = f4_fma(ldsC[row * 8 + i], y, v);
-      if (i + 1 < S && ok) st4_g(p.kbuf + (size_t)i * p.row_elems, own, y);   // (a padding row's thread addresses node 0)
+      if (i + 1 < S && f.ok) st4_g(p.kbuf + (size_t)i * p.row_elems, f.own, y);   // (a padding row's thread addresses node 0)
       else u = v;
       const bool last = (n == p.n_steps - 1 && i == S - 1);
-      if (ok) {
-        if (last) st4_g(p.u_out, own, v);
-        else store_sc1(p.xs + (p.taped ? e + 1 : ((e + 1) & 1)) * p.row_elems, own, v);
+      if (f.ok) {
+        if (last) st4_g(p.u_out, f.own, v);
+        else store_sc1(p.xs + (p.taped ? e + 1 : ((e + 1) & 1)) * p.row_elems, f.own, v);
       }
       NGPDE_STAMP(l.stamps, 16, 14, memtime);
-      if (!last) gat_publish(p.s, t, tile, ph);
+      if (!last) gat_publish(p.s, t, f.tile, ph);
       NGPDE_STAMP(l.stamps, 16, 15, memtime);
     }
   }
-  if (dead && ok) st4_g(p.u_out, own, f4_nan());
+  if (dead && f.ok) st4_g(p.u_out, f.own, f4_nan());
 }
 
 struct GatNodeBwdK {
@@ -1078,35 +1063,74 @@ struct GatNodeBwdK {
   size_t flag_stride, xs_stride, yz_stride, alpha_stride, dal_stride;
 };
 
+// The adjoint solver kernels' LDS, one region for both halves: [Xh | DZ | DA] by target, [Xh | S | DWX | XT | Bt | DD] by source (W is
+// copied into Bt before every by-source half, under the wait: Bt overlaps DA)
+constexpr int kNodeBwdLdsF = kFwdXhF + kBwdSF + 2 * kBwdTileF + kBwdBtF + kBwdDDF;
+static_assert(kBwdDZF + kBwdDAF <= kBwdSF + 2 * kBwdTileF + kBwdBtF + kBwdDDF, "the by-target tiles fit the by-source layout");
+__device__ __forceinline__ GatBwdTLds gat_node_bwd_lds_target(float *lds) { return {lds, lds + kFwdXhF, lds + kFwdXhF + kBwdDZF}; }
+__device__ __forceinline__ GatBwdSLds gat_node_bwd_lds_source(float *lds) {
+  float *o = lds + kFwdXhF;
+  return {lds, o, o + kBwdSF, o + kBwdSF + kBwdTileF, o + kBwdSF + 2 * kBwdTileF, o + kBwdSF + 2 * kBwdTileF + kBwdBtF};
+}
+// What the two adjoint solver kernels set up per thread, once: the lane's attention vectors, the thread's node and own-row byte offset.
+// (The tile, coefficient table, abort verdict, wait-list entry and zeroed accumulators stay in the kernels: with the wait-list load or
+// the accumulator array in here the batch or four-head kernels gain 4 - 12 bytes per lane of scratch, profiles/r11_a_handoff_once.txt.)
+struct GatNodeBwdFrame {
+  float4 al4, ar4;
+  bool ok;
+  unsigned own;
+};
+template <int H>
+__device__ __forceinline__ void gat_node_bwd_enter(int tile, const int4 *sched, const float *a, const GatThread &t, GatNodeBwdFrame &f) {
+  constexpr int C = GD / H;
+  const int hq = (4 * t.q) / C;
+  f.al4 = *reinterpret_cast<const float4 *>(a + (size_t)hq * 2 * C + (4 * t.q) % C);
+  f.ar4 = *reinterpret_cast<const float4 *>(a + (size_t)hq * 2 * C + C + (4 * t.q) % C);
+  const int node = sched[(size_t)tile * kTM + t.grp].x;   // (the same node in both directions' schedules: checked by the host)
+  f.ok = node >= 0;
+  f.own = (unsigned)max(node, 0) * (unsigned)(GD * 4) + (unsigned)(t.q * 16);
+}
+// ... and what they leave in the tile's slabs: dW, db and (through W in Bt) da; NaN when aborted.  (Slabs by pointer: same reason.)
+template <int H>
+__device__ __forceinline__ void gat_node_bwd_leave(float *slab_dw, float *slab_db, float *slab_u, const float *wt, const GatBwdSLds &LS,
+                                                   const GatThread &t, bool dead, const f32x4 (&dw)[GG::DWT], float dbacc, float uacc) {
+  constexpr int NT = GG::CT * GG::CT;
+  const float bad = __int_as_float(0x7fc00000);
+  float4 *slab4 = reinterpret_cast<float4 *>(slab_dw);
+#pragma unroll
+  for (int mm = 0; mm < GG::DWT; ++mm) {
+    const int t2 = t.wave_u + GG::WAVES * mm;
+    if (t2 < NT) slab4[t2 * 64 + t.lane] = dead ? f4_nan() : make_float4(dw[mm][0], dw[mm][1], dw[mm][2], dw[mm][3]);
+  }
+  if (t.tid % GG::DBP == 0) slab_db[t.tid / GG::DBP] = dead ? bad : dbacc;
+  __syncthreads();
+  gat_load_bt(wt, LS.Bt, t.tid);
+  __syncthreads();
+  gat_bwd_source_finish<H>(slab_u, LS, t, dead ? bad : uacc);
+}
+
 // BATCH adjoint: per phase, the by-target halves of both slots (each published as soon as its stores have drained), then the
 // by-source halves -- each slot's wait for its neighbours has the other slot's half in front of it.  lambda lives in p.lam (own
 // rows, same thread), the weight-gradient accumulators run on over slots and members.
 template <int H>
 __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_batch_kernel(const GatNodeBwdK p) {
-  constexpr int C = GD / H;
-  __shared__ __attribute__((aligned(16))) float lds[kFwdXhF + kBwdSF + 2 * kBwdTileF + kBwdBtF + kBwdDDF];
+  __shared__ __attribute__((aligned(16))) float lds[kNodeBwdLdsF];
   __shared__ float ldsC[64];
   __shared__ int s_ok;
   float *ldsXh = lds;
-  const GatBwdTLds LT = {ldsXh, ldsXh + kFwdXhF, ldsXh + kFwdXhF + kBwdDZF};
-  float *o = ldsXh + kFwdXhF;
-  const GatBwdSLds LS = {ldsXh, o, o + kBwdSF, o + kBwdSF + kBwdTileF, o + kBwdSF + 2 * kBwdTileF, o + kBwdSF + 2 * kBwdTileF + kBwdBtF};
+  const GatBwdTLds LT = gat_node_bwd_lds_target(lds);
+  const GatBwdSLds LS = gat_node_bwd_lds_source(lds);
   const GatThread t = gat_thread();
+  f32x4 dw[GG::DWT];
+#pragma unroll
+  for (int mm = 0; mm < GG::DWT; ++mm) dw[mm] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int tile = xcd_tile(blockIdx.x, p.t.n_tiles);
   if (t.tid < 64) ldsC[t.tid] = p.cb[t.tid];
   if (t.tid == 0) s_ok = 1;
   const int my_nbr = p.y.nbr[(size_t)tile * kNbrStride + t.lane];
-  const int hq = (4 * t.q) / C;
-  const float4 al4 = *reinterpret_cast<const float4 *>(p.s.a + (size_t)hq * 2 * C + (4 * t.q) % C);
-  const float4 ar4 = *reinterpret_cast<const float4 *>(p.s.a + (size_t)hq * 2 * C + C + (4 * t.q) % C);
-  constexpr int NT = GG::CT * GG::CT;
-  f32x4 dw[GG::DWT];
-#pragma unroll
-  for (int mm = 0; mm < GG::DWT; ++mm) dw[mm] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  GatNodeBwdFrame f;
+  gat_node_bwd_enter<H>(tile, p.t.sched, p.s.a, t, f);
   float uacc = 0.f, dbacc = 0.f;
-  const int node = p.t.sched[(size_t)tile * kTM + t.grp].x;
-  const bool ok = node >= 0;
-  const unsigned own = (unsigned)max(node, 0) * (unsigned)(GD * 4) + (unsigned)(t.q * 16);
   const int S = p.S;
   const unsigned P = (unsigned)(p.n_steps * S);
   GatBwdTK tk = p.t;
@@ -1118,7 +1142,7 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_batch_ker
   for (int mb = 0; mb < p.n_members && !dead; mb += 2, ph0 += P) {
     const int nsl = min(2, p.n_members - mb);
     for (int sl = 0; sl < nsl; ++sl)
-      if (ok) st4_g(p.lam + (size_t)(mb + sl) * p.row_elems, own, ld4_g(p.duT + (size_t)(mb + sl) * p.row_elems, own));
+      if (f.ok) st4_g(p.lam + (size_t)(mb + sl) * p.row_elems, f.own, ld4_g(p.duT + (size_t)(mb + sl) * p.row_elems, f.own));
     unsigned lp = 0;
     for (int n = p.n_steps - 1; n >= 0 && !dead; --n) {
       for (int i = S - 1; i >= 0 && !dead; --i) {
@@ -1135,15 +1159,15 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_batch_ker
           tk.alpha = p.alpha + (size_t)(mb + sl) * p.alpha_stride + e * p.alpha_elems;
           tk.dscore = p.dscore + (size_t)(sl * 2 + (ph & 1)) * p.dscore_elems;
           tk.dal = p.t.dal + (size_t)sl * p.dal_stride;
-          const float4 lamv = ld4_g(lam, own);
+          const float4 lamv = ld4_g(lam, f.own);
           float4 yzv = f4_zero();
-          if (p.yz) yzv = ld4_g(p.yz + (size_t)(mb + sl) * p.yz_stride + e * p.row_elems, own);
-          float4 v = f4_scale(ldsC[i * 8 + i], ok ? lamv : f4_zero());
-          for (int j = i + 1; j < S; ++j) v = f4_fma(ldsC[i * 8 + j], ld4_g(ub + (size_t)j * p.row_elems, own), v);
+          if (p.yz) yzv = ld4_g(p.yz + (size_t)(mb + sl) * p.yz_stride + e * p.row_elems, f.own);
+          float4 v = f4_scale(ldsC[i * 8 + i], f.ok ? lamv : f4_zero());
+          for (int j = i + 1; j < S; ++j) v = f4_fma(ldsC[i * 8 + j], ld4_g(ub + (size_t)j * p.row_elems, f.own), v);
           if (p.yz) v = f4_mul(v, f4_dact(tk.act, yzv));
-          if (!ok) v = f4_zero();
+          if (!f.ok) v = f4_zero();
           float *dzb = p.dzbuf + (size_t)(sl * 2 + (ph & 1)) * p.row_elems;
-          if (ok) store_sc1(dzb, own, v);
+          if (f.ok) store_sc1(dzb, f.own, v);
           dbacc += gat_bwd_target_compute<H, true>(tk, LT, t, mt, tile, v);
           gat_publish(ys, t, tile, ph);
         }
@@ -1166,65 +1190,45 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_batch_ker
           gat_bwd_source_prefetch<H>(sk, t, ms.sc, spre);   // the tape's share of the half's loads: under the wait
           if (!gat_wait(ys, t, my_nbr, ph, &s_ok)) { dead = true; break; }
           halo_round2<GD, true, 16>(reinterpret_cast<const float4 *>(dzb), t.q, t.grp, ldsXh, hrs);
-          const float4 dxv = gat_bwd_source_core<H, true>(sk, LS, t, ms, al4, ar4, dw, uacc, spre);
+          const float4 dxv = gat_bwd_source_core<H, true>(sk, LS, t, ms, f.al4, f.ar4, dw, uacc, spre);
           if (i > 0) {
-            if (ok) st4_g(ub + (size_t)i * p.row_elems, own, dxv);
+            if (f.ok) st4_g(ub + (size_t)i * p.row_elems, f.own, dxv);
           } else {
-            float4 w = f4_scale(1.0f, ok ? ld4_g(lam, own) : f4_zero());
+            float4 w = f4_scale(1.0f, f.ok ? ld4_g(lam, f.own) : f4_zero());
             w = f4_fma(1.0f, dxv, w);
-            for (int j = 1; j < S; ++j) w = f4_fma(1.0f, ld4_g(ub + (size_t)j * p.row_elems, own), w);
-            if (ok) st4_g(lam, own, w);
+            for (int j = 1; j < S; ++j) w = f4_fma(1.0f, ld4_g(ub + (size_t)j * p.row_elems, f.own), w);
+            if (f.ok) st4_g(lam, f.own, w);
           }
         }
       }
     }
   }
-  if (ok && dead)
-    for (int mb = 0; mb < p.n_members; ++mb) st4_g(p.lam + (size_t)mb * p.row_elems, own, f4_nan());
-  const float bad = __int_as_float(0x7fc00000);
-  float4 *slab4 = reinterpret_cast<float4 *>(p.s.slab_dw + (size_t)tile * GD * GD);
-#pragma unroll
-  for (int mm = 0; mm < GG::DWT; ++mm) {
-    const int t2 = t.wave_u + GG::WAVES * mm;
-    if (t2 < NT) slab4[t2 * 64 + t.lane] = dead ? f4_nan() : make_float4(dw[mm][0], dw[mm][1], dw[mm][2], dw[mm][3]);
-  }
-  if (t.tid % GG::DBP == 0) p.slab_db[(size_t)tile * GD + t.tid / GG::DBP] = dead ? bad : dbacc;
-  __syncthreads();
-  gat_load_bt(p.s.wt, LS.Bt, t.tid);
-  __syncthreads();
-  gat_bwd_source_finish<H>(p.s.slab_u + (size_t)tile * 2 * GD, LS, t, dead ? bad : uacc);
+  if (f.ok && dead)
+    for (int mb = 0; mb < p.n_members; ++mb) st4_g(p.lam + (size_t)mb * p.row_elems, f.own, f4_nan());
+  gat_node_bwd_leave<H>(p.s.slab_dw + (size_t)tile * GD * GD, p.slab_db + (size_t)tile * GD, p.s.slab_u + (size_t)tile * 2 * GD, p.s.wt, LS, t, dead, dw,
+                        dbacc, uacc);
 }
 
 template <int H>
 __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(const GatNodeBwdK p) {
-  constexpr int C = GD / H;
-  // one region for both halves: [Xh | DZ | DA] by target, [Xh | S | DWX | XT | Bt | DD] by source (W is copied into Bt before every
-  // by-source half, under the wait: Bt overlaps DA)
-  __shared__ __attribute__((aligned(16))) float lds[kFwdXhF + kBwdSF + 2 * kBwdTileF + kBwdBtF + kBwdDDF];
-  static_assert(kBwdDZF + kBwdDAF <= kBwdSF + 2 * kBwdTileF + kBwdBtF + kBwdDDF, "the by-target tiles fit the by-source layout");
+  __shared__ __attribute__((aligned(16))) float lds[kNodeBwdLdsF];
   __shared__ float ldsC[64];
   __shared__ int s_ok;
   float *ldsXh = lds;
-  const GatBwdTLds LT = {ldsXh, ldsXh + kFwdXhF, ldsXh + kFwdXhF + kBwdDZF};
-  float *o = ldsXh + kFwdXhF;
-  const GatBwdSLds LS = {ldsXh, o, o + kBwdSF, o + kBwdSF + kBwdTileF, o + kBwdSF + 2 * kBwdTileF, o + kBwdSF + 2 * kBwdTileF + kBwdBtF};
+  const GatBwdTLds LT = gat_node_bwd_lds_target(lds);
+  const GatBwdSLds LS = gat_node_bwd_lds_source(lds);
   const GatThread t = gat_thread();
+  f32x4 dw[GG::DWT];
+#pragma unroll
+  for (int mm = 0; mm < GG::DWT; ++mm) dw[mm] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int tile = xcd_tile(blockIdx.x, p.t.n_tiles);
   if (t.tid < 64) ldsC[t.tid] = p.cb[t.tid];
   if (t.tid == 0) s_ok = 1;
   const int my_nbr = p.y.nbr[(size_t)tile * kNbrStride + t.lane];
-  const int hq = (4 * t.q) / C;
-  const float4 al4 = *reinterpret_cast<const float4 *>(p.s.a + (size_t)hq * 2 * C + (4 * t.q) % C);
-  const float4 ar4 = *reinterpret_cast<const float4 *>(p.s.a + (size_t)hq * 2 * C + C + (4 * t.q) % C);
-  constexpr int NT = GG::CT * GG::CT;
-  f32x4 dw[GG::DWT];
-#pragma unroll
-  for (int mm = 0; mm < GG::DWT; ++mm) dw[mm] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  GatNodeBwdFrame f;
+  gat_node_bwd_enter<H>(tile, p.t.sched, p.s.a, t, f);
   float uacc = 0.f, dbacc = 0.f;
-  const int node = p.t.sched[(size_t)tile * kTM + t.grp].x;   // (the same node in both directions' schedules: checked by the host)
-  const bool ok = node >= 0;
-  const unsigned own = (unsigned)max(node, 0) * (unsigned)(GD * 4) + (unsigned)(t.q * 16);
-  float4 lam = ok ? ld4_g(p.duT, own) : f4_zero();
+  float4 lam = f.ok ? ld4_g(p.duT, f.own) : f4_zero();
   const int S = p.S;
   GatBwdTK tk = p.t;
   GatBwdSK sk = p.s;
@@ -1244,13 +1248,13 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
       tk.alpha = p.alpha + e * p.alpha_elems;
       tk.dscore = p.dscore + (size_t)(ph & 1) * p.dscore_elems;
       float4 yzv = f4_zero();
-      if (p.yz) yzv = ld4_g(p.yz + e * p.row_elems, own);
+      if (p.yz) yzv = ld4_g(p.yz + e * p.row_elems, f.own);
       float4 v = f4_scale(ldsC[i * 8 + i], lam);
-      for (int j = i + 1; j < S; ++j) v = f4_fma(ldsC[i * 8 + j], ld4_g(p.ubar + (size_t)j * p.row_elems, own), v);
+      for (int j = i + 1; j < S; ++j) v = f4_fma(ldsC[i * 8 + j], ld4_g(p.ubar + (size_t)j * p.row_elems, f.own), v);
       if (p.yz) v = f4_mul(v, f4_dact(tk.act, yzv));
-      if (!ok) v = f4_zero();
+      if (!f.ok) v = f4_zero();
       float *dzb = p.dzbuf + (size_t)(ph & 1) * p.row_elems;
-      if (ok) store_sc1(dzb, own, v);
+      if (f.ok) store_sc1(dzb, f.own, v);
       NGPDE_STAMP(p.stamps, 16, 1, memtime);
       dbacc += gat_bwd_target_compute<H, true>(tk, LT, t, mt, tile, v);
       NGPDE_STAMP(p.stamps, 16, 2, memtime);
@@ -1271,31 +1275,21 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
       if (!gat_wait(p.y, t, my_nbr, ph, &s_ok)) { dead = true; break; }
       NGPDE_STAMP(p.stamps, 16, 5, memtime);
       halo_round2<GD, true, 16>(reinterpret_cast<const float4 *>(dzb), t.q, t.grp, ldsXh, hrs);
-      const float4 dxv = gat_bwd_source_core<H, true>(sk, LS, t, ms, al4, ar4, dw, uacc, spre);
+      const float4 dxv = gat_bwd_source_core<H, true>(sk, LS, t, ms, f.al4, f.ar4, dw, uacc, spre);
       NGPDE_STAMP(p.stamps, 16, 6, memtime);
       if (i > 0) {
-        if (ok) st4_g(p.ubar + (size_t)i * p.row_elems, own, dxv);
+        if (f.ok) st4_g(p.ubar + (size_t)i * p.row_elems, f.own, dxv);
       } else {   // lambda of the step before: 1 * lambda + sum_j 1 * U-bar_j, j ascending
         float4 w = f4_scale(1.0f, lam);
         w = f4_fma(1.0f, dxv, w);
-        for (int j = 1; j < S; ++j) w = f4_fma(1.0f, ld4_g(p.ubar + (size_t)j * p.row_elems, own), w);
-        lam = ok ? w : f4_zero();
+        for (int j = 1; j < S; ++j) w = f4_fma(1.0f, ld4_g(p.ubar + (size_t)j * p.row_elems, f.own), w);
+        lam = f.ok ? w : f4_zero();
       }
     }
   }
-  if (ok) st4_g(p.lam, own, dead ? f4_nan() : lam);
-  const float bad = __int_as_float(0x7fc00000);
-  float4 *slab4 = reinterpret_cast<float4 *>(p.s.slab_dw + (size_t)tile * GD * GD);
-#pragma unroll
-  for (int mm = 0; mm < GG::DWT; ++mm) {
-    const int t2 = t.wave_u + GG::WAVES * mm;
-    if (t2 < NT) slab4[t2 * 64 + t.lane] = dead ? f4_nan() : make_float4(dw[mm][0], dw[mm][1], dw[mm][2], dw[mm][3]);
-  }
-  if (t.tid % GG::DBP == 0) p.slab_db[(size_t)tile * GD + t.tid / GG::DBP] = dead ? bad : dbacc;
-  __syncthreads();
-  gat_load_bt(p.s.wt, LS.Bt, t.tid);
-  __syncthreads();
-  gat_bwd_source_finish<H>(p.s.slab_u + (size_t)tile * 2 * GD, LS, t, dead ? bad : uacc);
+  if (f.ok) st4_g(p.lam, f.own, dead ? f4_nan() : lam);
+  gat_node_bwd_leave<H>(p.s.slab_dw + (size_t)tile * GD * GD, p.slab_db + (size_t)tile * GD, p.s.slab_u + (size_t)tile * 2 * GD, p.s.wt, LS, t, dead, dw,
+                        dbacc, uacc);
 }
 
 inline bool no_fused_gat_layer_env() {   // read on every call: tests flip it inside one process

@@ -377,11 +377,12 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
           const bool nexists = (same_phase || !last_phase) && KT > 1;   // (one tile: its own rows of the next phase are stored in THIS turn)
           const float *nX = same_phase ? X : (nlayer == 0 ? p.bufA : p.bufB);   // (only the launch's very first phase reads u_in)
           const float *nmeta = ldsMeta + ns * kMS;
-          // its flags: fetched now, looked at behind the aggregation (they were published K - 1 turns ago: one look is enough)
+          // its flags: fetched now, looked at behind the aggregation (they were published K - 1 turns ago: one look is enough).
+          // (kFlagLine spelled out here and at pend_flags below: with flag_line this kernel's instructions move)
           unsigned f1 = 0;
           if (nexists && wave_u == 0) {
             const int nb = reinterpret_cast<const int *>(nmeta + kMetaF + kTM * 4)[lane];
-            const unsigned *addr = (lane == 63) ? p.m.abort_word : (nb >= 0 ? p.m.flags + 32 * nb : nullptr);
+            const unsigned *addr = (lane == 63) ? p.m.abort_word : (nb >= 0 ? p.m.flags + kFlagLine * nb : nullptr);
             f1 = (lane == 63) ? 0u : 0xffffffffu;
             if (addr) f1 = __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
@@ -428,7 +429,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_fwd_persistentKP_kernel(cons
             }
           }
           if (pre && nlayer == 1) load_state(cn, ownn, nn, i);   // (this turn's state rows are dead from here; a layer-2 turn that follows this one belongs to stage i)
-          pend_flags = p.m.flags + 32 * tile;
+          pend_flags = p.m.flags + kFlagLine * tile;
           pend_ph = ph;
           if constexpr (TAPE && ACT == NGPDE_ACT_RELU) stu8_g(p.masks + ev * p.mask_bytes + (size_t)tile * kThreads, (unsigned)tid, sign_bits);
           else if (TAPE && c.valid) st4_stream_g(p.ztape + ev * p.row_elems, own, z);
@@ -556,7 +557,7 @@ __device__ __forceinline__ bool fwd_slot_phase(const PFwdK &p, const TileCtx &c,
     S.xown = v;
   }
   NGPDE_PHASE_STAMP(p.m.stamps, ph, 5);
-  pend_flags = flags + 32 * c.tile;     // published at the next T0 (or behind the loops)
+  pend_flags = flag_line(flags, c.tile);     // published at the next T0 (or behind the loops)
   pend_ph = ph;
   if (TAPE) stu8_g(p.masks + ev * p.mask_bytes + (size_t)c.tile * kThreads, (unsigned)c.tid, sign_bits);
   NGPDE_PHASE_STAMP(p.m.stamps, ph, 6);
@@ -991,7 +992,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistent2_kernel(const
     }
     if (c.valid) store_sc1(gout, own, gv);
     NGPDE_PHASE_STAMP(p.m.stamps, ph, 5);
-    pend_flags = flags + 32 * c.tile;
+    pend_flags = flag_line(flags, c.tile);
     pend_ph = ph;
   };
 
@@ -1423,7 +1424,7 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
       halo_fill_all(cn, nx.X, ldsXh);
     }
     if (c.valid) store_sc1(gout, own, gv);
-    pend_flags = p.m.flags + 32 * c.tile;
+    pend_flags = flag_line(p.m.flags, c.tile);
     pend_ph = ph;
   };
 

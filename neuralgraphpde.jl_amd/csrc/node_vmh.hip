@@ -322,35 +322,15 @@ __device__ __forceinline__ bool vmh_wait(const VmhMeta &m, const VCtx &c, int ne
   if (need <= 0) return true;
   if (c.wave == 0) {
     const int nb = c.lane < 63 ? m.nbr[(size_t)c.tile * VNbr + c.lane] : -1;
-    const unsigned *a0 = (c.lane == 63) ? m.abort_word : (nb >= 0 ? m.flags + 32 * (2 * nb) : nullptr);
-    const unsigned *a1 = (c.lane < 63 && nb >= 0) ? m.flags + 32 * (2 * nb + 1) : nullptr;
-    const unsigned *a2 = (c.lane == 0) ? m.flags + 32 * (c.wg ^ 1) : nullptr;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    bool ok = true;
-    for (unsigned it = 1;; ++it) {
-      unsigned f0 = (c.lane == 63) ? 0u : (unsigned)need, f1 = (unsigned)need, f2 = (unsigned)need;
-      if (a0) f0 = __hip_atomic_load(a0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a1) f1 = __hip_atomic_load(a1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a2) f2 = __hip_atomic_load(a2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__any((int)(c.lane == 63 && f0 != 0))) { ok = false; break; }
-      if (__all((int)(c.lane == 63 || (f0 >= (unsigned)need && f1 >= (unsigned)need && f2 >= (unsigned)need)))) break;
-      if ((it & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {
-        if (c.lane == 0) __hip_atomic_store(m.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = false;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    if (c.lane == 0) *s_ok = ok ? 1 : 0;
+    const unsigned *const a[3] = {watch_first(m.abort_word, m.flags, c.lane, nb >= 0 ? 2 * nb : -1),
+                                  watch_line(m.flags, nb >= 0 ? 2 * nb + 1 : -1), watch_line(m.flags, c.lane == 0 ? (c.wg ^ 1) : -1)};
+    flag_poll<3>(a, m.abort_word, c.lane, (unsigned)need, s_ok);
   }
   __syncthreads();
   return *s_ok != 0;
 }
 __device__ __forceinline__ void vmh_publish(const VmhMeta &m, const VCtx &c, int ph, bool whole_tile) {
-  wait_vmcnt0();
-  __syncthreads();
-  if (c.tid == 0) __hip_atomic_store(m.flags + 32 * c.wg, (unsigned)ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (whole_tile && c.tid == 1) __hip_atomic_store(m.flags + 32 * (c.wg + 1), (unsigned)ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  flag_publish(m.flags, c.tid, (unsigned)ph, c.wg, whole_tile ? c.wg + 1 : -1);
 }
 
 __device__ __forceinline__ float ld_sc1(const float *p) {

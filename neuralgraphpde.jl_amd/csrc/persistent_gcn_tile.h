@@ -136,32 +136,15 @@ __device__ __forceinline__ void tile_ctx_from_lds(TileCtx &c, int tile, const fl
   c.lds_w = WGT ? base + kMetaKF : nullptr;
 }
 
-// Wait until every tile of the wait list has finished phase ph - 1: wave 0 polls, one flag per lane (lanes 0..62) and the abort
-// word on lane 63, ONE load per lane and round (a second dependent load per round would double the polling period, which is
-// the granularity a published flag is seen with); everybody meets at the barrier.  Returns false when the solve was aborted.
-// Bounded: after ~2 s of the 100 MHz counter (the whole solve takes ~6 ms) the wave raises the abort word itself.
+// Wait until every tile of the wait list has finished phase ph - 1: wave 0 polls (flag_poll, persistent_sync.h), one flag per lane
+// (lanes 0..62) and the abort word on lane 63; everybody meets at the barrier.  Returns false when the solve was aborted.
 // (tile_wait_arrive: the wait without the look at its verdict -- *s_ok, valid behind the barrier -- for callers that read it later, see
 // tile_gather_foreign_checked)
 __device__ __forceinline__ void tile_wait_arrive(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags) {
   if (ph <= 1) return;
   if (c.wave_u == 0) {
-    const unsigned need = (unsigned)(ph - 1);
-    const unsigned *addr = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? flags + 32 * c.my_nbr : nullptr);
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    bool ok = true;
-    for (unsigned it = 1;; ++it) {
-      unsigned f = need;
-      if (addr) f = __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__any((int)(c.lane == 63 && f != 0))) { ok = false; break; }              // somebody gave up
-      if (__all((int)(c.lane == 63 || f >= need))) break;
-      if ((it & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {
-        if (c.lane == 0) __hip_atomic_store(m.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = false;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);   // (2 / 4 / 8 measured: no difference beyond run-to-run noise; the polling period is not what a phase waits for)
-    }
-    if (c.lane == 0) *s_ok = ok ? 1 : 0;
+    const unsigned *const a[1] = {watch_first(m.abort_word, flags, c.lane, c.my_nbr)};
+    flag_poll<1>(a, m.abort_word, c.lane, (unsigned)(ph - 1), s_ok);
   }
   __syncthreads();
 }
@@ -174,20 +157,17 @@ __device__ __forceinline__ bool tile_wait(const TileMeta &m, const TileCtx &c, i
 // The same wait with its first round of flag loads issued earlier by the caller (poll_issue: `f` holds wave 0's samples, in flight
 // under whatever the workgroup did in between).  A workgroup that is level with its neighbours finds the flags in that sample
 // and only meets at the barrier; one that runs ahead spins here exactly as long as it leads.  (Used by the interleaved adjoint,
-// whose slot-phase is long enough for the flags to be there.  What the stamps of tools/stamps.py interleaved say about the hand-off:
-// a flag store is seen by a poll from another XCD ~3-4 k cycles (1.2-1.5 us) after it was issued, a poll or a gather is a
-// ~1.5 k-cycle round trip, the drain in front of the flag ~1 k: with only two slots the ~2.4 us of hand-off exceed the ~1.7 us of
-// work the other slot offers in the forward kernel -- wherever the look is put, the difference is waited for.)
+// whose slot-phase is long enough for the flags to be there.)
 __device__ __forceinline__ void tile_wait_primed_arrive(const TileMeta &m, const TileCtx &c, int ph, int *s_ok, const unsigned *flags, unsigned f) {
   if (c.wave_u == 0) {
     const unsigned need = (unsigned)(ph - 1);
-    const unsigned *addr = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? flags + 32 * c.my_nbr : nullptr);
+    const unsigned *addr = watch_first(m.abort_word, flags, c.lane, c.my_nbr);
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     bool ok = true;
     for (unsigned it = 1;; ++it) {
       if (__any((int)(c.lane == 63 && f != 0))) { ok = false; break; }
       if (__all((int)(c.lane == 63 || f >= need))) break;
-      if ((it & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {
+      if ((it & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > kWaitTicks) {
         if (c.lane == 0) __hip_atomic_store(m.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ok = false;
         break;
@@ -205,12 +185,7 @@ __device__ __forceinline__ bool tile_wait_primed(const TileMeta &m, const TileCt
   return *s_ok != 0;
 }
 
-// every storing wave drains, the workgroup meets, ONE lane publishes (Guideline 16, R1)
-__device__ __forceinline__ void tile_publish(const TileCtx &c, int ph, unsigned *flags) {
-  wait_vmcnt0();
-  __syncthreads();
-  if (c.tid == 0) __hip_atomic_store(flags + 32 * c.tile, (unsigned)ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+__device__ __forceinline__ void tile_publish(const TileCtx &c, int ph, unsigned *flags) { flag_publish(flags, c.tid, (unsigned)ph, c.tile); }
 __device__ __forceinline__ void tile_publish(const TileMeta &m, const TileCtx &c, int ph) { tile_publish(c, ph, m.flags); }
 
 // the rows of OTHER tiles this tile's halo references: memory -> LDS slots 32.., sc1 (the producers stored them write-through
@@ -457,14 +432,15 @@ __device__ __forceinline__ void hub_ctx_init(const TileMeta &m, HubCtx &c, float
   c.my_nbr = nb[c.lane]; c.nb1 = nb[c.lane + 64]; c.nb2 = nb[c.lane + 128]; c.nb3 = nb[c.lane + 192];
 }
 
-// tile_wait for a wait list of up to 255 tiles: four independent flag loads per lane and round
+// tile_wait for a wait list of up to 255 tiles: four independent flag loads per lane and round.  (Its own copy of flag_poll's loop,
+// with the stride spelled out: through flag_poll<4>, or with flag_line here, the hub kernels come out different and measured slower.)
 __device__ __forceinline__ bool hub_wait(const TileMeta &m, const HubCtx &c, int ph, int *s_ok) {
   if (ph <= 1) return true;
   if (c.wave_u == 0) {
     const unsigned need = (unsigned)(ph - 1);
-    const unsigned *a0 = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? m.flags + 32 * c.my_nbr : nullptr);
-    const unsigned *a1 = c.nb1 >= 0 ? m.flags + 32 * c.nb1 : nullptr, *a2 = c.nb2 >= 0 ? m.flags + 32 * c.nb2 : nullptr,
-                   *a3 = c.nb3 >= 0 ? m.flags + 32 * c.nb3 : nullptr;
+    const unsigned *a0 = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? m.flags + kFlagLine * c.my_nbr : nullptr);
+    const unsigned *a1 = c.nb1 >= 0 ? m.flags + kFlagLine * c.nb1 : nullptr, *a2 = c.nb2 >= 0 ? m.flags + kFlagLine * c.nb2 : nullptr,
+                   *a3 = c.nb3 >= 0 ? m.flags + kFlagLine * c.nb3 : nullptr;
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     bool ok = true;
     for (unsigned it = 1;; ++it) {
@@ -475,7 +451,7 @@ __device__ __forceinline__ bool hub_wait(const TileMeta &m, const HubCtx &c, int
       if (a3) f3 = __hip_atomic_load(a3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (__any((int)(c.lane == 63 && f0 != 0))) { ok = false; break; }              // somebody gave up
       if (__all((int)((c.lane == 63 || f0 >= need) && f1 >= need && f2 >= need && f3 >= need))) break;
-      if ((it & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {
+      if ((it & 1023u) == 0 && __builtin_amdgcn_s_memrealtime() - t0 > kWaitTicks) {
         if (c.lane == 0) __hip_atomic_store(m.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ok = false;
         break;
@@ -595,7 +571,7 @@ __device__ __forceinline__ void load_weight_lds(const float *wt, float *ldsBt, i
 // ---- pieces of the interleaved kernels' software pipeline -------------------------------------------------------------------
 // wave 0: one flag load per lane of the wait list (lane 63: the abort word), NOT waited for
 __device__ __forceinline__ unsigned poll_issue(const TileMeta &m, const TileCtx &c, const unsigned *flags) {
-  const unsigned *addr = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? flags + 32 * c.my_nbr : nullptr);
+  const unsigned *addr = (c.lane == 63) ? m.abort_word : (c.my_nbr >= 0 ? flag_line(flags, c.my_nbr) : nullptr);
   unsigned f = (c.lane == 63) ? 0u : 0xffffffffu;
   if (addr) f = __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return f;
