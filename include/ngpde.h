@@ -442,7 +442,8 @@ int32_t ngpde_coo_add_self_loops(int64_t n_nodes, int64_t n_edges, const int32_t
  * RANDOMNESS: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), stateless: a value is a
  * pure function of (seed, stream, counter) -- key (lo32(seed), hi32(seed)), counter (c0, c1, stream, 0), the 64-bit draw
  * out[0] | out[1] << 32 -- never of the thread, the launch geometry or the call order.  Streams: 1 = the neighbour keys, 2 = the draws
- * with replacement, 3 = the split keys, so one seed gives the three operations independent values. */
+ * with replacement, 3 = the split keys, 4 = the negative-sampling candidates (graph editing, below), so one seed gives the four
+ * operations independent values. */
 
 /* out[i] (device uint64[n]) = the draw at counter (lo32(first + i), c1, stream_id, 0): the generator's bits through the ABI, for tests.
  * The samplers below evaluate the same device function in their kernels and write no keys they do not need. */
@@ -490,6 +491,71 @@ int32_t ngpde_coo_sample_neighbors(int64_t n_nodes, int64_t n_edges, const int32
 int32_t ngpde_coo_rand_split(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int64_t n_first,
                              int32_t by_pair, uint64_t seed, int32_t *side_out, int64_t *kept0, int64_t *kept1, int64_t *n0_out,
                              ngpde_stream_t stream);
+
+/* ---- graph editing on a device COO list (src/NeuralGraphPDE.jl:4 re-exports GNNGraphs: add_edges, remove_edges, remove_nodes,
+ * to_unidirected, negative_sample): the transforms that CHANGE a graph -- a cloud refined, coarsened or cut between two updategraph
+ * calls, the non-edges an edge predictor trains against.  The conventions are those of the two blocks above: int32 lists with
+ * `index_base`, outputs sized by the caller to the upper bound given with each, n_nodes, n_edges and every count <= 2^31 - 1 (refused
+ * beyond), NULL and negative arguments refused before any device call (NGPDE_ERR_INVALID_ARGUMENT), an edge end outside the node range
+ * NGPDE_ERR_DIMENSION_MISMATCH from the entries that build a sort key, without a read or write through it, temporaries from hipMalloc
+ * inside the call (not capturable), data-dependent counts and errors through the status / HOST pointers after one synchronisation of
+ * `stream` (ngpde_coo_negative_sample: one per round).  No float arithmetic and no racing writes of different values: every result is
+ * bitwise equal from run to run. */
+
+/* add_edges: s_out, t_out int32[n_edges + n_new] = the old edges in order, then the new ones (s_new, t_new: device int32[n_new], with
+ * `index_base`) in the order given.  Concatenation and checks in ONE launch: a new end outside the node range is
+ * NGPDE_ERR_DIMENSION_MISMATCH; with graph_of (device int32[n_nodes], the graph of every node; nullable) a new edge whose ends lie in
+ * different graphs is NGPDE_ERR_INVALID_ARGUMENT.  Both are detected on the device and read back once.  Synchronises. */
+int32_t ngpde_coo_append(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int64_t n_new,
+                         const int32_t *s_new, const int32_t *t_new, const int32_t *graph_of, int32_t *s_out, int32_t *t_out,
+                         ngpde_stream_t stream);
+
+/* remove_edges, one of two forms per call (the other form's pointers NULL):
+ *   positions    device int64[n_listed], 0-based COO positions; repeats allowed; an entry outside 0 : n_edges - 1 is
+ *                NGPDE_ERR_INVALID_ARGUMENT.  A flag array.
+ *   ls, lt       device int32[n_listed], with `index_base`: every edge whose (s, t) equals a listed pair goes, all its parallel copies
+ *                included; a listed pair the list does not hold is ignored; a listed end outside the node range is
+ *                NGPDE_ERR_INVALID_ARGUMENT.  The listed 64-BIT keys s*n_nodes + t are radix-sorted and one thread per edge does a binary
+ *                search.
+ * Then the stable compaction of ngpde_coo_compact (one definition: csrc/coo_compact.h) with the same outputs: s_out, t_out
+ * int32[n_edges], kept int64[n_edges] (upper bounds), n_out host.  The kept edges stay in COO order.  Synchronises. */
+int32_t ngpde_coo_remove_edges(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int64_t n_listed,
+                               const int64_t *positions, const int32_t *ls, const int32_t *lt, int32_t *s_out, int32_t *t_out, int64_t *kept,
+                               int64_t *n_out, ngpde_stream_t stream);
+
+/* remove_nodes, first half: out device int64[n_nodes] (upper bound) = the nodes NOT listed (nodes: device int64[n_listed], 0-based,
+ * repeats allowed, an entry out of range NGPDE_ERR_INVALID_ARGUMENT), ascending; n_out host: how many.  What ngpde_coo_compact then
+ * takes as `nodes`.  Synchronises. */
+int32_t ngpde_coo_complement_nodes(int64_t n_nodes, int64_t n_listed, const int64_t *nodes, int64_t *out, int64_t *n_out,
+                                   ngpde_stream_t stream);
+
+/* to_unidirected, first half: (s_out, t_out)[e] = (min(s, t), max(s, t)), int32[n_edges]; ngpde_coo_coalesce then merges the copies
+ * and checks the ends.  One launch, no synchronisation. */
+int32_t ngpde_coo_orient(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t *s_out, int32_t *t_out,
+                         ngpde_stream_t stream);
+
+/* negative_sample: n_target pairs of distinct nodes that are not edges of the list; never a self loop.  A pure function of (list,
+ * arguments, seed).  With U = n_nodes * (n_nodes - 1), candidate j = 0, 1, 2, ... has the code
+ *   c_j = (draw(stream 4, counter (lo32(j), hi32(j))) * U) >> 64      (64-bit multiply-high; its bias is at most U / 2^64, U < 2^62)
+ * which decodes as a = c / (n_nodes - 1), b' = c % (n_nodes - 1), b = b' + (b' >= a); with bidirected != 0 the pair is then made
+ * (min, max).  A candidate is a NEGATIVE if (a, b) is not an edge -- with bidirected, nor (b, a).  The result is THE FIRST n_target
+ * DISTINCT NEGATIVES OF THE SEQUENCE, IN SEQUENCE ORDER: s_out, t_out device int32[n_target] = the pairs; with bidirected
+ * int32[2 * n_target] = [a; b], [b; a].  n_out host: the number of edges written.
+ *   K            the number of distinct non-loop pairs of the list (unordered with bidirected), counted on the device; with U_eff = U
+ *                (U / 2 with bidirected), n_target > U_eff - K is NGPDE_ERR_INVALID_ARGUMENT
+ *   chunk        candidates per round, <= 2^24; 0: the library's choice (the expected number for n_target negatives and a quarter more,
+ *                at least 256).  THE RESULT DOES NOT DEPEND ON IT.  Setup, once: the list's keys a*n_nodes + b (64 bits; canonical with
+ *                bidirected, so one search answers both orientations) radix-sorted, K counted.  A round: draw and decode in the
+ *                kernel, binary-search the list's keys and the keys accepted so far, stable-sort the survivors by key with j as the
+ *                payload, the heads of the key groups are the new negatives, merge them into the accepted set, read back the count.
+ *                At the end the accepted set is sorted by j and cut at n_target.
+ *   cap          the walk stops with NGPDE_ERR_STATE once 64 * ceil(U_eff / (U_eff - K)) * (n_target + 16) candidates are behind it
+ *                without n_target negatives (coupon collecting needs about U_eff * ln(U_eff - K): never reached in practice; nothing
+ *                spins).  It never truncates.
+ * Synchronises (once per round). */
+int32_t ngpde_coo_negative_sample(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int64_t n_target,
+                                  int32_t bidirected, uint64_t seed, int64_t chunk, int32_t *s_out, int32_t *t_out, int64_t *n_out,
+                                  ngpde_stream_t stream);
 
 /* GNOConv message (src/layers.jl:527-530): K_e = reshape(phi_out[:, e], cout, cin) column-major,
  * m_e = K_e * h[:, s_e].  k: [E][cin*cout] p order (element o + cout*i), h: [N][cin], m: [E][cout]. */

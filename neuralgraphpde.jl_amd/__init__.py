@@ -18,6 +18,8 @@ from .readout import (broadcast_edges, broadcast_nodes, graph_indicator, reduce_
 from .graphops import (add_self_loops, degree, getgraph, has_multi_edges, has_self_loops, induced_subgraph, is_bidirected,
                        remove_multi_edges, remove_self_loops, to_bidirected, unbatch)
 from .sampling import rand_edge_split, sample_neighbors
+from .editing import (add_edges, add_nodes, get_edge_weight, negative_sample, remove_edges, remove_nodes, set_edge_weight,
+                      to_unidirected)
 from . import dist, optim, synth
 
 
@@ -36,4 +38,5 @@ __all__ = [
     "reduce_nodes", "reduce_edges", "softmax_nodes", "softmax_edges", "broadcast_nodes", "broadcast_edges", "graph_indicator",
     "degree", "has_self_loops", "has_multi_edges", "is_bidirected", "add_self_loops", "remove_self_loops", "remove_multi_edges",
     "to_bidirected", "induced_subgraph", "getgraph", "unbatch", "sample_neighbors", "rand_edge_split",
+    "add_nodes", "add_edges", "remove_edges", "remove_nodes", "to_unidirected", "set_edge_weight", "get_edge_weight", "negative_sample",
 ]

@@ -200,6 +200,11 @@ SIGNATURES = {
     "ngpde_coo_sample_neighbors": (_i32, [_i64, _i64, _vp, _vp, _i32, _i32, _i64, _vp, _i32, _i32, C.c_uint64, _vp, _vp, _vp,
                                           C.POINTER(_i64), _vp]),
     "ngpde_coo_rand_split": (_i32, [_i64, _i64, _vp, _vp, _i32, _i64, _i32, C.c_uint64, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_coo_append": (_i32, [_i64, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_coo_remove_edges": (_i32, [_i64, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_coo_complement_nodes": (_i32, [_i64, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_coo_orient": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_coo_negative_sample": (_i32, [_i64, _i64, _vp, _vp, _i32, _i64, _i32, C.c_uint64, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
     "ngpde_gno_contract_forward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_gno_contract_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_gno_apply_supported": (_i32, [_i32, _i32]),

@@ -18,35 +18,14 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "coo_compact.h"
 #include "row_lanes.h"
 
 namespace ngpde {
 
 namespace {
 
-constexpr int kB = 256;
-inline unsigned blocks_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kB - 1) / kB); }
 inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-struct Scratch {   // device temporaries of one call; freed on scope exit
-  std::vector<void *> ptrs;
-  ~Scratch() {
-    for (void *p : ptrs) (void)hipFree(p);
-  }
-  template <class T>
-  int32_t get(T **p, size_t count) {
-    *p = nullptr;
-    NGPDE_HIP_CHECK(hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
-    ptrs.push_back(*p);
-    return NGPDE_OK;
-  }
-};
-
-unsigned bits_for(unsigned long long n) {   // bits that hold every value below n
-  unsigned b = 1;
-  while (b < 64 && (1ull << b) < n) ++b;
-  return b;
-}
 
 // device flag words of one call
 enum { kBad = 0, kSelf = 1, kMulti = 2, kAsym = 3, kCount = 4, kFlagWords = 8 };
@@ -157,22 +136,6 @@ __global__ void keep_kernel(int64_t m, int64_t n, int base, int drop_self_loops,
     if (relabel && (relabel[a] < 0 || relabel[b] < 0)) k = 0;
   }
   keep[e] = k;
-}
-
-__global__ void compact_kernel(int64_t m, int base, const int32_t *__restrict__ s, const int32_t *__restrict__ t,
-                               const int32_t *__restrict__ relabel, const int32_t *__restrict__ keep, const int32_t *__restrict__ pos,
-                               int32_t *__restrict__ s_out, int32_t *__restrict__ t_out, int64_t *__restrict__ kept,
-                               int32_t *__restrict__ flags) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= m) return;
-  const int32_t p = pos[e];
-  if (keep[e]) {   // (a kept edge has both ends in range)
-    const int32_t a = s[e] - base, b = t[e] - base;
-    s_out[p] = (relabel ? relabel[a] : a) + base;
-    t_out[p] = (relabel ? relabel[b] : b) + base;
-    kept[p] = e;
-  }
-  if (e == m - 1) flags[kCount] = p + keep[e];
 }
 
 // ---- coalesce -----------------------------------------------------------------------------------------------------------------
@@ -327,22 +290,6 @@ int32_t sorted_pair_keys(int64_t n_copies, int64_t n_edges, int64_t n, int base,
   return NGPDE_OK;
 }
 
-template <class T>
-int32_t scan_i32(bool inclusive, const int32_t *in, T *out, size_t count, Scratch &sc, hipStream_t stream) {
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  if (inclusive) {
-    NGPDE_HIP_CHECK(rocprim::inclusive_scan(nullptr, bytes, in, out, count, rocprim::plus<int32_t>(), stream));
-    if (int32_t st = sc.get((char **)&tmp, bytes)) return st;
-    NGPDE_HIP_CHECK(rocprim::inclusive_scan(tmp, bytes, in, out, count, rocprim::plus<int32_t>(), stream));
-  } else {
-    NGPDE_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, count, rocprim::plus<int32_t>(), stream));
-    if (int32_t st = sc.get((char **)&tmp, bytes)) return st;
-    NGPDE_HIP_CHECK(rocprim::exclusive_scan(tmp, bytes, in, out, 0, count, rocprim::plus<int32_t>(), stream));
-  }
-  return NGPDE_OK;
-}
-
 int32_t check_reduce(const char *fn, int64_t n_groups, int64_t n_rows, int32_t d, int32_t aggr) {
   NGPDE_REQUIRE(n_groups >= 0 && n_rows >= 0 && n_groups <= 0x7fffffffLL && n_rows <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT,
                 "%s: sizes outside 0 : 2^31 - 1 (n_groups %lld, n_rows %lld)", fn, (long long)n_groups, (long long)n_rows);
@@ -474,10 +421,7 @@ int32_t ngpde_coo_compact(int64_t n_nodes, int64_t n_edges, const int32_t *s, co
     hipLaunchKernelGGL(keep_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, n_nodes, index_base, drop_self_loops, s, t, relabel,
                        keep, flags);
     NGPDE_LAUNCH_CHECK("keep_kernel");
-    if ((st = scan_i32(false, keep, pos, (size_t)n_edges, sc, stream))) return st;
-    hipLaunchKernelGGL(compact_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, index_base, s, t, relabel, keep, pos, s_out, t_out,
-                       kept, flags);
-    NGPDE_LAUNCH_CHECK("compact_kernel");
+    if ((st = compact_flagged(n_edges, index_base, s, t, relabel, keep, pos, s_out, t_out, kept, flags + kCount, sc, stream))) return st;
   }
   int32_t h[kFlagWords];
   if ((st = read_flags(flags, h, stream))) return st;

@@ -3,7 +3,7 @@
 // The sibling of graph_ops.hip: a fresh sub-sample of every neighbourhood per epoch, or a random hold-out of the edges, without the
 // COO lists leaving the device.
 //
-// Randomness: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), stateless.  A value is a pure
+// Randomness: Philox4x32-10 (philox.h; Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), stateless.  A value is a pure
 // function of (seed, stream, counter) -- never of the thread, the launch geometry or the call order -- so a call gives the same bits
 // on every run and a test restates the generator in numpy.
 //
@@ -22,6 +22,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "philox.h"
 
 namespace ngpde {
 
@@ -32,8 +33,6 @@ constexpr int kWave = 64;
 constexpr int kRowsPerBlock = kB / kWave;                                // a wave per short row
 constexpr int kWaveRowMax = NGPDE_SAMPLE_LDS_ROW_MAX / kRowsPerBlock;    // 512: the four waves' rows share the block row's LDS
 static_assert(NGPDE_SAMPLE_LDS_ROW_MAX % kB == 0 && NGPDE_SAMPLE_LDS_ROW_MAX * 8 <= 64 * 1024, "the staged keys of a row must fit LDS");
-
-enum { kStreamNeighbor = 1, kStreamReplace = 2, kStreamSplit = 3 };
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kB - 1) / kB); }
 
@@ -60,25 +59,7 @@ unsigned bits_for(unsigned long long n) {   // bits that hold every value below 
 // device flag words of one call
 enum { kBadEdge = 0, kBadNode = 1, kBadCount = 2, kCount = 4, kFlagWords = 8 };
 
-// ---- the generator ----------------------------------------------------------------------------------------------------------
-// Philox4x32-10: counter (c0, c1, stream, 0), key (lo32(seed), hi32(seed)); the 64-bit draw is out[0] | out[1] << 32
-__device__ __forceinline__ unsigned long long philox_draw(unsigned long long seed, uint32_t stream, uint32_t c0, uint32_t c1) {
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  uint32_t x0 = c0, x1 = c1, x2 = stream, x3 = 0u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, x0), lo0 = 0xD2511F53u * x0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, x2), lo1 = 0xCD9E8D57u * x2;
-    x0 = hi1 ^ x1 ^ k0;
-    x1 = lo1;
-    x2 = hi0 ^ x3 ^ k1;
-    x3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return (unsigned long long)x0 | ((unsigned long long)x1 << 32);
-}
-
+// ---- the generator (philox.h) -----------------------------------------------------------------------------------------------
 __global__ void random_keys_kernel(unsigned long long seed, uint32_t stream, uint32_t c1, unsigned long long first, int64_t n,
                                    unsigned long long *__restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -106,9 +106,9 @@ def _select_all(data, index, n, dev):
 class _Coalesced:
     """what ngpde_coo_coalesce wrote: the groups of duplicate edges of a structure"""
 
-    def __init__(self, g, dev, symmetrize):
+    def __init__(self, g, dev, symmetrize, coo=None):
         lib = _lib.load()
-        s, t = _coo(g, dev)
+        s, t = _coo(g, dev) if coo is None else coo          # (coo: the lists to group in place of g's own -- editing.to_unidirected)
         e = g.num_edges
         m = 2 * e if symmetrize else e
         self.n_rows, self.copies = e, 2 if symmetrize else 1
@@ -302,14 +302,14 @@ def remove_self_loops(g):
                       edge_weight=None if w is None else _select(w, kept, g.num_edges, dev).reshape(-1), order=g._shared.get("order"))
 
 
-def _coalesce(g, aggr, symmetrize, what):
+def _coalesce(g, aggr, symmetrize, what, coo=None):
     code = _aggr_code(aggr)
     w = _edge_weight_of(g)
     for k, v in list(g.edata.items()) + ([("edge_weight", w)] if w is not None else []):
         if not _is_f32(v):
             raise _arg_error(f"{what}: edge feature '{k}' is {v.dtype}, only float32 features can be combined over duplicate edges")
     dev = _device()
-    coal = _Coalesced(g, dev, symmetrize)
+    coal = _Coalesced(g, dev, symmetrize, coo and coo(dev))
     edata = {k: _reduce(v, coal, code, g.num_edges, dev) for k, v in g.edata.items()}
     return _new_graph(coal.s, coal.t, g.num_nodes, dev, num_graphs=g.num_graphs, indicator=g.graph_indicator, ndata=g.ndata, edata=edata,
                       gdata=g.gdata, edge_weight=None if w is None else _reduce(w, coal, code, g.num_edges, dev).reshape(-1),
