@@ -442,8 +442,8 @@ int32_t ngpde_coo_add_self_loops(int64_t n_nodes, int64_t n_edges, const int32_t
  * RANDOMNESS: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), stateless: a value is a
  * pure function of (seed, stream, counter) -- key (lo32(seed), hi32(seed)), counter (c0, c1, stream, 0), the 64-bit draw
  * out[0] | out[1] << 32 -- never of the thread, the launch geometry or the call order.  Streams: 1 = the neighbour keys, 2 = the draws
- * with replacement, 3 = the split keys, 4 = the negative-sampling candidates (graph editing, below), so one seed gives the four
- * operations independent values. */
+ * with replacement, 3 = the split keys, 4 = the negative-sampling candidates (graph editing, below), 5 = the Lanczos start
+ * vector (graph matrices, below), so one seed gives the five operations independent values. */
 
 /* out[i] (device uint64[n]) = the draw at counter (lo32(first + i), c1, stream_id, 0): the generator's bits through the ABI, for tests.
  * The samplers below evaluate the same device function in their kernels and write no keys they do not need. */
@@ -556,6 +556,92 @@ int32_t ngpde_coo_orient(int64_t n_nodes, int64_t n_edges, const int32_t *s, con
 int32_t ngpde_coo_negative_sample(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int64_t n_target,
                                   int32_t bidirected, uint64_t seed, int64_t chunk, int32_t *s_out, int32_t *t_out, int64_t *n_out,
                                   ngpde_stream_t stream);
+
+/* ---- graph matrices on a device COO list (src/NeuralGraphPDE.jl:4 re-exports GNNGraphs: adjacency_matrix, laplacian_matrix,
+ * normalized_laplacian, scaled_laplacian, laplacian_lambda_max, khop_adj): the graph as a sparse float32 matrix -- the discrete
+ * diffusion operator, the step bound 2 / lambda_max of the explicit solvers, the operator of Chebyshev filters, the k-hop graph.
+ * A MATRIX is coalesced COO with a row pointer, all on the device: rows, cols int32[nnz] (0-BASED POSITIONS, whatever `index_base` the
+ * edge list carries), vals float[nnz], sorted by row, then column, each (row, col) at most once; row_ptr int32[n + 1].
+ * The conventions are those of the blocks above: int32 lists with `index_base`, outputs sized by the caller to the upper bound given
+ * with each, sizes <= 2^31 - 1 (refused beyond), NULL and negative arguments refused before any device call
+ * (NGPDE_ERR_INVALID_ARGUMENT), an edge end or a column outside the node range NGPDE_ERR_DIMENSION_MISMATCH without a read or write
+ * through it, temporaries from hipMalloc inside the call (not capturable), data-dependent counts and errors through the status / HOST
+ * pointers after one synchronisation of `stream`.  No float atomics: every result is bitwise equal from run to run. */
+enum { NGPDE_MATRIX_ADJ = 0, NGPDE_MATRIX_LAPLACIAN = 1, NGPDE_MATRIX_NORM_LAPLACIAN = 2 };
+
+/* The assembly (src/NeuralGraphPDE.jl:4).  With dir NGPDE_DIR_OUT an edge s -> t is position (s, t), with NGPDE_DIR_IN (t, s): the ends
+ * are swapped where the sort key is made, no second list is written.  The M copies -- the n_edges edges, then for LAPLACIAN and
+ * NORM_LAPLACIAN the n_nodes diagonal positions -- are sorted stably by the 64-BIT key row*n_nodes + col; a copy whose key differs from
+ * its predecessor's heads an entry.  a[i][j] = the sum of w (device float[n_edges], or NULL: ones) over the entry's edges in COO order
+ * from 0.0f, plus 1.0f last on the diagonal with add_self_loops (NORM_LAPLACIAN only); d[i] = the sum of a over row i, front to back.
+ *   ADJ             vals = a; only existing pairs are entries
+ *   LAPLACIAN       vals[i][j] = -a[i][j], vals[i][i] = d[i] - a[i][i]; every diagonal position is an entry
+ *   NORM_LAPLACIAN  vals[i][j] = (i == j) - ((1 / sqrt(d[i])) * a[i][j]) * (1 / sqrt(d[j])); every diagonal position is an entry.  A row
+ *                   sum that is not positive is NGPDE_ERR_INVALID_ARGUMENT (the smallest such node is named), found by the launch that
+ *                   adds the rows; no value is written through it.  With scale (device float[n_graphs], > 0, NOT CHECKED; graph_of
+ *                   device int32[n_nodes], 0-based, NULL for one graph) vals = (2 / scale[graph_of[i]]) * that - (i == j): the scaled
+ *                   Laplacian, every graph of a batch by its own lambda_max.
+ * Outputs, sized by the caller to M (group_ptr M + 1, row_ptr n_nodes + 1, deg n_nodes):
+ *   rows, cols, vals, row_ptr   the matrix
+ *   group_ptr, member           entry g holds the sorted copies group_ptr[g] .. group_ptr[g + 1] - 1; member[p] = the copy number (c <
+ *                               n_edges: edge c; else the diagonal position of node c - n_edges, always last in its entry)
+ *   group_of        [M]         the entry that copy c fell into: what a pullback to w reads
+ *   adj, deg, sym_tol           nullable: a per entry, d per node (not for ADJ), and per entry (m - 1) * 2^-23 * sum |w| over its m edges
+ *                               (0 for m <= 1): the rounding bound ngpde_csr_check_symmetric takes
+ *   nnz_out         host: the number of entries.  Synchronises. */
+int32_t ngpde_coo_matrix(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t kind, int32_t dir,
+                         int32_t add_self_loops, const float *w, int32_t n_graphs, const int32_t *graph_of, const float *scale, int32_t *rows,
+                         int32_t *cols, float *vals, int32_t *row_ptr, int32_t *group_ptr, int32_t *member, int32_t *group_of, float *adj,
+                         float *deg, float *sym_tol, int64_t *nnz_out, ngpde_stream_t stream);
+
+/* Is the matrix symmetric (src/NeuralGraphPDE.jl:4: what laplacian_lambda_max requires)?  A lane per off-diagonal entry (i, j) looks (j, i)
+ * up in row j by bisection; the entry fails if the partner is missing or |vals[i][j] - vals[j][i]| > tol[i][j] + tol[j][i] (tol device
+ * float[nnz] or NULL: exact; with the sym_tol of ngpde_coo_matrix two entries of one edge each must be equal).  NGPDE_ERR_INVALID_ARGUMENT
+ * names the failing pair with the smallest (i, j).  Synchronises. */
+int32_t ngpde_csr_check_symmetric(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *rows, const int32_t *cols, const float *vals,
+                                  const float *tol, ngpde_stream_t stream);
+
+/* laplacian_lambda_max (src/NeuralGraphPDE.jl:4): the largest eigenvalue of a SYMMETRIC matrix (NOT CHECKED here) that is block-diagonal
+ * over n_graphs graphs, per graph, by a Lanczos iteration that stays on the device; one sparse product per step serves every graph.
+ *   graph_of     device int32[n], 0-based, NON-DECREASING (checked on the device: NGPDE_ERR_INVALID_ARGUMENT), or NULL with n_graphs 1
+ *   start        v_0[i] = 0.5 + (draw(stream 5, counter (lo32(p), hi32(p))) >> 41) * 2^-23 with p the node's position INSIDE its graph
+ *                (uniform in [0.5, 1.5); a member of a batch starts as it would alone), normalised per graph
+ *   step j       w = M v_j (8 lanes per row, lane-strided, a fixed xor butterfly); twice: h = [v_0 .. v_j]' w, w -= sum_k h_k v_k (full
+ *                reorthogonalisation by two classical Gram-Schmidt passes; alpha_j = the two h_j); beta_j = |w|; v_(j+1) = w / beta_j.
+ *                Every inner product is per graph: a 256-thread workgroup per chunk of 1024 nodes of one graph, then one lane per (graph,
+ *                vector) adds the graph's partials in chunk order.  The basis (max_iter x n floats) lives in the workspace.
+ *   stops        a graph stops after min(max_iter, its node count) steps, or when beta_j <= 8 * 2^-23 * max_k(|alpha_k| + beta_k +
+ *                beta_(k-1)) (its Krylov space is exhausted: the value is exact), both decided on the device; alpha and beta are read
+ *                back once every 8 steps, the tridiagonal eigenproblem is solved on the host (implicit QL, double) and a graph with
+ *                |beta_j * s_last| <= tol * theta stops too.  A stopped graph is frozen: no kernel reads or writes its rows again.
+ *   outputs      device: lambda_out float[n_graphs] = theta; residual_out float[n_graphs] (nullable) = |M y - theta y| of the unit Ritz
+ *                vector y, by one more product; iterations_out int32[n_graphs] (nullable); vector_out float[n] (nullable) = y.  A graph
+ *                without nodes gets 0.
+ * max_iter <= 4096; tol finite, >= 0.  Synchronises (setup, every 8 steps, end). */
+size_t ngpde_csr_lambda_max_workspace_bytes(int64_t n, int32_t n_graphs, int32_t max_iter);
+int32_t ngpde_csr_lambda_max(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *cols, const float *vals, int32_t n_graphs,
+                             const int32_t *graph_of, int32_t max_iter, float tol, uint64_t seed, float *lambda_out, float *residual_out,
+                             int32_t *iterations_out, float *vector_out, void *workspace, size_t workspace_bytes, ngpde_stream_t stream);
+
+/* khop_adj (src/NeuralGraphPDE.jl:4): C = P A for two n x n matrices by expand, sort, combine.  Entry q of P at (i, j) expands to one term
+ * P[i][j] * A[j][c] per entry of row j of A; the terms are written row by row in ascending j (a lane per term, which finds its entry of P
+ * by bisection in the scanned counts: a hub row is spread over as many lanes as it has terms), sorted stably by the 64-bit key i*n + c and
+ * each entry's terms are added in that order -- ascending middle index -- from the first.  The structure is that of the boolean product:
+ * an entry whose terms cancel to 0.0 stays.
+ *   ngpde_csr_spgemm_count   total_out host = the number of terms (64-bit count and scan); above `limit` (<= 2^31 - 1)
+ *                            NGPDE_ERR_INVALID_ARGUMENT, "the product is too dense".  offsets_out device int64[nnz_p + 1] (nullable) =
+ *                            the scanned counts, offsets_out[nnz_p] = the total: what the product takes, so that it counts nothing
+ *                            again.  Synchronises.
+ *   ngpde_csr_spgemm         offsets, total = what the count wrote for the same matrices; rows_out, cols_out, vals_out sized to total,
+ *                            row_ptr_out to n + 1; nnz_out host.  Offsets that do not fit the matrices (a term without a place in its
+ *                            row of A, a last offset that is not total) are NGPDE_ERR_INVALID_ARGUMENT, found by the expanding launch,
+ *                            which reads nothing through them.  Synchronises once. */
+int32_t ngpde_csr_spgemm_count(int64_t n, int64_t nnz_p, const int32_t *p_cols, int64_t nnz_a, const int32_t *a_row_ptr, int64_t limit,
+                               int64_t *offsets_out, int64_t *total_out, ngpde_stream_t stream);
+int32_t ngpde_csr_spgemm(int64_t n, int64_t nnz_p, const int32_t *p_rows, const int32_t *p_cols, const float *p_vals, int64_t nnz_a,
+                         const int32_t *a_row_ptr, const int32_t *a_cols, const float *a_vals, const int64_t *offsets, int64_t total,
+                         int32_t *rows_out, int32_t *cols_out, float *vals_out, int32_t *row_ptr_out, int64_t *nnz_out,
+                         ngpde_stream_t stream);
 
 /* GNOConv message (src/layers.jl:527-530): K_e = reshape(phi_out[:, e], cout, cin) column-major,
  * m_e = K_e * h[:, s_e].  k: [E][cin*cout] p order (element o + cout*i), h: [N][cin], m: [E][cout]. */

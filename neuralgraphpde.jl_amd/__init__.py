@@ -20,6 +20,8 @@ from .graphops import (add_self_loops, degree, getgraph, has_multi_edges, has_se
 from .sampling import rand_edge_split, sample_neighbors
 from .editing import (add_edges, add_nodes, get_edge_weight, negative_sample, remove_edges, remove_nodes, set_edge_weight,
                       to_unidirected)
+from .matrices import (GraphMatrix, adjacency_matrix, has_isolated_nodes, khop_adj, laplacian_lambda_max, laplacian_matrix,
+                       normalized_laplacian, scaled_laplacian)
 from . import dist, optim, synth
 
 
@@ -39,4 +41,6 @@ __all__ = [
     "degree", "has_self_loops", "has_multi_edges", "is_bidirected", "add_self_loops", "remove_self_loops", "remove_multi_edges",
     "to_bidirected", "induced_subgraph", "getgraph", "unbatch", "sample_neighbors", "rand_edge_split",
     "add_nodes", "add_edges", "remove_edges", "remove_nodes", "to_unidirected", "set_edge_weight", "get_edge_weight", "negative_sample",
+    "GraphMatrix", "adjacency_matrix", "laplacian_matrix", "normalized_laplacian", "scaled_laplacian", "laplacian_lambda_max", "khop_adj",
+    "has_isolated_nodes",
 ]

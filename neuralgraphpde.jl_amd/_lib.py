@@ -205,6 +205,13 @@ SIGNATURES = {
     "ngpde_coo_complement_nodes": (_i32, [_i64, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
     "ngpde_coo_orient": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ngpde_coo_negative_sample": (_i32, [_i64, _i64, _vp, _vp, _i32, _i64, _i32, C.c_uint64, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_coo_matrix": (_i32, [_i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                C.POINTER(_i64), _vp]),
+    "ngpde_csr_check_symmetric": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_csr_lambda_max_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "ngpde_csr_lambda_max": (_i32, [_i64, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _f32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ngpde_csr_spgemm_count": (_i32, [_i64, _i64, _vp, _i64, _vp, _i64, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_csr_spgemm": (_i32, [_i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
     "ngpde_gno_contract_forward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_gno_contract_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_gno_apply_supported": (_i32, [_i32, _i32]),

@@ -12,7 +12,7 @@
 
 namespace ngpde {
 
-enum { kStreamNeighbor = 1, kStreamReplace = 2, kStreamSplit = 3, kStreamNegative = 4 };
+enum { kStreamNeighbor = 1, kStreamReplace = 2, kStreamSplit = 3, kStreamNegative = 4, kStreamLanczos = 5 };
 
 // counter (c0, c1, stream, 0), key (lo32(seed), hi32(seed)); the 64-bit draw is out[0] | out[1] << 32
 __device__ __forceinline__ unsigned long long philox_draw(unsigned long long seed, uint32_t stream, uint32_t c0, uint32_t c1) {
