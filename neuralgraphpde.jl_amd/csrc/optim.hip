@@ -425,13 +425,14 @@ int32_t ngpde_accumulate_many(int32_t n_arrays, float *const *acc, const float *
   NGPDE_REQUIRE(n_arrays >= 0, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_accumulate_many: n_arrays < 0");
   if (n_arrays == 0) return NGPDE_OK;
   NGPDE_REQUIRE(acc && g && counts, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_accumulate_many: NULL argument");
+  for (int a = 0; a < n_arrays; ++a)      // every array before the first launch: a refused call has written nothing
+    NGPDE_REQUIRE(counts[a] >= 0 && (counts[a] == 0 || (acc[a] && g[a])), NGPDE_ERR_INVALID_ARGUMENT,
+                  "ngpde_accumulate_many: array %d is NULL or has a negative count", a);
   for (int a0 = 0; a0 < n_arrays; a0 += kManyMax) {
     ManyK k{};
     const int m = std::min(kManyMax, n_arrays - a0);
     int64_t longest = 0;
     for (int a = 0; a < m; ++a) {
-      NGPDE_REQUIRE(counts[a0 + a] >= 0 && (counts[a0 + a] == 0 || (acc[a0 + a] && g[a0 + a])), NGPDE_ERR_INVALID_ARGUMENT,
-                    "ngpde_accumulate_many: array %d is NULL or has a negative count", a0 + a);
       k.acc[a] = acc[a0 + a]; k.g[a] = g[a0 + a]; k.count[a] = counts[a0 + a];
       longest = std::max(longest, counts[a0 + a]);
     }

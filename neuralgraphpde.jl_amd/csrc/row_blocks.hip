@@ -184,14 +184,14 @@ int32_t ngpde_rows_index(int64_t outer, int64_t n_rows, int64_t n_index, int32_t
                          int32_t scatter, ngpde_stream_t stream) {
   NGPDE_RANGE();
   NGPDE_REQUIRE(outer >= 0 && n_rows >= 0 && n_index >= 0 && d > 0, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rows_index: bad sizes");
+  const int64_t total = outer * n_index * d;
+  NGPDE_REQUIRE(total == 0 || (index && src && dst), NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rows_index: NULL argument");   // before the zero fill: a refused call has written nothing
   if (scatter && outer * n_rows > 0) {
     NGPDE_REQUIRE(dst != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rows_index: dst is NULL");
     int32_t st = launch_zero(dst, (size_t)(outer * n_rows * d) * sizeof(float), (hipStream_t)stream);   // rows no index names are zero
     if (st) return st;
   }
-  const int64_t total = outer * n_index * d;
   if (total == 0) return NGPDE_OK;
-  NGPDE_REQUIRE(index && src && dst, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_rows_index: NULL argument");
   hipLaunchKernelGGL(ngpde::rows_index_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, outer, n_rows, n_index, d, index,
                      src, dst, scatter);
   NGPDE_LAUNCH_CHECK("rows_index_kernel");

@@ -1057,9 +1057,9 @@ def rprop_init(x, eta=1e-3):
     return dict(g=np.zeros_like(x, dtype=np.float32), step=np.full_like(x, eta, dtype=np.float32))
 
 
-def rprop_step(x, g, state, ell=(0.5, 1.2), gamma=(1e-6, 50.0)):
+def rprop_step(x, g, state, ell=(0.5, 1.2), gamma=(1e-6, 50.0), grad_scale=1.0):
     f = np.float32
-    g = g.astype(np.float32)
+    g = f(grad_scale) * g.astype(np.float32)        # the data-parallel mean folded into the step
     p = state["g"] * g
     s = state["step"]
     s = np.where(p > 0, np.minimum(s * f(ell[1]), f(gamma[1])), np.where(p < 0, np.maximum(s * f(ell[0]), f(gamma[0])), s)).astype(np.float32)
