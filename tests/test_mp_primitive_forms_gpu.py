@@ -145,26 +145,32 @@ def read_i32(ptr, count):
 
 
 class Gr:
-    """a graph, its p order restated, and the library's handle -- whose by-target lists must equal the restatement"""
+    """a graph, its p order and its by-source order restated, and the library's handle -- whose by-target and by-source lists must
+    equal the restatement (attach=False: numpy only, until attach() is called)"""
 
-    def __init__(self, s, t, n):
+    def __init__(self, s, t, n, attach=True):
         self.s, self.t, self.n, self.E = np.asarray(s, dtype=np.int64), np.asarray(t, dtype=np.int64), n, len(s)
         self.perm = np.argsort(self.t, kind="stable")           # p -> position in the COO list
         self.sp, self.tp = self.s[self.perm], self.t[self.perm]
+        self.perm_s = np.argsort(self.s, kind="stable")         # the same by source
         self.indeg, self.outdeg = np.bincount(self.t, minlength=n), np.bincount(self.s, minlength=n)
         self.rowptr = np.concatenate([[0], np.cumsum(self.indeg)])
-        self.attach()
+        self.rowptr_s = np.concatenate([[0], np.cumsum(self.outdeg)])
+        if attach:
+            self.attach()
 
     def attach(self):
-        n = self.n
+        n, lib = self.n, _lib.load()
         self.g = ng.GNNGraph(self.s, self.t, num_nodes=n, index_base=0)
         self.handle = self.g.handle()
         self.ptr = self.handle.ptr
-        rp, col, eid = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _lib.check(_lib.load().ngpde_graph_csr_by_target(self.ptr, C.byref(rp), C.byref(col), C.byref(eid)))
-        assert np.array_equal(read_i32(rp.value, n + 1), self.rowptr), "rowptr"
-        assert np.array_equal(read_i32(col.value, self.E), self.sp), "col"
-        assert np.array_equal(read_i32(eid.value, self.E), self.perm), "eid"
+        for fn, rowptr, col, eid in ((lib.ngpde_graph_csr_by_target, self.rowptr, self.sp, self.perm),
+                                     (lib.ngpde_graph_csr_by_source, self.rowptr_s, self.t[self.perm_s], self.perm_s)):
+            rp, cl, ei = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            _lib.check(fn(self.ptr, C.byref(rp), C.byref(cl), C.byref(ei)))
+            assert np.array_equal(read_i32(rp.value, n + 1), rowptr), "rowptr"
+            assert np.array_equal(read_i32(cl.value, self.E), col), "col"
+            assert np.array_equal(read_i32(ei.value, self.E), eid), "eid"
 
 
 _GRAPHS = {}
@@ -295,7 +301,10 @@ def sum_of_bounded(k, abs_sum, slack_sum):
     return slack_sum + lin(k, abs_sum + slack_sum)
 
 
-def within(out, ref, bound, fam, what):
+def within(out, ref, bound, fam, what, worst=None):
+    """every element within its bound of the float64 ref, non-finite entries the same; records the worst err / bound of `fam` (in
+    `worst`: another module's table)"""
+    worst = WORST if worst is None else worst
     got = (out.get() if isinstance(out, Out) else np.asarray(out)).astype(np.float64)
     ref = np.asarray(ref, dtype=np.float64)
     assert got.shape == ref.shape, (what, got.shape, ref.shape)
@@ -305,9 +314,9 @@ def within(out, ref, bound, fam, what):
     err, b = np.abs(got[fin] - ref[fin]), bound[fin]
     with np.errstate(divide="ignore", invalid="ignore"):
         ratio = np.where(err == 0, 0.0, err / b)
-    worst = float(ratio.max(initial=0.0))
-    WORST[fam] = max(WORST.get(fam, 0.0), worst)
-    if not worst <= 1.0:
+    top = float(ratio.max(initial=0.0))
+    worst[fam] = max(worst.get(fam, 0.0), top)
+    if not top <= 1.0:
         k = int(np.argmax(ratio))
         where = np.argwhere(fin)[k]
         raise AssertionError(f"{what} [{fam}]: {int((ratio > 1).sum())} of {ratio.size} elements out of bound; worst at {tuple(where)}: "
@@ -330,8 +339,12 @@ def same_bits(a, b, what):
 
 
 def seg_sum(x, idx, n):
+    """float64 sums of the rows of x by segment idx (sorted, then reduceat: the arrays of the forms files reach a million elements)"""
     out = np.zeros((n,) + x.shape[1:], dtype=np.float64)
-    np.add.at(out, idx, x)
+    counts = np.bincount(idx, minlength=n)
+    ne = counts > 0
+    if ne.any():
+        out[ne] = np.add.reduceat(np.asarray(x, dtype=np.float64)[np.argsort(idx, kind="stable")], (np.cumsum(counts) - counts)[ne], axis=0)
     return out
 
 
