@@ -643,6 +643,95 @@ int32_t ngpde_csr_spgemm(int64_t n, int64_t nnz_p, const int32_t *p_rows, const 
                          int32_t *rows_out, int32_t *cols_out, float *vals_out, int32_t *row_ptr_out, int64_t *nnz_out,
                          ngpde_stream_t stream);
 
+/* ---- graph queries by node and by pair on a device COO list (src/NeuralGraphPDE.jl:4 re-exports GNNGraphs and with it the Graphs.jl
+ * queries a GNNGraph answers: has_edge, neighbors / inneighbors / outneighbors, adjacency_list, intersect, random_walk_pe): "is (s, t)
+ * an edge?", "who are node i's neighbours?", "which edges do two graphs share?", and the random-walk positional encoding.  The
+ * conventions are those of the blocks above: int32 lists with `index_base`, outputs sized by the caller to the upper bound given with
+ * each, sizes <= 2^31 - 1 (refused beyond), NULL and negative arguments refused before any device call (NGPDE_ERR_INVALID_ARGUMENT), a
+ * node id outside the node range NGPDE_ERR_DIMENSION_MISMATCH, found on the device by the launch that does the work without a read or
+ * write through it, the SMALLEST offending id named; data-dependent counts and errors through the status / HOST pointers after one
+ * synchronisation of `stream`.  No float atomics: every result is bitwise equal from run to run and independent of the launch
+ * geometry.  Only ngpde_coo_has_edge and ngpde_csr_random_walk_pe allocate nothing and can be captured into a HIP graph. */
+
+/* The sorted-key plan of a list (src/NeuralGraphPDE.jl:4: what has_edge and intersect read): keys_out device uint64[n_edges] = the 64-BIT
+ * keys s*n_nodes + t (0-based ends) ascending, positions_out device int32[n_edges] = the COO position of every sorted key.  ONE stable
+ * radix sort (the sort of ngpde_coo_coalesce and ngpde_coo_matrix), so equal keys ascend by COO position: the first sorted copy of a
+ * pair is its smallest position.  Temporaries from hipMalloc inside the call (not capturable).  Synchronises. */
+int32_t ngpde_coo_sort_keys(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, uint64_t *keys_out,
+                            int32_t *positions_out, ngpde_stream_t stream);
+
+/* has_edge (src/NeuralGraphPDE.jl:4): one lane per query bisects the plan (keys, positions: what ngpde_coo_sort_keys wrote; NULL with
+ * n_edges 0) for the first key >= qs*n_nodes + qt.  qs, qt device int64[n_queries] with `index_base`; found_out device uint8[n_queries]
+ * (nullable) = 1 / 0; eid_out device int32[n_queries] (nullable) = the SMALLEST COO position of an edge qs -> qt, or -1; at least one
+ * of the two.  status: device uint64[1], the caller's -- the entry zeroes it and the launch leaves 0 there or, if a query end lies
+ * outside the node range, a word that is not 0 (such a query gets 0 / -1).  Allocates nothing.  Outside a capture the word is read
+ * back after one synchronisation and a bad end is NGPDE_ERR_DIMENSION_MISMATCH naming the smallest; on a stream that is being captured
+ * nothing is read back and the word stays with the caller.  Zero queries and zero edges are valid. */
+int32_t ngpde_coo_has_edge(int64_t n_nodes, int64_t n_edges, const uint64_t *keys, const int32_t *positions, int64_t n_queries,
+                           const int64_t *qs, const int64_t *qt, int32_t index_base, uint8_t *found_out, int32_t *eid_out, uint64_t *status,
+                           ngpde_stream_t stream);
+
+/* adjacency_list / neighbors (src/NeuralGraphPDE.jl:4), in two entries like ngpde_csr_spgemm_count / ngpde_csr_spgemm.  The ROW of a node
+ * is that of ngpde_coo_sample_neighbors -- the COO positions of its outbound (NGPDE_DIR_OUT) or inbound (NGPDE_DIR_IN) edges in COO order,
+ * built by the same code (csrc/coo_rows.h) -- so parallel edges repeat and self loops are included.  nodes: device int64[n_listed],
+ * 0-based, in any order, repeats allowed (a node listed twice gets two rows), or NULL (with n_listed 0): every node.
+ *   ngpde_coo_adjacency_count   row_ptr_out int32[n_nodes + 1], row_eid_out int32[n_edges]: the rows of ALL nodes (what the fill reads);
+ *                               ptr_out int32[R + 1] (R = n_listed, or n_nodes with nodes NULL) = the exclusive scan of the listed rows'
+ *                               lengths (counted and scanned in 64 bits); total_out host = ptr_out[R], above 2^31 - 1
+ *                               NGPDE_ERR_INVALID_ARGUMENT.  A listed id outside the node range is NGPDE_ERR_DIMENSION_MISMATCH.
+ *                               Temporaries from hipMalloc.  Synchronises.
+ *   ngpde_coo_adjacency_fill    neighbors_out, eid_out int32[total]: row i of the result is neighbors_out[ptr[i] .. ptr[i + 1] - 1] = the
+ *                               other ends (as stored: with the list's index base) and eid_out = their COO positions.  One lane per
+ *                               OUTPUT ELEMENT, which finds its row by bisection in ptr: a hub's row is spread over as many lanes as it
+ *                               has neighbours.  Lists that are not what the count wrote (an element without a place in its row, a last
+ *                               offset that is not total) are NGPDE_ERR_INVALID_ARGUMENT, found by the launch, which reads nothing
+ *                               through them.  Synchronises once. */
+int32_t ngpde_coo_adjacency_count(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t dir,
+                                  int64_t n_listed, const int64_t *nodes, int32_t *row_ptr_out, int32_t *row_eid_out, int32_t *ptr_out,
+                                  int64_t *total_out, ngpde_stream_t stream);
+int32_t ngpde_coo_adjacency_fill(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t dir, int64_t n_listed,
+                                 const int64_t *nodes, const int32_t *row_ptr, const int32_t *row_eid, const int32_t *ptr, int64_t total,
+                                 int32_t *neighbors_out, int32_t *eid_out, ngpde_stream_t stream);
+
+/* intersect (src/NeuralGraphPDE.jl:4): the DISTINCT pairs (s, t) that are edges of both lists, in the order of their first appearance
+ * in the first list.  (s, t): the first list; keys, positions: its plan; keys2 uint64[n_edges2]: the sorted keys of the second list's
+ * plan (same n_nodes).  One lane per edge of the first list: it is kept iff its position is the one its own plan lists first for
+ * its key and the key occurs in keys2 (two bisections); then the stable compaction of ngpde_coo_compact (csrc/coo_compact.h): s_out,
+ * t_out int32[n_edges], kept int64[n_edges] (upper bounds) = the kept edges' positions in the first list, n_out host.  Temporaries
+ * from hipMalloc.  Synchronises. */
+int32_t ngpde_coo_intersect(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, const uint64_t *keys,
+                            const int32_t *positions, int64_t n_edges2, const uint64_t *keys2, int32_t *s_out, int32_t *t_out, int64_t *kept,
+                            int64_t *n_out, ngpde_stream_t stream);
+
+/* random_walk_pe (src/NeuralGraphPDE.jl:4): pe float[walk_length][n], pe[k - 1][i] = (RW^k)[i][i].  No gradient, as upstream.
+ *   A            (row_ptr, cols, vals) = adjacency_matrix(g, dir = out, weighted) exactly as ngpde_coo_matrix(NGPDE_MATRIX_ADJ) assembles
+ *                it: coalesced, weights summed in COO order, entries ordered by row, then column
+ *   d[j]         the sum of row j's entries, front to back, from 0.0f;  inv[j] = d[j] == 0 ? 0 : 1.0f / d[j]
+ *   RW[i][j]     = A[i][j] * inv[j], rounded once.  A node without outgoing weight has an all-zero column: its pe is 0, never inf / nan
+ *   Y = RW X     per row i and column c: Y[i][c] = the sum over the entries of row i IN ASCENDING COLUMN ORDER, from 0.0f, of
+ *                RW[i][j] * X[j][c], every term one multiply and one add, each rounded (the library is built with -ffp-contract=off)
+ * Seeds are taken in blocks of `block` consecutive nodes [b0, b0 + block): the state X [n][block] holds in column c the walk started
+ * at node b0 + c (X_0 = those rows of the identity), one step is X <- RW X, ping-ponged between two buffers of the workspace, and the
+ * step's launch stores the diagonal itself: the wave that finishes row i in [b0, b0 + block) writes Y[i][i - b0] to pe[k - 1][i].  A wave
+ * per (row, 64 or 256 columns), the lanes over the columns, so an entry's row of X is one contiguous read.  ceil(n / block) *
+ * walk_length step launches and one init launch per block.
+ *   block        a multiple of 64 (anything else NGPDE_ERR_INVALID_ARGUMENT); 0: the library's choice (256, fewer for fewer nodes or where
+ *                the state would pass 256 MiB).  Columns are independent and every sum has a fixed order: THE RESULT DOES NOT DEPEND ON
+ *                IT, nor on the grid, nor on whether a graph is solved alone or as a member of a batch.
+ *   graph_of     device int32[n], 0-based, or NULL with n_graphs 1: the matrix is block-diagonal over the graphs (NOT CHECKED).  Where
+ *                graph_of is non-decreasing (checked on the device) a block's launches cover only the rows of the graphs its seeds lie
+ *                in -- a batch costs the sum of N_g^2, not N^2 --, otherwise all rows.  An id outside 0 : n_graphs - 1 is
+ *                NGPDE_ERR_INVALID_ARGUMENT.
+ *   workspace    ngpde_csr_random_walk_pe_workspace_bytes(n, block) = 2 * n * block * 4 (the two states) plus a part that does not depend
+ *                on block: n * 4 rounded up to a multiple of 256 (inv) + 256 (flag words); 0 for invalid arguments.  16-byte aligned.
+ * Allocates nothing.  Outside a capture it synchronises once before the first step (the flags and the row ranges are read back; a
+ * column or row pointer outside the matrix is NGPDE_ERR_DIMENSION_MISMATCH); on a stream that is being captured nothing is read back,
+ * every launch covers all rows -- the same bits -- and a column outside the matrix contributes nothing. */
+size_t ngpde_csr_random_walk_pe_workspace_bytes(int64_t n, int32_t block);
+int32_t ngpde_csr_random_walk_pe(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *cols, const float *vals, int32_t n_graphs,
+                                 const int32_t *graph_of, int32_t walk_length, int32_t block, float *pe, void *workspace, size_t workspace_bytes,
+                                 ngpde_stream_t stream);
+
 /* GNOConv message (src/layers.jl:527-530): K_e = reshape(phi_out[:, e], cout, cin) column-major,
  * m_e = K_e * h[:, s_e].  k: [E][cin*cout] p order (element o + cout*i), h: [N][cin], m: [E][cout]. */
 int32_t ngpde_gno_contract_forward(const ngpde_graph_t *g, int32_t cin, int32_t cout, const float *k, const float *h,

@@ -22,6 +22,7 @@ from .editing import (add_edges, add_nodes, get_edge_weight, negative_sample, re
                       to_unidirected)
 from .matrices import (GraphMatrix, adjacency_matrix, has_isolated_nodes, khop_adj, laplacian_lambda_max, laplacian_matrix,
                        normalized_laplacian, scaled_laplacian)
+from .queries import (AdjacencyList, adjacency_list, has_edge, inneighbors, intersect, neighbors, outneighbors, random_walk_pe)
 from . import dist, optim, synth
 
 
@@ -43,4 +44,5 @@ __all__ = [
     "add_nodes", "add_edges", "remove_edges", "remove_nodes", "to_unidirected", "set_edge_weight", "get_edge_weight", "negative_sample",
     "GraphMatrix", "adjacency_matrix", "laplacian_matrix", "normalized_laplacian", "scaled_laplacian", "laplacian_lambda_max", "khop_adj",
     "has_isolated_nodes",
+    "AdjacencyList", "adjacency_list", "has_edge", "neighbors", "inneighbors", "outneighbors", "intersect", "random_walk_pe",
 ]

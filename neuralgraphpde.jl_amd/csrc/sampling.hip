@@ -22,6 +22,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "coo_rows.h"
 #include "philox.h"
 
 namespace ngpde {
@@ -66,21 +67,7 @@ __global__ void random_keys_kernel(unsigned long long seed, uint32_t stream, uin
   if (i < n) out[i] = philox_draw(seed, stream, (uint32_t)(first + (unsigned long long)i), c1);
 }
 
-// ---- rows -------------------------------------------------------------------------------------------------------------------
-// the sort key of edge e: the node whose row it lies in.  Both ends are checked; a bad edge raises kBadEdge and goes to row 0.
-__global__ void row_keys_kernel(int64_t m, int64_t n, int base, int dir, const int32_t *__restrict__ s, const int32_t *__restrict__ t,
-                                uint32_t *__restrict__ key, int32_t *__restrict__ iota, int32_t *__restrict__ flags) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= m) return;
-  const int64_t a = (int64_t)s[e] - base, b = (int64_t)t[e] - base;
-  int64_t v = dir == NGPDE_DIR_IN ? b : a;
-  if (a < 0 || a >= n || b < 0 || b >= n) {
-    atomicOr(&flags[kBadEdge], 1);
-    v = 0;
-  }
-  key[e] = (uint32_t)v;
-  iota[e] = (int32_t)e;
-}
+// ---- rows: coo_rows.h (row_keys_kernel, rowptr_kernel, Rows, build_rows), shared with graph_query.hip ---------------------------
 
 // listed[v] = 1 for every listed node; an entry out of range or listed twice raises kBadNode
 __global__ void mark_listed_kernel(int64_t n_listed, int64_t n, const int64_t *__restrict__ nodes, int32_t *__restrict__ listed,
@@ -90,19 +77,6 @@ __global__ void mark_listed_kernel(int64_t n_listed, int64_t n, const int64_t *_
   const int64_t v = nodes[i];
   if (v < 0 || v >= n) atomicOr(&flags[kBadNode], 1);
   else if (atomicExch(&listed[v], 1) != 0) atomicOr(&flags[kBadNode], 1);
-}
-
-// rowptr[v] = the first position of the sorted row keys that is >= v, v = 0 .. n
-__global__ void rowptr_kernel(int64_t n, int64_t m, const uint32_t *__restrict__ key, int32_t *__restrict__ rowptr) {
-  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v > n) return;
-  int64_t lo = 0, hi = m;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (key[mid] < (uint32_t)v) lo = mid + 1;
-    else hi = mid;
-  }
-  rowptr[v] = (int32_t)lo;
 }
 
 // ---- selection without replacement --------------------------------------------------------------------------------------------
@@ -350,34 +324,6 @@ int32_t inclusive_scan_i32(const int32_t *in, int32_t *out, size_t count, Scratc
   return NGPDE_OK;
 }
 
-// the rows of the list: the COO positions grouped stably by target (NGPDE_DIR_IN) or source, as ngpde_coo_degree groups them
-struct Rows {
-  uint32_t *row_of = nullptr;   // [E] the node of every sorted position
-  int32_t *eid = nullptr;       // [E] the COO position of every sorted position
-  int32_t *rowptr = nullptr;    // [N + 1]
-};
-
-int32_t build_rows(int64_t n, int64_t m, const int32_t *s, const int32_t *t, int base, int dir, Rows *rows, int32_t *flags, Scratch &sc,
-                   hipStream_t stream) {
-  uint32_t *key = nullptr;
-  int32_t *iota = nullptr;
-  int32_t st;
-  if ((st = sc.get(&key, (size_t)m)) || (st = sc.get(&rows->row_of, (size_t)m)) || (st = sc.get(&iota, (size_t)m)) ||
-      (st = sc.get(&rows->eid, (size_t)m)) || (st = sc.get(&rows->rowptr, (size_t)n + 1)))
-    return st;
-  hipLaunchKernelGGL(row_keys_kernel, dim3(blocks_for(m)), dim3(kB), 0, stream, m, n, base, dir, s, t, key, iota, flags);
-  NGPDE_LAUNCH_CHECK("row_keys_kernel");
-  const unsigned end_bit = bits_for((unsigned long long)std::max<int64_t>(n, 2));
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key, rows->row_of, iota, rows->eid, (size_t)m, 0u, end_bit, stream));
-  if ((st = sc.get((char **)&tmp, bytes))) return st;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, key, rows->row_of, iota, rows->eid, (size_t)m, 0u, end_bit, stream));
-  hipLaunchKernelGGL(rowptr_kernel, dim3(blocks_for(n + 1)), dim3(kB), 0, stream, n, m, rows->row_of, rows->rowptr);
-  NGPDE_LAUNCH_CHECK("rowptr_kernel");
-  return NGPDE_OK;
-}
-
 }  // namespace
 
 }  // namespace ngpde
@@ -433,7 +379,7 @@ int32_t ngpde_coo_sample_neighbors(int64_t n_nodes, int64_t n_edges, const int32
   }
   if (n_edges > 0) {
     Rows rows;
-    if ((st = build_rows(n_nodes, n_edges, s, t, index_base, dir, &rows, flags, sc, stream))) return st;
+    if ((st = build_rows(n_nodes, n_edges, s, t, index_base, dir, &rows, flags + kBadEdge, sc, stream))) return st;
     if (!replace) {
       int32_t *keep = nullptr, *pos = nullptr;
       if ((st = sc.get(&keep, (size_t)n_edges)) || (st = sc.get(&pos, (size_t)n_edges))) return st;
