@@ -1,58 +1,27 @@
-// coo_compact.h -- what the files that rewrite a device COO list share (graph_ops.hip, graph_edit.hip): the temporaries of one call,
-// the rocPRIM scans, and the stable compaction
+// coo_compact.h -- the stable compaction that the files that rewrite a device COO list share (graph_ops.hip, graph_edit.hip,
+// graph_query.hip, graph_matrix.hip):
 //   flags -> exclusive scan -> scatter: kept edges stay in COO order
-// so that ngpde_coo_compact and ngpde_coo_remove_edges run one definition of it.  Everything here has internal linkage.
+// so that ngpde_coo_compact, ngpde_coo_remove_edges and ngpde_coo_intersect run one definition of it.  The temporaries and the rest of
+// the host-side kit are device_scratch.h's.  Everything here has internal linkage.
 #pragma once
 
-#include <algorithm>
 #include <cstdint>
-#include <vector>
 
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "device_scratch.h"
 
 namespace ngpde {
 
 namespace {
 
-constexpr int kB = 256;
-inline unsigned blocks_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kB - 1) / kB); }
-
-struct Scratch {   // device temporaries of one call; freed on scope exit
-  std::vector<void *> ptrs;
-  ~Scratch() {
-    for (void *p : ptrs) (void)hipFree(p);
-  }
-  template <class T>
-  int32_t get(T **p, size_t count) {
-    *p = nullptr;
-    NGPDE_HIP_CHECK(hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
-    ptrs.push_back(*p);
-    return NGPDE_OK;
-  }
-};
-
-unsigned bits_for(unsigned long long n) {   // bits that hold every value below n
-  unsigned b = 1;
-  while (b < 64 && (1ull << b) < n) ++b;
-  return b;
-}
-
 template <class T>
 int32_t scan_i32(bool inclusive, const int32_t *in, T *out, size_t count, Scratch &sc, hipStream_t stream) {
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  if (inclusive) {
-    NGPDE_HIP_CHECK(rocprim::inclusive_scan(nullptr, bytes, in, out, count, rocprim::plus<int32_t>(), stream));
-    if (int32_t st = sc.get((char **)&tmp, bytes)) return st;
-    NGPDE_HIP_CHECK(rocprim::inclusive_scan(tmp, bytes, in, out, count, rocprim::plus<int32_t>(), stream));
-  } else {
-    NGPDE_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, count, rocprim::plus<int32_t>(), stream));
-    if (int32_t st = sc.get((char **)&tmp, bytes)) return st;
-    NGPDE_HIP_CHECK(rocprim::exclusive_scan(tmp, bytes, in, out, 0, count, rocprim::plus<int32_t>(), stream));
-  }
-  return NGPDE_OK;
+  return with_temp(sc, [&](void *tmp, size_t &bytes) {
+    return inclusive ? rocprim::inclusive_scan(tmp, bytes, in, out, count, rocprim::plus<int32_t>(), stream)
+                     : rocprim::exclusive_scan(tmp, bytes, in, out, 0, count, rocprim::plus<int32_t>(), stream);
+  });
 }
 
 // edge e with keep[e] != 0 goes to slot pos[e] (pos = the exclusive scan of keep), renumbered through `relabel` if given; *count =

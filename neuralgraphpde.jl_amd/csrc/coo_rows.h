@@ -1,7 +1,8 @@
 // coo_rows.h -- the by-node rows of a device COO list, shared by the files that walk a node's edges in COO order (sampling.hip:
 // sample_neighbors; graph_query.hip: adjacency_list), so that both read one definition of a ROW: the COO positions grouped stably by
 // target (NGPDE_DIR_IN) or source (NGPDE_DIR_OUT) with rocPRIM's LSD radix sort, as ngpde_coo_degree groups them, and a row pointer
-// found by bisection.  Everything here has internal linkage; the temporaries come from the including file's Scratch type.
+// found by bisection.  Everything here has internal linkage; the temporaries, the launch sizing and the bisection are
+// device_scratch.h's.
 #pragma once
 
 #include <algorithm>
@@ -10,13 +11,11 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "device_scratch.h"
 
 namespace ngpde {
 
 namespace {
-
-constexpr int kRowsB = 256;
-inline unsigned rows_blocks_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kRowsB - 1) / kRowsB); }
 
 // the sort key of edge e: the node whose row it lies in.  Both ends are checked; a bad edge sets *bad and goes to row 0.
 __global__ void row_keys_kernel(int64_t m, int64_t n, int base, int dir, const int32_t *__restrict__ s, const int32_t *__restrict__ t,
@@ -37,13 +36,7 @@ __global__ void row_keys_kernel(int64_t m, int64_t n, int base, int dir, const i
 __global__ void rowptr_kernel(int64_t n, int64_t m, const uint32_t *__restrict__ key, int32_t *__restrict__ rowptr) {
   const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (v > n) return;
-  int64_t lo = 0, hi = m;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (key[mid] < (uint32_t)v) lo = mid + 1;
-    else hi = mid;
-  }
-  rowptr[v] = (int32_t)lo;
+  rowptr[v] = (int32_t)lower_bound_dev(key, m, (uint32_t)v);
 }
 
 struct Rows {
@@ -54,8 +47,7 @@ struct Rows {
 
 // A member of *rows that is not NULL on entry is the caller's buffer and is written in place; the others are temporaries of `sc`.
 // bad: the device word an edge end outside the node range sets.
-template <class ScratchT>
-int32_t build_rows(int64_t n, int64_t m, const int32_t *s, const int32_t *t, int base, int dir, Rows *rows, int32_t *bad, ScratchT &sc,
+int32_t build_rows(int64_t n, int64_t m, const int32_t *s, const int32_t *t, int base, int dir, Rows *rows, int32_t *bad, Scratch &sc,
                    hipStream_t stream) {
   uint32_t *key = nullptr;
   int32_t *iota = nullptr;
@@ -63,16 +55,14 @@ int32_t build_rows(int64_t n, int64_t m, const int32_t *s, const int32_t *t, int
   if ((st = sc.get(&key, (size_t)m)) || (!rows->row_of && (st = sc.get(&rows->row_of, (size_t)m))) || (st = sc.get(&iota, (size_t)m)) ||
       (!rows->eid && (st = sc.get(&rows->eid, (size_t)m))) || (!rows->rowptr && (st = sc.get(&rows->rowptr, (size_t)n + 1))))
     return st;
-  hipLaunchKernelGGL(row_keys_kernel, dim3(rows_blocks_for(m)), dim3(kRowsB), 0, stream, m, n, base, dir, s, t, key, iota, bad);
+  hipLaunchKernelGGL(row_keys_kernel, dim3(blocks_for(m)), dim3(kB), 0, stream, m, n, base, dir, s, t, key, iota, bad);
   NGPDE_LAUNCH_CHECK("row_keys_kernel");
-  unsigned end_bit = 1;   // bits that hold every node id below max(n, 2)
-  while (end_bit < 64 && (1ull << end_bit) < (unsigned long long)std::max<int64_t>(n, 2)) ++end_bit;
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key, rows->row_of, iota, rows->eid, (size_t)m, 0u, end_bit, stream));
-  if ((st = sc.get((char **)&tmp, bytes))) return st;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, key, rows->row_of, iota, rows->eid, (size_t)m, 0u, end_bit, stream));
-  hipLaunchKernelGGL(rowptr_kernel, dim3(rows_blocks_for(n + 1)), dim3(kRowsB), 0, stream, n, m, rows->row_of, rows->rowptr);
+  const unsigned end_bit = bits_for(std::max<int64_t>(n, 2));
+  auto sort = [&](void *tmp, size_t &bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, key, rows->row_of, iota, rows->eid, (size_t)m, 0u, end_bit, stream);
+  };
+  if ((st = with_temp(sc, sort))) return st;
+  hipLaunchKernelGGL(rowptr_kernel, dim3(blocks_for(n + 1)), dim3(kB), 0, stream, n, m, rows->row_of, rows->rowptr);
   NGPDE_LAUNCH_CHECK("rowptr_kernel");
   return NGPDE_OK;
 }

@@ -57,6 +57,9 @@ __device__ __forceinline__ float act_deriv(int act, float z) {
   }
 }
 
+// is p 16-byte aligned (may a float4 be read through it)?  What the entries ask before they take a float4 kernel.
+inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float4 f4_fma(float a, float4 v, float4 c) {
   return make_float4(fmaf(a, v.x, c.x), fmaf(a, v.y, c.y), fmaf(a, v.z, c.z), fmaf(a, v.w, c.w));

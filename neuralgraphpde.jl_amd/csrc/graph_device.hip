@@ -18,6 +18,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "device_scratch.h"
 
 namespace ngpde {
 
@@ -25,9 +26,6 @@ std::vector<int32_t> locality_order_host(int64_t n, const std::vector<int32_t> &
                                          const std::vector<int32_t> &rp_out, const std::vector<int32_t> &col_out, int tile);
 
 namespace {
-
-constexpr int kB = 256;
-inline unsigned blocks_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kB - 1) / kB); }
 
 template <class I>
 __global__ void convert_kernel(int64_t m, int64_t n, int base, const I *__restrict__ s, const I *__restrict__ t,
@@ -237,37 +235,11 @@ __global__ void order_check_kernel(int64_t n, const int32_t *__restrict__ order,
   else if (atomicAdd(&seen[o], 1) != 0) atomicOr(bad, 1);
 }
 
-template <class T>
-int32_t dalloc(T **p, size_t count) {
-  *p = nullptr;
-  NGPDE_HIP_CHECK(hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
-  return NGPDE_OK;
-}
-
-struct Scratch {   // frees on scope exit
-  std::vector<void *> ptrs;
-  ~Scratch() {
-    for (void *p : ptrs) (void)hipFree(p);
-  }
-  template <class T>
-  int32_t get(T **p, size_t count) {
-    int32_t st = dalloc(p, count);
-    if (!st) ptrs.push_back(*p);
-    return st;
-  }
-};
-
-int bits_for(int64_t n) {
-  int b = 1;
-  while (((int64_t)1 << b) < n) ++b;
-  return b;
-}
-
 // CSR of one direction: stable sort of the COO positions by `key`
 int32_t build_csr_device(int64_t n, int64_t m, const int32_t *key, const int32_t *other, const int32_t *iota, Csr &out,
                          int32_t *pos_of_edge, Scratch &sc, hipStream_t stream) {
   int32_t st;
-  if ((st = dalloc(&out.rowptr, (size_t)n + 1)) || (st = dalloc(&out.col, (size_t)m)) || (st = dalloc(&out.eid, (size_t)m)))
+  if ((st = dev_alloc(&out.rowptr, (size_t)n + 1)) || (st = dev_alloc(&out.col, (size_t)m)) || (st = dev_alloc(&out.eid, (size_t)m)))
     return st;
   int32_t *deg = nullptr, *keys_sorted = nullptr;
   if ((st = sc.get(&deg, (size_t)n + 1)) || (st = sc.get(&keys_sorted, (size_t)m))) return st;
@@ -276,18 +248,16 @@ int32_t build_csr_device(int64_t n, int64_t m, const int32_t *key, const int32_t
     hipLaunchKernelGGL(count_kernel, dim3(blocks_for(m)), dim3(kB), 0, stream, m, key, deg);
     NGPDE_LAUNCH_CHECK("count_kernel");
   }
-  size_t tb = 0;
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, deg, out.rowptr, 0, (size_t)n + 1, rocprim::plus<int32_t>(), stream));
-  void *tmp = nullptr;
-  if ((st = sc.get((char **)&tmp, tb))) return st;
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(tmp, tb, deg, out.rowptr, 0, (size_t)n + 1, rocprim::plus<int32_t>(), stream));
+  auto scan = [&](void *tmp, size_t &bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, deg, out.rowptr, 0, (size_t)n + 1, rocprim::plus<int32_t>(), stream);
+  };
+  if ((st = with_temp(sc, scan))) return st;
   if (m > 0) {
-    size_t sb = 0;
-    const unsigned end_bit = (unsigned)bits_for(std::max<int64_t>(n, 2));
-    NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sb, key, keys_sorted, iota, out.eid, (size_t)m, 0u, end_bit, stream));
-    void *tmp2 = nullptr;
-    if ((st = sc.get((char **)&tmp2, sb))) return st;
-    NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp2, sb, key, keys_sorted, iota, out.eid, (size_t)m, 0u, end_bit, stream));
+    const unsigned end_bit = bits_for(std::max<int64_t>(n, 2));
+    auto sort = [&](void *tmp, size_t &bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, key, keys_sorted, iota, out.eid, (size_t)m, 0u, end_bit, stream);
+    };
+    if ((st = with_temp(sc, sort))) return st;
     hipLaunchKernelGGL(gather_col_kernel, dim3(blocks_for(m)), dim3(kB), 0, stream, m, out.eid, other, out.col, pos_of_edge);
     NGPDE_LAUNCH_CHECK("gather_col_kernel");
   }
@@ -320,7 +290,7 @@ int32_t set_gcn_norm_device(ngpde_graph *g, int add_self_loops, const float *w_d
   const int64_t n = g->n_nodes, m = g->n_edges;
   free_norm(g);
   int32_t st;
-  if ((st = dalloc(&g->c, (size_t)n))) return st;
+  if ((st = dev_alloc(&g->c, (size_t)n))) return st;
   if (n > 0) {
     hipLaunchKernelGGL(norm_kernel, dim3(blocks_for(n)), dim3(kB), 0, stream, n, add_self_loops, weighted_degree, g->by_t.rowptr,
                        g->by_t.eid, w_dev, g->c);
@@ -333,11 +303,11 @@ int32_t set_gcn_norm_device(ngpde_graph *g, int add_self_loops, const float *w_d
   NGPDE_HIP_CHECK(hipMemsetAsync(bad, 0, 8 * sizeof(int32_t), stream));
   int dir = 0;
   for (Csr *c2 : {&g->by_t, &g->by_s}) {
-    if ((st = dalloc(&c2->ent, (size_t)m)) || (st = dalloc(&c2->sched, (size_t)g->n_sched)) ||
-        (st = dalloc(&c2->ell, (size_t)g->n_sched * kEllWidth)) || (st = dalloc(&c2->halo, (size_t)n_tiles * kHaloCap)) ||
-        (st = dalloc(&c2->tile_info, (size_t)n_tiles)) || (st = dalloc(&c2->slots, (size_t)g->n_sched * kSlotWidth)))
+    if ((st = dev_alloc(&c2->ent, (size_t)m)) || (st = dev_alloc(&c2->sched, (size_t)g->n_sched)) ||
+        (st = dev_alloc(&c2->ell, (size_t)g->n_sched * kEllWidth)) || (st = dev_alloc(&c2->halo, (size_t)n_tiles * kHaloCap)) ||
+        (st = dev_alloc(&c2->tile_info, (size_t)n_tiles)) || (st = dev_alloc(&c2->slots, (size_t)g->n_sched * kSlotWidth)))
       return st;
-    if (w_dev && (st = dalloc(&c2->slot_w, (size_t)g->n_sched * kSlotWidth))) return st;
+    if (w_dev && (st = dev_alloc(&c2->slot_w, (size_t)g->n_sched * kSlotWidth))) return st;
     if (m > 0) {
       hipLaunchKernelGGL(ent_kernel, dim3(blocks_for(m)), dim3(kB), 0, stream, m, c2->col, c2->eid, w_dev, g->c, c2->ent);
       NGPDE_LAUNCH_CHECK("ent_kernel");
@@ -360,7 +330,7 @@ int32_t set_gcn_norm_device(ngpde_graph *g, int add_self_loops, const float *w_d
   g->by_t.halo_ok = n_tiles > 0 && h_bad[0] == 0;
   g->by_s.halo_ok = n_tiles > 0 && h_bad[4] == 0;
   if (w_dev && m > 0 && !(g->by_t.halo_ok && g->by_s.halo_ok)) {   // (kept for the persistent solver's hub geometry: graph.hip)
-    if ((st = dalloc(&g->w_coo, (size_t)m))) return st;
+    if ((st = dev_alloc(&g->w_coo, (size_t)m))) return st;
     NGPDE_HIP_CHECK(hipMemcpyAsync(g->w_coo, w_dev, (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, stream));
     NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
   }
@@ -404,7 +374,7 @@ int32_t graph_create_device(int64_t n_nodes, int64_t n_edges, const I *s, const 
   if ((st = build_csr_device(n_nodes, n_edges, t32, s32, iota, g->by_t, pos_t, sc, stream)) ||
       (st = build_csr_device(n_nodes, n_edges, s32, t32, iota, g->by_s, pos_s, sc, stream)))
     return bail(st);
-  if ((st = dalloc(&g->by_t.xpos, (size_t)n_edges)) || (st = dalloc(&g->by_s.xpos, (size_t)n_edges))) return bail(st);
+  if ((st = dev_alloc(&g->by_t.xpos, (size_t)n_edges)) || (st = dev_alloc(&g->by_s.xpos, (size_t)n_edges))) return bail(st);
   if (n_edges > 0) {
     hipLaunchKernelGGL(xpos_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, g->by_t.eid, pos_s, g->by_t.xpos);
     hipLaunchKernelGGL(xpos_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, g->by_s.eid, pos_t, g->by_s.xpos);
@@ -425,7 +395,7 @@ int32_t graph_create_device(int64_t n_nodes, int64_t n_edges, const I *s, const 
                      (long long)h_bad + index_base, (long long)n_nodes));
   g->max_in_degree = h_max[0];
   g->max_out_degree = h_max[1];
-  if ((st = dalloc(&g->order, (size_t)n_nodes))) return bail(st);
+  if ((st = dev_alloc(&g->order, (size_t)n_nodes))) return bail(st);
   if (order_dev) {
     int32_t *seen = nullptr;
     if ((st = sc.get(&seen, (size_t)n_nodes + 1))) return bail(st);

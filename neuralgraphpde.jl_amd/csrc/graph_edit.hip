@@ -31,53 +31,14 @@ namespace ngpde {
 namespace {
 
 // device flag words of one call
-enum { kBadEnd = 0, kCross = 1, kBadListed = 2, kBadEdge = 3, kCount = 4, kPairs = 5, kFlagWords = 8 };
+enum { kBadEnd = 0, kCross = 1, kBadListed = 2, kBadEdge = 3, kCount = 4, kPairs = 5 };
 
 using u64 = unsigned long long;
 
-int32_t check_coo(const char *fn, int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t) {
-  NGPDE_REQUIRE(n_nodes >= 0 && n_edges >= 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: negative size (n_nodes %lld, n_edges %lld)", fn,
-                (long long)n_nodes, (long long)n_edges);
-  NGPDE_REQUIRE(n_nodes <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "%s: %lld nodes, at most 2^31 - 1", fn, (long long)n_nodes);
-  NGPDE_REQUIRE(n_edges <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "%s: %lld edges, at most 2^31 - 1", fn, (long long)n_edges);
-  NGPDE_REQUIRE(n_edges == 0 || (s && t), NGPDE_ERR_INVALID_ARGUMENT, "%s: s / t is NULL", fn);
-  NGPDE_REQUIRE(n_edges == 0 || n_nodes > 0, NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: %lld edges on a graph without nodes", fn,
-                (long long)n_edges);
-  return NGPDE_OK;
-}
-
-int32_t read_flags(const int32_t *flags, int32_t *h, hipStream_t stream) {
-  NGPDE_HIP_CHECK(hipMemcpyAsync(h, flags, kFlagWords * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
-  return NGPDE_OK;
-}
-
-int32_t new_flags(Scratch &sc, int32_t **flags, hipStream_t stream) {
-  if (int32_t st = sc.get(flags, kFlagWords)) return st;
-  NGPDE_HIP_CHECK(hipMemsetAsync(*flags, 0, kFlagWords * sizeof(int32_t), stream));
-  return NGPDE_OK;
-}
-
 // is v among the m ascending keys?
 __device__ __forceinline__ bool contains_u64(const u64 *__restrict__ key, int64_t m, u64 v) {
-  int64_t lo = 0, hi = m;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (key[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
+  const int64_t lo = lower_bound_dev(key, m, v);
   return lo < m && key[lo] == v;
-}
-
-// the number of the m ascending keys that are < v
-__device__ __forceinline__ int64_t lower_bound_u64(const u64 *__restrict__ key, int64_t m, u64 v) {
-  int64_t lo = 0, hi = m;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (key[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // ---- append -------------------------------------------------------------------------------------------------------------------
@@ -240,12 +201,12 @@ __global__ void merge_kernel(int64_t n_a, int64_t c, const u64 *__restrict__ key
   if (i >= n_a + c) return;
   const int64_t n_new = *n_new_;
   if (i < n_a) {
-    const int64_t o = i + lower_bound_u64(key_new, n_new, key_a[i]);
+    const int64_t o = i + lower_bound_dev(key_new, n_new, key_a[i]);
     key_out[o] = key_a[i];
     seq_out[o] = seq_a[i];
   } else if (i - n_a < n_new) {
     const int64_t k = i - n_a;
-    const int64_t o = k + lower_bound_u64(key_a, n_a, key_new[k]);
+    const int64_t o = k + lower_bound_dev(key_a, n_a, key_new[k]);
     key_out[o] = key_new[k];
     seq_out[o] = seq_new[k];
   }
@@ -266,12 +227,7 @@ __global__ void decode_kernel(int64_t n_target, u64 n, int base, int both, const
 }
 
 int32_t sort_keys_u64(const u64 *in, u64 *out, size_t count, unsigned end_bit, Scratch &sc, hipStream_t stream) {
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, in, out, count, 0u, end_bit, stream));
-  if (int32_t st = sc.get((char **)&tmp, bytes)) return st;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_keys(tmp, bytes, in, out, count, 0u, end_bit, stream));
-  return NGPDE_OK;
+  return with_temp(sc, [&](void *tmp, size_t &bytes) { return rocprim::radix_sort_keys(tmp, bytes, in, out, count, 0u, end_bit, stream); });
 }
 
 }  // namespace
@@ -478,8 +434,10 @@ int32_t ngpde_coo_negative_sample(int64_t n_nodes, int64_t n_edges, const int32_
   int32_t *head = nullptr, *pos = nullptr;
   void *sort_tmp = nullptr, *scan_tmp = nullptr;   // one allocation each for all the rounds
   size_t sort_bytes = 0, scan_bytes = 0;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, key, key_sorted, seq, seq_sorted, c, 0u, key_bits, stream));
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, head, pos, 0, c, rocprim::plus<int32_t>(), stream));
+  // (by reference: the lists are allocated below, and a size query reads none of them)
+  auto sort = [&](void *tmp, size_t &bytes) { return rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, seq, seq_sorted, c, 0u, key_bits, stream); };
+  auto scan = [&](void *tmp, size_t &bytes) { return rocprim::exclusive_scan(tmp, bytes, head, pos, 0, c, rocprim::plus<int32_t>(), stream); };
+  if ((st = temp_bytes(&sort_bytes, sort)) || (st = temp_bytes(&scan_bytes, scan))) return st;
   if ((st = sc.get(&key, c)) || (st = sc.get(&seq, c)) || (st = sc.get(&key_sorted, c)) || (st = sc.get(&seq_sorted, c)) ||
       (st = sc.get(&key_new, c)) || (st = sc.get(&seq_new, c)) || (st = sc.get(&head, c)) || (st = sc.get(&pos, c)) ||
       (st = sc.get(&key_acc[0], room)) || (st = sc.get(&seq_acc[0], room)) || (st = sc.get(&key_acc[1], room)) ||
@@ -495,10 +453,10 @@ int32_t ngpde_coo_negative_sample(int64_t n_nodes, int64_t n_edges, const int32_
     hipLaunchKernelGGL(candidates_kernel, dim3(blocks_for(chunk)), dim3(kB), 0, stream, chunk, done, (u64)seed, n, n_codes, bidirected ? 1 : 0, graph,
                        n_edges, key_acc[cur], n_acc, none, key, seq);
     NGPDE_LAUNCH_CHECK("candidates_kernel");
-    NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(sort_tmp, sort_bytes, key, key_sorted, seq, seq_sorted, c, 0u, key_bits, stream));
+    NGPDE_HIP_CHECK(sort(sort_tmp, sort_bytes));
     hipLaunchKernelGGL(new_heads_kernel, dim3(blocks_for(chunk)), dim3(kB), 0, stream, chunk, none, key_sorted, head);
     NGPDE_LAUNCH_CHECK("new_heads_kernel");
-    NGPDE_HIP_CHECK(rocprim::exclusive_scan(scan_tmp, scan_bytes, head, pos, 0, c, rocprim::plus<int32_t>(), stream));
+    NGPDE_HIP_CHECK(scan(scan_tmp, scan_bytes));
     hipLaunchKernelGGL(take_heads_kernel, dim3(blocks_for(chunk)), dim3(kB), 0, stream, chunk, key_sorted, seq_sorted, head, pos, key_new, seq_new,
                        flags + kCount);
     NGPDE_LAUNCH_CHECK("take_heads_kernel");
@@ -513,13 +471,12 @@ int32_t ngpde_coo_negative_sample(int64_t n_nodes, int64_t n_edges, const int32_
   // the accepted set in sequence order, cut at n_target
   {
     u64 *seq_by = nullptr, *key_by = nullptr;
-    void *tmp = nullptr;
-    size_t bytes = 0;
     const unsigned seq_bits = bits_for(done + 1);
     if ((st = sc.get(&seq_by, (size_t)n_acc)) || (st = sc.get(&key_by, (size_t)n_acc))) return st;
-    NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, seq_acc[cur], seq_by, key_acc[cur], key_by, (size_t)n_acc, 0u, seq_bits, stream));
-    if ((st = sc.get((char **)&tmp, bytes))) return st;
-    NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, seq_acc[cur], seq_by, key_acc[cur], key_by, (size_t)n_acc, 0u, seq_bits, stream));
+    auto by_seq = [&](void *tmp, size_t &bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, seq_acc[cur], seq_by, key_acc[cur], key_by, (size_t)n_acc, 0u, seq_bits, stream);
+    };
+    if ((st = with_temp(sc, by_seq))) return st;
     hipLaunchKernelGGL(decode_kernel, dim3(blocks_for(n_target)), dim3(kB), 0, stream, n_target, n, index_base, bidirected ? 1 : 0, key_by, s_out,
                        t_out);
     NGPDE_LAUNCH_CHECK("decode_kernel");

@@ -31,46 +31,19 @@ namespace ngpde {
 namespace {
 
 // device flag words of one call
-enum { fBad = 0, fCount = 1, fZeroRow = 2, fOrder = 3, fCsr = 4, fWords = 8 };
+enum { fBad = 0, fCount = 1, fZeroRow = 2, fOrder = 3, fCsr = 4 };
 
 constexpr int kDotChunk = 1024;     // nodes per inner-product chunk: four per lane of the 256-thread workgroup
 constexpr int kSpmvLanes = 8;       // lanes per matrix row in the sparse product with a vector
 constexpr int kCheckEvery = 8;      // Lanczos steps between two read-backs of the tridiagonal matrix
 constexpr int kMaxIter = 4096;      // grid.y of the multi-vector inner product
 
-int32_t new_flags(Scratch &sc, int32_t **flags, hipStream_t stream) {
-  if (int32_t st = sc.get(flags, fWords)) return st;
-  NGPDE_HIP_CHECK(hipMemsetAsync(*flags, 0, fWords * sizeof(int32_t), stream));
-  return NGPDE_OK;
-}
-
-int32_t read_flags(const int32_t *flags, int32_t *h, hipStream_t stream) {
-  NGPDE_HIP_CHECK(hipMemcpyAsync(h, flags, fWords * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
-  return NGPDE_OK;
-}
-
 // the stable sort of m 64-bit keys below 2^end_bit with their positions as the payload
 int32_t sort_positions(int64_t m, unsigned end_bit, unsigned long long *key, unsigned long long *key_sorted, int32_t *iota, int32_t *perm,
                        Scratch &sc, hipStream_t stream) {
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key, key_sorted, iota, perm, (size_t)m, 0u, end_bit, stream));
-  if (int32_t st = sc.get((char **)&tmp, bytes)) return st;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, iota, perm, (size_t)m, 0u, end_bit, stream));
-  return NGPDE_OK;
-}
-
-// first position of the ascending list that is >= v
-template <class T>
-__device__ __forceinline__ int64_t lower_bound_dev(const T *__restrict__ a, int64_t m, T v) {
-  int64_t lo = 0, hi = m;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
+  return with_temp(sc, [&](void *tmp, size_t &bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, iota, perm, (size_t)m, 0u, end_bit, stream);
+  });
 }
 
 // ---- assembly -----------------------------------------------------------------------------------------------------------------
@@ -294,12 +267,9 @@ int32_t expand_offsets(int64_t n, int64_t nnz_p, const int32_t *p_cols, const in
   NGPDE_HIP_CHECK(hipMemsetAsync(cnt + nnz_p, 0, sizeof(long long), stream));
   hipLaunchKernelGGL(expand_count_kernel, dim3(blocks_for(nnz_p)), dim3(kB), 0, stream, nnz_p, n, nnz_a, p_cols, a_row_ptr, cnt, flags);
   NGPDE_LAUNCH_CHECK("expand_count_kernel");
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, cnt, *off, 0ll, (size_t)nnz_p + 1, rocprim::plus<long long>(), stream));
-  if ((st = sc.get((char **)&tmp, bytes))) return st;
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(tmp, bytes, cnt, *off, 0ll, (size_t)nnz_p + 1, rocprim::plus<long long>(), stream));
-  return NGPDE_OK;
+  return with_temp(sc, [&](void *tmp, size_t &bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, cnt, *off, 0ll, (size_t)nnz_p + 1, rocprim::plus<long long>(), stream);
+  });
 }
 
 int32_t check_product(const char *fn, int64_t n, int64_t nnz_p, int64_t nnz_a, const int32_t *p_cols, const int32_t *a_row_ptr) {
@@ -657,7 +627,7 @@ int32_t ngpde_coo_matrix(int64_t n_nodes, int64_t n_edges, const int32_t *s, con
   hipLaunchKernelGGL(matrix_values_kernel, dim3(blocks_for(m)), dim3(kB), 0, stream, m, kind, n_graphs, graph_of, scale, rows, cols, a, d, vals,
                      flags);
   NGPDE_LAUNCH_CHECK("matrix_values_kernel");
-  int32_t h[fWords];
+  int32_t h[kFlagWords];
   if ((st = read_flags(flags, h, stream))) return st;
   NGPDE_REQUIRE(!h[fBad], NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: an edge references a node outside the %lld nodes", fn,
                 (long long)n_nodes);
@@ -689,7 +659,7 @@ int32_t ngpde_csr_check_symmetric(int64_t n, int64_t nnz, const int32_t *row_ptr
   NGPDE_LAUNCH_CHECK("symmetry_kernel");
   unsigned long long h_first = 0;
   NGPDE_HIP_CHECK(hipMemcpyAsync(&h_first, first, sizeof(h_first), hipMemcpyDeviceToHost, stream));
-  int32_t h[fWords];
+  int32_t h[kFlagWords];
   if ((st = read_flags(flags, h, stream))) return st;
   NGPDE_REQUIRE(!h[fCsr], NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: an entry or a row pointer lies outside the %lld x %lld matrix", fn,
                 (long long)n, (long long)n);
@@ -746,7 +716,7 @@ int32_t ngpde_csr_lambda_max(int64_t n, int64_t nnz, const int32_t *row_ptr, con
   NGPDE_LAUNCH_CHECK("graph_ptr_kernel");
   std::vector<int32_t> h_gptr((size_t)n_graphs + 1);
   NGPDE_HIP_CHECK(hipMemcpyAsync(h_gptr.data(), gptr, h_gptr.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  int32_t hf[fWords];
+  int32_t hf[kFlagWords];
   if ((st = read_flags(flags, hf, stream))) return st;
   NGPDE_REQUIRE(!hf[fCsr], NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: a column or a row pointer lies outside the %lld x %lld matrix", fn,
                 (long long)n, (long long)n);
@@ -888,7 +858,7 @@ int32_t ngpde_csr_spgemm_count(int64_t n, int64_t nnz_p, const int32_t *p_cols, 
   if ((st = new_flags(sc, &flags, stream)) || (st = expand_offsets(n, nnz_p, p_cols, a_row_ptr, nnz_a, &off, flags, sc, stream))) return st;
   long long total = 0;
   NGPDE_HIP_CHECK(hipMemcpyAsync(&total, off + nnz_p, sizeof(total), hipMemcpyDeviceToHost, stream));
-  int32_t h[fWords];
+  int32_t h[kFlagWords];
   if ((st = read_flags(flags, h, stream))) return st;
   NGPDE_REQUIRE(!h[fBad] && !h[fCsr], NGPDE_ERR_DIMENSION_MISMATCH,
                 "%s: DimensionMismatch: a column of P or a row pointer of A lies outside the %lld x %lld matrices", fn, (long long)n, (long long)n);
@@ -944,7 +914,7 @@ int32_t ngpde_csr_spgemm(int64_t n, int64_t nnz_p, const int32_t *p_rows, const 
   NGPDE_LAUNCH_CHECK("product_values_kernel");
   hipLaunchKernelGGL(row_ptr_kernel, dim3(blocks_for(n + 1)), dim3(kB), 0, stream, n, rows_out, flags, row_ptr_out);
   NGPDE_LAUNCH_CHECK("row_ptr_kernel");
-  int32_t h[fWords];
+  int32_t h[kFlagWords];
   if ((st = read_flags(flags, h, stream))) return st;
   NGPDE_REQUIRE(!h[fCsr], NGPDE_ERR_INVALID_ARGUMENT, "%s: offsets / total are not what ngpde_csr_spgemm_count gives for these matrices", fn);
   NGPDE_REQUIRE(!h[fBad], NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: a row of P or a column of A lies outside the %lld x %lld matrices",

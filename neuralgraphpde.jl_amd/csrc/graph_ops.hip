@@ -25,10 +25,8 @@ namespace ngpde {
 
 namespace {
 
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // device flag words of one call
-enum { kBad = 0, kSelf = 1, kMulti = 2, kAsym = 3, kCount = 4, kFlagWords = 8 };
+enum { kBad = 0, kSelf = 1, kMulti = 2, kAsym = 3, kCount = 4 };
 
 // ---- keys ---------------------------------------------------------------------------------------------------------------------
 // copy c < E is edge c, copy c >= E edge c - E reversed; `reverse` flips every copy.  An end outside the node range raises kBad and
@@ -90,23 +88,12 @@ __global__ void node_keys_kernel(int64_t m, int64_t n, int base, const int32_t *
   iota[e] = (int32_t)e;
 }
 
-// first position of the sorted keys that is >= v
-__device__ __forceinline__ int64_t lower_bound_u32(const uint32_t *__restrict__ key, int64_t m, uint32_t v) {
-  int64_t lo = 0, hi = m;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (key[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // one thread per node: its run of the sorted positions, added front to back (COO order: the sort is stable)
 __global__ void degree_sum_kernel(int64_t n, int64_t m, const uint32_t *__restrict__ key, const int32_t *__restrict__ eid,
                                   const float *__restrict__ w, int accumulate, float *__restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  int64_t p = lower_bound_u32(key, m, (uint32_t)i);
+  int64_t p = lower_bound_dev(key, m, (uint32_t)i);
   float acc = 0.f;
   for (; p < m && key[p] == (uint32_t)i; ++p) acc += w[eid[p]];
   out[i] = accumulate ? out[i] + acc : acc;
@@ -168,16 +155,8 @@ __global__ void groups_kernel(int64_t m, int64_t n_edges, int64_t n, int base, c
 }
 
 // ---- group reduce -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float vmax2(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ float4 vmax2(float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
-__device__ __forceinline__ float vmin2(float a, float b) { return fminf(a, b); }
-__device__ __forceinline__ float4 vmin2(float4 a, float4 b) { return make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z), fminf(a.w, b.w)); }
 __device__ __forceinline__ float vdiv(float a, float c) { return a / c; }
 __device__ __forceinline__ float4 vdiv(float4 a, float c) { return make_float4(a.x / c, a.y / c, a.z / c, a.w / c); }
-__device__ __forceinline__ float vsel_eq(float a, float b, float v) { return a == b ? v : 0.f; }
-__device__ __forceinline__ float4 vsel_eq(float4 a, float4 b, float4 v) {
-  return make_float4(a.x == b.x ? v.x : 0.f, a.y == b.y ? v.y : 0.f, a.z == b.z ? v.z : 0.f, a.w == b.w ? v.w : 0.f);
-}
 
 // a lane per (group, column chunk): T = float4 covers 4 columns, T = float one; w = chunks per row.  Adjacent lanes take adjacent
 // chunks of the same group, so a member row is read as one contiguous run.
@@ -194,7 +173,7 @@ __global__ void group_reduce_fwd_kernel(int64_t n_groups, int w, int aggr, const
     acc = src[(size_t)member[begin] * w + c];
     for (int32_t p = begin + 1; p < end; ++p) {
       const T v = src[(size_t)member[p] * w + c];
-      acc = aggr == NGPDE_AGGR_MAX ? vmax2(acc, v) : aggr == NGPDE_AGGR_MIN ? vmin2(acc, v) : vadd(acc, v);
+      acc = aggr == NGPDE_AGGR_MAX ? vmax(acc, v) : aggr == NGPDE_AGGR_MIN ? vmin(acc, v) : vadd(acc, v);
     }
     if (aggr == NGPDE_AGGR_MEAN) acc = vdiv(acc, (float)(end - begin));
   }
@@ -239,30 +218,6 @@ __global__ void add_self_loops_kernel(int64_t n, int64_t m, int base, const int3
 }
 
 // ---- host helpers -------------------------------------------------------------------------------------------------------------
-int32_t check_coo(const char *fn, int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int64_t copies) {
-  NGPDE_REQUIRE(n_nodes >= 0 && n_edges >= 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: negative size (n_nodes %lld, n_edges %lld)", fn,
-                (long long)n_nodes, (long long)n_edges);
-  NGPDE_REQUIRE(n_nodes <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "%s: %lld nodes, at most 2^31 - 1", fn, (long long)n_nodes);
-  NGPDE_REQUIRE(n_edges <= 0x7fffffffLL / copies, NGPDE_ERR_INVALID_ARGUMENT, "%s: %lld edges%s, at most 2^31 - 1", fn,
-                (long long)(n_edges * copies), copies > 1 ? " after symmetrising" : "");
-  NGPDE_REQUIRE(n_edges == 0 || (s && t), NGPDE_ERR_INVALID_ARGUMENT, "%s: s / t is NULL", fn);
-  NGPDE_REQUIRE(n_edges == 0 || n_nodes > 0, NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: %lld edges on a graph without nodes", fn,
-                (long long)n_edges);
-  return NGPDE_OK;
-}
-
-int32_t read_flags(const int32_t *flags, int32_t *h, hipStream_t stream) {
-  NGPDE_HIP_CHECK(hipMemcpyAsync(h, flags, kFlagWords * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
-  return NGPDE_OK;
-}
-
-int32_t new_flags(Scratch &sc, int32_t **flags, hipStream_t stream) {
-  if (int32_t st = sc.get(flags, kFlagWords)) return st;
-  NGPDE_HIP_CHECK(hipMemsetAsync(*flags, 0, kFlagWords * sizeof(int32_t), stream));
-  return NGPDE_OK;
-}
-
 // the keys of the copies, sorted; with `copy_sorted`, the stable permutation too
 int32_t sorted_pair_keys(int64_t n_copies, int64_t n_edges, int64_t n, int base, int reverse, const int32_t *s, const int32_t *t,
                          unsigned long long **key_sorted, int32_t **copy_sorted, bool want_copies, int32_t *flags, Scratch &sc,
@@ -276,18 +231,10 @@ int32_t sorted_pair_keys(int64_t n_copies, int64_t n_edges, int64_t n, int base,
                      flags);
   NGPDE_LAUNCH_CHECK("pair_keys_kernel");
   const unsigned end_bit = bits_for((unsigned long long)n * (unsigned long long)n);
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  if (want_copies) {
-    NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key, *key_sorted, iota, *copy_sorted, (size_t)n_copies, 0u, end_bit, stream));
-    if ((st = sc.get((char **)&tmp, bytes))) return st;
-    NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, key, *key_sorted, iota, *copy_sorted, (size_t)n_copies, 0u, end_bit, stream));
-  } else {
-    NGPDE_HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, key, *key_sorted, (size_t)n_copies, 0u, end_bit, stream));
-    if ((st = sc.get((char **)&tmp, bytes))) return st;
-    NGPDE_HIP_CHECK(rocprim::radix_sort_keys(tmp, bytes, key, *key_sorted, (size_t)n_copies, 0u, end_bit, stream));
-  }
-  return NGPDE_OK;
+  return with_temp(sc, [&](void *tmp, size_t &bytes) {
+    return want_copies ? rocprim::radix_sort_pairs(tmp, bytes, key, *key_sorted, iota, *copy_sorted, (size_t)n_copies, 0u, end_bit, stream)
+                       : rocprim::radix_sort_keys(tmp, bytes, key, *key_sorted, (size_t)n_copies, 0u, end_bit, stream);
+  });
 }
 
 int32_t check_reduce(const char *fn, int64_t n_groups, int64_t n_rows, int32_t d, int32_t aggr) {
@@ -313,7 +260,7 @@ int32_t ngpde_coo_degree(int64_t n_nodes, int64_t n_edges, const int32_t *s, con
                          const float *w, int32_t *out_counts, float *out_sums, ngpde_stream_t stream_) {
   NGPDE_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  if (int32_t st = check_coo("ngpde_coo_degree", n_nodes, n_edges, s, t, 1)) return st;
+  if (int32_t st = check_coo("ngpde_coo_degree", n_nodes, n_edges, s, t)) return st;
   NGPDE_REQUIRE(dir == NGPDE_DIR_OUT || dir == NGPDE_DIR_IN || dir == NGPDE_DIR_BOTH, NGPDE_ERR_INVALID_ARGUMENT,
                 "ngpde_coo_degree: dir %d is none of NGPDE_DIR_OUT / IN / BOTH", dir);
   NGPDE_REQUIRE(n_nodes == 0 || ((out_counts != nullptr) != (out_sums != nullptr)), NGPDE_ERR_INVALID_ARGUMENT,
@@ -337,13 +284,13 @@ int32_t ngpde_coo_degree(int64_t n_nodes, int64_t n_edges, const int32_t *s, con
     if ((st = sc.get(&key, (size_t)n_edges)) || (st = sc.get(&key_sorted, (size_t)n_edges)) || (st = sc.get(&iota, (size_t)n_edges)) ||
         (st = sc.get(&eid, (size_t)n_edges)))
       return st;
-    size_t bytes = 0;
-    void *tmp = nullptr;
-    const unsigned end_bit = bits_for((unsigned long long)std::max<int64_t>(n_nodes, 2));
-    if (n_edges > 0) {
-      NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key, key_sorted, iota, eid, (size_t)n_edges, 0u, end_bit, stream));
-      if ((st = sc.get((char **)&tmp, bytes))) return st;
-    }
+    const unsigned end_bit = bits_for(std::max<int64_t>(n_nodes, 2));
+    auto sort = [&](void *tmp, size_t &bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, iota, eid, (size_t)n_edges, 0u, end_bit, stream);
+    };
+    size_t sort_bytes = 0;
+    void *sort_tmp = nullptr;   // one temporary for the sorts of both directions
+    if (n_edges > 0 && ((st = temp_bytes(&sort_bytes, sort)) || (st = sc.get((char **)&sort_tmp, sort_bytes)))) return st;
     int pass = 0;
     for (int which : {NGPDE_DIR_OUT, NGPDE_DIR_IN}) {
       if (dir != NGPDE_DIR_BOTH && dir != which) continue;
@@ -351,7 +298,7 @@ int32_t ngpde_coo_degree(int64_t n_nodes, int64_t n_edges, const int32_t *s, con
         hipLaunchKernelGGL(node_keys_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, n_nodes, index_base,
                            which == NGPDE_DIR_OUT ? s : t, key, iota, flags);
         NGPDE_LAUNCH_CHECK("node_keys_kernel");
-        NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, iota, eid, (size_t)n_edges, 0u, end_bit, stream));
+        NGPDE_HIP_CHECK(sort(sort_tmp, sort_bytes));
       }
       hipLaunchKernelGGL(degree_sum_kernel, dim3(blocks_for(n_nodes)), dim3(kB), 0, stream, n_nodes, n_edges, key_sorted, eid, w, pass, out_sums);
       NGPDE_LAUNCH_CHECK("degree_sum_kernel");
@@ -369,7 +316,7 @@ int32_t ngpde_coo_flags(int64_t n_nodes, int64_t n_edges, const int32_t *s, cons
                         int32_t *has_multi_edges, int32_t *is_bidirected, ngpde_stream_t stream_) {
   NGPDE_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  if (int32_t st = check_coo("ngpde_coo_flags", n_nodes, n_edges, s, t, 1)) return st;
+  if (int32_t st = check_coo("ngpde_coo_flags", n_nodes, n_edges, s, t)) return st;
   int32_t h[kFlagWords] = {0};
   if (n_edges > 0) {
     Scratch sc;
@@ -397,7 +344,7 @@ int32_t ngpde_coo_compact(int64_t n_nodes, int64_t n_edges, const int32_t *s, co
                           ngpde_stream_t stream_) {
   NGPDE_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  if (int32_t st = check_coo("ngpde_coo_compact", n_nodes, n_edges, s, t, 1)) return st;
+  if (int32_t st = check_coo("ngpde_coo_compact", n_nodes, n_edges, s, t)) return st;
   NGPDE_REQUIRE(n_out != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_coo_compact: n_out is NULL");
   *n_out = 0;
   NGPDE_REQUIRE(n_keep >= 0 && n_keep <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_coo_compact: n_keep %lld outside 0 : 2^31 - 1",
@@ -515,7 +462,7 @@ int32_t ngpde_group_reduce_backward(int64_t n_groups, int64_t n_rows, int32_t co
 int32_t ngpde_coo_add_self_loops(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, const float *w,
                                  int32_t *s_out, int32_t *t_out, float *w_out, ngpde_stream_t stream) {
   NGPDE_RANGE();
-  if (int32_t st = check_coo("ngpde_coo_add_self_loops", n_nodes, n_edges, s, t, 1)) return st;
+  if (int32_t st = check_coo("ngpde_coo_add_self_loops", n_nodes, n_edges, s, t)) return st;
   NGPDE_REQUIRE(n_edges + n_nodes <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_coo_add_self_loops: %lld edges with the loops, at most 2^31 - 1",
                 (long long)(n_edges + n_nodes));
   if (n_edges + n_nodes == 0) return NGPDE_OK;

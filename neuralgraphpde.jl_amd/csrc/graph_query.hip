@@ -29,7 +29,7 @@ namespace ngpde {
 namespace {
 
 // device flag words of one call (int32; words 0 and 1 are ONE 64-bit word, 8-byte aligned: the smallest offending id)
-enum { fOffender = 0, fBadEdge = 2, fCsr = 3, fGraph = 4, fOrder = 5, fWords = 8 };
+enum { fOffender = 0, fBadEdge = 2, fCsr = 3, fGraph = 4, fOrder = 5 };
 
 constexpr int kWave = 64;
 constexpr int kRwFixedBytes = 256;                       // the flag words of ngpde_csr_random_walk_pe, at the end of its workspace
@@ -44,20 +44,6 @@ __device__ __forceinline__ void report_offender(unsigned long long *word, int64_
 }
 inline int64_t decode_offender(unsigned long long w) { return (int64_t)((~w) ^ (1ull << 63)); }
 
-int32_t new_flags(Scratch &sc, int32_t **flags, hipStream_t stream) {
-  unsigned long long *words = nullptr;   // (allocated as 64-bit words: word 0 is one)
-  if (int32_t st = sc.get(&words, fWords / 2)) return st;
-  *flags = reinterpret_cast<int32_t *>(words);
-  NGPDE_HIP_CHECK(hipMemsetAsync(*flags, 0, fWords * sizeof(int32_t), stream));
-  return NGPDE_OK;
-}
-
-int32_t read_flags(const int32_t *flags, int32_t *h, hipStream_t stream) {
-  NGPDE_HIP_CHECK(hipMemcpyAsync(h, flags, fWords * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
-  return NGPDE_OK;
-}
-
 inline unsigned long long offender_of(const int32_t *h) {
   unsigned long long w;
   std::memcpy(&w, h + fOffender, sizeof(w));
@@ -68,18 +54,6 @@ bool capturing(hipStream_t stream) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
   return cs != hipStreamCaptureStatusNone;
-}
-
-// first position of the ascending list that is >= v
-template <class T>
-__device__ __forceinline__ int64_t lower_bound_dev(const T *__restrict__ a, int64_t m, T v) {
-  int64_t lo = 0, hi = m;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 int32_t check_sizes(const char *fn, int64_t n_nodes, int64_t n_edges) {
@@ -389,12 +363,11 @@ int32_t ngpde_coo_sort_keys(int64_t n_nodes, int64_t n_edges, const int32_t *s, 
   NGPDE_LAUNCH_CHECK("pair_keys_kernel");
   const unsigned end_bit = bits_for((unsigned long long)n_nodes * (unsigned long long)n_nodes);
   unsigned long long *sorted = reinterpret_cast<unsigned long long *>(keys_out);
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key, sorted, iota, positions_out, (size_t)n_edges, 0u, end_bit, stream));
-  if ((st = sc.get((char **)&tmp, bytes))) return st;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, key, sorted, iota, positions_out, (size_t)n_edges, 0u, end_bit, stream));
-  int32_t h[fWords];
+  auto sort = [&](void *tmp, size_t &bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, key, sorted, iota, positions_out, (size_t)n_edges, 0u, end_bit, stream);
+  };
+  if ((st = with_temp(sc, sort))) return st;
+  int32_t h[kFlagWords];
   if ((st = read_flags(flags, h, stream))) return st;   // (the temporaries are freed on return: the stream must be done with them)
   NGPDE_REQUIRE(!offender_of(h), NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: an edge references node %lld, outside the %lld nodes", fn,
                 (long long)decode_offender(offender_of(h)), (long long)n_nodes);
@@ -463,16 +436,15 @@ int32_t ngpde_coo_adjacency_count(int64_t n_nodes, int64_t n_edges, const int32_
   }
   hipLaunchKernelGGL(adjacency_count_kernel, dim3(blocks_for(n_rows + 1)), dim3(kB), 0, stream, n_rows, n_nodes, nodes, row_ptr_out, cnt, flags);
   NGPDE_LAUNCH_CHECK("adjacency_count_kernel");
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, cnt, off, 0ll, (size_t)n_rows + 1, rocprim::plus<long long>(), stream));
-  if ((st = sc.get((char **)&tmp, bytes))) return st;
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(tmp, bytes, cnt, off, 0ll, (size_t)n_rows + 1, rocprim::plus<long long>(), stream));
+  auto scan = [&](void *tmp, size_t &bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, cnt, off, 0ll, (size_t)n_rows + 1, rocprim::plus<long long>(), stream);
+  };
+  if ((st = with_temp(sc, scan))) return st;
   hipLaunchKernelGGL(narrow_offsets_kernel, dim3(blocks_for(n_rows + 1)), dim3(kB), 0, stream, n_rows + 1, off, ptr_out);
   NGPDE_LAUNCH_CHECK("narrow_offsets_kernel");
   long long total = 0;
   NGPDE_HIP_CHECK(hipMemcpyAsync(&total, off + n_rows, sizeof(total), hipMemcpyDeviceToHost, stream));
-  int32_t h[fWords];
+  int32_t h[kFlagWords];
   if ((st = read_flags(flags, h, stream))) return st;
   NGPDE_REQUIRE(!h[fBadEdge], NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: an edge references a node outside the %lld nodes", fn,
                 (long long)n_nodes);
@@ -509,7 +481,7 @@ int32_t ngpde_coo_adjacency_fill(int64_t n_nodes, int64_t n_edges, const int32_t
   hipLaunchKernelGGL(adjacency_fill_kernel, dim3(blocks_for(total)), dim3(kB), 0, stream, total, n_rows, n_nodes, n_edges, dir, nodes, s, t, row_ptr,
                      row_eid, ptr, neighbors_out, eid_out, flags);
   NGPDE_LAUNCH_CHECK("adjacency_fill_kernel");
-  int32_t h[fWords];
+  int32_t h[kFlagWords];
   if ((st = read_flags(flags, h, stream))) return st;
   NGPDE_REQUIRE(!h[fCsr], NGPDE_ERR_INVALID_ARGUMENT, "%s: ptr / row_ptr / row_eid are not what ngpde_coo_adjacency_count wrote for this list", fn);
   return NGPDE_OK;
@@ -544,7 +516,7 @@ int32_t ngpde_coo_intersect(int64_t n_nodes, int64_t n_edges, const int32_t *s, 
   if ((st = compact_flagged(n_edges, index_base, s, t, nullptr, keep, pos, s_out, t_out, kept, count, sc, stream))) return st;
   int32_t h_count = 0;
   NGPDE_HIP_CHECK(hipMemcpyAsync(&h_count, count, sizeof(h_count), hipMemcpyDeviceToHost, stream));
-  int32_t h[fWords];
+  int32_t h[kFlagWords];
   if ((st = read_flags(flags, h, stream))) return st;
   NGPDE_REQUIRE(!offender_of(h), NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: an edge references node %lld, outside the %lld nodes", fn,
                 (long long)decode_offender(offender_of(h)), (long long)n_nodes);
@@ -589,7 +561,7 @@ int32_t ngpde_csr_random_walk_pe(int64_t n, int64_t nnz, const int32_t *row_ptr,
   int32_t *flags = (int32_t *)(base + lay.flags);
   const int32_t n_blocks = (int32_t)((n + block - 1) / block);
   int32_t st;
-  if ((st = launch_zero(flags, fWords * sizeof(int32_t), stream))) return st;
+  if ((st = launch_zero(flags, kFlagWords * sizeof(int32_t), stream))) return st;
   hipLaunchKernelGGL(rw_check_kernel, dim3(blocks_for(std::max(n, nnz))), dim3(kB), 0, stream, n, nnz, row_ptr, cols, n_graphs, graph_of, flags);
   NGPDE_LAUNCH_CHECK("rw_check_kernel");
   hipLaunchKernelGGL(rw_inverse_kernel, dim3(blocks_for(n)), dim3(kB), 0, stream, n, nnz, row_ptr, vals, inv);
@@ -607,7 +579,7 @@ int32_t ngpde_csr_random_walk_pe(int64_t n, int64_t nnz, const int32_t *row_ptr,
       NGPDE_LAUNCH_CHECK("rw_ranges_kernel");
       NGPDE_HIP_CHECK(hipMemcpyAsync(range.data(), range_dev, range.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     }
-    int32_t h[fWords];
+    int32_t h[kFlagWords];
     if ((st = read_flags(flags, h, stream))) return st;
     NGPDE_REQUIRE(!h[fCsr], NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: a row pointer lies outside the %lld entries", fn, (long long)nnz);
     NGPDE_REQUIRE(!offender_of(h), NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: an entry names column %lld, outside the %lld nodes", fn,

@@ -180,7 +180,6 @@ __global__ __launch_bounds__(256) void edge_combine_bwd_target4_kernel(int n_nod
 
 // lanes per entry for a row of c4n float4: the next power of two (4 .. 64)
 inline int dpl_for(int c4n) { return c4n <= 4 ? 4 : c4n <= 8 ? 8 : c4n <= 16 ? 16 : c4n <= 32 ? 32 : 64; }
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 #define NGPDE_DPL_DISPATCH(KERNEL, c4n, grid, stream, ...)                                               \
   switch (dpl_for(c4n)) {                                                                                \
     case 4: hipLaunchKernelGGL(KERNEL<4>, grid, dim3(256), 0, stream, __VA_ARGS__); break;                \

@@ -240,7 +240,6 @@ __global__ __launch_bounds__(256) void softmax_edge_bwd_kernel(int n_nodes, int 
   }
 }
 
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline unsigned rows4(int64_t rows) { return (unsigned)((rows + 3) / 4); }
 
 // the flat (entry, column) index of the gather walks one row in int: a hub's in-degree times the width must fit

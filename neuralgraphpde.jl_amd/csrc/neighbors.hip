@@ -21,32 +21,10 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "device_scratch.h"
 
 namespace ngpde {
 namespace {
-
-constexpr int kB = 256;
-inline unsigned blocks_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kB - 1) / kB); }
-
-struct Scratch {   // frees on scope exit
-  std::vector<void *> ptrs;
-  ~Scratch() {
-    for (void *p : ptrs) (void)hipFree(p);
-  }
-  template <class T>
-  int32_t get(T **p, size_t count) {
-    *p = nullptr;
-    NGPDE_HIP_CHECK(hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
-    ptrs.push_back(*p);
-    return NGPDE_OK;
-  }
-};
-
-int bits_for(int64_t n) {
-  int b = 1;
-  while (((int64_t)1 << b) < n) ++b;
-  return b;
-}
 
 struct Grid {
   float lo[3];
@@ -455,12 +433,11 @@ int32_t sort_into_cells(int64_t n, const Grid &g, int n_graphs, const float *pts
     return st;
   hipLaunchKernelGGL(cell_key_kernel<DIM>, dim3(blocks_for(n)), dim3(kB), 0, stream, n, g, pts, gid, id_base, key, iota);
   NGPDE_LAUNCH_CHECK("cell_key_kernel");
-  size_t sb = 0;
-  const unsigned end_bit = (unsigned)bits_for(std::max<int64_t>(total, 2));
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sb, key, out.key, iota, out.idx, (size_t)n, 0u, end_bit, stream));
-  void *tmp = nullptr;
-  if ((st = sc.get((char **)&tmp, sb))) return st;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, sb, key, out.key, iota, out.idx, (size_t)n, 0u, end_bit, stream));
+  const unsigned end_bit = bits_for(std::max<int64_t>(total, 2));
+  auto sort = [&](void *tmp, size_t &bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, key, out.key, iota, out.idx, (size_t)n, 0u, end_bit, stream);
+  };
+  if ((st = with_temp(sc, sort))) return st;
   hipLaunchKernelGGL(gather_points_kernel<DIM>, dim3(blocks_for(n)), dim3(kB), 0, stream, n, pts, out.idx, out.pts);
   NGPDE_LAUNCH_CHECK("gather_points_kernel");
   hipLaunchKernelGGL(cell_start_kernel, dim3(blocks_for(total + 1)), dim3(kB), 0, stream, total, n, out.key, out.start);
@@ -497,25 +474,21 @@ int32_t radius_graph_impl(int64_t n, const float *pts, float r, const int32_t *g
   NGPDE_REQUIRE((int64_t)h_total <= capacity, NGPDE_ERR_INVALID_ARGUMENT,
                 "radius graph has %llu edges, the output arrays hold %lld", h_total, (long long)capacity);
   if (h_total == 0) return NGPDE_OK;
-  size_t tb = 0;
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, deg, rowptr, 0, (size_t)n + 1, rocprim::plus<int32_t>(), stream));
-  void *tmp = nullptr;
-  if ((st = sc.get((char **)&tmp, tb))) return st;
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(tmp, tb, deg, rowptr, 0, (size_t)n + 1, rocprim::plus<int32_t>(), stream));
+  auto scan = [&](void *tmp, size_t &bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, deg, rowptr, 0, (size_t)n + 1, rocprim::plus<int32_t>(), stream);
+  };
+  if ((st = with_temp(sc, scan))) return st;
   int32_t *nbr = nullptr;
   if ((st = sc.get(&nbr, (size_t)h_total))) return st;
   int32_t *nb_out = dir_out ? t : s, *me_out = dir_out ? s : t;
   hipLaunchKernelGGL((radius_kernel<DIM, true>), dim3(blocks_for(n)), dim3(kB), 0, stream, n, g, r2, self_loops, out_base, so.pts,
                      so.idx, so.key, so.start, (int32_t *)nullptr, (unsigned long long *)nullptr, (const int32_t *)rowptr, nbr, me_out);
   NGPDE_LAUNCH_CHECK("radius_kernel(fill)");
-  size_t sb = 0;
-  const unsigned end_bit = (unsigned)bits_for(std::max<int64_t>(n + out_base + 1, 2));
-  NGPDE_HIP_CHECK(rocprim::segmented_radix_sort_keys(nullptr, sb, nbr, nb_out, (unsigned)h_total, (unsigned)n, rowptr, rowptr + 1, 0u,
-                                                     end_bit, stream));
-  void *tmp2 = nullptr;
-  if ((st = sc.get((char **)&tmp2, sb))) return st;
-  NGPDE_HIP_CHECK(rocprim::segmented_radix_sort_keys(tmp2, sb, nbr, nb_out, (unsigned)h_total, (unsigned)n, rowptr, rowptr + 1, 0u,
-                                                     end_bit, stream));
+  const unsigned end_bit = bits_for(std::max<int64_t>(n + out_base + 1, 2));
+  auto sort = [&](void *tmp, size_t &bytes) {
+    return rocprim::segmented_radix_sort_keys(tmp, bytes, nbr, nb_out, (unsigned)h_total, (unsigned)n, rowptr, rowptr + 1, 0u, end_bit, stream);
+  };
+  if ((st = with_temp(sc, sort))) return st;
   NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
   return NGPDE_OK;
 }
@@ -569,12 +542,11 @@ int32_t spatial_order_impl(int64_t n, const float *pts, const int32_t *gid, int 
   if ((st = sc.get(&key, (size_t)n)) || (st = sc.get(&key_sorted, (size_t)n)) || (st = sc.get(&iota, (size_t)n))) return st;
   hipLaunchKernelGGL(curve_key_kernel<DIM>, dim3(blocks_for(n)), dim3(kB), 0, stream, n, qz, pts, gid, id_base, key, iota);
   NGPDE_LAUNCH_CHECK("curve_key_kernel");
-  size_t sb = 0;
-  const unsigned end_bit = 32u + (unsigned)bits_for(std::max<int64_t>(n_graphs, 2));
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sb, key, key_sorted, iota, order, (size_t)n, 0u, end_bit, stream));
-  void *tmp = nullptr;
-  if ((st = sc.get((char **)&tmp, sb))) return st;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, sb, key, key_sorted, iota, order, (size_t)n, 0u, end_bit, stream));
+  const unsigned end_bit = 32u + bits_for(std::max<int64_t>(n_graphs, 2));
+  auto sort = [&](void *tmp, size_t &bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, iota, order, (size_t)n, 0u, end_bit, stream);
+  };
+  if ((st = with_temp(sc, sort))) return st;
   NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
   return NGPDE_OK;
 }

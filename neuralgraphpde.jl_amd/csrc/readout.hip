@@ -20,6 +20,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "device_scratch.h"
 #include "device_utils.h"
 #include "row_lanes.h"
 
@@ -41,11 +42,7 @@ namespace ngpde {
 namespace {
 
 constexpr int kChunkRows = 256;   // rows per chunk: the starting value, no alternative measured yet ("Per-graph readouts")
-constexpr int kB = 256;
 constexpr unsigned kMaxGrid = 2048;   // memory-bound grid-stride launches: 256 CUs x 8 workgroups
-
-inline unsigned blocks_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kB - 1) / kB); }
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 struct View {
   const int32_t *seg_of_item, *segptr, *perm, *chunk_seg, *chunk_begin, *chunk_end, *seg_chunkptr;
@@ -109,26 +106,6 @@ __global__ void chunk_fill_kernel(int64_t n_chunks, int n_segments, const int32_
   }
 }
 
-struct Scratch {   // frees on scope exit
-  std::vector<void *> ptrs;
-  ~Scratch() {
-    for (void *p : ptrs) (void)hipFree(p);
-  }
-  template <class T>
-  int32_t get(T **p, size_t count) {
-    *p = nullptr;
-    NGPDE_HIP_CHECK(hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
-    ptrs.push_back(*p);
-    return NGPDE_OK;
-  }
-};
-
-template <class T>
-int32_t dev_alloc(T **p, size_t count) {
-  NGPDE_HIP_CHECK(hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
-  return NGPDE_OK;
-}
-
 int32_t build_plan(ngpde_readout *r, const int32_t *id, const int32_t *index, int id_base, hipStream_t stream) {
   const int64_t n = r->n_items;
   const int S = r->n_segments;
@@ -152,15 +129,13 @@ int32_t build_plan(ngpde_readout *r, const int32_t *id, const int32_t *index, in
   const int32_t *sorted_key = r->seg_of_item;
   if (!r->contiguous) {   // stable sort of the items by segment: ties keep the item order, so the plan is deterministic
     if ((st = dev_alloc(&r->perm, (size_t)n)) || (st = sc.get(&key, (size_t)n))) return st;
-    unsigned end_bit = 1;
-    while (((int64_t)1 << end_bit) < S) ++end_bit;
-    size_t sb = 0;
+    const unsigned end_bit = bits_for(S);
     const unsigned *key_in = reinterpret_cast<const unsigned *>(r->seg_of_item);   // (ids are checked: non-negative)
     unsigned *key_out = reinterpret_cast<unsigned *>(key);
-    NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sb, key_in, key_out, iota, r->perm, (size_t)n, 0u, end_bit, stream));
-    void *tmp = nullptr;
-    if ((st = sc.get((char **)&tmp, sb))) return st;
-    NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, sb, key_in, key_out, iota, r->perm, (size_t)n, 0u, end_bit, stream));
+    auto sort = [&](void *tmp, size_t &bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, key_in, key_out, iota, r->perm, (size_t)n, 0u, end_bit, stream);
+    };
+    if ((st = with_temp(sc, sort))) return st;
     sorted_key = key;
   }
   hipLaunchKernelGGL(segptr_kernel, dim3(std::min(blocks_for(n + 1), kMaxGrid)), dim3(kB), 0, stream, n, S, sorted_key, r->segptr);
@@ -168,13 +143,10 @@ int32_t build_plan(ngpde_readout *r, const int32_t *id, const int32_t *index, in
   hipLaunchKernelGGL(seg_chunk_count_kernel, dim3(std::min(blocks_for((int64_t)S + 1), kMaxGrid)), dim3(kB), 0, stream, S, r->segptr,
                      count, flags);
   NGPDE_LAUNCH_CHECK("seg_chunk_count_kernel");
-  {
-    size_t sb = 0;
-    NGPDE_HIP_CHECK(rocprim::exclusive_scan(nullptr, sb, count, r->seg_chunkptr, (int32_t)0, (size_t)S + 1, rocprim::plus<int32_t>(), stream));
-    void *tmp = nullptr;
-    if ((st = sc.get((char **)&tmp, sb))) return st;
-    NGPDE_HIP_CHECK(rocprim::exclusive_scan(tmp, sb, count, r->seg_chunkptr, (int32_t)0, (size_t)S + 1, rocprim::plus<int32_t>(), stream));
-  }
+  auto scan = [&](void *tmp, size_t &bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, count, r->seg_chunkptr, (int32_t)0, (size_t)S + 1, rocprim::plus<int32_t>(), stream);
+  };
+  if ((st = with_temp(sc, scan))) return st;
   int32_t h_chunks = 0;
   NGPDE_HIP_CHECK(hipMemcpyAsync(&h_chunks, r->seg_chunkptr + S, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   NGPDE_HIP_CHECK(hipMemcpyAsync(h_flags + 2, flags + 2, sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -197,10 +169,6 @@ int32_t build_plan(ngpde_readout *r, const int32_t *id, const int32_t *index, in
 // A term names its accumulator type A and: identity(), term(flat index of (item, column)), combine(a, b), finalize(a, rows of the
 // segment), and exchange(a, xor offset) for the butterfly.
 
-__device__ __forceinline__ float vmaxv(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ float4 vmaxv(float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
-__device__ __forceinline__ float vminv(float a, float b) { return fminf(a, b); }
-__device__ __forceinline__ float4 vminv(float4 a, float4 b) { return make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z), fminf(a.w, b.w)); }
 __device__ __forceinline__ float vfill(float, float v) { return v; }
 __device__ __forceinline__ float4 vfill(float4, float v) { return make_float4(v, v, v, v); }
 
@@ -222,7 +190,7 @@ struct ExtremumTerm {
   const T *x;
   __device__ __forceinline__ A identity() const { return vfill(T(), MAX ? -INFINITY : INFINITY); }
   __device__ __forceinline__ A term(size_t k) const { return x[k]; }
-  __device__ __forceinline__ A combine(A a, A b) const { return MAX ? vmaxv(a, b) : vminv(a, b); }
+  __device__ __forceinline__ A combine(A a, A b) const { return MAX ? vmax(a, b) : vmin(a, b); }
   __device__ __forceinline__ A exchange(A a, int o) const { return vxor(a, o); }
   __device__ __forceinline__ A finalize(A a, int) const { return a; }
 };
@@ -376,10 +344,6 @@ int32_t launch_items(const ngpde_readout *r, int w, const F &f, hipStream_t stre
   return NGPDE_OK;
 }
 
-__device__ __forceinline__ float vsel_eq(float a, float b, float v) { return a == b ? v : 0.f; }
-__device__ __forceinline__ float4 vsel_eq(float4 a, float4 b, float4 v) {
-  return make_float4(a.x == b.x ? v.x : 0.f, a.y == b.y ? v.y : 0.f, a.z == b.z ? v.z : 0.f, a.w == b.w ? v.w : 0.f);
-}
 __device__ __forceinline__ float soft_y(float x, float m, float s) { return fast_exp(x - m) / s; }
 __device__ __forceinline__ float4 soft_y(float4 x, float4 m, float4 s) {
   return make_float4(soft_y(x.x, m.x, s.x), soft_y(x.y, m.y, s.y), soft_y(x.z, m.z, s.z), soft_y(x.w, m.w, s.w));

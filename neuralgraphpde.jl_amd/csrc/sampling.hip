@@ -29,36 +29,13 @@ namespace ngpde {
 
 namespace {
 
-constexpr int kB = 256;
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = kB / kWave;                                // a wave per short row
 constexpr int kWaveRowMax = NGPDE_SAMPLE_LDS_ROW_MAX / kRowsPerBlock;    // 512: the four waves' rows share the block row's LDS
 static_assert(NGPDE_SAMPLE_LDS_ROW_MAX % kB == 0 && NGPDE_SAMPLE_LDS_ROW_MAX * 8 <= 64 * 1024, "the staged keys of a row must fit LDS");
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kB - 1) / kB); }
-
-struct Scratch {   // device temporaries of one call; freed on scope exit
-  std::vector<void *> ptrs;
-  ~Scratch() {
-    for (void *p : ptrs) (void)hipFree(p);
-  }
-  template <class T>
-  int32_t get(T **p, size_t count) {
-    *p = nullptr;
-    NGPDE_HIP_CHECK(hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T)));
-    ptrs.push_back(*p);
-    return NGPDE_OK;
-  }
-};
-
-unsigned bits_for(unsigned long long n) {   // bits that hold every value below n
-  unsigned b = 1;
-  while (b < 64 && (1ull << b) < n) ++b;
-  return b;
-}
-
 // device flag words of one call
-enum { kBadEdge = 0, kBadNode = 1, kBadCount = 2, kCount = 4, kFlagWords = 8 };
+enum { kBadEdge = 0, kBadNode = 1, kBadCount = 2, kCount = 4 };
 
 // ---- the generator (philox.h) -----------------------------------------------------------------------------------------------
 __global__ void random_keys_kernel(unsigned long long seed, uint32_t stream, uint32_t c1, unsigned long long first, int64_t n,
@@ -283,45 +260,12 @@ __global__ void split_compact_kernel(int64_t m, const int32_t *__restrict__ firs
 }
 
 // ---- host helpers -------------------------------------------------------------------------------------------------------------
-int32_t check_coo(const char *fn, int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t) {
-  NGPDE_REQUIRE(n_nodes >= 0 && n_edges >= 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: negative size (n_nodes %lld, n_edges %lld)", fn,
-                (long long)n_nodes, (long long)n_edges);
-  NGPDE_REQUIRE(n_nodes <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "%s: %lld nodes, at most 2^31 - 1", fn, (long long)n_nodes);
-  NGPDE_REQUIRE(n_edges <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "%s: %lld edges, at most 2^31 - 1", fn, (long long)n_edges);
-  NGPDE_REQUIRE(n_edges == 0 || (s && t), NGPDE_ERR_INVALID_ARGUMENT, "%s: s / t is NULL", fn);
-  NGPDE_REQUIRE(n_edges == 0 || n_nodes > 0, NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: %lld edges on a graph without nodes", fn,
-                (long long)n_edges);
-  return NGPDE_OK;
-}
-
-int32_t read_flags(const int32_t *flags, int32_t *h, hipStream_t stream) {
-  NGPDE_HIP_CHECK(hipMemcpyAsync(h, flags, kFlagWords * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
-  return NGPDE_OK;
-}
-
-int32_t new_flags(Scratch &sc, int32_t **flags, hipStream_t stream) {
-  if (int32_t st = sc.get(flags, kFlagWords)) return st;
-  NGPDE_HIP_CHECK(hipMemsetAsync(*flags, 0, kFlagWords * sizeof(int32_t), stream));
-  return NGPDE_OK;
-}
-
 int32_t exclusive_scan_i32(const int32_t *in, int32_t *out, size_t count, Scratch &sc, hipStream_t stream) {
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, count, rocprim::plus<int32_t>(), stream));
-  if (int32_t st = sc.get((char **)&tmp, bytes)) return st;
-  NGPDE_HIP_CHECK(rocprim::exclusive_scan(tmp, bytes, in, out, 0, count, rocprim::plus<int32_t>(), stream));
-  return NGPDE_OK;
+  return with_temp(sc, [&](void *tmp, size_t &bytes) { return rocprim::exclusive_scan(tmp, bytes, in, out, 0, count, rocprim::plus<int32_t>(), stream); });
 }
 
 int32_t inclusive_scan_i32(const int32_t *in, int32_t *out, size_t count, Scratch &sc, hipStream_t stream) {
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  NGPDE_HIP_CHECK(rocprim::inclusive_scan(nullptr, bytes, in, out, count, rocprim::plus<int32_t>(), stream));
-  if (int32_t st = sc.get((char **)&tmp, bytes)) return st;
-  NGPDE_HIP_CHECK(rocprim::inclusive_scan(tmp, bytes, in, out, count, rocprim::plus<int32_t>(), stream));
-  return NGPDE_OK;
+  return with_temp(sc, [&](void *tmp, size_t &bytes) { return rocprim::inclusive_scan(tmp, bytes, in, out, count, rocprim::plus<int32_t>(), stream); });
 }
 
 }  // namespace
@@ -402,13 +346,11 @@ int32_t ngpde_coo_sample_neighbors(int64_t n_nodes, int64_t n_edges, const int32
         hipLaunchKernelGGL(long_keys_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, (unsigned long long)seed, rows.row_of, rows.eid,
                            seg_begin, seg_end, key);
         NGPDE_LAUNCH_CHECK("long_keys_kernel");
-        size_t bytes = 0;
-        void *tmp = nullptr;
-        NGPDE_HIP_CHECK(rocprim::segmented_radix_sort_pairs(nullptr, bytes, key, key_sorted, rows.eid, eid_sorted, (unsigned)n_edges,
-                                                            (unsigned)n_nodes, seg_begin, seg_end, 0u, 64u, stream));
-        if ((st = sc.get((char **)&tmp, bytes))) return st;
-        NGPDE_HIP_CHECK(rocprim::segmented_radix_sort_pairs(tmp, bytes, key, key_sorted, rows.eid, eid_sorted, (unsigned)n_edges,
-                                                            (unsigned)n_nodes, seg_begin, seg_end, 0u, 64u, stream));
+        auto sort = [&](void *tmp, size_t &bytes) {
+          return rocprim::segmented_radix_sort_pairs(tmp, bytes, key, key_sorted, rows.eid, eid_sorted, (unsigned)n_edges, (unsigned)n_nodes,
+                                                     seg_begin, seg_end, 0u, 64u, stream);
+        };
+        if ((st = with_temp(sc, sort))) return st;
         hipLaunchKernelGGL(long_take_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, k, rows.row_of, eid_sorted, seg_begin, seg_end,
                            keep);
         NGPDE_LAUNCH_CHECK("long_take_kernel");
@@ -464,11 +406,8 @@ int32_t ngpde_coo_rand_split(int64_t n_nodes, int64_t n_edges, const int32_t *s,
   hipLaunchKernelGGL(split_keys_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, n_nodes, index_base, by_pair,
                      (unsigned long long)seed, s, t, key, iota, upper, flags);
   NGPDE_LAUNCH_CHECK("split_keys_kernel");
-  size_t bytes = 0;
-  void *tmp = nullptr;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key, key_sorted, iota, eid_sorted, m, 0u, 64u, stream));
-  if ((st = sc.get((char **)&tmp, bytes))) return st;
-  NGPDE_HIP_CHECK(rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, iota, eid_sorted, m, 0u, 64u, stream));
+  auto sort = [&](void *tmp, size_t &bytes) { return rocprim::radix_sort_pairs(tmp, bytes, key, key_sorted, iota, eid_sorted, m, 0u, 64u, stream); };
+  if ((st = with_temp(sc, sort))) return st;
   if (!by_pair) {
     hipLaunchKernelGGL(side_by_rank_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, n_first, eid_sorted, side_out);
     NGPDE_LAUNCH_CHECK("side_by_rank_kernel");
