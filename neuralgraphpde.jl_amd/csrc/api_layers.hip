@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "switches.h"
 
 using namespace ngpde;
 
@@ -24,11 +25,6 @@ namespace {
 
 constexpr int kMaxL = NGPDE_MLP_MAX_LAYERS;
 constexpr int kMaxBlocks = 4;   // input blocks of one Dense (ngpde_dense_forward)
-
-bool env_is(const char *name, char v) {
-  const char *e = std::getenv(name);
-  return e && e[0] == v;
-}
 
 // Bump allocator over the workspace in units of floats, 256-byte granules; with base == nullptr it only measures.
 struct Arena {
@@ -238,9 +234,9 @@ int32_t make_plan(const ngpde_graph *g, const ngpde_edge_layer_t &L, bool traini
   // layers, tiles within the LDS halo; max / min only without gradients), the primitives otherwise
   // (max / min / *: with gradients only where the one-launch pullback takes it -- the primitives' pullbacks of those need the per-edge
   // messages, which the fused forward does not keep)
-  const bool bwd_ok = !env_is("NGPDE_NO_FUSED_EDGE_BWD", '1') &&
+  const bool bwd_ok = !switch_on(Switch::NoFusedEdgeBwd) &&
                       ngpde_edge_mlp_backward_supported(g, p.h1, p.n_tail, p.n_tail ? p.tail_dout : nullptr, p.aggr) == 1;
-  p.fused_msg = !env_is("NGPDE_NO_FUSED_EDGE", '1') && p.E > 0 && p.n_tail <= 3 &&
+  p.fused_msg = !switch_on(Switch::NoFusedEdge) && p.E > 0 && p.n_tail <= 3 &&
                 (p.aggr == NGPDE_AGGR_SUM || p.aggr == NGPDE_AGGR_MEAN || !training || bwd_ok) &&
                 ngpde_edge_mlp_supported(g, p.h1, p.n_tail, p.n_tail ? p.tail_dout : nullptr) == 1;
   if (p.fused_msg && training) {
@@ -248,7 +244,9 @@ int32_t make_plan(const ngpde_graph *g, const ngpde_edge_layer_t &L, bool traini
     if (p.fused_bwd && p.n_tail >= 2) {
       // three / four-layer message MLPs: the one-launch pullback pays from ~32 k nodes up (one 4-wave workgroup per CU walks a long
       // chain per tile); NGPDE_DEEP_EDGE_BWD=1 / 0 forces it on / off
-      p.fused_bwd = env_is("NGPDE_DEEP_EDGE_BWD", '1') || (!env_is("NGPDE_DEEP_EDGE_BWD", '0') && p.N >= 32768);
+      const char *deep = switch_text(Switch::DeepEdgeBwd);
+      const char d0 = deep ? deep[0] : '\0';
+      p.fused_bwd = d0 == '1' || (d0 != '0' && p.N >= 32768);
     }
   }
 
@@ -408,10 +406,10 @@ int32_t make_gno_plan(const ngpde_graph *g, const ngpde_gno_layer_t &L, bool tra
   if (p.de) p.rows.block(o++, p.de, {{2 * p.ds, 1.f}});
   p.rows.n_out = o;
   p.kdim = phi.dims[p.L - 1];
-  p.reassoc = p.L >= 2 && phi.act[p.L - 1] == NGPDE_ACT_IDENTITY && !env_is("NGPDE_GNO_MATERIALIZE", '1') &&
+  p.reassoc = p.L >= 2 && phi.act[p.L - 1] == NGPDE_ACT_IDENTITY && !switch_on(Switch::GnoMaterialize) &&
               ngpde_gno_apply_supported(p.cout, p.kdim) == 1;
   p.has_b2 = p.reassoc && phi.bias[p.L - 1] != nullptr;
-  p.fused_msg = p.reassoc && p.L == 2 && p.E > 0 && !env_is("NGPDE_NO_GNO_MFMA", '1') && (p.act1 == NGPDE_ACT_IDENTITY || p.act1 == NGPDE_ACT_RELU) &&
+  p.fused_msg = p.reassoc && p.L == 2 && p.E > 0 && !switch_on(Switch::NoGnoMfma) && (p.act1 == NGPDE_ACT_IDENTITY || p.act1 == NGPDE_ACT_RELU) &&
                 ngpde_gno_message_supported(p.cout, p.kdim) == 1;
   p.fused_agg = p.fused_msg && (p.aggr == NGPDE_AGGR_SUM || p.aggr == NGPDE_AGGR_MEAN);
   // the edge index contracted first, per target: the forward needs neither T nor the [E][out] message (the pullback keeps the

@@ -262,8 +262,6 @@ struct NodePersistBwd {
   bool no_latch = false;       // the caller latches the fault word in its next kernel (node.hip: the slab reduction)
 };
 const unsigned *node_persistent_abort_word(const NodePersist *ps);   // the abort word of the plan's persistent launches
-bool node_persistent_interleave_env();
-bool node_persistent_disabled_env();
 bool node_persistent_supported(const ngpde_graph *g, int d, int act, bool with_bwd);
 int node_persistent_mode(const ngpde_graph *g, int d, int act, bool with_bwd);   // 0 none, 1 one tile per workgroup, 2 tile pairs, 3 tile rounds
 // graphs the modes above refuse because a tile does not fit the handle's halo lists (hubs): can the hub geometry be tried?  (Whether

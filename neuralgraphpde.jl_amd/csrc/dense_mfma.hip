@@ -10,6 +10,7 @@
 #include "common.h"
 #include "device_utils.h"
 #include "stamps.h"
+#include "switches.h"
 
 namespace ngpde {
 
@@ -1256,8 +1257,7 @@ __global__ __launch_bounds__(256) void dense_weight_reduce_kernel(int nchunk, in
 
 // 128-row tiles once they alone give every CU two workgroups
 static bool use_wide_tiles(int64_t n, int cols) {
-  static const bool off = getenv("NGPDE_DENSE_NARROW") != nullptr;
-  return !off && ((n + BM2 - 1) / BM2) * ((cols + BN - 1) / BN) >= 512;
+  return !switch_on(Switch::DenseNarrow) && ((n + BM2 - 1) / BM2) * ((cols + BN - 1) / BN) >= 512;
 }
 
 int32_t launch_dense_seg_fwd(int64_t n, const SegTable &segs, int din, int dout, int act, const float *wt,
@@ -1266,9 +1266,8 @@ int32_t launch_dense_seg_fwd(int64_t n, const SegTable &segs, int din, int dout,
   if (const int sgrid = dense_small_fwd_grid(n, din, dout))   // 17 .. 64 inputs, at most 64 outputs, latency-bound row counts: one contraction pass
     return launch_dense_small_fwd(n, segs, din, dout, act, wt, bias, y, save_z, sgrid, stream);
   {   // wide outputs from one 16-byte-loadable block: 128 x 128 tiles
-    static const bool no_gemm = getenv("NGPDE_DENSE_NO_GEMM128") != nullptr;
     const int64_t tiles = ((n + BG - 1) / BG) * ((dout + BG - 1) / BG);
-    if (!no_gemm && segs.n == 1 && segs.vec[0] && segs.row_div[0] == 1 && din % BKG == 0 && dout % 4 == 0 && dout >= BG && tiles >= 512 &&
+    if (!switch_on(Switch::DenseNoGemm128) && segs.n == 1 && segs.vec[0] && segs.row_div[0] == 1 && din % BKG == 0 && dout % 4 == 0 && dout >= BG && tiles >= 512 &&
         ((reinterpret_cast<uintptr_t>(wt) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(save_z)) & 15) == 0) {
       hipLaunchKernelGGL(dense_gemm128_fwd_kernel, dim3((unsigned)((n + BG - 1) / BG), (dout + BG - 1) / BG), dim3(256), 0, stream, n,
                          segs.ptr[0], din, dout, act, wt, bias, y, save_z);
@@ -1282,8 +1281,7 @@ int32_t launch_dense_seg_fwd(int64_t n, const SegTable &segs, int din, int dout,
     for (int i = segs.n - 1; i >= 1 && din - segs.offset[i] <= 8; --i)
       if (segs.offset[i] % BK2 == 0) din_main = segs.offset[i];
     // a 64-deep contraction over 16-byte-loadable blocks: the streaming form (whole input tile by LDS-DMA in one burst)
-    static const bool no_stream = getenv("NGPDE_DENSE_NO_STREAM") != nullptr;
-    bool stream_ok = !no_stream && din_main == 64 && dout <= 64;
+    bool stream_ok = !switch_on(Switch::DenseNoStream) && din_main == 64 && dout <= 64;
     for (int i = 0; i < segs.n && segs.offset[i] < din_main; ++i) stream_ok = stream_ok && segs.vec[i] && segs.offset[i + 1] <= din_main;
     if (stream_ok) {
       static int cus = 0, per_cu = 0;
@@ -1433,8 +1431,7 @@ int32_t launch_dense_bwd_input_splitk(int64_t n, float *dx, int din, int dout, c
   const int oper = ((dout + ns - 1) / ns + BK2 - 1) / BK2 * BK2;
   const int nz = (dout + oper - 1) / oper;
   {   // 128 x 128 tiles (GNOConv's T = W2 (x) h: 4096 x 128 <= 8192)
-    static const bool no_gemm = getenv("NGPDE_DENSE_NO_GEMM128") != nullptr;
-    if (!no_gemm && nz > 1 && din >= BG && din % 4 == 0 && dout % BKG == 0 && oper % BKG == 0 && n < (1 << 30) &&
+    if (!switch_on(Switch::DenseNoGemm128) && nz > 1 && din >= BG && din % 4 == 0 && dout % BKG == 0 && oper % BKG == 0 && n < (1 << 30) &&
         ((reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(wt) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(part)) & 15) == 0) {
       hipLaunchKernelGGL((dense_gemm128_split_kernel<false, true>), dim3((unsigned)((n + BG - 1) / BG), (din + BG - 1) / BG, nz), dim3(256), 0,
                          stream, (int)n, din, dout, oper, dz, dout, wt, dout, dx, part, (size_t)n * din, din);
@@ -1483,8 +1480,7 @@ int32_t launch_dense_seg_bwd_weight(int64_t n, const SegTable &segs, int din, in
   const int nchunk = dense_weight_chunks(n, din, dout);
   const int64_t rpc = std::max<int64_t>(BK, (((n + nchunk - 1) / nchunk) + BK - 1) / BK * BK);
   {   // 128 x 128 tiles for a wide layer without bias gradient (GNOConv's T): slabs in the layout dense_weight_reduce_kernel sums
-    static const bool no_gemm = getenv("NGPDE_DENSE_NO_GEMM128") != nullptr;
-    if (!no_gemm && db == nullptr && nchunk > 1 && segs.n == 1 && segs.vec[0] && segs.row_div[0] == 1 && din >= BG && din % 4 == 0 &&
+    if (!switch_on(Switch::DenseNoGemm128) && db == nullptr && nchunk > 1 && segs.n == 1 && segs.vec[0] && segs.row_div[0] == 1 && din >= BG && din % 4 == 0 &&
         dout >= BG && dout % 4 == 0 && n % BKG == 0 && n < (1 << 30) &&
         ((reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(partial)) & 15) == 0) {
       const size_t slab = (size_t)(din + 1) * dout;
@@ -1520,8 +1516,7 @@ static int stream_main_blocks(const SegTable &t, int din) {
   return (nm >= 1 && din - 64 * nm <= kNarrow) ? nm : 0;
 }
 static bool stream2_enabled(int64_t n) {
-  const char *e = getenv("NGPDE_DENSE_NO_STREAM2");   // read per call: the tests switch it at run time
-  return !(e && e[0] == '1') && (n + BM2 - 1) / BM2 >= 512;
+  return !switch_on(Switch::DenseNoStream2) && (n + BM2 - 1) / BM2 >= 512;
 }
 
 bool dense_pair_fwd_applicable(int64_t n, const SegTable &ta, int dina, int douta, const SegTable &tb, int dinb, int doutb) {

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "device_utils.h"
 #include "stamps.h"
+#include "switches.h"
 
 namespace ngpde {
 
@@ -359,8 +360,7 @@ __global__ __launch_bounds__(kT) void dense_small_fwd_kernel(const SmallFwdK p) 
 
 // the forward of the same shapes in one contraction pass (0: not this form's shape)
 int dense_small_fwd_grid(int64_t n, int din, int dout) {
-  static const bool off = std::getenv("NGPDE_DENSE_NO_SMALL_FWD") != nullptr;
-  if (off || din < 17 || din > kW || dout < 1 || dout > kW || n < 1 || n > 65536) return 0;   // (din <= 16 is ONE step of the general kernel)
+  if (switch_on(Switch::DenseNoSmallFwd) || din < 17 || din > kW || dout < 1 || dout > kW || n < 1 || n > 65536) return 0;   // (din <= 16 is ONE step of the general kernel)
   return (int)std::min<int64_t>((n + kR - 1) / kR, 1024);
 }
 
@@ -378,8 +378,7 @@ int32_t launch_dense_small_fwd(int64_t n, const SegTable &t, int din, int dout, 
 // launches are latency-bound (beyond that its 16-byte / LDS-DMA loads win), and enough rows for the slabs to fit the [n][dout] dz
 // area of the composed path's workspace (which this form does not use otherwise)
 int dense_small_bwd_grid(int64_t n, int din, int dout) {
-  static const bool off = std::getenv("NGPDE_DENSE_NO_SMALL_BWD") != nullptr;
-  if (off || din < 1 || din > kW || dout < 1 || dout > kW || n < 1 || n > 65536) return 0;
+  if (switch_on(Switch::DenseNoSmallBwd) || din < 1 || din > kW || dout < 1 || dout > kW || n < 1 || n > 65536) return 0;
   const int64_t n_tiles = (n + kR - 1) / kR;
   const int64_t grid = std::min<int64_t>(std::min<int64_t>(n_tiles, 1024), n / (din + 1));
   return grid >= 1 ? (int)grid : 0;

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "device_utils.h"
 #include "stamps.h"
+#include "switches.h"
 
 namespace ngpde {
 
@@ -574,18 +575,13 @@ __global__ __launch_bounds__(kBT, 2) void dense_pair64_bwd_kernel(const DensePai
   }
 }
 
-bool env_on(const char *name) {
-  const char *e = std::getenv(name);
-  return e && e[0] == '1';
-}
-
 }  // namespace
 
 // Applies when: 64 outputs, one or two blocks of exactly 64 features (row_div 1, 16-byte aligned), every other feature
 // narrow (<= 4 in total) and without a gradient request, enough rows for a resident wave of tiles, and the slabs fit the dz
-// area of the caller's workspace.  NGPDE_DENSE_NO_STREAM_BWD=1 keeps the composed path (read per call).
+// area of the caller's workspace.  NGPDE_DENSE_NO_STREAM_BWD=1 keeps the composed path.
 int dense_stream_bwd_grid(int64_t n, const SegTable &t, int din, int dout, float *const *dseg) {
-  if (env_on("NGPDE_DENSE_NO_STREAM_BWD") || dout != kD || n < 32768 || n > (1 << 24)) return 0;   // (32-bit byte offsets)
+  if (switch_on(Switch::DenseNoStreamBwd) || dout != kD || n < 32768 || n > (1 << 24)) return 0;   // (32-bit byte offsets)
   int n_main = 0, n_narrow = 0;
   for (int b = 0; b < t.n; ++b) {
     const bool grad = dseg && dseg[b] && t.row_div[b] == 1;
@@ -644,7 +640,7 @@ static bool pair_side_ok(const SegTable &t, int din) {
   return din - kD <= kMaxNarrow;
 }
 int dense_pair_bwd_grid(int64_t n, const SegTable &ta, int dina, const SegTable &tb, int dinb) {
-  if (env_on("NGPDE_DENSE_NO_STREAM_BWD") || n < 32768 || n > (1 << 24)) return 0;
+  if (switch_on(Switch::DenseNoStreamBwd) || n < 32768 || n > (1 << 24)) return 0;
   if (!pair_side_ok(ta, dina) || !pair_side_ok(tb, dinb) || ta.ptr[0] != tb.ptr[0]) return 0;
   return std::min((int)((n + kTR - 1) / kTR), 256 * 2);
 }

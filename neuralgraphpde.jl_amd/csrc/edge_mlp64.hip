@@ -20,6 +20,7 @@
 #include "device_utils.h"
 #include "edge_mlp_tile.h"
 #include "stamps.h"
+#include "switches.h"
 
 namespace ngpde {
 
@@ -604,18 +605,12 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_bwd_kernel(const EdgeMlp64B
   }
 }
 
-bool env_off(const char *name) {
-  const char *e = std::getenv(name);
-  return e && e[0] == '1';
-}
-
 }  // namespace
 
 // The specialised launch applies to: P and Q present, no per-edge term, h1 = 64, one further Dense 64 => 64, nothing saved per
-// edge, + / mean, and an activation pair that is instantiated below.  NGPDE_NO_EDGE64=1 keeps the general kernel (read per call:
-// the tests switch it at run time).
+// edge, + / mean, and an activation pair that is instantiated below.  NGPDE_NO_EDGE64=1 keeps the general kernel.
 bool edge_mlp64_fwd_applicable(const ngpde_graph *g, const EdgeMlpArgs &a) {
-  if (env_off("NGPDE_NO_EDGE64")) return false;
+  if (switch_on(Switch::NoEdge64)) return false;
   if (!a.P || !a.Q || a.Eterm || a.h1 != kW || a.n_tail != 1 || a.din[0] != kW || a.dout[0] != kW) return false;
   for (int l = 0; l < 4; ++l)
     if (a.save_z[l]) return false;
@@ -659,7 +654,7 @@ __global__ __launch_bounds__(256) void edge64_dq_combine_kernel(int n_listed, co
 // ---- pullback launch.  Same conditions as the forward specialisation (the activation pairs instantiated below); workspace =
 // one [65][64] slab per workgroup of the larger grid (two workgroups per CU).
 bool edge_mlp64_bwd_applicable(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
-  if (env_off("NGPDE_NO_EDGE64")) return false;
+  if (switch_on(Switch::NoEdge64)) return false;
   if (!a.P || !a.Q || a.Eterm || a.h1 != kW || a.n_tail != 1 || a.dw != kW) return false;
   if (a.aggr != NGPDE_AGGR_SUM && a.aggr != NGPDE_AGGR_MEAN) return false;
   const bool a1 = a.act1 == NGPDE_ACT_SWISH || a.act1 == NGPDE_ACT_RELU || a.act1 == NGPDE_ACT_TANH;
@@ -669,7 +664,7 @@ bool edge_mlp64_bwd_applicable(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
 static size_t edge64_slab_bytes(const ngpde_graph *g) { return slab_bytes(edge_persistent_grid(g, 64), kW, kW); }
 // the by-source sum inside the launch (no [E][64] array): no per-edge term, every halo within kDqStride rows
 bool edge_mlp64_bwd_dq_in_launch(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
-  if (env_off("NGPDE_EDGE64_NO_DQ")) return false;
+  if (switch_on(Switch::Edge64NoDq)) return false;
   return a.Eterm == nullptr && a.dQ != nullptr && g->by_t.halo_ok && g->by_t.max_halo <= kDqStride;
 }
 size_t edge_mlp64_bwd_workspace(const ngpde_graph *g) {

@@ -27,6 +27,7 @@
 #include "persistent_mem.h"
 #include "persistent_sync.h"
 #include "stamps.h"
+#include "switches.h"
 
 namespace ngpde {
 
@@ -1292,11 +1293,6 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
                         dbacc, uacc);
 }
 
-inline bool no_fused_gat_layer_env() {   // read on every call: tests flip it inside one process
-  const char *e = std::getenv("NGPDE_NO_FUSED_GAT_LAYER");
-  return e && e[0] == '1';
-}
-
 inline int src_wgs(const ngpde_graph *g) { return (fused_num_blocks(g->n_nodes) + kSrcTiles - 1) / kSrcTiles; }
 
 struct GatWs {   // carving of the caller's pullback workspace (256-byte aligned pieces)
@@ -1320,7 +1316,7 @@ inline GatWs gat_ws(const ngpde_graph *g, int heads) {
 
 bool gat_layer_fused_supported(const ngpde_graph *g, int din, int heads, int c) {
   return g && g->has_norm && g->n_edges > 0 && g->by_t.halo_ok && g->by_s.halo_ok && din == GD && heads * c == GD &&
-         (heads == 1 || heads == 2 || heads == 4) && (uint64_t)g->n_nodes * GD * 4 < (1ull << 32) && !no_fused_gat_layer_env();
+         (heads == 1 || heads == 2 || heads == 4) && (uint64_t)g->n_nodes * GD * 4 < (1ull << 32) && !switch_on(Switch::NoFusedGatLayer);
 }
 
 size_t gat_layer_workspace_bytes(const ngpde_graph *g, int heads) { return g ? gat_ws(g, heads).total : 0; }
@@ -1418,7 +1414,7 @@ inline GatSync gat_sync(const NodePersist &ps) {
 size_t gat_node_dscore_elems(const ngpde_graph *g) { return (size_t)g->n_sched * kSlotWidth * 4; }
 
 bool gat_node_persistent_supported(const ngpde_graph *g, int heads, int c) {
-  if (node_persistent_disabled_env() || !gat_layer_fused_supported(g, GD, heads, c)) return false;
+  if (switch_on(Switch::NoPersistent) || !gat_layer_fused_supported(g, GD, heads, c)) return false;
   int dev = 0, cus = 0, occ = 1 << 30;
   if (hipGetDevice(&dev) != hipSuccess) return false;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;

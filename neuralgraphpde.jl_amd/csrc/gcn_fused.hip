@@ -23,6 +23,7 @@
 #include "device_utils.h"
 #include "gcn_tile.h"
 #include "stamps.h"
+#include "switches.h"
 
 namespace ngpde {
 
@@ -845,12 +846,6 @@ CombDev to_dev(const Comb &c) {
   return d;
 }
 
-// NGPDE_NO_HALO=1 forces the per-row global gather (A/B measurements and tests of the fallback path)
-inline bool no_halo_env() {
-  static const bool v = [] { const char *e = std::getenv("NGPDE_NO_HALO"); return e && e[0] == '1'; }();
-  return v;
-}
-
 // paired workgroups for the backward kernels (D <= 64: two 60 KB regions fit the CU's LDS)
 inline bool fused_bwd_pairs(int d) { return d <= 64; }
 
@@ -863,7 +858,7 @@ inline int act_template(int act) { return (act == NGPDE_ACT_RELU || act == NGPDE
 // and c finite and positive (self loops: degree >= 1)
 bool fused_prescaled_supported(const ngpde_graph *g, int d) {
   return g && g->has_norm && g->self_loops && d <= 128 && fused_supported(d, d) && g->by_t.halo_ok && g->by_s.halo_ok &&
-         !no_halo_env();
+         !switch_on(Switch::NoHalo);
 }
 bool fused_supported(int din, int dout) { return din == dout && (din == 16 || din == 32 || din == 64 || din == 128); }
 int fused_tile_rows() { return kTM; }
@@ -888,7 +883,7 @@ int32_t launch_fused_fwd(const FusedFwdArgs &a, hipStream_t stream) {
   FwdK k;
   k.x = a.x; k.sched = g->by_t.sched; k.ent = g->by_t.ent; k.ell = g->by_t.ell;
   k.halo = g->by_t.halo; k.tile_info = g->by_t.tile_info; k.slots = g->by_t.slots; k.slot_w = g->by_t.slot_w;
-  if (a.of && a.of->slots && g->by_t.halo_ok && !no_halo_env()) {   // a solver plan's own-first tables (LDS-staged aggregation only:
+  if (a.of && a.of->slots && g->by_t.halo_ok && !switch_on(Switch::NoHalo)) {   // a solver plan's own-first tables (LDS-staged aggregation only:
     k.slots = a.of->slots; k.sched = a.of->sched;                   // the same rows in another order, padded lengths in the schedule)
     if (k.slot_w) k.slot_w = a.of->slot_w;
   }
@@ -897,7 +892,7 @@ int32_t launch_fused_fwd(const FusedFwdArgs &a, hipStream_t stream) {
   k.has_comb = a.has_comb ? 1 : 0; k.comb = to_dev(a.comb); k.comb_out = a.comb_out;
   k.save_mask = a.save_mask;
   NGPDE_STAMP_SET(k, kStampGcn, (int64_t)k.n_tiles * 16);
-  const bool use_halo = g->by_t.halo_ok && !no_halo_env();
+  const bool use_halo = g->by_t.halo_ok && !switch_on(Switch::NoHalo);
   NGPDE_REQUIRE(!a.pre || fused_prescaled_supported(g, a.d), NGPDE_ERR_UNSUPPORTED,
                 "the pre-scaled form needs self loops and tiles that fit the LDS halo in both directions");
   const dim3 grid(k.n_tiles), block(kThreads);
@@ -949,7 +944,7 @@ int32_t launch_fused_bwd(const FusedBwdArgs &a, hipStream_t stream) {
   k.tape_late = a.has_comb ? 0 : 1;
   k.g_out = a.g_out; k.slab_dw = a.slab_dw; k.slab_db = a.slab_db;
   NGPDE_STAMP_SET(k, kStampGcn, (int64_t)k.n_tiles * 16);
-  const bool use_halo = g->by_s.halo_ok && !no_halo_env();
+  const bool use_halo = g->by_s.halo_ok && !switch_on(Switch::NoHalo);
   NGPDE_REQUIRE(!a.pre || fused_prescaled_supported(g, a.d), NGPDE_ERR_UNSUPPORTED,
                 "the pre-scaled form needs self loops and tiles that fit the LDS halo in both directions");
   const bool pair = fused_bwd_pairs(a.d);   // (D <= 64: the launches below instantiate the paired kernel only)

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "device_utils.h"
 #include "persistent_mem.h"
+#include "switches.h"
 
 namespace ngpde {
 
@@ -232,11 +233,6 @@ __global__ void gno_gform_finish_kernel(int64_t count4, int cout4, int act, int 
   }
 }
 
-inline bool no_gform_env() {
-  const char *e = std::getenv("NGPDE_NO_GNO_GFORM");
-  return e && e[0] == '1';
-}
-
 }  // namespace
 
 }  // namespace ngpde
@@ -246,7 +242,7 @@ using namespace ngpde;
 extern "C" {
 
 int32_t ngpde_gno_gform_supported(int32_t in_chs, int32_t kdim) {
-  return (!no_gform_env() && kdim == kGK && (in_chs == 32 || in_chs == 64 || in_chs == 128)) ? 1 : 0;
+  return (!switch_on(Switch::NoGnoGform) && kdim == kGK && (in_chs == 32 || in_chs == 64 || in_chs == 128)) ? 1 : 0;
 }
 
 int32_t ngpde_gno_gform_preferred(int64_t n_nodes, int64_t n_edges, int32_t in_chs, int32_t kdim, int32_t cout, int32_t training) {
@@ -287,8 +283,8 @@ int32_t ngpde_gno_gform_aggregate(const ngpde_graph_t *g, int32_t in_chs, int32_
   a.P = p_target; a.Q = q_source; a.Et = e_term; a.h = h; a.G = gout; a.hsum = hsum; a.z_out = z_out; a.act1 = act1; a.mean = mean ? 1 : 0;
   const dim3 grid((unsigned)g->n_nodes), block(256);
   hipStream_t s = (hipStream_t)stream;
-  // edges per chunk (A/B runs): NGPDE_GNO_GFORM_CHUNK=16; unset or any other value means 32.  Read per call, as the other switches.
-  const char *chunk_env = std::getenv("NGPDE_GNO_GFORM_CHUNK");
+  // edges per chunk (A/B runs): NGPDE_GNO_GFORM_CHUNK=16; unset or any other value means 32
+  const char *chunk_env = switch_text(Switch::GnoGformChunk);
   const int chunk = chunk_env && std::atoi(chunk_env) == 16 ? 16 : 32;
 #define NGPDE_GF2(CC, AA)                                                                         \
   do {                                                                                            \

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "switches.h"
 
 namespace ngpde {
 
@@ -318,16 +319,12 @@ __global__ __launch_bounds__(256, NOB == 8 ? 4 : 2) void gno_apply_mfma_bwd_kern
   }
 }
 
-inline bool no_gno_mfma_env() {
-  const char *e = std::getenv("NGPDE_NO_GNO_MFMA");
-  return e && e[0] == '1';
-}
 inline size_t gno_mfma_bwd_lds(int cout, int kdim) { return (size_t)(kEBb * (kdim + 4) + kEBb * (cout + 4)) * sizeof(float); }
 
 }  // namespace
 
 bool gno_apply_mfma_supported(int cout, int kdim) {
-  return !no_gno_mfma_env() && cout % 16 == 0 && cout >= 16 && cout <= 256 && (kdim == 16 || kdim == 32 || kdim == 64) &&
+  return !switch_on(Switch::NoGnoMfma) && cout % 16 == 0 && cout >= 16 && cout <= 256 && (kdim == 16 || kdim == 32 || kdim == 64) &&
          gno_mfma_bwd_lds(cout, kdim) <= 150 * 1024;
 }
 

@@ -8,6 +8,7 @@
 #include <new>
 
 #include "common.h"
+#include "switches.h"
 #include <dlfcn.h>
 
 namespace ngpde {
@@ -17,12 +18,10 @@ const RoctxApi &roctx_api() {
     // Ranges are for profiling runs: on when the marker library is ALREADY in the process (rocprofv3 preloads it: RTLD_NOLOAD finds
     // it without loading anything) or when NGPDE_ROCTX=1 asks for it; a production process never pulls a profiler library in, and
     // never with global symbol visibility.  NGPDE_NO_ROCTX=1 turns them off even under a profiler.
-    const char *off = std::getenv("NGPDE_NO_ROCTX");
-    if (off && off[0] == '1') return a;
+    if (switch_on(Switch::NoRoctx)) return a;
     void *h = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
     if (!h) h = dlopen("librocprofiler-sdk-roctx.so.1", RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
-    const char *on = std::getenv("NGPDE_ROCTX");
-    if (!h && on && on[0] == '1') {
+    if (!h && switch_on(Switch::Roctx)) {
       h = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_LOCAL);
       if (!h) h = dlopen("librocprofiler-sdk-roctx.so.1", RTLD_NOW | RTLD_LOCAL);
     }

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.h"
+#include "switches.h"
 
 using namespace ngpde;
 
@@ -586,14 +587,14 @@ static int32_t node_create(const ngpde_graph_t *g, int32_t members, int32_t d, i
   p->row_elems = (size_t)p->n * d;
   p->all_elems = (size_t)members * p->row_elems;
   p->nb = fused_num_blocks(p->n);
-  p->mask_mode = p->with_bwd && act == NGPDE_ACT_RELU && std::getenv("NGPDE_NO_MASK") == nullptr;
-  p->pre = fused_prescaled_supported(g, d) && std::getenv("NGPDE_NO_PRESCALE") == nullptr;
+  p->mask_mode = p->with_bwd && act == NGPDE_ACT_RELU && !switch_on(Switch::NoMask);
+  p->pre = fused_prescaled_supported(g, d) && !switch_on(Switch::NoPrescale);
   // The persistent form (node_persistent.hip) is decided here, before the tape is sized: with an activation other than relu its
   // adjoint reads the pre-activations from a tape of its own layout.  (Interleaved batches: relu only.)
   int pmode = p->pre ? node_persistent_mode(g, d, act, p->with_bwd) : 0;
   // Graphs with hubs (a tile beyond the handle's 96-row halo lists, BASELINE config 1): the hub geometry of the persistent kernels, on
   // pre-scaled arrays like every persistent plan -- both directions or not at all (there is no pre-scaled replayed plan for them)
-  bool hub = !p->pre && pmode == 0 && std::getenv("NGPDE_NO_PRESCALE") == nullptr && node_persistent_hub_possible(g, d) &&
+  bool hub = !p->pre && pmode == 0 && !switch_on(Switch::NoPrescale) && node_persistent_hub_possible(g, d) &&
              (!p->with_bwd || p->mask_mode || act != NGPDE_ACT_RELU);
   if (hub) {
     pmode = 4;
@@ -646,18 +647,17 @@ static int32_t node_create(const ngpde_graph_t *g, int32_t members, int32_t d, i
   int dev_ = 0, cus_ = 0;
   const bool one_wave = hipGetDevice(&dev_) == hipSuccess && hipDeviceGetAttribute(&cus_, hipDeviceAttributeMultiprocessorCount, dev_) == hipSuccess &&
                         p->nb <= 2 * cus_;
-  if (st == NGPDE_OK && p->pre && !hub && one_wave) {
-    const char *nof = std::getenv("NGPDE_NO_OWN_FIRST");
-    if (!(nof && nof[0] == '1')) {
-      st = own_first_tables_build(g, &p->of, nullptr);
-      p->has_of = st == NGPDE_OK;
-    }
+  if (st == NGPDE_OK && p->pre && !hub && one_wave && !switch_on(Switch::NoOwnFirst)) {
+    st = own_first_tables_build(g, &p->of, nullptr);
+    p->has_of = st == NGPDE_OK;
   }
   // activations other than relu: the persistent adjoint reads the pre-activations from a tape of its own layout
   p->ztape_mode = p->with_bwd && !p->mask_mode && p->persistent;
   p->slots = p->mask_mode ? 2 : (p->ztape_mode ? 4 : (p->with_bwd ? (p->needs_z ? 6 : 4) : 4));
   p->mask_bytes = p->mask_mode ? fused_mask_bytes(p->n, d) : 0;
-  p->interleave = members > 1 && !hub && node_persistent_interleave_env();   // (hub geometry: the members one after the other)
+  // two members at a time; one after the other in the hub geometry and under NGPDE_NO_INTERLEAVE=1 (the form the interleaved kernels are
+  // compared with bit for bit)
+  p->interleave = members > 1 && !hub && !switch_on(Switch::NoInterleave);
   const size_t xslots = p->interleave ? 2 : 1;   // [N][d] arrays per exchanged buffer
   auto A = [&](float **ptr, size_t elems) {
     if (st == NGPDE_OK) st = dev_alloc(ptr, elems);
@@ -730,8 +730,7 @@ int32_t ngpde_node_gcn2_create_batch(const ngpde_graph_t *g, int32_t members, in
                                      int32_t n_steps, float dt, int32_t with_backward, ngpde_node_t **out) {
   NGPDE_RANGE();
   // d = 16 / 32 where the 64-wide persistent solver can take the graph: run widened (NGPDE_NO_WIDEN=1: the native-width replayed plan)
-  const char *nw = std::getenv("NGPDE_NO_WIDEN");
-  if (out && g && (d == 16 || d == 32) && !(nw && nw[0] == '1') && g->has_norm && g->n_nodes >= 1 &&
+  if (out && g && (d == 16 || d == 32) && !switch_on(Switch::NoWiden) && g->has_norm && g->n_nodes >= 1 &&
       (node_persistent_mode(g, 64, act, with_backward != 0) != 0 || node_persistent_hub_possible(g, 64))) {
     ngpde_node_t *w = nullptr;
     if (node_create(g, members, 64, d, act, tableau, n_steps, dt, with_backward, &w) == NGPDE_OK) {

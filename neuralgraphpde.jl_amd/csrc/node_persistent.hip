@@ -36,6 +36,7 @@
 #include "common.h"
 #include "persistent_gcn_tile.h"
 #include "stamps.h"
+#include "switches.h"
 
 namespace ngpde {
 
@@ -1536,11 +1537,6 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-bool node_persistent_disabled_env() {   // read at every plan creation: tests switch it per plan
-  const char *e = std::getenv("NGPDE_NO_PERSISTENT");
-  return e && e[0] == '1';
-}
-
 // Wait lists: tile T waits for every tile that owns a row of T's halo in either direction, and for every tile whose halo holds
 // a row of T (they read what T is about to overwrite).  [n_tiles][kNbrStride], -1 padded.  Returns false when a list overflows.
 static bool build_wait_lists(const ngpde_graph *g, std::vector<int> &out) {
@@ -1587,7 +1583,7 @@ bool node_wait_lists_fit(const ngpde_graph *g) {
 // workgroups co-resident.)  0: no.  1: one tile per workgroup (graphs of at most CUs x occupancy tiles).  2: two tiles per
 // workgroup through the two-slot kernels (up to twice as many tiles; relu when a backward is asked for).
 int node_persistent_mode(const ngpde_graph *g, int d, int act, bool with_bwd) {
-  if (node_persistent_disabled_env()) return 0;
+  if (switch_on(Switch::NoPersistent)) return 0;
   if (!g || d != PD || !fused_prescaled_supported(g, d)) return 0;
   const bool weighted = g->by_t.slot_w || g->by_s.slot_w;
   if (weighted && !(g->by_t.slot_w && g->by_s.slot_w)) return 0;
@@ -1627,15 +1623,12 @@ int node_persistent_mode(const ngpde_graph *g, int d, int act, bool with_bwd) {
     take(ow_f, node_fwd_persistent_kernel<-1, false, true>);
     take(ow_b, node_bwd_persistent_kernel<NGPDE_ACT_RELU, true>);
     take(ow_b, node_bwd_persistent_kernel<-1, true>);
-    const char *no1 = std::getenv("NGPDE_WEIGHTED_TILE_ROUNDS");   // 1: the tile-round kernels also where one tile per workgroup would do (A/B runs)
-    if (nt <= cus * std::min(ow_f, ow_b) && !(no1 && no1[0] == '1')) return 1;
+    if (nt <= cus * std::min(ow_f, ow_b) && !switch_on(Switch::WeightedTileRounds)) return 1;
     return nt <= kMaxTileRoundsW * resident ? 3 : 0;
   }
   if (nt <= resident) return 1;
-  const char *no_pairs = std::getenv("NGPDE_NO_TILE_PAIRS");
-  if (no_pairs && no_pairs[0] == '1') return 0;
-  const char *rounds = std::getenv("NGPDE_TILE_ROUNDS");   // 1: tile rounds also where tile pairs would do (A/B runs)
-  if (nt <= 2 * resident && (!with_bwd || act == NGPDE_ACT_RELU) && !(rounds && rounds[0] == '1')) return 2;
+  if (switch_on(Switch::NoTilePairs)) return 0;
+  if (nt <= 2 * resident && (!with_bwd || act == NGPDE_ACT_RELU) && !switch_on(Switch::TileRounds)) return 2;
   if (nt <= kMaxTileRounds * resident) return 3;   // K tiles per workgroup taking turns (node_*_persistentK_kernel)
   return 0;
 }
@@ -1668,8 +1661,7 @@ int node_persistent_rounds(const ngpde_graph *g) {   // K of mode 3: tiles per w
 bool node_persistent_supported(const ngpde_graph *g, int d, int act, bool with_bwd) { return node_persistent_mode(g, d, act, with_bwd) == 1; }
 
 bool node_persistent_hub_possible(const ngpde_graph *g, int d) {
-  const char *nh = std::getenv("NGPDE_NO_HALO");   // (asks for the per-row global gather everywhere)
-  if (node_persistent_disabled_env() || (nh && nh[0] == '1')) return false;
+  if (switch_on(Switch::NoHalo) || switch_on(Switch::NoPersistent)) return false;   // (NO_HALO asks for the per-row global gather everywhere)
   if (!g || d != PD || !g->has_norm || !g->self_loops || ((g->by_t.slot_w || g->by_s.slot_w) && !g->w_coo)) return false;
   if (g->by_t.halo_ok && g->by_s.halo_ok) return false;   // the 96-row geometry takes it
   int dev = 0, cus = 0, occ = 1 << 30;
@@ -1851,13 +1843,6 @@ extern "C" int32_t ngpde_hub_partition_host(int64_t n_nodes, const int32_t *rowp
   return NGPDE_OK;
 }
 namespace ngpde {
-
-// NGPDE_NO_INTERLEAVE=1: a batch's members one after the other (the round-2 form) instead of two at a time -- the A/B switch and
-// the reference the interleaved kernels are compared with bit for bit
-bool node_persistent_interleave_env() {
-  const char *e = std::getenv("NGPDE_NO_INTERLEAVE");
-  return !(e && e[0] == '1');
-}
 
 // ---- a plan's own-first slot tables (OwnFirst, common.h) ----------------------------------------------------------------------------
 namespace {
@@ -2141,8 +2126,7 @@ int32_t PersistentTurn::enter(const NodePersist &p, hipStream_t s) {
   }
   int32_t st;
   if ((st = launch_zero(p.sync, p.sync_bytes, stream))) return st;
-  const char *fa = std::getenv("NGPDE_DEBUG_FORCE_ABORT");   // (read at every launch: the tests set it around one call)
-  if (fa && fa[0] == '1') hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(64), 0, stream, sync_abort_word(p.sync, p.n_tiles), 1u);
+  if (switch_on(Switch::DebugForceAbort)) hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(64), 0, stream, sync_abort_word(p.sync, p.n_tiles), 1u);
   return NGPDE_OK;
 }
 int32_t PersistentTurn::latch() {

@@ -41,6 +41,7 @@
 #include "persistent_mem.h"
 #include "persistent_sync.h"
 #include "stamps.h"
+#include "switches.h"
 
 namespace ngpde {
 
@@ -1155,8 +1156,7 @@ static VmhPlanGeo vmh_geo_uncached(int n_mats, int n_tiles, bool no_rounds) {
 }
 // (asked at every launch: the attribute / occupancy queries behind it are remembered per shape and device)
 static VmhPlanGeo vmh_geo(int n_mats, int n_tiles) {
-  const char *nr = std::getenv("NGPDE_NO_VMH_ROUNDS");   // (tests and A/B runs: graphs beyond the resident half tiles to the generic solver)
-  const bool no_rounds = nr && nr[0] == '1';
+  const bool no_rounds = switch_on(Switch::NoVmhRounds);   // (graphs beyond the resident half tiles go to the generic solver)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return VmhPlanGeo();
   static std::mutex mu;
@@ -1174,8 +1174,7 @@ static VmhPlanGeo vmh_geo(int n_mats, int n_tiles) {
 }  // namespace
 
 bool node_vmh_supported(const ngpde_graph *g, const VmhShape &s) {
-  const char *off = std::getenv("NGPDE_NO_VMH_NODE");
-  if (off && off[0] == '1') return false;
+  if (switch_on(Switch::NoVmhNode)) return false;
   if (!g || !g->has_norm || !g->by_t.halo_ok || !g->by_s.halo_ok) return false;
   if (s.hd != 1 || s.pd < 1 || s.pd > 3) return false;
   if (s.n_phi < 2 || s.n_phi > kVmhMaxL || s.n_gam < 2 || s.n_gam > kVmhMaxL) return false;
