@@ -5,19 +5,17 @@
 //   BASELINE config 3                                              (one GAT-style layer; src/NeuralGraphPDE.jl:7)
 // The choice of plan -- which of the three solvers takes the right-hand side, whether a batch of identical structures runs on the member's
 // handle, what the shapes must satisfy -- was host code (node.py) until round 6; a Julia host would have had to write it again.  The
-// plans themselves are ngpde_node_gcn2_* / ngpde_node_gat_* / ngpde_node_vmh_* (node.hip, gat_fused.hip, node_vmh.hip), unchanged.
+// plans themselves are ngpde_node_gcn2_* / ngpde_node_gat_* / ngpde_node_vmh_* (node.hip, node_gat_plan.hip, node_vmh_plan.hip), unchanged;
+// what they share -- ownership, tape size, the fault word -- is read through their base (plan_host.h).
 #include <cstring>
-#include <new>
 
-#include "common.h"
+#include "plan_host.h"
 
 using namespace ngpde;
 
 struct ngpde_ode {
   int32_t rhs = 0;
-  ngpde_node_t *gcn = nullptr;
-  ngpde_node_gat_t *gat = nullptr;
-  ngpde_node_vmh_t *vmh = nullptr;
+  ResidentPlan *plan = nullptr;   // ngpde_node / ngpde_node_gat / ngpde_node_vmh by `rhs`
   ngpde_ode_desc_t desc;
   int32_t flags = 0;
 };
@@ -45,12 +43,10 @@ int32_t check_mlp_chain(const char *name, int32_t n, const int32_t *dims, const 
 extern "C" {
 
 int32_t ngpde_ode_create(const ngpde_graph_t *g, const ngpde_ode_desc_t *d, ngpde_ode_t **out, int32_t *flags) {
-  NGPDE_REQUIRE(g != nullptr && d != nullptr && out != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_create: NULL argument");
-  *out = nullptr;
+  NGPDE_REQUIRE(d != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_create: NULL argument");
   if (flags) *flags = 0;
-  NGPDE_REQUIRE(d->tableau == NGPDE_TABLEAU_EULER || d->tableau == NGPDE_TABLEAU_TSIT5, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_create: unknown tableau %d",
-                d->tableau);
-  NGPDE_REQUIRE(d->n_steps >= 1 && d->members >= 1, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_create: n_steps = %d, members = %d", d->n_steps, d->members);
+  // (the activation is judged by the plan's own create, after what that create puts before it)
+  NGPDE_TRY(plan_check_create("ngpde_ode_create", g, out, d->tableau, d->n_steps, NGPDE_ACT_IDENTITY, d->members));
   ngpde_ode *o = new (std::nothrow) ngpde_ode();
   NGPDE_REQUIRE(o != nullptr, NGPDE_ERR_HIP, "ngpde_ode_create: out of host memory");
   o->rhs = d->rhs;
@@ -58,9 +54,10 @@ int32_t ngpde_ode_create(const ngpde_graph_t *g, const ngpde_ode_desc_t *d, ngpd
   int32_t st = NGPDE_OK, fl = 0;
   switch (d->rhs) {
     case NGPDE_RHS_GCN2: {
-      if (d->members > 1) st = ngpde_node_gcn2_create_batch(g, d->members, d->width, d->act, d->tableau, d->n_steps, (float)d->dt, d->with_backward, &o->gcn);
-      else st = ngpde_node_gcn2_create(g, d->width, d->act, d->tableau, d->n_steps, (float)d->dt, d->with_backward, &o->gcn);
-      if (st == NGPDE_OK) (void)ngpde_node_flags(o->gcn, &fl);
+      ngpde_node_t *gcn = nullptr;
+      st = ngpde_node_gcn2_create_batch(g, d->members, d->width, d->act, d->tableau, d->n_steps, (float)d->dt, d->with_backward, &gcn);
+      if (st == NGPDE_OK) (void)ngpde_node_flags(gcn, &fl);
+      o->plan = gcn;
       break;
     }
     case NGPDE_RHS_GAT: {
@@ -70,9 +67,9 @@ int32_t ngpde_ode_create(const ngpde_graph_t *g, const ngpde_ode_desc_t *d, ngpd
                                          "the LDS halo): step the layer with ngpde_gat_layer_* and ngpde_rk_stage_combine");
         break;
       }
-      if (d->members > 1)
-        st = ngpde_node_gat_create_batch(g, d->members, d->heads, d->head_width, d->negative_slope, d->act, d->tableau, d->n_steps, d->dt, d->with_backward, &o->gat);
-      else st = ngpde_node_gat_create(g, d->heads, d->head_width, d->negative_slope, d->act, d->tableau, d->n_steps, d->dt, d->with_backward, &o->gat);
+      ngpde_node_gat_t *gat = nullptr;
+      st = ngpde_node_gat_create_batch(g, d->members, d->heads, d->head_width, d->negative_slope, d->act, d->tableau, d->n_steps, d->dt, d->with_backward, &gat);
+      o->plan = gat;
       fl = NGPDE_NODE_PERSISTENT_FWD | (d->with_backward ? NGPDE_NODE_PERSISTENT_BWD : 0);
       break;
     }
@@ -90,10 +87,12 @@ int32_t ngpde_ode_create(const ngpde_graph_t *g, const ngpde_ode_desc_t *d, ngpd
                                          "ngpde_rk_stage_combine");
         break;
       }
+      ngpde_node_vmh_t *vmh = nullptr;
       st = ngpde_node_vmh_create(g, hd, d->pos_width, d->pos, d->n_phi, d->phi_dims, d->phi_acts, d->n_gamma, d->gamma_dims, d->gamma_acts, d->aggr, d->tableau,
-                                 d->n_steps, d->dt, d->with_backward, &o->vmh);
+                                 d->n_steps, d->dt, d->with_backward, &vmh);
       fl = NGPDE_NODE_PERSISTENT_FWD | (d->with_backward ? NGPDE_NODE_PERSISTENT_BWD : 0);
-      if (st == NGPDE_OK && node_vmh_plan_tile_rounds(o->vmh)) fl |= NGPDE_NODE_TILE_ROUNDS;
+      if (st == NGPDE_OK && node_vmh_tile_rounds(g, vmh->shape)) fl |= NGPDE_NODE_TILE_ROUNDS;
+      o->plan = vmh;
       break;
     }
     default: st = fail(NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_create: unknown right-hand side %d", d->rhs);
@@ -111,26 +110,16 @@ int32_t ngpde_ode_create(const ngpde_graph_t *g, const ngpde_ode_desc_t *d, ngpd
 
 int32_t ngpde_ode_destroy(ngpde_ode_t *o) {
   if (!o) return NGPDE_OK;
-  int32_t st = NGPDE_OK;
-  if (o->gcn) st = ngpde_node_destroy(o->gcn);
-  if (o->gat) st = ngpde_node_gat_destroy(o->gat);
-  if (o->vmh) st = ngpde_node_vmh_destroy(o->vmh);
+  delete o->plan;
   delete o;
-  return st;
+  return NGPDE_OK;
 }
 
-size_t ngpde_ode_tape_bytes(const ngpde_ode_t *o) {
-  if (!o) return 0;
-  if (o->gcn) return ngpde_node_tape_bytes(o->gcn);
-  if (o->gat) return ngpde_node_gat_tape_bytes(o->gat);
-  return o->vmh ? ngpde_node_vmh_tape_bytes(o->vmh) : 0;
-}
+size_t ngpde_ode_tape_bytes(const ngpde_ode_t *o) { return o ? o->plan->tape_bytes : 0; }
 
 int32_t ngpde_ode_fault(ngpde_ode_t *o, ngpde_stream_t stream, int32_t *fault) {
-  NGPDE_REQUIRE(o != nullptr && fault != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_fault: NULL argument");
-  if (o->gcn) return ngpde_node_fault(o->gcn, stream, fault);
-  if (o->gat) return ngpde_node_gat_fault(o->gat, stream, fault);
-  return ngpde_node_vmh_fault(o->vmh, stream, fault);
+  NGPDE_REQUIRE(o != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_fault: NULL argument");
+  return plan_fault("ngpde_ode_fault", o->plan, stream, fault);
 }
 
 int32_t ngpde_ode_forward(ngpde_ode_t *o, const float *u0, const ngpde_ode_params_t *p, int32_t save_every, int32_t save_start, float *out,
@@ -141,14 +130,16 @@ int32_t ngpde_ode_forward(ngpde_ode_t *o, const float *u0, const ngpde_ode_param
   switch (o->rhs) {
     case NGPDE_RHS_GCN2:
       NGPDE_REQUIRE(p->first.weight[0] && p->first.weight[1], NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_forward: layer_1 / layer_2 weight is NULL");
-      return ngpde_node_gcn2_forward(o->gcn, u0, p->first.weight[0], p->first.bias[0], p->first.weight[1], p->first.bias[1], out, stream);
+      return ngpde_node_gcn2_forward(static_cast<ngpde_node_t *>(o->plan), u0, p->first.weight[0], p->first.bias[0], p->first.weight[1], p->first.bias[1], out, stream);
     case NGPDE_RHS_GAT:
       NGPDE_REQUIRE(p->first.weight[0] && p->attention, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_ode_forward: weight or attention vector is NULL");
-      return ngpde_node_gat_forward(o->gat, u0, p->first.weight[0], p->attention, p->first.bias[0], out, stream);
-    default:
+      return ngpde_node_gat_forward(static_cast<ngpde_node_gat_t *>(o->plan), u0, p->first.weight[0], p->attention, p->first.bias[0], out, stream);
+    default: {
+      ngpde_node_vmh_t *vmh = static_cast<ngpde_node_vmh_t *>(o->plan);
       if (save_every > 0)
-        return ngpde_node_vmh_forward_saveat(o->vmh, u0, p->first.weight, p->first.bias, p->second.weight, p->second.bias, save_every, save_start, out, stream);
-      return ngpde_node_vmh_forward(o->vmh, u0, p->first.weight, p->first.bias, p->second.weight, p->second.bias, out, stream);
+        return ngpde_node_vmh_forward_saveat(vmh, u0, p->first.weight, p->first.bias, p->second.weight, p->second.bias, save_every, save_start, out, stream);
+      return ngpde_node_vmh_forward(vmh, u0, p->first.weight, p->first.bias, p->second.weight, p->second.bias, out, stream);
+    }
   }
 }
 
@@ -158,15 +149,17 @@ int32_t ngpde_ode_backward(ngpde_ode_t *o, const ngpde_ode_params_t *p, int32_t 
   NGPDE_REQUIRE(save_every == 0 || o->rhs == NGPDE_RHS_VMH, NGPDE_ERR_UNSUPPORTED, "ngpde_ode_backward: saveat is served by the VMH plan only");
   switch (o->rhs) {
     case NGPDE_RHS_GCN2:
-      return ngpde_node_gcn2_backward(o->gcn, dout, du0, gr->first.dweight[0], gr->first.dbias[0], gr->first.dweight[1], gr->first.dbias[1], stream);
+      return ngpde_node_gcn2_backward(static_cast<ngpde_node_t *>(o->plan), dout, du0, gr->first.dweight[0], gr->first.dbias[0], gr->first.dweight[1], gr->first.dbias[1], stream);
     case NGPDE_RHS_GAT:
-      return ngpde_node_gat_backward(o->gat, p->first.weight[0], p->attention, dout, du0, gr->first.dweight[0], gr->dattention, gr->first.dbias[0], stream);
-    default:
+      return ngpde_node_gat_backward(static_cast<ngpde_node_gat_t *>(o->plan), p->first.weight[0], p->attention, dout, du0, gr->first.dweight[0], gr->dattention, gr->first.dbias[0], stream);
+    default: {
+      ngpde_node_vmh_t *vmh = static_cast<ngpde_node_vmh_t *>(o->plan);
       if (save_every > 0)
-        return ngpde_node_vmh_backward_saveat(o->vmh, p->first.weight, p->second.weight, save_every, save_start, dout, du0, gr->first.dweight, gr->first.dbias,
+        return ngpde_node_vmh_backward_saveat(vmh, p->first.weight, p->second.weight, save_every, save_start, dout, du0, gr->first.dweight, gr->first.dbias,
                                               gr->second.dweight, gr->second.dbias, stream);
-      return ngpde_node_vmh_backward(o->vmh, p->first.weight, p->second.weight, dout, du0, gr->first.dweight, gr->first.dbias, gr->second.dweight,
+      return ngpde_node_vmh_backward(vmh, p->first.weight, p->second.weight, dout, du0, gr->first.dweight, gr->first.dbias, gr->second.dweight,
                                      gr->second.dbias, stream);
+    }
   }
 }
 

@@ -212,7 +212,7 @@ struct NodePersist {
   unsigned *fault = nullptr;   // sticky: some persistent launch of this plan gave up waiting (device pointer of fault_host)
   volatile unsigned *fault_host = nullptr;   // the same word in pinned host memory: readable without a synchronisation
   int *stats = nullptr;        // [n_tiles][2]: slot-phases of the last forward / adjoint launch gathered ahead of time (interleaved kernels)
-  float *coef = nullptr;       // device tables indexed by the stage: forward [42], adjoint [48] (layout: node.hip)
+  float *coef = nullptr;       // device tables indexed by the stage: forward [42], adjoint [48] (layout: rk_tableau.h, node.hip)
   // hub geometry (node_persistent.hip: graphs whose tiles do not fit the handle's 96-row halo lists): per direction (0 by target,
   // 1 by source) the tile lists the HUB kernels read, built by node_persistent_setup; `nbr` is then [n_tiles][256]
   bool hub = false;
@@ -295,7 +295,7 @@ struct PersistentTurn {
   PersistentTurn(const PersistentTurn &) = delete;
   PersistentTurn &operator=(const PersistentTurn &) = delete;
 };
-// the GAT-style layer (64 => heads x c = 64) as ODE right-hand side, device-resident (gat_fused.hip; plan: node_gat.hip)
+// the GAT-style layer (64 => heads x c = 64) as ODE right-hand side, device-resident (gat_fused.hip; plan: node_gat_plan.hip)
 struct GatNodeFwd {
   const ngpde_graph *g = nullptr;
   const NodePersist *ps = nullptr;   // wait lists, flags, abort / fault words (node_persistent_setup)
@@ -329,7 +329,7 @@ size_t gat_node_dscore_elems(const ngpde_graph *g);                       // flo
 int32_t launch_gat_node_xpad(const ngpde_graph *g, int *pad_of_p, int *xpad, hipStream_t stream);
 int32_t launch_gat_node_fwd(const GatNodeFwd &a, hipStream_t stream);
 int32_t launch_gat_node_bwd(const GatNodeBwd &a, hipStream_t stream);
-// NeuralODE(VMHConv(phi, gamma)) device-resident (node_vmh.hip; plan: node.hip)
+// NeuralODE(VMHConv(phi, gamma)) device-resident (node_vmh.hip; plan: node_vmh_plan.hip)
 constexpr int kVmhMaxL = 4;      // Dense layers per MLP
 struct VmhShape {
   int hd = 1, pd = 2, aggr = 1, n_phi = 0, n_gam = 0;
@@ -358,7 +358,6 @@ struct VmhLaunch {
 };
 bool node_vmh_supported(const ngpde_graph *g, const VmhShape &s);
 bool node_vmh_tile_rounds(const ngpde_graph *g, const VmhShape &s);   // a supported shape: does the plan run in tile rounds?
-bool node_vmh_plan_tile_rounds(const ngpde_node_vmh_t *plan);          // ... of a plan (node.hip)
 int32_t launch_node_vmh_fwd(const VmhLaunch &a, hipStream_t stream);
 int32_t launch_node_vmh_bwd(const VmhLaunch &a, hipStream_t stream);
 int32_t launch_vmh_copy_block(const float *src, int sp, float *dst, int dp, int rows, int cols, hipStream_t stream);

@@ -4,7 +4,7 @@ ngpde_node_gcn2_create[_batch] (csrc/node.hip: node_create) solves du/dt = Chain
 ONE forward launch and ONE adjoint launch (csrc/node_persistent.hip, persistent_gcn_tile.h, persistent_sync.h) whose 32-row tiles
 hand their rows over through per-tile phase flags.  Which kernels run is decided by node_persistent_mode (node_persistent.hip:1585),
 restated:
-  0  no persistent plan: NGPDE_NO_PERSISTENT=1, d != 64 (16 / 32 are widened onto 64 first, node.hip:733), or a handle that is not
+  0  no persistent plan: NGPDE_NO_PERSISTENT=1, d != 64 (16 / 32 are widened onto 64 first, node.hip:572), or a handle that is not
      fused_prescaled_supported (gcn_fused.hip:859: self loops and halo_ok in BOTH directions); weights in one direction only.
      resident = CUs x the smallest occupancy of the instantiations the plan may launch (2 on an MI355X: every kernel's LDS is held to
      80 KB - 64 by a static_assert, node_persistent.hip:200, :302, :661, :1157, :1338).
@@ -19,13 +19,13 @@ restated:
      (node_persistent_rounds, :1635): node_*_persistentKP_kernel (:299, :1333), weighted handles node_*_persistentK_kernel (:197, :1152).
   A batch of `members` same-structure graphs (create_batch) runs mode 1 with relu only, two members per workgroup on
   node_*_persistent2_kernel<.., PAIR = false>, an odd last member alone; NGPDE_NO_INTERLEAVE=1: member after member on the one-tile
-  kernels (node.hip:660).
+  kernels (node.hip:514).
 The caps: kHaloCap = 96 staged rows and kSlotWidth = 32 list entries per row (common.h:79, :80) in both directions, or the handle is
 not halo_ok; kNbrStride - 1 = 63 tiles in a wait list (persistent_sync.h:16; build_wait_lists, node_persistent.hip:1542), or
-node_persistent_setup returns NGPDE_ERR_UNSUPPORTED and node_create keeps the pre-scaled replayed plan (node.hip:625).  The self
+node_persistent_setup returns NGPDE_ERR_UNSUPPORTED and node_create keeps the pre-scaled replayed plan (node.hip:481).  The self
 loop is not a list entry (the kernels add the own row after the slots, persistent_gcn_tile.h:231), so a row at the slot cap has 32
 constructed in-edges, 33 terms with the loop, and the first row beyond it 33.  A handle beyond a halo or slot cap goes to the hub
-geometry (<.., HUB = true>, node.hip:597) where ngpde_hub_partition_host accepts it.
+geometry (<.., HUB = true>, node.hip:458) where ngpde_hub_partition_host accepts it.
 
 Sections and the instantiations they reach (every plan's flag word is asserted BEFORE anything is compared):
   A  one tile per workgroup, unweighted: <RELU, true> + bwd<RELU>; <-1, true> + bwd<-1> (tanh, sigmoid); <RELU / -1, false> (forward-only
@@ -44,7 +44,7 @@ geometry without a GPU), asserts the regime from the host geometry and the libra
 points with uT, du0, dW1, db1, dW2, db2 starting as NaN in front of guard words, requires ngpde_node_fault == 0 after the forward and
 after the backward, compares everything with the oracle's float64 gcn2_rhs / rk_solve / rk_adjoint (weighted: gcn_conv with
 use_edge_weight) and solves a second time on the same plan: every output bit for bit (slabs per tile or workgroup, summed in a
-fixed order by reduce4_slabs_kernel, node.hip:144; no atomics).  dt = 0.1, Tsit5 x 2 and Euler x 3 steps (section E: see above).
+fixed order by reduce4_slabs_kernel, node.hip:115; no atomics).  dt = 0.1, Tsit5 x 2 and Euler x 3 steps (section E: see above).
 
 Tolerances are test_node_persistent_plan_against_oracle's, over whole arrays in the max norm: u(T) 2e-4 * max|ref| + 1e-5, du0
 5e-4 * max|ref| + 1e-4, dW and db 5e-4 * max|ref| + 1e-3.  Relu: graphs of up to 33 nodes redraw their inputs until no float64

@@ -1,6 +1,6 @@
 """The device-resident NeuralODE(VMHConv(phi, gamma)) plan against float64 across its shape envelope.
 
-ngpde_node_vmh_* (csrc/node_vmh.hip; plan and entries: csrc/node.hip) solves du/dt = VMHConv(phi, gamma)(u) on a scalar state with ONE
+ngpde_node_vmh_* (csrc/node_vmh.hip; plan and entries: csrc/node_vmh_plan.hip) solves du/dt = VMHConv(phi, gamma)(u) on a scalar state with ONE
 persistent forward launch and ONE persistent adjoint launch, each in two template forms (vmh_geo_uncached, node_vmh.hip:1166):
   ROUNDS = false  every 16-row half tile of the handle's node order its own workgroup, all of them resident at once
                   (2 * tiles <= CUs x occupancy);
@@ -751,7 +751,7 @@ def test_g_supported_implies_create():
 
 
 def test_g_gat_supported_implies_create():
-    # ngpde_node_gat_create builds the same wait lists (node.hip): the same graph, the same contract
+    # ngpde_node_gat_create builds the same wait lists (node_gat_plan.hip): the same graph, the same contract
     lib = _lib.load()
     g = nbr_graph(64)
     sup = lib.ngpde_node_gat_supported(g.ptr, 64, 4, 16)

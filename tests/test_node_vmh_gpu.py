@@ -446,7 +446,7 @@ def test_vmh_tapes_of_a_destroyed_plan_are_parked_and_can_be_released(monkeypatc
 
 
 def test_vmh_solve_on_parked_tapes_of_another_graph_is_bitwise_the_solve_on_fresh_tapes(monkeypatch):
-    # parked tapes are handed on unzeroed (node.hip: tape_pool_*): what the next plan reads of them must all have been written by its own
+    # parked tapes are handed on unzeroed (node_vmh_plan.hip: tape_pool_*): what the next plan reads of them must all have been written by its own
     # solve.  A wide, dense first model (k = 8: every edge row of a round is real; 60-wide layers) leaves its rows behind; the second
     # one -- variable degrees, 20 / 12-wide layers, fewer nodes -- runs on them, then again on freshly zeroed tapes: every output equal
     monkeypatch.delenv("NGPDE_NO_VMH_NODE", raising=False)
