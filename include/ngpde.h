@@ -643,6 +643,46 @@ int32_t ngpde_csr_spgemm(int64_t n, int64_t nnz_p, const int32_t *p_rows, const 
                          int32_t *rows_out, int32_t *cols_out, float *vals_out, int32_t *row_ptr_out, int64_t *nnz_out,
                          ngpde_stream_t stream);
 
+/* ---- graph solves (csrc/graph_solve.hip): the inverse side of a graph matrix, what upstream writes as `A \ b` or IterativeSolvers.cg on
+ * the SparseMatrixCSC -- an implicit Euler step (I + dt L) u+ = u, a screened Poisson solve, Laplacian smoothing.
+ * ngpde_csr_cg solves (shift I + scale M) x_d = b_d for every one of the n_rhs feature rows of B by the conjugate-gradient iteration.
+ * shift I + scale M must be SYMMETRIC (NOT CHECKED here: ngpde_csr_check_symmetric) and positive definite (found out by the iteration).
+ * M is block-diagonal over n_graphs graphs; every (graph, column) PAIR is its own CG with its own scalars, stop and iteration count.
+ *   graph_of     device int32[n], 0-based, NON-DECREASING (checked on the device), or NULL with n_graphs 1
+ *   B, x0, X     device float, (n_rhs x n) row-major: column d of the system is the contiguous row d, as GraphMatrix.matmul takes it;
+ *                x0 nullable (start at 0).  X may not alias B or x0.
+ *   precondition NGPDE_CG_NONE: z = r.  NGPDE_CG_JACOBI: z = r * (1 / (shift + scale * M[i][i])) (M[i][i] = 0 where the diagonal is no
+ *                entry); a diagonal that is not > 0 is NGPDE_ERR_INVALID_ARGUMENT naming the smallest such node, found by the launch
+ *                that builds the diagonal
+ *   iteration    r = b - A x0 (r = b without x0), z, p = z, rho = r . z; step: q = A p, alpha = rho / (p . q), x = x + alpha * p,
+ *                r = r - alpha * q, z, rho' = r . z, beta = rho' / rho, p = z + beta * p.  A pair stops with status 0 when
+ *                sqrt(r . r) <= max(rtol * sqrt(b . b), atol) (r: the recurrence residual; checked before the first step too, so a start
+ *                that solves the system takes 0 iterations), with status 1 after max_iter steps, with status 2 (breakdown: not positive
+ *                definite) at a step with p . q <= 0 or a non-finite alpha, beta, rho or r . r; the breaking step changes nothing.  A
+ *                stopped pair is frozen: no later launch reads or writes its columns.
+ *   sum orders   (the contract: a pair's bits depend on neither n_rhs, the column's place in B, the other graphs of the batch nor
+ *                check_every)
+ *                product: (A p)[i] = shift * p[i] + scale * s, s = the row's entries in ascending column from 0.0f, one multiply and one
+ *                add each.  Inner product: per chunk of 256 rows -- a graph's chunks start at its first node -- the balanced binary tree
+ *                over the chunk's rows (row 2 j with 2 j + 1, then pairs of pairs; rows past the graph's end count 0.0f); a graph's chunk
+ *                sums are then added in chunk order from 0.0f by every workgroup that needs the scalar.
+ *   launches     three per step, every dependency between steps a launch boundary (no cooperative launch, no spin-wait, no float
+ *                atomics): q = A p with the chunk sums of p . q | alpha, x, r, z with the chunk sums of r . z and r . r | beta, the
+ *                stops, p.  The state is node-major ([n][n_rhs padded]); B is transposed where it is loaded, X where a pair stops.
+ *   check_every  0: no read-back at all -- exactly max_iter steps are enqueued, stopped pairs freeze on the device, the call may be
+ *                captured into a HIP graph; input the device refuses (graph_of, a CSR list, the diagonal) then leaves every status 2
+ *                and X unwritten.  k > 0: the refusals are read once after the setup (named errors) and every k steps ONE word, the
+ *                number of pairs still running; the loop ends when it is 0.
+ *   outputs      device, [n_graphs][n_rhs]: status_out int32 (0 converged, 1 max_iter reached, 2 breakdown), iterations_out int32,
+ *                residual_out float = sqrt(r . r) at the stop.  A graph without nodes: 0, 0, 0.
+ * The call allocates nothing: everything lives in `workspace` (ngpde_csr_cg_workspace_bytes; 0 = sizes it refuses), device memory. */
+enum { NGPDE_CG_NONE = 0, NGPDE_CG_JACOBI = 1 };
+size_t ngpde_csr_cg_workspace_bytes(int64_t n, int32_t n_graphs, int32_t n_rhs);
+int32_t ngpde_csr_cg(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *cols, const float *vals, int32_t n_graphs,
+                     const int32_t *graph_of, float shift, float scale, int32_t n_rhs, const float *B, const float *x0, float *X,
+                     int32_t precondition, float rtol, float atol, int32_t max_iter, int32_t check_every, int32_t *status_out,
+                     int32_t *iterations_out, float *residual_out, void *workspace, size_t workspace_bytes, ngpde_stream_t stream);
+
 /* ---- graph queries by node and by pair on a device COO list (src/NeuralGraphPDE.jl:4 re-exports GNNGraphs and with it the Graphs.jl
  * queries a GNNGraph answers: has_edge, neighbors / inneighbors / outneighbors, adjacency_list, intersect, random_walk_pe): "is (s, t)
  * an edge?", "who are node i's neighbours?", "which edges do two graphs share?", and the random-walk positional encoding.  The

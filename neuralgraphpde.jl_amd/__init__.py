@@ -23,6 +23,7 @@ from .editing import (add_edges, add_nodes, get_edge_weight, negative_sample, re
 from .matrices import (GraphMatrix, adjacency_matrix, has_isolated_nodes, khop_adj, laplacian_lambda_max, laplacian_matrix,
                        normalized_laplacian, scaled_laplacian)
 from .queries import (AdjacencyList, adjacency_list, has_edge, inneighbors, intersect, neighbors, outneighbors, random_walk_pe)
+from .linsolve import CGInfo, cg_solve
 from . import dist, optim, synth
 
 
@@ -43,6 +44,6 @@ __all__ = [
     "to_bidirected", "induced_subgraph", "getgraph", "unbatch", "sample_neighbors", "rand_edge_split",
     "add_nodes", "add_edges", "remove_edges", "remove_nodes", "to_unidirected", "set_edge_weight", "get_edge_weight", "negative_sample",
     "GraphMatrix", "adjacency_matrix", "laplacian_matrix", "normalized_laplacian", "scaled_laplacian", "laplacian_lambda_max", "khop_adj",
-    "has_isolated_nodes",
+    "has_isolated_nodes", "cg_solve", "CGInfo",
     "AdjacencyList", "adjacency_list", "has_edge", "neighbors", "inneighbors", "outneighbors", "intersect", "random_walk_pe",
 ]

@@ -212,6 +212,9 @@ SIGNATURES = {
     "ngpde_csr_lambda_max": (_i32, [_i64, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _f32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_csr_spgemm_count": (_i32, [_i64, _i64, _vp, _i64, _vp, _i64, _vp, C.POINTER(_i64), _vp]),
     "ngpde_csr_spgemm": (_i32, [_i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_csr_cg_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "ngpde_csr_cg": (_i32, [_i64, _i64, _vp, _vp, _vp, _i32, _vp, _f32, _f32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp,
+                            _vp, _sz, _vp]),
     "ngpde_coo_sort_keys": (_i32, [_i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     "ngpde_coo_has_edge": (_i32, [_i64, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_coo_adjacency_count": (_i32, [_i64, _i64, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),

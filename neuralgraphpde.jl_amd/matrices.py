@@ -75,6 +75,18 @@ class GraphMatrix:
         no gradient through it; hence e_mul_xj here."""
         return propagate(e_mul_xj, self.as_graph(), "+", xj=X, e=self.values)
 
+    def diagonal(self):
+        """the (N,) float32 diagonal, 0 where the diagonal position is no entry; gradients flow to `values` (distinct positions: a plain
+        indexed write)"""
+        on = self.rows == self.cols
+        out = torch.zeros(self.shape[0], dtype=torch.float32, device=self.values.device)
+        return out.index_put((self.rows[on].to(torch.int64),), self.values[on])
+
+    def solve(self, B, **kw):
+        """X (D x N) with (shift I + scale M) X[d] = B[d]: linsolve.cg_solve(self, B, **kw), conjugate gradients on the device"""
+        from .linsolve import cg_solve
+        return cg_solve(self, B, **kw)
+
 
 class _Assembly:
     """what one ngpde_coo_matrix call wrote: the matrix's structure and what the pullback to the edge weights reads"""
