@@ -772,6 +772,85 @@ int32_t ngpde_csr_random_walk_pe(int64_t n, int64_t nnz, const int32_t *row_ptr,
                                  const int32_t *graph_of, int32_t walk_length, int32_t block, float *pe, void *workspace, size_t workspace_bytes,
                                  ngpde_stream_t stream);
 
+/* ---- graph traversal on a device COO list (csrc/graph_traverse.hip; src/NeuralGraphPDE.jl:4 re-exports GNNGraphs, whose GNNGraph is a
+ * Graphs.AbstractGraph -- `using Graphs`, src/NeuralGraphPDE.jl:16 -- so that connected_components, is_connected, gdistances and
+ * neighborhood work on it): "which nodes hang together?" and "how many edges from the nearest source?".  The conventions are those of
+ * the block above: int32 lists with `index_base`, sizes <= 2^31 - 1 (refused beyond), NULL and negative arguments refused before any
+ * device call (NGPDE_ERR_INVALID_ARGUMENT), an edge end or a listed node outside the node range NGPDE_ERR_DIMENSION_MISMATCH, found on
+ * the device by the launch that does the work without a read or write through it, the SMALLEST offending id named.  Every result is an
+ * integer and the only atomics are integer min / or / add, which commute: the bits depend neither on the COO order, the launch
+ * geometry nor the run.  Kernel boundaries are the only synchronisation (no spin-wait, no grid barrier).
+ *   check_every  as in ngpde_csr_cg.  k > 0: rounds / levels are enqueued in groups of k; every launch exits at once when the round /
+ *                level before it found nothing, and the host reads the 64-byte control block once per group (the named errors with
+ *                the first).  0: nothing is read back, exactly max_rounds rounds / max_hops levels are enqueued, the call allocates
+ *                nothing and may be captured into a HIP graph; input the device refuses is skipped and not raised. */
+
+/* connected_components, the labelling (src/NeuralGraphPDE.jl:4, :16): weak connectivity, the edges seen as undirected; self loops,
+ * parallel edges, isolated nodes and n_edges 0 are valid.  labels_out device int32[n_nodes]: the SMALLEST MEMBER (0-based) of every
+ * node's component -- a function of the edge set alone.  Root hooking with compression on labels_out itself (parent[i] = i to start):
+ *   round        hook: one lane per edge reads the roots of its two ends and, where they differ, runs an agent-scope int32 atomicMin
+ *                on parent[larger root] with the smaller.  compress: every parent[i] is brought to its root by path halving --
+ *                parent[i] <- its ancestor 8 links up, in place -- in ceil(ceil(log2 n) / 3) launches, each of which exits at once when
+ *                the one before found every node at its root: a chain of depth n (a sequentially numbered path after its first hook)
+ *                costs log launches, not n loads in one lane.  1 + ceil(ceil(log2 n) / 3) launches per round, 4 bytes per node.
+ *   stale reads  parent[x] <= x always, so there is no cycle.  Within a launch a lane may read a value of parent[x] that another
+ *                compute unit has since lowered; every value it can read is a start-of-round root of x's true component (hook) or an
+ *                ancestor of x (compress), and the kernels are correct for each (csrc/graph_traverse.hip, the file comment).
+ *   stop         the first round that hooks nothing.  max_rounds 0: the library's choice, 2 * ceil(log2(max(n, 2))) + 8 rounded up to
+ *                whole groups.  Still hooking after max_rounds rounds: NGPDE_ERR_STATE (check_every > 0), never a silent partial answer.
+ *   rounds_out   device int32[2], nullable: [0] the rounds run, the confirming one included; [1] 1 if the last enqueued round still
+ *                hooked (what a caller with check_every 0 reads instead of the status).
+ *   workspace    ngpde_coo_components_workspace_bytes(n_nodes) = 256 (the control block); 0 for sizes it refuses.  8-byte aligned. */
+size_t ngpde_coo_components_workspace_bytes(int64_t n_nodes);
+int32_t ngpde_coo_components(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t max_rounds,
+                             int32_t check_every, int32_t *labels_out, int32_t *rounds_out, void *workspace, size_t workspace_bytes,
+                             ngpde_stream_t stream);
+
+/* connected_components, the ranking (src/NeuralGraphPDE.jl:4, :16): from labels (what ngpde_coo_components wrote; anything else is
+ * NGPDE_ERR_INVALID_ARGUMENT, found on the device) the components ranked by their smallest member.  A root flag and an exclusive scan
+ * (rocPRIM) give rank_out int32[n_nodes]; ONE stable radix sort of the ranks with the node ids gives order_out int32[n_nodes], the nodes
+ * grouped by component and ascending inside it; ptr_out int32[n_nodes + 1] (upper bound; count + 1 written) by bisection, component k =
+ * order_out[ptr_out[k] .. ptr_out[k + 1] - 1]; sizes_out int32[n_nodes] (upper bound; count written); count_out HOST.  per_graph_out
+ * device int32[n_graphs], nullable: the components of every graph of a batch (graph_of device int32[n_nodes], 0-based, any order, or
+ * NULL with n_graphs 1; an id outside 0 : n_graphs - 1 is NGPDE_ERR_INVALID_ARGUMENT).  Temporaries from hipMalloc.  Synchronises. */
+int32_t ngpde_components_rank(int64_t n_nodes, const int32_t *labels, int32_t n_graphs, const int32_t *graph_of, int32_t *rank_out,
+                              int32_t *sizes_out, int32_t *order_out, int32_t *ptr_out, int64_t *count_out, int32_t *per_graph_out,
+                              ngpde_stream_t stream);
+
+/* The rows plan of a list (src/NeuralGraphPDE.jl:4, :16: what the level loop below walks): the by-node rows of csrc/coo_rows.h -- the one
+ * definition ngpde_coo_sample_neighbors and ngpde_coo_adjacency_count use -- grouped by source (NGPDE_DIR_OUT) or target (NGPDE_DIR_IN),
+ * COO order inside a row.  row_ptr_out int32[n_nodes + 1]; row_other_out int32[n_edges] = the 0-BASED other end of every row entry.
+ * Temporaries from hipMalloc.  Synchronises. */
+int32_t ngpde_coo_rows(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t dir,
+                       int32_t *row_ptr_out, int32_t *row_other_out, ngpde_stream_t stream);
+
+/* gdistances (src/NeuralGraphPDE.jl:4, :16): breadth-first levels by a level-synchronous PULL on 64-bit source masks.  (row_ptr_a,
+ * other_a, nnz_a) and, for both directions, a second set b (NULL, NULL, 0 otherwise) are rows plans: node v is reached at a level from
+ * the other ends of its rows that were reached at the level before.  Following edges s -> t needs the rows grouped by TARGET
+ * (NGPDE_DIR_IN), against them the rows grouped by source, either way both.
+ *   sources      device int64[n_sources] with `index_base`, any order, repeats allowed
+ *   separate 0   dist_out int32[n]: the edges on a shortest path from the NEAREST source (all sources share mask bit 0; one pass)
+ *   separate 1   dist_out int32[n_sources][n]: row i from source i alone; 64 sources per pass (bit b = source b of the pass),
+ *                ceil(n_sources / 64) passes
+ *   max_hops     nodes further than max_hops edges, and unreachable ones, get -1; negative: no bound (needs check_every > 0)
+ *   level        ONE launch, a lane per node: it ORs the frontier words of the other ends of its rows, masks with ~seen[v], stores the
+ *                level for every new bit, writes seen[v] and next[v] -- a lane writes its own node only: no atomics, no race, the same
+ *                bits whatever the geometry.  A row of NGPDE_HOP_WAVE_ROW entries or more is walked by the whole wave with an OR
+ *                across its lanes: a hub row does not serialise on one lane.  A node that has seen every source reads no row.
+ *   workspace    ngpde_csr_hop_distance_workspace_bytes(n) = 3 * (8 n rounded up to 256) + 256: seen and the double-buffered frontier,
+ *                24 bytes per node, and the control block; 0 for sizes it refuses.  8-byte aligned.
+ * A row pointer or entry outside the lists is NGPDE_ERR_DIMENSION_MISMATCH (nothing is read through it). */
+#define NGPDE_HOP_WAVE_ROW 64
+size_t ngpde_csr_hop_distance_workspace_bytes(int64_t n);
+int32_t ngpde_csr_hop_distance(int64_t n, int64_t nnz_a, const int32_t *row_ptr_a, const int32_t *other_a, int64_t nnz_b,
+                               const int32_t *row_ptr_b, const int32_t *other_b, int64_t n_sources, const int64_t *sources, int32_t index_base,
+                               int32_t separate, int64_t max_hops, int32_t check_every, int32_t *dist_out, void *workspace,
+                               size_t workspace_bytes, ngpde_stream_t stream);
+
+/* neighborhood (src/NeuralGraphPDE.jl:4, :16): nodes_out int64[n] (upper bound) = the nodes with dist[i] >= 0, ascending, with
+ * `index_base`; n_out HOST.  The flags -> exclusive scan -> scatter of csrc/coo_compact.h.  Temporaries from hipMalloc.  Synchronises. */
+int32_t ngpde_hop_reached_nodes(int64_t n, const int32_t *dist, int32_t index_base, int64_t *nodes_out, int64_t *n_out, ngpde_stream_t stream);
+
 /* GNOConv message (src/layers.jl:527-530): K_e = reshape(phi_out[:, e], cout, cin) column-major,
  * m_e = K_e * h[:, s_e].  k: [E][cin*cout] p order (element o + cout*i), h: [N][cin], m: [E][cout]. */
 int32_t ngpde_gno_contract_forward(const ngpde_graph_t *g, int32_t cin, int32_t cout, const float *k, const float *h,

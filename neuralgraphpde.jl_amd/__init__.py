@@ -24,6 +24,7 @@ from .matrices import (GraphMatrix, adjacency_matrix, has_isolated_nodes, khop_a
                        normalized_laplacian, scaled_laplacian)
 from .queries import (AdjacencyList, adjacency_list, has_edge, inneighbors, intersect, neighbors, outneighbors, random_walk_pe)
 from .linsolve import CGInfo, cg_solve
+from .traversal import Components, connected_components, hop_distance, is_connected, neighborhood, split_components
 from . import dist, optim, synth
 
 
@@ -46,4 +47,5 @@ __all__ = [
     "GraphMatrix", "adjacency_matrix", "laplacian_matrix", "normalized_laplacian", "scaled_laplacian", "laplacian_lambda_max", "khop_adj",
     "has_isolated_nodes", "cg_solve", "CGInfo",
     "AdjacencyList", "adjacency_list", "has_edge", "neighbors", "inneighbors", "outneighbors", "intersect", "random_walk_pe",
+    "Components", "connected_components", "is_connected", "split_components", "hop_distance", "neighborhood",
 ]

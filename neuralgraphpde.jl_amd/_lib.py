@@ -222,6 +222,13 @@ SIGNATURES = {
     "ngpde_coo_intersect": (_i32, [_i64, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
     "ngpde_csr_random_walk_pe_workspace_bytes": (_sz, [_i64, _i32]),
     "ngpde_csr_random_walk_pe": (_i32, [_i64, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "ngpde_coo_components_workspace_bytes": (_sz, [_i64]),
+    "ngpde_coo_components": (_i32, [_i64, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ngpde_components_rank": (_i32, [_i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _vp]),
+    "ngpde_coo_rows": (_i32, [_i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "ngpde_csr_hop_distance_workspace_bytes": (_sz, [_i64]),
+    "ngpde_csr_hop_distance": (_i32, [_i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "ngpde_hop_reached_nodes": (_i32, [_i64, _vp, _i32, _vp, C.POINTER(_i64), _vp]),
     "ngpde_gno_contract_forward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_gno_contract_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_gno_apply_supported": (_i32, [_i32, _i32]),

@@ -1,7 +1,7 @@
 // device_scratch.h -- the host-side kit of the files that work on device lists (graph_device.hip, graph_ops.hip, graph_edit.hip,
-// graph_query.hip, graph_matrix.hip, sampling.hip, neighbors.hip, readout.hip; coo_compact.h and coo_rows.h stand on it): the
+// graph_query.hip, graph_traverse.hip, graph_matrix.hip, sampling.hip, neighbors.hip, readout.hip; coo_compact.h and coo_rows.h stand on it): the
 // temporaries of one call, the launch sizing, the rocPRIM size-query-then-run call, the eight flag words of a call with their one
-// read-back, the argument checks of a COO list, and the bisection the kernels share.  Everything here has internal linkage.
+// read-back, the word that names the smallest offending id, the argument checks of a COO list, and the bisection the kernels share.  Everything here has internal linkage.
 #pragma once
 
 #include <algorithm>
@@ -93,6 +93,22 @@ int32_t check_coo(const char *fn, int64_t n_nodes, int64_t n_edges, const int32_
   NGPDE_REQUIRE(n_edges == 0 || n_nodes > 0, NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: %lld edges on a graph without nodes", fn,
                 (long long)n_edges);
   return NGPDE_OK;
+}
+
+// The smallest id reported wins: the word holds the complement of the order-preserving map of the signed id to unsigned, so that
+// atomicMax keeps the smallest id and 0 means "none".
+__device__ __forceinline__ void report_offender(unsigned long long *word, int64_t v) {
+  unsigned long long enc = (unsigned long long)v ^ (1ull << 63);
+  if (enc == ~0ull) enc = ~0ull - 1;
+  atomicMax(word, ~enc);
+}
+inline int64_t decode_offender(unsigned long long w) { return (int64_t)((~w) ^ (1ull << 63)); }
+
+// is the stream being captured into a HIP graph?  (no read-back and no allocation then)
+inline bool capturing(hipStream_t stream) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
+  return cs != hipStreamCaptureStatusNone;
 }
 
 // first position of the ascending list that is >= v

@@ -35,25 +35,10 @@ constexpr int kWave = 64;
 constexpr int kRwFixedBytes = 256;                       // the flag words of ngpde_csr_random_walk_pe, at the end of its workspace
 constexpr size_t kRwWorkspaceCap = (size_t)256 << 20;    // what the library's own choice of `block` keeps the two state buffers under
 
-// The smallest id reported wins: the word holds the complement of the order-preserving map of the signed id to unsigned, so that
-// atomicMax keeps the smallest id and 0 means "none".
-__device__ __forceinline__ void report_offender(unsigned long long *word, int64_t v) {
-  unsigned long long enc = (unsigned long long)v ^ (1ull << 63);
-  if (enc == ~0ull) enc = ~0ull - 1;
-  atomicMax(word, ~enc);
-}
-inline int64_t decode_offender(unsigned long long w) { return (int64_t)((~w) ^ (1ull << 63)); }
-
 inline unsigned long long offender_of(const int32_t *h) {
   unsigned long long w;
   std::memcpy(&w, h + fOffender, sizeof(w));
   return w;
-}
-
-bool capturing(hipStream_t stream) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
-  return cs != hipStreamCaptureStatusNone;
 }
 
 int32_t check_sizes(const char *fn, int64_t n_nodes, int64_t n_edges) {
