@@ -39,6 +39,9 @@ int32_t fail(int32_t code, const char *fmt, ...);
     if (!(cond)) return ::ngpde::fail(code, __VA_ARGS__);                                         \
   } while (0)
 
+// is the stream being captured into a HIP graph?  (no read-back, no allocation and no event wait / record then; persistent_plan.hip)
+bool capturing(hipStream_t stream);
+
 // One direction of the derived graph.  Row r lists the edges whose target (by_target) or source
 // (by_source) is r, in the caller's COO order (stable counting sort), so segmented sums visit
 // contributions in the same order as NNlib's serial scatter over the COO list.
@@ -262,7 +265,6 @@ struct NodePersistBwd {
   bool no_latch = false;       // the caller latches the fault word in its next kernel (node.hip: the slab reduction)
 };
 const unsigned *node_persistent_abort_word(const NodePersist *ps);   // the abort word of the plan's persistent launches
-bool node_persistent_supported(const ngpde_graph *g, int d, int act, bool with_bwd);
 int node_persistent_mode(const ngpde_graph *g, int d, int act, bool with_bwd);   // 0 none, 1 one tile per workgroup, 2 tile pairs, 3 tile rounds
 // graphs the modes above refuse because a tile does not fit the handle's halo lists (hubs): can the hub geometry be tried?  (Whether
 // every tile fits ITS caps is found out by node_persistent_setup(..., hub = true), which returns NGPDE_ERR_UNSUPPORTED otherwise.)
@@ -275,7 +277,7 @@ bool node_wait_lists_fit(const ngpde_graph *g);
 void node_persistent_free(NodePersist *ps);
 int32_t launch_node_fwd_persistent(const NodePersistFwd &a, hipStream_t stream);
 int32_t launch_node_bwd_persistent(const NodePersistBwd &a, hipStream_t stream);
-// The bracket of every persistent launch (node_persistent.hip): enter, launch, latch, leave.  Persistent launches of one process
+// The bracket of every persistent launch (persistent_plan.hip): enter, launch, latch, leave.  Persistent launches of one process
 // take turns per device: enter() takes the device's turnstile lock and makes `stream` wait for the previous persistent launch on the
 // device, then zeroes the plan's sync arena and, under NGPDE_DEBUG_FORCE_ABORT=1 (tests only), sets its abort word; latch() enqueues
 // fault |= abort word (skipped by a caller that latches in its own next kernel); leave() records this launch and releases the lock.

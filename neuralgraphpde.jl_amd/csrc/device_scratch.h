@@ -104,13 +104,6 @@ __device__ __forceinline__ void report_offender(unsigned long long *word, int64_
 }
 inline int64_t decode_offender(unsigned long long w) { return (int64_t)((~w) ^ (1ull << 63)); }
 
-// is the stream being captured into a HIP graph?  (no read-back and no allocation then)
-inline bool capturing(hipStream_t stream) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
-  return cs != hipStreamCaptureStatusNone;
-}
-
 // first position of the ascending list that is >= v
 template <class T>
 __device__ __forceinline__ int64_t lower_bound_dev(const T *__restrict__ a, int64_t m, T v) {

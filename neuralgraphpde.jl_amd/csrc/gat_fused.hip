@@ -1409,30 +1409,30 @@ inline GatSync gat_sync(const NodePersist &ps) {
   y.nbr = ps.nbr; y.flags = ps.sync; y.abort_word = sync_abort_word(ps.sync, ps.n_tiles);
   return y;
 }
+// The persistent solver's kernel table: forward or adjoint, heads (1, 2, else 4), one member or a batch.  The residency query and both
+// launchers read it.
+template <bool FWD, int H>
+auto gat_node_kernel_h(bool batch) {
+  if constexpr (FWD) return batch ? gat_node_fwd_persistent_batch_kernel<H> : gat_node_fwd_persistent_kernel<H>;
+  else return batch ? gat_node_bwd_persistent_batch_kernel<H> : gat_node_bwd_persistent_kernel<H>;
+}
+template <bool FWD>
+auto gat_node_kernel(int heads, bool batch) {
+  return heads == 1 ? gat_node_kernel_h<FWD, 1>(batch) : heads == 2 ? gat_node_kernel_h<FWD, 2>(batch) : gat_node_kernel_h<FWD, 4>(batch);
+}
 }  // namespace
 
 size_t gat_node_dscore_elems(const ngpde_graph *g) { return (size_t)g->n_sched * kSlotWidth * 4; }
 
 bool gat_node_persistent_supported(const ngpde_graph *g, int heads, int c) {
   if (switch_on(Switch::NoPersistent) || !gat_layer_fused_supported(g, GD, heads, c)) return false;
-  int dev = 0, cus = 0, occ = 1 << 30;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-  auto take = [&](auto kernel) {   // every workgroup spins for its neighbours: all of them must be resident
-    int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, kThreads, 0) != hipSuccess) o = 0;
-    occ = std::min(occ, o);
-  };
-  switch (heads) {
-    case 1: take(gat_node_fwd_persistent_kernel<1>); take(gat_node_bwd_persistent_kernel<1>);
-            take(gat_node_fwd_persistent_batch_kernel<1>); take(gat_node_bwd_persistent_batch_kernel<1>); break;
-    case 2: take(gat_node_fwd_persistent_kernel<2>); take(gat_node_bwd_persistent_kernel<2>);
-            take(gat_node_fwd_persistent_batch_kernel<2>); take(gat_node_bwd_persistent_batch_kernel<2>); break;
-    default: take(gat_node_fwd_persistent_kernel<4>); take(gat_node_bwd_persistent_kernel<4>);
-             take(gat_node_fwd_persistent_batch_kernel<4>); take(gat_node_bwd_persistent_batch_kernel<4>); break;
+  std::vector<const void *> kernels;   // every workgroup spins for its neighbours: all of them must be resident
+  for (const bool batch : {false, true}) {
+    kernels.push_back(reinterpret_cast<const void *>(gat_node_kernel<true>(heads, batch)));
+    kernels.push_back(reinterpret_cast<const void *>(gat_node_kernel<false>(heads, batch)));
   }
   const int nt = g->n_sched / kTileRows;
-  if (nt < 1 || nt > cus * occ) return false;
+  if (nt < 1 || nt > resident_workgroups(kernels, kThreads, 0)) return false;
   if (!node_wait_lists_fit(g)) return false;   // (node_persistent_setup refuses a tile that neighbours more than 63 others)
   // both directions' schedules must name the same node at every position (the solver keeps per-thread state across the halves):
   // compared on the device ONCE per handle (a launch on the NULL stream and a blocking copy -- not something to repeat per solve)
@@ -1477,20 +1477,7 @@ int32_t launch_gat_node_fwd(const GatNodeFwd &a, hipStream_t stream) {
   k.n_members = a.n_members; k.flag_stride = sync_slot_stride(ps.n_tiles); k.xs_stride = a.xs_stride; k.yz_stride = a.yz_stride;
   k.alpha_stride = a.alpha_stride;
   const dim3 grid(ps.n_tiles), block(kThreads);
-#define NGPDE_GN_LAUNCH(KERNEL) launch_timed(KERNEL, grid, block, 0, stream, a.ev_start, a.ev_stop, k);
-  if (a.n_members > 1) {
-    switch (a.heads) {
-      case 1: NGPDE_GN_LAUNCH(gat_node_fwd_persistent_batch_kernel<1>) break;
-      case 2: NGPDE_GN_LAUNCH(gat_node_fwd_persistent_batch_kernel<2>) break;
-      default: NGPDE_GN_LAUNCH(gat_node_fwd_persistent_batch_kernel<4>) break;
-    }
-  } else {
-    switch (a.heads) {
-      case 1: NGPDE_GN_LAUNCH(gat_node_fwd_persistent_kernel<1>) break;
-      case 2: NGPDE_GN_LAUNCH(gat_node_fwd_persistent_kernel<2>) break;
-      default: NGPDE_GN_LAUNCH(gat_node_fwd_persistent_kernel<4>) break;
-    }
-  }
+  launch_timed(gat_node_kernel<true>(a.heads, a.n_members > 1), grid, block, 0, stream, a.ev_start, a.ev_stop, k);
   NGPDE_LAUNCH_CHECK("gat_node_fwd_persistent_kernel");
   if ((st = turn.latch())) return st;
   return turn.leave();
@@ -1522,20 +1509,7 @@ int32_t launch_gat_node_bwd(const GatNodeBwd &a, hipStream_t stream) {
   k.alpha_stride = a.alpha_stride; k.dal_stride = (size_t)g->n_nodes * a.heads;
   NGPDE_REQUIRE(ident || a.yz, NGPDE_ERR_INVALID_ARGUMENT, "persistent GAT adjoint: the saved y / z rows are missing");
   const dim3 grid(ps.n_tiles), block(kThreads);
-  if (a.n_members > 1) {
-    switch (a.heads) {
-      case 1: NGPDE_GN_LAUNCH(gat_node_bwd_persistent_batch_kernel<1>) break;
-      case 2: NGPDE_GN_LAUNCH(gat_node_bwd_persistent_batch_kernel<2>) break;
-      default: NGPDE_GN_LAUNCH(gat_node_bwd_persistent_batch_kernel<4>) break;
-    }
-  } else {
-    switch (a.heads) {
-      case 1: NGPDE_GN_LAUNCH(gat_node_bwd_persistent_kernel<1>) break;
-      case 2: NGPDE_GN_LAUNCH(gat_node_bwd_persistent_kernel<2>) break;
-      default: NGPDE_GN_LAUNCH(gat_node_bwd_persistent_kernel<4>) break;
-    }
-  }
-#undef NGPDE_GN_LAUNCH
+  launch_timed(gat_node_kernel<false>(a.heads, a.n_members > 1), grid, block, 0, stream, a.ev_start, a.ev_stop, k);
   NGPDE_LAUNCH_CHECK("gat_node_bwd_persistent_kernel");
   if ((st = turn.latch())) return st;
   hipLaunchKernelGGL(gat_layer_reduce_kernel, dim3(67), dim3(1024), 0, stream, a.slab_dw, ps.n_tiles, a.slab_db, ps.n_tiles, a.slab_u, a.dwt,

@@ -29,9 +29,9 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
+#include <initializer_list>
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 #include "persistent_gcn_tile.h"
@@ -1535,49 +1535,65 @@ __global__ __launch_bounds__(kThreads, 4) void node_bwd_persistentKP_kernel(cons
 
 }  // namespace
 
-// ---- host side -----------------------------------------------------------------------------------------------------------
+// ---- host side (wait lists, setup, launch bracket: persistent_plan.hip) ------------------------------------------------------
 
-// Wait lists: tile T waits for every tile that owns a row of T's halo in either direction, and for every tile whose halo holds
-// a row of T (they read what T is about to overwrite).  [n_tiles][kNbrStride], -1 padded.  Returns false when a list overflows.
-static bool build_wait_lists(const ngpde_graph *g, std::vector<int> &out) {
-  const int nt = g->n_sched / kTileRows;
-  std::vector<int32_t> order((size_t)g->n_nodes);
-  if (!g->h_order.empty()) order = g->h_order;
-  else if (hipMemcpy(order.data(), g->order, order.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
-  std::vector<int32_t> tile_of((size_t)g->n_nodes, 0);
-  for (int64_t pos = 0; pos < g->n_nodes; ++pos) tile_of[order[pos]] = (int32_t)(pos / kTileRows);
-  std::vector<std::vector<int>> nb(nt);
-  for (const Csr *c : {&g->by_t, &g->by_s}) {
-    std::vector<int2> halo((size_t)nt * kHaloCap), info(nt);
-    if (hipMemcpy(halo.data(), c->halo, halo.size() * sizeof(int2), hipMemcpyDeviceToHost) != hipSuccess) return false;
-    if (hipMemcpy(info.data(), c->tile_info, info.size() * sizeof(int2), hipMemcpyDeviceToHost) != hipSuccess) return false;
-    for (int t = 0; t < nt; ++t)
-      for (int k = kTileRows; k < info[t].x; ++k) {
-        const int u = tile_of[halo[(size_t)t * kHaloCap + k].x];
-        if (u == t) continue;
-        nb[t].push_back(u);
-        nb[u].push_back(t);
-      }
-  }
-  out.assign((size_t)nt * kNbrStride, -1);
-  for (int t = 0; t < nt; ++t) {
-    std::sort(nb[t].begin(), nb[t].end());
-    nb[t].erase(std::unique(nb[t].begin(), nb[t].end()), nb[t].end());
-    if ((int)nb[t].size() > kNbrStride - 1) return false;
-    for (size_t k = 0; k < nb[t].size(); ++k) out[(size_t)t * kNbrStride + k] = nb[t][k];
-  }
-  return true;
-}
+// The kernel table: every instantiation a plan can launch, by family.  The residency queries below and the two launchers read the
+// same entries, so the grid a query admits is measured on the kernels the launch will pick from.
+namespace {
+enum class Family { OneTile, OneTileW, Hub, Pair, Interleaved, Rounds, RoundsW };   // Rounds: pipelined (KP); RoundsW: plain (K), weighted graphs
+using FwdKernel = void (*)(const PFwdK);
+using BwdKernel = void (*)(const PBwdK);
 
-bool node_wait_lists_fit(const ngpde_graph *g) {
-  if (!g) return false;
-  std::lock_guard<std::mutex> lock(g->lazy_mu);
-  if (g->wait_lists_fit < 0) {
-    std::vector<int> lists;
-    g->wait_lists_fit = build_wait_lists(g, lists) ? 1 : 0;
+template <int ACT, bool TAPE>
+FwdKernel fwd_kernel_of(Family f) {
+  constexpr bool kSlots2 = !(TAPE && ACT != NGPDE_ACT_RELU);   // the two-slot kernels keep no pre-activation tape
+  switch (f) {
+    case Family::OneTile: return node_fwd_persistent_kernel<ACT, TAPE>;
+    case Family::OneTileW: return node_fwd_persistent_kernel<ACT, TAPE, true>;
+    case Family::Hub: return node_fwd_persistent_kernel<ACT, TAPE, false, true>;
+    case Family::Pair: if constexpr (kSlots2) return node_fwd_persistent2_kernel<ACT, TAPE, true>; else return nullptr;
+    case Family::Interleaved: if constexpr (kSlots2) return node_fwd_persistent2_kernel<ACT, TAPE, false>; else return nullptr;
+    case Family::Rounds: return node_fwd_persistentKP_kernel<ACT, TAPE>;
+    case Family::RoundsW: return node_fwd_persistentK_kernel<ACT, TAPE>;
   }
-  return g->wait_lists_fit == 1;
+  return nullptr;
 }
+template <int ACT>
+BwdKernel bwd_kernel_of(Family f) {
+  switch (f) {
+    case Family::OneTile: return node_bwd_persistent_kernel<ACT>;
+    case Family::OneTileW: return node_bwd_persistent_kernel<ACT, true>;
+    case Family::Hub: return node_bwd_persistent_kernel<ACT, false, true>;
+    case Family::Pair: return ACT == NGPDE_ACT_RELU ? node_bwd_persistent2_kernel<true> : nullptr;
+    case Family::Interleaved: return node_bwd_persistent2_kernel<false>;   // (one kernel, the activation a launch argument)
+    case Family::Rounds: return node_bwd_persistentKP_kernel<ACT>;
+    case Family::RoundsW: return node_bwd_persistentK_kernel<ACT>;
+  }
+  return nullptr;
+}
+// null: the family has no such kernel
+FwdKernel fwd_kernel(Family f, bool relu, bool tape) {
+  if (relu) return tape ? fwd_kernel_of<NGPDE_ACT_RELU, true>(f) : fwd_kernel_of<NGPDE_ACT_RELU, false>(f);
+  return tape ? fwd_kernel_of<-1, true>(f) : fwd_kernel_of<-1, false>(f);
+}
+BwdKernel bwd_kernel(Family f, bool relu) { return relu ? bwd_kernel_of<NGPDE_ACT_RELU>(f) : bwd_kernel_of<-1>(f); }
+
+// co-residency of the spin-waiting workgroups: over EVERY kernel of the families a plan of this kind can launch
+int resident_tiles(std::initializer_list<Family> families) {
+  std::vector<const void *> kernels;
+  const auto add = [&](auto kernel) {
+    const void *k = reinterpret_cast<const void *>(kernel);
+    if (k && std::find(kernels.begin(), kernels.end(), k) == kernels.end()) kernels.push_back(k);
+  };
+  for (Family f : families)
+    for (int relu = 0; relu < 2; ++relu) {
+      add(fwd_kernel(f, relu, true));
+      add(fwd_kernel(f, relu, false));
+      add(bwd_kernel(f, relu));
+    }
+  return resident_workgroups(kernels, kThreads, 0);
+}
+}  // namespace
 
 // Can the plan run as two persistent launches?  (same conditions as the pre-scaled replayed plan, plus: d = 64, unweighted, ALL
 // workgroups co-resident.)  0: no.  1: one tile per workgroup (graphs of at most CUs x occupancy tiles).  2: two tiles per
@@ -1587,43 +1603,12 @@ int node_persistent_mode(const ngpde_graph *g, int d, int act, bool with_bwd) {
   if (!g || d != PD || !fused_prescaled_supported(g, d)) return 0;
   const bool weighted = g->by_t.slot_w || g->by_s.slot_w;
   if (weighted && !(g->by_t.slot_w && g->by_s.slot_w)) return 0;
-  int dev = 0, cus = 0, occ_f = 0, occ_b = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  // co-residency of the spin-waiting workgroups: the minimum over EVERY instantiation a plan of this kind can launch
-  occ_f = occ_b = 1 << 30;
-  auto take = [&](int &acc, auto kernel) {
-    int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, kThreads, 0) != hipSuccess) o = 0;
-    acc = std::min(acc, o);
-  };
-  take(occ_f, node_fwd_persistent_kernel<NGPDE_ACT_RELU, true>);
-  take(occ_f, node_fwd_persistent_kernel<NGPDE_ACT_RELU, false>);
-  take(occ_f, node_fwd_persistent_kernel<-1, false>);
-  take(occ_f, node_fwd_persistent2_kernel<NGPDE_ACT_RELU, true, false>);
-  take(occ_f, node_fwd_persistent2_kernel<NGPDE_ACT_RELU, false, false>);
-  take(occ_f, node_fwd_persistent2_kernel<-1, false, false>);
-  take(occ_f, node_fwd_persistent2_kernel<NGPDE_ACT_RELU, true, true>);
-  take(occ_f, node_fwd_persistent2_kernel<NGPDE_ACT_RELU, false, true>);
-  take(occ_f, node_fwd_persistent2_kernel<-1, false, true>);
-  take(occ_b, node_bwd_persistent_kernel<NGPDE_ACT_RELU>);
-  take(occ_b, node_bwd_persistent_kernel<-1>);
-  take(occ_f, node_fwd_persistent_kernel<-1, true>);
-  take(occ_b, node_bwd_persistent2_kernel<false>);
-  take(occ_b, node_bwd_persistent2_kernel<true>);
-  const int nt = g->n_sched / kTileRows, resident = cus * std::min(occ_f, occ_b);
+  const int nt = g->n_sched / kTileRows, resident = resident_tiles({Family::OneTile, Family::Interleaved, Family::Pair});
   if (nt < 1) return 0;
   if (weighted) {
     // edge weights: one tile per workgroup on the WGT one-tile kernels (slot weights in the LDS of one W; W1 as register fragments)
     // where the graph is one wave of workgroups, else the tile-round kernels (they keep one W in LDS anyway)
-    int ow_f = 1 << 30, ow_b = 1 << 30;
-    take(ow_f, node_fwd_persistent_kernel<NGPDE_ACT_RELU, true, true>);
-    take(ow_f, node_fwd_persistent_kernel<NGPDE_ACT_RELU, false, true>);
-    take(ow_f, node_fwd_persistent_kernel<-1, true, true>);
-    take(ow_f, node_fwd_persistent_kernel<-1, false, true>);
-    take(ow_b, node_bwd_persistent_kernel<NGPDE_ACT_RELU, true>);
-    take(ow_b, node_bwd_persistent_kernel<-1, true>);
-    if (nt <= cus * std::min(ow_f, ow_b) && !switch_on(Switch::WeightedTileRounds)) return 1;
+    if (nt <= resident_tiles({Family::OneTileW}) && !switch_on(Switch::WeightedTileRounds)) return 1;
     return nt <= kMaxTileRoundsW * resident ? 3 : 0;
   }
   if (nt <= resident) return 1;
@@ -1633,23 +1618,9 @@ int node_persistent_mode(const ngpde_graph *g, int d, int act, bool with_bwd) {
   return 0;
 }
 int node_persistent_rounds(const ngpde_graph *g) {   // K of mode 3: tiles per workgroup
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  int occ = 1 << 30;
-  auto take = [&](auto kernel) {
-    int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, kThreads, 0) != hipSuccess) o = 0;
-    occ = std::min(occ, o);
-  };
-  take(node_fwd_persistentKP_kernel<NGPDE_ACT_RELU, true>); take(node_fwd_persistentKP_kernel<NGPDE_ACT_RELU, false>);
-  take(node_fwd_persistentKP_kernel<-1, true>); take(node_fwd_persistentKP_kernel<-1, false>);
-  take(node_bwd_persistentKP_kernel<NGPDE_ACT_RELU>); take(node_bwd_persistentKP_kernel<-1>);
-  if (g->by_t.slot_w) {   // (weighted graphs: the K kernels)
-    take(node_fwd_persistentK_kernel<NGPDE_ACT_RELU, true>); take(node_fwd_persistentK_kernel<NGPDE_ACT_RELU, false>);
-    take(node_fwd_persistentK_kernel<-1, true>); take(node_fwd_persistentK_kernel<-1, false>);
-    take(node_bwd_persistentK_kernel<NGPDE_ACT_RELU>); take(node_bwd_persistentK_kernel<-1>);
-  }
-  const int nt = g->n_sched / kTileRows, resident = cus * occ;
+  // (weighted graphs: the K kernels as well)
+  const int resident = g->by_t.slot_w ? resident_tiles({Family::Rounds, Family::RoundsW}) : resident_tiles({Family::Rounds});
+  const int nt = g->n_sched / kTileRows;
   if (resident < 1) return 0;
   const int k = (nt + resident - 1) / resident;
   // (the K kernels' occupancy can be lower than what node_persistent_mode assumed from the one-tile kernels: a k beyond what the
@@ -1658,191 +1629,14 @@ int node_persistent_rounds(const ngpde_graph *g) {   // K of mode 3: tiles per w
   if (k > (g->by_t.slot_w ? kMaxTileRoundsW : kMaxTileRounds)) return 0;
   return k;
 }
-bool node_persistent_supported(const ngpde_graph *g, int d, int act, bool with_bwd) { return node_persistent_mode(g, d, act, with_bwd) == 1; }
 
 bool node_persistent_hub_possible(const ngpde_graph *g, int d) {
   if (switch_on(Switch::NoHalo) || switch_on(Switch::NoPersistent)) return false;   // (NO_HALO asks for the per-row global gather everywhere)
   if (!g || d != PD || !g->has_norm || !g->self_loops || ((g->by_t.slot_w || g->by_s.slot_w) && !g->w_coo)) return false;
   if (g->by_t.halo_ok && g->by_s.halo_ok) return false;   // the 96-row geometry takes it
-  int dev = 0, cus = 0, occ = 1 << 30;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-  auto take = [&](auto kernel) {
-    int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, kThreads, 0) != hipSuccess) o = 0;
-    occ = std::min(occ, o);
-  };
-  take(node_fwd_persistent_kernel<NGPDE_ACT_RELU, true, false, true>); take(node_fwd_persistent_kernel<NGPDE_ACT_RELU, false, false, true>);
-  take(node_fwd_persistent_kernel<-1, true, false, true>); take(node_fwd_persistent_kernel<-1, false, false, true>);
-  take(node_bwd_persistent_kernel<NGPDE_ACT_RELU, false, true>); take(node_bwd_persistent_kernel<-1, false, true>);
   const int nt = g->n_sched / kTileRows;
-  return nt >= 1 && nt <= cus * occ;
+  return nt >= 1 && nt <= resident_tiles({Family::Hub});
 }
-
-// The hub geometry's lists of one direction, from the CSR lists and the schedule order (host copies, or downloaded from a
-// device-built handle).  Slot numbering: own rows first (slot k = k-th row of the tile), every other row in order of first reference
-// (rows of the tile in order, entries in CSR order).  false: some tile exceeds a cap.
-// The hub geometry's own tile partition.  The handle's locality order grows clusters breadth-first, which puts a hub and the hubs
-// next to it into ONE tile (Cora-shaped graphs: > 256 distinct rows).  Here the nodes are dealt out worst first, in order of
-// descending degree: the n_tiles highest-degree nodes one per tile, every further node to the tile whose set of referenced rows H_t
-// (members and all their neighbours, both directions) grows least by it, among the tiles with a free slot that stay within the cap
-// with one row reserved per slot still free; a node with more than kSlotWidth entries (a long row: summed by the whole workgroup, two
-// barriers each) prefers the tiles with the fewest long rows.  Leaves end up with the hub they hang on (growth 0), hubs apart from each
-// other: at BASELINE config 1's shape one long row per tile at most, 94 referenced rows per tile on average, 131 at most (the first form
-// of this deal -- least growth only -- put the hubs next to each other: the tile with most of them took 17 k cycles per phase and every
-// other tile waited for it; the second -- hubs apart, least growth -- filled the largest hub's tile to the cap of 255 rows).  Returns the positions -> node order (tile t = positions 32 t ..), or an empty vector when some node fits nowhere.
-static std::vector<int32_t> hub_partition(int64_t n, const std::vector<int32_t> rp[2], const std::vector<int32_t> cl[2], bool balance) {
-  const int nt = (int)((n + kTileRows - 1) / kTileRows);
-  std::vector<std::vector<int32_t>> nb((size_t)n);
-  for (int64_t v = 0; v < n; ++v) {
-    std::vector<int32_t> &a = nb[(size_t)v];
-    for (int dir = 0; dir < 2; ++dir)
-      for (int32_t p = rp[dir][v]; p < rp[dir][v + 1]; ++p)
-        if (cl[dir][p] != v) a.push_back(cl[dir][p]);
-    std::sort(a.begin(), a.end());
-    a.erase(std::unique(a.begin(), a.end()), a.end());
-  }
-  std::vector<int32_t> by_degree((size_t)n);
-  for (int64_t v = 0; v < n; ++v) by_degree[(size_t)v] = (int32_t)v;
-  std::stable_sort(by_degree.begin(), by_degree.end(), [&](int32_t a, int32_t b) { return nb[a].size() > nb[b].size(); });
-  std::vector<uint8_t> in_h((size_t)nt * n, 0);
-  std::vector<int> h_size(nt, 0), cap(nt, kTileRows);
-  std::vector<int> n_long(nt, 0);
-  std::vector<std::vector<int32_t>> members(nt);
-  cap[nt - 1] = (int)(n - (int64_t)kTileRows * (nt - 1));
-  int64_t dealt = 0;
-  for (int32_t v : by_degree) {
-    const bool is_long = (int)nb[v].size() > kSlotWidth;
-    int best_t = -1, best_score = 1 << 30, best_l = 1 << 30;
-    if (dealt < nt) best_t = (int)dealt;   // the n_tiles highest-degree nodes: one per tile
-    ++dealt;
-    for (int t = 0; t < nt && dealt > nt; ++t) {
-      if ((int)members[t].size() >= cap[t]) continue;
-      const uint8_t *h = in_h.data() + (size_t)t * n;
-      int inc = h[v] ? 0 : 1;
-      for (int32_t w : nb[v]) inc += h[w] ? 0 : 1;
-      if (h_size[t] + inc + (cap[t] - (int)members[t].size() - 1) > kHubHalo) continue;
-      const int l = is_long ? n_long[t] : 0;
-      // growth, plus a sixteenth of what the tile already references: every tile waits for the slowest one each phase, so a node that
-      // would add one row to a tile of 200 goes to a tile of 60 even if it adds three there (largest tile at config 1's shape: 255 -> 131
-      // rows, the average unchanged at 94)
-      const int score = balance ? 16 * inc + h_size[t] : 512 * inc + h_size[t];   // (not balanced: least growth, then the smaller tile)
-      if (l < best_l || (l == best_l && score < best_score)) { best_t = t; best_score = score; best_l = l; }
-    }
-    if (best_t < 0) return {};
-    uint8_t *h = in_h.data() + (size_t)best_t * n;
-    if (!h[v]) { h[v] = 1; ++h_size[best_t]; }
-    for (int32_t w : nb[v])
-      if (!h[w]) { h[w] = 1; ++h_size[best_t]; }
-    if (h_size[best_t] + (cap[best_t] - (int)members[best_t].size() - 1) > kHubHalo) return {};   // (a seed beyond the cap: a hub of > ~224 neighbours)
-    members[best_t].push_back(v);
-    n_long[best_t] += is_long ? 1 : 0;
-  }
-  std::vector<int32_t> order;
-  order.reserve((size_t)n);
-  for (int t = 0; t < nt; ++t) order.insert(order.end(), members[t].begin(), members[t].end());
-  return order;
-}
-
-struct HubHost {
-  std::vector<int32_t> halo;
-  std::vector<float> w;   // beside `slots` (weighted graphs), else empty
-  std::vector<uint8_t> slots, longs;
-  std::vector<int2> rows;
-  std::vector<int4> info;
-};
-static bool host_csr(const ngpde_graph *g, const Csr &c, std::vector<int32_t> &rowptr, std::vector<int32_t> &col) {
-  const int64_t n = g->n_nodes, m = g->n_edges;
-  if (!c.h_rowptr.empty()) { rowptr = c.h_rowptr; col = c.h_col; return true; }
-  rowptr.resize((size_t)n + 1); col.resize((size_t)std::max<int64_t>(m, 1));
-  if (hipMemcpy(rowptr.data(), c.rowptr, rowptr.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
-  if (m > 0 && hipMemcpy(col.data(), c.col, (size_t)m * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
-  return true;
-}
-// w_csr: the entries' edge weights in the list's own order, or NULL
-static bool build_hub_lists(int64_t n, int nt, const std::vector<int32_t> &rowptr, const std::vector<int32_t> &col,
-                            const std::vector<int32_t> &order, HubHost &o, const float *w_csr = nullptr) {
-  o.halo.assign((size_t)nt * kHubHalo, 0);
-  o.slots.assign((size_t)nt * kHubList, 0);
-  if (w_csr) o.w.assign((size_t)nt * kHubList, 0.f);
-  o.longs.assign((size_t)nt * kTileRows, 0);
-  o.rows.assign((size_t)nt * kTileRows, make_int2(0, 0));
-  o.info.assign((size_t)nt, make_int4(0, 0, 0, 0));
-  std::vector<int32_t> slot_of((size_t)n, -1), stamp((size_t)n, -1);
-  for (int t = 0; t < nt; ++t) {
-    int count = kTileRows, bytes = 0, n_long = 0;
-    for (int k = 0; k < kTileRows; ++k) {
-      const int64_t pos = (int64_t)t * kTileRows + k;
-      if (pos >= n) continue;
-      const int32_t v = order[pos];
-      stamp[v] = t; slot_of[v] = k;
-      o.halo[(size_t)t * kHubHalo + k] = v;
-    }
-    for (int k = 0; k < kTileRows; ++k) {
-      const int64_t pos = (int64_t)t * kTileRows + k;
-      if (pos >= n) break;
-      const int32_t v = order[pos];
-      const int32_t rs = rowptr[v], deg = rowptr[v + 1] - rs;
-      if (bytes + deg > kHubList) return false;
-      o.rows[(size_t)pos] = make_int2(bytes, deg);
-      if (deg > kSlotWidth) o.longs[(size_t)t * kTileRows + n_long++] = (uint8_t)k;
-      for (int j = 0; j < deg; ++j) {
-        const int32_t u = col[rs + j];
-        if (stamp[u] != t) {
-          if (count >= kHubHalo) return false;
-          stamp[u] = t; slot_of[u] = count;
-          o.halo[(size_t)t * kHubHalo + count++] = u;
-        }
-        o.slots[(size_t)t * kHubList + bytes + j] = (uint8_t)slot_of[u];
-        if (w_csr) o.w[(size_t)t * kHubList + bytes + j] = w_csr[rs + j];
-      }
-      bytes = (bytes + deg + 3) & ~3;
-      if (bytes > kHubList) return false;
-    }
-    o.info[t] = make_int4(count, (bytes + 15) & ~15, n_long, 0);
-  }
-  return true;
-}
-
-// Host only (no device call): the hub geometry's tile partition of a graph given as its two CSR lists -- what node_persistent_setup
-// would use -- so that a caller (and the CPU tests, tests/test_hub_partition.py) can ask whether a graph with hubs fits the persistent
-// solver.  order[32 t + k] = the node in row k of tile t; tile_rows[2 t + dir] = the distinct rows tile t references in direction
-// dir (0: lists by target, 1: by source; members included).
-}  // namespace ngpde
-extern "C" int32_t ngpde_hub_partition_host(int64_t n_nodes, const int32_t *rowptr_by_target, const int32_t *col_by_target,
-                                            const int32_t *rowptr_by_source, const int32_t *col_by_source, int32_t *order,
-                                            int32_t *tile_rows) {
-  using namespace ngpde;
-  NGPDE_REQUIRE(n_nodes > 0 && rowptr_by_target && rowptr_by_source && order, NGPDE_ERR_INVALID_ARGUMENT,
-                "ngpde_hub_partition_host: n_nodes > 0, both row pointer arrays and `order` are required");
-  const int nt = (int)((n_nodes + kTileRows - 1) / kTileRows);
-  NGPDE_REQUIRE(nt <= kHubNbr, NGPDE_ERR_UNSUPPORTED, "persistent solver, hub geometry: at most %d tiles, one per workgroup", kHubNbr);
-  std::vector<int32_t> rp[2], cl[2];
-  const int32_t *rps[2] = {rowptr_by_target, rowptr_by_source}, *cls[2] = {col_by_target, col_by_source};
-  for (int dir = 0; dir < 2; ++dir) {
-    rp[dir].assign(rps[dir], rps[dir] + n_nodes + 1);
-    const int64_t m = rp[dir][(size_t)n_nodes];
-    NGPDE_REQUIRE(rp[dir][0] == 0 && m >= 0 && (m == 0 || cls[dir]), NGPDE_ERR_INVALID_ARGUMENT, "ngpde_hub_partition_host: CSR list %d is malformed", dir);
-    for (int64_t v = 0; v < n_nodes; ++v)
-      NGPDE_REQUIRE(rp[dir][v] <= rp[dir][v + 1], NGPDE_ERR_INVALID_ARGUMENT, "ngpde_hub_partition_host: row pointers of list %d decrease at row %lld", dir, (long long)v);
-    cl[dir].assign(cls[dir], cls[dir] + m);
-    for (int64_t e = 0; e < m; ++e)
-      NGPDE_REQUIRE(cl[dir][e] >= 0 && cl[dir][e] < n_nodes, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_hub_partition_host: list %d names node %d of %lld", dir, cl[dir][e], (long long)n_nodes);
-  }
-  std::vector<int32_t> ord = hub_partition(n_nodes, rp, cl, true);
-  if ((int64_t)ord.size() != n_nodes) ord = hub_partition(n_nodes, rp, cl, false);
-  NGPDE_REQUIRE((int64_t)ord.size() == n_nodes, NGPDE_ERR_UNSUPPORTED,
-                "persistent solver, hub geometry: no partition into 32-row tiles of at most %d referenced rows each (a node of more than %d distinct in+out neighbours, or tiles that do not close)",
-                kHubHalo, kHubHalo - kTileRows);
-  HubHost hh[2];
-  NGPDE_REQUIRE(build_hub_lists(n_nodes, nt, rp[0], cl[0], ord, hh[0]) && build_hub_lists(n_nodes, nt, rp[1], cl[1], ord, hh[1]), NGPDE_ERR_UNSUPPORTED,
-                "persistent solver, hub geometry: a tile references more than %d distinct rows or holds more than %d entries", kHubHalo, kHubList);
-  std::copy(ord.begin(), ord.end(), order);
-  if (tile_rows)
-    for (int t = 0; t < nt; ++t)
-      for (int dir = 0; dir < 2; ++dir) tile_rows[2 * t + dir] = hh[dir].info[(size_t)t].x;
-  return NGPDE_OK;
-}
-namespace ngpde {
 
 // ---- a plan's own-first slot tables (OwnFirst, common.h) ----------------------------------------------------------------------------
 namespace {
@@ -1929,152 +1723,6 @@ void own_first_tables_free(OwnFirst *of) {
   *of = OwnFirst();
 }
 
-int32_t node_persistent_setup(const ngpde_graph *g, const float *coef_host, NodePersist *ps, bool pair, bool hub) {
-  std::vector<int> lists;
-  const int nt = g->n_sched / kTileRows;
-  ps->hub = false;
-  if (hub) {
-    NGPDE_REQUIRE(!pair && nt <= kHubNbr, NGPDE_ERR_UNSUPPORTED, "persistent solver, hub geometry: at most %d tiles, one per workgroup", kHubNbr);
-    std::vector<int32_t> rp[2], cl[2];
-    NGPDE_REQUIRE(host_csr(g, g->by_t, rp[0], cl[0]) && host_csr(g, g->by_s, rp[1], cl[1]), NGPDE_ERR_HIP, "download of the CSR lists failed");
-    // (the balanced deal can strand the last nodes when a hub's tile is near the cap and only its own leaves would fit it: then least growth alone)
-    std::vector<int32_t> order = hub_partition(g->n_nodes, rp, cl, true);
-    if ((int64_t)order.size() != g->n_nodes) order = hub_partition(g->n_nodes, rp, cl, false);
-    NGPDE_REQUIRE((int64_t)order.size() == g->n_nodes, NGPDE_ERR_UNSUPPORTED,
-                  "persistent solver, hub geometry: no partition into 32-row tiles of at most %d referenced rows each (a node of more than %d distinct in+out neighbours, or tiles that do not close)",
-                  kHubHalo, kHubHalo - kTileRows);
-    // edge weights: the handle's COO copy through each list's entry -> COO position map
-    std::vector<float> wcsr[2];
-    if (g->w_coo && g->n_edges > 0) {
-      std::vector<float> wc((size_t)g->n_edges);
-      NGPDE_HIP_CHECK(hipMemcpy(wc.data(), g->w_coo, wc.size() * sizeof(float), hipMemcpyDeviceToHost));
-      const Csr *cs[2] = {&g->by_t, &g->by_s};
-      for (int dir = 0; dir < 2; ++dir) {
-        std::vector<int32_t> eid = cs[dir]->h_eid;
-        if (eid.empty()) {
-          eid.resize((size_t)g->n_edges);
-          NGPDE_HIP_CHECK(hipMemcpy(eid.data(), cs[dir]->eid, eid.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        }
-        wcsr[dir].resize((size_t)g->n_edges);
-        for (int64_t e = 0; e < g->n_edges; ++e) wcsr[dir][(size_t)e] = wc[(size_t)eid[(size_t)e]];
-      }
-    }
-    HubHost hh[2];
-    NGPDE_REQUIRE(build_hub_lists(g->n_nodes, nt, rp[0], cl[0], order, hh[0], wcsr[0].empty() ? nullptr : wcsr[0].data()) &&
-                      build_hub_lists(g->n_nodes, nt, rp[1], cl[1], order, hh[1], wcsr[1].empty() ? nullptr : wcsr[1].data()),
-                  NGPDE_ERR_UNSUPPORTED,
-                  "persistent solver, hub geometry: a tile references more than %d distinct rows or holds more than %d entries", kHubHalo, kHubList);
-    // the partition's schedule: {node, 0, 0, bits of c[node]} per position, -1 padded
-    std::vector<float> cnode((size_t)g->n_nodes);
-    NGPDE_HIP_CHECK(hipMemcpy(cnode.data(), g->c, cnode.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<int4> hsched((size_t)nt * kTileRows, make_int4(-1, 0, 0, 0));
-    for (int64_t pos = 0; pos < g->n_nodes; ++pos) {
-      int4 e = make_int4(order[pos], 0, 0, 0);
-      std::memcpy(&e.w, &cnode[order[pos]], 4);
-      hsched[(size_t)pos] = e;
-    }
-    // wait lists: symmetric closure over both directions, up to 255 tiles, position 63 left free (that lane watches the abort word)
-    std::vector<int32_t> tile_of((size_t)g->n_nodes, 0);
-    for (int64_t pos = 0; pos < g->n_nodes; ++pos) tile_of[order[pos]] = (int32_t)(pos / kTileRows);
-    std::vector<std::vector<int>> nb(nt);
-    for (const HubHost &h : hh)
-      for (int t = 0; t < nt; ++t)
-        for (int k = kTileRows; k < h.info[t].x; ++k) {
-          const int u = tile_of[h.halo[(size_t)t * kHubHalo + k]];
-          if (u == t) continue;
-          nb[t].push_back(u);
-          nb[u].push_back(t);
-        }
-    lists.assign((size_t)nt * kHubNbr, -1);
-    for (int t = 0; t < nt; ++t) {
-      std::sort(nb[t].begin(), nb[t].end());
-      nb[t].erase(std::unique(nb[t].begin(), nb[t].end()), nb[t].end());
-      NGPDE_REQUIRE((int)nb[t].size() <= kHubNbr - 1, NGPDE_ERR_UNSUPPORTED, "persistent solver, hub geometry: a wait list exceeds %d tiles", kHubNbr - 1);
-      for (size_t k = 0; k < nb[t].size(); ++k) lists[(size_t)t * kHubNbr + (k < 63 ? k : k + 1)] = nb[t][k];
-    }
-    for (int dir = 0; dir < 2; ++dir) {
-      NodePersist::HubLists &L = ps->hub_lists[dir];
-      const HubHost &h = hh[dir];
-      auto up = [&](auto **dst, const auto &v) -> int32_t {
-        NGPDE_HIP_CHECK(hipMalloc((void **)dst, std::max<size_t>(v.size(), 1) * sizeof(v[0])));
-        NGPDE_HIP_CHECK(hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-        return NGPDE_OK;
-      };
-      int32_t st;
-      if ((st = up(&L.halo, h.halo)) || (st = up(&L.slots, h.slots)) || (st = up(&L.rows, h.rows)) || (st = up(&L.info, h.info)) ||
-          (st = up(&L.longs, h.longs)) || (st = up(&L.sched, hsched)))
-        return st;
-      if (!h.w.empty() && (st = up(&L.w, h.w))) return st;
-    }
-    ps->hub = true;
-  } else {
-    NGPDE_REQUIRE(build_wait_lists(g, lists), NGPDE_ERR_UNSUPPORTED, "persistent solver: a tile's wait list exceeds %d tiles", kNbrStride);
-  }
-  ps->n_tiles = nt;
-  ps->pair_wgs = 0;
-  if (pair) {
-    // workgroup b holds tiles t = xcd_tile(b, W) and t + W (W = ceil(nt / 2)): half a schedule apart, so never neighbours on a
-    // graph with any locality -- but it is checked: a tile waiting for its own workgroup's other tile would wait for a flag that is
-    // published only after the wait
-    const int W = (nt + 1) / 2;
-    for (int t = 0; t + W < nt; ++t)
-      for (int k = 0; k < kNbrStride; ++k)
-        NGPDE_REQUIRE(lists[(size_t)t * kNbrStride + k] != t + W, NGPDE_ERR_UNSUPPORTED,
-                      "persistent solver: tiles %d and %d of one workgroup are neighbours", t, t + W);
-    ps->pair_wgs = W;
-  }
-  NGPDE_HIP_CHECK(hipMalloc((void **)&ps->nbr, lists.size() * sizeof(int)));
-  NGPDE_HIP_CHECK(hipMemcpy(ps->nbr, lists.data(), lists.size() * sizeof(int), hipMemcpyHostToDevice));
-  // flag words: one 128-byte line per tile and slot (two slots: the interleaved kernels), + one line for the abort word; zeroed
-  // (by a kernel) before every launch
-  ps->sync_bytes = (size_t)(2 * nt + 1) * 128;
-  NGPDE_HIP_CHECK(hipMalloc((void **)&ps->sync, ps->sync_bytes));
-  NGPDE_HIP_CHECK(hipMemset(ps->sync, 0, ps->sync_bytes));
-  NGPDE_HIP_CHECK(hipMalloc((void **)&ps->coef, 90 * sizeof(float)));
-  NGPDE_HIP_CHECK(hipMemcpy(ps->coef, coef_host, 90 * sizeof(float), hipMemcpyHostToDevice));
-  // the sticky fault word lives in pinned, device-mapped HOST memory: the latch kernel writes it through the device pointer, and
-  // every later entry of the plan can look at it without a synchronisation (ngpde_node_gcn2_forward / _backward refuse to go on)
-  NGPDE_HIP_CHECK(hipHostMalloc((void **)&ps->fault_host, 128, hipHostMallocMapped));
-  *ps->fault_host = 0u;
-  NGPDE_HIP_CHECK(hipHostGetDevicePointer((void **)&ps->fault, const_cast<unsigned *>(ps->fault_host), 0));
-  NGPDE_HIP_CHECK(hipMalloc((void **)&ps->stats, (size_t)nt * 2 * sizeof(int)));
-  NGPDE_HIP_CHECK(hipMemset(ps->stats, 0, (size_t)nt * 2 * sizeof(int)));
-  return NGPDE_OK;
-}
-
-void node_persistent_free(NodePersist *ps) {
-  if (ps->nbr) (void)hipFree(ps->nbr);
-  if (ps->sync) (void)hipFree(ps->sync);
-  if (ps->fault_host) (void)hipHostFree(const_cast<unsigned *>(ps->fault_host));
-  ps->fault_host = nullptr;
-  if (ps->coef) (void)hipFree(ps->coef);
-  if (ps->stats) (void)hipFree(ps->stats);
-  ps->stats = nullptr;
-  for (NodePersist::HubLists &L : ps->hub_lists) {
-    if (L.halo) (void)hipFree(L.halo);
-    if (L.slots) (void)hipFree(L.slots);
-    if (L.rows) (void)hipFree(L.rows);
-    if (L.info) (void)hipFree(L.info);
-    if (L.longs) (void)hipFree(L.longs);
-    if (L.sched) (void)hipFree(L.sched);
-    if (L.w) (void)hipFree(L.w);
-    L = NodePersist::HubLists();
-  }
-  ps->hub = false;
-  ps->nbr = nullptr; ps->sync = nullptr; ps->fault = nullptr; ps->coef = nullptr;
-}
-
-namespace {
-// NGPDE_DEBUG_FORCE_ABORT=1 (tests only): the launch starts with its abort word set, i.e. every workgroup gives up at its first wait
-__global__ void set_word_kernel(unsigned *w, unsigned v) {
-  if (threadIdx.x == 0) *w = v;
-}
-// fault |= abort word of the launch that just ran (sticky, read by ngpde_node_fault)
-__global__ void latch_fault_kernel(const unsigned *abort_word, unsigned *fault) {
-  if (threadIdx.x == 0 && *abort_word != 0) *fault = 1u;
-}
-}  // namespace
-const unsigned *node_persistent_abort_word(const NodePersist *ps) { return ps->sync ? sync_abort_word(ps->sync, ps->n_tiles) : nullptr; }
 namespace {
 // of: the plan's own-first tables (forward only, dir 0), or NULL
 TileMeta make_meta(const Csr &c, const NodePersist &ps, int dir, const OwnFirst *of = nullptr) {
@@ -2094,67 +1742,14 @@ TileMeta make_meta(const Csr &c, const NodePersist &ps, int dir, const OwnFirst 
   NGPDE_STAMP_SET(m, kStampPersistent, 0);
   return m;
 }
-}  // namespace
-
-// A persistent launch needs ALL its workgroups resident, and two of them in flight on one device (two plans on two streams) can
-// starve each other of residency until both time out.  Inside one process they are therefore made to take turns: every persistent
-// launch first makes its stream wait for the event recorded behind the previous persistent launch on that device, whatever stream
-// that one ran on.  (Nothing can be done about another PROCESS on the same device: one rank per GPU, include/ngpde.h.)
-namespace {
-struct Turnstile {
-  std::mutex mu;
-  hipEvent_t last[16] = {};
-  bool used[16] = {};
-};
-Turnstile &turnstile() {
-  static Turnstile t;
-  return t;
+// the family a launch belongs to (m: its make_meta, whose slot_w says "weighted" for every geometry but the hub's)
+Family family_of(int k_tiles, const TileMeta &m, bool hub, bool pair, bool interleave) {
+  if (k_tiles > 0) return m.slot_w ? Family::RoundsW : Family::Rounds;
+  if (hub) return Family::Hub;
+  if (m.slot_w) return Family::OneTileW;
+  return pair ? Family::Pair : interleave ? Family::Interleaved : Family::OneTile;
 }
 }  // namespace
-
-int32_t PersistentTurn::enter(const NodePersist &p, hipStream_t s) {
-  ps = &p;
-  stream = s;
-  NGPDE_HIP_CHECK(hipGetDevice(&dev));
-  if (dev >= 0 && dev < 16) {
-    Turnstile &t = turnstile();
-    t.mu.lock();
-    held = true;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
-    if (cs == hipStreamCaptureStatusNone && t.used[dev]) NGPDE_HIP_CHECK(hipStreamWaitEvent(stream, t.last[dev], 0));
-  }
-  int32_t st;
-  if ((st = launch_zero(p.sync, p.sync_bytes, stream))) return st;
-  if (switch_on(Switch::DebugForceAbort)) hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(64), 0, stream, sync_abort_word(p.sync, p.n_tiles), 1u);
-  return NGPDE_OK;
-}
-int32_t PersistentTurn::latch() {
-  hipLaunchKernelGGL(latch_fault_kernel, dim3(1), dim3(64), 0, stream, sync_abort_word(ps->sync, ps->n_tiles), ps->fault);
-  NGPDE_LAUNCH_CHECK("latch_fault_kernel");
-  return NGPDE_OK;
-}
-int32_t PersistentTurn::leave() {
-  if (!held) return NGPDE_OK;
-  Turnstile &t = turnstile();
-  int32_t st = NGPDE_OK;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
-  if (cs == hipStreamCaptureStatusNone) {
-    if (!t.last[dev] && hipEventCreateWithFlags(&t.last[dev], hipEventDisableTiming) != hipSuccess) st = fail(NGPDE_ERR_HIP, "hipEventCreate failed");
-    if (st == NGPDE_OK && hipEventRecord(t.last[dev], stream) != hipSuccess) st = fail(NGPDE_ERR_HIP, "hipEventRecord failed");
-    if (st == NGPDE_OK) t.used[dev] = true;
-  }
-  held = false;
-  t.mu.unlock();
-  return st;
-}
-PersistentTurn::~PersistentTurn() {
-  if (held) {
-    held = false;
-    turnstile().mu.unlock();
-  }
-}
 
 int32_t launch_node_fwd_persistent(const NodePersistFwd &a, hipStream_t stream) {
   const ngpde_graph *g = a.g;
@@ -2172,62 +1767,39 @@ int32_t launch_node_fwd_persistent(const NodePersistFwd &a, hipStream_t stream) 
   k.pair_wgs = a.pair ? ps.pair_wgs : 0;
   k.cf = ps.coef;
   NGPDE_REQUIRE(!a.pair || (ps.pair_wgs > 0 && !a.interleave && a.n_members == 1), NGPDE_ERR_STATE, "tile-pair launch without its setup");
-  k.k_tiles = a.k_tiles; k.state = a.state;
-  const auto launch = [&](auto kernel, dim3 grid) { launch_timed(kernel, grid, dim3(kThreads), 0, stream, a.ev_start, a.ev_stop, k); };
+  k.k_tiles = a.k_tiles; k.state = a.state; k.ztape = a.ztape;
+  const Family family = family_of(a.k_tiles, k.m, ps.hub, a.pair, a.interleave);
+  const bool relu = a.act == NGPDE_ACT_RELU;
+  dim3 grid(a.pair ? ps.pair_wgs : ps.n_tiles);
+  const char *name = "node_fwd_persistent_kernel";
   if (a.k_tiles > 0) {   // tile rounds: K tiles per workgroup, state in memory
+    // unweighted: the pipelined kernel; weighted: the plain tile-round kernel (the slot weights leave no LDS for the pipeline)
     NGPDE_REQUIRE(ps.pair_wgs > 0 && a.n_members == 1 && a.state, NGPDE_ERR_STATE, "tile-round launch without its setup");
     NGPDE_REQUIRE(a.k_tiles <= kMaxTileRounds, NGPDE_ERR_STATE, "tile rounds: at most %d tiles per workgroup", kMaxTileRounds);
-    k.pair_wgs = ps.pair_wgs; k.ztape = a.ztape;
+    k.pair_wgs = ps.pair_wgs;
     if ((st = launch_zero(a.state + a.row_elems, 6 * a.row_elems * sizeof(float), stream))) return st;   // k_0 .. k_5 start from zero
-    const dim3 gridk(ps.pair_wgs);
+    grid = dim3(ps.pair_wgs);
     NGPDE_REQUIRE(!k.m.slot_w || a.k_tiles <= kMaxTileRoundsW, NGPDE_ERR_STATE, "weighted tile rounds: at most %d tiles per workgroup", kMaxTileRoundsW);
-    // unweighted: the pipelined kernel; weighted: the plain tile-round kernel (the slot weights leave no LDS for the pipeline)
-#define NGPDE_PFK_LAUNCH(AA, TT) \
-    launch(k.m.slot_w ? node_fwd_persistentK_kernel<AA, TT> : node_fwd_persistentKP_kernel<AA, TT>, gridk);
-    if (a.tape && a.act == NGPDE_ACT_RELU) { NGPDE_PFK_LAUNCH(NGPDE_ACT_RELU, true) }
-    else if (a.tape) { NGPDE_PFK_LAUNCH(-1, true) }
-    else if (a.act == NGPDE_ACT_RELU) { NGPDE_PFK_LAUNCH(NGPDE_ACT_RELU, false) }
-    else { NGPDE_PFK_LAUNCH(-1, false) }
-#undef NGPDE_PFK_LAUNCH
-    NGPDE_LAUNCH_CHECK("node_fwd_persistentK_kernel");
-    if (!a.no_latch && (st = turn.latch())) return st;
-    return turn.leave();
-  }
-  NGPDE_REQUIRE(!k.m.slot_w || (!a.pair && !a.interleave && a.n_members == 1), NGPDE_ERR_STATE,
-                "weighted graphs: one tile per workgroup or tile rounds, one member");
-  const dim3 grid(a.pair ? ps.pair_wgs : ps.n_tiles);
-  if (ps.hub) {   // hub geometry: one tile per workgroup and CU
-    NGPDE_REQUIRE(!a.pair && !a.interleave, NGPDE_ERR_STATE, "hub geometry: one tile per workgroup, the members of a batch one after the other");
-    k.ztape = a.ztape;
-    NGPDE_REQUIRE(!a.tape || (a.act == NGPDE_ACT_RELU ? a.masks != nullptr : a.ztape != nullptr), NGPDE_ERR_INVALID_ARGUMENT,
-                  "persistent forward with a tape needs the sign-bit masks (relu) or the pre-activation tape");
-    if (a.tape && a.act == NGPDE_ACT_RELU) launch(node_fwd_persistent_kernel<NGPDE_ACT_RELU, true, false, true>, grid);
-    else if (a.tape) launch(node_fwd_persistent_kernel<-1, true, false, true>, grid);
-    else if (a.act == NGPDE_ACT_RELU) launch(node_fwd_persistent_kernel<NGPDE_ACT_RELU, false, false, true>, grid);
-    else launch(node_fwd_persistent_kernel<-1, false, false, true>, grid);
-    NGPDE_LAUNCH_CHECK("node_fwd_persistent_kernel (hub geometry)");
-    if (!a.no_latch && (st = turn.latch())) return st;
-    return turn.leave();
-  }
-#define NGPDE_PF_LAUNCH(AA, TT)                                                                                  \
-  launch(k.m.slot_w ? node_fwd_persistent_kernel<AA, TT, true>                                                   \
-         : a.pair ? node_fwd_persistent2_kernel<AA, TT, true>                                                    \
-         : a.interleave ? node_fwd_persistent2_kernel<AA, TT, false> : node_fwd_persistent_kernel<AA, TT>, grid);
-  k.ztape = a.ztape;
-  if (a.tape && a.act == NGPDE_ACT_RELU) {
-    NGPDE_REQUIRE(a.masks != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "persistent forward with a relu tape needs the sign-bit masks");
-    NGPDE_PF_LAUNCH(NGPDE_ACT_RELU, true)
-  } else if (a.tape) {
-    NGPDE_REQUIRE(a.ztape != nullptr && !a.interleave && !a.pair, NGPDE_ERR_INVALID_ARGUMENT,
-                  "persistent forward with a tape: activations other than relu keep the pre-activations (one member at a time)");
-    NGPDE_PF_LAUNCH(-1, true)
-  } else if (a.act == NGPDE_ACT_RELU) {
-    NGPDE_PF_LAUNCH(NGPDE_ACT_RELU, false)
+    name = "node_fwd_persistentK_kernel";
   } else {
-    NGPDE_PF_LAUNCH(-1, false)
+    NGPDE_REQUIRE(!k.m.slot_w || (!a.pair && !a.interleave && a.n_members == 1), NGPDE_ERR_STATE,
+                  "weighted graphs: one tile per workgroup or tile rounds, one member");
+    if (family == Family::Hub) {   // hub geometry: one tile per workgroup and CU
+      NGPDE_REQUIRE(!a.pair && !a.interleave, NGPDE_ERR_STATE, "hub geometry: one tile per workgroup, the members of a batch one after the other");
+      NGPDE_REQUIRE(!a.tape || (relu ? a.masks != nullptr : a.ztape != nullptr), NGPDE_ERR_INVALID_ARGUMENT,
+                    "persistent forward with a tape needs the sign-bit masks (relu) or the pre-activation tape");
+      name = "node_fwd_persistent_kernel (hub geometry)";
+    } else if (a.tape && relu) {
+      NGPDE_REQUIRE(a.masks != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "persistent forward with a relu tape needs the sign-bit masks");
+    } else if (a.tape) {
+      NGPDE_REQUIRE(a.ztape != nullptr && !a.interleave && !a.pair, NGPDE_ERR_INVALID_ARGUMENT,
+                    "persistent forward with a tape: activations other than relu keep the pre-activations (one member at a time)");
+    }
   }
-#undef NGPDE_PF_LAUNCH
-  NGPDE_LAUNCH_CHECK("node_fwd_persistent_kernel");
+  const FwdKernel kernel = fwd_kernel(family, relu, a.tape != nullptr);
+  NGPDE_REQUIRE(kernel, NGPDE_ERR_STATE, "persistent forward: no kernel of this form");
+  launch_timed(kernel, grid, dim3(kThreads), 0, stream, a.ev_start, a.ev_stop, k);
+  NGPDE_LAUNCH_CHECK(name);
   if (!a.no_latch && (st = turn.latch())) return st;
   return turn.leave();
 }
@@ -2251,44 +1823,34 @@ int32_t launch_node_bwd_persistent(const NodePersistBwd &a, hipStream_t stream) 
   NGPDE_REQUIRE(!a.pair || (ps.pair_wgs > 0 && !a.interleave && a.n_members == 1 && a.act == NGPDE_ACT_RELU), NGPDE_ERR_STATE,
                 "tile-pair launch without its setup");
   k.k_tiles = a.k_tiles;
-  const auto launch = [&](auto kernel, dim3 grid) { launch_timed(kernel, grid, dim3(kThreads), 0, stream, a.ev_start, a.ev_stop, k); };
+  const Family family = family_of(a.k_tiles, k.m, ps.hub, a.pair, a.interleave);
+  const bool relu = a.act == NGPDE_ACT_RELU;
+  dim3 grid(a.pair ? ps.pair_wgs : ps.n_tiles);
+  const char *name = "node_bwd_persistent_kernel";
+  const char *const need_ztape = "persistent adjoint: activations other than relu need the saved pre-activations";
   if (a.k_tiles > 0) {   // tile rounds
     NGPDE_REQUIRE(ps.pair_wgs > 0 && a.n_members == 1 && a.ubar, NGPDE_ERR_STATE, "tile-round launch without its setup");
     NGPDE_REQUIRE(a.k_tiles <= kMaxTileRounds, NGPDE_ERR_STATE, "tile rounds: at most %d tiles per workgroup", kMaxTileRounds);
-    NGPDE_REQUIRE(a.act == NGPDE_ACT_RELU || a.ztape, NGPDE_ERR_INVALID_ARGUMENT, "persistent adjoint: activations other than relu need the saved pre-activations");
+    NGPDE_REQUIRE(relu || a.ztape, NGPDE_ERR_INVALID_ARGUMENT, "%s", need_ztape);
     k.pair_wgs = ps.pair_wgs;
     if ((st = launch_zero(a.ubar, 5 * a.row_elems * sizeof(float), stream))) return st;   // the stage adjoints start from zero
-    const dim3 gridk(ps.pair_wgs);
+    grid = dim3(ps.pair_wgs);
     NGPDE_REQUIRE(!k.m.slot_w || a.k_tiles <= kMaxTileRoundsW, NGPDE_ERR_STATE, "weighted tile rounds: at most %d tiles per workgroup", kMaxTileRoundsW);
-    if (a.act == NGPDE_ACT_RELU) launch(k.m.slot_w ? node_bwd_persistentK_kernel<NGPDE_ACT_RELU> : node_bwd_persistentKP_kernel<NGPDE_ACT_RELU>, gridk);
-    else launch(k.m.slot_w ? node_bwd_persistentK_kernel<-1> : node_bwd_persistentKP_kernel<-1>, gridk);
-    NGPDE_LAUNCH_CHECK("node_bwd_persistentK_kernel");
-    if (!a.no_latch && (st = turn.latch())) return st;
-    return turn.leave();
-  }
-  NGPDE_REQUIRE(!k.m.slot_w || (!a.pair && !a.interleave && a.n_members == 1), NGPDE_ERR_STATE,
-                "weighted graphs: one tile per workgroup or tile rounds, one member");
-  const dim3 grid(a.pair ? ps.pair_wgs : ps.n_tiles);
-  if (ps.hub) {
-    NGPDE_REQUIRE(!a.pair && !a.interleave, NGPDE_ERR_STATE, "hub geometry: one tile per workgroup, the members of a batch one after the other");
-    NGPDE_REQUIRE(a.act == NGPDE_ACT_RELU || a.ztape, NGPDE_ERR_INVALID_ARGUMENT, "persistent adjoint: activations other than relu need the saved pre-activations");
-    launch(a.act == NGPDE_ACT_RELU ? node_bwd_persistent_kernel<NGPDE_ACT_RELU, false, true> : node_bwd_persistent_kernel<-1, false, true>, grid);
-  } else if (k.m.slot_w) {
-    NGPDE_REQUIRE(a.act == NGPDE_ACT_RELU || a.ztape, NGPDE_ERR_INVALID_ARGUMENT, "persistent adjoint: activations other than relu need the saved pre-activations");
-    launch(a.act == NGPDE_ACT_RELU ? node_bwd_persistent_kernel<NGPDE_ACT_RELU, true> : node_bwd_persistent_kernel<-1, true>, grid);
-  } else if (a.pair) {
-    NGPDE_REQUIRE(a.ubar != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "tile-pair persistent adjoint without its stage-adjoint scratch");
-    launch(node_bwd_persistent2_kernel<true>, grid);
-  } else if (a.interleave) {
-    NGPDE_REQUIRE(a.ubar != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "interleaved persistent adjoint without its stage-adjoint scratch");
-    launch(node_bwd_persistent2_kernel<false>, grid);
-  } else if (a.act != NGPDE_ACT_RELU) {
-    NGPDE_REQUIRE(a.ztape != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "persistent adjoint: activations other than relu need the saved pre-activations");
-    launch(node_bwd_persistent_kernel<-1>, grid);
+    name = "node_bwd_persistentK_kernel";
   } else {
-    launch(node_bwd_persistent_kernel<NGPDE_ACT_RELU>, grid);
+    NGPDE_REQUIRE(!k.m.slot_w || (!a.pair && !a.interleave && a.n_members == 1), NGPDE_ERR_STATE,
+                  "weighted graphs: one tile per workgroup or tile rounds, one member");
+    if (family == Family::Hub)
+      NGPDE_REQUIRE(!a.pair && !a.interleave, NGPDE_ERR_STATE, "hub geometry: one tile per workgroup, the members of a batch one after the other");
+    if (family == Family::Pair) NGPDE_REQUIRE(a.ubar != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "tile-pair persistent adjoint without its stage-adjoint scratch");
+    else if (family == Family::Interleaved)
+      NGPDE_REQUIRE(a.ubar != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "interleaved persistent adjoint without its stage-adjoint scratch");
+    else NGPDE_REQUIRE(relu || a.ztape, NGPDE_ERR_INVALID_ARGUMENT, "%s", need_ztape);
   }
-  NGPDE_LAUNCH_CHECK("node_bwd_persistent_kernel");
+  const BwdKernel kernel = bwd_kernel(family, relu);
+  NGPDE_REQUIRE(kernel, NGPDE_ERR_STATE, "persistent adjoint: no kernel of this form");
+  launch_timed(kernel, grid, dim3(kThreads), 0, stream, a.ev_start, a.ev_stop, k);
+  NGPDE_LAUNCH_CHECK(name);
   if (!a.no_latch && (st = turn.latch())) return st;
   return turn.leave();
 }

@@ -1118,39 +1118,41 @@ struct VmhPlanGeo {
   int grid = 0, turns = 0, s_rows = 64;
   size_t lds = 0;
 };
-template <bool ROUNDS>
-static VmhPlanGeo vmh_geo_of(int n_mats, int units, int cus) {
+// The kernel table: forward or adjoint, every half tile its own workgroup or tile rounds.  vmh_geo_of and both launchers read it.
+template <bool FWD>
+static auto vmh_kernel(bool rounds) {
+  if constexpr (FWD) return rounds ? node_vmh_fwd_kernel<true> : node_vmh_fwd_kernel<false>;
+  else return rounds ? node_vmh_bwd_kernel<true> : node_vmh_bwd_kernel<false>;
+}
+static VmhPlanGeo vmh_geo_of(bool rounds, int n_mats, int units) {
   VmhPlanGeo geo;
-  geo.rounds = ROUNDS;
-  hipFuncAttributes fa{}, ba{};
-  if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(node_vmh_fwd_kernel<ROUNDS>)) != hipSuccess) return geo;
-  if (hipFuncGetAttributes(&ba, reinterpret_cast<const void *>(node_vmh_bwd_kernel<ROUNDS>)) != hipSuccess) return geo;
-  const size_t fixed = std::max(fa.sharedSizeBytes, ba.sharedSizeBytes), cap = 160 * 1024;
+  geo.rounds = rounds;
+  const std::vector<const void *> kernels = {reinterpret_cast<const void *>(vmh_kernel<true>(rounds)), reinterpret_cast<const void *>(vmh_kernel<false>(rounds))};
+  size_t fixed = 0;
+  for (const void *kernel : kernels) {
+    hipFuncAttributes fa{};
+    if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) return geo;
+    fixed = std::max(fixed, fa.sharedSizeBytes);
+  }
+  const size_t cap = 160 * 1024;
   geo.s_rows = 0;
   for (int rows = VROUND; rows >= 64; rows -= 32)
     if (vmh_lds_bytes(n_mats, rows) + fixed <= cap) { geo.s_rows = rows; break; }
   if (geo.s_rows == 0) return geo;
   geo.lds = vmh_lds_bytes(n_mats, geo.s_rows);
-  int occ = 1 << 30;
-  auto take = [&](auto kernel) {
-    int o = 0;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.lds) != hipSuccess) o = 0;
-    else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, VT, geo.lds) != hipSuccess) o = 0;
-    occ = std::min(occ, o);
-  };
-  take(node_vmh_fwd_kernel<ROUNDS>); take(node_vmh_bwd_kernel<ROUNDS>);
-  if (occ < 1 || units < 1) return geo;
-  geo.grid = std::min(units, cus * occ);
+  for (const void *kernel : kernels)
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.lds) != hipSuccess) return geo;
+  const int resident = resident_workgroups(kernels, VT, geo.lds);
+  if (resident < 1 || units < 1) return geo;
+  geo.grid = std::min(units, resident);
   geo.turns = (units + geo.grid - 1) / geo.grid;
   return geo;
 }
 static VmhPlanGeo vmh_geo_uncached(int n_mats, int n_tiles, bool no_rounds) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return VmhPlanGeo();
-  VmhPlanGeo one = vmh_geo_of<false>(n_mats, 2 * n_tiles, cus);
+  VmhPlanGeo one = vmh_geo_of(false, n_mats, 2 * n_tiles);
   if (one.grid > 0 && one.turns == 1) return one;
   if (no_rounds) return VmhPlanGeo();
-  VmhPlanGeo many = vmh_geo_of<true>(n_mats, n_tiles, cus);
+  VmhPlanGeo many = vmh_geo_of(true, n_mats, n_tiles);
   if (many.grid > 0 && many.turns <= kVmhMaxTurns) return many;
   return VmhPlanGeo();
 }
@@ -1238,13 +1240,9 @@ int32_t launch_node_vmh_fwd(const VmhLaunch &a, hipStream_t stream) {
   NGPDE_REQUIRE(geo.grid > 0, NGPDE_ERR_UNSUPPORTED, "node_vmh_fwd_kernel: the graph does not fit the device-resident plan");
   k.m.s_rows = geo.s_rows;
   // (the attribute is per function, and another shape's geometry may have lowered it since)
-  if (geo.rounds) {
-    NGPDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(node_vmh_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.lds));
-    hipLaunchKernelGGL(node_vmh_fwd_kernel<true>, dim3(geo.grid), dim3(VT), geo.lds, stream, k);
-  } else {
-    NGPDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(node_vmh_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.lds));
-    hipLaunchKernelGGL(node_vmh_fwd_kernel<false>, dim3(geo.grid), dim3(VT), geo.lds, stream, k);
-  }
+  const auto kernel = vmh_kernel<true>(geo.rounds);
+  NGPDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.lds));
+  hipLaunchKernelGGL(kernel, dim3(geo.grid), dim3(VT), geo.lds, stream, k);
   NGPDE_LAUNCH_CHECK("node_vmh_fwd_kernel");
   if ((st = turn.latch())) return st;
   return turn.leave();
@@ -1264,13 +1262,9 @@ int32_t launch_node_vmh_bwd(const VmhLaunch &a, hipStream_t stream) {
   const VmhPlanGeo geo = vmh_geo(k.m.n_phi + k.m.n_gam, k.m.n_tiles);
   NGPDE_REQUIRE(geo.grid > 0, NGPDE_ERR_UNSUPPORTED, "node_vmh_bwd_kernel: the graph does not fit the device-resident plan");
   k.m.s_rows = geo.s_rows;
-  if (geo.rounds) {
-    NGPDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(node_vmh_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.lds));
-    hipLaunchKernelGGL(node_vmh_bwd_kernel<true>, dim3(geo.grid), dim3(VT), geo.lds, stream, k);
-  } else {
-    NGPDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(node_vmh_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.lds));
-    hipLaunchKernelGGL(node_vmh_bwd_kernel<false>, dim3(geo.grid), dim3(VT), geo.lds, stream, k);
-  }
+  const auto kernel = vmh_kernel<false>(geo.rounds);
+  NGPDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.lds));
+  hipLaunchKernelGGL(kernel, dim3(geo.grid), dim3(VT), geo.lds, stream, k);
   NGPDE_LAUNCH_CHECK("node_vmh_bwd_kernel");
   if ((st = turn.latch())) return st;
   return turn.leave();

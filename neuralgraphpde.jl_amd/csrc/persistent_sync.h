@@ -1,7 +1,10 @@
 // persistent_sync.h -- the tile hand-off protocol the device-resident solvers share (node_persistent.hip, node_vmh.hip, gat_fused.hip).
-// Host half: the sync arena's layout and the timed launch (the launch bracket is PersistentTurn, common.h).  Device half: the bounded
+// Host half: the sync arena's layout, the timed launch and the residency of a set of kernels (the launch bracket is PersistentTurn,
+// common.h; the wait lists and the rest of the shared host side: persistent_plan.hip).  Device half: the bounded
 // flag poll and the publish; tile_wait_arrive, vmh_wait, gat_wait and the three *_publish build their addresses and call these.
 #pragma once
+
+#include <algorithm>
 
 #include <hip/hip_ext.h>
 
@@ -30,6 +33,21 @@ void launch_timed(void (*kernel)(P...), dim3 grid, dim3 block, unsigned lds, hip
                   A... args) {
   if (ev_start) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, ev_start, ev_stop, 0, args...);
   else hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+}
+
+// Workgroups of `block` threads and `lds` dynamic LDS bytes the current device keeps resident at once whichever of `kernels` they
+// run: CUs x the least occupancy over the list.  Every workgroup of a persistent launch spin-waits on its neighbours, so a plan's
+// grid must fit this number taken over EVERY kernel the plan can later launch: a solver's "does it fit" query and its launcher read
+// the same kernel table.  0: a query failed.
+inline int resident_workgroups(const std::vector<const void *> &kernels, int block, size_t lds) {
+  int dev = 0, cus = 0, occ = kernels.empty() ? 0 : 1 << 30;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+  for (const void *kernel : kernels) {
+    int o = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, block, lds) != hipSuccess) o = 0;
+    occ = std::min(occ, o);
+  }
+  return cus * occ;
 }
 
 // ---- device half ----------------------------------------------------------------------------------------------------------

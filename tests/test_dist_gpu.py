@@ -168,7 +168,7 @@ def test_bench_more_gpus_than_devices_prints_a_skip_record():
 
 def test_two_persistent_plans_on_two_streams_take_turns():
     # two persistent solves in flight on one device could starve each other of residency (every workgroup of a launch must be
-    # resident); inside a process the launches take turns (node_persistent.hip, turnstile): both finish, no fault, same bits as
+    # resident); inside a process the launches take turns (persistent_plan.hip, turnstile): both finish, no fault, same bits as
     # alone
     import ngpde_amd as ng
     from ngpde_amd import _lib, synth as S

@@ -2,7 +2,7 @@
 
 ngpde_node_gcn2_create[_batch] (csrc/node.hip: node_create) solves du/dt = Chain(GCNConv(d => d, act), GCNConv(d => d, act))(u) with
 ONE forward launch and ONE adjoint launch (csrc/node_persistent.hip, persistent_gcn_tile.h, persistent_sync.h) whose 32-row tiles
-hand their rows over through per-tile phase flags.  Which kernels run is decided by node_persistent_mode (node_persistent.hip:1585),
+hand their rows over through per-tile phase flags.  Which kernels run is decided by node_persistent_mode (node_persistent.hip:1601),
 restated:
   0  no persistent plan: NGPDE_NO_PERSISTENT=1, d != 64 (16 / 32 are widened onto 64 first, node.hip:572), or a handle that is not
      fused_prescaled_supported (gcn_fused.hip:859: self loops and halo_ok in BOTH directions); weights in one direction only.
@@ -14,14 +14,14 @@ restated:
   2  tile pairs, resident < tiles <= 2 resident, unweighted, relu when a backward is asked for, neither NGPDE_NO_TILE_PAIRS=1 (which
      returns 0 for EVERY graph beyond resident -- "the old forms", docs/DESIGN_ROUNDS_1_4.md:497 -- not tile rounds) nor
      NGPDE_TILE_ROUNDS=1: node_*_persistent2_kernel<.., PAIR = true> (:569, :901), workgroup b holding tiles t and t + ceil(tiles / 2)
-     (node_persistent_setup, :2016).
+     (node_persistent_setup, persistent_plan.hip:319).
   3  tile rounds, up to kMaxTileRounds = 8 (weighted: 3) tiles per workgroup taking turns, K = ceil(tiles / resident)
-     (node_persistent_rounds, :1635): node_*_persistentKP_kernel (:299, :1333), weighted handles node_*_persistentK_kernel (:197, :1152).
+     (node_persistent_rounds, :1620): node_*_persistentKP_kernel (:299, :1333), weighted handles node_*_persistentK_kernel (:197, :1152).
   A batch of `members` same-structure graphs (create_batch) runs mode 1 with relu only, two members per workgroup on
   node_*_persistent2_kernel<.., PAIR = false>, an odd last member alone; NGPDE_NO_INTERLEAVE=1: member after member on the one-tile
   kernels (node.hip:514).
-The caps: kHaloCap = 96 staged rows and kSlotWidth = 32 list entries per row (common.h:79, :80) in both directions, or the handle is
-not halo_ok; kNbrStride - 1 = 63 tiles in a wait list (persistent_sync.h:16; build_wait_lists, node_persistent.hip:1542), or
+The caps: kHaloCap = 96 staged rows and kSlotWidth = 32 list entries per row (common.h:82, :83) in both directions, or the handle is
+not halo_ok; kNbrStride - 1 = 63 tiles in a wait list (persistent_sync.h:19; build_wait_lists, persistent_plan.hip:50), or
 node_persistent_setup returns NGPDE_ERR_UNSUPPORTED and node_create keeps the pre-scaled replayed plan (node.hip:481).  The self
 loop is not a list entry (the kernels add the own row after the slots, persistent_gcn_tile.h:231), so a row at the slot cap has 32
 constructed in-edges, 33 terms with the loop, and the first row beyond it 33.  A handle beyond a halo or slot cap goes to the hub

@@ -2,7 +2,7 @@
 
 The persistent GCN solver (csrc/node_persistent.hip) takes a handle whose 32-row tiles fit, in BOTH directions, kHaloCap = 96 staged
 rows (32 own rows, padding included, plus the distinct foreign rows) and kSlotWidth = 32 list entries per row, and whose tiles wait
-for at most kNbrStride - 1 = 63 other tiles (build_wait_lists: the symmetric closure over both directions' halos).  The self loop is
+for at most kNbrStride - 1 = 63 other tiles (persistent_plan.hip, build_wait_lists: the symmetric closure over both directions' halos).  The self loop is
 NOT a list entry: the kernels add a row's own row after its slots (persistent_gcn_tile.h: "sum of the row's neighbours (slot bytes,
 in CSR order) + its own row (self loop)"), and build_halo_lists (graph_device.hip) counts rowptr differences of the given edges.  A
 row at the slot cap therefore has 32 constructed in-edges -- 33 terms with the loop -- and the first row beyond it 33; the cases

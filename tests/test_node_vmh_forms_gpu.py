@@ -26,7 +26,7 @@ The regimes inside a launch, each of which a case below claims from host-side ge
   ragged ends     padding rows of the last tile have sched.x < 0 (vctx_init, :196-205); N mod 32 <= 16 leaves the last tile's second
                   half tile without rows; t.inv = 1 / in-degree per ROW under mean, 0 for a row without in-edges (:205).
   geometry        both directions' tiles within kHaloCap = 96 staged rows and kSlotWidth = 32 entries per row; a wait list of at
-                  most 63 tiles (node_persistent.hip: build_wait_lists) -- ngpde_node_vmh_supported answers for all of it, and what
+                  most 63 tiles (persistent_plan.hip: build_wait_lists) -- ngpde_node_vmh_supported answers for all of it, and what
                   it accepts ngpde_node_vmh_create must build (section G).
 
 Every case builds its handle with ngpde_graph_create_device and an explicit node order (tiles = consecutive 32-node runs of it, half
