@@ -777,9 +777,10 @@ int32_t ngpde_csr_random_walk_pe(int64_t n, int64_t nnz, const int32_t *row_ptr,
  * neighborhood work on it): "which nodes hang together?" and "how many edges from the nearest source?".  The conventions are those of
  * the block above: int32 lists with `index_base`, sizes <= 2^31 - 1 (refused beyond), NULL and negative arguments refused before any
  * device call (NGPDE_ERR_INVALID_ARGUMENT), an edge end or a listed node outside the node range NGPDE_ERR_DIMENSION_MISMATCH, found on
- * the device by the launch that does the work without a read or write through it, the SMALLEST offending id named.  Every result is an
- * integer and the only atomics are integer min / or / add, which commute: the bits depend neither on the COO order, the launch
- * geometry nor the run.  Kernel boundaries are the only synchronisation (no spin-wait, no grid barrier).
+ * the device by the launch that does the work without a read or write through it, the SMALLEST offending id named.  Every result but
+ * the shortest paths is an integer and the only atomics are integer min / or / add, which commute: the bits depend neither on the COO
+ * order, the launch geometry nor the run (the float32 shortest paths use no atomic in their rounds and are as reproducible: their
+ * comment).  Kernel boundaries are the only synchronisation (no spin-wait, no grid barrier).
  *   check_every  as in ngpde_csr_cg.  k > 0: rounds / levels are enqueued in groups of k; every launch exits at once when the round /
  *                level before it found nothing, and the host reads the 64-byte control block once per group (the named errors with
  *                the first).  0: nothing is read back, exactly max_rounds rounds / max_hops levels are enqueued, the call allocates
@@ -850,6 +851,64 @@ int32_t ngpde_csr_hop_distance(int64_t n, int64_t nnz_a, const int32_t *row_ptr_
 /* neighborhood (src/NeuralGraphPDE.jl:4, :16): nodes_out int64[n] (upper bound) = the nodes with dist[i] >= 0, ascending, with
  * `index_base`; n_out HOST.  The flags -> exclusive scan -> scatter of csrc/coo_compact.h.  Temporaries from hipMalloc.  Synchronises. */
 int32_t ngpde_hop_reached_nodes(int64_t n, const int32_t *dist, int32_t index_base, int64_t *nodes_out, int64_t *n_out, ngpde_stream_t stream);
+
+/* The rows plan with its COO positions (src/NeuralGraphPDE.jl:4, :16: what the relaxation rounds below walk): ngpde_coo_rows, and
+ * row_eid_out int32[n_edges] = the 0-BASED COO position of every row entry (the `eid` of csrc/coo_rows.h, which ngpde_coo_rows drops):
+ * the weight of an entry is weights[eid], and a tree edge is named by it.  Temporaries from hipMalloc.  Synchronises. */
+int32_t ngpde_coo_rows_eid(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t dir,
+                           int32_t *row_ptr_out, int32_t *row_other_out, int32_t *row_eid_out, ngpde_stream_t stream);
+
+/* dijkstra_shortest_paths / bellman_ford_shortest_paths (src/NeuralGraphPDE.jl:4, :16): weighted shortest paths by synchronous
+ * relaxation rounds (csrc/graph_paths.hip).  The rows plans a and b (NULL, NULL, NULL, 0 otherwise) are those of ngpde_coo_rows_eid for ONE
+ * list, so nnz_b, where given, equals nnz_a = E; the directions are ngpde_csr_hop_distance's (following s -> t: the rows grouped by TARGET).
+ *   weights      device float[nnz_a] in COO order, or NULL: 1 per edge.  +inf and 0 are valid; a NEGATIVE or NaN weight is
+ *                NGPDE_ERR_INVALID_ARGUMENT, found on the device by the launch that gathers the weights into row order (so that a
+ *                round's loads are contiguous), the SMALLEST offending 0-based COO position named; nothing is relaxed through it.
+ *   sources      device int64[n_sources] with `index_base`, any order, repeats allowed; one outside the node range is
+ *                NGPDE_ERR_DIMENSION_MISMATCH, the smallest named
+ *   separate 0   dist_out float[n]: the distance from the NEAREST source.  separate 1: dist_out float[n_sources][n], row i from
+ *                source i alone; NGPDE_SSSP_PASS sources per pass, ceil(n_sources / NGPDE_SSSP_PASS) passes, ONE launch per round
+ *                covers every source of a pass (grid y: groups of NGPDE_SSSP_LANE_SOURCES sources, which a lane relaxes from one read
+ *                of its row; a lane's stores into row i of the [n_sources][n] outputs are contiguous across the wave)
+ *   the result   d = the FIXED POINT of d[v] = min(d[v], min over row entries p of fl32(d[other[p]] + w[p])) that the rounds descend to
+ *                from d0 = 0 at the sources, +inf elsewhere: the greatest one below d0, every value the fp32 length of a walk from
+ *                a source.  fp32 addition is monotone, so d is a pure function of graph, weights and sources, bitwise what a
+ *                float32 heap Dijkstra returns; +inf where unreachable or farther than max_dist (candidates above max_dist are
+ *                dropped: exact, because distances do not decrease along a path; +inf: no bound; negative or NaN refused)
+ *   round        DOUBLE-BUFFERED: round r reads only the values of round r - 1 (two buffers of the workspace alternate; a lane that
+ *                lowers a distance also stores it, and the tree edge, into the caller's arrays, which so hold the last value of
+ *                every cell).  ONE launch, __launch_bounds__(256), a lane per (node, source group): it writes its own cells only
+ *                -- no atomics, no race, the same bits whatever the geometry; the only flag writes are the plain "changed"
+ *                stores into three rotating control words.  A launch exits at once when the round before changed nothing.
+ *                The round buffers are one slab [n][NGPDE_SSSP_LANE_SOURCES] per group of sources (the last group padded): what a
+ *                round gathers, the distances of a row entry's other end for the lane's sources, is one aligned 16-byte load,
+ *                and a wave's own cells are contiguous.
+ *                A row of NGPDE_SSSP_WAVE_ROW entries or more is walked by the whole wave, which reduces (distance, row position)
+ *                lexicographically.  Kernel boundaries are the only synchronisation.
+ *   parents      parent_eid_out / parent_out int32, shaped like dist_out, each nullable: the COO position of the tree edge into
+ *                every node and the 0-based node at its other end; -1 at sources and unreached nodes.  Written only when the node's
+ *                distance STRICTLY decreases; among the equal candidates of one round the first in row order wins (COO order inside
+ *                a row, set a before set b).  Rounds are defined, so parents and rounds_out are pure functions too, every parent
+ *                edge is tight -- fl32(d[parent] + w) == d[v] -- and the parents form a tree also with zero or absorbed weights.
+ *   max_rounds   0: the library's choice, n (a shortest path has fewer than n edges, so n rounds suffice, the confirming one
+ *                included).  Still changing after max_rounds rounds: NGPDE_ERR_STATE (check_every > 0), never a silent partial answer.
+ *   check_every  as above; 0 needs max_rounds > 0 and replays from a HIP graph
+ *   rounds_out   device int32[2], nullable: [0] the rounds run, the confirming one included (the largest over the passes); [1] 1 if
+ *                the last enqueued round of a pass still changed a distance (what a caller with check_every 0 reads)
+ *   workspace    ngpde_csr_shortest_paths_workspace_bytes(n, nnz_a, nnz_b, n_sources, separate) = (2 x 4 n width + 4 nnz_a +
+ *                4 nnz_b, each term rounded up to 256) + 256: the two round buffers of a pass, the weights in row order and the
+ *                control block; width = 1 for one row of dist_out, else min(n_sources, NGPDE_SSSP_PASS) rounded up to a multiple
+ *                of NGPDE_SSSP_LANE_SOURCES; 0 for sizes it refuses.  16-byte aligned.
+ * A row pointer, entry or COO position outside the lists is NGPDE_ERR_DIMENSION_MISMATCH (nothing is read through it). */
+#define NGPDE_SSSP_WAVE_ROW 64
+#define NGPDE_SSSP_PASS 64
+#define NGPDE_SSSP_LANE_SOURCES 4
+size_t ngpde_csr_shortest_paths_workspace_bytes(int64_t n, int64_t nnz_a, int64_t nnz_b, int64_t n_sources, int32_t separate);
+int32_t ngpde_csr_shortest_paths(int64_t n, int64_t nnz_a, const int32_t *row_ptr_a, const int32_t *other_a, const int32_t *eid_a,
+                                 int64_t nnz_b, const int32_t *row_ptr_b, const int32_t *other_b, const int32_t *eid_b, int64_t n_sources,
+                                 const int64_t *sources, int32_t index_base, int32_t separate, const float *weights, float max_dist,
+                                 int32_t max_rounds, int32_t check_every, float *dist_out, int32_t *parent_eid_out, int32_t *parent_out,
+                                 int32_t *rounds_out, void *workspace, size_t workspace_bytes, ngpde_stream_t stream);
 
 /* GNOConv message (src/layers.jl:527-530): K_e = reshape(phi_out[:, e], cout, cin) column-major,
  * m_e = K_e * h[:, s_e].  k: [E][cin*cout] p order (element o + cout*i), h: [N][cin], m: [E][cout]. */

@@ -24,7 +24,8 @@ from .matrices import (GraphMatrix, adjacency_matrix, has_isolated_nodes, khop_a
                        normalized_laplacian, scaled_laplacian)
 from .queries import (AdjacencyList, adjacency_list, has_edge, inneighbors, intersect, neighbors, outneighbors, random_walk_pe)
 from .linsolve import CGInfo, cg_solve
-from .traversal import Components, connected_components, hop_distance, is_connected, neighborhood, split_components
+from .traversal import (Components, ShortestPaths, connected_components, hop_distance, is_connected, neighborhood, shortest_paths,
+                        split_components)
 from . import dist, optim, synth
 
 
@@ -48,4 +49,5 @@ __all__ = [
     "has_isolated_nodes", "cg_solve", "CGInfo",
     "AdjacencyList", "adjacency_list", "has_edge", "neighbors", "inneighbors", "outneighbors", "intersect", "random_walk_pe",
     "Components", "connected_components", "is_connected", "split_components", "hop_distance", "neighborhood",
+    "ShortestPaths", "shortest_paths",
 ]

@@ -40,6 +40,7 @@ _vp, _i32, _i64, _sz, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_f
 
 MLP_MAX_LAYERS = 8
 SAMPLE_LDS_ROW_MAX = 2048          # NGPDE_SAMPLE_LDS_ROW_MAX
+SSSP_WAVE_ROW, SSSP_PASS, SSSP_LANE_SOURCES = 64, 64, 4          # NGPDE_SSSP_WAVE_ROW, NGPDE_SSSP_PASS, NGPDE_SSSP_LANE_SOURCES
 
 
 class Mlp(C.Structure):
@@ -229,6 +230,10 @@ SIGNATURES = {
     "ngpde_csr_hop_distance_workspace_bytes": (_sz, [_i64]),
     "ngpde_csr_hop_distance": (_i32, [_i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _sz, _vp]),
     "ngpde_hop_reached_nodes": (_i32, [_i64, _vp, _i32, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_coo_rows_eid": (_i32, [_i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ngpde_csr_shortest_paths_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i32]),
+    "ngpde_csr_shortest_paths": (_i32, [_i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _f32, _i32, _i32, _vp, _vp,
+                                        _vp, _vp, _vp, _sz, _vp]),
     "ngpde_gno_contract_forward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ngpde_gno_contract_backward": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ngpde_gno_apply_supported": (_i32, [_i32, _i32]),

@@ -463,15 +463,14 @@ int32_t ngpde_components_rank(int64_t n_nodes, const int32_t *labels, int32_t n_
   return NGPDE_OK;
 }
 
-int32_t ngpde_coo_rows(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t dir,
-                       int32_t *row_ptr_out, int32_t *row_other_out, ngpde_stream_t stream_) {
-  NGPDE_RANGE();
-  const char *fn = "ngpde_coo_rows";
-  hipStream_t stream = (hipStream_t)stream_;
+// ngpde_coo_rows and ngpde_coo_rows_eid: the rows of coo_rows.h with the other end of every entry; with_eid keeps the COO positions
+static int32_t coo_rows_entry(const char *fn, bool with_eid, int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t,
+                              int32_t index_base, int32_t dir, int32_t *row_ptr_out, int32_t *row_other_out, int32_t *row_eid_out,
+                              hipStream_t stream) {
   if (int32_t st = check_coo(fn, n_nodes, n_edges, s, t)) return st;
   NGPDE_REQUIRE(dir == NGPDE_DIR_OUT || dir == NGPDE_DIR_IN, NGPDE_ERR_INVALID_ARGUMENT, "%s: dir %d is neither NGPDE_DIR_OUT nor NGPDE_DIR_IN", fn,
                 dir);
-  NGPDE_REQUIRE(row_ptr_out && (n_edges == 0 || row_other_out), NGPDE_ERR_INVALID_ARGUMENT, "%s: an output is NULL", fn);
+  NGPDE_REQUIRE(row_ptr_out && (n_edges == 0 || (row_other_out && (row_eid_out || !with_eid))), NGPDE_ERR_INVALID_ARGUMENT, "%s: an output is NULL", fn);
   if (n_edges == 0) {
     NGPDE_HIP_CHECK(hipMemsetAsync(row_ptr_out, 0, ((size_t)n_nodes + 1) * sizeof(int32_t), stream));
     return NGPDE_OK;
@@ -482,6 +481,7 @@ int32_t ngpde_coo_rows(int64_t n_nodes, int64_t n_edges, const int32_t *s, const
   if ((st = new_flags(sc, &flags, stream))) return st;
   Rows rows;
   rows.rowptr = row_ptr_out;
+  rows.eid = row_eid_out;   // (NULL: a temporary)
   if ((st = build_rows(n_nodes, n_edges, s, t, index_base, dir, &rows, flags + fRowsBad, sc, stream))) return st;
   hipLaunchKernelGGL(rows_other_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, n_nodes, index_base, dir, s, t, rows.eid,
                      row_other_out, flags);
@@ -492,6 +492,19 @@ int32_t ngpde_coo_rows(int64_t n_nodes, int64_t n_edges, const int32_t *s, const
                 (long long)decode_offender(offender_of(h)), (long long)n_nodes);
   NGPDE_REQUIRE(!h[fBad], NGPDE_ERR_HIP, "%s: the sort returned a position outside the list", fn);
   return NGPDE_OK;
+}
+
+int32_t ngpde_coo_rows(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t dir,
+                       int32_t *row_ptr_out, int32_t *row_other_out, ngpde_stream_t stream) {
+  NGPDE_RANGE();
+  return coo_rows_entry("ngpde_coo_rows", false, n_nodes, n_edges, s, t, index_base, dir, row_ptr_out, row_other_out, nullptr, (hipStream_t)stream);
+}
+
+int32_t ngpde_coo_rows_eid(int64_t n_nodes, int64_t n_edges, const int32_t *s, const int32_t *t, int32_t index_base, int32_t dir,
+                           int32_t *row_ptr_out, int32_t *row_other_out, int32_t *row_eid_out, ngpde_stream_t stream) {
+  NGPDE_RANGE();
+  return coo_rows_entry("ngpde_coo_rows_eid", true, n_nodes, n_edges, s, t, index_base, dir, row_ptr_out, row_other_out, row_eid_out,
+                        (hipStream_t)stream);
 }
 
 size_t ngpde_csr_hop_distance_workspace_bytes(int64_t n) {

@@ -7,10 +7,13 @@ Graphs`, src/NeuralGraphPDE.jl:16; GNNGraphs re-exported at src/NeuralGraphPDE.j
     laplacian_lambda_max(gb); cg_solve(L(gb), B)              # ... one null vector per COMPONENT, which the per-graph solvers need
     d = hop_distance(g, boundary_nodes)                       # the hop distance to the boundary: a node feature, and "do L layers reach?"
     patch = induced_subgraph(g, neighborhood(g, seeds, 3))    # the nodes within 3 hops: a sub-domain to train on
+    sp = shortest_paths(g, boundary_nodes, edge_weight=lengths)   # the geodesic distance to the boundary along edges of length |x_s - x_t|
 
-Node positions are 0-based, as in graphops.py.  Everything runs on the device over the int32 COO lists (include/ngpde.h, "graph
-traversal"; csrc/graph_traverse.hip); there is no CPU fallback.  The results are integers and the only atomics are integer min / or /
-add: every result is bitwise equal from run to run and depends neither on the COO order nor on the launch geometry.
+(the last is upstream `dijkstra_shortest_paths(g, srcs, distmx)`).  Node positions are 0-based, as in graphops.py.  Everything runs on
+the device over the int32 COO lists (include/ngpde.h, "graph traversal"; csrc/graph_traverse.hip, csrc/graph_paths.hip); there is no
+CPU fallback.  The components and hop distances are integers and their only atomics are integer min / or / add; the shortest paths
+are float32 and use no atomics at all (synchronous rounds, fp32 addition is monotone): every result is bitwise equal from run to run
+and depends neither on the launch geometry nor -- the parents of shortest_paths apart, which follow a stated row order -- on the COO order.
 """
 from __future__ import annotations
 
@@ -20,11 +23,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .graphops import _DIRS, _Index, _arg_error, _coo, _device, _induced, _new_graph
+from .graphops import _DIRS, _Index, _arg_error, _coo, _device, _edge_weight_of, _f32_device, _induced, _is_f32, _new_graph
 from .matrices import _is_int
 from .queries import _ids
 
-__all__ = ["Components", "connected_components", "is_connected", "split_components", "hop_distance", "neighborhood"]
+__all__ = ["Components", "connected_components", "is_connected", "split_components", "hop_distance", "neighborhood", "ShortestPaths",
+           "shortest_paths"]
 
 
 def _rounds_args(max_rounds, check_every, what="max_rounds"):
@@ -246,6 +250,161 @@ def hop_distance(g, sources, dir="out", max_hops=None, separate=False, check_eve
                                           int(bool(separate)), -1 if max_hops is None else int(max_hops), int(check_every), _lib.ptr(dist),
                                           _lib.ptr(ws), nbytes, _lib.current_stream()))
     return dist
+
+
+class _RowsEidPlan:
+    """what ngpde_coo_rows_eid wrote: _RowsPlan and the COO position of every row entry"""
+
+    def __init__(self, g, code, dev):
+        s, t = _coo(g, dev)
+        self.nnz = g.num_edges
+        self.row_ptr = torch.empty(g.num_nodes + 1, dtype=torch.int32, device=dev)
+        self.other = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+        self.eid = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().ngpde_coo_rows_eid(g.num_nodes, self.nnz, _lib.ptr(s), _lib.ptr(t), 0, code, _lib.ptr(self.row_ptr),
+                                                  _lib.ptr(self.other), _lib.ptr(self.eid), _lib.current_stream()))
+
+
+def _rows_eid_plan(g, code, dev):
+    """the rows with their COO positions on `dev`, kept with the structure under a key of their own: a second call sorts nothing"""
+    key = ("rows_eid", code, str(dev))
+    p = g._shared.get(key)
+    if p is None:
+        p = g._shared[key] = _RowsEidPlan(g, code, dev)
+    return p
+
+
+class ShortestPaths:
+    """[UPSTREAM Graphs.DijkstraState / BellmanFordState] what shortest_paths returns, on the device:
+        dist         float32 [N], or [S, N] with separate=True: 0 at the sources, +inf where unreachable or farther than max_dist
+        parent_eid   int32, shaped like dist (None without return_parents): the COO position of the tree edge into every node, -1
+                     at sources and unreached nodes
+        parents      int32, shaped like dist (None without return_parents): the node at the other end of that edge, -1 likewise
+        flags        int32[2] on the device: [the rounds run, 1 if the last enqueued round still lowered a distance]
+        rounds       the relaxation rounds run, the confirming one included (read from `flags` on first use)
+        unfinished   did the distances still change after max_rounds rounds?  What a caller with check_every=0 asks instead of
+                     catching NGPDE_ERR_STATE (read from `flags` on first use)"""
+
+    def __init__(self, dist, parent_eid, parents, flags):
+        self.dist, self.parent_eid, self.parents, self.flags = dist, parent_eid, parents, flags
+        self._host_flags = self._host_parents = self._host_dist = None
+
+    def _flags(self):
+        if self._host_flags is None:
+            self._host_flags = self.flags.cpu().numpy()
+        return self._host_flags
+
+    @property
+    def rounds(self):
+        return int(self._flags()[0])
+
+    @property
+    def unfinished(self):
+        return bool(self._flags()[1])
+
+    def __repr__(self):
+        return f"ShortestPaths(dist {tuple(self.dist.shape)}{'' if self.parents is None else ', with parents'})"
+
+    def path_to(self, v, row=0):
+        """[UPSTREAM Graphs.enumerate_paths(state, v)] the nodes from the source to `v` along the tree, as a Python list; [] if `v`
+        is unreached.  `row` picks the source with separate=True.  The parents are read to the host once and kept."""
+        if self.parents is None:
+            raise _arg_error("path_to needs the parents: call shortest_paths(..., return_parents=True)")
+        rows = self.dist.shape[0] if self.dist.dim() == 2 else 1
+        n = int(self.dist.shape[-1])
+        if not _is_int(v) or not 0 <= v < n:
+            raise _arg_error(f"path_to: v must be a node in 0 : {n - 1}, not {v!r}")
+        if not _is_int(row) or not 0 <= row < rows:
+            raise _arg_error(f"path_to: row must be in 0 : {rows - 1}, not {row!r}")
+        if self._host_parents is None:
+            self._host_parents = self.parents.reshape(rows, n).cpu().numpy()
+            self._host_dist = self.dist.reshape(rows, n).cpu().numpy()
+        if not np.isfinite(self._host_dist[row, v]):
+            return []
+        parent, path = self._host_parents[row], [int(v)]
+        while parent[path[-1]] >= 0:
+            path.append(int(parent[path[-1]]))
+            if len(path) > n:
+                raise _lib.NgpdeError(_lib.ERR_STATE, "path_to: the parents do not form a tree (were the rounds left unfinished?)")
+        return path[::-1]
+
+
+def _path_weights(g, edge_weight):
+    """the weights in COO order -- the graph's own, or the E float32 values given -- or None: 1 per edge.  Checked on the host."""
+    if edge_weight is None:
+        return _edge_weight_of(g)
+    w = edge_weight if isinstance(edge_weight, torch.Tensor) else np.asarray(edge_weight)
+    if not _is_f32(w):
+        raise _arg_error(f"shortest_paths: edge_weight must be float32, not {w.dtype}")
+    if int(np.prod(tuple(w.shape))) != g.num_edges:
+        raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
+                                     f"DimensionMismatch: edge_weight has {int(np.prod(tuple(w.shape)))} entries for {g.num_edges} edges")
+    return w
+
+
+def shortest_paths(g, sources, edge_weight=None, dir="out", separate=False, max_dist=None, max_rounds=None, check_every=8,
+                   return_parents=False):
+    """[UPSTREAM Graphs.dijkstra_shortest_paths(g, srcs, distmx) / bellman_ford_shortest_paths] weighted shortest paths: a
+    ShortestPaths on the device.  `dist` is float32, [N] -- the length of a shortest path from the NEAREST listed source -- or, with
+    separate=True, [len(sources), N], one row per listed source; +inf where unreachable, 0 at the sources.  `sources`, `dir`,
+    `separate`, batches (a source reaches only its own graph) and the errors for bad sources are hop_distance's.
+
+    edge_weight=None takes the graph's own `edge_weight` if it has one, else 1 per edge; otherwise a float32 tensor / array of E
+    weights in COO order -- for the geodesic distance along a mesh or a radius graph, the edge lengths |x_s - x_t| that apply_edges
+    computes.  +inf and 0 are valid weights; a negative or NaN weight is an ArgumentError that names the smallest offending COO
+    position (found on the device by the launch that gathers the weights into row order).  `max_dist` (a float >= 0, rounded to
+    float32, or None): nodes farther than it get +inf; a node at exactly max_dist keeps its distance.  There is NO gradient to
+    edge_weight (as upstream): it is read detached.
+
+    Synchronous relaxation rounds (ngpde_csr_shortest_paths): a round sets d[v] = min(d[v], min over v's row of fl32(d[u] + w)) from
+    the values of the round before only (two buffers alternate), one launch with a lane per node and group of sources that writes
+    its own cells only -- no atomics; a hub's row is walked by a whole wave.  fp32 addition is monotone, so `dist` is a pure
+    function of graph, weights and sources: bitwise what a float32 heap Dijkstra returns, whatever the COO order or the geometry.
+    With return_parents=True `parent_eid` / `parents` name the tree edge into every node: recorded only when the distance strictly
+    decreases, the first candidate in row order winning a tie (COO order inside a row; for dir="both" the edges into the node before
+    those out of it), so they are a pure function of the COO list too, every parent edge is tight and the parents form a tree also
+    with zero weights; `sp.path_to(v)` walks it.  separate=True runs ceil(S / 64) passes, one launch per round for all the sources
+    of a pass.  The rows are sorted once per (graph, direction) and kept with the structure.
+
+    Rounds are enqueued in groups of `check_every` with one read-back per group.  `max_rounds` (None: N, which always suffices
+    with non-negative weights) bounds them: still changing after that many is an error (status NGPDE_ERR_STATE), never a partial
+    answer.  check_every=0 needs max_rounds, enqueues exactly that many rounds and reads nothing back: once the rows plan exists,
+    with `sources` an int64 and `edge_weight` a float32 device tensor, the call can be captured into a HIP graph; `sp.unfinished`
+    then tells what the status would have (bad sources and weights are not raised there: nothing is relaxed through them)."""
+    code = _DIRS.get(dir) if isinstance(dir, str) else None
+    if code is None:
+        raise _arg_error(f"dir must be 'out', 'in' or 'both', not {dir!r}")
+    _rounds_args(max_rounds, check_every)
+    for name, flag in (("separate", separate), ("return_parents", return_parents)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise _arg_error(f"{name} must be a bool, not {flag!r}")
+    if max_dist is not None and (isinstance(max_dist, (bool, np.bool_)) or not isinstance(max_dist, (int, float, np.integer, np.floating))
+                                 or not max_dist >= 0):
+        raise _arg_error(f"max_dist must be a number >= 0 (or None: no bound), not {max_dist!r}")
+    sources = _node_list(sources, "shortest_paths: sources")
+    w = _path_weights(g, edge_weight)
+    dev = _device()
+    if w is not None:
+        w = _f32_device(w, dev).detach().reshape(-1).contiguous()
+    src = _ids(sources, dev, "shortest_paths: sources")
+    lib, n, k = _lib.load(), g.num_nodes, int(src.numel())
+    # following s -> t, a node is relaxed from the SOURCES of its incoming edges: the rows grouped by target
+    plans = [_rows_eid_plan(g, c, dev) for c in ((1,), (0,), (1, 0))[code]]
+    a, b = plans[0], (plans[1] if len(plans) > 1 else None)
+    shape = (k, n) if separate else (n,)
+    dist = torch.empty(shape, dtype=torch.float32, device=dev)
+    parent_eid = torch.empty(shape, dtype=torch.int32, device=dev) if return_parents else None
+    parents = torch.empty(shape, dtype=torch.int32, device=dev) if return_parents else None
+    flags = torch.empty(2, dtype=torch.int32, device=dev)
+    nbytes = int(lib.ngpde_csr_shortest_paths_workspace_bytes(n, a.nnz, 0 if b is None else b.nnz, k, int(bool(separate))))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    none = (0, None, None, None)
+    _lib.check(lib.ngpde_csr_shortest_paths(n, a.nnz, _lib.ptr(a.row_ptr), _lib.ptr(a.other), _lib.ptr(a.eid),
+                                            *(none if b is None else (b.nnz, _lib.ptr(b.row_ptr), _lib.ptr(b.other), _lib.ptr(b.eid))), k,
+                                            _lib.ptr(src), 0, int(bool(separate)), _lib.ptr(w), float("inf") if max_dist is None else float(max_dist),
+                                            0 if max_rounds is None else int(max_rounds), int(check_every), _lib.ptr(dist), _lib.ptr(parent_eid),
+                                            _lib.ptr(parents), _lib.ptr(flags), _lib.ptr(ws), nbytes, _lib.current_stream()))
+    return ShortestPaths(dist, parent_eid, parents, flags)
 
 
 def neighborhood(g, nodes, d, dir="out"):
