@@ -879,7 +879,7 @@ int32_t ngpde_coo_rows_eid(int64_t n_nodes, int64_t n_edges, const int32_t *s, c
  *                lowers a distance also stores it, and the tree edge, into the caller's arrays, which so hold the last value of
  *                every cell).  ONE launch, __launch_bounds__(256), a lane per (node, source group): it writes its own cells only
  *                -- no atomics, no race, the same bits whatever the geometry; the only flag writes are the plain "changed"
- *                stores into three rotating control words.  A launch exits at once when the round before changed nothing.
+ *                stores into three rotating control words (csrc/traverse_rounds.h).  A launch exits at once when the round before changed nothing.
  *                The round buffers are one slab [n][NGPDE_SSSP_LANE_SOURCES] per group of sources (the last group padded): what a
  *                round gathers, the distances of a row entry's other end for the lane's sources, is one aligned 16-byte load,
  *                and a wave's own cells are contiguous.

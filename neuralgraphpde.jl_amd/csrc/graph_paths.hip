@@ -22,47 +22,28 @@
 //                therefore one slab [nodes][kLane] per group of kLane sources (the last group padded): the kLane distances a lane
 //                needs of a neighbour are ONE aligned 16-byte load, not kLane loads from kLane rows, a wave's own cells are one
 //                contiguous KiB, and a group's lanes touch their slab only.  A padded column stays +inf and is never stored.
-//   hub rows     a row of NGPDE_SSSP_WAVE_ROW entries or more is walked by the whole wave, lane l taking entries l, l + 64, ...; the
+//   hub rows     a row of NGPDE_SSSP_WAVE_ROW entries or more is walked by the whole wave (traverse_rounds.h, the hub-row walk); the
 //                wave reduces (distance, row position) lexicographically, so the first-in-row rule holds for them too.
 //   max_dist     a candidate above it is dropped.  Distances do not decrease along a path, so every node within max_dist keeps
 //                its exact distance and parent.
-// Kernel boundaries are the only synchronisation: no spin-wait, no grid barrier, no cooperative launch.
-#include <algorithm>
+// Kernel boundaries are the only synchronisation: no spin-wait, no grid barrier (stop words and round loop: traverse_rounds.h).
 #include <climits>
 #include <cmath>
-#include <cstdint>
-#include <cstring>
 
-#include "common.h"
-#include "device_scratch.h"
+#include "traverse_rounds.h"
 
 namespace ngpde {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kLane = NGPDE_SSSP_LANE_SOURCES;   // the sources a lane relaxes from one read of its row (1 when the call has one row)
-constexpr size_t kCtlBytes = 256;                // the control words of a call, the workspace's last 256 bytes
-constexpr int64_t kMaxUncheckedLaunches = 1 << 20;   // what a call with check_every 0 may enqueue at most
 
 static_assert(kLane == 4, "a lane's sources of one neighbour are one float4");
-static_assert(NGPDE_SSSP_PASS % NGPDE_SSSP_LANE_SOURCES == 0, "a pass is a whole number of lane groups");
+static_assert(NGPDE_SSSP_PASS == kPassSources && NGPDE_SSSP_PASS % NGPDE_SSSP_LANE_SOURCES == 0, "a pass is a whole number of lane groups");
 
-// the control words (int32; words 0 - 1 and 2 - 3 are ONE 64-bit word each: the smallest offending source / COO position)
-enum { cSource = 0, cWeight = 2, cCsr = 4, cChanged = 5, cRounds = 8, cState = 9 };
-
-inline unsigned long long word_of(const int32_t *h, int at) {
-  unsigned long long w;
-  std::memcpy(&w, h + at, sizeof(w));
-  return w;
-}
-
-struct PathRows {   // the rows of one direction: row v = positions ptr[v] .. ptr[v + 1] - 1 of other / eid / w; ptr NULL: no such set
-  const int32_t *ptr;
-  const int32_t *other;
+struct PathRows : HopRows {   // HopRows with, per position, the COO position eid and the weight w
   const int32_t *eid;
   const float *w;   // in row order; NULL: 1 per entry
-  int64_t nnz;
 };
 
 // w_rows[p] = weights[eid[p]] for the positions of set a, then of set b.  A negative or NaN weight is reported by its COO position
@@ -86,26 +67,11 @@ __global__ void sssp_weights_kernel(int64_t nnz_a, int64_t nnz_b, int64_t m, con
   (second ? w_b : w_a)[p] = w;
 }
 
-// dist = +inf, the parents = -1 everywhere; every listed source is checked here, whichever pass it belongs to
-__global__ void sssp_fill_kernel(int64_t total, float *__restrict__ dist, int32_t *__restrict__ parent_eid, int32_t *__restrict__ parent,
-                                 int64_t n_sources, const int64_t *__restrict__ sources, int base, int64_t n, int32_t *__restrict__ ctl) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < total) {
-    dist[i] = INFINITY;
-    if (parent_eid) parent_eid[i] = -1;
-    if (parent) parent[i] = -1;
-  }
-  if (i < n_sources) {
-    const int64_t v = sources[i] - base;
-    if (v < 0 || v >= n) report_offender(reinterpret_cast<unsigned long long *>(ctl + cSource), v);
-  }
-}
-
-// a pass starts: its first round buffer is +inf; changed[0] = 1: "round 0 changed something" (the sources), so that round 1 runs
+// a pass starts: its first round buffer is +inf; "round 0 changed something" (the sources), so that round 1 runs
 __global__ void sssp_pass_kernel(int64_t cells, float *__restrict__ buf, int32_t *__restrict__ ctl) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < cells) buf[i] = INFINITY;
-  if (i < 3) ctl[cChanged + i] = i == 0 ? 1 : 0;
+  rounds_arm(ctl, cTurn, i);
 }
 
 // source i of the pass gets distance 0 in its cell of the round buffer (the layout of sssp_round_kernel) and in its row of dist (all
@@ -115,10 +81,10 @@ __global__ void sssp_sources_kernel(int64_t cnt, int64_t n, int base, int separa
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= cnt) return;
   const int64_t v = sources[i] - base;
-  if (v < 0 || v >= n) return;   // (reported by sssp_fill_kernel)
+  if (v < 0 || v >= n) return;   // (reported by fill_sources_kernel)
   const int64_t col = separate ? i : 0, k = width > 1 ? kLane : 1;   // slab col / k, column col % k of the node's cells
   buf[((size_t)(col / k) * (size_t)n + (size_t)v) * (size_t)k + (size_t)(col % k)] = 0.f;
-  dist[(size_t)(separate ? row0 + i : 0) * (size_t)n + (size_t)v] = 0.f;
+  dist[source_cell(separate, row0, i, n, v)] = 0.f;
 }
 
 template <int K>
@@ -188,18 +154,15 @@ __device__ __forceinline__ void wave_first_min(float &d, int32_t &p) {
 
 // Round `round` >= 1 of a pass.  prev / next: [gridDim.y][n][K] -- a slab per group of K sources --, blockIdx.y the lane's group, v
 // its node; dist / parent_eid / parent: the pass's `cnt` rows of the caller's arrays, row stride n.  prev is not written by this launch and
-// every cell a lane writes is its own, so the launch has no race.  The three `changed` words rotate as hop_level_kernel's `any` words do.
+// every cell a lane writes is its own, so the launch has no race.  Its cTurn word says "this round lowered a distance".
 template <int K>
 __global__ __launch_bounds__(256) void sssp_round_kernel(int64_t n, int round, PathRows ra, PathRows rb, int cnt, float max_dist,
                                                          const float *__restrict__ prev, float *__restrict__ next, float *__restrict__ dist,
                                                          int32_t *__restrict__ parent_eid, int32_t *__restrict__ parent, int32_t *ctl) {
   const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & (kWave - 1);
-  const int go = ctl[cChanged + (round + 2) % 3];
-  if (v == 0 && blockIdx.y == 0) {
-    ctl[cChanged + (round + 1) % 3] = 0;
-    if (go && round > ctl[cRounds]) ctl[cRounds] = round;
-  }
+  const int go = round_go(ctl, cTurn, round, v == 0 && blockIdx.y == 0);
+  if (v == 0 && blockIdx.y == 0 && go && round > ctl[cRounds]) ctl[cRounds] = round;
   if (!go) return;   // (the whole grid: the round before lowered nothing)
   const int k0 = (int)blockIdx.y * K;
   const size_t slab = (size_t)blockIdx.y * (size_t)n * K;
@@ -217,24 +180,14 @@ __global__ __launch_bounds__(256) void sssp_round_kernel(int64_t n, int round, P
   for (int s = 0; s < 2; ++s) {
     const PathRows &r = s == 0 ? ra : rb;
     if (!r.ptr) continue;   // (uniform)
-    int64_t b = 0, e = 0;
-    if (mine) {
-      b = r.ptr[v], e = r.ptr[v + 1];
-      if (b < 0 || e > r.nnz || b > e) {
-        ctl[cCsr] = 1;
-        b = e = 0;
-      }
-    }
+    int64_t b, e;
+    row_span(r, v, mine, b, e, ctl);
     Best<K> here;   // this set's own first minimum below what the earlier set left
 #pragma unroll
     for (int k = 0; k < K; ++k) here.d[k] = best.d[k], here.p[k] = -1;
     const bool wide = e - b >= NGPDE_SSSP_WAVE_ROW;
     if (!wide) relax_entries<K>(r, b, e, 1, n, max_dist, prev, here, ctl);
-    unsigned long long todo = __ballot(wide);   // the rows of this wave that the whole wave walks, one after the other
-    while (todo) {
-      const int owner = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int64_t wb = __shfl(b, owner, kWave), we = __shfl(e, owner, kWave);
+    for_wide_rows(wide, b, e, [&](int owner, int64_t wb, int64_t we) {
       Best<K> part;   // (every lane starts from the owner's bound)
 #pragma unroll
       for (int k = 0; k < K; ++k) part.d[k] = __shfl(best.d[k], owner, kWave), part.p[k] = -1;
@@ -245,7 +198,7 @@ __global__ __launch_bounds__(256) void sssp_round_kernel(int64_t n, int round, P
         wave_first_min(part.d[k], part.p[k]);
         if (lane == owner && part.p[k] != INT_MAX) here.d[k] = part.d[k], here.p[k] = part.p[k];
       }
-    }
+    });
 #pragma unroll
     for (int k = 0; k < K; ++k)
       if (here.p[k] >= 0) best.d[k] = here.d[k], best.p[k] = here.p[k], set[k] = s;
@@ -266,13 +219,13 @@ __global__ __launch_bounds__(256) void sssp_round_kernel(int64_t n, int round, P
     }
   }
   store_cells<K>(next + (size_t)v * K, now);
-  if (lowered) ctl[cChanged + round % 3] = 1;
+  if (lowered) round_mark(ctl, cTurn, round);
 }
 
 // a pass ends: did its last enqueued round still lower a distance?  rounds_out[0] = the rounds run so far (the largest over the passes)
 __global__ void sssp_pass_end_kernel(int last_round, int32_t *__restrict__ ctl, int32_t *__restrict__ rounds_out) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (last_round > 0 && ctl[cChanged + last_round % 3]) ctl[cState] = 1;
+    if (last_round > 0 && ctl[round_word(cTurn, last_round)]) ctl[cState] = 1;
     if (rounds_out) rounds_out[0] = ctl[cRounds], rounds_out[1] = ctl[cState];
   }
 }
@@ -281,21 +234,13 @@ struct PathLayout {
   size_t buf0, buf1, w_a, w_b, ctl, total;
 };
 
-inline size_t up256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 // the columns of a round buffer for `rows` sources: 1, or the next multiple of kLane
 inline int64_t width_for(int64_t rows) { return rows <= 1 ? 1 : (rows + kLane - 1) / kLane * kLane; }
 
 PathLayout path_layout(int64_t n, int64_t nnz_a, int64_t nnz_b, int64_t n_sources, int separate) {
-  PathLayout a;
   const size_t buf = up256((size_t)n * (size_t)width_for(separate ? std::min<int64_t>(n_sources, NGPDE_SSSP_PASS) : 1) * sizeof(float));
-  a.buf0 = 0;
-  a.buf1 = buf;
-  a.w_a = 2 * buf;
-  a.w_b = a.w_a + up256((size_t)nnz_a * sizeof(float));
-  a.ctl = a.w_b + up256((size_t)nnz_b * sizeof(float));
-  a.total = a.ctl + kCtlBytes;
-  return a;
+  const size_t w_b = 2 * buf + up256((size_t)nnz_a * sizeof(float)), ctl = w_b + up256((size_t)nnz_b * sizeof(float));
+  return {0, buf, 2 * buf, w_b, ctl, ctl + kCtlBytes};
 }
 
 bool sizes_ok(int64_t n, int64_t nnz_a, int64_t nnz_b, int64_t n_sources) {
@@ -303,26 +248,8 @@ bool sizes_ok(int64_t n, int64_t nnz_a, int64_t nnz_b, int64_t n_sources) {
   return n >= 0 && n <= top && nnz_a >= 0 && nnz_a <= top && nnz_b >= 0 && nnz_b <= top && n_sources >= 0 && n_sources <= top;
 }
 
-int32_t read_ctl(const int32_t *ctl, int32_t *h, hipStream_t stream) {   // (synchronises)
-  NGPDE_HIP_CHECK(hipMemcpyAsync(h, ctl, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
-  return NGPDE_OK;
-}
-
 int32_t check_rows(const char *fn, const char *what, const int32_t *ptr, const int32_t *other, const int32_t *eid, int64_t nnz) {
   NGPDE_REQUIRE(ptr && (nnz == 0 || (other && eid)), NGPDE_ERR_INVALID_ARGUMENT, "%s: a row list of set %s is NULL", fn, what);
-  return NGPDE_OK;
-}
-
-// the named errors of the control block, in the order the header lists them
-int32_t named_errors(const char *fn, const int32_t *h, int64_t n) {
-  NGPDE_REQUIRE(!word_of(h, cSource), NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: sources lists node %lld, outside the %lld nodes", fn,
-                (long long)decode_offender(word_of(h, cSource)), (long long)n);
-  NGPDE_REQUIRE(!h[cCsr], NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: a row pointer, a row entry or a COO position lies outside the lists",
-                fn);
-  NGPDE_REQUIRE(!word_of(h, cWeight), NGPDE_ERR_INVALID_ARGUMENT,
-                "%s: ArgumentError: the weight at COO position %lld is negative or NaN (weights must be >= 0; +inf and 0 are valid)", fn,
-                (long long)decode_offender(word_of(h, cWeight)));
   return NGPDE_OK;
 }
 
@@ -366,20 +293,15 @@ int32_t ngpde_csr_shortest_paths(int64_t n, int64_t nnz_a, const int32_t *row_pt
   NGPDE_REQUIRE(check_every >= 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: check_every %d is negative (0: no read-back)", fn, check_every);
   NGPDE_REQUIRE(check_every > 0 || max_rounds > 0, NGPDE_ERR_INVALID_ARGUMENT,
                 "%s: check_every 0 enqueues exactly max_rounds rounds: max_rounds must be given (positive)", fn);
-  const int64_t n_rows = separate ? n_sources : 1;
-  const int64_t total = n_rows * n;
-  NGPDE_REQUIRE(total <= ((int64_t)1 << 40), NGPDE_ERR_UNSUPPORTED, "%s: %lld sources x %lld nodes: the result is too large", fn, (long long)n_rows,
-                (long long)n);
-  NGPDE_REQUIRE(dist_out || total == 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: dist_out is NULL", fn);
+  int64_t total;
+  if (int32_t st = check_result(fn, n, n_sources, separate, dist_out, &total)) return st;
   const PathLayout lay = path_layout(n, nnz_a, nnz_b, n_sources, separate);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= lay.total, NGPDE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes,
-                lay.total);
-  NGPDE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: the workspace is not 16-byte aligned", fn);
-  const int64_t rounds = max_rounds > 0 ? max_rounds : std::max<int64_t>(n, 1);
-  const int64_t passes = n_sources == 0 || total == 0 ? 0 : (separate ? (n_sources + NGPDE_SSSP_PASS - 1) / NGPDE_SSSP_PASS : 1);
-  NGPDE_REQUIRE(check_every > 0 || rounds * passes <= kMaxUncheckedLaunches, NGPDE_ERR_UNSUPPORTED,
-                "%s: max_rounds %d with check_every 0 would enqueue %lld launches", fn, max_rounds, (long long)(rounds * passes));
-  const int64_t most = std::max({total, nnz_a + nnz_b, n * width_for(std::min<int64_t>(n_rows, NGPDE_SSSP_PASS))});
+  if (int32_t st = check_workspace(fn, workspace, workspace_bytes, lay.total, 16)) return st;
+  const int64_t max_r = max_rounds > 0 ? max_rounds : std::max<int64_t>(n, 1);
+  const int64_t per = pass_sources(n_sources, separate), passes = total == 0 ? 0 : (n_sources + per - 1) / per;
+  NGPDE_REQUIRE(check_every > 0 || max_r * passes <= kMaxUncheckedLaunches, NGPDE_ERR_UNSUPPORTED,
+                "%s: max_rounds %d with check_every 0 would enqueue %lld launches", fn, max_rounds, (long long)(max_r * passes));
+  const int64_t most = std::max({total, nnz_a + nnz_b, n * width_for(std::min<int64_t>(separate ? n_sources : 1, NGPDE_SSSP_PASS))});
   NGPDE_REQUIRE(most / kB < 0x7fffffffLL, NGPDE_ERR_UNSUPPORTED, "%s: %lld cells in one launch", fn, (long long)most);
 
   char *base = (char *)workspace;
@@ -395,29 +317,28 @@ int32_t ngpde_csr_shortest_paths(int64_t n, int64_t nnz_a, const int32_t *row_pt
     NGPDE_LAUNCH_CHECK("sssp_weights_kernel");
   }
   if (std::max(total, n_sources) > 0) {
-    hipLaunchKernelGGL(sssp_fill_kernel, dim3(blocks_for(std::max(total, n_sources))), dim3(kB), 0, stream, total, dist_out, parent_eid_out,
-                       parent_out, n_sources, sources, index_base, n, ctl);
-    NGPDE_LAUNCH_CHECK("sssp_fill_kernel");
+    hipLaunchKernelGGL(fill_sources_kernel<float>, dim3(blocks_for(std::max(total, n_sources))), dim3(kB), 0, stream, total, INFINITY, dist_out,
+                       parent_eid_out, parent_out, n_sources, sources, index_base, n, ctl);
+    NGPDE_LAUNCH_CHECK("fill_sources_kernel");
   }
-  const PathRows ra = {row_ptr_a, other_a, eid_a, weights ? w_a : nullptr, nnz_a};
-  const PathRows rb = {two ? row_ptr_b : nullptr, other_b, eid_b, weights ? w_b : nullptr, nnz_b};
-  bool checked = false, unfinished = false;
-  for (int64_t pass = 0; pass < passes; ++pass) {
-    const int64_t row0 = separate ? pass * NGPDE_SSSP_PASS : 0;
-    const int64_t cnt = separate ? std::min<int64_t>(NGPDE_SSSP_PASS, n_sources - row0) : n_sources;
+  const PathRows ra = {{row_ptr_a, other_a, nnz_a}, eid_a, weights ? w_a : nullptr};
+  const PathRows rb = {{two ? row_ptr_b : nullptr, other_b, nnz_b}, eid_b, weights ? w_b : nullptr};
+  auto errors = [&](const int32_t *h) { return named_errors(fn, h, n, "a row pointer, a row entry or a COO position"); };
+  Rounds rounds = {check_every, ctl, stream};
+  bool unfinished = false;
+  for (int64_t row0 = 0; row0 < passes * per && !unfinished; row0 += per) {
+    const int64_t cnt = std::min(per, n_sources - row0);
     const int rows_here = separate ? (int)cnt : 1;
     const int width = (int)width_for(rows_here);
     const size_t at = (size_t)row0 * (size_t)n;
+    float *dist = dist_out + at;
+    int32_t *pe = parent_eid_out ? parent_eid_out + at : nullptr, *pa = parent_out ? parent_out + at : nullptr;
     hipLaunchKernelGGL(sssp_pass_kernel, dim3(blocks_for(n * width)), dim3(kB), 0, stream, n * width, buf[0], ctl);
     NGPDE_LAUNCH_CHECK("sssp_pass_kernel");
     hipLaunchKernelGGL(sssp_sources_kernel, dim3(blocks_for(cnt)), dim3(kB), 0, stream, cnt, n, index_base, separate ? 1 : 0, row0, width,
-                       sources + (separate ? row0 : 0), buf[0], dist_out);
+                       sources + row0, buf[0], dist_out);
     NGPDE_LAUNCH_CHECK("sssp_sources_kernel");
-    int64_t last = 0;
-    bool done = false;
-    for (int64_t r = 1; r <= rounds && !done; ++r) {
-      float *dist = dist_out + at;
-      int32_t *pe = parent_eid_out ? parent_eid_out + at : nullptr, *pa = parent_out ? parent_out + at : nullptr;
+    auto round = [&](int64_t r) -> int32_t {
       if (width == 1)
         hipLaunchKernelGGL(sssp_round_kernel<1>, dim3(blocks_for(n), 1), dim3(kB), 0, stream, n, (int)r, ra, rb, rows_here, max_dist,
                            buf[(r - 1) & 1], buf[r & 1], dist, pe, pa, ctl);
@@ -425,31 +346,21 @@ int32_t ngpde_csr_shortest_paths(int64_t n, int64_t nnz_a, const int32_t *row_pt
         hipLaunchKernelGGL(sssp_round_kernel<kLane>, dim3(blocks_for(n), (unsigned)(width / kLane)), dim3(kB), 0, stream, n, (int)r, ra, rb,
                            rows_here, max_dist, buf[(r - 1) & 1], buf[r & 1], dist, pe, pa, ctl);
       NGPDE_LAUNCH_CHECK("sssp_round_kernel");
-      last = r;
-      if (check_every > 0 && (r % check_every == 0 || r == rounds)) {   // one read-back per group of rounds
-        int32_t h[16];
-        if ((st = read_ctl(ctl, h, stream))) return st;
-        checked = true;
-        if ((st = named_errors(fn, h, n))) return st;
-        done = h[cChanged + r % 3] == 0;
-      }
-    }
-    if (check_every > 0 && !done) unfinished = true;
-    hipLaunchKernelGGL(sssp_pass_end_kernel, dim3(1), dim3(kWave), 0, stream, (int)last, ctl, rounds_out);
+      return NGPDE_OK;
+    };
+    if ((st = rounds.run(max_r, round, errors))) return st;
+    unfinished = check_every > 0 && !rounds.done;
+    hipLaunchKernelGGL(sssp_pass_end_kernel, dim3(1), dim3(kWave), 0, stream, (int)rounds.last, ctl, rounds_out);
     NGPDE_LAUNCH_CHECK("sssp_pass_end_kernel");
-    if (unfinished) break;
   }
   if (passes == 0 && rounds_out) {   // (no pass ran: no rounds)
     hipLaunchKernelGGL(sssp_pass_end_kernel, dim3(1), dim3(kWave), 0, stream, 0, ctl, rounds_out);
     NGPDE_LAUNCH_CHECK("sssp_pass_end_kernel");
   }
-  if (check_every > 0 && !checked) {   // (no round ran: the sources and the weights are still to be answered for)
-    int32_t h[16];
-    if ((st = read_ctl(ctl, h, stream))) return st;
-    if ((st = named_errors(fn, h, n))) return st;
-  }
+  // (no round ran: the sources and the weights are still to be answered for)
+  if ((st = rounds.answer(errors))) return st;
   NGPDE_REQUIRE(!unfinished, NGPDE_ERR_STATE,
-                "%s: still changing after max_rounds = %lld rounds: the distances are not final (raise max_rounds)", fn, (long long)rounds);
+                "%s: still changing after max_rounds = %lld rounds: the distances are not final (raise max_rounds)", fn, (long long)max_r);
   return NGPDE_OK;
 }
 

@@ -34,7 +34,7 @@
 // sources share bit 0 when one distance to the NEAREST source is asked).  One level is one launch with a lane per node: it ORs the
 // frontier words of the other ends of its row(s), keeps the bits it has not seen, stores level for each and writes seen[v],
 // next[v] -- a lane writes its own node only: no atomics in the level loop, no race, the same bits whatever the geometry.  Rows of
-// NGPDE_HOP_WAVE_ROW entries or more are walked by the whole wave with an OR across its lanes, so a hub row does not serialise on one lane.
+// NGPDE_HOP_WAVE_ROW entries or more take the hub-row walk of traverse_rounds.h (which also holds the stop words and the round loop).
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -44,47 +44,39 @@
 #include "common.h"
 #include "coo_compact.h"
 #include "coo_rows.h"
+#include "traverse_rounds.h"
 
 namespace ngpde {
 
 namespace {
 
-typedef unsigned long long u64;
+constexpr int kJumpLinks = 7;   // links a compress lane follows beyond parent[i]: a launch divides the depth by 8
 
-constexpr int kWave = 64;
-constexpr int kJumpLinks = 7;                 // links a compress lane follows beyond parent[i]: a launch divides the depth by 8
-constexpr size_t kCtlBytes = 256;             // the control words of a call, the workspace's last (components: only) 256 bytes
-constexpr int64_t kMaxUncheckedLaunches = 1 << 20;   // what a call with check_every 0 may enqueue at most (rounds, levels)
-
-// the control words (int32; words 0 and 1 are ONE 64-bit word: the smallest offending id)
-enum { cOffender = 0, cCsr = 2, cHooked = 4, cMore = 7, cRounds = 10, cAny = 12 };
 // flag words of the calls that take their temporaries from Scratch (device_scratch.h)
 enum { fOffender = 0, fBad = 2, fLabel = 3, fGraph = 4, fRowsBad = 5 };
 
-inline unsigned long long offender_of(const int32_t *h) {
-  unsigned long long w;
-  std::memcpy(&w, h + cOffender, sizeof(w));
-  return w;
+int32_t edge_error(const char *fn, const int32_t *h, int at, int64_t n_nodes) {   // the 64-bit word at h[at]: the smallest offending end
+  NGPDE_REQUIRE(!word_of(h, at), NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: an edge references node %lld, outside the %lld nodes", fn,
+                (long long)decode_offender(word_of(h, at)), (long long)n_nodes);
+  return NGPDE_OK;
 }
 
 inline int jumps_for(int64_t n) { return std::max(1, ((int)bits_for((unsigned long long)std::max<int64_t>(n, 2)) + 2) / 3); }
 
 // ---- components -----------------------------------------------------------------------------------------------------------------
-// hooked[0] = 1: "round 0 hooked", so that round 1 runs
+// every control word cleared but the first cTurn word: "round 0 hooked", so that round 1 runs (each word has ONE writer)
 __global__ void cc_init_kernel(int64_t n, int32_t *__restrict__ parent, int32_t *__restrict__ ctl) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) parent[i] = (int32_t)i;
-  if (i < 16) ctl[i] = i == cHooked ? 1 : 0;
+  if (i < kCtlRead) ctl[i] = i == cTurn ? 1 : 0;
 }
 
-// Round `round` >= 1.  The three hooked words rotate: this launch reads the word of the round before (0: that round hooked nothing,
-// every launch from there on exits at once), sets its own and clears the next round's, which no launch in flight reads.
+// Round `round` >= 1; its cTurn word says "this round hooked".
 __global__ void cc_hook_kernel(int64_t m, int64_t n, int base, int round, const int32_t *__restrict__ s, const int32_t *__restrict__ t,
                                int32_t *parent, int32_t *ctl) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int go = ctl[cHooked + (round + 2) % 3];
+  const int go = round_go(ctl, cTurn, round, e == 0);
   if (e == 0) {
-    ctl[cHooked + (round + 1) % 3] = 0;
     ctl[cMore] = 0;   // (the first compress launch of the round sets it)
     if (go) ctl[cRounds] = round;
   }
@@ -97,15 +89,15 @@ __global__ void cc_hook_kernel(int64_t m, int64_t n, int base, int round, const 
   const int32_t ra = parent[a], rb = parent[b];   // start-of-round roots of the true components of a and b, whatever is read (above)
   if (ra == rb) return;
   __hip_atomic_fetch_min(&parent[ra > rb ? ra : rb], ra > rb ? rb : ra, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  ctl[cHooked + round % 3] = 1;
+  round_mark(ctl, cTurn, round);
 }
 
 // Launch j of the compression of round `round`: runs if the round hooked (j = 0) or the launch before left a node short of its root.
-// The three `more` words rotate like the hooked words.
+// The cMore words rotate over j as the cTurn words do over the rounds.
 __global__ void cc_compress_kernel(int64_t n, int round, int j, int32_t *parent, int32_t *ctl) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int go = j == 0 ? ctl[cHooked + round % 3] : ctl[cMore + (j + 2) % 3];
-  if (i == 0) ctl[cMore + (j + 1) % 3] = 0;
+  const int go = ctl[j == 0 ? round_word(cTurn, round) : round_word(cMore, j + 2)];   // (round_go, but launch 0 follows the hook)
+  if (i == 0) ctl[round_word(cMore, j + 1)] = 0;
   if (!go || i >= n) return;
   const int32_t p0 = parent[i];
   int32_t p = p0;
@@ -120,14 +112,14 @@ __global__ void cc_compress_kernel(int64_t n, int round, int j, int32_t *parent,
     p = gp;
   }
   if (p != p0) parent[i] = p;   // an ancestor of p0: a lane that reads the old or the new word climbs the same tree
-  if (!root) ctl[cMore + j % 3] = 1;
+  if (!root) round_mark(ctl, cMore, j);
 }
 
 // rounds_out[0] = the rounds run (the confirming one included), rounds_out[1] = did the last enqueued round still hook?
 __global__ void cc_finish_kernel(int last_round, const int32_t *__restrict__ ctl, int32_t *__restrict__ rounds_out) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     rounds_out[0] = ctl[cRounds];
-    rounds_out[1] = ctl[cHooked + last_round % 3] ? 1 : 0;
+    rounds_out[1] = ctl[round_word(cTurn, last_round)] ? 1 : 0;
   }
 }
 
@@ -197,28 +189,11 @@ __global__ void rows_other_kernel(int64_t m, int64_t n, int base, int dir, const
 }
 
 // ---- hop distances --------------------------------------------------------------------------------------------------------------
-struct HopRows {   // the rows of one direction: row v = other[ptr[v] .. ptr[v + 1] - 1]; ptr NULL: no such set
-  const int32_t *ptr;
-  const int32_t *other;
-  int64_t nnz;
-};
-
-// dist = -1 everywhere; every listed source is checked here, whichever pass it belongs to (the smallest bad one is named)
-__global__ void hop_fill_kernel(int64_t total, int32_t *__restrict__ dist, int64_t n_sources, const int64_t *__restrict__ sources, int base,
-                                int64_t n, int32_t *__restrict__ ctl) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < total) dist[i] = -1;
-  if (i < n_sources) {
-    const int64_t v = sources[i] - base;
-    if (v < 0 || v >= n) report_offender(reinterpret_cast<unsigned long long *>(ctl + cOffender), v);
-  }
-}
-
-// a pass starts: nothing seen, an empty frontier; any[0] = 1: "level 0 found something" (the sources), so that level 1 runs
+// a pass starts: nothing seen, an empty frontier; "level 0 found something" (the sources), so that level 1 runs
 __global__ void hop_init_kernel(int64_t n, u64 *__restrict__ seen, u64 *__restrict__ frontier, int32_t *__restrict__ ctl) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) seen[i] = 0, frontier[i] = 0;
-  if (i < 3) ctl[cAny + i] = i == 0 ? 1 : 0;
+  rounds_arm(ctl, cTurn, i);
 }
 
 // source i of the pass takes bit i (bit 0 in union mode) of its node's words and distance 0 in its row of dist; integer atomicOr
@@ -228,11 +203,11 @@ __global__ void hop_sources_kernel(int64_t cnt, int64_t n, int base, int separat
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= cnt) return;
   const int64_t v = sources[i] - base;
-  if (v < 0 || v >= n) return;   // (reported by hop_fill_kernel)
+  if (v < 0 || v >= n) return;   // (reported by fill_sources_kernel)
   const u64 bit = separate ? 1ull << i : 1ull;
   atomicOr(&seen[v], bit);
   atomicOr(&frontier[v], bit);
-  dist[(size_t)(separate ? row0 + i : 0) * (size_t)n + (size_t)v] = 0;
+  dist[source_cell(separate, row0, i, n, v)] = 0;
 }
 
 __device__ __forceinline__ u64 wave_or(u64 v) {
@@ -254,17 +229,15 @@ __device__ __forceinline__ u64 or_entries(const HopRows &r, int64_t first, int64
   return acc;
 }
 
-// Level `level` >= 1 of a pass: node v gets distance `level` from every source whose bit reaches it now.  The three `any` words rotate
-// as the hooked words of the components do.  cur is not written by this launch and every other word a lane reads or writes is its
-// own node's, so the launch has no race.  A node that has seen every source of the pass reads no row.
+// Level `level` >= 1 of a pass: node v gets distance `level` from every source whose bit reaches it now; its cTurn word says "this
+// level found a new bit".  cur is not written by this launch and every other word a lane reads or writes is its own node's, so the
+// launch has no race.  A node that has seen every source of the pass reads no row.
 __global__ __launch_bounds__(256) void hop_level_kernel(int64_t n, int level, HopRows ra, HopRows rb, u64 pass_mask, int64_t row0,
                                                         const u64 *__restrict__ cur, u64 *__restrict__ next, u64 *__restrict__ seen,
                                                         int32_t *__restrict__ dist, int32_t *ctl) {
   const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & (kWave - 1);
-  const int go = ctl[cAny + (level + 2) % 3];
-  if (v == 0) ctl[cAny + (level + 1) % 3] = 0;
-  if (!go) return;   // (the whole grid: the level before found nothing new)
+  if (!round_go(ctl, cTurn, level, v == 0)) return;   // (the whole grid: the level before found nothing new)
   const bool live = v < n;
   const u64 mine = live ? seen[v] : 0;
   const u64 want = live ? pass_mask & ~mine : 0;
@@ -273,24 +246,14 @@ __global__ __launch_bounds__(256) void hop_level_kernel(int64_t n, int level, Ho
   for (int k = 0; k < 2; ++k) {
     const HopRows &r = k == 0 ? ra : rb;
     if (!r.ptr) continue;   // (uniform)
-    int64_t b = 0, e = 0;
-    if (want) {
-      b = r.ptr[v], e = r.ptr[v + 1];
-      if (b < 0 || e > r.nnz || b > e) {
-        ctl[cCsr] = 1;
-        b = e = 0;
-      }
-    }
+    int64_t b, e;
+    row_span(r, v, want != 0, b, e, ctl);
     const bool wide = e - b >= NGPDE_HOP_WAVE_ROW;
     if (!wide) acc |= or_entries(r, b, e, 1, n, cur, ctl);
-    u64 todo = __ballot(wide);   // the rows of this wave that the whole wave walks, one after the other
-    while (todo) {
-      const int owner = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int64_t wb = __shfl(b, owner, kWave), we = __shfl(e, owner, kWave);
+    for_wide_rows(wide, b, e, [&](int owner, int64_t wb, int64_t we) {
       const u64 part = wave_or(or_entries(r, wb + lane, we, kWave, n, cur, ctl));
       if (lane == owner) acc |= part;
-    }
+    });
   }
   if (!live) return;
   const u64 fresh = acc & want;
@@ -301,7 +264,7 @@ __global__ __launch_bounds__(256) void hop_level_kernel(int64_t n, int level, Ho
     const int bit = __ffsll((long long)bits) - 1;
     dist[(size_t)(row0 + bit) * (size_t)n + (size_t)v] = level;
   }
-  ctl[cAny + level % 3] = 1;
+  round_mark(ctl, cTurn, level);
 }
 
 // keep[i] = node i was reached
@@ -319,26 +282,8 @@ __global__ void reached_scatter_kernel(int64_t n, int base, const int32_t *__res
   if (i == n - 1) *count = pos[i] + keep[i];
 }
 
-struct HopLayout {
-  size_t seen, fr0, fr1, ctl, total;
-};
-
-HopLayout hop_layout(int64_t n) {
-  HopLayout a;
-  const size_t words = (((size_t)n * sizeof(u64)) + 255) & ~(size_t)255;
-  a.seen = 0;
-  a.fr0 = words;
-  a.fr1 = 2 * words;
-  a.ctl = 3 * words;
-  a.total = a.ctl + kCtlBytes;
-  return a;
-}
-
-int32_t read_ctl(const int32_t *ctl, int32_t *h, hipStream_t stream) {   // (synchronises)
-  NGPDE_HIP_CHECK(hipMemcpyAsync(h, ctl, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-  NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
-  return NGPDE_OK;
-}
+// the workspace: seen, the two frontiers -- hop_words(n) bytes each -- and the control block
+inline size_t hop_words(int64_t n) { return up256((size_t)n * sizeof(u64)); }
 
 int32_t check_rows(const char *fn, const char *what, int64_t nnz, const int32_t *ptr, const int32_t *other) {
   NGPDE_REQUIRE(nnz >= 0 && nnz <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "%s: %s %lld outside 0 : 2^31 - 1 (negative, or too large)", fn, what,
@@ -370,9 +315,7 @@ int32_t ngpde_coo_components(int64_t n_nodes, int64_t n_edges, const int32_t *s,
   NGPDE_REQUIRE(max_rounds >= 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: max_rounds %d is negative (0: the library's choice)", fn, max_rounds);
   NGPDE_REQUIRE(check_every >= 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: check_every %d is negative (0: no read-back)", fn, check_every);
   NGPDE_REQUIRE(labels_out || n_nodes == 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: labels_out is NULL", fn);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= kCtlBytes, NGPDE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes,
-                kCtlBytes);
-  NGPDE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: the workspace is not 8-byte aligned", fn);
+  if (int32_t st = check_workspace(fn, workspace, workspace_bytes, kCtlBytes, 8)) return st;
   if (max_rounds == 0) {   // 2 ceil(log2 N) + 8, in whole groups
     max_rounds = 2 * (int32_t)bits_for((unsigned long long)std::max<int64_t>(n_nodes, 2)) + 8;
     if (check_every > 0) max_rounds = (max_rounds + check_every - 1) / check_every * check_every;
@@ -383,29 +326,22 @@ int32_t ngpde_coo_components(int64_t n_nodes, int64_t n_edges, const int32_t *s,
   int32_t *ctl = (int32_t *)workspace;
   hipLaunchKernelGGL(cc_init_kernel, dim3(blocks_for(n_nodes)), dim3(kB), 0, stream, n_nodes, labels_out, ctl);
   NGPDE_LAUNCH_CHECK("cc_init_kernel");
-  bool done = false;
-  int32_t last = 0;
-  for (int32_t r = 1; r <= max_rounds && !done; ++r) {
-    hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, n_nodes, index_base, r, s, t, labels_out, ctl);
+  auto round = [&](int64_t r) -> int32_t {
+    hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks_for(n_edges)), dim3(kB), 0, stream, n_edges, n_nodes, index_base, (int)r, s, t, labels_out, ctl);
     NGPDE_LAUNCH_CHECK("cc_hook_kernel");
     for (int j = 0; j < jumps; ++j) {
-      hipLaunchKernelGGL(cc_compress_kernel, dim3(blocks_for(n_nodes)), dim3(kB), 0, stream, n_nodes, r, j, labels_out, ctl);
+      hipLaunchKernelGGL(cc_compress_kernel, dim3(blocks_for(n_nodes)), dim3(kB), 0, stream, n_nodes, (int)r, j, labels_out, ctl);
       NGPDE_LAUNCH_CHECK("cc_compress_kernel");
     }
-    last = r;
-    if (check_every > 0 && (r % check_every == 0 || r == max_rounds)) {   // one read-back per group of rounds
-      int32_t h[16];
-      if (int32_t st = read_ctl(ctl, h, stream)) return st;
-      NGPDE_REQUIRE(!offender_of(h), NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: an edge references node %lld, outside the %lld nodes", fn,
-                    (long long)decode_offender(offender_of(h)), (long long)n_nodes);
-      done = h[cHooked + r % 3] == 0;
-    }
-  }
+    return NGPDE_OK;
+  };
+  Rounds rounds = {check_every, ctl, stream};
+  if (int32_t st = rounds.run(max_rounds, round, [&](const int32_t *h) { return edge_error(fn, h, cOffender, n_nodes); })) return st;
   if (rounds_out) {
-    hipLaunchKernelGGL(cc_finish_kernel, dim3(1), dim3(kWave), 0, stream, last, ctl, rounds_out);
+    hipLaunchKernelGGL(cc_finish_kernel, dim3(1), dim3(kWave), 0, stream, (int)rounds.last, ctl, rounds_out);
     NGPDE_LAUNCH_CHECK("cc_finish_kernel");
   }
-  NGPDE_REQUIRE(check_every == 0 || done, NGPDE_ERR_STATE,
+  NGPDE_REQUIRE(check_every == 0 || rounds.done, NGPDE_ERR_STATE,
                 "%s: still hooking after max_rounds = %d rounds: the labels are not final (raise max_rounds)", fn, max_rounds);
   return NGPDE_OK;
 }
@@ -488,8 +424,7 @@ static int32_t coo_rows_entry(const char *fn, bool with_eid, int64_t n_nodes, in
   NGPDE_LAUNCH_CHECK("rows_other_kernel");
   int32_t h[kFlagWords];
   if ((st = read_flags(flags, h, stream))) return st;
-  NGPDE_REQUIRE(!offender_of(h), NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: an edge references node %lld, outside the %lld nodes", fn,
-                (long long)decode_offender(offender_of(h)), (long long)n_nodes);
+  if ((st = edge_error(fn, h, fOffender, n_nodes))) return st;
   NGPDE_REQUIRE(!h[fBad], NGPDE_ERR_HIP, "%s: the sort returned a position outside the list", fn);
   return NGPDE_OK;
 }
@@ -509,7 +444,7 @@ int32_t ngpde_coo_rows_eid(int64_t n_nodes, int64_t n_edges, const int32_t *s, c
 
 size_t ngpde_csr_hop_distance_workspace_bytes(int64_t n) {
   if (n < 0 || n > 0x7fffffffLL) return 0;
-  return hop_layout(n).total;
+  return 3 * hop_words(n) + kCtlBytes;
 }
 
 int32_t ngpde_csr_hop_distance(int64_t n, int64_t nnz_a, const int32_t *row_ptr_a, const int32_t *other_a, int64_t nnz_b,
@@ -530,63 +465,44 @@ int32_t ngpde_csr_hop_distance(int64_t n, int64_t nnz_a, const int32_t *row_ptr_
   NGPDE_REQUIRE(check_every >= 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: check_every %d is negative (0: no read-back)", fn, check_every);
   NGPDE_REQUIRE(check_every > 0 || max_hops >= 0, NGPDE_ERR_INVALID_ARGUMENT,
                 "%s: check_every 0 enqueues exactly max_hops levels: max_hops must be given (not negative)", fn);
-  const int64_t n_rows = separate ? n_sources : 1;
-  const int64_t total = n_rows * n;
-  NGPDE_REQUIRE(total <= ((int64_t)1 << 40), NGPDE_ERR_UNSUPPORTED, "%s: %lld sources x %lld nodes: the result is too large", fn, (long long)n_rows,
-                (long long)n);
+  int64_t total;
+  if (int32_t st = check_result(fn, n, n_sources, separate, dist_out, &total)) return st;
   if (total == 0) return NGPDE_OK;
-  NGPDE_REQUIRE(dist_out != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "%s: dist_out is NULL", fn);
-  const HopLayout lay = hop_layout(n);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= lay.total, NGPDE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes,
-                lay.total);
-  NGPDE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: the workspace is not 8-byte aligned", fn);
+  const size_t words = hop_words(n);
+  if (int32_t st = check_workspace(fn, workspace, workspace_bytes, 3 * words + kCtlBytes, 8)) return st;
   const int64_t levels = std::min<int64_t>(max_hops < 0 ? n - 1 : max_hops, n - 1);   // (a shortest path has fewer than n edges)
-  const int64_t passes = n_sources == 0 ? 0 : (separate ? (n_sources + 63) / 64 : 1);
+  const int64_t per = pass_sources(n_sources, separate), passes = (n_sources + per - 1) / per;
   NGPDE_REQUIRE(check_every > 0 || levels * passes <= kMaxUncheckedLaunches, NGPDE_ERR_UNSUPPORTED,
                 "%s: max_hops %lld with check_every 0 would enqueue %lld launches", fn, (long long)max_hops, (long long)(levels * passes));
   char *base = (char *)workspace;
-  u64 *seen = (u64 *)(base + lay.seen), *fr[2] = {(u64 *)(base + lay.fr0), (u64 *)(base + lay.fr1)};
-  int32_t *ctl = (int32_t *)(base + lay.ctl);
-  int32_t st;
-  if ((st = launch_zero(ctl, kCtlBytes, stream))) return st;
+  u64 *seen = (u64 *)base, *fr[2] = {(u64 *)(base + words), (u64 *)(base + 2 * words)};
+  int32_t *ctl = (int32_t *)(base + 3 * words);
+  if (int32_t st = launch_zero(ctl, kCtlBytes, stream)) return st;
   NGPDE_REQUIRE(blocks_for(total) <= 0x7fffffffu && total / kB <= 0x7fffffffLL, NGPDE_ERR_UNSUPPORTED, "%s: %lld cells in one launch", fn,
                 (long long)total);
-  hipLaunchKernelGGL(hop_fill_kernel, dim3(blocks_for(std::max(total, n_sources))), dim3(kB), 0, stream, total, dist_out, n_sources, sources,
-                     index_base, n, ctl);
-  NGPDE_LAUNCH_CHECK("hop_fill_kernel");
+  hipLaunchKernelGGL(fill_sources_kernel<int32_t>, dim3(blocks_for(std::max(total, n_sources))), dim3(kB), 0, stream, total, -1, dist_out, nullptr,
+                     nullptr, n_sources, sources, index_base, n, ctl);
+  NGPDE_LAUNCH_CHECK("fill_sources_kernel");
   const HopRows ra = {row_ptr_a, other_a, nnz_a}, rb = {row_ptr_b, other_b, nnz_b};
-  bool checked = false;
-  for (int64_t pass = 0; pass < passes; ++pass) {
-    const int64_t row0 = separate ? pass * 64 : 0;
-    const int64_t cnt = separate ? std::min<int64_t>(64, n_sources - row0) : n_sources;
+  auto errors = [&](const int32_t *h) { return named_errors(fn, h, n, "a row pointer or a row entry"); };
+  Rounds rounds = {check_every, ctl, stream};
+  for (int64_t row0 = 0; row0 < n_sources; row0 += per) {
+    const int64_t cnt = std::min(per, n_sources - row0);
     const u64 pass_mask = !separate ? 1ull : (cnt == 64 ? ~0ull : (1ull << cnt) - 1);
     hipLaunchKernelGGL(hop_init_kernel, dim3(blocks_for(n)), dim3(kB), 0, stream, n, seen, fr[0], ctl);
     NGPDE_LAUNCH_CHECK("hop_init_kernel");
-    hipLaunchKernelGGL(hop_sources_kernel, dim3(blocks_for(cnt)), dim3(kB), 0, stream, cnt, n, index_base, separate ? 1 : 0, row0,
-                       sources + (separate ? row0 : 0), seen, fr[0], dist_out);
+    hipLaunchKernelGGL(hop_sources_kernel, dim3(blocks_for(cnt)), dim3(kB), 0, stream, cnt, n, index_base, separate ? 1 : 0, row0, sources + row0,
+                       seen, fr[0], dist_out);
     NGPDE_LAUNCH_CHECK("hop_sources_kernel");
-    for (int64_t l = 1; l <= levels; ++l) {
-      hipLaunchKernelGGL(hop_level_kernel, dim3(blocks_for(n)), dim3(kB), 0, stream, n, (int)l, ra, rb, pass_mask, row0, fr[(l - 1) & 1],
-                         fr[l & 1], seen, dist_out, ctl);
+    auto level = [&](int64_t l) -> int32_t {
+      hipLaunchKernelGGL(hop_level_kernel, dim3(blocks_for(n)), dim3(kB), 0, stream, n, (int)l, ra, rb, pass_mask, row0, fr[(l - 1) & 1], fr[l & 1],
+                         seen, dist_out, ctl);
       NGPDE_LAUNCH_CHECK("hop_level_kernel");
-      if (check_every > 0 && (l % check_every == 0 || l == levels)) {   // one read-back per group of levels
-        int32_t h[16];
-        if ((st = read_ctl(ctl, h, stream))) return st;
-        checked = true;
-        NGPDE_REQUIRE(!offender_of(h), NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: sources lists node %lld, outside the %lld nodes", fn,
-                      (long long)decode_offender(offender_of(h)), (long long)n);
-        NGPDE_REQUIRE(!h[cCsr], NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: a row pointer or a row entry lies outside the lists", fn);
-        if (!h[cAny + l % 3]) break;
-      }
-    }
+      return NGPDE_OK;
+    };
+    if (int32_t st = rounds.run(levels, level, errors)) return st;
   }
-  if (check_every > 0 && !checked) {   // (no level ran: the sources are still to be answered for)
-    int32_t h[16];
-    if ((st = read_ctl(ctl, h, stream))) return st;
-    NGPDE_REQUIRE(!offender_of(h), NGPDE_ERR_DIMENSION_MISMATCH, "%s: DimensionMismatch: sources lists node %lld, outside the %lld nodes", fn,
-                  (long long)decode_offender(offender_of(h)), (long long)n);
-  }
-  return NGPDE_OK;
+  return rounds.answer(errors);   // (no level ran: the sources are still to be answered for)
 }
 
 int32_t ngpde_hop_reached_nodes(int64_t n, const int32_t *dist, int32_t index_base, int64_t *nodes_out, int64_t *n_out, ngpde_stream_t stream_) {

@@ -31,9 +31,23 @@ __all__ = ["Components", "connected_components", "is_connected", "split_componen
            "shortest_paths"]
 
 
-def _rounds_args(max_rounds, check_every, what="max_rounds"):
+def _check_every_arg(check_every):
     if not _is_int(check_every) or not 0 <= check_every < 2 ** 31:
         raise _arg_error(f"check_every must be an integer >= 0 (0: no read-back), not {check_every!r}")
+
+
+def _bool_args(**flags):
+    for name, flag in flags.items():
+        if not isinstance(flag, (bool, np.bool_)):
+            raise _arg_error(f"{name} must be a bool, not {flag!r}")
+
+
+def _workspace(nbytes, dev):
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+
+
+def _rounds_args(max_rounds, check_every, what="max_rounds"):
+    _check_every_arg(check_every)
     if max_rounds is not None and (not _is_int(max_rounds) or not 1 <= max_rounds < 2 ** 31):
         raise _arg_error(f"{what} must be an integer >= 1 (or None: the library's choice), not {max_rounds!r}")
     if check_every == 0 and max_rounds is None:
@@ -51,7 +65,7 @@ def _label(n, e, s, t, index_base, max_rounds, check_every, labels=None, rounds=
     if rounds is None:
         rounds = torch.empty(2, dtype=torch.int32, device=dev)
     if ws is None:
-        ws = torch.empty(int(lib.ngpde_coo_components_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+        ws = _workspace(lib.ngpde_coo_components_workspace_bytes(n), dev)
     _lib.check(lib.ngpde_coo_components(n, e, _lib.ptr(s), _lib.ptr(t), index_base, 0 if max_rounds is None else int(max_rounds), int(check_every),
                                         _lib.ptr(labels), _lib.ptr(rounds), _lib.ptr(ws), int(ws.numel()), _lib.current_stream()))
     return labels, rounds
@@ -170,34 +184,45 @@ def split_components(g):
 
 class _RowsPlan:
     """what ngpde_coo_rows wrote: the structure's rows grouped by source (code 0) or target (1) and the 0-based other end of every
-    row entry"""
+    row entry; with_eid (ngpde_coo_rows_eid): the COO position of every row entry as well"""
 
-    def __init__(self, g, code, dev):
+    def __init__(self, g, code, dev, with_eid=False):
         s, t = _coo(g, dev)
         self.nnz = g.num_edges
         self.row_ptr = torch.empty(g.num_nodes + 1, dtype=torch.int32, device=dev)
         self.other = torch.empty(self.nnz, dtype=torch.int32, device=dev)
-        _lib.check(_lib.load().ngpde_coo_rows(g.num_nodes, self.nnz, _lib.ptr(s), _lib.ptr(t), 0, code, _lib.ptr(self.row_ptr), _lib.ptr(self.other),
-                                              _lib.current_stream()))
+        self.eid = torch.empty(self.nnz, dtype=torch.int32, device=dev) if with_eid else None
+        lib = _lib.load()
+        entry, eid = (lib.ngpde_coo_rows_eid, (_lib.ptr(self.eid),)) if with_eid else (lib.ngpde_coo_rows, ())
+        _lib.check(entry(g.num_nodes, self.nnz, _lib.ptr(s), _lib.ptr(t), 0, code, _lib.ptr(self.row_ptr), _lib.ptr(self.other), *eid,
+                         _lib.current_stream()))
 
 
-def _rows_plan(g, code, dev):
-    """the structure's rows on `dev`, shared by every copy of the graph (as the key plan is): a second call sorts nothing"""
-    key = ("rows", code, str(dev))
-    p = g._shared.get(key)
-    if p is None:
-        p = g._shared[key] = _RowsPlan(g, code, dev)
-    return p
+def _row_sets(g, code, dev, with_eid=False):
+    """(a, b): the rows plans a direction code walks, b None unless "both" -- following s -> t, a node is reached from the SOURCES of
+    its incoming edges: the rows grouped by target.  A plan lives on `dev` with the structure, shared by every copy of the graph (as
+    the key plan is), those with COO positions under a key of their own: a second call sorts nothing"""
+    plans = []
+    for c in ((1,), (0,), (1, 0))[code]:
+        key = ("rows_eid" if with_eid else "rows", c, str(dev))
+        if key not in g._shared:
+            g._shared[key] = _RowsPlan(g, c, dev, with_eid)
+        plans.append(g._shared[key])
+    return plans[0], (plans[1] if len(plans) > 1 else None)
 
 
-def _hop_args(dir, max_hops, check_every, what="max_hops"):
+def _dir_code(dir):
     code = _DIRS.get(dir) if isinstance(dir, str) else None
     if code is None:
         raise _arg_error(f"dir must be 'out', 'in' or 'both', not {dir!r}")
+    return code
+
+
+def _hop_args(dir, max_hops, check_every, what="max_hops"):
+    code = _dir_code(dir)
     if max_hops is not None and (not _is_int(max_hops) or not 0 <= max_hops < 2 ** 62):
         raise _arg_error(f"{what} must be an integer >= 0{'' if what == 'd' else ' (or None: no bound)'}, not {max_hops!r}")
-    if not _is_int(check_every) or not 0 <= check_every < 2 ** 31:
-        raise _arg_error(f"check_every must be an integer >= 0 (0: no read-back), not {check_every!r}")
+    _check_every_arg(check_every)
     if check_every == 0 and max_hops is None:
         raise _arg_error("check_every=0 enqueues exactly max_hops levels without a read-back: max_hops must be given")
     return code
@@ -233,45 +258,19 @@ def hop_distance(g, sources, dir="out", max_hops=None, separate=False, check_eve
     plan exists and `sources` is an int64 device tensor the call can be captured into a HIP graph (a bad source is not raised
     there: it reaches nothing)."""
     code = _hop_args(dir, max_hops, check_every)
-    if not isinstance(separate, (bool, np.bool_)):
-        raise _arg_error(f"separate must be a bool, not {separate!r}")
+    _bool_args(separate=separate)
     sources = _node_list(sources, "hop_distance: sources")
     dev = _device()
     src = _ids(sources, dev, "hop_distance: sources")
     lib, n, k = _lib.load(), g.num_nodes, int(src.numel())
-    # following s -> t, a node is reached from the SOURCES of its incoming edges: the rows grouped by target
-    plans = [_rows_plan(g, c, dev) for c in ((1,), (0,), (1, 0))[code]]
-    a, b = plans[0], (plans[1] if len(plans) > 1 else None)
+    a, b = _row_sets(g, code, dev)
     dist = torch.empty((k, n) if separate else (n,), dtype=torch.int32, device=dev)
-    nbytes = int(lib.ngpde_csr_hop_distance_workspace_bytes(n))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.ngpde_csr_hop_distance_workspace_bytes(n), dev)
     _lib.check(lib.ngpde_csr_hop_distance(n, a.nnz, _lib.ptr(a.row_ptr), _lib.ptr(a.other), 0 if b is None else b.nnz,
                                           None if b is None else _lib.ptr(b.row_ptr), None if b is None else _lib.ptr(b.other), k, _lib.ptr(src), 0,
                                           int(bool(separate)), -1 if max_hops is None else int(max_hops), int(check_every), _lib.ptr(dist),
-                                          _lib.ptr(ws), nbytes, _lib.current_stream()))
+                                          _lib.ptr(ws), int(ws.numel()), _lib.current_stream()))
     return dist
-
-
-class _RowsEidPlan:
-    """what ngpde_coo_rows_eid wrote: _RowsPlan and the COO position of every row entry"""
-
-    def __init__(self, g, code, dev):
-        s, t = _coo(g, dev)
-        self.nnz = g.num_edges
-        self.row_ptr = torch.empty(g.num_nodes + 1, dtype=torch.int32, device=dev)
-        self.other = torch.empty(self.nnz, dtype=torch.int32, device=dev)
-        self.eid = torch.empty(self.nnz, dtype=torch.int32, device=dev)
-        _lib.check(_lib.load().ngpde_coo_rows_eid(g.num_nodes, self.nnz, _lib.ptr(s), _lib.ptr(t), 0, code, _lib.ptr(self.row_ptr),
-                                                  _lib.ptr(self.other), _lib.ptr(self.eid), _lib.current_stream()))
-
-
-def _rows_eid_plan(g, code, dev):
-    """the rows with their COO positions on `dev`, kept with the structure under a key of their own: a second call sorts nothing"""
-    key = ("rows_eid", code, str(dev))
-    p = g._shared.get(key)
-    if p is None:
-        p = g._shared[key] = _RowsEidPlan(g, code, dev)
-    return p
 
 
 class ShortestPaths:
@@ -371,13 +370,9 @@ def shortest_paths(g, sources, edge_weight=None, dir="out", separate=False, max_
     answer.  check_every=0 needs max_rounds, enqueues exactly that many rounds and reads nothing back: once the rows plan exists,
     with `sources` an int64 and `edge_weight` a float32 device tensor, the call can be captured into a HIP graph; `sp.unfinished`
     then tells what the status would have (bad sources and weights are not raised there: nothing is relaxed through them)."""
-    code = _DIRS.get(dir) if isinstance(dir, str) else None
-    if code is None:
-        raise _arg_error(f"dir must be 'out', 'in' or 'both', not {dir!r}")
+    code = _dir_code(dir)
     _rounds_args(max_rounds, check_every)
-    for name, flag in (("separate", separate), ("return_parents", return_parents)):
-        if not isinstance(flag, (bool, np.bool_)):
-            raise _arg_error(f"{name} must be a bool, not {flag!r}")
+    _bool_args(separate=separate, return_parents=return_parents)
     if max_dist is not None and (isinstance(max_dist, (bool, np.bool_)) or not isinstance(max_dist, (int, float, np.integer, np.floating))
                                  or not max_dist >= 0):
         raise _arg_error(f"max_dist must be a number >= 0 (or None: no bound), not {max_dist!r}")
@@ -388,22 +383,19 @@ def shortest_paths(g, sources, edge_weight=None, dir="out", separate=False, max_
         w = _f32_device(w, dev).detach().reshape(-1).contiguous()
     src = _ids(sources, dev, "shortest_paths: sources")
     lib, n, k = _lib.load(), g.num_nodes, int(src.numel())
-    # following s -> t, a node is relaxed from the SOURCES of its incoming edges: the rows grouped by target
-    plans = [_rows_eid_plan(g, c, dev) for c in ((1,), (0,), (1, 0))[code]]
-    a, b = plans[0], (plans[1] if len(plans) > 1 else None)
+    a, b = _row_sets(g, code, dev, with_eid=True)
     shape = (k, n) if separate else (n,)
     dist = torch.empty(shape, dtype=torch.float32, device=dev)
     parent_eid = torch.empty(shape, dtype=torch.int32, device=dev) if return_parents else None
     parents = torch.empty(shape, dtype=torch.int32, device=dev) if return_parents else None
     flags = torch.empty(2, dtype=torch.int32, device=dev)
-    nbytes = int(lib.ngpde_csr_shortest_paths_workspace_bytes(n, a.nnz, 0 if b is None else b.nnz, k, int(bool(separate))))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.ngpde_csr_shortest_paths_workspace_bytes(n, a.nnz, 0 if b is None else b.nnz, k, int(bool(separate))), dev)
     none = (0, None, None, None)
     _lib.check(lib.ngpde_csr_shortest_paths(n, a.nnz, _lib.ptr(a.row_ptr), _lib.ptr(a.other), _lib.ptr(a.eid),
                                             *(none if b is None else (b.nnz, _lib.ptr(b.row_ptr), _lib.ptr(b.other), _lib.ptr(b.eid))), k,
                                             _lib.ptr(src), 0, int(bool(separate)), _lib.ptr(w), float("inf") if max_dist is None else float(max_dist),
                                             0 if max_rounds is None else int(max_rounds), int(check_every), _lib.ptr(dist), _lib.ptr(parent_eid),
-                                            _lib.ptr(parents), _lib.ptr(flags), _lib.ptr(ws), nbytes, _lib.current_stream()))
+                                            _lib.ptr(parents), _lib.ptr(flags), _lib.ptr(ws), int(ws.numel()), _lib.current_stream()))
     return ShortestPaths(dist, parent_eid, parents, flags)
 
 

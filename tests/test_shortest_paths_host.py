@@ -262,6 +262,8 @@ def test_entries_are_declared_bound_and_cited():
         assert text in new, text
     source = open(os.path.join(root, "neuralgraphpde.jl_amd", "csrc", "graph_paths.hip")).read()
     assert "__launch_bounds__(256)" in source and "atomic" not in source.split("namespace ngpde {")[1].replace("report_offender", "")
+    shared = open(os.path.join(root, "neuralgraphpde.jl_amd", "csrc", "traverse_rounds.h")).read()          # what the round kernel includes
+    assert '#include "traverse_rounds.h"' in source and "atomic" not in shared.split("namespace ngpde {")[1].replace("report_offender", "")
 
 
 def test_argument_errors_come_before_any_device_call():

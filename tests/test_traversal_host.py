@@ -237,6 +237,7 @@ def test_entries_are_declared_bound_and_cited():
     assert "NGPDE_HOP_WAVE_ROW 64" in block and "stale reads" in block and "atomicMin" in block
     makefile = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "neuralgraphpde.jl_amd", "csrc", "Makefile")).read()
     assert "coo_rows.h" in makefile and "coo_compact.h" in makefile and "device_scratch.h" in makefile          # what the new file includes
+    assert "traverse_rounds.h" in makefile.split("HDRS :=")[1].split("\n")[0]
 
 
 def test_argument_errors_come_before_any_device_call():
@@ -280,6 +281,32 @@ def test_argument_errors_come_before_any_device_call():
 # ---- the C entries --------------------------------------------------------------------------------------------------------------
 
 ONE = C.c_void_p(16)     # (never dereferenced: the checks come before any device call)
+
+
+def test_workspace_bytes_are_the_formulas_of_the_header():
+    """include/ngpde.h, written out: components 256 (the control block); hop distances 3 * (8 n rounded up to 256) + 256; shortest
+    paths (2 x 4 n width + 4 nnz_a + 4 nnz_b, each term rounded up to 256) + 256 with width = 1 for one row of dist_out, else
+    min(n_sources, NGPDE_SSSP_PASS = 64) rounded up to a multiple of NGPDE_SSSP_LANE_SOURCES = 4; 0 for the sizes they refuse"""
+    lib = _lib.load()
+    up = lambda x: (x + 255) // 256 * 256
+    refused = (-1, 2 ** 31)
+    for n in (0, 1, 31, 32, 33):
+        assert lib.ngpde_coo_components_workspace_bytes(n) == 256
+        assert lib.ngpde_csr_hop_distance_workspace_bytes(n) == 3 * up(8 * n) + 256
+        for nnz in (0, 1, 64):
+            for k in (0, 1, 4, 5, 64, 65):
+                for separate in (0, 1):
+                    width = 1 if not separate or min(k, 64) <= 1 else (min(k, 64) + 3) // 4 * 4
+                    want = 2 * up(4 * n * width) + up(4 * nnz) + up(4 * nnz) + 256
+                    assert lib.ngpde_csr_shortest_paths_workspace_bytes(n, nnz, nnz, k, separate) == want, (n, nnz, k, separate)
+                    assert lib.ngpde_csr_shortest_paths_workspace_bytes(n, nnz, 0, k, separate) == want - up(4 * nnz), (n, nnz, k, separate)
+    for bad in refused:
+        assert lib.ngpde_coo_components_workspace_bytes(bad) == 0 and lib.ngpde_csr_hop_distance_workspace_bytes(bad) == 0
+        for separate in (0, 1):
+            for at in range(4):
+                sizes = [33, 64, 64, 5]
+                sizes[at] = bad
+                assert lib.ngpde_csr_shortest_paths_workspace_bytes(*sizes, separate) == 0, (sizes, separate)
 
 
 def test_components_entries_refuse_null_and_negative_arguments():
