@@ -9,8 +9,6 @@ using namespace ngpde;
 
 namespace {
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // one block of the Dense kernels' segmented-input table
 SegTable one_seg(const float *ptr, int width) {
   SegTable t;
@@ -39,29 +37,59 @@ int32_t check_common(const char *fn, const ngpde_graph_t *g, int32_t din, int32_
   return NGPDE_OK;
 }
 
+// the forward's one region; the fused path needs none.  Any width: the Dense part on the fp32-MFMA kernels of dense_mfma.hip, and
+// the region holds the aggregated input (dout >= din) or the split-K partial products of W x (dout < din)
+float *gcn_fwd_layout(Workspace &w, const ngpde_graph_t *g, int32_t din, int32_t dout) {
+  if (fused_supported(din, dout)) return nullptr;
+  const size_t n = (size_t)g->n_nodes;
+  const size_t parts = dout < din ? (size_t)dense_fwd_split_count(din, dense_fwd_splits((int64_t)n, din, dout)) : 1;
+  return w.take<float>(n * (dout < din ? (size_t)dout * parts : (size_t)std::max(din, dout)));
+}
+
+struct GcnBwdWs {
+  float *slab_dw, *slab_db, *gbuf;   // fused: the weight and bias slabs of the blocks (zeroed as one span), dz W^T
+  float *dz, *tmp, *partial;         // any width: dz, one [N][max] buffer, the weight pullback's slabs
+  float *ew_dx, *ew_xw, *ew_nd;      // behind those when dedge_weight is asked for
+};
+constexpr size_t kGcnSlack = 256;    // what the queries add behind the pullback's own pieces; the ew pieces start after it
+
+void gcn_bwd_layout(Workspace &w, const ngpde_graph_t *g, int32_t din, int32_t dout, bool ew, GcnBwdWs &p) {
+  const size_t n = (size_t)g->n_nodes;
+  p = GcnBwdWs{};
+  if (fused_supported(din, dout)) {
+    const size_t nb = (size_t)fused_num_blocks(g->n_nodes);
+    p.slab_dw = w.take<float>(nb * (size_t)din * dout);
+    p.slab_db = w.take<float>(nb * (size_t)dout);
+    p.gbuf = w.take<float>(n * din);
+  } else {
+    const size_t dmax = (size_t)std::max(din, dout);
+    p.dz = w.take<float>(n * dmax);
+    p.tmp = w.take<float>(n * dmax);
+    // this region serves two users: the weight pullback's slabs (chunks x (din + 1) x dout) and, when dout < din, the two-stage
+    // column sums of the bias gradient (launch_colsum2: kColsumChunks x dout) -- with narrow layers the second is the larger one
+    const size_t slabs = (size_t)dense_weight_chunks((int64_t)n, din, dout) * (din + 1) * dout;
+    p.partial = w.take<float>(std::max(slabs, (size_t)kColsumChunks * dout));
+  }
+  w.take<char>(kGcnSlack);
+  if (!ew) return;
+  // dx (the caller may pass none), x W (Dout < Din: the array that entered the propagation), the per-node degree terms
+  p.ew_dx = w.take<float>(n * din);
+  p.ew_xw = w.take<float>(n * (size_t)std::min(din, dout));
+  p.ew_nd = w.take<float>(n);
+}
+
+size_t gcn_bwd_bytes(const ngpde_graph_t *g, int32_t din, int32_t dout, bool ew) {
+  GcnBwdWs p;
+  return measure(gcn_bwd_layout, g, din, dout, ew, p);
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t ngpde_gcn_workspace_bytes(const ngpde_graph_t *g, int32_t din, int32_t dout, int32_t backward) {
   if (!g) return 0;
-  const size_t n = (size_t)g->n_nodes;
-  if (fused_supported(din, dout)) {
-    if (!backward) return 256;
-    const size_t nb = (size_t)fused_num_blocks(g->n_nodes);
-    return align256(nb * (size_t)din * dout * 4) + align256(nb * (size_t)dout * 4) + align256(n * din * 4) + 256;
-  }
-  // any-width path: the Dense part on the fp32-MFMA kernels of dense_mfma.hip.  Forward: the aggregated input (dout >= din) or
-  // the split-K partial products of W x (dout < din); backward: dz, one [N][max] buffer, the weight-pullback slabs.
-  const size_t dmax = (size_t)std::max(din, dout);
-  if (!backward) {
-    const size_t parts = dout < din ? (size_t)dense_fwd_split_count(din, dense_fwd_splits((int64_t)n, din, dout)) : 1;
-    return align256(n * (dout < din ? (size_t)dout * parts : dmax) * 4) + 256;
-  }
-  // the third region serves two users: the weight pullback's slabs (chunks x (din + 1) x dout) and, when dout < din, the two-stage
-  // column sums of the bias gradient (launch_colsum2: kColsumChunks x dout) -- with narrow layers the second is the larger one
-  const size_t slabs = (size_t)dense_weight_chunks((int64_t)n, din, dout) * (din + 1) * dout;
-  return 2 * align256(n * dmax * 4) + align256(std::max(slabs, (size_t)kColsumChunks * dout) * 4) + 256;
+  return backward ? gcn_bwd_bytes(g, din, dout, false) : measure(gcn_fwd_layout, g, din, dout) + kGcnSlack;
 }
 
 int32_t ngpde_gcn_forward(const ngpde_graph_t *g, int32_t din, int32_t dout, int32_t act, const float *x,
@@ -80,10 +108,9 @@ int32_t ngpde_gcn_forward(const ngpde_graph_t *g, int32_t din, int32_t dout, int
     a.save_agg = save_agg; a.save_z = save_z;
     return launch_fused_fwd(a, stream);
   }
-  const size_t need = ngpde_gcn_workspace_bytes(g, din, dout, 0);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= need, NGPDE_ERR_WORKSPACE,
-                "ngpde_gcn_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
-  float *tmp = (float *)workspace;
+  if ((st = check_workspace("ngpde_gcn_forward", workspace, workspace_bytes, ngpde_gcn_workspace_bytes(g, din, dout, 0), 1))) return st;
+  Workspace w(workspace);
+  float *tmp = gcn_fwd_layout(w, g, din, dout);
   if (dout >= din) {  // aggregate, then multiply (src/layers.jl:235-237)
     float *agg = save_agg ? save_agg : tmp;
     if ((st = launch_spmm_generic(g, false, true, din, NGPDE_AGGR_SUM, x, nullptr, agg, stream))) return st;
@@ -100,13 +127,6 @@ int32_t ngpde_gcn_forward(const ngpde_graph_t *g, int32_t din, int32_t dout, int
 }  // extern "C"
 
 namespace {
-// extra bytes behind ngpde_gcn_workspace_bytes(.., 1) when the gradient w.r.t. the edge_weight argument is asked for: dx (the
-// caller may pass none), x W (Dout < Din: the array that entered the propagation), the per-node degree terms
-size_t ew_extra_bytes(const ngpde_graph_t *g, int32_t din, int32_t dout) {
-  const size_t n = (size_t)g->n_nodes;
-  return align256(n * din * 4) + align256(n * (size_t)std::min(din, dout) * 4) + align256(n * 4);
-}
-
 // bias: only read when dedge_weight is asked for and Dout < Din (x3 = z - bias there)
 int32_t gcn_backward_impl(const char *fn, const ngpde_graph_t *g, int32_t din, int32_t dout, int32_t act, const float *x, const float *weight,
                           const float *bias, const float *z, const float *saved_agg, const float *dy, float *dx, float *dweight, float *dbias,
@@ -125,25 +145,18 @@ int32_t gcn_backward_impl(const char *fn, const ngpde_graph_t *g, int32_t din, i
   NGPDE_REQUIRE(dout >= din || x, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gcn_backward: x is NULL");
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t n = g->n_nodes;
-  const size_t base = ngpde_gcn_workspace_bytes(g, din, dout, 1);
-  const size_t need = base + (dedge_weight ? ew_extra_bytes(g, din, dout) : 0);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= need, NGPDE_ERR_WORKSPACE,
-                "ngpde_gcn_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
-  char *ws = (char *)workspace;
-  float *ew_dx = nullptr, *ew_xw = nullptr, *ew_nd = nullptr;
+  if ((st = check_workspace(fn, workspace, workspace_bytes, gcn_bwd_bytes(g, din, dout, dedge_weight != nullptr), 1))) return st;
+  Workspace w(workspace);
+  GcnBwdWs p;
+  gcn_bwd_layout(w, g, din, dout, dedge_weight != nullptr, p);
+  float *const ew_xw = p.ew_xw, *const ew_nd = p.ew_nd;
   if (dedge_weight) {
     NGPDE_REQUIRE(x != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gcn_backward_ew: x is NULL");
-    ew_dx = (float *)(ws + base);
-    ew_xw = (float *)(ws + base + align256((size_t)n * din * 4));
-    ew_nd = (float *)(ws + base + align256((size_t)n * din * 4) + align256((size_t)n * (size_t)std::min(din, dout) * 4));
-    if (!dx) dx = ew_dx;      // the degree term needs the layer's input gradient
+    if (!dx) dx = p.ew_dx;      // the degree term needs the layer's input gradient
   }
   if (fused_supported(din, dout)) {
-    const size_t nb = (size_t)fused_num_blocks(n);
-    float *slab_dw = (float *)ws;
-    float *slab_db = (float *)(ws + align256(nb * (size_t)din * dout * 4));
-    float *gbuf = (float *)((char *)slab_db + align256(nb * (size_t)dout * 4));
-    { const int32_t zs = launch_zero(slab_dw, (size_t)((char *)gbuf - ws), stream); if (zs) return zs; }
+    float *const slab_dw = p.slab_dw, *const slab_db = p.slab_db, *const gbuf = p.gbuf;
+    { const int32_t zs = launch_zero(slab_dw, (size_t)((char *)gbuf - (char *)slab_dw), stream); if (zs) return zs; }
     FusedBwdArgs a;
     a.g = g; a.d = din; a.act = act; a.aggregate = false; a.g_in = dy;
     a.do_dense = true; a.z = z; a.saved_agg = saved_agg; a.wt = weight; a.g_out = gbuf;
@@ -161,10 +174,7 @@ int32_t gcn_backward_impl(const char *fn, const ngpde_graph_t *g, int32_t din, i
     if (dedge_weight) return launch_gcn_edge_weight_grad(g, din, gbuf, saved_agg, nullptr, dx, x, ew_nd, dedge_weight, stream);
     return NGPDE_OK;
   }
-  const size_t dmax = (size_t)std::max(din, dout);
-  float *dz = (float *)ws;
-  float *tmp = (float *)(ws + align256((size_t)n * dmax * 4));
-  float *partial = (float *)(ws + 2 * align256((size_t)n * dmax * 4));
+  float *const dz = p.dz, *const tmp = p.tmp, *const partial = p.partial;
   if ((st = launch_act_bwd(n * dout, act, dy, z, dz, stream))) return st;
   if (dout >= din) {   // y = act(agg W + b): dW = agg^T dz, db = column sums of dz (the weight pullback's bias row), dx = A^T (dz W^T)
     if ((st = launch_dense_seg_bwd_weight(n, one_seg(saved_agg, din), din, dout, dz, dweight, dbias, partial, stream))) return st;
@@ -203,7 +213,7 @@ int32_t ngpde_gcn_backward(const ngpde_graph_t *g, int32_t din, int32_t dout, in
 
 size_t ngpde_gcn_backward_ew_workspace_bytes(const ngpde_graph_t *g, int32_t din, int32_t dout) {
   if (!g) return 0;
-  return ngpde_gcn_workspace_bytes(g, din, dout, 1) + ew_extra_bytes(g, din, dout);
+  return gcn_bwd_bytes(g, din, dout, true);
 }
 
 int32_t ngpde_gcn_backward_ew(const ngpde_graph_t *g, int32_t din, int32_t dout, int32_t act, const float *x, const float *weight,

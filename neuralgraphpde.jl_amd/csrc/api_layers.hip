@@ -26,18 +26,6 @@ namespace {
 constexpr int kMaxL = NGPDE_MLP_MAX_LAYERS;
 constexpr int kMaxBlocks = 4;   // input blocks of one Dense (ngpde_dense_forward)
 
-// Bump allocator over the workspace in units of floats, 256-byte granules; with base == nullptr it only measures.
-struct Arena {
-  float *base = nullptr;
-  size_t off = 0;
-  float *take(size_t floats) {
-    float *p = base ? base + off : nullptr;
-    off += (floats + 63) & ~(size_t)63;
-    return p;
-  }
-  void *take_bytes(size_t bytes) { return take((bytes + 3) / 4); }
-};
-
 constexpr size_t kArenaSlack = 256;   // the arena starts at the first 256-byte boundary inside the caller's buffer
 inline float *arena_base(void *workspace) {
   return reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(workspace) + (kArenaSlack - 1)) & ~(uintptr_t)(kArenaSlack - 1));
@@ -145,8 +133,8 @@ int32_t check_mlp(const char *what, const ngpde_mlp_t &m, int min_layers) {
   return NGPDE_OK;
 }
 
-// Fills the plan for (graph, descriptor, training).  a.base == nullptr: sizes only.
-int32_t make_plan(const ngpde_graph *g, const ngpde_edge_layer_t &L, bool training, Arena &a, Plan &p) {
+// Fills the plan for (graph, descriptor, training).  a without a base: sizes only.
+int32_t make_plan(const ngpde_graph *g, const ngpde_edge_layer_t &L, bool training, Workspace &a, Plan &p) {
   NGPDE_REQUIRE(L.kind >= NGPDE_LAYER_EDGECONV && L.kind <= NGPDE_LAYER_MPPDE, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_edge_layer: unknown kind %d", L.kind);
   NGPDE_REQUIRE(L.aggr >= NGPDE_AGGR_SUM && L.aggr <= NGPDE_AGGR_MUL, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_edge_layer: unknown aggregation %d", L.aggr);
   NGPDE_REQUIRE(L.n_state >= 1 && L.n_state <= 4, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_edge_layer: 1..4 state blocks, got %d", L.n_state);
@@ -251,45 +239,45 @@ int32_t make_plan(const ngpde_graph *g, const ngpde_edge_layer_t &L, bool traini
   }
 
   // ---- forward region
-  p.wA = a.take((size_t)p.rows.out_rows[0] * p.h1);
-  p.wB = a.take((size_t)p.rows.out_rows[1] * p.h1);
-  p.wD = p.de ? a.take((size_t)p.de * p.h1) : nullptr;
-  p.P = a.take(N * p.h1);
-  p.Q = a.take(N * p.h1);
-  p.Et = p.de ? a.take(E * p.h1) : nullptr;
+  p.wA = a.take<float>((size_t)p.rows.out_rows[0] * p.h1);
+  p.wB = a.take<float>((size_t)p.rows.out_rows[1] * p.h1);
+  p.wD = p.de ? a.take<float>((size_t)p.de * p.h1) : nullptr;
+  p.P = a.take<float>(N * p.h1);
+  p.Q = a.take<float>(N * p.h1);
+  p.Et = p.de ? a.take<float>(E * p.h1) : nullptr;
   for (int l = 0; l <= kMaxL; ++l) p.save[l] = nullptr;
   for (int l = 0; l < kMaxL; ++l) p.ty[l] = p.tz[l] = p.ua[l] = p.uz[l] = nullptr;
   if (p.fused_msg) {
     if (training && !p.fused_bwd) {
-      p.save[0] = a.take(E * p.h1);
-      for (int l = 0; l < p.n_tail; ++l) p.save[l + 1] = a.take(E * p.tail_dout[l]);
+      p.save[0] = a.take<float>(E * p.h1);
+      for (int l = 0; l < p.n_tail; ++l) p.save[l + 1] = a.take<float>(E * p.tail_dout[l]);
     }
   } else {
-    p.a0 = a.take(E * p.h1);
-    p.z0 = (training && p.act1 != 0) ? a.take(E * p.h1) : nullptr;
+    p.a0 = a.take<float>(E * p.h1);
+    p.z0 = (training && p.act1 != 0) ? a.take<float>(E * p.h1) : nullptr;
     for (int l = 0; l < p.n_tail; ++l) {
-      p.ty[l] = a.take(E * p.tail_dout[l]);
-      p.tz[l] = (training && p.tail_act[l] != 0) ? a.take(E * p.tail_dout[l]) : nullptr;
+      p.ty[l] = a.take<float>(E * p.tail_dout[l]);
+      p.tz[l] = (training && p.tail_act[l] != 0) ? a.take<float>(E * p.tail_dout[l]) : nullptr;
     }
   }
   // (ExplicitEdgeConv: the aggregate IS y -- kept here too where the pullback of max / min / * needs it)
-  p.m = (p.n_upd || (training && !p.fused_msg && p.aggr >= NGPDE_AGGR_MAX)) ? a.take(N * p.mw) : nullptr;
+  p.m = (p.n_upd || (training && !p.fused_msg && p.aggr >= NGPDE_AGGR_MAX)) ? a.take<float>(N * p.mw) : nullptr;
   if (p.n_upd) {
     const ngpde_mlp_t &u = L.update;
     p.U.ptr[p.u_m] = p.m ? p.m : reinterpret_cast<const float *>((uintptr_t)256);   // (measuring pass: any aligned non-NULL address)
     p.chain2 = p.n_upd >= 2;
     if (p.chain2) {
       p.chain2_fused = ngpde_dense_chain2_fused(p.N, p.U.n, p.U.ptr, p.U.width, p.U.row_div, u.dims[1], u.dims[2]) == 1;
-      p.ua[0] = (training || !p.chain2_fused) ? a.take(N * u.dims[1]) : nullptr;
+      p.ua[0] = (training || !p.chain2_fused) ? a.take<float>(N * u.dims[1]) : nullptr;
     }
     for (int l = 0; l < p.n_upd; ++l) {
-      if (l + 1 < p.n_upd && !(p.chain2 && l == 0)) p.ua[l] = a.take(N * u.dims[l + 1]);
-      p.uz[l] = (training && u.act[l] != 0) ? a.take(N * u.dims[l + 1]) : nullptr;
+      if (l + 1 < p.n_upd && !(p.chain2 && l == 0)) p.ua[l] = a.take<float>(N * u.dims[l + 1]);
+      p.uz[l] = (training && u.act[l] != 0) ? a.take<float>(N * u.dims[l + 1]) : nullptr;
     }
   }
-  p.fwd_floats = a.off;
+  p.fwd_floats = a.bytes() / sizeof(float);
   if (!training) {
-    p.total_floats = a.off;
+    p.total_floats = a.bytes() / sizeof(float);
     return NGPDE_OK;
   }
 
@@ -299,33 +287,33 @@ int32_t make_plan(const ngpde_graph *g, const ngpde_edge_layer_t &L, bool traini
   for (int l = 0; l < p.n_upd; ++l) nmax = std::max(nmax, (int)L.update.dims[l + 1]);
   size_t wsb = 0;
   auto dense_ws = [&](int64_t n, int din, int dout) { wsb = std::max(wsb, ngpde_dense_workspace_bytes(n, din, dout)); };
-  p.dm = p.n_upd ? a.take(N * p.mw) : nullptr;
+  p.dm = p.n_upd ? a.take<float>(N * p.mw) : nullptr;
   if (p.n_upd) {
-    p.ng[0] = a.take(N * nmax);
-    p.ng[1] = a.take(N * nmax);
+    p.ng[0] = a.take<float>(N * nmax);
+    p.ng[1] = a.take<float>(N * nmax);
     for (int i = 0; i < p.U.n; ++i)
-      if (p.U.state_of[i] >= 0) p.dU[i] = a.take(N * p.U.width[i]);
+      if (p.U.state_of[i] >= 0) p.dU[i] = a.take<float>(N * p.U.width[i]);
     dense_ws(p.N, p.U.total(), L.update.dims[1]);
     for (int l = 1; l < p.n_upd; ++l) dense_ws(p.N, L.update.dims[l], L.update.dims[l + 1]);
   }
-  p.dP = a.take(N * p.h1);
-  p.dQ = a.take(N * p.h1);
+  p.dP = a.take<float>(N * p.h1);
+  p.dQ = a.take<float>(N * p.h1);
   if (p.fused_bwd) {
     p.need_dE = p.de > 0 || ngpde_edge_mlp_backward_needs_edge_buffer(g, p.h1, p.act1, p.de > 0, p.n_tail, p.n_tail ? p.tail_dout : nullptr,
                                                                        p.n_tail ? p.tail_act : nullptr, p.aggr) == 1;
     wsb = std::max(wsb, ngpde_edge_mlp_backward_workspace_bytes(g, p.h1, p.n_tail, p.n_tail ? p.tail_dout : nullptr));
-    p.dE = p.need_dE ? a.take(E * p.h1) : nullptr;
+    p.dE = p.need_dE ? a.take<float>(E * p.h1) : nullptr;
   } else {
-    p.eg[0] = a.take(E * emax);
-    p.eg[1] = a.take(E * emax);
-    p.ea = p.fused_msg ? a.take(E * emax) : nullptr;
-    p.dE = a.take(E * p.h1);
+    p.eg[0] = a.take<float>(E * emax);
+    p.eg[1] = a.take<float>(E * emax);
+    p.ea = p.fused_msg ? a.take<float>(E * emax) : nullptr;
+    p.dE = a.take<float>(E * p.h1);
     int prev = p.h1;
     for (int l = 0; l < p.n_tail; ++l) { dense_ws(p.E, prev, p.tail_dout[l]); prev = p.tail_dout[l]; }
   }
-  p.dwA = a.take((size_t)p.rows.out_rows[0] * p.h1);
-  p.dwB = a.take((size_t)p.rows.out_rows[1] * p.h1);
-  p.dwD = p.de ? a.take((size_t)p.de * p.h1) : nullptr;
+  p.dwA = a.take<float>((size_t)p.rows.out_rows[0] * p.h1);
+  p.dwB = a.take<float>((size_t)p.rows.out_rows[1] * p.h1);
+  p.dwD = p.de ? a.take<float>((size_t)p.de * p.h1) : nullptr;
   if (p.de) dense_ws(p.E, p.de, p.h1);
   // the pair's pullback in one launch: both halves 64 wide, the shared leading block the only one that wants a gradient
   size_t pair_ws = 0;
@@ -337,14 +325,14 @@ int32_t make_plan(const ngpde_graph *g, const ngpde_edge_layer_t &L, bool traini
   wsb = std::max(wsb, pair_ws);
   for (int i = 0; i < p.A.n; ++i)
     if (p.A.state_of[i] >= 0) {
-      p.dA[i] = a.take(N * p.A.width[i]);
-      if (!p.pair_shared) p.dB[i] = a.take(N * p.B.width[i]);
+      p.dA[i] = a.take<float>(N * p.A.width[i]);
+      if (!p.pair_shared) p.dB[i] = a.take<float>(N * p.B.width[i]);
     }
   dense_ws(p.N, p.A.total(), p.h1);
   dense_ws(p.N, p.B.total(), p.h1);
   p.ws_bytes = wsb;
-  p.ws = a.take_bytes(wsb);
-  p.total_floats = a.off;
+  p.ws = a.take<char>(wsb);
+  p.total_floats = a.bytes() / sizeof(float);
   return NGPDE_OK;
 }
 
@@ -383,7 +371,7 @@ struct GnoPlan {
   size_t ws_bytes = 0, total_floats = 0;
 };
 
-int32_t make_gno_plan(const ngpde_graph *g, const ngpde_gno_layer_t &L, bool training, Arena &a, GnoPlan &p) {
+int32_t make_gno_plan(const ngpde_graph *g, const ngpde_gno_layer_t &L, bool training, Workspace &a, GnoPlan &p) {
   NGPDE_REQUIRE(L.in_chs > 0 && L.out_chs > 0, NGPDE_ERR_DIMENSION_MISMATCH, "ngpde_gno_layer: in_chs / out_chs must be positive");
   NGPDE_REQUIRE(L.aggr >= NGPDE_AGGR_SUM && L.aggr <= NGPDE_AGGR_MUL, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_layer: unknown aggregation %d", L.aggr);
   NGPDE_REQUIRE(L.act >= NGPDE_ACT_IDENTITY && L.act <= NGPDE_ACT_SOFTPLUS, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_layer: unknown activation %d", L.act);
@@ -420,77 +408,77 @@ int32_t make_gno_plan(const ngpde_graph *g, const ngpde_gno_layer_t &L, bool tra
   const size_t msg_w = (size_t)p.cout;
   for (int l = 0; l < kMaxL; ++l) p.ty[l] = p.tz[l] = nullptr;
   // ---- forward region
-  if (p.ds) { p.wa = a.take((size_t)p.ds * p.h1); p.wb = a.take((size_t)p.ds * p.h1); }
-  if (p.de) p.wd = a.take((size_t)p.de * p.h1);
-  if (p.ds) { p.P = a.take(N * p.h1); p.Q = a.take(N * p.h1); }
-  if (p.de) p.Et = a.take(E * p.h1);
+  if (p.ds) { p.wa = a.take<float>((size_t)p.ds * p.h1); p.wb = a.take<float>((size_t)p.ds * p.h1); }
+  if (p.de) p.wd = a.take<float>((size_t)p.de * p.h1);
+  if (p.ds) { p.P = a.take<float>(N * p.h1); p.Q = a.take<float>(N * p.h1); }
+  if (p.de) p.Et = a.take<float>(E * p.h1);
   if (p.reassoc) {
     if (!p.gform || training) {
-      p.wr = a.take((size_t)p.cin * p.cout * p.kdim);
-      p.T = a.take(N * p.cout * p.kdim);
+      p.wr = a.take<float>((size_t)p.cin * p.cout * p.kdim);
+      p.T = a.take<float>(N * p.cout * p.kdim);
     }
-    if (p.has_b2 && !p.gform) p.Bh = a.take(N * p.cout);
+    if (p.has_b2 && !p.gform) p.Bh = a.take<float>(N * p.cout);
   }
   if (p.gform) {
-    p.G = a.take(N * p.cin * p.kdim);
-    if (p.has_b2) p.hs = a.take(N * p.cin);
+    p.G = a.take<float>(N * p.cin * p.kdim);
+    if (p.has_b2) p.hs = a.take<float>(N * p.cin);
     p.nsplit = ngpde_gno_gform_splits(p.N, p.cin, p.kdim, p.cout);
-    p.slabs = a.take((size_t)(p.nsplit + 2) * N * p.cout);   // + the b2 term and W h, formed in the same launch
+    p.slabs = a.take<float>((size_t)(p.nsplit + 2) * N * p.cout);   // + the b2 term and W h, formed in the same launch
   } else {
-    p.Wh = a.take(N * p.cout);
+    p.Wh = a.take<float>(N * p.cout);
   }
   if (p.fused_msg) {
-    p.a = training ? a.take(E * p.kdim) : nullptr;
+    p.a = training ? a.take<float>(E * p.kdim) : nullptr;
   } else {
-    p.a0 = a.take(E * p.h1);
-    p.z0 = (training && p.act1 != 0) ? a.take(E * p.h1) : nullptr;
+    p.a0 = a.take<float>(E * p.h1);
+    p.z0 = (training && p.act1 != 0) ? a.take<float>(E * p.h1) : nullptr;
     for (int l = 0; l < p.n_mid; ++l) {
-      p.ty[l] = a.take(E * phi.dims[l + 2]);
-      p.tz[l] = (training && phi.act[l + 1] != 0) ? a.take(E * phi.dims[l + 2]) : nullptr;
+      p.ty[l] = a.take<float>(E * phi.dims[l + 2]);
+      p.tz[l] = (training && phi.act[l + 1] != 0) ? a.take<float>(E * phi.dims[l + 2]) : nullptr;
     }
   }
   if (!p.gform) {
-    p.m = a.take(E * msg_w);
-    p.agg = a.take(N * msg_w);
+    p.m = a.take<float>(E * msg_w);
+    p.agg = a.take<float>(N * msg_w);
   }
-  p.zt = (training && p.act != 0) ? a.take(N * msg_w) : nullptr;
+  p.zt = (training && p.act != 0) ? a.take<float>(N * msg_w) : nullptr;
   if (!training) {
-    p.total_floats = a.off;
+    p.total_floats = a.bytes() / sizeof(float);
     return NGPDE_OK;
   }
   // ---- pullback scratch
   size_t wsb = ngpde_bias_act_workspace_bytes(p.cout);
   auto dense_ws = [&](int64_t n, int din, int dout) { wsb = std::max(wsb, ngpde_dense_workspace_bytes(n, din, dout)); };
-  p.dz = a.take(N * msg_w);
-  if (p.fused_agg && p.aggr == NGPDE_AGGR_MEAN) { p.dagg_s = a.take(N * msg_w); p.inv = a.take(N); }
+  p.dz = a.take<float>(N * msg_w);
+  if (p.fused_agg && p.aggr == NGPDE_AGGR_MEAN) { p.dagg_s = a.take<float>(N * msg_w); p.inv = a.take<float>(N); }
   if (p.reassoc) {
-    p.dT = a.take(N * p.cout * p.kdim);
-    p.dwr = a.take((size_t)p.cin * p.cout * p.kdim);
-    p.dxT = a.take(N * p.cin);
-    if (p.has_b2) { p.dBh = a.take(N * p.cout); p.dxB = a.take(N * p.cin); p.dsum = a.take(N * p.cin); }
+    p.dT = a.take<float>(N * p.cout * p.kdim);
+    p.dwr = a.take<float>((size_t)p.cin * p.cout * p.kdim);
+    p.dxT = a.take<float>(N * p.cin);
+    if (p.has_b2) { p.dBh = a.take<float>(N * p.cout); p.dxB = a.take<float>(N * p.cin); p.dsum = a.take<float>(N * p.cin); }
     dense_ws(p.N, p.cin, p.cout * p.kdim);
   } else {
-    p.dxC = a.take(N * p.cin);
+    p.dxC = a.take<float>(N * p.cin);
     wsb = std::max(wsb, (size_t)p.E * p.cin * sizeof(float));
   }
-  p.dxW = a.take(N * p.cin);
+  p.dxW = a.take<float>(N * p.cin);
   dense_ws(p.N, p.cin, p.cout);
-  p.dzE = a.take(E * p.h1);
-  if (p.ds) { p.dP = a.take(N * p.h1); p.dQ = a.take(N * p.h1); p.dwa = a.take((size_t)p.ds * p.h1); p.dwb = a.take((size_t)p.ds * p.h1); dense_ws(p.N, p.ds, p.h1); }
-  if (p.de) { p.dwd = a.take((size_t)p.de * p.h1); dense_ws(p.E, p.de, p.h1); }
-  if (!p.fused_agg) p.dm = a.take(E * msg_w);
+  p.dzE = a.take<float>(E * p.h1);
+  if (p.ds) { p.dP = a.take<float>(N * p.h1); p.dQ = a.take<float>(N * p.h1); p.dwa = a.take<float>((size_t)p.ds * p.h1); p.dwb = a.take<float>((size_t)p.ds * p.h1); dense_ws(p.N, p.ds, p.h1); }
+  if (p.de) { p.dwd = a.take<float>((size_t)p.de * p.h1); dense_ws(p.E, p.de, p.h1); }
+  if (!p.fused_agg) p.dm = a.take<float>(E * msg_w);
   if (!p.fused_msg) {
     int emax = p.h1;
     for (int l = 0; l <= p.n_mid; ++l) emax = std::max(emax, (int)phi.dims[l + 1]);
-    p.eg[0] = a.take(E * emax);
-    p.eg[1] = a.take(E * emax);
+    p.eg[0] = a.take<float>(E * emax);
+    p.eg[1] = a.take<float>(E * emax);
     for (int l = 0; l < p.n_mid; ++l) dense_ws(p.E, phi.dims[l + 1], phi.dims[l + 2]);
   } else if (!p.fused_agg) {
-    p.eg[0] = a.take(E * p.kdim);
+    p.eg[0] = a.take<float>(E * p.kdim);
   }
   p.ws_bytes = wsb;
-  p.ws = a.take_bytes(wsb);
-  p.total_floats = a.off;
+  p.ws = a.take<char>(wsb);
+  p.total_floats = a.bytes() / sizeof(float);
   return NGPDE_OK;
 }
 
@@ -516,7 +504,7 @@ extern "C" {
 
 size_t ngpde_edge_layer_workspace_bytes(const ngpde_graph_t *g, const ngpde_edge_layer_t *L, int32_t training) {
   if (!g || !L) return 0;
-  Arena a;
+  Workspace a;
   Plan p;
   if (make_plan(g, *L, training != 0, a, p) != NGPDE_OK) return 0;
   return p.total_floats * sizeof(float) + kArenaSlack;
@@ -527,14 +515,12 @@ int32_t ngpde_edge_layer_forward(const ngpde_graph_t *g, const ngpde_edge_layer_
   NGPDE_RANGE();
   int32_t st;
   if ((st = check_common("ngpde_edge_layer_forward", g, L))) return st;
-  Arena a;
-  a.base = arena_base(workspace);
+  Workspace a(arena_base(workspace));
   Plan p;
   if ((st = make_plan(g, *L, training != 0, a, p))) return st;
   if (g->n_nodes == 0) return NGPDE_OK;
   NGPDE_REQUIRE(y != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_edge_layer_forward: y is NULL");
-  NGPDE_REQUIRE(workspace != nullptr && workspace_bytes >= p.total_floats * sizeof(float) + kArenaSlack, NGPDE_ERR_WORKSPACE,
-                "ngpde_edge_layer_forward: workspace of %zu bytes, %zu needed", workspace_bytes, p.total_floats * sizeof(float) + kArenaSlack);
+  if ((st = check_workspace("ngpde_edge_layer_forward", workspace, workspace_bytes, p.total_floats * sizeof(float) + kArenaSlack, 1))) return st;
   if (training) stamp_set(workspace, edge_plan_key(g, p));
   const ngpde_mlp_t &phi = L->phi;
   // the recombined first-layer weights in one launch
@@ -600,8 +586,7 @@ int32_t ngpde_edge_layer_backward(const ngpde_graph_t *g, const ngpde_edge_layer
   NGPDE_RANGE();
   int32_t st;
   if ((st = check_common("ngpde_edge_layer_backward", g, L))) return st;
-  Arena a;
-  a.base = arena_base(workspace);
+  Workspace a(arena_base(workspace));
   Plan p;
   if ((st = make_plan(g, *L, true, a, p))) return st;
   if (g->n_nodes == 0) return NGPDE_OK;
@@ -610,8 +595,7 @@ int32_t ngpde_edge_layer_backward(const ngpde_graph_t *g, const ngpde_edge_layer
   NGPDE_REQUIRE(stamp_agrees(workspace, edge_plan_key(g, p)), NGPDE_ERR_STATE,
                 "ngpde_edge_layer_backward: this workspace was filled by a forward that chose another kernel sequence or layout (descriptor, graph or "
                 "an NGPDE_* path switch changed between the two calls)");
-  NGPDE_REQUIRE(workspace != nullptr && workspace_bytes >= p.total_floats * sizeof(float) + kArenaSlack, NGPDE_ERR_WORKSPACE,
-                "ngpde_edge_layer_backward: workspace of %zu bytes, %zu needed", workspace_bytes, p.total_floats * sizeof(float) + kArenaSlack);
+  if ((st = check_workspace("ngpde_edge_layer_backward", workspace, workspace_bytes, p.total_floats * sizeof(float) + kArenaSlack, 1))) return st;
   const ngpde_mlp_t &phi = L->phi;
   for (int l = 0; l < phi.n_layers; ++l)
     NGPDE_REQUIRE(dphi->dweight[l] != nullptr && (phi.bias[l] == nullptr || dphi->dbias[l] != nullptr), NGPDE_ERR_INVALID_ARGUMENT,
@@ -755,7 +739,7 @@ int32_t ngpde_edge_layer_backward(const ngpde_graph_t *g, const ngpde_edge_layer
 
 size_t ngpde_gno_layer_workspace_bytes(const ngpde_graph_t *g, const ngpde_gno_layer_t *L, int32_t training) {
   if (!g || !L) return 0;
-  Arena a;
+  Workspace a;
   GnoPlan p;
   if (make_gno_plan(g, *L, training != 0, a, p) != NGPDE_OK) return 0;
   return p.total_floats * sizeof(float) + kArenaSlack;
@@ -765,15 +749,13 @@ int32_t ngpde_gno_layer_forward(const ngpde_graph_t *g, const ngpde_gno_layer_t 
                                 size_t workspace_bytes, ngpde_stream_t stream) {
   NGPDE_RANGE();
   NGPDE_REQUIRE(g != nullptr && L != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_layer_forward: graph or layer descriptor is NULL");
-  Arena a;
-  a.base = arena_base(workspace);
+  Workspace a(arena_base(workspace));
   GnoPlan p;
   int32_t st;
   if ((st = make_gno_plan(g, *L, training != 0, a, p))) return st;
   if (g->n_nodes == 0) return NGPDE_OK;
   NGPDE_REQUIRE(y != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_layer_forward: y is NULL");
-  NGPDE_REQUIRE(workspace != nullptr && workspace_bytes >= p.total_floats * sizeof(float) + kArenaSlack, NGPDE_ERR_WORKSPACE,
-                "ngpde_gno_layer_forward: workspace of %zu bytes, %zu needed", workspace_bytes, p.total_floats * sizeof(float) + kArenaSlack);
+  if ((st = check_workspace("ngpde_gno_layer_forward", workspace, workspace_bytes, p.total_floats * sizeof(float) + kArenaSlack, 1))) return st;
   if (training) stamp_set(workspace, gno_plan_key(g, p));
   const ngpde_mlp_t &phi = L->phi;
   float *outs[3];
@@ -846,8 +828,7 @@ int32_t ngpde_gno_layer_backward(const ngpde_graph_t *g, const ngpde_gno_layer_t
                                  float *dweight, float *dbias, void *workspace, size_t workspace_bytes, ngpde_stream_t stream) {
   NGPDE_RANGE();
   NGPDE_REQUIRE(g != nullptr && L != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_layer_backward: graph or layer descriptor is NULL");
-  Arena a;
-  a.base = arena_base(workspace);
+  Workspace a(arena_base(workspace));
   GnoPlan p;
   int32_t st;
   if ((st = make_gno_plan(g, *L, true, a, p))) return st;
@@ -861,8 +842,7 @@ int32_t ngpde_gno_layer_backward(const ngpde_graph_t *g, const ngpde_gno_layer_t
   NGPDE_REQUIRE(stamp_agrees(workspace, gno_plan_key(g, p)), NGPDE_ERR_STATE,
                 "ngpde_gno_layer_backward: this workspace was filled by a forward that chose another kernel sequence or layout (descriptor, graph or "
                 "an NGPDE_* path switch changed between the two calls)");
-  NGPDE_REQUIRE(workspace != nullptr && workspace_bytes >= p.total_floats * sizeof(float) + kArenaSlack, NGPDE_ERR_WORKSPACE,
-                "ngpde_gno_layer_backward: workspace of %zu bytes, %zu needed", workspace_bytes, p.total_floats * sizeof(float) + kArenaSlack);
+  if ((st = check_workspace("ngpde_gno_layer_backward", workspace, workspace_bytes, p.total_floats * sizeof(float) + kArenaSlack, 1))) return st;
   const int32_t one[1] = {1};
   const size_t N = (size_t)p.N;
   // ---- the tail y = act.(agg + W h + b): dz is the gradient of the aggregate AND of W h

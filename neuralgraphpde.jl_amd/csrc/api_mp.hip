@@ -9,8 +9,6 @@ using namespace ngpde;
 
 namespace {
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // n_rows = 0: a Dense over no rows (an edgeless graph's message MLP: /root/reference's scatter over an empty edge set gives zeros) --
 // its blocks may be NULL, as the empty arrays of most hosts are
 int32_t make_segs(const char *fn, int32_t n_seg, const float *const *seg_ptr, const int32_t *seg_width,
@@ -38,6 +36,28 @@ int32_t check_act(const char *fn, int32_t act) {
   NGPDE_REQUIRE(act >= NGPDE_ACT_IDENTITY && act <= NGPDE_ACT_SOFTPLUS, NGPDE_ERR_INVALID_ARGUMENT,
                 "%s: unknown activation code %d", fn, act);
   return NGPDE_OK;
+}
+
+constexpr size_t kWsSlack = 256;   // what the Dense and GAT queries add behind their pieces
+
+// the Dense pullback: dz (the one-launch forms put their slabs there), the weight pullback's slabs, the split input pullback's partials
+struct DenseBwdWs {
+  float *dz, *partial, *split_part;
+};
+void dense_bwd_layout(Workspace &w, int64_t n, int32_t din, int32_t dout, DenseBwdWs &p) {
+  p.dz = w.take<float>((size_t)std::max<int64_t>(n, 1) * dout);
+  p.partial = w.take<float>((size_t)dense_weight_chunks(n, din, dout) * (din + 1) * dout);
+  p.split_part = reinterpret_cast<float *>(w.take<char>(dense_bwd_input_split_bytes(n, din, dout)));
+}
+
+// the unfused GAT pullback: the edges' score gradients, the two per-node score gradients
+struct GatBwdWs {
+  float *dscore, *dal, *dar;
+};
+void gat_bwd_layout(Workspace &w, const ngpde_graph_t *g, int32_t heads, GatBwdWs &p) {
+  p.dscore = w.take<float>((size_t)std::max<int64_t>(g->n_edges, 1) * heads);
+  p.dal = w.take<float>((size_t)std::max<int64_t>(g->n_nodes, 1) * heads);
+  p.dar = w.take<float>((size_t)std::max<int64_t>(g->n_nodes, 1) * heads);
 }
 
 }  // namespace
@@ -168,16 +188,14 @@ int32_t ngpde_dense_pair_backward(int64_t n, int32_t n_seg_a, const float *const
                 "side and >= 32768 rows (ngpde_dense_pair_backward_workspace_bytes returns 0 otherwise): use two ngpde_dense_backward calls");
   NGPDE_REQUIRE(weight_a && weight_b && dy_a && dy_b && dweight_a && dweight_b && dx, NGPDE_ERR_INVALID_ARGUMENT,
                 "ngpde_dense_pair_backward: NULL argument");
-  NGPDE_REQUIRE(workspace && workspace_bytes >= dense_pair_bwd_workspace(grid, dina, dinb), NGPDE_ERR_WORKSPACE,
-                "ngpde_dense_pair_backward: workspace too small");
+  if ((st = check_workspace("ngpde_dense_pair_backward", workspace, workspace_bytes, dense_pair_bwd_workspace(grid, dina, dinb), 1))) return st;
   return launch_dense_pair_bwd(n, ta, dina, weight_a, dy_a, dweight_a, dbias_a, tb, dinb, weight_b, dy_b, dweight_b, dbias_b, dx, dx_addend,
                                workspace, grid, (hipStream_t)stream);
 }
 
 size_t ngpde_dense_workspace_bytes(int64_t n, int32_t din_total, int32_t dout) {
-  return align256((size_t)std::max<int64_t>(n, 1) * dout * 4) +
-         align256((size_t)dense_weight_chunks(n, din_total, dout) * (din_total + 1) * dout * 4) +
-         align256(dense_bwd_input_split_bytes(n, din_total, dout)) + 256;
+  DenseBwdWs p;
+  return measure(dense_bwd_layout, n, din_total, dout, p) + kWsSlack;
 }
 
 int32_t ngpde_dense_backward(int64_t n, int32_t n_seg, const float *const *seg_ptr, const int32_t *seg_width,
@@ -199,21 +217,21 @@ int32_t ngpde_dense_backward(int64_t n, int32_t n_seg, const float *const *seg_p
   }
   NGPDE_REQUIRE(weight && dy && (z || act == NGPDE_ACT_IDENTITY), NGPDE_ERR_INVALID_ARGUMENT,
                 "ngpde_dense_backward: weight/z/dy is NULL");
-  const size_t need = ngpde_dense_workspace_bytes(n, din, dout);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= need, NGPDE_ERR_WORKSPACE,
-                "ngpde_dense_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+  if ((st = check_workspace("ngpde_dense_backward", workspace, workspace_bytes, ngpde_dense_workspace_bytes(n, din, dout), 1))) return st;
   if (const int sgrid = dense_stream_bwd_grid(n, t, din, dout, dseg_ptr))   // one streaming launch (slabs in the dz area)
     return launch_dense_stream_bwd(n, t, din, act, weight, z, dy, dseg_ptr, dweight, dbias, (float *)workspace, sgrid, stream);
   if (const int sgrid = dense_small_bwd_grid(n, din, dout))                   // at most 64 x 64, latency-bound row counts: one launch too
     return launch_dense_small_bwd(n, t, din, dout, act, weight, z, dy, dseg_ptr, dweight, dbias, (float *)workspace, sgrid, stream);
-  float *dz = (float *)workspace;
-  float *partial = (float *)((char *)workspace + align256((size_t)n * dout * 4));
+  Workspace w(workspace);
+  DenseBwdWs p;
+  dense_bwd_layout(w, n, din, dout, p);
+  float *dz = p.dz;
   if (act == NGPDE_ACT_IDENTITY) {
     dz = const_cast<float *>(dy);   // read-only below
   } else if ((st = launch_dense_dz(n * dout, act, dy, z, dz, stream))) {
     return st;
   }
-  if ((st = launch_dense_seg_bwd_weight(n, t, din, dout, dz, dweight, dbias, partial, stream))) return st;
+  if ((st = launch_dense_seg_bwd_weight(n, t, din, dout, dz, dweight, dbias, p.partial, stream))) return st;
   if (dseg_ptr) {
     SegGrad gsg;
     gsg.n = t.n;
@@ -225,8 +243,7 @@ int32_t ngpde_dense_backward(int64_t n, int32_t n_seg, const float *const *seg_p
     }
     for (int i = 0; i <= 4; ++i) gsg.offset[i] = t.offset[i];
     if (any && t.n == 1 && dense_bwd_input_splits(n, din, dout) > 1) {   // few rows, very wide output: split the contraction
-      float *split_part = (float *)((char *)partial + align256((size_t)dense_weight_chunks(n, din, dout) * (din + 1) * dout * 4));
-      if ((st = launch_dense_bwd_input_splitk(n, gsg.ptr[0], din, dout, dz, weight, split_part, stream))) return st;
+      if ((st = launch_dense_bwd_input_splitk(n, gsg.ptr[0], din, dout, dz, weight, p.split_part, stream))) return st;
     } else if (any && (st = launch_dense_seg_bwd_input(n, gsg, din, dout, dz, weight, stream))) return st;
   }
   return NGPDE_OK;
@@ -306,10 +323,9 @@ int32_t ngpde_gno_contract_backward(const ngpde_graph_t *g, int32_t cin, int32_t
     return NGPDE_OK;
   }
   NGPDE_REQUIRE(cin > 0 && cout > 0 && k && h && dm, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_contract_backward: bad arguments");
-  const size_t need = (size_t)g->n_edges * cin * 4;
-  NGPDE_REQUIRE(!dh || (workspace && workspace_bytes >= need), NGPDE_ERR_WORKSPACE,
-                "ngpde_gno_contract_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
-  int32_t st = launch_gno_contract_bwd(g, cin, cout, k, h, dm, dk, dh ? (float *)workspace : nullptr, stream);
+  int32_t st;
+  if (dh && (st = check_workspace("ngpde_gno_contract_backward", workspace, workspace_bytes, (size_t)g->n_edges * cin * 4, 1))) return st;
+  st = launch_gno_contract_bwd(g, cin, cout, k, h, dm, dk, dh ? (float *)workspace : nullptr, stream);
   if (st) return st;
   if (dh) return launch_edge_sum_by_source(g, cin, (const float *)workspace, dh, stream);
   return NGPDE_OK;
@@ -391,7 +407,8 @@ int32_t ngpde_gat_forward(const ngpde_graph_t *g, int32_t heads, int32_t c, floa
 
 size_t ngpde_gat_workspace_bytes(const ngpde_graph_t *g, int32_t heads) {
   if (!g) return 0;
-  return align256((size_t)std::max<int64_t>(g->n_edges, 1) * heads * 4) + 2 * align256((size_t)std::max<int64_t>(g->n_nodes, 1) * heads * 4) + 256;
+  GatBwdWs p;
+  return measure(gat_bwd_layout, g, heads, p) + kWsSlack;
 }
 
 int32_t ngpde_gat_backward(const ngpde_graph_t *g, int32_t heads, int32_t c, float negative_slope, const float *wx,
@@ -402,14 +419,11 @@ int32_t ngpde_gat_backward(const ngpde_graph_t *g, int32_t heads, int32_t c, flo
   if (g->n_nodes == 0) return NGPDE_OK;
   NGPDE_REQUIRE(heads > 0 && c > 0 && wx && a && al && ar && dout && dwx && da, NGPDE_ERR_INVALID_ARGUMENT,
                 "ngpde_gat_backward: bad arguments");
-  const size_t need = ngpde_gat_workspace_bytes(g, heads);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= need, NGPDE_ERR_WORKSPACE,
-                "ngpde_gat_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
-  char *ws = (char *)workspace;
-  float *dscore = (float *)ws;
-  float *dal = (float *)(ws + align256((size_t)std::max<int64_t>(g->n_edges, 1) * heads * 4));
-  float *dar = (float *)((char *)dal + align256((size_t)g->n_nodes * heads * 4));
-  return launch_gat_bwd(g, heads, c, negative_slope, wx, a, al, ar, alpha, dout, dscore, dal, dar, dwx, da,
+  if (int32_t st = check_workspace("ngpde_gat_backward", workspace, workspace_bytes, ngpde_gat_workspace_bytes(g, heads), 1)) return st;
+  Workspace w(workspace);
+  GatBwdWs p;
+  gat_bwd_layout(w, g, heads, p);
+  return launch_gat_bwd(g, heads, c, negative_slope, wx, a, al, ar, alpha, dout, p.dscore, p.dal, p.dar, dwx, da,
                         (hipStream_t)stream_);
 }
 
@@ -476,8 +490,7 @@ int32_t ngpde_bias_act_backward(int64_t n, int32_t d, int32_t act, const float *
   if (d == 0) return NGPDE_OK;
   NGPDE_REQUIRE((n == 0 || (dy && dz)) && (act == NGPDE_ACT_IDENTITY || z || n == 0), NGPDE_ERR_INVALID_ARGUMENT,
                 "ngpde_bias_act_backward: NULL argument");
-  NGPDE_REQUIRE(!dbias || (workspace && workspace_bytes >= ngpde_bias_act_workspace_bytes(d)), NGPDE_ERR_WORKSPACE,
-                "ngpde_bias_act_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, ngpde_bias_act_workspace_bytes(d));
+  if (dbias && (st = check_workspace("ngpde_bias_act_backward", workspace, workspace_bytes, ngpde_bias_act_workspace_bytes(d), 1))) return st;
   if (n > 0 && !(act == NGPDE_ACT_IDENTITY && dz == dy)) {   // identity with dz aliasing dy: nothing to compute
     st = launch_dense_dz(n * d, act, dy, z ? z : dy, dz, (hipStream_t)stream);   // identity: act' = 1 whatever z is
     if (st) return st;

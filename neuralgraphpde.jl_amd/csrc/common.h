@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ngpde.h"
+#include "workspace.h"
 
 namespace ngpde {
 

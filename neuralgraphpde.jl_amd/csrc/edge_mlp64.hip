@@ -661,15 +661,20 @@ bool edge_mlp64_bwd_applicable(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
   const bool a2 = a.act2 == a.act1 || a.act2 == NGPDE_ACT_IDENTITY;
   return a1 && a2;
 }
-static size_t edge64_slab_bytes(const ngpde_graph *g) { return slab_bytes(edge_persistent_grid(g, 64), kW, kW); }
 // the by-source sum inside the launch (no [E][64] array): no per-edge term, every halo within kDqStride rows
 bool edge_mlp64_bwd_dq_in_launch(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
   if (switch_on(Switch::Edge64NoDq)) return false;
   return a.Eterm == nullptr && a.dQ != nullptr && g->by_t.halo_ok && g->by_t.max_halo <= kDqStride;
 }
+// the slabs of the larger grid; behind them, on a graph whose halos allow the by-source sum inside the launch, its per-tile partials
+static void edge64_bwd_layout(Workspace &w, const ngpde_graph *g, float *&partial, float *&dqpart) {
+  partial = take_slabs(w, edge_persistent_grid(g, 64), kW, kW);
+  const bool part = g->by_t.halo_ok && g->by_t.max_halo <= kDqStride;
+  dqpart = part ? w.take<float>((size_t)(g->n_sched / kTileRows) * kDqStride * kW) : nullptr;
+}
 size_t edge_mlp64_bwd_workspace(const ngpde_graph *g) {
-  const size_t part = (g->by_t.halo_ok && g->by_t.max_halo <= kDqStride) ? (size_t)(g->n_sched / kTileRows) * kDqStride * kW * sizeof(float) : 0;
-  return edge64_slab_bytes(g) + part + 256;
+  float *partial, *dqpart;
+  return measure(edge64_bwd_layout, g, partial, dqpart) + 256;
 }
 
 int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hipStream_t stream) {
@@ -677,7 +682,10 @@ int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hip
   fill_tile_args(g, k);
   k.aggr = a.aggr;
   k.P = a.P; k.Q = a.Q; k.wt = a.wt; k.bias = a.bias; k.dout = a.dout;
-  k.dP = a.dP; k.dE = a.dE; k.partial = (float *)a.workspace;
+  k.dP = a.dP; k.dE = a.dE;
+  Workspace w(a.workspace);   // (launch_edge_mlp_fused_bwd checked its size)
+  float *dqpart;
+  edge64_bwd_layout(w, g, k.partial, dqpart);
   const bool dq = edge_mlp64_bwd_dq_in_launch(g, a);
   const HaloInverse *hinv = nullptr;
   if (dq) {
@@ -685,7 +693,7 @@ int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hip
     if (sti) return sti;
   }
   NGPDE_REQUIRE(dq || a.dE != nullptr || g->n_edges == 0, NGPDE_ERR_INVALID_ARGUMENT, "fused edge-MLP pullback: the [E][h1] buffer dE is required");
-  k.dqpart = dq ? reinterpret_cast<float *>(reinterpret_cast<char *>(a.workspace) + edge64_slab_bytes(g)) : nullptr;
+  k.dqpart = dq ? dqpart : nullptr;
   k.dQ = dq ? a.dQ : nullptr;
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kChunk4 * kTS + 2 * (size_t)kW * kTS) * sizeof(float);
   // two workgroups per CU, or one when the halo region is large (the workspace holds slabs for the larger grid)

@@ -209,14 +209,21 @@ bool edge_mlp_deep_bwd_supported(const ngpde_graph *g, int h1, int n_tail, const
   return aggr == NGPDE_AGGR_SUM || aggr == NGPDE_AGGR_MEAN;
 }
 
-size_t edge_mlp_deep_bwd_workspace(const ngpde_graph *g, int h1, int n_tail, const int *dout) {
-  size_t bytes = 256;
+namespace {
+// partial[l]: the weight slabs of tail layer l, one per workgroup; nullptr from n_tail on
+void deep_bwd_layout(Workspace &w, const ngpde_graph *g, int h1, int n_tail, const int *dout, float *(&partial)[kMaxTail]) {
+  const int grid = deep_grid(g);
   int din = h1;
-  for (int l = 0; l < n_tail; ++l) {
-    bytes += slab_bytes(deep_grid(g), din, dout[l]);
-    din = dout[l];
+  for (int l = 0; l < kMaxTail; ++l) {
+    partial[l] = l < n_tail ? take_slabs(w, grid, din, dout[l]) : nullptr;
+    if (l < n_tail) din = dout[l];
   }
-  return bytes;
+}
+}  // namespace
+
+size_t edge_mlp_deep_bwd_workspace(const ngpde_graph *g, int h1, int n_tail, const int *dout) {
+  float *partial[kMaxTail];
+  return measure(deep_bwd_layout, g, h1, n_tail, dout, partial) + 256;
 }
 
 int32_t launch_edge_mlp_deep_bwd(const ngpde_graph *g, const EdgeMlpDeepBwdArgs &a, hipStream_t stream) {
@@ -224,32 +231,25 @@ int32_t launch_edge_mlp_deep_bwd(const ngpde_graph *g, const EdgeMlpDeepBwdArgs 
                 "deep fused edge-MLP pullback needs widths <= 64 and multiples of 4, 2 or 3 layers after the first, + or mean "
                 "aggregation and a graph whose tiles fit the LDS halo");
   if (g->n_nodes == 0) return NGPDE_OK;
-  const size_t need = edge_mlp_deep_bwd_workspace(g, a.h1, a.n_tail, a.dout);
-  NGPDE_REQUIRE(a.workspace && a.workspace_bytes >= need, NGPDE_ERR_WORKSPACE, "deep fused edge-MLP pullback: workspace too small (%zu < %zu bytes)",
-                a.workspace_bytes, need);
+  if (int32_t st = check_workspace("deep fused edge-MLP pullback", a.workspace, a.workspace_bytes, edge_mlp_deep_bwd_workspace(g, a.h1, a.n_tail, a.dout), 1))
+    return st;
   NGPDE_REQUIRE(a.dE != nullptr || g->n_edges == 0, NGPDE_ERR_INVALID_ARGUMENT, "deep fused edge-MLP pullback: the [E][h1] buffer dE is required");
   DeepBwdK k;
   fill_tile_args(g, k);
   k.h1 = a.h1; k.act1 = a.act1; k.aggr = a.aggr; k.n_tail = a.n_tail;
   k.P = a.P; k.Q = a.Q; k.Eterm = a.Eterm; k.dout_grad = a.dout_grad; k.dP = a.dP; k.dE = a.dE;
   const int grid = deep_grid(g);
-  char *ws = reinterpret_cast<char *>(a.workspace);
-  int din = a.h1;
+  Workspace w(a.workspace);
+  deep_bwd_layout(w, g, a.h1, a.n_tail, a.dout, k.partial);
   for (int l = 0; l < kMaxTail; ++l) {
     k.dout[l] = l < a.n_tail ? a.dout[l] : 0; k.act[l] = l < a.n_tail ? a.act[l] : 0;
     k.wt[l] = l < a.n_tail ? a.wt[l] : nullptr; k.bias[l] = l < a.n_tail ? a.bias[l] : nullptr;
-    k.partial[l] = nullptr;
-    if (l < a.n_tail) {
-      k.partial[l] = reinterpret_cast<float *>(ws);
-      ws += slab_bytes(grid, din, a.dout[l]);
-      din = a.dout[l];
-    }
   }
   const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kChunk4 * kTS + 2 * (size_t)a.n_tail * kW * kTS) * sizeof(float);
   int32_t st = a.n_tail == 2 ? launch_with_lds(edge_mlp_deep_bwd_kernel<2>, grid, kT4, lds, stream, k, "edge_mlp_deep_bwd_kernel")
                              : launch_with_lds(edge_mlp_deep_bwd_kernel<3>, grid, kT4, lds, stream, k, "edge_mlp_deep_bwd_kernel");
   if (st) return st;
-  din = a.h1;
+  int din = a.h1;
   for (int l = 0; l < a.n_tail; ++l) {
     if ((st = launch_dense_weight_reduce(grid, din, a.dout[l], k.partial[l], a.dwt[l], a.dbias[l], stream))) return st;
     din = a.dout[l];

@@ -521,9 +521,8 @@ int32_t launch_edge_mlp_fused_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a,
                 "fused edge-MLP pullback needs widths <= 64 and multiples of 4, at most one layer after the first and a graph whose tiles fit "
                 "the LDS halo");
   if (g->n_nodes == 0) return NGPDE_OK;
-  const size_t need = edge_mlp_fused_bwd_workspace(g, a.h1, a.n_tail, a.dw);
-  NGPDE_REQUIRE(a.workspace && a.workspace_bytes >= need, NGPDE_ERR_WORKSPACE, "fused edge-MLP pullback: workspace too small (%zu < %zu bytes)",
-                a.workspace_bytes, need);
+  if (int32_t st = check_workspace("fused edge-MLP pullback", a.workspace, a.workspace_bytes, edge_mlp_fused_bwd_workspace(g, a.h1, a.n_tail, a.dw), 1))
+    return st;
   if (edge_mlp64_bwd_applicable(g, a)) return launch_edge_mlp64_bwd(g, a, stream);   // (checks dE itself: not needed when it sums by source in the launch)
   NGPDE_REQUIRE(a.dE != nullptr || g->n_edges == 0, NGPDE_ERR_INVALID_ARGUMENT, "fused edge-MLP pullback: the [E][h1] buffer dE is required");
   EdgeMlpBwdK k;

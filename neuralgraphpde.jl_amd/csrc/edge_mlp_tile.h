@@ -50,7 +50,8 @@ inline int edge_persistent_grid(const ngpde_graph *g, int per_xcd_cap) {
 }
 
 // one [(din + 1)][dw] weight-gradient slab per workgroup (row din = bias gradient), rounded to 256 bytes
-inline size_t slab_bytes(int grid, int din, int dw) { return ((size_t)grid * (din + 1) * dw * sizeof(float) + 255) / 256 * 256; }
+inline size_t slab_bytes(int grid, int din, int dw) { return round_up256((size_t)grid * (din + 1) * dw * sizeof(float)); }
+inline float *take_slabs(Workspace &w, int grid, int din, int dw) { return reinterpret_cast<float *>(w.take<char>(slab_bytes(grid, din, dw))); }
 
 // more than 64 KB of dynamic LDS has to be requested explicitly
 template <class KERNEL, class ARGS>

@@ -1295,21 +1295,16 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
 
 inline int src_wgs(const ngpde_graph *g) { return (fused_num_blocks(g->n_nodes) + kSrcTiles - 1) / kSrcTiles; }
 
-struct GatWs {   // carving of the caller's pullback workspace (256-byte aligned pieces)
-  size_t dz, dscore, dal, slab_db, slab_dw, slab_u, total;
+struct GatLayerBwdWs {   // the pieces of the caller's pullback workspace
+  float *dz, *dscore, *dal, *slab_db, *slab_dw, *slab_u;
 };
-inline GatWs gat_ws(const ngpde_graph *g, int heads) {
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  GatWs w;
-  size_t o = 0;
-  w.dz = o; o += up((size_t)g->n_nodes * GD * 4);
-  w.dscore = o; o += up((size_t)std::max<int64_t>(g->n_edges, 1) * heads * 4);
-  w.dal = o; o += up((size_t)g->n_nodes * heads * 4);
-  w.slab_db = o; o += up((size_t)fused_num_blocks(g->n_nodes) * GD * 4);
-  w.slab_dw = o; o += up((size_t)src_wgs(g) * GD * GD * 4);
-  w.slab_u = o; o += up((size_t)src_wgs(g) * 2 * GD * 4);
-  w.total = o;
-  return w;
+inline void gat_layer_bwd_layout(Workspace &w, const ngpde_graph *g, int heads, GatLayerBwdWs &p) {
+  p.dz = w.take<float>((size_t)g->n_nodes * GD);
+  p.dscore = w.take<float>((size_t)std::max<int64_t>(g->n_edges, 1) * heads);
+  p.dal = w.take<float>((size_t)g->n_nodes * heads);
+  p.slab_db = w.take<float>((size_t)fused_num_blocks(g->n_nodes) * GD);
+  p.slab_dw = w.take<float>((size_t)src_wgs(g) * GD * GD);
+  p.slab_u = w.take<float>((size_t)src_wgs(g) * 2 * GD);
 }
 
 }  // namespace
@@ -1319,7 +1314,10 @@ bool gat_layer_fused_supported(const ngpde_graph *g, int din, int heads, int c) 
          (heads == 1 || heads == 2 || heads == 4) && (uint64_t)g->n_nodes * GD * 4 < (1ull << 32) && !switch_on(Switch::NoFusedGatLayer);
 }
 
-size_t gat_layer_workspace_bytes(const ngpde_graph *g, int heads) { return g ? gat_ws(g, heads).total : 0; }
+size_t gat_layer_workspace_bytes(const ngpde_graph *g, int heads) {
+  GatLayerBwdWs p;
+  return g ? measure(gat_layer_bwd_layout, g, heads, p) : 0;
+}
 
 int32_t launch_gat_layer_fwd(const ngpde_graph *g, int heads, float slope, int act, const float *x, const float *wt, const float *a,
                              const float *bias, float *y, float *alpha, float *save_z, hipStream_t stream) {
@@ -1342,13 +1340,11 @@ int32_t launch_gat_layer_fwd(const ngpde_graph *g, int heads, float slope, int a
 int32_t launch_gat_layer_bwd(const ngpde_graph *g, int heads, float slope, int act, const float *x, const float *wt, const float *a,
                              const float *yz, const float *alpha, const float *dy, float *dx, float *dwt, float *da, float *db,
                              void *workspace, size_t workspace_bytes, hipStream_t stream) {
-  const GatWs w = gat_ws(g, heads);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= w.total, NGPDE_ERR_WORKSPACE, "ngpde_gat_layer_backward: workspace too small (%zu < %zu bytes)",
-                workspace_bytes, w.total);
-  char *ws = static_cast<char *>(workspace);
-  float *dz = reinterpret_cast<float *>(ws + w.dz), *dscore = reinterpret_cast<float *>(ws + w.dscore);
-  float *dal = reinterpret_cast<float *>(ws + w.dal), *slab_db = reinterpret_cast<float *>(ws + w.slab_db);
-  float *slab_dw = reinterpret_cast<float *>(ws + w.slab_dw), *slab_u = reinterpret_cast<float *>(ws + w.slab_u);
+  if (int32_t st = check_workspace("ngpde_gat_layer_backward", workspace, workspace_bytes, gat_layer_workspace_bytes(g, heads), 1)) return st;
+  Workspace w(workspace);
+  GatLayerBwdWs p;
+  gat_layer_bwd_layout(w, g, heads, p);
+  float *const dz = p.dz, *const dscore = p.dscore, *const dal = p.dal, *const slab_db = p.slab_db, *const slab_dw = p.slab_dw, *const slab_u = p.slab_u;
   const int n_tiles = fused_num_blocks(g->n_nodes), n_wg = src_wgs(g);
   const bool ident = act == NGPDE_ACT_IDENTITY;
   if (g->n_nodes > 0) {

@@ -506,42 +506,33 @@ bool largest_ritz(const float *alpha, const float *beta, int m, double *theta, s
   return true;
 }
 
-size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct LanczosLayout {
-  size_t V, w, y, partial, h, alpha, beta, coef, anorm, theta, steps, stop, gptr, cptr, chunk_graph, chunk_begin, chunk_end, total;
-  int64_t max_chunks;
-};
-
-LanczosLayout lanczos_layout(int64_t n, int32_t n_graphs, int32_t max_iter) {
-  LanczosLayout a;
-  a.max_chunks = (n + kDotChunk - 1) / kDotChunk + n_graphs;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    const size_t here = at;
-    at += align_up(bytes);
-    return here;
-  };
+// the view's pieces, in workspace order.  The entry clears alpha .. coef and anorm .. stop as one span each and reads alpha and beta
+// back as one block, so these stay neighbours
+void lanczos_layout(Workspace &w, int64_t n, int32_t n_graphs, int32_t max_iter, LanczosView &L) {
+  const size_t max_chunks = (size_t)((n + kDotChunk - 1) / kDotChunk + n_graphs);
   const size_t gl = (size_t)n_graphs * (size_t)max_iter;
-  a.V = take((size_t)max_iter * (size_t)n * 4);
-  a.w = take((size_t)n * 4);
-  a.y = take((size_t)n * 4);
-  a.partial = take((size_t)max_iter * (size_t)a.max_chunks * 4);
-  a.h = take(gl * 4);
-  a.alpha = take(gl * 4);   // (alpha and beta are read back as one block)
-  a.beta = take(gl * 4);
-  a.coef = take(gl * 4);
-  a.anorm = take((size_t)n_graphs * 4);
-  a.theta = take((size_t)n_graphs * 4);
-  a.steps = take((size_t)n_graphs * 4);
-  a.stop = take((size_t)n_graphs * 8);
-  a.gptr = take(((size_t)n_graphs + 1) * 4);
-  a.cptr = take(((size_t)n_graphs + 1) * 4);
-  a.chunk_graph = take((size_t)a.max_chunks * 4);
-  a.chunk_begin = take((size_t)a.max_chunks * 4);
-  a.chunk_end = take((size_t)a.max_chunks * 4);
-  a.total = at;
-  return a;
+  L.V = w.take<float>((size_t)max_iter * (size_t)n);
+  L.w = w.take<float>((size_t)n);
+  L.y = w.take<float>((size_t)n);
+  L.partial = w.take<float>((size_t)max_iter * max_chunks);
+  L.h = w.take<float>(gl);
+  L.alpha = w.take<float>(gl);
+  L.beta = w.take<float>(gl);
+  L.coef = w.take<float>(gl);
+  L.anorm = w.take<float>((size_t)n_graphs);
+  L.theta = w.take<float>((size_t)n_graphs);
+  L.steps = w.take<int32_t>((size_t)n_graphs);
+  L.stop = w.take<int32_t>(2 * (size_t)n_graphs);
+  L.gptr = w.take<int32_t>((size_t)n_graphs + 1);
+  L.cptr = w.take<int32_t>((size_t)n_graphs + 1);
+  L.chunk_graph = w.take<int32_t>(max_chunks);
+  L.chunk_begin = w.take<int32_t>(max_chunks);
+  L.chunk_end = w.take<int32_t>(max_chunks);
+}
+
+size_t lanczos_bytes(int64_t n, int32_t n_graphs, int32_t max_iter) {
+  LanczosView L;
+  return measure(lanczos_layout, n, n_graphs, max_iter, L);
 }
 
 int32_t check_lanczos_sizes(const char *fn, int64_t n, int64_t nnz, int32_t n_graphs, int32_t max_iter) {
@@ -673,7 +664,7 @@ int32_t ngpde_csr_check_symmetric(int64_t n, int64_t nnz, const int32_t *row_ptr
 
 size_t ngpde_csr_lambda_max_workspace_bytes(int64_t n, int32_t n_graphs, int32_t max_iter) {
   if (n < 0 || n > 0x7fffffffLL || n_graphs < 1 || max_iter < 1 || max_iter > kMaxIter) return 0;
-  return lanczos_layout(n, n_graphs, max_iter).total;
+  return lanczos_bytes(n, n_graphs, max_iter);
 }
 
 int32_t ngpde_csr_lambda_max(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *cols, const float *vals, int32_t n_graphs,
@@ -687,23 +678,20 @@ int32_t ngpde_csr_lambda_max(int64_t n, int64_t nnz, const int32_t *row_ptr, con
   NGPDE_REQUIRE(n_graphs == 1 || graph_of, NGPDE_ERR_INVALID_ARGUMENT, "%s: graph_of is NULL with %d graphs", fn, n_graphs);
   NGPDE_REQUIRE(lambda_out != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "%s: lambda_out is NULL", fn);
   NGPDE_REQUIRE(row_ptr && (nnz == 0 || (cols && vals)), NGPDE_ERR_INVALID_ARGUMENT, "%s: row_ptr / cols / vals is NULL", fn);
-  const LanczosLayout lay = lanczos_layout(n, n_graphs, max_iter);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= lay.total, NGPDE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes,
-                lay.total);
-  char *base = (char *)workspace;
+  if (int32_t st = check_workspace(fn, workspace, workspace_bytes, lanczos_bytes(n, n_graphs, max_iter), 1)) return st;
+  Workspace w(workspace);
   LanczosView L;
+  lanczos_layout(w, n, n_graphs, max_iter, L);
   L.n = n;
   L.n_graphs = n_graphs;
   L.ld = max_iter;
   L.graph_of = graph_of;
-  int32_t *gptr = (int32_t *)(base + lay.gptr), *cptr = (int32_t *)(base + lay.cptr), *chunk_graph = (int32_t *)(base + lay.chunk_graph),
-          *chunk_begin = (int32_t *)(base + lay.chunk_begin), *chunk_end = (int32_t *)(base + lay.chunk_end);
-  L.gptr = gptr, L.cptr = cptr, L.chunk_graph = chunk_graph, L.chunk_begin = chunk_begin, L.chunk_end = chunk_end;
-  L.stop = (int32_t *)(base + lay.stop), L.steps = (int32_t *)(base + lay.steps);
-  L.V = (float *)(base + lay.V), L.w = (float *)(base + lay.w), L.y = vector_out ? vector_out : (float *)(base + lay.y);
-  L.partial = (float *)(base + lay.partial), L.h = (float *)(base + lay.h), L.alpha = (float *)(base + lay.alpha);
-  L.beta = (float *)(base + lay.beta), L.coef = (float *)(base + lay.coef), L.anorm = (float *)(base + lay.anorm);
-  L.theta = (float *)(base + lay.theta);
+  if (vector_out) L.y = vector_out;
+  // the kernels only read the view's tables; the setup below fills them
+  auto writable = [](const int32_t *p) { return const_cast<int32_t *>(p); };
+  int32_t *gptr = writable(L.gptr), *cptr = writable(L.cptr), *chunk_graph = writable(L.chunk_graph), *chunk_begin = writable(L.chunk_begin),
+          *chunk_end = writable(L.chunk_end);
+  auto span = [](const void *from, const void *to) { return (size_t)((const char *)to - (const char *)from); };
 
   // ---- setup: the CSR lists and the graph ids checked, the graphs' node ranges read back once, the chunk table uploaded
   Scratch sc;
@@ -739,12 +727,12 @@ int32_t ngpde_csr_lambda_max(int64_t n, int64_t nnz, const int32_t *row_ptr, con
     NGPDE_HIP_CHECK(hipMemcpyAsync(chunk_begin, h_cb.data(), cb, hipMemcpyHostToDevice, stream));
     NGPDE_HIP_CHECK(hipMemcpyAsync(chunk_end, h_ce.data(), cb, hipMemcpyHostToDevice, stream));
   }
-  NGPDE_HIP_CHECK(hipMemsetAsync(base + lay.anorm, 0, lay.gptr - lay.anorm, stream));   // anorm, theta, steps, stop
-  NGPDE_HIP_CHECK(hipMemsetAsync(base + lay.alpha, 0, lay.anorm - lay.alpha, stream));   // alpha, beta, coef
+  NGPDE_HIP_CHECK(hipMemsetAsync(L.anorm, 0, span(L.anorm, gptr), stream));   // anorm, theta, steps, stop
+  NGPDE_HIP_CHECK(hipMemsetAsync(L.alpha, 0, span(L.alpha, L.anorm), stream));   // alpha, beta, coef
 
   const size_t gl = (size_t)n_graphs * (size_t)max_iter;
-  std::vector<float> h_ab(2 * gl + (lay.beta - lay.alpha - gl * 4) / 4, 0.f);   // alpha, the layout's padding, beta
-  const size_t beta_at = (lay.beta - lay.alpha) / 4;
+  const size_t beta_at = (size_t)(L.beta - L.alpha);
+  std::vector<float> h_ab(beta_at + gl, 0.f);   // alpha, the layout's padding, beta
   std::vector<int32_t> h_steps((size_t)n_graphs, 0), h_stop((size_t)n_graphs, 0), h_done((size_t)n_graphs, 0);
   std::vector<double> coef;
   auto read_state = [&]() -> int32_t {

@@ -230,17 +230,21 @@ __global__ void sssp_pass_end_kernel(int last_round, int32_t *__restrict__ ctl, 
   }
 }
 
-struct PathLayout {
-  size_t buf0, buf1, w_a, w_b, ctl, total;
-};
-
 // the columns of a round buffer for `rows` sources: 1, or the next multiple of kLane
 inline int64_t width_for(int64_t rows) { return rows <= 1 ? 1 : (rows + kLane - 1) / kLane * kLane; }
 
-PathLayout path_layout(int64_t n, int64_t nnz_a, int64_t nnz_b, int64_t n_sources, int separate) {
-  const size_t buf = up256((size_t)n * (size_t)width_for(separate ? std::min<int64_t>(n_sources, NGPDE_SSSP_PASS) : 1) * sizeof(float));
-  const size_t w_b = 2 * buf + up256((size_t)nnz_a * sizeof(float)), ctl = w_b + up256((size_t)nnz_b * sizeof(float));
-  return {0, buf, 2 * buf, w_b, ctl, ctl + kCtlBytes};
+struct PathWs {
+  float *buf[2];   // round r reads buf[(r - 1) & 1] and writes buf[r & 1]
+  float *w_a, *w_b;
+  int32_t *ctl;
+};
+void path_layout(Workspace &w, int64_t n, int64_t nnz_a, int64_t nnz_b, int64_t n_sources, int separate, PathWs &p) {
+  const size_t cells = (size_t)n * (size_t)width_for(separate ? std::min<int64_t>(n_sources, NGPDE_SSSP_PASS) : 1);
+  p.buf[0] = w.take<float>(cells);
+  p.buf[1] = w.take<float>(cells);
+  p.w_a = w.take<float>((size_t)nnz_a);
+  p.w_b = w.take<float>((size_t)nnz_b);
+  p.ctl = take_ctl(w);
 }
 
 bool sizes_ok(int64_t n, int64_t nnz_a, int64_t nnz_b, int64_t n_sources) {
@@ -263,7 +267,8 @@ extern "C" {
 
 size_t ngpde_csr_shortest_paths_workspace_bytes(int64_t n, int64_t nnz_a, int64_t nnz_b, int64_t n_sources, int32_t separate) {
   if (!sizes_ok(n, nnz_a, nnz_b, n_sources)) return 0;
-  return path_layout(n, nnz_a, nnz_b, n_sources, separate).total;
+  PathWs p;
+  return measure(path_layout, n, nnz_a, nnz_b, n_sources, separate, p);
 }
 
 int32_t ngpde_csr_shortest_paths(int64_t n, int64_t nnz_a, const int32_t *row_ptr_a, const int32_t *other_a, const int32_t *eid_a,
@@ -295,8 +300,8 @@ int32_t ngpde_csr_shortest_paths(int64_t n, int64_t nnz_a, const int32_t *row_pt
                 "%s: check_every 0 enqueues exactly max_rounds rounds: max_rounds must be given (positive)", fn);
   int64_t total;
   if (int32_t st = check_result(fn, n, n_sources, separate, dist_out, &total)) return st;
-  const PathLayout lay = path_layout(n, nnz_a, nnz_b, n_sources, separate);
-  if (int32_t st = check_workspace(fn, workspace, workspace_bytes, lay.total, 16)) return st;
+  if (int32_t st = check_workspace(fn, workspace, workspace_bytes, ngpde_csr_shortest_paths_workspace_bytes(n, nnz_a, nnz_b, n_sources, separate), 16))
+    return st;
   const int64_t max_r = max_rounds > 0 ? max_rounds : std::max<int64_t>(n, 1);
   const int64_t per = pass_sources(n_sources, separate), passes = total == 0 ? 0 : (n_sources + per - 1) / per;
   NGPDE_REQUIRE(check_every > 0 || max_r * passes <= kMaxUncheckedLaunches, NGPDE_ERR_UNSUPPORTED,
@@ -304,10 +309,11 @@ int32_t ngpde_csr_shortest_paths(int64_t n, int64_t nnz_a, const int32_t *row_pt
   const int64_t most = std::max({total, nnz_a + nnz_b, n * width_for(std::min<int64_t>(separate ? n_sources : 1, NGPDE_SSSP_PASS))});
   NGPDE_REQUIRE(most / kB < 0x7fffffffLL, NGPDE_ERR_UNSUPPORTED, "%s: %lld cells in one launch", fn, (long long)most);
 
-  char *base = (char *)workspace;
-  float *buf[2] = {(float *)(base + lay.buf0), (float *)(base + lay.buf1)};   // round r reads buf[(r - 1) & 1] and writes buf[r & 1]
-  float *w_a = (float *)(base + lay.w_a), *w_b = (float *)(base + lay.w_b);
-  int32_t *ctl = (int32_t *)(base + lay.ctl);
+  Workspace w(workspace);
+  PathWs p;
+  path_layout(w, n, nnz_a, nnz_b, n_sources, separate, p);
+  float *const *buf = p.buf, *const w_a = p.w_a, *const w_b = p.w_b;
+  int32_t *const ctl = p.ctl;
   int32_t st;
   if ((st = launch_zero(ctl, kCtlBytes, stream))) return st;
   if (weights && nnz_a > 0) {

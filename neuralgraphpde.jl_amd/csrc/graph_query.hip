@@ -282,8 +282,6 @@ __global__ __launch_bounds__(256) void rw_step_kernel(int64_t n, int64_t nnz, in
   }
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // the library's choice of block: 256 columns (a float4 per lane), fewer where the graph has fewer nodes or the two state buffers
 // would pass kRwWorkspaceCap
 int32_t rw_choose_block(int64_t n) {
@@ -292,19 +290,19 @@ int32_t rw_choose_block(int64_t n) {
   return (int32_t)b;
 }
 
-struct RwLayout {
-  size_t x0, x1, inv, flags, total;
+struct RwWs {
+  float *xbuf[2], *inv;   // the two state buffers [n][block], the inverse row sums
+  int32_t *flags;         // the last kRwFixedBytes
 };
-
-RwLayout rw_layout(int64_t n, int32_t block) {
-  RwLayout a;
-  const size_t state = (size_t)n * (size_t)block * 4;   // (a multiple of 256: block is one of 64)
-  a.x0 = 0;
-  a.x1 = state;
-  a.inv = 2 * state;
-  a.flags = a.inv + align256((size_t)n * 4);
-  a.total = a.flags + kRwFixedBytes;
-  return a;
+void rw_layout(Workspace &w, int64_t n, int32_t block, RwWs &p) {
+  p.xbuf[0] = w.take<float>((size_t)n * (size_t)block);
+  p.xbuf[1] = w.take<float>((size_t)n * (size_t)block);
+  p.inv = w.take<float>((size_t)n);
+  p.flags = w.take<int32_t>(kRwFixedBytes / sizeof(int32_t));
+}
+size_t rw_bytes(int64_t n, int32_t block) {
+  RwWs p;
+  return measure(rw_layout, n, block, p);
 }
 
 template <int V>
@@ -514,7 +512,7 @@ size_t ngpde_csr_random_walk_pe_workspace_bytes(int64_t n, int32_t block) {
   if (n < 0 || n > 0x7fffffffLL || block < 0 || block % kWave != 0) return 0;
   if (block == 0) block = rw_choose_block(n);
   if ((uint64_t)n * (uint64_t)block > (uint64_t)1 << 40) return 0;
-  return rw_layout(n, block).total;
+  return rw_bytes(n, block);
 }
 
 int32_t ngpde_csr_random_walk_pe(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *cols, const float *vals, int32_t n_graphs,
@@ -536,16 +534,14 @@ int32_t ngpde_csr_random_walk_pe(int64_t n, int64_t nnz, const int32_t *row_ptr,
   if (block == 0) block = rw_choose_block(n);
   NGPDE_REQUIRE((uint64_t)n * (uint64_t)block <= (uint64_t)1 << 40, NGPDE_ERR_UNSUPPORTED, "%s: %lld nodes x block %d: the state is too large", fn,
                 (long long)n, block);
-  const RwLayout lay = rw_layout(n, block);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= lay.total, NGPDE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes,
-                lay.total);
-  NGPDE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: the workspace is not 16-byte aligned", fn);
-  char *base = (char *)workspace;
-  float *xbuf[2] = {(float *)(base + lay.x0), (float *)(base + lay.x1)};
-  float *inv = (float *)(base + lay.inv);
-  int32_t *flags = (int32_t *)(base + lay.flags);
-  const int32_t n_blocks = (int32_t)((n + block - 1) / block);
   int32_t st;
+  if ((st = check_workspace(fn, workspace, workspace_bytes, rw_bytes(n, block), 16))) return st;
+  Workspace w(workspace);
+  RwWs p;
+  rw_layout(w, n, block, p);
+  float *const *xbuf = p.xbuf, *const inv = p.inv;
+  int32_t *const flags = p.flags;
+  const int32_t n_blocks = (int32_t)((n + block - 1) / block);
   if ((st = launch_zero(flags, kFlagWords * sizeof(int32_t), stream))) return st;
   hipLaunchKernelGGL(rw_check_kernel, dim3(blocks_for(std::max(n, nnz))), dim3(kB), 0, stream, n, nnz, row_ptr, cols, n_graphs, graph_of, flags);
   NGPDE_LAUNCH_CHECK("rw_check_kernel");

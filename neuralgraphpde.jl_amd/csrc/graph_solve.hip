@@ -385,48 +385,38 @@ __global__ __launch_bounds__(kBlock) void cg_direction_kernel(CgView V, int it) 
   }
 }
 
-size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int32_t pow2_ceil(int32_t v) {
   int32_t p = 1;
   while (p < v) p <<= 1;
   return p;
 }
 
-struct CgLayout {
-  size_t words, gptr, cptr, stop_it, brk, dinv, x, r, p, q, partial, rho, tol, total;
-  int64_t max_chunks;
-  int32_t dp, n_slabs, w_last;
-};
+// the view's geometry (n, n_graphs, d, dp, n_slabs, w_last, max_chunks) and its pieces, in workspace order
+void cg_layout(Workspace &w, int64_t n, int32_t n_graphs, int32_t n_rhs, CgView &V) {
+  V.n = n, V.n_graphs = n_graphs, V.d = n_rhs;
+  V.n_slabs = (n_rhs + kSlab - 1) / kSlab;
+  V.w_last = pow2_ceil(n_rhs - (V.n_slabs - 1) * kSlab);
+  V.dp = (V.n_slabs - 1) * kSlab + V.w_last;
+  V.max_chunks = (n + kChunk - 1) / kChunk + n_graphs;
+  const size_t pairs = (size_t)n_graphs * (size_t)V.dp, state = (size_t)n * (size_t)V.dp;
+  V.words = w.take<int32_t>(kCgWords);
+  V.gptr = w.take<int32_t>((size_t)n_graphs + 1);
+  V.cptr = w.take<int32_t>((size_t)n_graphs + 1);
+  V.stop_it = w.take<int32_t>(pairs);
+  V.brk = w.take<int32_t>(pairs);
+  V.dinv = w.take<float>((size_t)n);
+  V.x = w.take<float>(state);
+  V.r = w.take<float>(state);
+  V.p = w.take<float>(state);
+  V.q = w.take<float>(state);
+  V.partial = w.take<float>((size_t)kSlots * (size_t)V.max_chunks * (size_t)V.dp);
+  V.rho = w.take<float>(2 * pairs);
+  V.tol = w.take<float>(pairs);
+}
 
-CgLayout cg_layout(int64_t n, int32_t n_graphs, int32_t n_rhs) {
-  CgLayout a;
-  a.n_slabs = (n_rhs + kSlab - 1) / kSlab;
-  a.w_last = pow2_ceil(n_rhs - (a.n_slabs - 1) * kSlab);
-  a.dp = (a.n_slabs - 1) * kSlab + a.w_last;
-  a.max_chunks = (n + kChunk - 1) / kChunk + n_graphs;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    const size_t here = at;
-    at += align_up(bytes);
-    return here;
-  };
-  const size_t pairs = (size_t)n_graphs * (size_t)a.dp, state = (size_t)n * (size_t)a.dp * 4;
-  a.words = take(kCgWords * 4);
-  a.gptr = take(((size_t)n_graphs + 1) * 4);
-  a.cptr = take(((size_t)n_graphs + 1) * 4);
-  a.stop_it = take(pairs * 4);
-  a.brk = take(pairs * 4);
-  a.dinv = take((size_t)n * 4);
-  a.x = take(state);
-  a.r = take(state);
-  a.p = take(state);
-  a.q = take(state);
-  a.partial = take((size_t)kSlots * (size_t)a.max_chunks * (size_t)a.dp * 4);
-  a.rho = take(2 * pairs * 4);
-  a.tol = take(pairs * 4);
-  a.total = at;
-  return a;
+size_t cg_bytes(int64_t n, int32_t n_graphs, int32_t n_rhs) {
+  CgView V;
+  return measure(cg_layout, n, n_graphs, n_rhs, V);
 }
 
 bool cg_sizes_ok(int64_t n, int32_t n_graphs, int32_t n_rhs) {
@@ -446,7 +436,7 @@ extern "C" {
 
 size_t ngpde_csr_cg_workspace_bytes(int64_t n, int32_t n_graphs, int32_t n_rhs) {
   if (!cg_sizes_ok(n, n_graphs, n_rhs)) return 0;
-  return cg_layout(n, n_graphs, n_rhs).total;
+  return cg_bytes(n, n_graphs, n_rhs);
 }
 
 int32_t ngpde_csr_cg(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *cols, const float *vals, int32_t n_graphs,
@@ -475,19 +465,13 @@ int32_t ngpde_csr_cg(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32
   NGPDE_REQUIRE(row_ptr && (nnz == 0 || (cols && vals)), NGPDE_ERR_INVALID_ARGUMENT, "%s: row_ptr / cols / vals is NULL", fn);
   NGPDE_REQUIRE(n == 0 || (B && X), NGPDE_ERR_INVALID_ARGUMENT, "%s: B / X is NULL", fn);
   NGPDE_REQUIRE(status_out && iterations_out && residual_out, NGPDE_ERR_INVALID_ARGUMENT, "%s: an info array is NULL", fn);
-  const CgLayout lay = cg_layout(n, n_graphs, n_rhs);
-  NGPDE_REQUIRE(workspace && workspace_bytes >= lay.total, NGPDE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes,
-                lay.total);
-  char *base = (char *)workspace;
+  if (int32_t st = check_workspace(fn, workspace, workspace_bytes, cg_bytes(n, n_graphs, n_rhs), 1)) return st;
+  Workspace w(workspace);
   CgView V;
-  V.n = n, V.max_chunks = lay.max_chunks;
-  V.n_graphs = n_graphs, V.d = n_rhs, V.dp = lay.dp, V.n_slabs = lay.n_slabs, V.w_last = lay.w_last, V.max_iter = max_iter;
+  cg_layout(w, n, n_graphs, n_rhs, V);
+  V.max_iter = max_iter;
   V.row_ptr = row_ptr, V.cols = cols, V.graph_of = graph_of, V.vals = vals;
   V.shift = shift, V.scale = scale, V.rtol = rtol, V.atol = atol;
-  V.words = (int32_t *)(base + lay.words), V.gptr = (int32_t *)(base + lay.gptr), V.cptr = (int32_t *)(base + lay.cptr);
-  V.stop_it = (int32_t *)(base + lay.stop_it), V.brk = (int32_t *)(base + lay.brk);
-  V.dinv = (float *)(base + lay.dinv), V.x = (float *)(base + lay.x), V.r = (float *)(base + lay.r), V.p = (float *)(base + lay.p);
-  V.q = (float *)(base + lay.q), V.partial = (float *)(base + lay.partial), V.rho = (float *)(base + lay.rho), V.tol = (float *)(base + lay.tol);
   V.X = X, V.residual = residual_out, V.status = status_out, V.iterations = iterations_out;
 
   // ---- setup: the lists checked, the graphs' ranges and chunk counts, the diagonal, the pairs' state
@@ -500,7 +484,7 @@ int32_t ngpde_csr_cg(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32
   NGPDE_LAUNCH_CHECK("cg_setup_kernel");
   hipLaunchKernelGGL(cg_pairs_kernel, dim3(1), dim3(kBlock), 0, stream, V);
   NGPDE_LAUNCH_CHECK("cg_pairs_kernel");
-  const dim3 grid((unsigned)lay.max_chunks, (unsigned)lay.n_slabs), block(kBlock);
+  const dim3 grid((unsigned)V.max_chunks, (unsigned)V.n_slabs), block(kBlock);
   if (n > 0) {
     // ---- step 0: r = b - A x0, z, rho, the stop of a start that already solves the system, p = z
     hipLaunchKernelGGL(cg_load_kernel, grid, block, 0, stream, V, B, x0);

@@ -282,8 +282,17 @@ __global__ void reached_scatter_kernel(int64_t n, int base, const int32_t *__res
   if (i == n - 1) *count = pos[i] + keep[i];
 }
 
-// the workspace: seen, the two frontiers -- hop_words(n) bytes each -- and the control block
-inline size_t hop_words(int64_t n) { return up256((size_t)n * sizeof(u64)); }
+// the workspace: seen, the two frontiers -- a 64-bit word per node each -- and the control block
+struct HopWs {
+  u64 *seen, *fr[2];
+  int32_t *ctl;
+};
+void hop_layout(Workspace &w, int64_t n, HopWs &p) {
+  p.seen = w.take<u64>((size_t)n);
+  p.fr[0] = w.take<u64>((size_t)n);
+  p.fr[1] = w.take<u64>((size_t)n);
+  p.ctl = take_ctl(w);
+}
 
 int32_t check_rows(const char *fn, const char *what, int64_t nnz, const int32_t *ptr, const int32_t *other) {
   NGPDE_REQUIRE(nnz >= 0 && nnz <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "%s: %s %lld outside 0 : 2^31 - 1 (negative, or too large)", fn, what,
@@ -444,7 +453,8 @@ int32_t ngpde_coo_rows_eid(int64_t n_nodes, int64_t n_edges, const int32_t *s, c
 
 size_t ngpde_csr_hop_distance_workspace_bytes(int64_t n) {
   if (n < 0 || n > 0x7fffffffLL) return 0;
-  return 3 * hop_words(n) + kCtlBytes;
+  HopWs p;
+  return measure(hop_layout, n, p);
 }
 
 int32_t ngpde_csr_hop_distance(int64_t n, int64_t nnz_a, const int32_t *row_ptr_a, const int32_t *other_a, int64_t nnz_b,
@@ -468,15 +478,16 @@ int32_t ngpde_csr_hop_distance(int64_t n, int64_t nnz_a, const int32_t *row_ptr_
   int64_t total;
   if (int32_t st = check_result(fn, n, n_sources, separate, dist_out, &total)) return st;
   if (total == 0) return NGPDE_OK;
-  const size_t words = hop_words(n);
-  if (int32_t st = check_workspace(fn, workspace, workspace_bytes, 3 * words + kCtlBytes, 8)) return st;
+  if (int32_t st = check_workspace(fn, workspace, workspace_bytes, ngpde_csr_hop_distance_workspace_bytes(n), 8)) return st;
   const int64_t levels = std::min<int64_t>(max_hops < 0 ? n - 1 : max_hops, n - 1);   // (a shortest path has fewer than n edges)
   const int64_t per = pass_sources(n_sources, separate), passes = (n_sources + per - 1) / per;
   NGPDE_REQUIRE(check_every > 0 || levels * passes <= kMaxUncheckedLaunches, NGPDE_ERR_UNSUPPORTED,
                 "%s: max_hops %lld with check_every 0 would enqueue %lld launches", fn, (long long)max_hops, (long long)(levels * passes));
-  char *base = (char *)workspace;
-  u64 *seen = (u64 *)base, *fr[2] = {(u64 *)(base + words), (u64 *)(base + 2 * words)};
-  int32_t *ctl = (int32_t *)(base + 3 * words);
+  Workspace w(workspace);
+  HopWs p;
+  hop_layout(w, n, p);
+  u64 *const seen = p.seen, *const *fr = p.fr;
+  int32_t *const ctl = p.ctl;
   if (int32_t st = launch_zero(ctl, kCtlBytes, stream)) return st;
   NGPDE_REQUIRE(blocks_for(total) <= 0x7fffffffu && total / kB <= 0x7fffffffLL, NGPDE_ERR_UNSUPPORTED, "%s: %lld cells in one launch", fn,
                 (long long)total);

@@ -399,7 +399,8 @@ int32_t check_entry(const char *fn, const ngpde_readout *r, int32_t d, const int
   NGPDE_REQUIRE(r != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "%s: readout is NULL", fn);
   if (takes_workspace && d > 0) {
     const size_t need = workspace_floats(r, d) * sizeof(float);
-    NGPDE_REQUIRE(bytes >= need && (workspace || need == 0), NGPDE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, bytes, need);
+    if (need > 0)   // (a width the plan needs nothing for may come with no workspace)
+      if (int32_t st = check_workspace(fn, workspace, bytes, need, 1)) return st;
   }
   return NGPDE_OK;
 }

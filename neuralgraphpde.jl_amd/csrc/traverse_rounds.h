@@ -35,7 +35,7 @@ constexpr int64_t kMaxUncheckedLaunches = 1 << 20;   // what a call with check_e
 enum { cOffender = 0, cWeight = 2, cCsr = 4, cTurn = 5, cRounds = 8, cState = 9, cMore = 10, kCtlRead = 16 };
 
 inline u64 word_of(const int32_t *h, int at) { return (u64)(uint32_t)h[at] | (u64)(uint32_t)h[at + 1] << 32; }
-inline size_t up256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+inline int32_t *take_ctl(Workspace &w) { return w.take<int32_t>(kCtlBytes / sizeof(int32_t)); }   // taken LAST: the block ends the workspace
 
 __host__ __device__ __forceinline__ int round_word(int base, int r) { return base + r % 3; }
 __device__ __forceinline__ void rounds_arm(int32_t *ctl, int base, int64_t i) {   // lane i of the launch that starts a sequence of rounds
@@ -107,13 +107,6 @@ inline int32_t check_result(const char *fn, int64_t n, int64_t n_sources, int se
   NGPDE_REQUIRE(*total <= ((int64_t)1 << 40), NGPDE_ERR_UNSUPPORTED, "%s: %lld sources x %lld nodes: the result is too large", fn, (long long)n_rows,
                 (long long)n);
   NGPDE_REQUIRE(dist_out || *total == 0, NGPDE_ERR_INVALID_ARGUMENT, "%s: dist_out is NULL", fn);
-  return NGPDE_OK;
-}
-
-inline int32_t check_workspace(const char *fn, const void *workspace, size_t workspace_bytes, size_t needed, int align) {
-  NGPDE_REQUIRE(workspace && workspace_bytes >= needed, NGPDE_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, needed);
-  NGPDE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & (uintptr_t)(align - 1)) == 0, NGPDE_ERR_INVALID_ARGUMENT,
-                "%s: the workspace is not %d-byte aligned", fn, align);
   return NGPDE_OK;
 }
 
