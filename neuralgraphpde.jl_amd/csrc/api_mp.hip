@@ -15,20 +15,11 @@ int32_t make_segs(const char *fn, int32_t n_seg, const float *const *seg_ptr, co
                   const int32_t *seg_row_div, SegTable &t, int *din, int64_t n_rows = -1) {
   NGPDE_REQUIRE(n_seg >= 1 && n_seg <= 4, NGPDE_ERR_INVALID_ARGUMENT, "%s: 1..4 input blocks supported, got %d", fn, n_seg);
   NGPDE_REQUIRE(seg_ptr && seg_width, NGPDE_ERR_INVALID_ARGUMENT, "%s: NULL block table", fn);
-  t.n = n_seg;
-  int off = 0;
   for (int i = 0; i < n_seg; ++i) {
     NGPDE_REQUIRE(seg_width[i] >= 0, NGPDE_ERR_DIMENSION_MISMATCH, "%s: negative block width", fn);
     NGPDE_REQUIRE(seg_width[i] == 0 || n_rows == 0 || seg_ptr[i], NGPDE_ERR_INVALID_ARGUMENT, "%s: block %d is NULL", fn, i);
-    t.ptr[i] = seg_ptr[i];
-    t.width[i] = seg_width[i];
-    t.row_div[i] = (seg_row_div && seg_row_div[i] > 0) ? seg_row_div[i] : 1;
-    t.offset[i] = off;
-    t.vec[i] = (off % 4 == 0 && seg_width[i] % 4 == 0 && (reinterpret_cast<uintptr_t>(seg_ptr[i]) & 15) == 0) ? 1 : 0;
-    off += seg_width[i];
   }
-  for (int i = n_seg; i <= 4; ++i) t.offset[i] = off;
-  *din = off;
+  *din = fill_seg_table(t, n_seg, seg_ptr, seg_width, seg_row_div);
   return NGPDE_OK;
 }
 
@@ -36,18 +27,6 @@ int32_t check_act(const char *fn, int32_t act) {
   NGPDE_REQUIRE(act >= NGPDE_ACT_IDENTITY && act <= NGPDE_ACT_SOFTPLUS, NGPDE_ERR_INVALID_ARGUMENT,
                 "%s: unknown activation code %d", fn, act);
   return NGPDE_OK;
-}
-
-constexpr size_t kWsSlack = 256;   // what the Dense and GAT queries add behind their pieces
-
-// the Dense pullback: dz (the one-launch forms put their slabs there), the weight pullback's slabs, the split input pullback's partials
-struct DenseBwdWs {
-  float *dz, *partial, *split_part;
-};
-void dense_bwd_layout(Workspace &w, int64_t n, int32_t din, int32_t dout, DenseBwdWs &p) {
-  p.dz = w.take<float>((size_t)std::max<int64_t>(n, 1) * dout);
-  p.partial = w.take<float>((size_t)dense_weight_chunks(n, din, dout) * (din + 1) * dout);
-  p.split_part = reinterpret_cast<float *>(w.take<char>(dense_bwd_input_split_bytes(n, din, dout)));
 }
 
 // the unfused GAT pullback: the edges' score gradients, the two per-node score gradients
@@ -118,7 +97,7 @@ int32_t ngpde_dense_pair_forward(int64_t n, int32_t n_seg_a, const float *const 
                 "ngpde_dense_pair_forward: DimensionMismatch (rows must be in [0, 2^31), dout > 0)");
   if (n == 0) return NGPDE_OK;
   NGPDE_REQUIRE(weight_a && y_a && weight_b && y_b, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_dense_pair_forward: weight/y is NULL");
-  if (dense_pair_fwd_applicable(n, ta, dina, dout_a, tb, dinb, dout_b))
+  if (dense_pair_fwd_plan(n, ta, dina, dout_a, tb, dinb, dout_b).fused)
     return launch_dense_pair_fwd(n, ta, dina, dout_a, act_a, weight_a, bias_a, y_a, save_z_a, tb, dinb, dout_b, act_b, weight_b, bias_b,
                                  y_b, save_z_b, (hipStream_t)stream);
   if ((st = launch_dense_seg_fwd(n, ta, dina, dout_a, act_a, weight_a, bias_a, y_a, save_z_a, (hipStream_t)stream))) return st;
@@ -130,7 +109,7 @@ int32_t ngpde_dense_chain2_fused(int64_t n, int32_t n_seg, const float *const *s
   SegTable t;
   int din = 0;
   if (make_segs("ngpde_dense_chain2_fused", n_seg, seg_ptr, seg_width, seg_row_div, t, &din)) return 0;
-  return (n > 0 && n < ((int64_t)1 << 31) && dense_chain_fwd_applicable(n, t, din, dmid, dout)) ? 1 : 0;
+  return (n > 0 && n < ((int64_t)1 << 31) && dense_chain_fwd_plan(n, t, din, dmid, dout).n_main) ? 1 : 0;
 }
 
 int32_t ngpde_dense_chain2_forward(int64_t n, int32_t n_seg, const float *const *seg_ptr, const int32_t *seg_width,
@@ -146,8 +125,8 @@ int32_t ngpde_dense_chain2_forward(int64_t n, int32_t n_seg, const float *const 
                 "ngpde_dense_chain2_forward: DimensionMismatch (rows must be in [0, 2^31), widths > 0)");
   if (n == 0) return NGPDE_OK;
   NGPDE_REQUIRE(weight1 && weight2 && y, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_dense_chain2_forward: weight/y is NULL");
-  if (dense_chain_fwd_applicable(n, t, din, dmid, dout))
-    return launch_dense_chain_fwd(n, t, din, act1, weight1, bias1, a1, save_z1, dout, act2, weight2, bias2, y, save_z2, (hipStream_t)stream);
+  if (const DenseChainFwd chain = dense_chain_fwd_plan(n, t, din, dmid, dout); chain.n_main)
+    return launch_dense_chain_fwd(chain, n, t, din, act1, weight1, bias1, a1, save_z1, dout, act2, weight2, bias2, y, save_z2, (hipStream_t)stream);
   NGPDE_REQUIRE(a1 != nullptr, NGPDE_ERR_INVALID_ARGUMENT,
                 "ngpde_dense_chain2_forward: this shape runs as two launches and needs the [n][dmid] buffer a1 (ngpde_dense_chain2_fused)");
   if ((st = launch_dense_seg_fwd(n, t, din, dmid, act1, weight1, bias1, a1, save_z1, (hipStream_t)stream))) return st;
@@ -165,10 +144,9 @@ size_t ngpde_dense_pair_backward_workspace_bytes(int64_t n, int32_t n_seg_a, con
   SegTable ta, tb;
   int dina = 0, dinb = 0;
   if (make_segs("ngpde_dense_pair_backward", n_seg_a, seg_ptr_a, seg_width_a, seg_row_div_a, ta, &dina) ||
-      make_segs("ngpde_dense_pair_backward", n_seg_b, seg_ptr_b, seg_width_b, seg_row_div_b, tb, &dinb) || dout != 64)
+      make_segs("ngpde_dense_pair_backward", n_seg_b, seg_ptr_b, seg_width_b, seg_row_div_b, tb, &dinb))
     return 0;
-  const int grid = dense_pair_bwd_grid(n, ta, dina, tb, dinb);
-  return grid ? dense_pair_bwd_workspace(grid, dina, dinb) : 0;
+  return dense_pair_bwd_plan(n, ta, dina, tb, dinb, dout).workspace_bytes;
 }
 
 int32_t ngpde_dense_pair_backward(int64_t n, int32_t n_seg_a, const float *const *seg_ptr_a, const int32_t *seg_width_a,
@@ -182,20 +160,19 @@ int32_t ngpde_dense_pair_backward(int64_t n, int32_t n_seg_a, const float *const
   int dina = 0, dinb = 0;
   int32_t st = make_segs("ngpde_dense_pair_backward", n_seg_a, seg_ptr_a, seg_width_a, seg_row_div_a, ta, &dina);
   if (st || (st = make_segs("ngpde_dense_pair_backward", n_seg_b, seg_ptr_b, seg_width_b, seg_row_div_b, tb, &dinb))) return st;
-  const int grid = (dout == 64 && n > 0) ? dense_pair_bwd_grid(n, ta, dina, tb, dinb) : 0;
-  NGPDE_REQUIRE(grid > 0, NGPDE_ERR_UNSUPPORTED,
+  const DensePairBwd form = dense_pair_bwd_plan(n, ta, dina, tb, dinb, dout);
+  NGPDE_REQUIRE(form.grid > 0, NGPDE_ERR_UNSUPPORTED,
                 "ngpde_dense_pair_backward: needs 64 outputs, a shared 16-byte aligned 64-wide leading block, <= 4 narrow features per "
                 "side and >= 32768 rows (ngpde_dense_pair_backward_workspace_bytes returns 0 otherwise): use two ngpde_dense_backward calls");
   NGPDE_REQUIRE(weight_a && weight_b && dy_a && dy_b && dweight_a && dweight_b && dx, NGPDE_ERR_INVALID_ARGUMENT,
                 "ngpde_dense_pair_backward: NULL argument");
-  if ((st = check_workspace("ngpde_dense_pair_backward", workspace, workspace_bytes, dense_pair_bwd_workspace(grid, dina, dinb), 1))) return st;
-  return launch_dense_pair_bwd(n, ta, dina, weight_a, dy_a, dweight_a, dbias_a, tb, dinb, weight_b, dy_b, dweight_b, dbias_b, dx, dx_addend,
-                               workspace, grid, (hipStream_t)stream);
+  if ((st = check_workspace("ngpde_dense_pair_backward", workspace, workspace_bytes, form.workspace_bytes, 1))) return st;
+  return launch_dense_pair_bwd(form, n, ta, dina, weight_a, dy_a, dweight_a, dbias_a, tb, dinb, weight_b, dy_b, dweight_b, dbias_b, dx, dx_addend,
+                               workspace, (hipStream_t)stream);
 }
 
 size_t ngpde_dense_workspace_bytes(int64_t n, int32_t din_total, int32_t dout) {
-  DenseBwdWs p;
-  return measure(dense_bwd_layout, n, din_total, dout, p) + kWsSlack;
+  return dense_bwd_workspace_bytes(n, din_total, dout);
 }
 
 int32_t ngpde_dense_backward(int64_t n, int32_t n_seg, const float *const *seg_ptr, const int32_t *seg_width,
@@ -218,35 +195,18 @@ int32_t ngpde_dense_backward(int64_t n, int32_t n_seg, const float *const *seg_p
   NGPDE_REQUIRE(weight && dy && (z || act == NGPDE_ACT_IDENTITY), NGPDE_ERR_INVALID_ARGUMENT,
                 "ngpde_dense_backward: weight/z/dy is NULL");
   if ((st = check_workspace("ngpde_dense_backward", workspace, workspace_bytes, ngpde_dense_workspace_bytes(n, din, dout), 1))) return st;
-  if (const int sgrid = dense_stream_bwd_grid(n, t, din, dout, dseg_ptr))   // one streaming launch (slabs in the dz area)
-    return launch_dense_stream_bwd(n, t, din, act, weight, z, dy, dseg_ptr, dweight, dbias, (float *)workspace, sgrid, stream);
-  if (const int sgrid = dense_small_bwd_grid(n, din, dout))                   // at most 64 x 64, latency-bound row counts: one launch too
-    return launch_dense_small_bwd(n, t, din, dout, act, weight, z, dy, dseg_ptr, dweight, dbias, (float *)workspace, sgrid, stream);
-  Workspace w(workspace);
-  DenseBwdWs p;
-  dense_bwd_layout(w, n, din, dout, p);
-  float *dz = p.dz;
-  if (act == NGPDE_ACT_IDENTITY) {
-    dz = const_cast<float *>(dy);   // read-only below
-  } else if ((st = launch_dense_dz(n * dout, act, dy, z, dz, stream))) {
-    return st;
-  }
-  if ((st = launch_dense_seg_bwd_weight(n, t, din, dout, dz, dweight, dbias, p.partial, stream))) return st;
-  if (dseg_ptr) {
-    SegGrad gsg;
-    gsg.n = t.n;
-    bool any = false;
-    for (int i = 0; i < t.n; ++i) {
-      gsg.ptr[i] = (t.row_div[i] == 1) ? dseg_ptr[i] : nullptr;   // per-graph blocks carry no gradient (@ignore_derivatives, :397,:418)
-      gsg.width[i] = t.width[i];
-      any = any || gsg.ptr[i];
-    }
-    for (int i = 0; i <= 4; ++i) gsg.offset[i] = t.offset[i];
-    if (any && t.n == 1 && dense_bwd_input_splits(n, din, dout) > 1) {   // few rows, very wide output: split the contraction
-      if ((st = launch_dense_bwd_input_splitk(n, gsg.ptr[0], din, dout, dz, weight, p.split_part, stream))) return st;
-    } else if (any && (st = launch_dense_seg_bwd_input(n, gsg, din, dout, dz, weight, stream))) return st;
-  }
-  return NGPDE_OK;
+  const SegGrad grads = seg_grads(t, dseg_ptr);
+  const DenseBwd plan = dense_bwd_plan(n, t, grads, din, dout, act == NGPDE_ACT_IDENTITY, dbias != nullptr, weight, dy, workspace);
+  if (plan.form == DenseBwdForm::Stream)
+    return launch_dense_stream_bwd(plan.stream, n, t, grads, din, act, weight, z, dy, dweight, dbias, (float *)workspace, stream);
+  if (plan.form == DenseBwdForm::Small)
+    return launch_dense_small_bwd(n, t, din, dout, act, weight, z, dy, grads, dweight, dbias, (float *)workspace, plan.small_grid, stream);
+  const float *dz = plan.dz ? plan.ws.dz : dy;
+  if (plan.dz && (st = launch_dense_dz(n * dout, act, dy, z, plan.ws.dz, stream))) return st;
+  if ((st = launch_dense_seg_bwd_weight(plan.weight, n, t, din, dout, dz, dweight, dbias, plan.ws.partial, stream))) return st;
+  if (plan.input.form == DenseInputForm::Gemm128Split || plan.input.form == DenseInputForm::WideSplit)
+    return launch_dense_bwd_input_splitk(plan.input, n, grads.ptr[0], din, dout, dz, weight, plan.ws.split_part, stream);
+  return launch_dense_seg_bwd_input(plan.input, n, grads, din, dout, dz, weight, stream);
 }
 
 int32_t ngpde_edge_permute(const ngpde_graph_t *g, int32_t d, int32_t inverse, const float *src, float *dst,

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ngpde.h"
+#include "dense_forms.h"
 #include "workspace.h"
 
 namespace ngpde {
@@ -383,58 +384,50 @@ int32_t launch_act_bwd(int64_t count, int act, const float *dy, const float *z, 
 int32_t launch_colsum(int64_t n, int d, const float *a, float *out, hipStream_t stream);
 
 // ---- message-passing primitives (mp_kernels.hip) -------------------------------------------------------
-struct SegTable {   // virtual concatenation [X1 | X2 | ...] of up to 4 row-major blocks
-  int n = 0;
-  const float *ptr[4] = {nullptr, nullptr, nullptr, nullptr};
-  int width[4] = {0, 0, 0, 0};
-  int row_div[4] = {1, 1, 1, 1};   // block row = row / row_div (per-graph features repeated over a graph's rows)
-  int offset[5] = {0, 0, 0, 0, 0};
-  int vec[4] = {0, 0, 0, 0};       // block may be read with 16-byte loads (offset, width multiples of 4, base aligned)
-};
-struct SegGrad {
-  int n = 0;
-  float *ptr[4] = {nullptr, nullptr, nullptr, nullptr};
-  int width[4] = {0, 0, 0, 0};
-  int offset[5] = {0, 0, 0, 0, 0};
-};
+// (the block tables SegTable / SegGrad and every choice of a Dense kernel: dense_forms.h; the launchers below execute a decision)
 int32_t launch_dense_multi_fwd(int count, const int64_t *n, const SegTable *segs, const int *din, const int *dout, const int *act,
                                const float *const *wt, const float *const *bias, float *const *y, float *const *save_z, hipStream_t stream);
-int32_t launch_dense_seg_fwd(int64_t n, const SegTable &segs, int din, int dout, int act, const float *wt,
+int32_t launch_dense_seg_fwd(const DenseFwd &form, int64_t n, const SegTable &segs, int din, int dout, int act, const float *wt,
                              const float *bias, float *y, float *save_z, hipStream_t stream);
-int dense_fwd_splits(int64_t n, int din, int dout);
-// two Dense layers in one streaming launch (dense_mfma.hip): two outputs from one 64-wide input block / a two-layer chain
-bool dense_pair_fwd_applicable(int64_t n, const SegTable &ta, int dina, int douta, const SegTable &tb, int dinb, int doutb);
+inline int32_t launch_dense_seg_fwd(int64_t n, const SegTable &segs, int din, int dout, int act, const float *wt, const float *bias, float *y,
+                                    float *save_z, hipStream_t stream) {
+  return launch_dense_seg_fwd(dense_fwd_plan(n, segs, din, dout, wt, y, save_z), n, segs, din, dout, act, wt, bias, y, save_z, stream);
+}
+// two Dense layers in one streaming launch (dense_mfma.hip): two outputs from one 64-wide input block (dense_pair_fwd_plan says when) /
+// a two-layer chain over c.n_main = 1 or 2 leading blocks (dense_chain_fwd_plan)
 int32_t launch_dense_pair_fwd(int64_t n, const SegTable &ta, int dina, int douta, int acta, const float *wta, const float *ba, float *ya,
                               float *za, const SegTable &tb, int dinb, int doutb, int actb, const float *wtb, const float *bb, float *yb,
                               float *zb, hipStream_t stream);
-bool dense_chain_fwd_applicable(int64_t n, const SegTable &t1, int din1, int dmid, int dout2);
-int32_t launch_dense_chain_fwd(int64_t n, const SegTable &t1, int din1, int act1, const float *wt1, const float *b1, float *a1, float *z1,
+int32_t launch_dense_chain_fwd(const DenseChainFwd &c, int64_t n, const SegTable &t1, int din1, int act1, const float *wt1, const float *b1, float *a1, float *z1,
                                int dout2, int act2, const float *wt2, const float *b2, float *y, float *z2, hipStream_t stream);
-int dense_fwd_split_count(int din, int nsplit);
 int32_t launch_dense_seg_fwd_splitk(int64_t n, const SegTable &segs, int din, int dout, const float *wt, float *partial, int nsplit,
                                     hipStream_t stream);
 int32_t launch_sum_partials(int64_t count, int nparts, size_t stride, float *x, hipStream_t stream);
 int32_t launch_spmm_gcn_tail(const ngpde_graph *g, int d, const float *x, const float *bias, int act, float *out, float *save_z,
                              hipStream_t stream);
 int32_t launch_dense_dz(int64_t count, int act, const float *dy, const float *z, float *dz, hipStream_t stream);
-int32_t launch_dense_seg_bwd_input(int64_t n, const SegGrad &segs, int din, int dout, const float *dz, const float *wt,
+// the whole input pullback (form Wide or Mfma: dense_bwd_input_plan)
+int32_t launch_dense_seg_bwd_input(const DenseBwdInput &form, int64_t n, const SegGrad &segs, int din, int dout, const float *dz, const float *wt,
                                    hipStream_t stream);
-int dense_weight_chunks(int64_t n, int din, int dout);
-// dense_stream_bwd.hip: the whole Dense pullback (dz, input and weight pullbacks, bias) as one streaming launch; grid 0 = not applicable
-int dense_stream_bwd_grid(int64_t n, const SegTable &t, int din, int dout, float *const *dseg);
-int dense_pair_bwd_grid(int64_t n, const SegTable &ta, int dina, const SegTable &tb, int dinb);
-size_t dense_pair_bwd_workspace(int grid, int dina, int dinb);
-int32_t launch_dense_pair_bwd(int64_t n, const SegTable &ta, int dina, const float *wta, const float *dya, float *dwta, float *dba,
-                              const SegTable &tb, int dinb, const float *wtb, const float *dyb, float *dwtb, float *dbb, float *dx,
-                              const float *dx_add, void *workspace, int grid, hipStream_t stream);
-int32_t launch_dense_stream_bwd(int64_t n, const SegTable &t, int din, int act, const float *wt, const float *z, const float *dy,
-                                float *const *dseg, float *dwt, float *dbias, float *slabs, int grid, hipStream_t stream);
-int dense_bwd_input_splits(int64_t n, int din, int dout);
-size_t dense_bwd_input_split_bytes(int64_t n, int din, int dout);
-int32_t launch_dense_bwd_input_splitk(int64_t n, float *dx, int din, int dout, const float *dz, const float *wt, float *part,
-                                      hipStream_t stream);
-int32_t launch_dense_seg_bwd_weight(int64_t n, const SegTable &segs, int din, int dout, const float *dz, float *dwt,
+inline int32_t launch_dense_seg_bwd_input(int64_t n, const SegGrad &segs, int din, int dout, const float *dz, const float *wt, hipStream_t stream) {
+  return launch_dense_seg_bwd_input(dense_bwd_input_plan(n, din, dout), n, segs, din, dout, dz, wt, stream);
+}
+// dense_stream_bwd.hip: the whole Dense pullback (dz, input and weight pullbacks, bias) as one streaming launch, a pair's likewise
+int32_t launch_dense_pair_bwd(const DensePairBwd &form, int64_t n, const SegTable &ta, int dina, const float *wta, const float *dya, float *dwta,
+                              float *dba, const SegTable &tb, int dinb, const float *wtb, const float *dyb, float *dwtb, float *dbb, float *dx,
+                              const float *dx_add, void *workspace, hipStream_t stream);
+int32_t launch_dense_stream_bwd(const DenseStreamBwd &form, int64_t n, const SegTable &t, const SegGrad &grads, int din, int act, const float *wt,
+                                const float *z, const float *dy, float *dwt, float *dbias, float *slabs, hipStream_t stream);
+// a single block's input pullback split over the output features (form Gemm128Split or WideSplit: dense_bwd_input_split_plan)
+int32_t launch_dense_bwd_input_splitk(const DenseBwdInput &form, int64_t n, float *dx, int din, int dout, const float *dz, const float *wt,
+                                      float *part, hipStream_t stream);
+int32_t launch_dense_seg_bwd_weight(const DenseBwdWeight &form, int64_t n, const SegTable &segs, int din, int dout, const float *dz, float *dwt,
                                     float *db, float *partial, hipStream_t stream);
+inline int32_t launch_dense_seg_bwd_weight(int64_t n, const SegTable &segs, int din, int dout, const float *dz, float *dwt, float *db,
+                                           float *partial, hipStream_t stream) {
+  return launch_dense_seg_bwd_weight(dense_bwd_weight_plan(n, segs, din, dout, dz, db != nullptr, partial), n, segs, din, dout, dz, dwt, db, partial,
+                                     stream);
+}
 int32_t launch_edge_permute(const ngpde_graph *g, int d, bool inverse, const float *src, float *dst, hipStream_t stream);
 int32_t launch_edge_combine_fwd(const ngpde_graph *g, int h, int act, const float *P, const float *Q, const float *Eterm,
                                 float *a_out, float *z_out, hipStream_t stream);
@@ -520,12 +513,10 @@ size_t edge_mlp_fused_bwd_workspace(const ngpde_graph *g, int h1, int n_tail, in
 int32_t launch_edge_mlp_fused_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hipStream_t stream);
 int32_t launch_dense_weight_reduce(int nchunk, int din, int dout, const float *partial, float *dwt, float *db, hipStream_t stream);
 // the whole pullback of a Dense of at most 64 x 64 in one launch + the slab reduction (dense_small_bwd.hip)
-int dense_small_bwd_grid(int64_t n, int din, int dout);
-int dense_small_fwd_grid(int64_t n, int din, int dout);
 int32_t launch_dense_small_fwd(int64_t n, const SegTable &t, int din, int dout, int act, const float *wt, const float *bias, float *y,
                                float *save_z, int grid, hipStream_t stream);
 int32_t launch_dense_small_bwd(int64_t n, const SegTable &t, int din, int dout, int act, const float *wt, const float *z, const float *dy,
-                               float *const *dseg, float *dwt, float *dbias, float *slabs, int grid, hipStream_t stream);
+                               const SegGrad &grads, float *dwt, float *dbias, float *slabs, int grid, hipStream_t stream);
 int32_t launch_edge_sum_by_source(const ngpde_graph *g, int h, const float *per_edge, float *out, hipStream_t stream);
 bool edge_mlp_fused_supported(const ngpde_graph *g, const EdgeMlpArgs &a);
 int32_t launch_edge_mlp_fused_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hipStream_t stream);

@@ -10,13 +10,13 @@
 #include "common.h"
 #include "device_utils.h"
 #include "stamps.h"
-#include "switches.h"
 
 namespace ngpde {
 
 namespace {
 
 constexpr int BM = 64, BN = 64, BK = 16, LS = BK + 4;   // LDS row stride 20 floats: 16-byte aligned b128 rows
+static_assert(BM == kDenseRows64 && BN == kDenseCols64 && BK == kDenseK16, "dense_forms.h decides in these tiles");
 
 // rows are < 2^31 (host-checked), so the per-graph row division is a 32-bit one and only taken when a block asks for it
 __device__ __forceinline__ int64_t seg_row(int64_t row, int row_div) {
@@ -222,6 +222,7 @@ __global__ __launch_bounds__(256) void dense_mfma_bwd_input_kernel(int64_t n, Se
 // segmented input allows it, outputs transposed through LDS into full 256-byte row stores).  Used whenever the problem
 // has enough 128-row tiles to fill the chip; the 64-row kernels above serve the small cases.
 constexpr int BM2 = 128, BK2 = 32, LS2 = BK2 + 4, OS2 = BN + 4;
+static_assert(BM2 == kDenseRows128 && BK2 == kDenseK32, "dense_forms.h decides in these tiles");
 constexpr int kWideLds = (BM2 * OS2 > (BM2 + BN) * LS2) ? BM2 * OS2 : (BM2 + BN) * LS2;   // floats
 
 // 4 consecutive features k..k+3 of row `row` of the segmented input (k % 4 == 0)
@@ -370,6 +371,7 @@ __global__ __launch_bounds__(256, 4) void dense_wide_fwd_kernel(int64_t n, SegTa
 // through a private 16 x 64 LDS patch, row tile by row tile, as full 256-byte row segments.  Single 16-byte-loadable input
 // block, din % 16 == 0, dout % 4 == 0.
 constexpr int BG = 128, BKG = 16, LSG = BKG + 4;
+static_assert(BG == kDenseRows128 && BG == kDenseCols128 && BKG == kDenseK16, "dense_forms.h decides in these tiles");
 __global__ __launch_bounds__(256, 3) void dense_gemm128_fwd_kernel(int64_t n, const float *__restrict__ x, int din, int dout, int act,
                                                                 const float *__restrict__ wt, const float *__restrict__ bias,
                                                                 float *__restrict__ y, float *__restrict__ save_z) {
@@ -832,6 +834,7 @@ __device__ __forceinline__ void stage_cols(float *tile, int half, int ct, int la
 // workgroup), xn[row][kNarrowAll] = their values on the tile's rows (one or two loads per thread at the top of the tile, in
 // flight under the products) -- the epilogue then has no global load of its own.
 constexpr int kNarrow = 4, kNarrowAll = 8;
+static_assert(kNarrow == kDenseNarrow && kNarrowAll == kDenseTrailing, "dense_forms.h decides with these widths");
 __device__ __forceinline__ void narrow_weights(const StreamOut &o, int kmain, float *wn, int tid) {
   for (int idx = tid; idx < kNarrow * 64; idx += kStreamThreads) {
     const int f = idx >> 6, c = idx & 63;
@@ -1255,53 +1258,41 @@ __global__ __launch_bounds__(256) void dense_weight_reduce_kernel(int nchunk, in
 
 }  // namespace
 
-// 128-row tiles once they alone give every CU two workgroups
-static bool use_wide_tiles(int64_t n, int cols) {
-  return !switch_on(Switch::DenseNarrow) && ((n + BM2 - 1) / BM2) * ((cols + BN - 1) / BN) >= 512;
+// CUs times the workgroups of `kernel` (kStreamThreads threads, dyn_lds bytes of dynamic LDS) a CU holds: the grid of a persistent
+// streaming launch (one query per kernel and process: the callers keep it)
+static int stream_grid(const void *kernel, size_t dyn_lds) {
+  int dev = 0, cus = 0, per_cu = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kStreamThreads, dyn_lds);
+  return std::max(cus, 1) * std::max(per_cu, 1);
 }
 
-int32_t launch_dense_seg_fwd(int64_t n, const SegTable &segs, int din, int dout, int act, const float *wt,
+int32_t launch_dense_seg_fwd(const DenseFwd &form, int64_t n, const SegTable &segs, int din, int dout, int act, const float *wt,
                              const float *bias, float *y, float *save_z, hipStream_t stream) {
-  if (n == 0 || dout == 0) return NGPDE_OK;
-  if (const int sgrid = dense_small_fwd_grid(n, din, dout))   // 17 .. 64 inputs, at most 64 outputs, latency-bound row counts: one contraction pass
-    return launch_dense_small_fwd(n, segs, din, dout, act, wt, bias, y, save_z, sgrid, stream);
-  {   // wide outputs from one 16-byte-loadable block: 128 x 128 tiles
-    const int64_t tiles = ((n + BG - 1) / BG) * ((dout + BG - 1) / BG);
-    if (!switch_on(Switch::DenseNoGemm128) && segs.n == 1 && segs.vec[0] && segs.row_div[0] == 1 && din % BKG == 0 && dout % 4 == 0 && dout >= BG && tiles >= 512 &&
-        ((reinterpret_cast<uintptr_t>(wt) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(save_z)) & 15) == 0) {
+  switch (form.form) {
+    case DenseFwdForm::None: return NGPDE_OK;
+    case DenseFwdForm::Small: return launch_dense_small_fwd(n, segs, din, dout, act, wt, bias, y, save_z, form.grid, stream);
+    case DenseFwdForm::Gemm128:
       hipLaunchKernelGGL(dense_gemm128_fwd_kernel, dim3((unsigned)((n + BG - 1) / BG), (dout + BG - 1) / BG), dim3(256), 0, stream, n,
                          segs.ptr[0], din, dout, act, wt, bias, y, save_z);
       NGPDE_LAUNCH_CHECK("dense_gemm128_fwd_kernel");
       return NGPDE_OK;
-    }
-  }
-  if (use_wide_tiles(n, dout)) {
-    // trailing narrow blocks (<= 8 features in total behind a multiple of 32) leave the K loop: see dense_wide_fwd_kernel
-    int din_main = din;
-    for (int i = segs.n - 1; i >= 1 && din - segs.offset[i] <= 8; --i)
-      if (segs.offset[i] % BK2 == 0) din_main = segs.offset[i];
-    // a 64-deep contraction over 16-byte-loadable blocks: the streaming form (whole input tile by LDS-DMA in one burst)
-    bool stream_ok = !switch_on(Switch::DenseNoStream) && din_main == 64 && dout <= 64;
-    for (int i = 0; i < segs.n && segs.offset[i] < din_main; ++i) stream_ok = stream_ok && segs.vec[i] && segs.offset[i + 1] <= din_main;
-    if (stream_ok) {
-      static int cus = 0, per_cu = 0;
-      if (cus == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dense_stream64_fwd_kernel, kStreamThreads, 0);
-        cus = std::max(cus, 1); per_cu = std::max(per_cu, 1);
-      }
+    case DenseFwdForm::Stream: {
+      static int cap = 0;
+      if (!cap) cap = stream_grid(reinterpret_cast<const void *>(dense_stream64_fwd_kernel), 0);
       const int n_tiles = (int)((n + BM2 - 1) / BM2);
-      hipLaunchKernelGGL(dense_stream64_fwd_kernel, dim3((unsigned)std::min(n_tiles, cus * per_cu)), dim3(kStreamThreads), 0, stream,
+      hipLaunchKernelGGL(dense_stream64_fwd_kernel, dim3((unsigned)std::min(n_tiles, cap)), dim3(kStreamThreads), 0, stream,
                          n, segs, din, dout, act, wt, bias, y, save_z, n_tiles);
       NGPDE_LAUNCH_CHECK("dense_stream64_fwd_kernel");
       return NGPDE_OK;
     }
-    hipLaunchKernelGGL(dense_wide_fwd_kernel, dim3((unsigned)((n + BM2 - 1) / BM2), (dout + BN - 1) / BN), dim3(256), 0, stream,
-                       n, segs, din, dout, act, wt, bias, y, save_z, din_main);
-    NGPDE_LAUNCH_CHECK("dense_wide_fwd_kernel");
-    return NGPDE_OK;
+    case DenseFwdForm::Wide:
+      hipLaunchKernelGGL(dense_wide_fwd_kernel, dim3((unsigned)((n + BM2 - 1) / BM2), (dout + BN - 1) / BN), dim3(256), 0, stream,
+                         n, segs, din, dout, act, wt, bias, y, save_z, form.din_main);
+      NGPDE_LAUNCH_CHECK("dense_wide_fwd_kernel");
+      return NGPDE_OK;
+    case DenseFwdForm::General: break;
   }
   hipLaunchKernelGGL(dense_mfma_fwd_kernel, dim3((unsigned)((n + BM - 1) / BM), (dout + BN - 1) / BN), dim3(256), 0, stream,
                      n, segs, din, dout, act, wt, bias, y, save_z, din, (size_t)0);
@@ -1331,29 +1322,16 @@ int32_t launch_dense_multi_fwd(int count, const int64_t *n, const SegTable *segs
   return NGPDE_OK;
 }
 
-// number of K splits worth taking for X[n][din] x W[din][dout]: only when the row tiles alone leave most of the chip idle and
-// the contraction is long; every split gets a multiple of BK features
-int dense_fwd_splits(int64_t n, int din, int dout) {
-  const int64_t tiles = ((n + BM - 1) / BM) * ((dout + BN - 1) / BN);
-  if (tiles == 0 || tiles >= 256 || din < 256) return 1;   // (no rows: nothing to split, and no division by zero tiles)
-  const int64_t want = (512 + tiles - 1) / tiles;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(want, din / 64));
-}
-
 // partial[z][n][dout] = X[:, range z] x W[range z, :], z < nsplit (nsplit from dense_fwd_splits)
 int32_t launch_dense_seg_fwd_splitk(int64_t n, const SegTable &segs, int din, int dout, const float *wt, float *partial, int nsplit,
                                     hipStream_t stream) {
   if (n == 0 || dout == 0) return NGPDE_OK;
-  const int kper = ((din + nsplit - 1) / nsplit + BK - 1) / BK * BK;
+  const int kper = dense_fwd_split_features(din, nsplit);
   hipLaunchKernelGGL(dense_mfma_fwd_kernel, dim3((unsigned)((n + BM - 1) / BM), (dout + BN - 1) / BN, (din + kper - 1) / kper),
                      dim3(256), 0, stream, n, segs, din, dout, NGPDE_ACT_IDENTITY, wt, nullptr, partial, nullptr, kper,
                      (size_t)n * dout);
   NGPDE_LAUNCH_CHECK("dense_mfma_fwd_kernel (split-K)");
   return NGPDE_OK;
-}
-int dense_fwd_split_count(int din, int nsplit) {   // partial slabs launch_dense_seg_fwd_splitk actually writes
-  const int kper = ((din + nsplit - 1) / nsplit + BK - 1) / BK * BK;
-  return (din + kper - 1) / kper;
 }
 
 // C [M][N] = A [M][K] x B [K][N] (both row-major) on the 128 x 128 tiles, the contraction split into nsplit ranges of whole 16-chunks:
@@ -1380,19 +1358,21 @@ int32_t launch_gemm128_split_nn(int M, int N, int K, int nsplit, const float *A,
   return NGPDE_OK;
 }
 
-int32_t launch_dense_seg_bwd_input(int64_t n, const SegGrad &segs, int din, int dout, const float *dz, const float *wt,
+int32_t launch_dense_seg_bwd_input(const DenseBwdInput &form, int64_t n, const SegGrad &segs, int din, int dout, const float *dz, const float *wt,
                                    hipStream_t stream) {
-  if (n == 0 || din == 0) return NGPDE_OK;
-  if (use_wide_tiles(n, din)) {
-    hipLaunchKernelGGL(dense_wide_bwd_input_kernel, dim3((unsigned)((n + BM2 - 1) / BM2), (din + BN - 1) / BN), dim3(256), 0,
-                       stream, n, segs, din, dout, dz, wt, dout, (float *)nullptr, (size_t)0);
-    NGPDE_LAUNCH_CHECK("dense_wide_bwd_input_kernel");
-    return NGPDE_OK;
+  switch (form.form) {
+    case DenseInputForm::Wide:
+      hipLaunchKernelGGL(dense_wide_bwd_input_kernel, dim3((unsigned)((n + BM2 - 1) / BM2), (din + BN - 1) / BN), dim3(256), 0,
+                         stream, n, segs, din, dout, dz, wt, dout, (float *)nullptr, (size_t)0);
+      NGPDE_LAUNCH_CHECK("dense_wide_bwd_input_kernel");
+      return NGPDE_OK;
+    case DenseInputForm::Mfma:
+      hipLaunchKernelGGL(dense_mfma_bwd_input_kernel, dim3((unsigned)((n + BM - 1) / BM), (din + BN - 1) / BN), dim3(256), 0,
+                         stream, n, segs, din, dout, dz, wt, dout, (float *)nullptr, (size_t)0);
+      NGPDE_LAUNCH_CHECK("dense_mfma_bwd_input_kernel");
+      return NGPDE_OK;
+    default: return NGPDE_OK;   // (None: no rows or no inputs)
   }
-  hipLaunchKernelGGL(dense_mfma_bwd_input_kernel, dim3((unsigned)((n + BM - 1) / BM), (din + BN - 1) / BN), dim3(256), 0,
-                     stream, n, segs, din, dout, dz, wt, dout, (float *)nullptr, (size_t)0);
-  NGPDE_LAUNCH_CHECK("dense_mfma_bwd_input_kernel");
-  return NGPDE_OK;
 }
 
 namespace {
@@ -1412,55 +1392,35 @@ __global__ void add_partials_kernel(int64_t count, int nparts, size_t stride, co
 }
 }  // namespace
 
-// splits of the input pullback over the output features (see dense_mfma_bwd_input_kernel): 1 = none
-int dense_bwd_input_splits(int64_t n, int din, int dout) {
-  const int64_t tiles = ((n + BM2 - 1) / BM2) * ((din + BN - 1) / BN);
-  if (tiles == 0 || tiles >= 256 || dout < 512) return 1;   // (ngpde_dense_workspace_bytes asks for n = 0 too)
-  // enough workgroups for a few rounds of the chip, each still with a dozen or more K steps (the partial slabs cost a pass too)
-  return (int)std::max<int64_t>(1, std::min<int64_t>((2048 + tiles - 1) / tiles, dout / 256));
-}
-size_t dense_bwd_input_split_bytes(int64_t n, int din, int dout) {
-  const int ns = dense_bwd_input_splits(n, din, dout);
-  return ns > 1 ? (size_t)(ns - 1) * (size_t)n * din * sizeof(float) : 0;
-}
-// single-block input pullback, split over the output features; `part` holds dense_bwd_input_split_bytes
-int32_t launch_dense_bwd_input_splitk(int64_t n, float *dx, int din, int dout, const float *dz, const float *wt, float *part,
-                                      hipStream_t stream) {
-  if (n == 0 || din == 0) return NGPDE_OK;
-  const int ns = dense_bwd_input_splits(n, din, dout);
-  const int oper = ((dout + ns - 1) / ns + BK2 - 1) / BK2 * BK2;
-  const int nz = (dout + oper - 1) / oper;
-  {   // 128 x 128 tiles (GNOConv's T = W2 (x) h: 4096 x 128 <= 8192)
-    if (!switch_on(Switch::DenseNoGemm128) && nz > 1 && din >= BG && din % 4 == 0 && dout % BKG == 0 && oper % BKG == 0 && n < (1 << 30) &&
-        ((reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(wt) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(part)) & 15) == 0) {
-      hipLaunchKernelGGL((dense_gemm128_split_kernel<false, true>), dim3((unsigned)((n + BG - 1) / BG), (din + BG - 1) / BG, nz), dim3(256), 0,
-                         stream, (int)n, din, dout, oper, dz, dout, wt, dout, dx, part, (size_t)n * din, din);
+int32_t launch_dense_bwd_input_splitk(const DenseBwdInput &form, int64_t n, float *dx, int din, int dout, const float *dz, const float *wt,
+                                      float *part, hipStream_t stream) {
+  switch (form.form) {
+    case DenseInputForm::Gemm128Split:
+      hipLaunchKernelGGL((dense_gemm128_split_kernel<false, true>), dim3((unsigned)((n + BG - 1) / BG), (din + BG - 1) / BG, form.nz), dim3(256), 0,
+                         stream, (int)n, din, dout, form.oper, dz, dout, wt, dout, dx, part, (size_t)n * din, din);
       NGPDE_LAUNCH_CHECK("dense_gemm128_split_kernel (input pullback)");
-      const int64_t count = n * din;
-      hipLaunchKernelGGL(add_partials_kernel, dim3((unsigned)std::min<int64_t>((count + 255) / 256, 4096)), dim3(256), 0, stream, count,
-                         nz - 1, (size_t)n * din, part, dx);
-      NGPDE_LAUNCH_CHECK("add_partials_kernel");
-      return NGPDE_OK;
+      break;
+    case DenseInputForm::WideSplit: {
+      SegGrad segs;
+      segs.n = 1; segs.ptr[0] = dx; segs.width[0] = din;
+      for (int i = 1; i <= 4; ++i) segs.offset[i] = din;
+      // the 128-row tile kernel: 16-byte loads of dz and W rows (the 64-row kernel reads dz in 64-byte pieces)
+      hipLaunchKernelGGL(dense_wide_bwd_input_kernel, dim3((unsigned)((n + BM2 - 1) / BM2), (din + BN - 1) / BN, form.nz), dim3(256), 0, stream,
+                         n, segs, din, dout, dz, wt, form.oper, part, (size_t)n * din);
+      NGPDE_LAUNCH_CHECK("dense_mfma_bwd_input_kernel (split)");
+      break;
     }
+    default: return NGPDE_OK;   // (None: no rows or no inputs)
   }
-  SegGrad segs;
-  segs.n = 1; segs.ptr[0] = dx; segs.width[0] = din;
-  for (int i = 1; i <= 4; ++i) segs.offset[i] = din;
-  // the 128-row tile kernel: 16-byte loads of dz and W rows (the 64-row kernel reads dz in 64-byte pieces)
-  hipLaunchKernelGGL(dense_wide_bwd_input_kernel, dim3((unsigned)((n + BM2 - 1) / BM2), (din + BN - 1) / BN, nz), dim3(256), 0, stream,
-                     n, segs, din, dout, dz, wt, oper, part, (size_t)n * din);
-  NGPDE_LAUNCH_CHECK("dense_mfma_bwd_input_kernel (split)");
-  if (nz > 1) {
+  if (form.add) {
     const int64_t count = n * din;
     hipLaunchKernelGGL(add_partials_kernel, dim3((unsigned)std::min<int64_t>((count + 255) / 256, 4096)), dim3(256), 0, stream, count,
-                       nz - 1, (size_t)n * din, part, dx);
+                       form.nz - 1, (size_t)n * din, part, dx);
     NGPDE_LAUNCH_CHECK("add_partials_kernel");
   }
   return NGPDE_OK;
 }
 
-// row chunks of the weight pullback: enough (tile x chunk) workgroups to cover the chip several times over (the chunk
-// loop is a dependent global-load chain, ~16 rows per trip), at least 64 rows per chunk, at most 1024 partial slabs
 int32_t launch_dense_weight_reduce(int nchunk, int din, int dout, const float *partial, float *dwt, float *db, hipStream_t stream) {
   const int total = (din + 1) * dout;
   hipLaunchKernelGGL(dense_weight_reduce_kernel, dim3((total + 63) / 64), dim3(256), 0, stream, nchunk, din, dout, partial, dwt, db);
@@ -1468,61 +1428,27 @@ int32_t launch_dense_weight_reduce(int nchunk, int din, int dout, const float *p
   return NGPDE_OK;
 }
 
-int dense_weight_chunks(int64_t n, int din, int dout) {
-  const int64_t tiles = (int64_t)std::max(1, (din + BM - 1) / BM) * std::max(1, (dout + BN - 1) / BN);
-  const int64_t want = (4096 + tiles - 1) / tiles;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(1024, want), (n + 63) / 64));
-}
-
-int32_t launch_dense_seg_bwd_weight(int64_t n, const SegTable &segs, int din, int dout, const float *dz, float *dwt,
+int32_t launch_dense_seg_bwd_weight(const DenseBwdWeight &form, int64_t n, const SegTable &segs, int din, int dout, const float *dz, float *dwt,
                                     float *db, float *partial, hipStream_t stream) {
-  if (dout == 0) return NGPDE_OK;
-  const int nchunk = dense_weight_chunks(n, din, dout);
-  const int64_t rpc = std::max<int64_t>(BK, (((n + nchunk - 1) / nchunk) + BK - 1) / BK * BK);
-  {   // 128 x 128 tiles for a wide layer without bias gradient (GNOConv's T): slabs in the layout dense_weight_reduce_kernel sums
-    if (!switch_on(Switch::DenseNoGemm128) && db == nullptr && nchunk > 1 && segs.n == 1 && segs.vec[0] && segs.row_div[0] == 1 && din >= BG && din % 4 == 0 &&
-        dout >= BG && dout % 4 == 0 && n % BKG == 0 && n < (1 << 30) &&
-        ((reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(partial)) & 15) == 0) {
+  switch (form.form) {
+    case DenseWeightForm::None: return NGPDE_OK;
+    case DenseWeightForm::Gemm128Split: {
       const size_t slab = (size_t)(din + 1) * dout;
-      hipLaunchKernelGGL((dense_gemm128_split_kernel<true, false>), dim3((din + BG - 1) / BG, (dout + BG - 1) / BG, nchunk), dim3(256), 0, stream,
-                         din, dout, (int)n, (int)rpc, segs.ptr[0], din, dz, dout, partial, partial + slab, slab, dout);
+      hipLaunchKernelGGL((dense_gemm128_split_kernel<true, false>), dim3((din + BG - 1) / BG, (dout + BG - 1) / BG, form.nchunk), dim3(256), 0, stream,
+                         din, dout, (int)n, (int)form.rpc, segs.ptr[0], din, dz, dout, partial, partial + slab, slab, dout);
       NGPDE_LAUNCH_CHECK("dense_gemm128_split_kernel (weight pullback)");
-      return launch_dense_weight_reduce(nchunk, din, dout, partial, dwt, db, stream);
+      break;
     }
+    case DenseWeightForm::Mfma:
+      hipLaunchKernelGGL(dense_mfma_bwd_weight_kernel, dim3(std::max(1, (din + BM - 1) / BM), (dout + BN - 1) / BN, form.nchunk), dim3(256), 0,
+                         stream, n, segs, din, dout, dz, form.rpc, partial);
+      NGPDE_LAUNCH_CHECK("dense_mfma_bwd_weight_kernel");
+      break;
   }
-  hipLaunchKernelGGL(dense_mfma_bwd_weight_kernel, dim3(std::max(1, (din + BM - 1) / BM), (dout + BN - 1) / BN, nchunk), dim3(256), 0,
-                     stream, n, segs, din, dout, dz, rpc, partial);
-  NGPDE_LAUNCH_CHECK("dense_mfma_bwd_weight_kernel");
-  const int total = (din + 1) * dout;
-  hipLaunchKernelGGL(dense_weight_reduce_kernel, dim3((total + 63) / 64), dim3(256), 0, stream, nchunk, din, dout, partial,
-                     dwt, db);
-  NGPDE_LAUNCH_CHECK("dense_weight_reduce_kernel");
-  return NGPDE_OK;
+  return launch_dense_weight_reduce(form.nchunk, din, dout, partial, dwt, db, stream);
 }
-
 
 // ---- launches of the two-layer streaming forwards ----------------------------------------------------------------------------------
-static int stream_grid(const void *kernel, size_t dyn_lds, int n_tiles) {
-  int dev = 0, cus = 0, per_cu = 0;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kStreamThreads, dyn_lds);
-  return std::min(n_tiles, std::max(cus, 1) * std::max(per_cu, 1));
-}
-// leading blocks of exactly 64 features that LDS-DMA can fetch (row_div 1, 16-byte aligned); the rest must be narrow
-static int stream_main_blocks(const SegTable &t, int din) {
-  int nm = 0;
-  while (nm < t.n && t.width[nm] == 64 && t.row_div[nm] == 1 && t.vec[nm]) ++nm;
-  return (nm >= 1 && din - 64 * nm <= kNarrow) ? nm : 0;
-}
-static bool stream2_enabled(int64_t n) {
-  return !switch_on(Switch::DenseNoStream2) && (n + BM2 - 1) / BM2 >= 512;
-}
-
-bool dense_pair_fwd_applicable(int64_t n, const SegTable &ta, int dina, int douta, const SegTable &tb, int dinb, int doutb) {
-  return stream2_enabled(n) && douta <= 64 && doutb <= 64 && stream_main_blocks(ta, dina) == 1 && stream_main_blocks(tb, dinb) == 1 &&
-         ta.ptr[0] == tb.ptr[0];
-}
 int32_t launch_dense_pair_fwd(int64_t n, const SegTable &ta, int dina, int douta, int acta, const float *wta, const float *ba, float *ya,
                               float *za, const SegTable &tb, int dinb, int doutb, int actb, const float *wtb, const float *bb, float *yb,
                               float *zb, hipStream_t stream) {
@@ -1532,7 +1458,7 @@ int32_t launch_dense_pair_fwd(int64_t n, const SegTable &ta, int dina, int douta
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dense_pair_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return fail(NGPDE_ERR_HIP, "dense_pair_fwd_kernel: LDS request of %zu bytes refused: %s", lds, hipGetErrorString(e));
   static int cap = 0;   // resident workgroups of this kernel on this device (one occupancy query per process)
-  if (!cap) cap = stream_grid(reinterpret_cast<const void *>(dense_pair_fwd_kernel), lds, 1 << 30);
+  if (!cap) cap = stream_grid(reinterpret_cast<const void *>(dense_pair_fwd_kernel), lds);
   const int grid = std::min(n_tiles, cap);
   NGPDE_STAMP_SET(a, kStampPair, 0);
   hipLaunchKernelGGL(dense_pair_fwd_kernel, dim3((unsigned)grid), dim3(kStreamThreads), lds, stream, n, n_tiles, ta.ptr[0], a, b);
@@ -1540,16 +1466,12 @@ int32_t launch_dense_pair_fwd(int64_t n, const SegTable &ta, int dina, int douta
   return NGPDE_OK;
 }
 
-bool dense_chain_fwd_applicable(int64_t n, const SegTable &t1, int din1, int dmid, int dout2) {
-  const int nm = stream_main_blocks(t1, din1);
-  return stream2_enabled(n) && dmid == 64 && dout2 <= 64 && (nm == 1 || nm == 2);
-}
-int32_t launch_dense_chain_fwd(int64_t n, const SegTable &t1, int din1, int act1, const float *wt1, const float *b1, float *a1, float *z1,
+int32_t launch_dense_chain_fwd(const DenseChainFwd &c, int64_t n, const SegTable &t1, int din1, int act1, const float *wt1, const float *b1, float *a1, float *z1,
                                int dout2, int act2, const float *wt2, const float *b2, float *y, float *z2, hipStream_t stream) {
   SegTable t2;
   t2.n = 1; t2.width[0] = 64; t2.offset[1] = t2.offset[2] = t2.offset[3] = t2.offset[4] = 64;
   StreamOut l1{t1, din1, 64, act1, wt1, b1, a1, z1}, l2{t2, 64, dout2, act2, wt2, b2, y, z2};
-  const int nm = stream_main_blocks(t1, din1);
+  const int nm = c.n_main;
   const int tr = 64;
   const int n_tiles = (int)((n + tr - 1) / tr);
   const size_t lds = ((size_t)2 * (tr * OS2 + (nm == 2 ? tr * 64 : 0)) + kNarrow * 64 + (size_t)tr * kNarrowAll + 128) * sizeof(float);
@@ -1557,7 +1479,7 @@ int32_t launch_dense_chain_fwd(int64_t n, const SegTable &t1, int din1, int act1
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     static int cap[3] = {0, 0, 0};
-    if (!cap[nm]) cap[nm] = stream_grid(reinterpret_cast<const void *>(kernel), lds, 1 << 30);
+    if (!cap[nm]) cap[nm] = stream_grid(reinterpret_cast<const void *>(kernel), lds);
     const int grid = std::min(n_tiles, cap[nm]);
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kStreamThreads), lds, stream, n, n_tiles, t1.ptr[0], nm == 2 ? t1.ptr[1] : nullptr,
                        l1, l2);

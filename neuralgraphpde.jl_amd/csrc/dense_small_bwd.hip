@@ -18,7 +18,6 @@
 #include "common.h"
 #include "device_utils.h"
 #include "stamps.h"
-#include "switches.h"
 
 namespace ngpde {
 
@@ -29,6 +28,7 @@ namespace {
 #define NGPDE_KEEP(x) asm volatile("" : "+v"(x))
 
 constexpr int kT = 256, kR = 64, kW = 64;
+static_assert(kR == kDenseRows64 && kW == kDenseCols64, "dense_forms.h decides in these tiles (dense_small_fwd_grid, dense_small_bwd_grid)");
 constexpr int kSZ = kW + 4;    // dz and W tiles: 16-byte rows, conflict-free row reads (16 rows x one 16-byte chunk)
 constexpr int kSX = kW + 16;   // X tile: read only transposed (rows 4 s + kq, 16 consecutive columns): stride 80 spreads kq over the banks
 
@@ -358,12 +358,7 @@ __global__ __launch_bounds__(kT) void dense_small_fwd_kernel(const SmallFwdK p) 
 
 }  // namespace
 
-// the forward of the same shapes in one contraction pass (0: not this form's shape)
-int dense_small_fwd_grid(int64_t n, int din, int dout) {
-  if (switch_on(Switch::DenseNoSmallFwd) || din < 17 || din > kW || dout < 1 || dout > kW || n < 1 || n > 65536) return 0;   // (din <= 16 is ONE step of the general kernel)
-  return (int)std::min<int64_t>((n + kR - 1) / kR, 1024);
-}
-
+// the forward of the same shapes in one contraction pass (grid: dense_small_fwd_grid)
 int32_t launch_dense_small_fwd(int64_t n, const SegTable &t, int din, int dout, int act, const float *wt, const float *bias, float *y,
                                float *save_z, int grid, hipStream_t stream) {
   SmallFwdK k{};
@@ -374,27 +369,13 @@ int32_t launch_dense_small_fwd(int64_t n, const SegTable &t, int din, int dout, 
   return NGPDE_OK;
 }
 
-// grid of the one-launch form, or 0 when the shape is not its own: widths up to 64, few enough rows that the composed path's
-// launches are latency-bound (beyond that its 16-byte / LDS-DMA loads win), and enough rows for the slabs to fit the [n][dout] dz
-// area of the composed path's workspace (which this form does not use otherwise)
-int dense_small_bwd_grid(int64_t n, int din, int dout) {
-  if (switch_on(Switch::DenseNoSmallBwd) || din < 1 || din > kW || dout < 1 || dout > kW || n < 1 || n > 65536) return 0;
-  const int64_t n_tiles = (n + kR - 1) / kR;
-  const int64_t grid = std::min<int64_t>(std::min<int64_t>(n_tiles, 1024), n / (din + 1));
-  return grid >= 1 ? (int)grid : 0;
-}
-
+// the pullback (grid: dense_small_bwd_grid; grads: seg_grads)
 int32_t launch_dense_small_bwd(int64_t n, const SegTable &t, int din, int dout, int act, const float *wt, const float *z, const float *dy,
-                               float *const *dseg, float *dwt, float *dbias, float *slabs, int grid, hipStream_t stream) {
+                               const SegGrad &grads, float *dwt, float *dbias, float *slabs, int grid, hipStream_t stream) {
   SmallBwdK k{};
   k.n = n; k.n_tiles = (int)((n + kR - 1) / kR); k.din = din; k.dout = dout; k.act = act;
   k.segs = t;
-  k.grads.n = t.n;
-  for (int b = 0; b < t.n; ++b) {
-    k.grads.ptr[b] = (dseg && t.row_div[b] == 1) ? dseg[b] : nullptr;   // per-graph blocks carry no gradient (@ignore_derivatives, :397, :418)
-    k.grads.width[b] = t.width[b];
-  }
-  for (int b = 0; b <= 4; ++b) k.grads.offset[b] = t.offset[b];
+  k.grads = grads;
   k.wt = wt; k.z = (act == NGPDE_ACT_IDENTITY) ? nullptr : z; k.dy = dy; k.partial = slabs;
   NGPDE_STAMP_SET(k, kStampSmallDense, 0);
   hipLaunchKernelGGL(dense_small_bwd_kernel, dim3(grid), dim3(kT), 0, stream, k);

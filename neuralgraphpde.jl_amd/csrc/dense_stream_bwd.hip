@@ -27,13 +27,13 @@
 #include "common.h"
 #include "device_utils.h"
 #include "stamps.h"
-#include "switches.h"
 
 namespace ngpde {
 
 namespace {
 
 constexpr int kBT = 256, kTR = 64, kD = 64, kPS = kD + 4, kMaxNarrow = 4;
+static_assert(kTR == kDenseRows64 && kD == kDenseCols64 && kMaxNarrow == kDenseNarrow, "dense_forms.h decides in these tiles (dense_stream_bwd_plan, dense_pair_bwd_plan)");
 
 struct DenseBwdK {
   int64_t n;
@@ -577,40 +577,17 @@ __global__ __launch_bounds__(kBT, 2) void dense_pair64_bwd_kernel(const DensePai
 
 }  // namespace
 
-// Applies when: 64 outputs, one or two blocks of exactly 64 features (row_div 1, 16-byte aligned), every other feature
-// narrow (<= 4 in total) and without a gradient request, enough rows for a resident wave of tiles, and the slabs fit the dz
-// area of the caller's workspace.  NGPDE_DENSE_NO_STREAM_BWD=1 keeps the composed path.
-int dense_stream_bwd_grid(int64_t n, const SegTable &t, int din, int dout, float *const *dseg) {
-  if (switch_on(Switch::DenseNoStreamBwd) || dout != kD || n < 32768 || n > (1 << 24)) return 0;   // (32-bit byte offsets)
-  int n_main = 0, n_narrow = 0;
-  for (int b = 0; b < t.n; ++b) {
-    const bool grad = dseg && dseg[b] && t.row_div[b] == 1;
-    if (t.width[b] == kD && t.row_div[b] == 1 && (reinterpret_cast<uintptr_t>(t.ptr[b]) & 15) == 0 &&
-        (!grad || (reinterpret_cast<uintptr_t>(dseg[b]) & 15) == 0)) {
-      ++n_main;
-    } else {
-      if (grad) return 0;
-      n_narrow += t.width[b];
-    }
-  }
-  if (n_main < 1 || n_main > 2 || n_narrow > kMaxNarrow) return 0;
-  const int n_tiles = (int)((n + kTR - 1) / kTR);
-  int grid = std::min(n_tiles, 256 * 2);
-  grid = (int)std::min<int64_t>(grid, n / (din + 1));   // slabs live in the [n][64] dz area of the workspace
-  return grid >= 256 ? grid : 0;
-}
-
-int32_t launch_dense_stream_bwd(int64_t n, const SegTable &t, int din, int act, const float *wt, const float *z, const float *dy,
-                                float *const *dseg, float *dwt, float *dbias, float *slabs, int grid, hipStream_t stream) {
+// form: dense_stream_bwd_plan's grid and its sorting of the blocks into 64-wide ones and narrow features; grads: seg_grads
+int32_t launch_dense_stream_bwd(const DenseStreamBwd &form, int64_t n, const SegTable &t, const SegGrad &grads, int din, int act, const float *wt,
+                                const float *z, const float *dy, float *dwt, float *dbias, float *slabs, hipStream_t stream) {
+  const int grid = form.grid;
   DenseBwdK k{};
   k.n = n; k.n_tiles = (int)((n + kTR - 1) / kTR); k.din = din; k.act = act;
   k.wt = wt; k.z = (act == NGPDE_ACT_IDENTITY) ? nullptr : z; k.dy = dy; k.partial = slabs;
   int n_main = 0;
   for (int b = 0; b < t.n; ++b) {
-    const bool grad = dseg && dseg[b] && t.row_div[b] == 1;
-    if (t.width[b] == kD && t.row_div[b] == 1 && (reinterpret_cast<uintptr_t>(t.ptr[b]) & 15) == 0 &&
-        (!grad || (reinterpret_cast<uintptr_t>(dseg[b]) & 15) == 0)) {
-      k.x[n_main] = t.ptr[b]; k.dx[n_main] = grad ? dseg[b] : nullptr; k.main_off[n_main] = t.offset[b];
+    if (form.main[b]) {
+      k.x[n_main] = t.ptr[b]; k.dx[n_main] = grads.ptr[b]; k.main_off[n_main] = t.offset[b];
       ++n_main;
     } else {
       for (int c = 0; c < t.width[b]; ++c) {
@@ -634,21 +611,11 @@ int32_t launch_dense_stream_bwd(int64_t n, const SegTable &t, int din, int act, 
   return launch_dense_weight_reduce(grid, din, kD, slabs, dwt, dbias, stream);
 }
 
-// ---- the pair pullback: both sides one 64-wide leading block at the SAME address + narrow blocks, 64 outputs, no activation
-static bool pair_side_ok(const SegTable &t, int din) {
-  if (t.n < 1 || t.width[0] != kD || t.row_div[0] != 1 || (reinterpret_cast<uintptr_t>(t.ptr[0]) & 15)) return false;
-  return din - kD <= kMaxNarrow;
-}
-int dense_pair_bwd_grid(int64_t n, const SegTable &ta, int dina, const SegTable &tb, int dinb) {
-  if (switch_on(Switch::DenseNoStreamBwd) || n < 32768 || n > (1 << 24)) return 0;
-  if (!pair_side_ok(ta, dina) || !pair_side_ok(tb, dinb) || ta.ptr[0] != tb.ptr[0]) return 0;
-  return std::min((int)((n + kTR - 1) / kTR), 256 * 2);
-}
-size_t dense_pair_bwd_workspace(int grid, int dina, int dinb) { return (size_t)grid * (dina + dinb + 2) * kD * sizeof(float) + 512; }
-
-int32_t launch_dense_pair_bwd(int64_t n, const SegTable &ta, int dina, const float *wta, const float *dya, float *dwta, float *dba,
-                              const SegTable &tb, int dinb, const float *wtb, const float *dyb, float *dwtb, float *dbb, float *dx,
-                              const float *dx_add, void *workspace, int grid, hipStream_t stream) {
+// ---- the pair pullback (form: dense_pair_bwd_plan)
+int32_t launch_dense_pair_bwd(const DensePairBwd &form, int64_t n, const SegTable &ta, int dina, const float *wta, const float *dya, float *dwta,
+                              float *dba, const SegTable &tb, int dinb, const float *wtb, const float *dyb, float *dwtb, float *dbb, float *dx,
+                              const float *dx_add, void *workspace, hipStream_t stream) {
+  const int grid = form.grid;
   DensePairBwdK k{};
   k.n = n; k.n_tiles = (int)((n + kTR - 1) / kTR); k.x = ta.ptr[0]; k.dx = dx; k.dx_add = dx_add;
   NGPDE_STAMP_SET(k, kStampPairBwd, 0);

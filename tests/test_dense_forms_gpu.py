@@ -1,36 +1,9 @@
 """The Dense family against float64 across every form and boundary.
 
-Every entry point picks its kernel(s) from the shape, the pointers' alignment and tile-count thresholds.  This file restates those
-choices (fwd_form, bwd_form, pair_fwd_fused, chain2_fused, pair_bwd_grid below), asserts for every case that it lands where it means
-to, and compares the outputs with float64.
-
-ngpde_dense_forward (csrc/dense_mfma.hip launch_dense_seg_fwd), in this order:
-  small    dense_small_fwd_kernel       17 <= din <= 64, 1 <= dout <= 64, 1 <= n <= 65 536 (dense_small_bwd.hip dense_small_fwd_grid)
-  gemm128  dense_gemm128_fwd_kernel     one block, 16-byte loadable (`vec`), row_div 1, din % 16 == 0, dout % 4 == 0, dout >= 128,
-                                        ceil(n / 128) * ceil(dout / 128) >= 512 tiles, weight, y and save_z 16-byte aligned
-  stream   dense_stream64_fwd_kernel    128-row tiles (ceil(n / 128) * ceil(dout / 64) >= 512), din_main == 64, dout <= 64 and every
-                                        block before din_main `vec` and inside it
-  wide     dense_wide_fwd_kernel        128-row tiles otherwise
-  general  dense_mfma_fwd_kernel        everything else
-  din_main: trailing blocks with at most 8 features behind them leave the K loop when their offset is a multiple of 32.
-  vec (api_mp.hip make_segs): offset % 4 == 0, width % 4 == 0 and a 16-byte aligned base.
-ngpde_dense_multi_forward: dense_mfma_multi_fwd_kernel over the problems with rows (none: no launch).
-ngpde_dense_pair_forward: dense_pair_fwd_kernel when ceil(n / 128) >= 512 (NGPDE_DENSE_NO_STREAM2 unset), both douts <= 64 and
-  both sides are ONE leading 64-wide `vec` row_div-1 block at the same address plus <= 4 narrow features; two forwards otherwise.
-ngpde_dense_chain2_forward: dense_chain_fwd_kernel<1 / 2> under the same tile rule when dmid == 64, dout <= 64 and the table has one
-  or two leading 64-wide blocks plus <= 4 narrow features; two forwards otherwise, and then a1 is required.
-ngpde_dense_backward (api_mp.hip), in this order:
-  stream   dense_stream64_bwd_kernel<1 / 2> + reduce   dout == 64, 32 768 <= n <= 2^24, one or two 64-wide row_div-1 aligned blocks
-                                        (aligned gradient too), <= 4 other features and none of them with a gradient, grid =
-                                        min(ceil(n / 64), 512, n / (din + 1)) >= 256 (dense_stream_bwd_grid; NGPDE_DENSE_NO_STREAM_BWD)
-  small    dense_small_bwd_kernel + reduce      din, dout <= 64, n <= 65 536, grid = min(ceil(n / 64), 1024, n / (din + 1)) >= 1
-  composed dense_dz_kernel (act != identity); dense_gemm128_split_kernel<true,false> (no dbias, > 1 chunk, one vec block, din and
-           dout >= 128 and % 4, n % 16 == 0, dz and slabs aligned) or dense_mfma_bwd_weight_kernel; dense_weight_reduce_kernel; then
-           for the input pullback: one block and dense_bwd_input_splits > 1 -> dense_gemm128_split_kernel<false,true> (din >= 128,
-           din % 4, dout % 16, aligned) or dense_wide_bwd_input_kernel split over z, + add_partials_kernel when split;
-           otherwise dense_wide_bwd_input_kernel at 128-row tiles, dense_mfma_bwd_input_kernel below.
-ngpde_dense_pair_backward: dense_pair64_bwd_kernel + two reduces when dout == 64, 32 768 <= n <= 2^24 and both sides are one aligned
-  64-wide leading block at the same address plus <= 4 features (dense_pair_bwd_grid); ERR_UNSUPPORTED otherwise.
+Every entry point picks its kernel(s) from the shape, the pointers' alignment and tile-count thresholds.  tests/dense_forms_spec.py
+restates those choices (fwd_form, bwd_form, pair_fwd_fused, chain2_fused, pair_bwd_grid; its docstring describes the dispatch, and
+tests/test_dense_forms_host.py ties it to the library's csrc/dense_forms.h); this file asserts for every case that it lands where
+it means to, and compares the outputs with float64.
 
 NGPDE_DENSE_NARROW, _NO_GEMM128, _NO_STREAM, _NO_SMALL_FWD and _NO_SMALL_BWD are read once per process (any value): the restatement
 reads them at import and follows them; under one of them (the suite's switch matrix) the cases' fixed expectations are not asserted,
@@ -49,12 +22,13 @@ forward 1e-4 * max|ref| + 1e-5, gradients 3e-4 relative (5e-4 past 10^5 rows of 
 """
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from dense_forms_spec import (ONCE, PER_CALL, align256, bwd_form, cdiv, chain2_fused, din_main, fwd_form, pair_bwd_grid, pair_bwd_workspace,
+                              pair_fwd_fused, small_bwd_grid, stream_bwd_grid, stream_main_blocks, table, weight_chunks, workspace_bytes)
 from ngpde_amd import _lib
 from oracle import ngpde_oracle as O
 from test_edge_mlp_forms_gpu import ACTS
@@ -63,10 +37,7 @@ from test_mp_gpu import close
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 ALL_ACTS = ("identity", "relu", "tanh", "sigmoid", "swish", "gelu", "leakyrelu", "elu", "softplus")
-ONCE = {k: os.environ.get(k) is not None for k in ("NGPDE_DENSE_NARROW", "NGPDE_DENSE_NO_GEMM128", "NGPDE_DENSE_NO_STREAM",
-                                                    "NGPDE_DENSE_NO_SMALL_FWD", "NGPDE_DENSE_NO_SMALL_BWD")}
 SWITCHED = any(ONCE.values())
-PER_CALL = ("NGPDE_DENSE_NO_STREAM2", "NGPDE_DENSE_NO_STREAM_BWD")
 GRAD = dict(rtol=3e-4, atol=1e-5)
 GUARD = 64                                     # guard words on each side of every device buffer
 CHUNK = 1 << 17                                # rows per chunk of the float64 reference
@@ -76,196 +47,6 @@ CHUNK = 1 << 17                                # rows per chunk of the float64 r
 def _per_call_switches(monkeypatch):
     for v in PER_CALL:
         monkeypatch.delenv(v, raising=False)
-
-
-def env_on(name):
-    v = os.environ.get(name)
-    return bool(v) and v[0] == "1"
-
-
-def cdiv(a, b):
-    return -(-a // b)
-
-
-def align256(b):
-    return (b + 255) & ~255
-
-
-# ---- the restatement of the form choice ---------------------------------------------------------------------------------------------
-
-class Seg:
-    def __init__(self, ptr, w, rd, off):
-        self.ptr, self.w, self.rd, self.off = ptr or 0, w, max(rd, 1), off
-        self.vec = off % 4 == 0 and w % 4 == 0 and self.ptr % 16 == 0      # make_segs
-
-
-def table(ptrs, widths, rds):
-    segs, off = [], 0
-    for p, w, rd in zip(ptrs, widths, rds):
-        segs.append(Seg(p, w, rd, off))
-        off += w
-    return segs
-
-
-def din_of(T):
-    return sum(s.w for s in T)
-
-
-def aligned(*ptrs):
-    return all((p or 0) % 16 == 0 for p in ptrs)
-
-
-def small_fwd_grid(n, din, dout):
-    if ONCE["NGPDE_DENSE_NO_SMALL_FWD"] or not (17 <= din <= 64 and 1 <= dout <= 64 and 1 <= n <= 65536):
-        return 0
-    return min(cdiv(n, 64), 1024)
-
-
-def small_bwd_grid(n, din, dout):
-    if ONCE["NGPDE_DENSE_NO_SMALL_BWD"] or not (1 <= din <= 64 and 1 <= dout <= 64 and 1 <= n <= 65536):
-        return 0
-    g = min(cdiv(n, 64), 1024, n // (din + 1))
-    return g if g >= 1 else 0
-
-
-def wide_tiles(n, cols):
-    return not ONCE["NGPDE_DENSE_NARROW"] and cdiv(n, 128) * cdiv(cols, 64) >= 512
-
-
-def din_main(T):
-    din, dm = din_of(T), din_of(T)
-    for s in reversed(T[1:]):
-        if din - s.off > 8:
-            break
-        if s.off % 32 == 0:
-            dm = s.off
-    return dm
-
-
-def fwd_form(n, T, dout, wt, y, z):
-    """the kernel launch_dense_seg_fwd picks (None: no launch)"""
-    din = din_of(T)
-    if n == 0:
-        return None
-    if small_fwd_grid(n, din, dout):
-        return "dense_small_fwd_kernel"
-    if (not ONCE["NGPDE_DENSE_NO_GEMM128"] and len(T) == 1 and T[0].vec and T[0].rd == 1 and din % 16 == 0 and dout % 4 == 0
-            and dout >= 128 and cdiv(n, 128) * cdiv(dout, 128) >= 512 and aligned(wt, y, z)):
-        return "dense_gemm128_fwd_kernel"
-    if wide_tiles(n, dout):
-        dm = din_main(T)
-        ok = not ONCE["NGPDE_DENSE_NO_STREAM"] and dm == 64 and dout <= 64
-        ok = ok and all(s.vec and s.off + s.w <= dm for s in T if s.off < dm)
-        return "dense_stream64_fwd_kernel" if ok else "dense_wide_fwd_kernel"
-    return "dense_mfma_fwd_kernel"
-
-
-def stream2(n):
-    return not env_on("NGPDE_DENSE_NO_STREAM2") and cdiv(n, 128) >= 512
-
-
-def stream_main_blocks(T):
-    nm = 0
-    while nm < len(T) and T[nm].w == 64 and T[nm].rd == 1 and T[nm].vec:
-        nm += 1
-    return nm if nm >= 1 and din_of(T) - 64 * nm <= 4 else 0
-
-
-def pair_fwd_fused(n, Ta, douta, Tb, doutb):
-    return (stream2(n) and douta <= 64 and doutb <= 64 and stream_main_blocks(Ta) == 1 and stream_main_blocks(Tb) == 1
-            and Ta[0].ptr == Tb[0].ptr)
-
-
-def chain2_fused(n, T, dmid, dout):
-    return 0 < n < 2 ** 31 and stream2(n) and dmid == 64 and dout <= 64 and stream_main_blocks(T) in (1, 2)
-
-
-def stream_bwd_grid(n, T, dout, dseg):
-    if env_on("NGPDE_DENSE_NO_STREAM_BWD") or dout != 64 or n < 32768 or n > 2 ** 24:
-        return 0, 0
-    n_main = n_narrow = 0
-    for i, s in enumerate(T):
-        grad = bool(dseg and dseg[i]) and s.rd == 1
-        if s.w == 64 and s.rd == 1 and s.ptr % 16 == 0 and (not grad or dseg[i] % 16 == 0):
-            n_main += 1
-        elif grad:
-            return 0, 0
-        else:
-            n_narrow += s.w
-    if not 1 <= n_main <= 2 or n_narrow > 4:
-        return 0, 0
-    g = min(cdiv(n, 64), 512, n // (din_of(T) + 1))
-    return (g, n_main) if g >= 256 else (0, 0)
-
-
-def weight_chunks(n, din, dout):
-    tiles = max(1, cdiv(din, 64)) * max(1, cdiv(dout, 64))
-    return max(1, min(1024, cdiv(4096, tiles), cdiv(n, 64)))
-
-
-def input_splits(n, din, dout):
-    tiles = cdiv(n, 128) * cdiv(din, 64)
-    if tiles == 0 or tiles >= 256 or dout < 512:
-        return 1
-    return max(1, min(cdiv(2048, tiles), dout // 256))
-
-
-def workspace_bytes(n, din, dout):
-    ns = input_splits(n, din, dout)
-    split = (ns - 1) * n * din * 4 if ns > 1 else 0
-    return align256(max(n, 1) * dout * 4) + align256(weight_chunks(n, din, dout) * (din + 1) * dout * 4) + align256(split) + 256
-
-
-def bwd_form(n, T, dout, act, wt, dy, dseg, has_bias, ws):
-    """the kernels ngpde_dense_backward launches, in order (() for n == 0: two fills)"""
-    din = din_of(T)
-    if n == 0:
-        return ()
-    g, nm = stream_bwd_grid(n, T, dout, dseg)
-    if g:
-        return (f"dense_stream64_bwd_kernel<{nm}>", "dense_weight_reduce_kernel")
-    if small_bwd_grid(n, din, dout):
-        return ("dense_small_bwd_kernel", "dense_weight_reduce_kernel")
-    ks = []
-    dz = dy if act == "identity" else ws
-    if act != "identity":
-        ks.append("dense_dz_kernel")
-    partial = ws + align256(n * dout * 4)
-    nchunk = weight_chunks(n, din, dout)
-    if (not ONCE["NGPDE_DENSE_NO_GEMM128"] and not has_bias and nchunk > 1 and len(T) == 1 and T[0].vec and T[0].rd == 1
-            and din >= 128 and din % 4 == 0 and dout >= 128 and dout % 4 == 0 and n % 16 == 0 and n < 2 ** 30 and aligned(dz, partial)):
-        ks.append("dense_gemm128_split_kernel<true,false>")
-    else:
-        ks.append("dense_mfma_bwd_weight_kernel")
-    ks.append("dense_weight_reduce_kernel")
-    grads = [bool(dseg and dseg[i]) and s.rd == 1 for i, s in enumerate(T)]
-    if any(grads) and len(T) == 1 and input_splits(n, din, dout) > 1:
-        ns = input_splits(n, din, dout)
-        oper = cdiv(cdiv(dout, ns), 32) * 32
-        nz = cdiv(dout, oper)
-        part = partial + align256(nchunk * (din + 1) * dout * 4)
-        if (not ONCE["NGPDE_DENSE_NO_GEMM128"] and nz > 1 and din >= 128 and din % 4 == 0 and dout % 16 == 0 and oper % 16 == 0
-                and n < 2 ** 30 and aligned(dz, wt, dseg[0], part)):
-            ks += ["dense_gemm128_split_kernel<false,true>", "add_partials_kernel"]
-        else:
-            ks += ["dense_wide_bwd_input_kernel"] + (["add_partials_kernel"] if nz > 1 else [])
-    elif any(grads):
-        ks.append("dense_wide_bwd_input_kernel" if wide_tiles(n, din) else "dense_mfma_bwd_input_kernel")
-    return tuple(ks)
-
-
-def pair_bwd_grid(n, Ta, Tb, dout):
-    def side_ok(T):
-        return len(T) >= 1 and T[0].w == 64 and T[0].rd == 1 and T[0].ptr % 16 == 0 and din_of(T) - 64 <= 4
-    if dout != 64 or env_on("NGPDE_DENSE_NO_STREAM_BWD") or n < 32768 or n > 2 ** 24:
-        return 0
-    if not side_ok(Ta) or not side_ok(Tb) or Ta[0].ptr != Tb[0].ptr:
-        return 0
-    return min(cdiv(n, 64), 512)
-
-
-def pair_bwd_workspace(grid, dina, dinb):
-    return grid * (dina + dinb + 2) * 64 * 4 + 512 if grid else 0
 
 
 def assert_form(form, expected, what=""):
