@@ -116,9 +116,16 @@ int32_t ngpde_graph_info(const ngpde_graph_t *g, int64_t *n_nodes, int64_t *n_ed
  * d2 <= r*r (float).  ngpde_radius_graph with s == t == NULL only counts; otherwise `capacity` entries are available and
  * *n_edges (host) receives the number written.  k-NN writes exactly n*k entries; coincident points are ordered by index
  * (the reference keeps a point's own entry only while it is among the k+1 nearest).  Both synchronise `stream`.
+ * The float rule holds at every magnitude: a call with finite coordinates and a valid r or k returns the brute-force list
+ * of that rule or is refused by name.  Where r*r is inf (r = inf, or a finite r above 1.8e19) every pair of a graph is
+ * connected; where r*r and the squares round to 0 or to denormals (below ~1e-19) d2 <= r*r connects pairs further apart
+ * than r, all of them once both sides are 0; k-NN orders distances that are all 0 or all inf by index.  Points whose
+ * span max - min is not finite in some coordinate (e.g. -3e38 .. 3e38) are refused with NGPDE_ERR_INVALID_ARGUMENT, like a
+ * non-finite coordinate, by all three entries.
  * ngpde_spatial_order: a node permutation (device int32[n]) along a space-filling curve through the points -- Hilbert in
  * 2-D, Morton in 3-D, the coordinate in 1-D, graph by graph -- usable as `order` of ngpde_graph_create_device, so that a
- * structure never seen before gets its locality schedule without a host traversal.
+ * structure never seen before gets its locality schedule without a host traversal.  A coordinate whose extent is below
+ * 2^-69 (1.7e-21) does not take part in the curve: it quantises as extent 0.
  * ---------------------------------------------------------------------------------------------- */
 #define NGPDE_KNN_MAX_K 128
 int32_t ngpde_radius_graph(int64_t n, int32_t dim, const float *points, float r, const int32_t *graph_id, int32_t n_graphs,

@@ -10,9 +10,19 @@
 //   dir = :in (default): neighbours are SOURCES, i the target; the list is ordered by i, neighbours ascending by index
 //   (radius) or by (d2, index) (k-NN).  The reference's tree searches return an implementation-defined order of the
 //   same edge set.
+//   The float rule holds at every magnitude: any call with finite coordinates and a valid r or k returns the brute-force
+//   list bit for bit or is refused by name before the grid is sized.
+//     r*r = inf (r = inf, or a finite r above 1.8e19): d2 <= inf accepts every pair of a graph; the grid is one cell.
+//     squares that underflow (coordinates or r below ~1e-19): df*df and r*r round to multiples of 2^-149, d2 <= r*r then
+//       accepts pairs further apart than r (all of them where both sides round to 0); the cell edge never goes below
+//       kMinCell = 2^-69, which covers every such pair (derivation above kMinCell in neighbor_grid.h).
+//     a coordinate whose span hi - lo is not finite (e.g. -3e38 .. 3e38): refused, NGPDE_ERR_INVALID_ARGUMENT, like a
+//       non-finite coordinate; so is the space-filling-curve order.  That order treats an extent below kMinCell as 0.
 // Method: uniform cell grid over the bounding box (cell >= 1.01 r, so the 3^dim block around a point's cell holds its
 // neighbours), points sorted by (graph, cell) with a stable radix sort, one thread per point walking contiguous cell
 // ranges; counts -> scan -> fill -> per-row sort.  k-NN walks rings of cells until the k-th distance is proven.
+// The grid's sizing, cell_of and the curve quantisation are host code in neighbor_grid.h, checked on the host by
+// tests/host/neighbor_grid_check.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -22,17 +32,10 @@
 
 #include "common.h"
 #include "device_scratch.h"
+#include "neighbor_grid.h"
 
 namespace ngpde {
 namespace {
-
-struct Grid {
-  float lo[3];
-  float inv;        // 1 / cell edge
-  float cell;       // cell edge
-  int nc[3];        // cells per dimension
-  int cells;        // per graph
-};
 
 __device__ __forceinline__ unsigned ordered_bits(float v) {
   const unsigned u = __float_as_uint(v);
@@ -72,19 +75,6 @@ __global__ void bbox_kernel(int64_t n, int dim, const float *__restrict__ pts, c
     }
   }
   if (bad) atomicOr(bad_id, 1);
-}
-
-template <int DIM>
-__device__ __forceinline__ void cell_of(const Grid &g, const float *p, int *c) {
-#pragma unroll
-  for (int d = 0; d < DIM; ++d) c[d] = min(g.nc[d] - 1, max(0, (int)((p[d] - g.lo[d]) * g.inv)));
-}
-template <int DIM>
-__device__ __forceinline__ int linear_cell(const Grid &g, const int *c) {
-  int l = c[0];
-#pragma unroll
-  for (int d = 1; d < DIM; ++d) l = l * g.nc[d] + c[d];
-  return l;
 }
 
 template <int DIM>
@@ -257,40 +247,56 @@ __global__ void knn_kernel(int64_t n, Grid g, int k, int self_loops, int out_bas
         for (int q = start[base + x], e = start[base + x + 1]; q < e; ++q) offer(q);
       }
     } else if constexpr (DIM == 2) {
-      for (int dx = -ring; dx <= ring; ++dx) {
-        const int x = c[0] + dx;
-        if (x < 0 || x >= g.nc[0]) continue;
-        const int step = (abs(dx) == ring || ring == 0) ? 1 : 2 * ring;
-        for (int dy = -ring; dy <= ring; dy += step) {
-          const int y = c[1] + dy;
-          if (y < 0 || y >= g.nc[1]) continue;
-          const int cell = base + x * g.nc[1] + y;
-          for (int q = start[cell], e = start[cell + 1]; q < e; ++q) offer(q);
-        }
+      // the two end columns x = c0 -+ ring in full, then the two end cells of every column between them; a column or a row
+      // outside the grid costs nothing, so a walk along a thin grid is linear in the rings, not quadratic
+      auto span = [&](int x, int ya, int yb) {   // cells (x, ya..yb) clipped to the grid: one range of sorted positions
+        ya = max(ya, 0);
+        yb = min(yb, g.nc[1] - 1);
+        if (x < 0 || x >= g.nc[0] || ya > yb) return;
+        const int row = base + x * g.nc[1];
+        for (int q = start[row + ya], e = start[row + yb + 1]; q < e; ++q) offer(q);
+      };
+      span(c[0] - ring, c[1] - ring, c[1] + ring);
+      if (ring > 0) {
+        span(c[0] + ring, c[1] - ring, c[1] + ring);
+        const bool y_lo = c[1] - ring >= 0, y_hi = c[1] + ring < g.nc[1];
+        if (y_lo || y_hi)
+          for (int x = max(c[0] - ring + 1, 0); x <= min(c[0] + ring - 1, g.nc[0] - 1); ++x) {
+            if (y_lo) span(x, c[1] - ring, c[1] - ring);
+            if (y_hi) span(x, c[1] + ring, c[1] + ring);
+          }
       }
     } else {
-      for (int dx = -ring; dx <= ring; ++dx) {
-        const int x = c[0] + dx;
-        if (x < 0 || x >= g.nc[0]) continue;
-        for (int dy = -ring; dy <= ring; ++dy) {
-          const int y = c[1] + dy;
-          if (y < 0 || y >= g.nc[1]) continue;
-          const bool shell = abs(dx) == ring || abs(dy) == ring;
-          const int step = (shell || ring == 0) ? 1 : 2 * ring;
-          for (int dz = -ring; dz <= ring; dz += step) {
-            const int z = c[2] + dz;
-            if (z < 0 || z >= g.nc[2]) continue;
-            const int cell = base + (x * g.nc[1] + y) * g.nc[2] + z;
-            for (int q = start[cell], e = start[cell + 1]; q < e; ++q) offer(q);
-          }
+      // the shell by faces: |dx| = ring; |dx| < ring and |dy| = ring; |dx|, |dy| < ring and |dz| = ring.  Only faces and
+      // cells inside the grid are looped over.
+      auto span = [&](int x, int y, int za, int zb) {   // cells (x, y, za..zb) clipped to the grid
+        za = max(za, 0);
+        zb = min(zb, g.nc[2] - 1);
+        if (x < 0 || x >= g.nc[0] || y < 0 || y >= g.nc[1] || za > zb) return;
+        const int row = base + (x * g.nc[1] + y) * g.nc[2];
+        for (int q = start[row + za], e = start[row + zb + 1]; q < e; ++q) offer(q);
+      };
+      if (c[0] - ring >= 0 || c[0] + ring < g.nc[0])
+        for (int y = max(c[1] - ring, 0); y <= min(c[1] + ring, g.nc[1] - 1); ++y) {
+          span(c[0] - ring, y, c[2] - ring, c[2] + ring);
+          if (ring > 0) span(c[0] + ring, y, c[2] - ring, c[2] + ring);
+        }
+      if (ring > 0) {
+        const int xa = max(c[0] - ring + 1, 0), xb = min(c[0] + ring - 1, g.nc[0] - 1);
+        const int ya = max(c[1] - ring + 1, 0), yb = min(c[1] + ring - 1, g.nc[1] - 1);
+        for (int side = -1; side <= 1; side += 2) {
+          const int y = c[1] + side * ring;
+          if (y >= 0 && y < g.nc[1])
+            for (int x = xa; x <= xb; ++x) span(x, y, c[2] - ring, c[2] + ring);
+          const int z = c[2] + side * ring;
+          if (z >= 0 && z < g.nc[2])
+            for (int x = xa; x <= xb; ++x)
+              for (int yy = ya; yy <= yb; ++yy) span(x, yy, z, z);
         }
       }
     }
     // every unvisited point is at least ring * cell away (the point lies inside its home cell)
-    if (have == k) {
-      const float reach = ((float)ring - 0.02f) * g.cell;
-      if (ring > 0 && ld[(k - 1) * kKnnThreads] < reach * reach) break;
-    }
+    if (have == k && ring > 0 && ld[(k - 1) * kKnnThreads] < ring_reach2(g, ring)) break;
   }
   if (have < k) atomicOr(short_rows, 1);
   int32_t *nb = dir_out ? t_out : s_out, *me = dir_out ? s_out : t_out;
@@ -301,12 +307,6 @@ __global__ void knn_kernel(int64_t n, Grid g, int k, int self_loops, int out_bas
 }
 
 // ---- space-filling-curve keys ---------------------------------------------------------------------------------------
-struct Quant {
-  float lo[3];
-  float scale[3];
-  int bits;
-};
-
 __device__ __forceinline__ unsigned hilbert2(unsigned x, unsigned y, int bits) {   // position along the Hilbert curve
   unsigned d = 0;
   const unsigned side = 1u << bits;
@@ -377,42 +377,10 @@ int32_t bounding_box(int64_t n, int dim, const float *pts, const int32_t *gid, i
     NGPDE_REQUIRE(std::isfinite(lo[d]) && std::isfinite(hi[d]), NGPDE_ERR_INVALID_ARGUMENT,
                   "points hold a non-finite coordinate");
   }
+  NGPDE_REQUIRE(span_is_finite(dim, lo, hi), NGPDE_ERR_INVALID_ARGUMENT,
+                "points span more than the largest finite float in a coordinate");
   return NGPDE_OK;
 }
-
-// cell edge >= want, at most ~budget cells in total over all graphs, at most kMaxCellsPerDim per dimension: a cell
-// coordinate (p - lo) * inv then carries an absolute rounding error <= 8192 * 2^-23 = 1e-3 cells, inside the 1 % by which
-// the cell edge exceeds the radius (and inside the margin of the k-NN ring bound)
-constexpr int kMaxCellsPerDim = 8192;
-Grid make_grid(int dim, const float *lo, const float *hi, float want, int64_t budget, int n_graphs) {
-  Grid g{};
-  float cell = want;
-  float ext_max = 0.f;
-  for (int d = 0; d < dim; ++d) ext_max = std::max(ext_max, hi[d] - lo[d]);
-  if (!std::isfinite(cell)) cell = std::max(ext_max, 1.f) * 2.f;              // everything in one cell
-  if (!(cell > 0.f)) cell = ext_max > 0.f ? ext_max / (float)kMaxCellsPerDim : 1.f;
-  cell = std::max(cell, ext_max / (float)kMaxCellsPerDim);
-  for (;;) {
-    int64_t cells = 1;
-    for (int d = 0; d < 3; ++d) {
-      g.nc[d] = 1;
-      if (d < dim) g.nc[d] = (int)std::min<double>((double)kMaxCellsPerDim, std::floor((double)(hi[d] - lo[d]) / cell) + 1.0);
-      cells *= g.nc[d];
-    }
-    if (cells * n_graphs <= budget || cells == 1) {
-      g.cells = (int)cells;
-      break;
-    }
-    cell *= 1.26f;
-  }
-  for (int d = 0; d < 3; ++d) g.lo[d] = lo[d];
-  g.cell = cell;
-  g.inv = 1.0f / cell;
-  return g;
-}
-
-// total cells over all graphs: ~4 per point, and (graph, cell) keys must fit 32 bits
-inline int64_t cell_budget(int64_t n) { return std::min<int64_t>(std::max<int64_t>(4 * n, 1 << 16), (int64_t)1 << 30); }
 
 struct Sorted {
   unsigned *key = nullptr;    // sorted (graph, cell) keys
@@ -453,7 +421,7 @@ int32_t radius_graph_impl(int64_t n, const float *pts, float r, const int32_t *g
   float lo[3], hi[3];
   int32_t st;
   if ((st = bounding_box(n, DIM, pts, gid, id_base, n_graphs, stream, sc, lo, hi))) return st;
-  const Grid g = make_grid(DIM, lo, hi, r * 1.01f, cell_budget(n), n_graphs);
+  const Grid g = make_grid(DIM, lo, hi, radius_want(r), cell_budget(n), n_graphs);
   Sorted so;
   if ((st = sort_into_cells<DIM>(n, g, n_graphs, pts, gid, id_base, stream, sc, so))) return st;
   int32_t *deg = nullptr, *rowptr = nullptr;
@@ -500,11 +468,7 @@ int32_t knn_graph_impl(int64_t n, const float *pts, int k, const int32_t *gid, i
   float lo[3], hi[3];
   int32_t st;
   if ((st = bounding_box(n, DIM, pts, gid, id_base, n_graphs, stream, sc, lo, hi))) return st;
-  // about k/2 points per cell on average: the first ring usually settles a point
-  double vol = 1.0;
-  for (int d = 0; d < DIM; ++d) vol *= std::max((double)hi[d] - (double)lo[d], 1e-30);
-  const double per_graph = std::max(1.0, (double)n / n_graphs);
-  const float want = (float)std::pow(vol * std::max(1.0, 0.5 * k) / per_graph, 1.0 / DIM);
+  const float want = knn_want(DIM, lo, hi, n, n_graphs, k);
   const Grid g = make_grid(DIM, lo, hi, want, cell_budget(n), n_graphs);
   Sorted so;
   if ((st = sort_into_cells<DIM>(n, g, n_graphs, pts, gid, id_base, stream, sc, so))) return st;
@@ -530,13 +494,7 @@ int32_t spatial_order_impl(int64_t n, const float *pts, const int32_t *gid, int 
   float lo[3], hi[3];
   int32_t st;
   if ((st = bounding_box(n, DIM, pts, gid, id_base, n_graphs, stream, sc, lo, hi))) return st;
-  Quant qz{};
-  qz.bits = DIM == 1 ? 30 : (DIM == 2 ? 16 : 10);
-  for (int d = 0; d < DIM; ++d) {
-    const float ext = hi[d] - lo[d];
-    qz.lo[d] = lo[d];
-    qz.scale[d] = ext > 0.f ? (float)(1u << qz.bits) / ext : 0.f;
-  }
+  const Quant qz = make_quant(DIM, lo, hi);
   unsigned long long *key = nullptr, *key_sorted = nullptr;
   int32_t *iota = nullptr;
   if ((st = sc.get(&key, (size_t)n)) || (st = sc.get(&key_sorted, (size_t)n)) || (st = sc.get(&iota, (size_t)n))) return st;

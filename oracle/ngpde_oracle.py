@@ -963,6 +963,7 @@ def knn_graph(points, k, graph_indicator=None, self_loops=False, dir="in", chunk
     me, nb = [], []
     for a in range(0, n, chunk):
         d2 = _pair_d2_f32(P[a:a + chunk], P).astype(np.float64)
+        d2[np.isinf(d2)] = 1e300               # a float32 square that overflowed is still a candidate (ties by index); inf marks "not one"
         if gi is not None:
             d2[gi[a:a + chunk, None] != gi[None, :]] = np.inf
         if not self_loops:
@@ -1008,7 +1009,8 @@ def _spread3(v):
 
 def spatial_order(points, graph_indicator=None, id_base=0):
     """node permutation along a space-filling curve (Hilbert 2-D, Morton 3-D, the coordinate 1-D), graph by graph;
-    coordinates quantised in float32 exactly as the device does; ties by index (stable sort)."""
+    coordinates quantised in float32 exactly as the device does; ties by index (stable sort).  An extent below 2^-69 (the
+    neighbour grid's smallest cell) quantises as extent 0: 2^bits / ext would leave the float range."""
     P = _points_rows(points)
     n, dim = P.shape
     if n == 0:
@@ -1016,8 +1018,8 @@ def spatial_order(points, graph_indicator=None, id_base=0):
     bits = {1: 30, 2: 16, 3: 10}[dim]
     lo = P.min(axis=0)
     ext = (P.max(axis=0) - lo).astype(np.float32)
-    with np.errstate(divide="ignore"):
-        scale = np.where(ext > 0, np.float32(1 << bits) / ext, np.float32(0)).astype(np.float32)
+    with np.errstate(divide="ignore", over="ignore"):
+        scale = np.where(ext >= np.float32(2.0 ** -69), np.float32(1 << bits) / ext, np.float32(0)).astype(np.float32)
     q = ((P - lo).astype(np.float32) * scale).astype(np.float32)
     q = np.clip(q.astype(np.int64), 0, (1 << bits) - 1)
     if dim == 1:
