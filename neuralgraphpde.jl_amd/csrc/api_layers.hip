@@ -219,24 +219,12 @@ int32_t make_plan(const ngpde_graph *g, const ngpde_edge_layer_t &L, bool traini
   const size_t N = (size_t)p.N, E = (size_t)p.E;
 
   // ---- message path: one fused launch where the message MLP fits the fused kernel (widths <= 64, multiples of 4, <= 3 further
-  // layers, tiles within the LDS halo; max / min only without gradients), the primitives otherwise
-  // (max / min / *: with gradients only where the one-launch pullback takes it -- the primitives' pullbacks of those need the per-edge
-  // messages, which the fused forward does not keep)
-  const bool bwd_ok = !switch_on(Switch::NoFusedEdgeBwd) &&
-                      ngpde_edge_mlp_backward_supported(g, p.h1, p.n_tail, p.n_tail ? p.tail_dout : nullptr, p.aggr) == 1;
-  p.fused_msg = !switch_on(Switch::NoFusedEdge) && p.E > 0 && p.n_tail <= 3 &&
-                (p.aggr == NGPDE_AGGR_SUM || p.aggr == NGPDE_AGGR_MEAN || !training || bwd_ok) &&
-                ngpde_edge_mlp_supported(g, p.h1, p.n_tail, p.n_tail ? p.tail_dout : nullptr) == 1;
-  if (p.fused_msg && training) {
-    p.fused_bwd = bwd_ok;
-    if (p.fused_bwd && p.n_tail >= 2) {
-      // three / four-layer message MLPs: the one-launch pullback pays from ~32 k nodes up (one 4-wave workgroup per CU walks a long
-      // chain per tile); NGPDE_DEEP_EDGE_BWD=1 / 0 forces it on / off
-      const char *deep = switch_text(Switch::DeepEdgeBwd);
-      const char d0 = deep ? deep[0] : '\0';
-      p.fused_bwd = d0 == '1' || (d0 != '0' && p.N >= 32768);
-    }
-  }
+  // layers, tiles within the LDS halo; max / min / * with gradients only where the one-launch pullback takes it), the primitives
+  // otherwise: edge_layer_msg_path in edge_mlp_forms.h, asked about the call the layer makes (P, Q and dQ; E iff edge features)
+  EdgeMlpDesc msg = edge_mlp_desc(p.h1, p.act1, p.n_tail, p.tail_dout, p.tail_act, p.aggr);
+  msg.P = msg.Q = msg.dQ = true; msg.Eterm = p.de > 0;
+  const EdgeMsgPath path = edge_layer_msg_path(edge_tile_geom(g), msg, training);
+  p.fused_msg = path.fused_msg; p.fused_bwd = path.fused_bwd;
 
   // ---- forward region
   p.wA = a.take<float>((size_t)p.rows.out_rows[0] * p.h1);
@@ -299,9 +287,8 @@ int32_t make_plan(const ngpde_graph *g, const ngpde_edge_layer_t &L, bool traini
   p.dP = a.take<float>(N * p.h1);
   p.dQ = a.take<float>(N * p.h1);
   if (p.fused_bwd) {
-    p.need_dE = p.de > 0 || ngpde_edge_mlp_backward_needs_edge_buffer(g, p.h1, p.act1, p.de > 0, p.n_tail, p.n_tail ? p.tail_dout : nullptr,
-                                                                       p.n_tail ? p.tail_act : nullptr, p.aggr) == 1;
-    wsb = std::max(wsb, ngpde_edge_mlp_backward_workspace_bytes(g, p.h1, p.n_tail, p.n_tail ? p.tail_dout : nullptr));
+    p.need_dE = path.need_dE;
+    wsb = std::max(wsb, path.bwd_workspace_bytes);
     p.dE = p.need_dE ? a.take<float>(E * p.h1) : nullptr;
   } else {
     p.eg[0] = a.take<float>(E * emax);

@@ -459,13 +459,9 @@ int32_t ngpde_bias_act_backward(int64_t n, int32_t d, int32_t act, const float *
   return NGPDE_OK;
 }
 
+// The message-MLP entries and queries: edge_mlp_forms.h decides from the graph's tile geometry and the call's description.
 int32_t ngpde_edge_mlp_supported(const ngpde_graph_t *g, int32_t h1, int32_t n_tail, const int32_t *tail_dout) {
-  EdgeMlpArgs a;
-  a.h1 = h1; a.n_tail = n_tail;
-  if (n_tail < 0 || n_tail > 3 || (n_tail > 0 && !tail_dout)) return 0;
-  int prev = h1;
-  for (int l = 0; l < n_tail; ++l) { a.din[l] = prev; a.dout[l] = tail_dout[l]; prev = tail_dout[l]; }
-  return edge_mlp_fused_supported(g, a) ? 1 : 0;
+  return edge_mlp_fwd_supported(edge_tile_geom(g), edge_mlp_desc(h1, 0, n_tail, tail_dout, nullptr, 0)) ? 1 : 0;
 }
 
 int32_t ngpde_edge_mlp_forward(const ngpde_graph_t *g, int32_t h1, int32_t act1, const float *p_target,
@@ -484,43 +480,36 @@ int32_t ngpde_edge_mlp_forward(const ngpde_graph_t *g, int32_t h1, int32_t act1,
   if (g->n_nodes == 0) return NGPDE_OK;
   NGPDE_REQUIRE(out != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_edge_mlp_forward: out is NULL");
   EdgeMlpArgs a;
-  a.h1 = h1; a.act1 = act1; a.aggr = aggr; a.n_tail = n_tail;
+  a.d = edge_mlp_desc(h1, act1, n_tail, tail_dout, tail_act, aggr);
   a.P = p_target; a.Q = q_source; a.Eterm = e_term; a.out = out;
-  int prev = h1;
   for (int l = 0; l < n_tail; ++l) {
     if ((st = check_act("ngpde_edge_mlp_forward", tail_act[l]))) return st;
     NGPDE_REQUIRE(tail_weight[l] != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_edge_mlp_forward: layer %d weight is NULL", l);
-    a.din[l] = prev; a.dout[l] = tail_dout[l]; a.act[l] = tail_act[l];
     a.wt[l] = tail_weight[l]; a.bias[l] = tail_bias ? tail_bias[l] : nullptr;
-    prev = tail_dout[l];
   }
   if (save_z)
-    for (int l = 0; l <= n_tail; ++l) a.save_z[l] = save_z[l];
-  return launch_edge_mlp_fused_fwd(g, a, (hipStream_t)stream);
+    for (int l = 0; l <= n_tail; ++l) {
+      a.save_z[l] = save_z[l];
+      a.d.save_z = a.d.save_z || save_z[l];
+    }
+  a.d.P = a.P != nullptr; a.d.Q = a.Q != nullptr; a.d.Eterm = a.Eterm != nullptr;
+  return launch_edge_mlp_fused_fwd(g, edge_mlp_fwd_plan(edge_tile_geom(g), a.d), a, (hipStream_t)stream);
 }
 
 int32_t ngpde_edge_mlp_backward_supported(const ngpde_graph_t *g, int32_t h1, int32_t n_tail, const int32_t *tail_dout, int32_t aggr) {
-  if (n_tail >= 2) return edge_mlp_deep_bwd_supported(g, h1, n_tail, tail_dout, aggr) ? 1 : 0;   // 3 / 4-layer message MLPs (edge_mlp_deep_bwd.hip)
-  return edge_mlp_fused_bwd_supported(g, h1, n_tail, (n_tail == 1 && tail_dout) ? tail_dout[0] : 0, aggr) ? 1 : 0;
+  return edge_mlp_bwd_plan(edge_tile_geom(g), edge_mlp_desc(h1, 0, n_tail, tail_dout, nullptr, aggr)).supported ? 1 : 0;
 }
 
 size_t ngpde_edge_mlp_backward_workspace_bytes(const ngpde_graph_t *g, int32_t h1, int32_t n_tail, const int32_t *tail_dout) {
-  if (!g) return 0;
-  if (n_tail >= 2) return (n_tail <= 3 && tail_dout) ? edge_mlp_deep_bwd_workspace(g, h1, n_tail, tail_dout) : 0;
-  return edge_mlp_fused_bwd_workspace(g, h1, n_tail, (n_tail == 1 && tail_dout) ? tail_dout[0] : 0);
+  return edge_mlp_bwd_workspace_bytes(edge_tile_geom(g), edge_mlp_desc(h1, 0, n_tail, tail_dout, nullptr, 0));
 }
 
 int32_t ngpde_edge_mlp_backward_needs_edge_buffer(const ngpde_graph_t *g, int32_t h1, int32_t act1, int32_t has_e_term, int32_t n_tail,
                                                    const int32_t *tail_dout, const int32_t *tail_act, int32_t aggr) {
-  if (!g || has_e_term) return 1;
-  EdgeMlpBwdArgs a;
-  static const float probe = 0.f;   // (pointers are only tested for NULL here)
-  a.h1 = h1; a.act1 = act1; a.aggr = aggr; a.n_tail = n_tail;
-  a.P = &probe; a.Q = &probe; a.Eterm = nullptr; a.dQ = const_cast<float *>(&probe);
-  if (n_tail == 1 && tail_dout && tail_act) {
-    a.dw = tail_dout[0]; a.act2 = tail_act[0];
-  }
-  return (edge_mlp64_bwd_applicable(g, a) && edge_mlp64_bwd_dq_in_launch(g, a)) ? 0 : 1;
+  EdgeMlpDesc d = edge_mlp_desc(h1, act1, n_tail, tail_dout, tail_act, aggr);   // a call with P, Q and dQ
+  d.tails = d.tails && (n_tail <= 0 || tail_act != nullptr);
+  d.P = d.Q = d.dQ = true; d.Eterm = has_e_term != 0;
+  return edge_mlp_bwd_plan(edge_tile_geom(g), d).edge_buffer ? 1 : 0;
 }
 
 int32_t ngpde_edge_mlp_backward(const ngpde_graph_t *g, int32_t h1, int32_t act1, const float *p_target, const float *q_source,
@@ -541,26 +530,17 @@ int32_t ngpde_edge_mlp_backward(const ngpde_graph_t *g, int32_t h1, int32_t act1
   }
   if (g->n_nodes == 0) return NGPDE_OK;
   NGPDE_REQUIRE(dout != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_edge_mlp_backward: dout is NULL");
-  if (n_tail >= 2) {   // message MLPs of three / four layers
-    EdgeMlpDeepBwdArgs d;
-    d.h1 = h1; d.act1 = act1; d.aggr = aggr; d.n_tail = n_tail;
-    d.P = p_target; d.Q = q_source; d.Eterm = e_term; d.dout_grad = dout;
-    for (int l = 0; l < n_tail; ++l) {
-      d.dout[l] = tail_dout[l]; d.act[l] = tail_act[l]; d.wt[l] = tail_weight[l]; d.bias[l] = tail_bias ? tail_bias[l] : nullptr;
-      d.dwt[l] = dtail_weight[l]; d.dbias[l] = dtail_bias ? dtail_bias[l] : nullptr;
-    }
-    d.dP = dp_target; d.dQ = dq_source; d.dE = de_term; d.workspace = workspace; d.workspace_bytes = workspace_bytes;
-    return launch_edge_mlp_deep_bwd(g, d, (hipStream_t)stream);
-  }
   EdgeMlpBwdArgs a;
-  a.h1 = h1; a.act1 = act1; a.aggr = aggr; a.n_tail = n_tail;
+  a.d = edge_mlp_desc(h1, act1, n_tail, tail_dout, tail_act, aggr);
   a.P = p_target; a.Q = q_source; a.Eterm = e_term; a.dout = dout;
-  if (n_tail) {
-    a.dw = tail_dout[0]; a.act2 = tail_act[0]; a.wt = tail_weight[0]; a.bias = tail_bias ? tail_bias[0] : nullptr;
-    a.dwt = dtail_weight[0]; a.dbias = dtail_bias ? dtail_bias[0] : nullptr;
+  for (int l = 0; l < n_tail; ++l) {
+    a.wt[l] = tail_weight[l]; a.bias[l] = tail_bias ? tail_bias[l] : nullptr;
+    a.dwt[l] = dtail_weight[l]; a.dbias[l] = dtail_bias ? dtail_bias[l] : nullptr;
   }
   a.dP = dp_target; a.dQ = dq_source; a.dE = de_term; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
-  return launch_edge_mlp_fused_bwd(g, a, (hipStream_t)stream);
+  a.d.P = a.P != nullptr; a.d.Q = a.Q != nullptr; a.d.Eterm = a.Eterm != nullptr; a.d.dQ = a.dQ != nullptr; a.d.dE = a.dE != nullptr;
+  const EdgeBwd p = edge_mlp_bwd_plan(edge_tile_geom(g), a.d);
+  return p.form == EdgeBwdForm::Deep ? launch_edge_mlp_deep_bwd(g, p, a, (hipStream_t)stream) : launch_edge_mlp_fused_bwd(g, p, a, (hipStream_t)stream);
 }
 
 int32_t ngpde_activation_forward(int64_t count, int32_t act, const float *z, float *a, ngpde_stream_t stream) {

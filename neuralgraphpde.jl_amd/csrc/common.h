@@ -12,6 +12,7 @@
 
 #include "../../include/ngpde.h"
 #include "dense_forms.h"
+#include "edge_mlp_forms.h"
 #include "workspace.h"
 
 namespace ngpde {
@@ -80,9 +81,7 @@ struct HaloInverse {
   int stride = 0;
 };
 
-constexpr int kTileRows = 32;  // node rows per workgroup of the fused kernels
-constexpr int kHaloCap = 96;   // unique rows a tile may stage in LDS (24 KB at D = 64), plus one zero row
-constexpr int kSlotWidth = 32;  // slot bytes per row of the LDS-staged aggregation (rows with more: global gather)
+// kTileRows, kHaloCap, kSlotWidth: edge_mlp_forms.h (host only; the message-MLP family decides in them)
 constexpr int kEllWidth = 16;  // entries per row held in the fixed-width block (rows with more spill to the CSR list)
 
 }  // namespace ngpde
@@ -114,6 +113,15 @@ struct ngpde_graph {
 };
 
 namespace ngpde {
+
+// all the message-MLP family's choices read of a handle (edge_mlp_forms.h); NULL: no graph
+inline EdgeTileGeom edge_tile_geom(const ngpde_graph *g) {
+  EdgeTileGeom t;
+  if (!g) return t;
+  t.graph = true; t.has_norm = g->has_norm; t.halo_ok = g->by_t.halo_ok; t.max_halo = g->by_t.max_halo;
+  t.n_tiles = (int)(g->n_sched / kTileRows); t.n_nodes = g->n_nodes; t.n_edges = g->n_edges;
+  return t;
+}
 
 // ---- device-side handle construction (graph_device.hip)
 template <class I>
@@ -478,39 +486,28 @@ int32_t launch_colsum2(int64_t n, int d, const float *a, float *partial, float *
 int32_t launch_bias_act2(int64_t n, int d, int act, const float *a, const float *addend, const float *bias, float *y, float *save_z,
                          hipStream_t stream);
 
-// ---- fused edge-MLP forward (edge_mlp_fused.hip) ----------------------------------------------------------
+// ---- one-launch message MLP (edge_mlp_fused.hip, edge_mlp64.hip, edge_mlp_deep_bwd.hip): edge_mlp_forms.h decides, these launch ----
 struct EdgeMlpArgs {
-  int h1 = 0, act1 = 0, aggr = 0, n_tail = 0;
+  EdgeMlpDesc d;
   const float *P = nullptr, *Q = nullptr, *Eterm = nullptr;
-  int din[3] = {0, 0, 0}, dout[3] = {0, 0, 0}, act[3] = {0, 0, 0};
   const float *wt[3] = {nullptr, nullptr, nullptr}, *bias[3] = {nullptr, nullptr, nullptr};
   float *out = nullptr;
   float *save_z[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 struct EdgeMlpBwdArgs {
-  int h1 = 0, act1 = 0, aggr = 0, n_tail = 0, dw = 0, act2 = 0;
-  const float *P = nullptr, *Q = nullptr, *Eterm = nullptr, *wt = nullptr, *bias = nullptr, *dout = nullptr;
-  float *dP = nullptr, *dQ = nullptr, *dE = nullptr, *dwt = nullptr, *dbias = nullptr;
-  void *workspace = nullptr;
-  size_t workspace_bytes = 0;
-};
-// edge_mlp_deep_bwd.hip: the same pullback for 2 or 3 Dense layers after the first (message MLPs of 3 / 4 layers)
-struct EdgeMlpDeepBwdArgs {
-  int h1 = 0, act1 = 0, aggr = 0, n_tail = 0;
-  int dout[3] = {0, 0, 0}, act[3] = {0, 0, 0};
-  const float *P = nullptr, *Q = nullptr, *Eterm = nullptr, *dout_grad = nullptr;
+  EdgeMlpDesc d;
+  const float *P = nullptr, *Q = nullptr, *Eterm = nullptr, *dout = nullptr;
   const float *wt[3] = {nullptr, nullptr, nullptr}, *bias[3] = {nullptr, nullptr, nullptr};
   float *dP = nullptr, *dQ = nullptr, *dE = nullptr;
   float *dwt[3] = {nullptr, nullptr, nullptr}, *dbias[3] = {nullptr, nullptr, nullptr};
   void *workspace = nullptr;
   size_t workspace_bytes = 0;
 };
-bool edge_mlp_deep_bwd_supported(const ngpde_graph *g, int h1, int n_tail, const int *dout, int aggr);
-size_t edge_mlp_deep_bwd_workspace(const ngpde_graph *g, int h1, int n_tail, const int *dout);
-int32_t launch_edge_mlp_deep_bwd(const ngpde_graph *g, const EdgeMlpDeepBwdArgs &a, hipStream_t stream);
-bool edge_mlp_fused_bwd_supported(const ngpde_graph *g, int h1, int n_tail, int dw, int aggr);
-size_t edge_mlp_fused_bwd_workspace(const ngpde_graph *g, int h1, int n_tail, int dw);
-int32_t launch_edge_mlp_fused_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hipStream_t stream);
+int32_t launch_edge_mlp_fused_fwd(const ngpde_graph *g, const EdgeFwd &p, const EdgeMlpArgs &a, hipStream_t stream);
+int32_t launch_edge_mlp64_fwd(const ngpde_graph *g, const EdgeFwd &p, const EdgeMlpArgs &a, hipStream_t stream);
+int32_t launch_edge_mlp_fused_bwd(const ngpde_graph *g, const EdgeBwd &p, const EdgeMlpBwdArgs &a, hipStream_t stream);
+int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeBwd &p, const EdgeMlpBwdArgs &a, hipStream_t stream);
+int32_t launch_edge_mlp_deep_bwd(const ngpde_graph *g, const EdgeBwd &p, const EdgeMlpBwdArgs &a, hipStream_t stream);
 int32_t launch_dense_weight_reduce(int nchunk, int din, int dout, const float *partial, float *dwt, float *db, hipStream_t stream);
 // the whole pullback of a Dense of at most 64 x 64 in one launch + the slab reduction (dense_small_bwd.hip)
 int32_t launch_dense_small_fwd(int64_t n, const SegTable &t, int din, int dout, int act, const float *wt, const float *bias, float *y,
@@ -518,16 +515,7 @@ int32_t launch_dense_small_fwd(int64_t n, const SegTable &t, int din, int dout, 
 int32_t launch_dense_small_bwd(int64_t n, const SegTable &t, int din, int dout, int act, const float *wt, const float *z, const float *dy,
                                const SegGrad &grads, float *dwt, float *dbias, float *slabs, int grid, hipStream_t stream);
 int32_t launch_edge_sum_by_source(const ngpde_graph *g, int h, const float *per_edge, float *out, hipStream_t stream);
-bool edge_mlp_fused_supported(const ngpde_graph *g, const EdgeMlpArgs &a);
-int32_t launch_edge_mlp_fused_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hipStream_t stream);
 int32_t launch_activation_fwd(int64_t count, int act, const float *z, float *a, hipStream_t stream);
-// edge_mlp64.hip: software-pipelined specialisations for the 64-wide two-layer message MLP (BASELINE config 4's shape)
-bool edge_mlp64_fwd_applicable(const ngpde_graph *g, const EdgeMlpArgs &a);
-int32_t launch_edge_mlp64_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hipStream_t stream);
-bool edge_mlp64_bwd_applicable(const ngpde_graph *g, const EdgeMlpBwdArgs &a);
-bool edge_mlp64_bwd_dq_in_launch(const ngpde_graph *g, const EdgeMlpBwdArgs &a);   // the by-source sum inside the launch: no [E][64] buffer needed
-size_t edge_mlp64_bwd_workspace(const ngpde_graph *g);
-int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hipStream_t stream);
 
 
 // ---- ROCTx ranges around the C-ABI entries (tracing).  rocprofv3 --marker-trace then attributes the

@@ -92,7 +92,6 @@ constexpr int kDenseTrailing = 8;                       // features of trailing 
 constexpr int64_t kDenseSmallRows = 65536;              // the small forms: latency-bound row counts
 constexpr int64_t kDenseStreamBwdRows = 32768;          // the streaming pullbacks: a resident wave of tiles ...
 constexpr int64_t kDenseStreamBwdMaxRows = 1 << 24;     // ... and 32-bit byte offsets
-constexpr size_t kWsSlack = 256;                        // what the Dense and GAT workspace queries add behind their pieces
 
 using KernelNames = std::vector<const char *>;
 inline int64_t dense_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -48,7 +48,7 @@ __device__ __forceinline__ unsigned lds_addr(const void *ptr) { return (unsigned
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kT4 = 256, kSlice = 16, kChunk4 = 64;   // (kW, kTS, kRows: edge_mlp_tile.h)
+constexpr int kSlice = 16;   // edges of a wave's slice (kT4, kChunk4, kW, kTS, kRows: edge_mlp_forms.h)
 using Shape = TwoRowsPerGroup;
 
 struct EdgeMlp64K : EdgeTileArgs {
@@ -350,8 +350,7 @@ struct EdgeMlp64BwdK : EdgeTileArgs {
   float *dqpart;              // DQ: [n_tiles][kDqStride][64] per-tile sums of dz1 by FOREIGN halo slot (the by-source sum, first half)
   float *dQ;                  // DQ: the sums of a tile's OWN slots (= its own rows) go straight to the node's row
 };
-constexpr int kDqSlots = 3;                 // halo slots per 16-lane group whose sums stay in registers (DQ)
-constexpr int kDqStride = 16 * kDqSlots;    // = the largest halo the in-launch by-source sum takes (48 rows)
+// kDqSlots halo slots per 16-lane group stay in registers (DQ); kDqStride = 16 kDqSlots rows: edge_mlp_forms.h
 
 // a = act(z), d = act'(z) with the shared transcendental evaluated once (same operations as act_apply / act_deriv)
 template <int ACT>
@@ -605,37 +604,28 @@ __global__ __launch_bounds__(kT4, 2) void edge_mlp64_bwd_kernel(const EdgeMlp64B
   }
 }
 
-}  // namespace
-
-// The specialised launch applies to: P and Q present, no per-edge term, h1 = 64, one further Dense 64 => 64, nothing saved per
-// edge, + / mean, and an activation pair that is instantiated below.  NGPDE_NO_EDGE64=1 keeps the general kernel.
-bool edge_mlp64_fwd_applicable(const ngpde_graph *g, const EdgeMlpArgs &a) {
-  if (switch_on(Switch::NoEdge64)) return false;
-  if (!a.P || !a.Q || a.Eterm || a.h1 != kW || a.n_tail != 1 || a.din[0] != kW || a.dout[0] != kW) return false;
-  for (int l = 0; l < 4; ++l)
-    if (a.save_z[l]) return false;
-  if (a.aggr != NGPDE_AGGR_SUM && a.aggr != NGPDE_AGGR_MEAN) return false;
-  const bool a1 = a.act1 == NGPDE_ACT_SWISH || a.act1 == NGPDE_ACT_RELU || a.act1 == NGPDE_ACT_TANH;
-  const bool a2 = a.act[0] == a.act1 || a.act[0] == NGPDE_ACT_IDENTITY;
-  return a1 && a2;
+// the instantiation of an activation pair edge_mlp_forms.h admits (edge64_shape): f(A1, A2) with both as integral constants
+template <class F>
+int32_t edge64_pair(int act1, int act2, F f) {
+  auto second = [&](auto a1) { return act2 == act1 ? f(a1, a1) : f(a1, std::integral_constant<int, NGPDE_ACT_IDENTITY>{}); };
+  switch (act1) {
+    case NGPDE_ACT_SWISH: return second(std::integral_constant<int, NGPDE_ACT_SWISH>{});
+    case NGPDE_ACT_RELU: return second(std::integral_constant<int, NGPDE_ACT_RELU>{});
+    default: return second(std::integral_constant<int, NGPDE_ACT_TANH>{});
+  }
 }
 
-int32_t launch_edge_mlp64_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hipStream_t stream) {
+}  // namespace
+
+int32_t launch_edge_mlp64_fwd(const ngpde_graph *g, const EdgeFwd &p, const EdgeMlpArgs &a, hipStream_t stream) {
   EdgeMlp64K k;
-  fill_tile_args(g, k);
-  k.aggr = a.aggr;
+  fill_tile_args(g, edge_tile_geom(g), k);
+  k.aggr = a.d.aggr;
   k.P = a.P; k.Q = a.Q; k.wt = a.wt[0]; k.bias = a.bias[0]; k.out = a.out;
   NGPDE_STAMP_SET(k, kStampEdge64, 0);
-  const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kW * kTS + 2 * (size_t)kChunk4 * kTS) * sizeof(float);
-  // two persistent workgroups per CU (one when the halo region is large), a multiple of the 8 XCDs
-  const int grid = edge_persistent_grid(g, lds + 4096 <= 80 * 1024 ? 64 : 32);
-  auto launch = [&](auto kernel) { return launch_with_lds(kernel, grid, kT4, lds, stream, k, "edge_mlp64_fwd_kernel"); };
-  const bool same = a.act[0] == a.act1;
-  switch (a.act1) {
-    case NGPDE_ACT_SWISH: return same ? launch(edge_mlp64_fwd_kernel<NGPDE_ACT_SWISH, NGPDE_ACT_SWISH>) : launch(edge_mlp64_fwd_kernel<NGPDE_ACT_SWISH, NGPDE_ACT_IDENTITY>);
-    case NGPDE_ACT_RELU: return same ? launch(edge_mlp64_fwd_kernel<NGPDE_ACT_RELU, NGPDE_ACT_RELU>) : launch(edge_mlp64_fwd_kernel<NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY>);
-    default: return same ? launch(edge_mlp64_fwd_kernel<NGPDE_ACT_TANH, NGPDE_ACT_TANH>) : launch(edge_mlp64_fwd_kernel<NGPDE_ACT_TANH, NGPDE_ACT_IDENTITY>);
-  }
+  return edge64_pair(p.act1, p.act2, [&](auto a1, auto a2) {
+    return launch_with_lds(edge_mlp64_fwd_kernel<decltype(a1)::value, decltype(a2)::value>, p.grid, p.threads, p.lds, stream, k, "edge_mlp64_fwd_kernel");
+  });
 }
 
 // dQ[node] += the partial rows of the OTHER tiles whose halo list holds the node (entries ascending by tile: fixed order); the node's
@@ -651,75 +641,38 @@ __global__ __launch_bounds__(256) void edge64_dq_combine_kernel(int n_listed, co
   *dst = a;
 }
 
-// ---- pullback launch.  Same conditions as the forward specialisation (the activation pairs instantiated below); workspace =
-// one [65][64] slab per workgroup of the larger grid (two workgroups per CU).
-bool edge_mlp64_bwd_applicable(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
-  if (switch_on(Switch::NoEdge64)) return false;
-  if (!a.P || !a.Q || a.Eterm || a.h1 != kW || a.n_tail != 1 || a.dw != kW) return false;
-  if (a.aggr != NGPDE_AGGR_SUM && a.aggr != NGPDE_AGGR_MEAN) return false;
-  const bool a1 = a.act1 == NGPDE_ACT_SWISH || a.act1 == NGPDE_ACT_RELU || a.act1 == NGPDE_ACT_TANH;
-  const bool a2 = a.act2 == a.act1 || a.act2 == NGPDE_ACT_IDENTITY;
-  return a1 && a2;
-}
-// the by-source sum inside the launch (no [E][64] array): no per-edge term, every halo within kDqStride rows
-bool edge_mlp64_bwd_dq_in_launch(const ngpde_graph *g, const EdgeMlpBwdArgs &a) {
-  if (switch_on(Switch::Edge64NoDq)) return false;
-  return a.Eterm == nullptr && a.dQ != nullptr && g->by_t.halo_ok && g->by_t.max_halo <= kDqStride;
-}
-// the slabs of the larger grid; behind them, on a graph whose halos allow the by-source sum inside the launch, its per-tile partials
-static void edge64_bwd_layout(Workspace &w, const ngpde_graph *g, float *&partial, float *&dqpart) {
-  partial = take_slabs(w, edge_persistent_grid(g, 64), kW, kW);
-  const bool part = g->by_t.halo_ok && g->by_t.max_halo <= kDqStride;
-  dqpart = part ? w.take<float>((size_t)(g->n_sched / kTileRows) * kDqStride * kW) : nullptr;
-}
-size_t edge_mlp64_bwd_workspace(const ngpde_graph *g) {
-  float *partial, *dqpart;
-  return measure(edge64_bwd_layout, g, partial, dqpart) + 256;
-}
-
-int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hipStream_t stream) {
+// ---- pullback launch (launch_edge_mlp_fused_bwd has checked the workspace and the dE rule)
+int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeBwd &p, const EdgeMlpBwdArgs &a, hipStream_t stream) {
+  const EdgeTileGeom t = edge_tile_geom(g);
   EdgeMlp64BwdK k;
-  fill_tile_args(g, k);
-  k.aggr = a.aggr;
-  k.P = a.P; k.Q = a.Q; k.wt = a.wt; k.bias = a.bias; k.dout = a.dout;
+  fill_tile_args(g, t, k);
+  k.aggr = a.d.aggr;
+  k.P = a.P; k.Q = a.Q; k.wt = a.wt[0]; k.bias = a.bias[0]; k.dout = a.dout;
   k.dP = a.dP; k.dE = a.dE;
-  Workspace w(a.workspace);   // (launch_edge_mlp_fused_bwd checked its size)
-  float *dqpart;
-  edge64_bwd_layout(w, g, k.partial, dqpart);
-  const bool dq = edge_mlp64_bwd_dq_in_launch(g, a);
+  Workspace w(a.workspace);
+  EdgeBwdWs ws;
+  edge_mlp_bwd_layout(w, t, a.d, p.form, ws);
+  k.partial = ws.partial[0];
   const HaloInverse *hinv = nullptr;
-  if (dq) {
+  if (p.dq) {
     int32_t sti = graph_halo_inverse(g, kDqStride, &hinv);
     if (sti) return sti;
   }
-  NGPDE_REQUIRE(dq || a.dE != nullptr || g->n_edges == 0, NGPDE_ERR_INVALID_ARGUMENT, "fused edge-MLP pullback: the [E][h1] buffer dE is required");
-  k.dqpart = dq ? dqpart : nullptr;
-  k.dQ = dq ? a.dQ : nullptr;
-  const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kChunk4 * kTS + 2 * (size_t)kW * kTS) * sizeof(float);
-  // two workgroups per CU, or one when the halo region is large (the workspace holds slabs for the larger grid)
-  const int grid = edge_persistent_grid(g, lds + 4096 <= 80 * 1024 ? 64 : 32);
-  auto launch = [&](auto kernel) { return launch_with_lds(kernel, grid, kT4, lds, stream, k, "edge_mlp64_bwd_kernel"); };
-  int32_t st;
-  const bool same = a.act2 == a.act1;
-#define NGPDE_E64B(A1, A2) (dq ? launch(edge_mlp64_bwd_kernel<A1, A2, true>) : launch(edge_mlp64_bwd_kernel<A1, A2, false>))
-  switch (a.act1) {
-    case NGPDE_ACT_SWISH: st = same ? NGPDE_E64B(NGPDE_ACT_SWISH, NGPDE_ACT_SWISH) : NGPDE_E64B(NGPDE_ACT_SWISH, NGPDE_ACT_IDENTITY); break;
-    case NGPDE_ACT_RELU: st = same ? NGPDE_E64B(NGPDE_ACT_RELU, NGPDE_ACT_RELU) : NGPDE_E64B(NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY); break;
-    default: st = same ? NGPDE_E64B(NGPDE_ACT_TANH, NGPDE_ACT_TANH) : NGPDE_E64B(NGPDE_ACT_TANH, NGPDE_ACT_IDENTITY); break;
-  }
-#undef NGPDE_E64B
+  k.dqpart = p.dq ? ws.dqpart : nullptr;
+  k.dQ = p.dq ? a.dQ : nullptr;
+  int32_t st = edge64_pair(p.act1, p.act2, [&](auto a1, auto a2) {
+    return p.dq ? launch_with_lds(edge_mlp64_bwd_kernel<decltype(a1)::value, decltype(a2)::value, true>, p.grid, p.threads, p.lds, stream, k, "edge_mlp64_bwd_kernel")
+                : launch_with_lds(edge_mlp64_bwd_kernel<decltype(a1)::value, decltype(a2)::value, false>, p.grid, p.threads, p.lds, stream, k, "edge_mlp64_bwd_kernel");
+  });
   if (st) return st;
-  if ((st = launch_dense_weight_reduce(grid, kW, kW, k.partial, a.dwt, a.dbias, stream))) return st;
-  if (dq) {
-    if (hinv->n_listed > 0) {
-      const int64_t threads = (int64_t)hinv->n_listed * 16;
-      hipLaunchKernelGGL(edge64_dq_combine_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, hinv->n_listed, hinv->node, hinv->ptr,
-                         hinv->ent, k.dqpart, a.dQ);
-      NGPDE_LAUNCH_CHECK("edge64_dq_combine_kernel");
-    }
-    return NGPDE_OK;
+  if ((st = launch_dense_weight_reduce(p.grid, kW, kW, k.partial, a.dwt[0], a.dbias[0], stream))) return st;
+  if (p.dq && hinv->n_listed > 0) {
+    const int64_t threads = (int64_t)hinv->n_listed * 16;
+    hipLaunchKernelGGL(edge64_dq_combine_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, hinv->n_listed, hinv->node, hinv->ptr,
+                       hinv->ent, k.dqpart, a.dQ);
+    NGPDE_LAUNCH_CHECK("edge64_dq_combine_kernel");
   }
-  if (a.dQ && (st = launch_edge_sum_by_source(g, kW, a.dE, a.dQ, stream))) return st;
+  if (p.by_source && (st = launch_edge_sum_by_source(g, kW, a.dE, a.dQ, stream))) return st;
   return NGPDE_OK;
 }
 

@@ -24,8 +24,7 @@ namespace ngpde {
 
 namespace {
 
-constexpr int kT4 = 256, kChunk4 = 64, kMaxTail = 3;   // (kW, kTS, kRows: edge_mlp_tile.h)
-using Shape = TwoRowsPerGroup;
+using Shape = TwoRowsPerGroup;   // (kT4, kChunk4, kMaxTail, kW, kTS, kRows: edge_mlp_forms.h)
 
 struct DeepBwdK : EdgeTileArgs {
   int h1, act1, aggr, n_tail;
@@ -197,64 +196,34 @@ __global__ __launch_bounds__(kT4, 1) void edge_mlp_deep_bwd_kernel(const DeepBwd
   }
 }
 
-int deep_grid(const ngpde_graph *g) { return edge_persistent_grid(g, 32); }   // one persistent workgroup per CU
-
 }  // namespace
 
-bool edge_mlp_deep_bwd_supported(const ngpde_graph *g, int h1, int n_tail, const int *dout, int aggr) {
-  if (!g || !g->has_norm || !g->by_t.halo_ok) return false;
-  if (h1 <= 0 || h1 > kW || h1 % 4 || n_tail < 2 || n_tail > kMaxTail || !dout) return false;
-  for (int l = 0; l < n_tail; ++l)
-    if (dout[l] <= 0 || dout[l] > kW || dout[l] % 4) return false;
-  return aggr == NGPDE_AGGR_SUM || aggr == NGPDE_AGGR_MEAN;
-}
-
-namespace {
-// partial[l]: the weight slabs of tail layer l, one per workgroup; nullptr from n_tail on
-void deep_bwd_layout(Workspace &w, const ngpde_graph *g, int h1, int n_tail, const int *dout, float *(&partial)[kMaxTail]) {
-  const int grid = deep_grid(g);
-  int din = h1;
-  for (int l = 0; l < kMaxTail; ++l) {
-    partial[l] = l < n_tail ? take_slabs(w, grid, din, dout[l]) : nullptr;
-    if (l < n_tail) din = dout[l];
-  }
-}
-}  // namespace
-
-size_t edge_mlp_deep_bwd_workspace(const ngpde_graph *g, int h1, int n_tail, const int *dout) {
-  float *partial[kMaxTail];
-  return measure(deep_bwd_layout, g, h1, n_tail, dout, partial) + 256;
-}
-
-int32_t launch_edge_mlp_deep_bwd(const ngpde_graph *g, const EdgeMlpDeepBwdArgs &a, hipStream_t stream) {
-  NGPDE_REQUIRE(edge_mlp_deep_bwd_supported(g, a.h1, a.n_tail, a.dout, a.aggr), NGPDE_ERR_UNSUPPORTED,
+int32_t launch_edge_mlp_deep_bwd(const ngpde_graph *g, const EdgeBwd &p, const EdgeMlpBwdArgs &a, hipStream_t stream) {
+  NGPDE_REQUIRE(p.supported, NGPDE_ERR_UNSUPPORTED,
                 "deep fused edge-MLP pullback needs widths <= 64 and multiples of 4, 2 or 3 layers after the first, + or mean "
                 "aggregation and a graph whose tiles fit the LDS halo");
-  if (g->n_nodes == 0) return NGPDE_OK;
-  if (int32_t st = check_workspace("deep fused edge-MLP pullback", a.workspace, a.workspace_bytes, edge_mlp_deep_bwd_workspace(g, a.h1, a.n_tail, a.dout), 1))
-    return st;
-  NGPDE_REQUIRE(a.dE != nullptr || g->n_edges == 0, NGPDE_ERR_INVALID_ARGUMENT, "deep fused edge-MLP pullback: the [E][h1] buffer dE is required");
+  if (!p.launch) return NGPDE_OK;   // no nodes
+  if (int32_t st = check_workspace("deep fused edge-MLP pullback", a.workspace, a.workspace_bytes, p.workspace_bytes, 1)) return st;
+  NGPDE_REQUIRE(!p.dE_missing, NGPDE_ERR_INVALID_ARGUMENT, "deep fused edge-MLP pullback: the [E][h1] buffer dE is required");
+  const EdgeMlpDesc &d = a.d;
+  const EdgeTileGeom t = edge_tile_geom(g);
   DeepBwdK k;
-  fill_tile_args(g, k);
-  k.h1 = a.h1; k.act1 = a.act1; k.aggr = a.aggr; k.n_tail = a.n_tail;
-  k.P = a.P; k.Q = a.Q; k.Eterm = a.Eterm; k.dout_grad = a.dout_grad; k.dP = a.dP; k.dE = a.dE;
-  const int grid = deep_grid(g);
+  fill_tile_args(g, t, k);
+  k.h1 = d.h1; k.act1 = d.act1; k.aggr = d.aggr; k.n_tail = d.n_tail;
+  k.P = a.P; k.Q = a.Q; k.Eterm = a.Eterm; k.dout_grad = a.dout; k.dP = a.dP; k.dE = a.dE;
   Workspace w(a.workspace);
-  deep_bwd_layout(w, g, a.h1, a.n_tail, a.dout, k.partial);
+  EdgeBwdWs ws;
+  edge_mlp_bwd_layout(w, t, d, p.form, ws);
   for (int l = 0; l < kMaxTail; ++l) {
-    k.dout[l] = l < a.n_tail ? a.dout[l] : 0; k.act[l] = l < a.n_tail ? a.act[l] : 0;
-    k.wt[l] = l < a.n_tail ? a.wt[l] : nullptr; k.bias[l] = l < a.n_tail ? a.bias[l] : nullptr;
+    k.partial[l] = ws.partial[l];
+    k.dout[l] = d.dout[l]; k.act[l] = d.act[l]; k.wt[l] = a.wt[l]; k.bias[l] = a.bias[l];   // (zero / NULL from n_tail on)
   }
-  const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kRows * kTS + (size_t)kChunk4 * kTS + 2 * (size_t)a.n_tail * kW * kTS) * sizeof(float);
-  int32_t st = a.n_tail == 2 ? launch_with_lds(edge_mlp_deep_bwd_kernel<2>, grid, kT4, lds, stream, k, "edge_mlp_deep_bwd_kernel")
-                             : launch_with_lds(edge_mlp_deep_bwd_kernel<3>, grid, kT4, lds, stream, k, "edge_mlp_deep_bwd_kernel");
+  int32_t st = p.n_tail == 2 ? launch_with_lds(edge_mlp_deep_bwd_kernel<2>, p.grid, p.threads, p.lds, stream, k, "edge_mlp_deep_bwd_kernel")
+                             : launch_with_lds(edge_mlp_deep_bwd_kernel<3>, p.grid, p.threads, p.lds, stream, k, "edge_mlp_deep_bwd_kernel");
   if (st) return st;
-  int din = a.h1;
-  for (int l = 0; l < a.n_tail; ++l) {
-    if ((st = launch_dense_weight_reduce(grid, din, a.dout[l], k.partial[l], a.dwt[l], a.dbias[l], stream))) return st;
-    din = a.dout[l];
-  }
-  if (a.dQ && (st = launch_edge_sum_by_source(g, a.h1, a.dE, a.dQ, stream))) return st;
+  for (int l = 0; l < p.n_tail; ++l)
+    if ((st = launch_dense_weight_reduce(p.grid, d.din(l), d.dout[l], k.partial[l], a.dwt[l], a.dbias[l], stream))) return st;
+  if (p.by_source && (st = launch_edge_sum_by_source(g, d.h1, a.dE, a.dQ, stream))) return st;
   return NGPDE_OK;
 }
 

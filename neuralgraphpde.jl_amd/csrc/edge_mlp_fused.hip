@@ -20,8 +20,7 @@ namespace ngpde {
 
 namespace {
 
-constexpr int kT = 512, kChunk = 128, kGroups = 32;   // kChunk = 8 waves x 16 edges (kW, kTS: edge_mlp_tile.h)
-using Shape = RowPerGroup;
+using Shape = RowPerGroup;   // (kT, kChunk = 8 waves x 16 edges, kGroups, kW, kTS: edge_mlp_forms.h)
 
 struct EdgeMlpK : EdgeTileArgs {
   int h1, act1, aggr;
@@ -462,83 +461,57 @@ __global__ void activation_fwd_kernel(int64_t count, int act, const float *__res
 
 }  // namespace
 
-bool edge_mlp_fused_supported(const ngpde_graph *g, const EdgeMlpArgs &a) {
-  if (!g || !g->has_norm || !g->by_t.halo_ok) return false;   // needs the tile schedule, halo lists and slot bytes
-  if (a.h1 <= 0 || a.h1 > kW || a.h1 % 4) return false;
-  if (a.n_tail < 0 || a.n_tail > 3) return false;
-  int prev = a.h1;
-  for (int l = 0; l < a.n_tail; ++l) {
-    if (a.din[l] != prev || a.dout[l] <= 0 || a.dout[l] > kW || a.dout[l] % 4) return false;
-    prev = a.dout[l];
-  }
-  return true;
-}
-
-int32_t launch_edge_mlp_fused_fwd(const ngpde_graph *g, const EdgeMlpArgs &a, hipStream_t stream) {
-  NGPDE_REQUIRE(edge_mlp_fused_supported(g, a), NGPDE_ERR_UNSUPPORTED,
+int32_t launch_edge_mlp_fused_fwd(const ngpde_graph *g, const EdgeFwd &p, const EdgeMlpArgs &a, hipStream_t stream) {
+  NGPDE_REQUIRE(p.supported, NGPDE_ERR_UNSUPPORTED,
                 "fused edge-MLP path needs widths <= 64 and multiples of 4, <= 3 layers after the first, and a graph whose "
                 "tiles fit the LDS halo (degree <= %d, <= %d distinct sources per 32-row tile)", kSlotWidth, kHaloCap);
-  if (g->n_nodes == 0) return NGPDE_OK;
-  if (edge_mlp64_fwd_applicable(g, a)) return launch_edge_mlp64_fwd(g, a, stream);
+  if (p.form == EdgeFwdForm::None) return NGPDE_OK;   // no nodes
+  if (p.form == EdgeFwdForm::Edge64) return launch_edge_mlp64_fwd(g, p, a, stream);
+  const EdgeMlpDesc &d = a.d;
   EdgeMlpK k;
-  fill_tile_args(g, k);   // (halo region sized by the largest halo of this graph's tiles)
-  k.h1 = a.h1; k.act1 = a.act1; k.aggr = a.aggr;
-  k.P = a.P; k.Q = a.Q; k.Eterm = a.Eterm; k.n_tail = a.n_tail;
+  fill_tile_args(g, edge_tile_geom(g), k);   // (halo region sized by the largest halo of this graph's tiles)
+  k.h1 = d.h1; k.act1 = d.act1; k.aggr = d.aggr;
+  k.P = a.P; k.Q = a.Q; k.Eterm = a.Eterm; k.n_tail = d.n_tail;
   for (int l = 0; l < 3; ++l) {
-    k.din[l] = a.din[l]; k.dout[l] = a.dout[l]; k.act[l] = a.act[l]; k.wt[l] = a.wt[l]; k.bias[l] = a.bias[l];
+    k.din[l] = l < d.n_tail ? d.din(l) : 0; k.dout[l] = d.dout[l]; k.act[l] = d.act[l]; k.wt[l] = a.wt[l]; k.bias[l] = a.bias[l];
   }
   k.out = a.out;
   for (int l = 0; l < 4; ++l) k.save_z[l] = a.save_z[l];
   NGPDE_STAMP_SET(k, kStampEdge, 0);
-  const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + (size_t)kGroups * kTS + (size_t)a.n_tail * kW * kTS + (size_t)kChunk * kTS) * sizeof(float);
-  const int grid = edge_persistent_grid(g, lds + 2048 <= 80 * 1024 ? 64 : 32);   // two workgroups per CU where the LDS allows
   const char *name = "edge_mlp_fused_fwd_kernel";
-  switch (a.n_tail) {
-    case 0: return launch_with_lds(edge_mlp_fused_fwd_kernel<0>, grid, kT, lds, stream, k, name);
-    case 1: return launch_with_lds(edge_mlp_fused_fwd_kernel<1>, grid, kT, lds, stream, k, name);
-    case 2: return launch_with_lds(edge_mlp_fused_fwd_kernel<2>, grid, kT, lds, stream, k, name);
-    default: return launch_with_lds(edge_mlp_fused_fwd_kernel<3>, grid, kT, lds, stream, k, name);
+  switch (p.n_tail) {
+    case 0: return launch_with_lds(edge_mlp_fused_fwd_kernel<0>, p.grid, p.threads, p.lds, stream, k, name);
+    case 1: return launch_with_lds(edge_mlp_fused_fwd_kernel<1>, p.grid, p.threads, p.lds, stream, k, name);
+    case 2: return launch_with_lds(edge_mlp_fused_fwd_kernel<2>, p.grid, p.threads, p.lds, stream, k, name);
+    default: return launch_with_lds(edge_mlp_fused_fwd_kernel<3>, p.grid, p.threads, p.lds, stream, k, name);
   }
 }
 
-static int edge_bwd_grid(const ngpde_graph *g) { return edge_persistent_grid(g, 32); }   // one persistent workgroup per CU
-
-bool edge_mlp_fused_bwd_supported(const ngpde_graph *g, int h1, int n_tail, int dw, int aggr) {
-  if (!g || !g->has_norm || !g->by_t.halo_ok) return false;
-  if (h1 <= 0 || h1 > kW || h1 % 4) return false;
-  if (n_tail < 0 || n_tail > 1) return false;                 // deeper message MLPs take the primitives' pullback
-  if (n_tail == 1 && (dw <= 0 || dw > kW || dw % 4)) return false;
-  return aggr >= NGPDE_AGGR_SUM && aggr <= NGPDE_AGGR_MUL;   // (max / min / * on this kernel only: the 64-wide and deep ones take + / mean)
-}
-
-size_t edge_mlp_fused_bwd_workspace(const ngpde_graph *g, int h1, int n_tail, int dw) {
-  const size_t general = n_tail ? (size_t)edge_bwd_grid(g) * (h1 + 1) * dw * sizeof(float) + 256 : 256;
-  return std::max(general, (h1 == kW && n_tail == 1 && dw == kW) ? edge_mlp64_bwd_workspace(g) : (size_t)0);   // (edge_mlp64.hip)
-}
-
-int32_t launch_edge_mlp_fused_bwd(const ngpde_graph *g, const EdgeMlpBwdArgs &a, hipStream_t stream) {
-  NGPDE_REQUIRE(edge_mlp_fused_bwd_supported(g, a.h1, a.n_tail, a.dw, a.aggr), NGPDE_ERR_UNSUPPORTED,
+int32_t launch_edge_mlp_fused_bwd(const ngpde_graph *g, const EdgeBwd &p, const EdgeMlpBwdArgs &a, hipStream_t stream) {
+  NGPDE_REQUIRE(p.supported, NGPDE_ERR_UNSUPPORTED,
                 "fused edge-MLP pullback needs widths <= 64 and multiples of 4, at most one layer after the first and a graph whose tiles fit "
                 "the LDS halo");
-  if (g->n_nodes == 0) return NGPDE_OK;
-  if (int32_t st = check_workspace("fused edge-MLP pullback", a.workspace, a.workspace_bytes, edge_mlp_fused_bwd_workspace(g, a.h1, a.n_tail, a.dw), 1))
-    return st;
-  if (edge_mlp64_bwd_applicable(g, a)) return launch_edge_mlp64_bwd(g, a, stream);   // (checks dE itself: not needed when it sums by source in the launch)
-  NGPDE_REQUIRE(a.dE != nullptr || g->n_edges == 0, NGPDE_ERR_INVALID_ARGUMENT, "fused edge-MLP pullback: the [E][h1] buffer dE is required");
+  if (!p.launch) return NGPDE_OK;   // no nodes
+  if (int32_t st = check_workspace("fused edge-MLP pullback", a.workspace, a.workspace_bytes, p.workspace_bytes, 1)) return st;
+  NGPDE_REQUIRE(!p.dE_missing, NGPDE_ERR_INVALID_ARGUMENT, "fused edge-MLP pullback: the [E][h1] buffer dE is required");
+  if (p.form == EdgeBwdForm::Edge64) return launch_edge_mlp64_bwd(g, p, a, stream);
+  const EdgeMlpDesc &d = a.d;
+  const EdgeTileGeom t = edge_tile_geom(g);
   EdgeMlpBwdK k;
-  fill_tile_args(g, k);
-  k.h1 = a.h1; k.act1 = a.act1; k.aggr = a.aggr; k.n_tail = a.n_tail;
-  k.dw = a.n_tail ? a.dw : a.h1; k.act2 = a.act2;
-  k.P = a.P; k.Q = a.Q; k.Eterm = a.Eterm; k.wt = a.wt; k.bias = a.bias; k.dout = a.dout;
-  k.dP = a.dP; k.dE = a.dE; k.partial = (float *)a.workspace;
-  const size_t lds = ((size_t)(k.halo_rows + 1) * kTS + 2 * (size_t)kGroups * kTS + (size_t)kChunk * kTS + (a.n_tail ? 2 * (size_t)kW * kTS : 0) +
-                      (a.aggr >= NGPDE_AGGR_MAX ? (size_t)kGroups * kTS : 0)) * sizeof(float);
-  const int grid = edge_bwd_grid(g);
-  int32_t st = a.n_tail ? launch_with_lds(edge_mlp_fused_bwd_kernel<1>, grid, kT, lds, stream, k, "edge_mlp_fused_bwd_kernel")
-                        : launch_with_lds(edge_mlp_fused_bwd_kernel<0>, grid, kT, lds, stream, k, "edge_mlp_fused_bwd_kernel");
+  fill_tile_args(g, t, k);
+  k.h1 = d.h1; k.act1 = d.act1; k.aggr = d.aggr; k.n_tail = d.n_tail;
+  k.dw = d.n_tail ? d.dout[0] : d.h1; k.act2 = d.act[0];
+  k.P = a.P; k.Q = a.Q; k.Eterm = a.Eterm; k.wt = a.wt[0]; k.bias = a.bias[0]; k.dout = a.dout;
+  k.dP = a.dP; k.dE = a.dE;
+  Workspace w(a.workspace);
+  EdgeBwdWs ws;
+  edge_mlp_bwd_layout(w, t, d, p.form, ws);
+  k.partial = ws.partial[0];
+  int32_t st = p.n_tail ? launch_with_lds(edge_mlp_fused_bwd_kernel<1>, p.grid, p.threads, p.lds, stream, k, "edge_mlp_fused_bwd_kernel")
+                        : launch_with_lds(edge_mlp_fused_bwd_kernel<0>, p.grid, p.threads, p.lds, stream, k, "edge_mlp_fused_bwd_kernel");
   if (st) return st;
-  if (a.n_tail && (st = launch_dense_weight_reduce(grid, a.h1, a.dw, k.partial, a.dwt, a.dbias, stream))) return st;
-  if (a.dQ && (st = launch_edge_sum_by_source(g, a.h1, a.dE, a.dQ, stream))) return st;
+  if (p.n_tail && (st = launch_dense_weight_reduce(p.grid, d.h1, d.dout[0], k.partial, a.dwt[0], a.dbias[0], stream))) return st;
+  if (p.by_source && (st = launch_edge_sum_by_source(g, d.h1, a.dE, a.dQ, stream))) return st;
   return NGPDE_OK;
 }
 

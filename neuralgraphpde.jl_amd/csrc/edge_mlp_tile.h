@@ -16,7 +16,7 @@
 namespace ngpde {
 namespace {
 
-constexpr int kW = 64, kTS = kW + 4, kRows = kTileRows;   // widest layer, LDS row stride (floats), rows of a tile
+using namespace edge_mlp;   // kW, kTS, kRows, thread counts and chunk sizes: edge_mlp_forms.h
 
 // Thread shapes: how the 16-lane groups of a workgroup map to the tile's 32 rows and to its halo list.
 struct RowPerGroup {       // 512 threads: group g <-> row g, halo rows g + 32 k
@@ -35,23 +35,11 @@ struct EdgeTileArgs {
   int n_tiles, halo_rows;   // halo_rows: LDS rows of the halo region = the largest halo of this graph's tiles
 };
 
-inline void fill_tile_args(const ngpde_graph *g, EdgeTileArgs &k) {
+inline void fill_tile_args(const ngpde_graph *g, const EdgeTileGeom &t, EdgeTileArgs &k) {
   k.sched = g->by_t.sched; k.halo = g->by_t.halo; k.slots = g->by_t.slots;
-  k.n_tiles = (int)(g->n_sched / kTileRows);
-  k.halo_rows = std::max<int>(kTileRows, std::min<int>(kHaloCap, g->by_t.max_halo));
+  k.n_tiles = t.n_tiles;
+  k.halo_rows = edge_halo_rows(t);
 }
-
-// Persistent workgroups, at most per_xcd_cap per XCD.  EdgeTileRange splits the tiles into 8 per-XCD ranges and lets gridDim.x / 8
-// workgroups walk each: the grid has to be a multiple of 8, or the workgroups beyond the last multiple walk tiles of their XCD a
-// second time (and add their weight gradients twice).
-inline int edge_persistent_grid(const ngpde_graph *g, int per_xcd_cap) {
-  const int n_tiles = (int)(g->n_sched / kTileRows);
-  return 8 * std::max(1, std::min(per_xcd_cap, (n_tiles + 7) / 8));
-}
-
-// one [(din + 1)][dw] weight-gradient slab per workgroup (row din = bias gradient), rounded to 256 bytes
-inline size_t slab_bytes(int grid, int din, int dw) { return round_up256((size_t)grid * (din + 1) * dw * sizeof(float)); }
-inline float *take_slabs(Workspace &w, int grid, int din, int dw) { return reinterpret_cast<float *>(w.take<char>(slab_bytes(grid, din, dw))); }
 
 // more than 64 KB of dynamic LDS has to be requested explicitly
 template <class KERNEL, class ARGS>

@@ -15,6 +15,7 @@ int32_t fail(int32_t code, const char *fmt, ...);   // (common.h) records the me
 
 constexpr size_t kGranule = 256;   // every piece starts on a multiple of this from the base
 inline size_t round_up256(size_t bytes) { return (bytes + (kGranule - 1)) & ~(kGranule - 1); }
+constexpr size_t kWsSlack = 256;   // what the Dense, GAT and message-MLP workspace queries add behind their pieces
 
 // A bump allocator over bytes in 256-byte granules.  Without a base it only measures: take() returns nullptr and advances.
 class Workspace {

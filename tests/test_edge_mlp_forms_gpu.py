@@ -19,10 +19,15 @@ asserts the regime it claims with tile_geometry() and the library's queries, and
 float64 restatement (torch double on the CPU, autograd for the MLP, the aggregation pullback as ngpde.h states it).  Outputs the
 contract says are written are pre-filled with NaN, and so is the workspace.
 
+The halo thresholds (48, 61, 68) are derived from those LDS formulas in tests/edge_mlp_forms_spec.py, the restatement of
+csrc/edge_mlp_forms.h, where every choice above is made; the last test pins the queries' answers to tests/golden/edge_mlp_forms.json.
+
 Tolerances are the suite's: forward 1e-4 * max|ref| + 1e-5, gradients 5e-4 relative.
 """
 import ctypes as C
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -31,16 +36,15 @@ import torch
 from ngpde_amd import _lib
 from ngpde_amd.functional import _int_array, _ptr_array
 import ngpde_amd as ng
+import edge_mlp_forms_spec as S
+# 48 (kDqStride), 61 and 68: derived there from the LDS formulas of csrc/edge_mlp_forms.h
+from edge_mlp_forms_spec import DQ_MAX_HALO, E64_FULL_GRID_MAX_HALO, FWD1_TWO_PER_CU_MAX_HALO, SWITCHES
 from test_mp_gpu import close
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 ROWS, HALO_CAP, SLOT_WIDTH = 32, 96, 32
-DQ_MAX_HALO = 48            # edge_mlp64.hip kDqStride
-E64_FULL_GRID_MAX_HALO = 61  # (halo + 225) * 272 + 4096 <= 80 KB
-FWD1_TWO_PER_CU_MAX_HALO = 68  # general forward, n_tail = 1: (halo + 225) * 272 + 2048 <= 80 KB
 MULTI_TILE = 8 * 64 + 1     # more tiles than any of these grids has workgroups (<= 64 per XCD)
-SWITCHES = ("NGPDE_NO_EDGE64", "NGPDE_EDGE64_NO_DQ")
 E64_PAIRS = [("swish", "swish"), ("swish", "identity"), ("relu", "relu"), ("relu", "identity"), ("tanh", "tanh"),
              ("tanh", "identity")]
 AGGRS = ("+", "mean", "max", "min", "*")
@@ -456,10 +460,8 @@ def test_default_order_handle_geometry(monkeypatch):
     pr.check_backward(pr.backward(), what="default order, general")
 
 
-def test_tiles_beyond_the_halo_cap_or_slot_width_are_refused(monkeypatch):
-    # one tile at 97 rows / one row of 33 entries: every query says 0 and the entries return ERR_UNSUPPORTED (no launch)
-    clear_switches(monkeypatch)
-    lib = _lib.load()
+def refused_graph(why):
+    """ten tiles, one of them at 97 rows ("halo 97") or with one row of 33 entries ("degree 33")"""
     n = 10 * ROWS
 
     def spec97(k, rows, rng):
@@ -471,9 +473,18 @@ def test_tiles_beyond_the_halo_cap_or_slot_width_are_refused(monkeypatch):
             d[7] = 33
         return 4, d
 
-    for spec, why in ((spec97, "halo 97"), (spec33, "degree 33")):
-        s, t, order = tiled_graph(n, spec, seed=11)
-        g = graph(("refused", why), lambda: TileGraph(s, t, n, order))
+    def make():
+        s, t, order = tiled_graph(n, {"halo 97": spec97, "degree 33": spec33}[why], seed=11)
+        return TileGraph(s, t, n, order)
+    return graph(("refused", why), make)
+
+
+def test_tiles_beyond_the_halo_cap_or_slot_width_are_refused(monkeypatch):
+    # one tile at 97 rows / one row of 33 entries: every query says 0 and the entries return ERR_UNSUPPORTED (no launch)
+    clear_switches(monkeypatch)
+    lib = _lib.load()
+    for why in ("halo 97", "degree 33"):
+        g = refused_graph(why)
         assert (g.max_halo == 97) if why == "halo 97" else (g.max_deg == 33 and g.max_halo <= HALO_CAP), why
         assert not g.fits()
         for h1, tail in ((64, [(64, "relu")]), (12, []), (60, [(64, "tanh")]), (4, [(12, "tanh"), (60, "swish")]),
@@ -735,3 +746,86 @@ def test_tile_counts(n_tiles, monkeypatch):
     g = tiles_graph(n_tiles)
     assert_regime(g, g.max_halo, g.max_halo)
     all_forms(g, monkeypatch, f"tiles={n_tiles}", seed=n_tiles)
+
+
+# ---- 6. the queries' answers, pinned to the build before csrc/edge_mlp_forms.h ----------------------------------------------------
+
+FORMS_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "edge_mlp_forms.json")
+QUERY_HALOS = sorted({ROWS, DQ_MAX_HALO, DQ_MAX_HALO + 1, HALO_CAP} | {b + k for b in S.TWO_PER_CU_BOUNDS for k in (0, 1)})
+QUERY_CONFIGS = {"e64 swish-identity": (64, "swish", [(64, "identity")]), "e64 relu-relu": (64, "relu", [(64, "relu")]),
+                 "64-64 gelu-gelu": (64, "gelu", [(64, "gelu")])}
+QUERY_CONFIGS.update({f"fwd {k}": v for k, v in FWD_CONFIGS.items()})
+QUERY_CONFIGS.update({f"pullback {k}": v for k, v in PULLBACK_CONFIGS.items()})
+QUERY_CONFIGS.update({f"deep {k}": v for k, v in DEEP_CONFIGS.items()})
+QUERY_SETTINGS = [None] + [(name, "1") for name in SWITCHES if name != S.DEEP_EDGE_BWD] + [(S.DEEP_EDGE_BWD, "0"), (S.DEEP_EDGE_BWD, "1")]
+SWITCHED_GRAPHS = (f"halo{DQ_MAX_HALO}", f"halo{E64_FULL_GRID_MAX_HALO + 1}")          # each switch alone, on these two
+
+
+def query_graphs():
+    gs = {f"halo{H}": halo_graph(H) for H in QUERY_HALOS}
+    gs["halo97"] = refused_graph("halo 97")
+    gs[f"tiles{MULTI_TILE}"] = halo_graph(DQ_MAX_HALO, n_tiles=MULTI_TILE, ragged=3)
+    return gs
+
+
+def layer_descriptor(kind, aggr, h1, act1, tail, x, ef, wt):
+    """ExplicitEdgeConv on one 8-wide state block, or MPPDEConv with 3 edge features and a one-layer update; the size query reads
+    the widths and tests the pointers for NULL"""
+    d = _lib.EdgeLayer()
+    d.kind, d.aggr, d.n_state = kind, _lib.AGGR[aggr], 1
+    d.state[0], d.state_width[0] = x.data_ptr(), 8
+    dims = [16, h1] + [w for w, _ in tail]
+    if kind == _lib.LAYER_MPPDE:
+        d.edge_feat, d.edge_feat_width = ef.data_ptr(), 3
+        dims[0] += 3
+        d.update.n_layers = 1
+        d.update.dims[0], d.update.dims[1] = 8 + dims[-1], 8
+        d.update.weight[0] = wt.data_ptr()
+    d.phi.n_layers = len(dims) - 1
+    for l, w in enumerate(dims):
+        d.phi.dims[l] = w
+    for l, a in enumerate([act1] + [a for _, a in tail]):
+        d.phi.act[l] = _lib.ACT[a]
+        d.phi.weight[l] = wt.data_ptr()
+    return d
+
+
+def query_answers(monkeypatch):
+    """[graph, switch setting, configuration, answers] of the five queries (ngpde_edge_layer_workspace_bytes for two layer kinds, two
+    aggregations, inference and training), as the library answers now"""
+    lib = _lib.load()
+    wt = torch.zeros(4096, device=DEV)
+    rows = []
+    for gname, g in query_graphs().items():
+        x, ef = torch.zeros(g.n, 8, device=DEV), torch.zeros(max(g.E, 1), 3, device=DEV)
+        for setting in QUERY_SETTINGS if gname in SWITCHED_GRAPHS else QUERY_SETTINGS[:1]:
+            clear_switches(monkeypatch)
+            if setting:
+                monkeypatch.setenv(*setting)
+            for cname, (h1, act1, tail) in QUERY_CONFIGS.items():
+                n_tail = len(tail)
+                douts = _int_array([w for w, _ in tail]) if tail else None
+                acts = _int_array([_lib.ACT[a] for _, a in tail]) if tail else None
+                ans = {"supported": int(lib.ngpde_edge_mlp_supported(g.ptr, h1, n_tail, douts)),
+                       "backward_supported": [int(lib.ngpde_edge_mlp_backward_supported(g.ptr, h1, n_tail, douts, _lib.AGGR[a])) for a in AGGRS],
+                       "needs_edge_buffer": [int(lib.ngpde_edge_mlp_backward_needs_edge_buffer(g.ptr, h1, _lib.ACT[act1], e, n_tail, douts, acts,
+                                                                                                _lib.AGGR[a])) for e in (0, 1) for a in ("+", "max")],
+                       "backward_workspace_bytes": int(lib.ngpde_edge_mlp_backward_workspace_bytes(g.ptr, h1, n_tail, douts)),
+                       "layer_workspace_bytes": [int(lib.ngpde_edge_layer_workspace_bytes(
+                           g.ptr, C.byref(layer_descriptor(kind, a, h1, act1, tail, x, ef, wt)), training))
+                           for kind in (_lib.LAYER_EDGECONV, _lib.LAYER_MPPDE) for a in ("+", "max") for training in (0, 1)]}
+                rows.append([gname, "=".join(setting) if setting else "", cname, ans])
+    clear_switches(monkeypatch)
+    return rows
+
+
+def test_queries_answer_what_the_build_before_the_forms_header_answered(monkeypatch):
+    # which kernel runs never shows in a float64 comparison; what the ABI queries say about it does.  tests/golden/edge_mlp_forms.json
+    # holds their answers from the library as it was before the choices moved into csrc/edge_mlp_forms.h (the field "recorded_from"
+    # names the commit), on graphs at every halo threshold, one beyond the cap and one of 513 tiles, each switch alone.  No kernel of
+    # the family is launched here.
+    want = json.load(open(FORMS_GOLDEN))
+    got = query_answers(monkeypatch)
+    assert len(got) == len(want["rows"]) and {r[1] for r in got} == {""} | {"=".join(s) for s in QUERY_SETTINGS[1:]}
+    wrong = [(g, w) for g, w in zip(got, want["rows"]) if g != w]
+    assert not wrong, f"{len(wrong)} of {len(got)} rows differ (now, recorded): {wrong[:4]}"

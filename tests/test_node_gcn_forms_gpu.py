@@ -20,7 +20,7 @@ restated:
   A batch of `members` same-structure graphs (create_batch) runs mode 1 with relu only, two members per workgroup on
   node_*_persistent2_kernel<.., PAIR = false>, an odd last member alone; NGPDE_NO_INTERLEAVE=1: member after member on the one-tile
   kernels (node.hip:514).
-The caps: kHaloCap = 96 staged rows and kSlotWidth = 32 list entries per row (common.h:82, :83) in both directions, or the handle is
+The caps: kHaloCap = 96 staged rows and kSlotWidth = 32 list entries per row (csrc/edge_mlp_forms.h) in both directions, or the handle is
 not halo_ok; kNbrStride - 1 = 63 tiles in a wait list (persistent_sync.h:19; build_wait_lists, persistent_plan.hip:50), or
 node_persistent_setup returns NGPDE_ERR_UNSUPPORTED and node_create keeps the pre-scaled replayed plan (node.hip:481).  The self
 loop is not a list entry (the kernels add the own row after the slots, persistent_gcn_tile.h:231), so a row at the slot cap has 32
