@@ -16,6 +16,11 @@
  *   - `stream` is a hipStream_t (NULL = the default stream).  Forward/backward calls only enqueue
  *     work; they never allocate, free or synchronise (graph-capture safe).  Handle creation is
  *     synchronous.
+ *   - Creates.  A create call that has no stream parameter (ngpde_node_gcn2_create*, ngpde_node_gat_create*,
+ *     ngpde_node_vmh_create, ngpde_ode_create) does its device work on the NULL stream, which is NOT ordered with
+ *     streams created hipStreamNonBlocking (torch's, AMDGPU.jl's).  Device arrays passed to such a call (`pos`) must
+ *     therefore be complete when it is called -- synchronise the stream that produces them first -- and the call
+ *     returns with its own device work complete: the plan may be used on any stream at once.
  *   - The library keeps no hidden parameter state: parameters and inputs are passed on every call,
  *     as in Lux's `y, st = layer(x, ps, st)` (src/layers.jl:200, :94, :312, :390, :509).  The only
  *     cached object is the derived-graph handle, whose life is tied to the GNNGraph in `st.graph`.

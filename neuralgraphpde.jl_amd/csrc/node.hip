@@ -561,6 +561,9 @@ static int32_t node_create(const ngpde_graph_t *g, int32_t members, int32_t d, i
     NGPDE_TRY(capture(p.get(), false));
     if (p->with_bwd) NGPDE_TRY(capture(p.get(), true));
   }
+  // the zeroed parameter padding of a widened plan and node_persistent_setup's memsets are NULL-stream work that may return ahead of its
+  // completion; the solves run on the caller's streams, which the NULL stream does not order (include/ngpde.h, "Creates")
+  NGPDE_HIP_CHECK(hipStreamSynchronize(nullptr));
   *out = p.release();
   return NGPDE_OK;
 }

@@ -68,6 +68,7 @@ int32_t ngpde_node_gat_create_batch(const ngpde_graph_t *g, int32_t members, int
   }
   NGPDE_HIP_CHECK(hipMemcpy(p->cf, cf.data(), cf.size() * 4, hipMemcpyHostToDevice));
   NGPDE_HIP_CHECK(hipMemcpy(p->cb, cb.data(), cb.size() * 4, hipMemcpyHostToDevice));
+  NGPDE_HIP_CHECK(hipStreamSynchronize(nullptr));   // (node_persistent_setup's memsets: include/ngpde.h, "Creates")
   *out = p.release();
   return NGPDE_OK;
 }

@@ -136,6 +136,9 @@ static int32_t vmh_build(ngpde_node_vmh *p, const float *pos, int tableau, doubl
   }
   NGPDE_HIP_CHECK(hipMemcpy(p->cf, cf, sizeof cf, hipMemcpyHostToDevice));
   NGPDE_HIP_CHECK(hipMemcpy(p->cb, cb, sizeof cb, hipMemcpyHostToDevice));
+  // the copy of pos and the zeroing above are NULL-stream work a device-to-device hipMemcpy / hipMemset may return ahead of: the solves run
+  // on the caller's streams, which the NULL stream does not order (include/ngpde.h, "Creates")
+  NGPDE_HIP_CHECK(hipStreamSynchronize(nullptr));
   return NGPDE_OK;
 }
 

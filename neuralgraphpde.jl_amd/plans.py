@@ -218,6 +218,10 @@ class _OdePlan(_ResidentPlan):
         self.kind = kind
         self.n_first, self.n_steps = int(desc.n_phi), int(desc.n_steps)
         out, fl = C.c_void_p(), C.c_int32()
+        if desc.pos:
+            # the create has no stream parameter and copies `pos` on the NULL stream, which is not ordered with torch's streams: the
+            # kernels that produce the array on the current stream have to be complete (creation is never inside a capture)
+            torch.cuda.current_stream().synchronize()
         _lib.check(self.lib.ngpde_ode_create(handle.ptr, C.byref(desc), C.byref(out), C.byref(fl)))
         self.ptr, self._flags = out, fl.value
 
