@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gno_forms.h"
 #include "switches.h"
 
 using namespace ngpde;
@@ -337,13 +338,9 @@ __global__ void inv_in_degree_kernel(int n, const int32_t *__restrict__ rowptr, 
   if (i < n) inv[i] = 1.0f / fmaxf((float)(rowptr[i + 1] - rowptr[i]), 1.0f);
 }
 
-struct GnoPlan {
+struct GnoPlan : GnoLayerForm {   // the form (gno_forms.h: reassoc, has_b2, fused_msg, fused_agg, gform, n_mid, nsplit) and its workspace
   int64_t N = 0, E = 0;
   int cin = 0, cout = 0, ds = 0, de = 0, h1 = 0, L = 0, kdim = 0, aggr = 1, act = 0, act1 = 0;
-  bool reassoc = false, fused_msg = false, fused_agg = false, has_b2 = false;
-  bool gform = false;      // aggregate-then-transform (gno_gform.hip): no [E][out] message, no T in the forward
-  int nsplit = 1;
-  int n_mid = 0;           // Dense layers of phi evaluated on [E] rows by the primitives (reassociated: 1 .. L - 2; literal: 1 .. L - 1)
   RowSpec rows;
   // forward region
   float *wa = nullptr, *wb = nullptr, *wd = nullptr, *wr = nullptr, *P = nullptr, *Q = nullptr, *Et = nullptr, *Bh = nullptr, *Wh = nullptr,
@@ -381,16 +378,7 @@ int32_t make_gno_plan(const ngpde_graph *g, const ngpde_gno_layer_t &L, bool tra
   if (p.de) p.rows.block(o++, p.de, {{2 * p.ds, 1.f}});
   p.rows.n_out = o;
   p.kdim = phi.dims[p.L - 1];
-  p.reassoc = p.L >= 2 && phi.act[p.L - 1] == NGPDE_ACT_IDENTITY && !switch_on(Switch::GnoMaterialize) &&
-              ngpde_gno_apply_supported(p.cout, p.kdim) == 1;
-  p.has_b2 = p.reassoc && phi.bias[p.L - 1] != nullptr;
-  p.fused_msg = p.reassoc && p.L == 2 && p.E > 0 && !switch_on(Switch::NoGnoMfma) && (p.act1 == NGPDE_ACT_IDENTITY || p.act1 == NGPDE_ACT_RELU) &&
-                ngpde_gno_message_supported(p.cout, p.kdim) == 1;
-  p.fused_agg = p.fused_msg && (p.aggr == NGPDE_AGGR_SUM || p.aggr == NGPDE_AGGR_MEAN);
-  // the edge index contracted first, per target: the forward needs neither T nor the [E][out] message (the pullback keeps the
-  // by-source form and makes its own T)
-  p.gform = p.fused_agg && ngpde_gno_gform_preferred(p.N, p.E, p.cin, p.kdim, p.cout, training ? 1 : 0) == 1;
-  p.n_mid = p.fused_msg ? 0 : (p.reassoc ? p.L - 2 : p.L - 1);
+  static_cast<GnoLayerForm &>(p) = gno_layer_form(p.N, p.E, p.cin, p.cout, p.L, p.kdim, p.act1, phi.act[p.L - 1], phi.bias[p.L - 1] != nullptr, p.aggr, training);
   const size_t N = (size_t)p.N, E = (size_t)p.E;
   const size_t msg_w = (size_t)p.cout;
   for (int l = 0; l < kMaxL; ++l) p.ty[l] = p.tz[l] = nullptr;
@@ -409,7 +397,6 @@ int32_t make_gno_plan(const ngpde_graph *g, const ngpde_gno_layer_t &L, bool tra
   if (p.gform) {
     p.G = a.take<float>(N * p.cin * p.kdim);
     if (p.has_b2) p.hs = a.take<float>(N * p.cin);
-    p.nsplit = ngpde_gno_gform_splits(p.N, p.cin, p.kdim, p.cout);
     p.slabs = a.take<float>((size_t)(p.nsplit + 2) * N * p.cout);   // + the b2 term and W h, formed in the same launch
   } else {
     p.Wh = a.take<float>(N * p.cout);
@@ -481,7 +468,7 @@ uint64_t gno_plan_key(const ngpde_graph *g, const GnoPlan &p) {
   uint64_t h = mix(0x676e6f00u, (uint64_t)(uintptr_t)g);
   h = mix(h, (uint64_t)p.N); h = mix(h, (uint64_t)p.E); h = mix(h, ((uint64_t)p.cin << 32) | (uint64_t)p.cout);
   h = mix(h, ((uint64_t)p.kdim << 32) | (uint64_t)(p.L * 64 + p.aggr * 8 + p.act1));
-  h = mix(h, (uint64_t)p.reassoc | (uint64_t)p.fused_msg << 1 | (uint64_t)p.fused_agg << 2 | (uint64_t)p.has_b2 << 3 | (uint64_t)p.gform << 4 | (uint64_t)p.nsplit << 8);
+  h = mix(h, p.bits());
   return mix(h, (uint64_t)p.total_floats);
 }
 

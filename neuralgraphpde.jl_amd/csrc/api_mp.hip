@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "gno_forms.h"
 
 using namespace ngpde;
 
@@ -291,14 +292,16 @@ int32_t ngpde_gno_contract_backward(const ngpde_graph_t *g, int32_t cin, int32_t
   return NGPDE_OK;
 }
 
-int32_t ngpde_gno_apply_supported(int32_t cout, int32_t kdim) { return gno_apply_supported(cout, kdim) ? 1 : 0; }
+// (the VALU envelope, also where the matrix-pipe kernel runs the shape: GnoApplyForm::apply_entry)
+int32_t ngpde_gno_apply_supported(int32_t cout, int32_t kdim) { return gno_apply_form(cout, kdim).apply_entry ? 1 : 0; }
 
 int32_t ngpde_gno_apply_forward(const ngpde_graph_t *g, int32_t cout, int32_t kdim, const float *t, const float *bh,
                                 const float *z, float *m, ngpde_stream_t stream) {
   NGPDE_RANGE();
   NGPDE_REQUIRE(g != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_apply_forward: graph is NULL");
-  NGPDE_REQUIRE(gno_apply_supported(cout, kdim), NGPDE_ERR_UNSUPPORTED,
-                "ngpde_gno_apply_forward: out = %d, k = %d outside the reassociated path (out, k <= 256; T_j [k][out] must fit 60 KB of LDS)", cout, kdim);
+  NGPDE_REQUIRE(gno_apply_form(cout, kdim).apply_entry, NGPDE_ERR_UNSUPPORTED,
+                "ngpde_gno_apply_forward: out = %d, k = %d outside the reassociated path (the register-tile kernels' envelope, whichever kernel would "
+                "run: out, k <= 256, their pullback's LDS within 60 KB)", cout, kdim);
   if (g->n_edges == 0) return NGPDE_OK;
   NGPDE_REQUIRE(t && z && m, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_apply_forward: NULL argument");
   return launch_gno_apply_fwd(g, cout, kdim, t, bh, z, m, (hipStream_t)stream);
@@ -308,7 +311,7 @@ int32_t ngpde_gno_apply_backward(const ngpde_graph_t *g, int32_t cout, int32_t k
                                  const float *dm, float *dt, float *dbh, float *dz, ngpde_stream_t stream) {
   NGPDE_RANGE();
   NGPDE_REQUIRE(g != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_apply_backward: graph is NULL");
-  NGPDE_REQUIRE(gno_apply_supported(cout, kdim), NGPDE_ERR_UNSUPPORTED, "ngpde_gno_apply_backward: unsupported out = %d, k = %d", cout, kdim);
+  NGPDE_REQUIRE(gno_apply_form(cout, kdim).apply_entry, NGPDE_ERR_UNSUPPORTED, "ngpde_gno_apply_backward: unsupported out = %d, k = %d", cout, kdim);
   if (g->n_nodes == 0) return NGPDE_OK;
   NGPDE_REQUIRE(t && (g->n_edges == 0 || (z && dm)), NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_apply_backward: NULL argument");
   return launch_gno_apply_bwd(g, cout, kdim, t, z, dm, dt, dbh, dz, (hipStream_t)stream);
@@ -325,7 +328,7 @@ int32_t ngpde_gno_message_backward_from_nodes(const ngpde_graph_t *g, int32_t co
   NGPDE_REQUIRE(aggr == NGPDE_AGGR_SUM || aggr == NGPDE_AGGR_MEAN, NGPDE_ERR_UNSUPPORTED,
                 "ngpde_gno_message_backward_from_nodes: aggregation %d has no node-level form (sum and mean do); use "
                 "ngpde_segment_reduce_backward + ngpde_gno_apply_backward", aggr);
-  NGPDE_REQUIRE(gno_apply_mfma_supported(cout, kdim), NGPDE_ERR_UNSUPPORTED,
+  NGPDE_REQUIRE(gno_apply_form(cout, kdim).message_entry, NGPDE_ERR_UNSUPPORTED,
                 "ngpde_gno_message_backward_from_nodes: needs out a multiple of 16 (<= 256) and k in {16, 32, 64}, got out = %d, k = %d",
                 cout, kdim);
   if (g->n_nodes == 0) return NGPDE_OK;
@@ -335,7 +338,7 @@ int32_t ngpde_gno_message_backward_from_nodes(const ngpde_graph_t *g, int32_t co
                                    act1, dq);
 }
 
-int32_t ngpde_gno_message_supported(int32_t cout, int32_t kdim) { return gno_apply_mfma_supported(cout, kdim) ? 1 : 0; }
+int32_t ngpde_gno_message_supported(int32_t cout, int32_t kdim) { return gno_apply_form(cout, kdim).message_entry ? 1 : 0; }
 
 int32_t ngpde_gno_message_forward(const ngpde_graph_t *g, int32_t cout, int32_t kdim, int32_t act1, const float *p_target,
                                   const float *q_source, const float *e_term, const float *t, const float *bh, float *z_out, float *m,
@@ -344,7 +347,7 @@ int32_t ngpde_gno_message_forward(const ngpde_graph_t *g, int32_t cout, int32_t 
   NGPDE_REQUIRE(g != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_message_forward: graph is NULL");
   int32_t st = check_act("ngpde_gno_message_forward", act1);
   if (st) return st;
-  NGPDE_REQUIRE(gno_apply_mfma_supported(cout, kdim), NGPDE_ERR_UNSUPPORTED,
+  NGPDE_REQUIRE(gno_apply_form(cout, kdim).message_entry, NGPDE_ERR_UNSUPPORTED,
                 "ngpde_gno_message_forward: needs out a multiple of 16 (<= 256) and k in {16, 32, 64}, got out = %d, k = %d; compose "
                 "ngpde_edge_combine_forward + ngpde_gno_apply_forward", cout, kdim);
   if (g->n_edges == 0) return NGPDE_OK;

@@ -449,12 +449,11 @@ int32_t launch_gno_contract_fwd(const ngpde_graph *g, int cin, int cout, const f
                                 hipStream_t stream);
 int32_t launch_gno_contract_bwd(const ngpde_graph *g, int cin, int cout, const float *K, const float *h, const float *dm,
                                 float *dK, float *dhe, hipStream_t stream);
-bool gno_apply_supported(int cout, int kdim);
 int32_t launch_gno_apply_fwd(const ngpde_graph *g, int cout, int kdim, const float *T, const float *Bh, const float *z,
                              float *m, hipStream_t stream);
 int32_t launch_gno_apply_bwd(const ngpde_graph *g, int cout, int kdim, const float *T, const float *z, const float *dm,
                              float *dT, float *dBh, float *dz, hipStream_t stream);
-bool gno_apply_mfma_supported(int cout, int kdim);   // gno_mfma.hip: the same message on the matrix pipe
+// gno_mfma.hip: the same message on the matrix pipe (which of the two runs: gno_apply_form in gno_forms.h)
 int32_t launch_gno_apply_mfma_fwd(const ngpde_graph *g, int cout, int kdim, const float *T, const float *Bh, const float *z, float *m,
                                   hipStream_t stream);
 int32_t launch_gno_message_mfma_fwd(const ngpde_graph *g, int cout, int kdim, int act1, const float *P, const float *Q, const float *E,

@@ -16,13 +16,10 @@
 // One workgroup (4 waves) per target; edges in chunks of 32: rows of h and Q go memory -> registers a chunk ahead, z is formed on the
 // way into LDS (and kept in z_out [E][k], p order, for the pullback), wave w owns G_i's rows 16 w .. 16 w + 15 (all `in` columns).
 // Shapes: k = 64, in in {32, 64, 128}; anything else keeps the by-source form.
-#include <algorithm>
-#include <cstdlib>
-
 #include "common.h"
 #include "device_utils.h"
+#include "gno_forms.h"
 #include "persistent_mem.h"
-#include "switches.h"
 
 namespace ngpde {
 
@@ -34,8 +31,7 @@ int32_t launch_gemm128_split_nn(int M, int N, int K, int nsplit, const float *A,
 
 namespace {
 
-constexpr int kGK = 64;    // k (width of phi's hidden layer)
-
+// (kGK = 64, the width of phi's hidden layer: gno_forms.h)
 // GC: edges per chunk.  The launch is bound by how many workgroups a CU holds (a target's prologue -- row pointers, sources, the first
 // rows: three dependent memory round trips -- and its 32 KB epilogue run no matrix instruction): 16-edge chunks and a two-tile
 // epilogue patch keep a workgroup at 14 KB of LDS, eight workgroups per CU (the wave limit) instead of five at 32 edges.
@@ -241,69 +237,41 @@ using namespace ngpde;
 
 extern "C" {
 
-int32_t ngpde_gno_gform_supported(int32_t in_chs, int32_t kdim) {
-  return (!switch_on(Switch::NoGnoGform) && kdim == kGK && (in_chs == 32 || in_chs == 64 || in_chs == 128)) ? 1 : 0;
-}
+// the three queries: gno_forms.h (act1 does not bear on their answers)
+int32_t ngpde_gno_gform_supported(int32_t in_chs, int32_t kdim) { return gno_gform_supported(in_chs, kdim) ? 1 : 0; }
 
 int32_t ngpde_gno_gform_preferred(int64_t n_nodes, int64_t n_edges, int32_t in_chs, int32_t kdim, int32_t cout, int32_t training) {
-  // Inference: always (config 5: 0.279 -> 0.200 ms at radius 0.1, 0.191 -> 0.147 ms at 0.05).  Training: the pullback stays in the
-  // by-source form and needs T = W2 (x) h, which only that form's forward leaves behind -- one more node-level product (86 us at
-  // config 5) that this form's forward must win back on the edges: it does from about 64 edges per node (radius 0.1, 117 per node:
-  // forward + backward 0.895 -> 0.861 ms; radius 0.05, 34 per node: 0.623 -> 0.657 ms, so not there).
-  if (ngpde_gno_gform_supported(in_chs, kdim) != 1 || cout % 4 != 0 || n_edges <= 0) return 0;
-  if ((uint64_t)n_nodes * (uint64_t)std::max(in_chs, kGK) * 4u >= (1ull << 32)) return 0;   // (h and Q rows: 32-bit byte offsets)
-  return (!training || n_edges >= 64 * n_nodes) ? 1 : 0;
+  return gno_gform_form(n_nodes, n_edges, in_chs, kdim, cout, 0, training != 0).preferred ? 1 : 0;
 }
 
-int32_t ngpde_gno_gform_splits(int64_t n_nodes, int32_t in_chs, int32_t kdim, int32_t cout) {
-  // enough workgroups for two per CU; every split a multiple of 16 of the contraction
-  const int64_t tiles = ((n_nodes + 127) / 128) * ((cout + 127) / 128);
-  const int K = in_chs * kdim;
-  int ns = (int)std::max<int64_t>(1, (512 + tiles - 1) / std::max<int64_t>(tiles, 1));
-  ns = std::min(ns, std::max(1, K / 256));
-  return std::min(ns, 32);
-}
+int32_t ngpde_gno_gform_splits(int64_t n_nodes, int32_t in_chs, int32_t kdim, int32_t cout) { return gno_gform_splits(n_nodes, in_chs, kdim, cout); }
 
 int32_t ngpde_gno_gform_aggregate(const ngpde_graph_t *g, int32_t in_chs, int32_t kdim, int32_t act1, int32_t mean, const float *p_target,
                                   const float *q_source, const float *e_term, const float *h, float *gout, float *hsum, float *z_out,
                                   ngpde_stream_t stream) {
   NGPDE_REQUIRE(g != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_gform_aggregate: graph is NULL");
-  NGPDE_REQUIRE(ngpde_gno_gform_supported(in_chs, kdim) == 1, NGPDE_ERR_UNSUPPORTED,
-                "ngpde_gno_gform_aggregate: needs k = 64 and in in {32, 64, 128}, got in = %d, k = %d", in_chs, kdim);
+  const GnoGform f = gno_gform_form(g->n_nodes, g->n_edges, in_chs, kdim, 0, act1, false);
+  NGPDE_REQUIRE(f.supported, NGPDE_ERR_UNSUPPORTED, "ngpde_gno_gform_aggregate: needs k = 64 and in in {32, 64, 128}, got in = %d, k = %d", in_chs, kdim);
   NGPDE_REQUIRE(act1 >= NGPDE_ACT_IDENTITY && act1 <= NGPDE_ACT_SOFTPLUS, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_gform_aggregate: unknown activation %d", act1);
   if (g->n_nodes == 0) return NGPDE_OK;
   NGPDE_REQUIRE(h && gout && (p_target || q_source || e_term), NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_gform_aggregate: NULL argument");
-  NGPDE_REQUIRE((uint64_t)g->n_nodes * (uint64_t)std::max(in_chs, kGK) * 4u < (1ull << 32), NGPDE_ERR_UNSUPPORTED,
-                "ngpde_gno_gform_aggregate: h or Q beyond 4 GB (rows are fetched with 32-bit offsets)");
+  NGPDE_REQUIRE(f.rows_ok, NGPDE_ERR_UNSUPPORTED, "ngpde_gno_gform_aggregate: h or Q beyond 4 GB (rows are fetched with 32-bit offsets)");
   NGPDE_REQUIRE(((reinterpret_cast<uintptr_t>(p_target) | reinterpret_cast<uintptr_t>(q_source) | reinterpret_cast<uintptr_t>(e_term) | reinterpret_cast<uintptr_t>(h) |
                   reinterpret_cast<uintptr_t>(gout) | reinterpret_cast<uintptr_t>(hsum) | reinterpret_cast<uintptr_t>(z_out)) & 15) == 0,
                 NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gno_gform_aggregate: every array must be 16-byte aligned");
   GFormArgs a;
   a.rowptr_t = g->by_t.rowptr; a.col_t = g->by_t.col;
   a.P = p_target; a.Q = q_source; a.Et = e_term; a.h = h; a.G = gout; a.hsum = hsum; a.z_out = z_out; a.act1 = act1; a.mean = mean ? 1 : 0;
-  const dim3 grid((unsigned)g->n_nodes), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  // edges per chunk (A/B runs): NGPDE_GNO_GFORM_CHUNK=16; unset or any other value means 32
-  const char *chunk_env = switch_text(Switch::GnoGformChunk);
-  const int chunk = chunk_env && std::atoi(chunk_env) == 16 ? 16 : 32;
-#define NGPDE_GF2(CC, AA)                                                                         \
-  do {                                                                                            \
-    if (chunk == 16) hipLaunchKernelGGL((gno_gform_fwd_kernel<CC, 16, AA>), grid, block, 0, s, a); \
-    else hipLaunchKernelGGL((gno_gform_fwd_kernel<CC, 32, AA>), grid, block, 0, s, a);             \
-  } while (0)
-#define NGPDE_GF(CC)                                              \
-  do {                                                            \
-    if (act1 == NGPDE_ACT_RELU) NGPDE_GF2(CC, NGPDE_ACT_RELU);    \
-    else if (act1 == NGPDE_ACT_IDENTITY) NGPDE_GF2(CC, NGPDE_ACT_IDENTITY); \
-    else NGPDE_GF2(CC, -1);                                       \
-  } while (0)
-  switch (in_chs) {
-    case 32: NGPDE_GF(32); break;
-    case 64: NGPDE_GF(64); break;
-    default: NGPDE_GF(128); break;
-  }
-#undef NGPDE_GF
-#undef NGPDE_GF2
+  // in x edges per chunk x act1 (relu and identity instantiated, anything else read at run time: -1)
+  const int act_arg = f.act1 == GnoAct1::Relu ? (int)NGPDE_ACT_RELU : f.act1 == GnoAct1::Identity ? (int)NGPDE_ACT_IDENTITY : -1;
+  gno_pick<32, 64, 128>(in_chs, [&](auto cin) {
+    gno_pick<kGformChunkAlt, kGformChunk>(f.chunk, [&](auto chunk) {
+      gno_pick<NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY, -1>(act_arg, [&](auto act) {
+        hipLaunchKernelGGL((gno_gform_fwd_kernel<decltype(cin)::value, decltype(chunk)::value, decltype(act)::value>), dim3((unsigned)g->n_nodes),
+                           dim3(kGnoThreads), 0, (hipStream_t)stream, a);
+      });
+    });
+  });
   NGPDE_LAUNCH_CHECK("gno_gform_fwd_kernel");
   return NGPDE_OK;
 }

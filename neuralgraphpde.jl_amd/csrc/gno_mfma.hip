@@ -10,20 +10,15 @@
 // index contracted, accumulators in registers over the node's edge tiles),  dBh_j = sum_e dm_e.
 // Used when out is a multiple of 16 (<= 256) and k is 16, 32 or 64; other shapes keep the register-tile kernels of
 // mp_kernels.hip.  No atomics; every output row has one writer.
-#include <algorithm>
-#include <cstdlib>
-
 #include "common.h"
 #include "device_utils.h"
-#include "switches.h"
+#include "gno_forms.h"
 
 namespace ngpde {
 
 namespace {
 
-constexpr int kET = 16;      // edges per MFMA tile
-constexpr int kEB = 64;      // edges staged per pass of the forward (4 tiles)
-constexpr int kEBb = 32;     // ... of the pullback (z and dm rows: 25 KB at 128 x 64)
+// (kET edges per MFMA tile, kEB / kEBb edges staged per pass of the forward / the pullback: gno_forms.h)
 
 // rows of a per-edge array ([E][w], p order) of the edges q0 .. q0 + nb of the source's list -> LDS [kEB][w + 4], zero rows
 // beyond nb; 16-byte loads (w % 4 == 0)
@@ -319,83 +314,46 @@ __global__ __launch_bounds__(256, NOB == 8 ? 4 : 2) void gno_apply_mfma_bwd_kern
   }
 }
 
-inline size_t gno_mfma_bwd_lds(int cout, int kdim) { return (size_t)(kEBb * (kdim + 4) + kEBb * (cout + 4)) * sizeof(float); }
+// the forward for the k of the call (the callers have asked gno_apply_form: k is 16, 32 or 64); FUSED: fz forms the per-edge input
+template <bool FUSED>
+int32_t launch_fwd(const ngpde_graph *g, int cout, int kdim, const float *T, const float *Bh, const float *z, float *m, const GnoFuse &fz,
+                   hipStream_t stream) {
+  if (g->n_edges == 0) return NGPDE_OK;
+  gno_pick<16, 32, 64>(kdim, [&](auto kd) {
+    hipLaunchKernelGGL((gno_apply_mfma_fwd_kernel<decltype(kd)::value, FUSED>), dim3((unsigned)g->n_nodes), dim3(kGnoThreads), 0, stream, cout,
+                       g->by_s.rowptr, g->by_s.xpos, T, Bh, z, m, fz);
+  });
+  NGPDE_LAUNCH_CHECK(FUSED ? "gno_apply_mfma_fwd_kernel (fused input)" : "gno_apply_mfma_fwd_kernel");
+  return NGPDE_OK;
+}
 
 }  // namespace
 
-bool gno_apply_mfma_supported(int cout, int kdim) {
-  return !switch_on(Switch::NoGnoMfma) && cout % 16 == 0 && cout >= 16 && cout <= 256 && (kdim == 16 || kdim == 32 || kdim == 64) &&
-         gno_mfma_bwd_lds(cout, kdim) <= 150 * 1024;
-}
-
 int32_t launch_gno_apply_mfma_fwd(const ngpde_graph *g, int cout, int kdim, const float *T, const float *Bh, const float *z, float *m,
                                   hipStream_t stream) {
-  if (g->n_edges == 0) return NGPDE_OK;
-  const dim3 grid((unsigned)g->n_nodes), block(256);
-  const GnoFuse nofuse{};
-#define NGPDE_GNO_F(KK) hipLaunchKernelGGL((gno_apply_mfma_fwd_kernel<KK, false>), grid, block, 0, stream, cout, g->by_s.rowptr, g->by_s.xpos, T, Bh, z, m, nofuse)
-  switch (kdim) {
-    case 16: NGPDE_GNO_F(16); break;
-    case 32: NGPDE_GNO_F(32); break;
-    default: NGPDE_GNO_F(64); break;
-  }
-#undef NGPDE_GNO_F
-  NGPDE_LAUNCH_CHECK("gno_apply_mfma_fwd_kernel");
-  return NGPDE_OK;
+  return launch_fwd<false>(g, cout, kdim, T, Bh, z, m, GnoFuse{}, stream);
 }
 
 // the same with the message's per-edge input formed in the kernel: z_e = act1(P[t_e] + Q[s_e] + E_e)
 int32_t launch_gno_message_mfma_fwd(const ngpde_graph *g, int cout, int kdim, int act1, const float *P, const float *Q, const float *E,
                                     const float *T, const float *Bh, float *z_out, float *m, hipStream_t stream) {
-  if (g->n_edges == 0) return NGPDE_OK;
-  const dim3 grid((unsigned)g->n_nodes), block(256);
-  GnoFuse fz;
-  fz.P = P; fz.Q = Q; fz.E = E; fz.col_s = g->by_s.col; fz.z_out = z_out; fz.act1 = act1;
-#define NGPDE_GNO_FF(KK) hipLaunchKernelGGL((gno_apply_mfma_fwd_kernel<KK, true>), grid, block, 0, stream, cout, g->by_s.rowptr, g->by_s.xpos, T, Bh, (const float *)nullptr, m, fz)
-  switch (kdim) {
-    case 16: NGPDE_GNO_FF(16); break;
-    case 32: NGPDE_GNO_FF(32); break;
-    default: NGPDE_GNO_FF(64); break;
-  }
-#undef NGPDE_GNO_FF
-  NGPDE_LAUNCH_CHECK("gno_apply_mfma_fwd_kernel (fused input)");
-  return NGPDE_OK;
+  return launch_fwd<true>(g, cout, kdim, T, Bh, nullptr, m, GnoFuse{P, Q, E, g->by_s.col, z_out, act1}, stream);
 }
 
 int32_t launch_gno_apply_mfma_bwd(const ngpde_graph *g, int cout, int kdim, const float *T, const float *z, const float *dm, float *dT,
                                   float *dBh, float *dz, hipStream_t stream, const float *dagg, int mean, int act1, float *dq) {
   if (g->n_nodes == 0) return NGPDE_OK;
-  const dim3 grid((unsigned)g->n_nodes), block(256);
-  const size_t lds = gno_mfma_bwd_lds(cout, kdim);
+  const GnoApplyForm f = gno_apply_form(cout, kdim);   // NOB and the LDS request (below the default limit: gno_forms.h asserts it)
+  NGPDE_REQUIRE(f.kind == GnoApplyKind::Mfma, NGPDE_ERR_UNSUPPORTED, "gno_apply_mfma_bwd_kernel: out = %d, k = %d outside the matrix-pipe kernels", cout, kdim);
   const GnoNodeGrad ng{dagg, g->by_s.col, g->by_t.rowptr, mean, act1, dq};
-#define NGPDE_GNO_B2(KK, NOB, NODE)                                                                                              \
-  do {                                                                                                                           \
-    if (lds > 64 * 1024)   /* beyond the default dynamic-LDS limit: raise it for this kernel (cheap, idempotent) */               \
-      NGPDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gno_apply_mfma_bwd_kernel<KK, NOB, NODE>),             \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                               \
-    hipLaunchKernelGGL((gno_apply_mfma_bwd_kernel<KK, NOB, NODE>), grid, block, lds, stream, cout, g->by_s.rowptr, g->by_s.xpos, T, z, \
-                       dm, dT, dBh, dz, ng);                                                                                     \
-  } while (0)
-#define NGPDE_GNO_B(KK, NOB)                                                                                                     \
-  do {                                                                                                                           \
-    if (dagg) NGPDE_GNO_B2(KK, NOB, true);                                                                                       \
-    else NGPDE_GNO_B2(KK, NOB, false);                                                                                           \
-  } while (0)
-  if (cout <= 128) {
-    switch (kdim) {
-      case 16: NGPDE_GNO_B(16, 8); break;
-      case 32: NGPDE_GNO_B(32, 8); break;
-      default: NGPDE_GNO_B(64, 8); break;
-    }
-  } else {
-    switch (kdim) {
-      case 16: NGPDE_GNO_B(16, 16); break;
-      case 32: NGPDE_GNO_B(32, 16); break;
-      default: NGPDE_GNO_B(64, 16); break;
-    }
-  }
-#undef NGPDE_GNO_B2
-#undef NGPDE_GNO_B
+  gno_pick<16, 32, 64>(kdim, [&](auto kd) {
+    gno_pick<kGnoMfmaNobSmall, kGnoMfmaNobLarge>(f.nob, [&](auto nob) {
+      gno_pick<1, 0>(dagg ? 1 : 0, [&](auto node) {
+        hipLaunchKernelGGL((gno_apply_mfma_bwd_kernel<decltype(kd)::value, decltype(nob)::value, decltype(node)::value != 0>), dim3((unsigned)g->n_nodes),
+                           dim3(kGnoThreads), f.lds_bwd, stream, cout, g->by_s.rowptr, g->by_s.xpos, T, z, dm, dT, dBh, dz, ng);
+      });
+    });
+  });
   NGPDE_LAUNCH_CHECK("gno_apply_mfma_bwd_kernel");
   return NGPDE_OK;
 }

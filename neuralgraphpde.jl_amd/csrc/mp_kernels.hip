@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "device_utils.h"
+#include "gno_forms.h"
 #include "switches.h"
 
 namespace ngpde {
@@ -327,8 +328,8 @@ __global__ __launch_bounds__(256) void gno_contract_bwd_kernel(int64_t n_edges, 
 // last Dense layer, K_e = reshape(W2 z_e + b2, out, in) and  m_e = K_e h_j = T_j z_e + (B2 h_j),
 // T_j[o][kk] = sum_i W2[o + out*i][kk] h_j[i]  a NODE-level product.  The in*out x E kernel tensor (64 KB per edge at
 // 128-d) is never formed.  One workgroup per SOURCE node stages T_j in LDS (row stride out + 1: conflict-free for
-// both access directions) and serves all edges leaving j; outputs land at the edges' p positions.
-constexpr int kGnoBatch = 16;   // edges of one source staged per LDS pass
+// both access directions) and serves all edges leaving j; outputs land at the edges' p positions, kGnoBatch (gno_forms.h) edges of
+// the source per LDS pass.
 
 __device__ __forceinline__ int pad4(int v) { return (v + 3) & ~3; }
 
@@ -946,36 +947,15 @@ int32_t launch_gno_contract_bwd(const ngpde_graph *g, int cin, int cout, const f
   return NGPDE_OK;
 }
 
-static int gno_kp_log2(int kdim) {
-  int l = 0;
-  while ((1 << l) < kdim) ++l;
-  return l;
-}
-
-static int gno_pad4(int v) { return (v + 3) & ~3; }
-
-// rows of dT_j per thread in the pullback: ceil(pad4(cout) / OG) rounded up to a multiple of 4
-static int gno_rows_per_thread(int cout, int kdim) {
-  const int og = 256 >> gno_kp_log2(kdim);
-  return gno_pad4((gno_pad4(cout) + og - 1) / og);
-}
-
-static size_t gno_lds_bytes(int cout, int kdim, bool bwd) {
-  const int cP = gno_pad4(cout), kdP = gno_pad4(kdim);
-  return ((size_t)kdP * (cP + 1) + (size_t)kGnoBatch * kdP + (bwd ? (size_t)kGnoBatch * cP : 0)) * sizeof(float);
-}
-
-bool gno_apply_supported(int cout, int kdim) {
-  if (cout <= 0 || kdim <= 0 || cout > 256 || kdim > 256) return false;
-  return gno_rows_per_thread(cout, kdim) <= 32 && gno_lds_bytes(cout, kdim, true) <= 60 * 1024;
-}
-
+// the reassociated message from a given z: the matrix-pipe kernels or the register-tile ones, as gno_forms.h decides
 int32_t launch_gno_apply_fwd(const ngpde_graph *g, int cout, int kdim, const float *T, const float *Bh, const float *z,
                              float *m, hipStream_t stream) {
   if (g->n_edges == 0) return NGPDE_OK;
-  if (gno_apply_mfma_supported(cout, kdim)) return launch_gno_apply_mfma_fwd(g, cout, kdim, T, Bh, z, m, stream);
-  hipLaunchKernelGGL(gno_apply_fwd_kernel, dim3((unsigned)g->n_nodes), dim3(256), gno_lds_bytes(cout, kdim, false), stream,
-                     (int)g->n_nodes, cout, kdim, g->by_s.rowptr, g->by_s.xpos, T, Bh, z, m);
+  const GnoApplyForm f = gno_apply_form(cout, kdim);
+  if (f.kind == GnoApplyKind::Mfma) return launch_gno_apply_mfma_fwd(g, cout, kdim, T, Bh, z, m, stream);
+  NGPDE_REQUIRE(f.kind == GnoApplyKind::Valu, NGPDE_ERR_UNSUPPORTED, "gno_apply_fwd_kernel: out = %d, k = %d outside every apply kernel", cout, kdim);
+  hipLaunchKernelGGL(gno_apply_fwd_kernel, dim3((unsigned)g->n_nodes), dim3(kGnoThreads), f.lds_fwd, stream, (int)g->n_nodes, cout, kdim,
+                     g->by_s.rowptr, g->by_s.xpos, T, Bh, z, m);
   NGPDE_LAUNCH_CHECK("gno_apply_fwd_kernel");
   return NGPDE_OK;
 }
@@ -983,10 +963,11 @@ int32_t launch_gno_apply_fwd(const ngpde_graph *g, int cout, int kdim, const flo
 int32_t launch_gno_apply_bwd(const ngpde_graph *g, int cout, int kdim, const float *T, const float *z, const float *dm,
                              float *dT, float *dBh, float *dz, hipStream_t stream) {
   if (g->n_nodes == 0) return NGPDE_OK;
-  if (gno_apply_mfma_supported(cout, kdim)) return launch_gno_apply_mfma_bwd(g, cout, kdim, T, z, dm, dT, dBh, dz, stream);
-  hipLaunchKernelGGL(gno_apply_bwd_kernel, dim3((unsigned)g->n_nodes), dim3(256), gno_lds_bytes(cout, kdim, true), stream,
-                     (int)g->n_nodes, cout, kdim, gno_kp_log2(kdim), gno_rows_per_thread(cout, kdim), g->by_s.rowptr,
-                     g->by_s.xpos, T, z, dm, dT, dBh, dz);
+  const GnoApplyForm f = gno_apply_form(cout, kdim);
+  if (f.kind == GnoApplyKind::Mfma) return launch_gno_apply_mfma_bwd(g, cout, kdim, T, z, dm, dT, dBh, dz, stream);
+  NGPDE_REQUIRE(f.kind == GnoApplyKind::Valu, NGPDE_ERR_UNSUPPORTED, "gno_apply_bwd_kernel: out = %d, k = %d outside every apply kernel", cout, kdim);
+  hipLaunchKernelGGL(gno_apply_bwd_kernel, dim3((unsigned)g->n_nodes), dim3(kGnoThreads), f.lds_bwd, stream, (int)g->n_nodes, cout, kdim,
+                     f.kp_log2, f.rows_per_thread, g->by_s.rowptr, g->by_s.xpos, T, z, dm, dT, dBh, dz);
   NGPDE_LAUNCH_CHECK("gno_apply_bwd_kernel");
   return NGPDE_OK;
 }

@@ -8,10 +8,17 @@ form is compared with a plain float64 computation of the same operation:
   c. the by-source entries (csrc/gno_mfma.hip: ngpde_gno_message_forward, ngpde_gno_apply_*, ngpde_gno_message_backward_from_nodes)
      at every supported (out, k);
   d. the GNOConv layer end to end against O.gno_conv / O.gno_conv_backward, one case per plan form;
-  e. the 4 GB guard of the aggregate-then-transform form.
+  e. the 4 GB guard of the aggregate-then-transform form;
+  f. the ABI queries' answers and the layer entry's workspace sizes, pinned to tests/golden/gno_forms.json.
+
+Which form a layer case must show comes from tests/gno_forms_spec.py, the restatement of csrc/gno_forms.h, where every choice is made.
 
 Tolerances are the suite's: forward 1e-4 * max|ref| + 1e-5, gradients 5e-4 relative.
 """
+import ctypes as C
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -19,13 +26,13 @@ import torch
 import ngpde_amd as ng
 from ngpde_amd import _lib
 from oracle import ngpde_oracle as O
-import composed
+import gno_forms_spec as S
 from test_mp_gpu import check_grads, close, mlp_grad_pairs, omlp, prep
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 K64 = 64
-SWITCHES = ("NGPDE_NO_GNO_GFORM", "NGPDE_NO_GNO_MFMA", "NGPDE_GNO_MATERIALIZE", "NGPDE_GNO_GFORM_CHUNK")
+SWITCHES = S.SWITCHES
 
 
 def clear_switches(monkeypatch):
@@ -325,43 +332,60 @@ def layer_graph(N, deg, seed, edata=0, node_data=True, isolated=0):
     return g, og, 3 if node_data else 0
 
 
-# (name, in, out, k, aggr, first, b2, N, deg, edata, node data, chunk, form in training, form in inference)
+# (name, in, out, k, aggr, first, b2, N, deg, edata, node data, chunk, form in training, form in inference, phi)
+# phi: "2" = Dense(., k, first), Dense(k, in out); "1" = Dense(., in out, first) alone; "3" = Dense(., 32, first), Dense(32, k, relu),
+# Dense(k, in out); "2-relu" = "2" with relu on the last layer (K_e is no longer linear in z_e: the literal contraction)
 LAYER_CASES = [
-    ("gform-train-in32-chunk16", 32, 48, 64, "+", "relu", True, 150, 64, 0, True, 16, "gform", "gform"),
-    ("gform-train-in64-mean", 64, 16, 64, "mean", "identity", True, 130, 70, 1, True, 32, "gform", "gform"),
-    ("gform-infer-in128", 128, 16, 64, "mean", "relu", True, 200, 20, 0, True, 32, "fused-agg", "gform"),
-    ("gform-infer-in32-chunk16", 32, 128, 64, "+", "identity", True, 129, 24, 2, True, 16, "fused-agg", "gform"),
-    ("by-source-sum-k16", 64, 48, 16, "+", "relu", True, 300, None, 0, True, 32, "fused-agg", "fused-agg"),
-    ("by-source-mean-k32", 32, 128, 32, "mean", "identity", True, 257, None, 2, True, 32, "fused-agg", "fused-agg"),
-    ("message-max", 32, 16, 64, "max", "relu", True, 257, None, 0, True, 32, "fused-msg", "fused-msg"),
-    ("edge-only", 32, 48, 64, "mean", "relu", True, 100, 70, 3, False, 32, "gform", "gform"),
-    ("no-b2", 128, 16, 64, "+", "relu", False, 100, 66, 0, True, 32, "gform", "gform"),
+    ("gform-train-in32-chunk16", 32, 48, 64, "+", "relu", True, 150, 64, 0, True, 16, "gform", "gform", "2"),
+    ("gform-train-in64-mean", 64, 16, 64, "mean", "identity", True, 130, 70, 1, True, 32, "gform", "gform", "2"),
+    ("gform-infer-in128", 128, 16, 64, "mean", "relu", True, 200, 20, 0, True, 32, "fused-agg", "gform", "2"),
+    ("gform-infer-in32-chunk16", 32, 128, 64, "+", "identity", True, 129, 24, 2, True, 16, "fused-agg", "gform", "2"),
+    ("by-source-sum-k16", 64, 48, 16, "+", "relu", True, 300, None, 0, True, 32, "fused-agg", "fused-agg", "2"),
+    ("by-source-mean-k32", 32, 128, 32, "mean", "identity", True, 257, None, 2, True, 32, "fused-agg", "fused-agg", "2"),
+    ("message-max", 32, 16, 64, "max", "relu", True, 257, None, 0, True, 32, "fused-msg", "fused-msg", "2"),
+    ("edge-only", 32, 48, 64, "mean", "relu", True, 100, 70, 3, False, 32, "gform", "gform", "2"),
+    ("no-b2", 128, 16, 64, "+", "relu", False, 100, 66, 0, True, 32, "gform", "gform", "2"),
+    ("phi-one-layer", 8, 12, 16, "+", "tanh", True, 129, 5, 1, True, 32, "literal", "literal", "1"),
+    ("phi-three-layers", 16, 20, 24, "mean", "swish", True, 130, None, 0, True, 32, "reassoc", "reassoc", "3"),
+    ("last-layer-relu", 8, 16, 64, "+", "relu", True, 129, 5, 0, True, 32, "literal", "literal", "2-relu"),
 ]
 
 
-def plan_form(N, E, cin, cout, k, act1, aggr, training):
-    """the layer entry's plan (api_layers.hip: make_gno_plan) through the library's own predicates"""
-    if not composed.gno_message_supported(cout, k, act1) or E == 0:
-        return "primitives"
-    if aggr not in ("+", "mean"):
-        return "fused-msg"
-    return "gform" if composed.gno_gform_preferred(N, E, cin, cout, k, act1, aggr, training) else "fused-agg"
+def phi_dims_acts(shape, d0, k, cin, cout, first):
+    """widths and activations of phi's Dense layers for a case's phi column"""
+    if shape == "1":
+        return [d0, cin * cout], [first]
+    if shape == "3":
+        return [d0, 32, k, cin * cout], [first, "relu", "identity"]
+    return [d0, k, cin * cout], [first, "relu" if shape == "2-relu" else "identity"]
+
+
+def plan_form(N, E, cin, cout, dims, acts, b2, aggr, training):
+    """the layer entry's form (csrc/gno_forms.h: gno_layer_form) by its restatement, under the environment of the moment"""
+    return S.layer_form_name(S.layer_form(N, E, cin, cout, len(acts), dims[-2], _lib.ACT[acts[0]], _lib.ACT[acts[-1]], b2, _lib.AGGR[aggr], training))
 
 
 @pytest.mark.parametrize("case", LAYER_CASES, ids=[c[0] for c in LAYER_CASES])
 def test_gno_layer_forms_against_float64(case, monkeypatch):
     # output, dx and every parameter gradient of GNOConv through the layer entry against the literal float64 layer (O.gno_conv:
     # K materialised, batched_mul, scatter): one case per plan form, node counts off the 128-row tiles, nodes without incoming edges
-    name, cin, cout, k, aggr, first, b2, N, deg, de, nd, chunk, f_train, f_infer = case
+    name, cin, cout, k, aggr, first, b2, N, deg, de, nd, chunk, f_train, f_infer, shape = case
     clear_switches(monkeypatch)
     monkeypatch.setenv("NGPDE_GNO_GFORM_CHUNK", str(chunk))
     g, og, ds = layer_graph(N, deg, 31, edata=de, node_data=nd, isolated=0 if deg is not None else 3)
     E = g.num_edges
     assert E * cin * cout <= 2.5e7                                       # (the literal oracle's [in out][E] arrays)
-    act1 = _lib.ACT[first]
-    assert plan_form(N, E, cin, cout, k, act1, aggr, True) == f_train, name
-    assert plan_form(N, E, cin, cout, k, act1, aggr, False) == f_infer, name
-    phi = ng.Chain(ng.Dense(2 * ds + de, k, first), ng.Dense(k, cin * cout, bias=b2))
+    dims, acts = phi_dims_acts(shape, 2 * ds + de, k, cin, cout, first)
+    assert plan_form(N, E, cin, cout, dims, acts, b2, aggr, True) == f_train, name
+    assert plan_form(N, E, cin, cout, dims, acts, b2, aggr, False) == f_infer, name
+    lib = _lib.load()                                                     # the library's queries say what the restatement says of this case
+    for training in (False, True):
+        f = S.layer_form(N, E, cin, cout, len(acts), dims[-2], _lib.ACT[acts[0]], _lib.ACT[acts[-1]], b2, _lib.AGGR[aggr], training)
+        assert lib.ngpde_gno_apply_supported(cout, dims[-2]) == int(f["apply"]["apply_entry"]), name
+        assert lib.ngpde_gno_message_supported(cout, dims[-2]) == int(f["apply"]["message_entry"]), name
+        assert lib.ngpde_gno_gform_preferred(N, E, cin, dims[-2], cout, int(training)) == int(f["by_target"]["preferred"]), name
+        assert lib.ngpde_gno_gform_splits(N, cin, dims[-2], cout) == f["by_target"]["nsplit"], name
+    phi = ng.Chain(*[ng.Dense(dims[l], dims[l + 1], acts[l], **({"bias": b2} if l + 1 == len(acts) else {})) for l in range(len(acts))])
     layer = ng.GNOConv((cin, cout), phi, "tanh", initialgraph=g, aggr=aggr)
     ps0, st = ng.setup(41, layer)
     ps = prep(ps0, 41)
@@ -395,3 +419,110 @@ def test_gform_guard_covers_the_q_rows(monkeypatch):
     assert lib.ngpde_gno_gform_preferred(1 << 23, E, 64, 64, 64, 0) == 1
     assert lib.ngpde_gno_gform_preferred(1 << 23, E, 128, 64, 64, 0) == 0
     assert lib.ngpde_gno_gform_preferred((1 << 23) - 1, E, 128, 64, 64, 0) == 1
+
+
+# ---- f. the queries' answers and the layer workspace sizes, pinned to the build before csrc/gno_forms.h ------------------------------
+
+FORMS_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gno_forms.json")
+QUERY_OUTS = (0, 1, 4, 15, 16, 17, 112, 128, 129, 144, 240, 256, 257, 272)
+QUERY_KS = (0, 1, 8, 15, 16, 17, 32, 33, 48, 64, 65, 128, 256, 257)
+QUERY_INS = (0, 16, 32, 48, 64, 96, 128, 256)
+QUERY_NS = (0, 1, 127, 128, 129, 4096, 1 << 20, (1 << 23) - 1, 1 << 23, 1 << 24)
+QUERY_SETTINGS = [None] + [(name, "1") for name in S.PATH_SWITCHES] + [(S.GNO_GFORM_CHUNK, v) for v in ("16", "32", "7")]
+LAYER_SETTINGS = QUERY_SETTINGS[:4]                                        # unswitched and each path switch alone
+DIGITS = "0123456789abcdefghijklmnopqrstuvwxyz"                            # ngpde_gno_gform_splits: one character per answer (at most 32)
+AS_UNSWITCHED = "as unswitched"
+
+
+def hexbits(vals):
+    """yes / no answers, four per hexadecimal digit, first answer in the highest bit (the last digit padded with zero bits)"""
+    bits = "".join("1" if v else "0" for v in vals)
+    bits += "0" * (-len(bits) % 4)
+    return f"{int(bits, 2):0{len(bits) // 4}x}"
+
+
+def query_edge_counts(N):
+    return (0, 1, 64 * N - 1, 64 * N, 1 << 30)
+
+
+def gno_descriptor(case, ds, dev_ptr):
+    """ngpde_gno_layer_t of a layer case: the size query reads the widths and tests the pointers for NULL"""
+    name, cin, cout, k, aggr, first, b2, N, deg, de, nd, chunk, f_train, f_infer, shape = case
+    dims, acts = phi_dims_acts(shape, 2 * ds + de, k, cin, cout, first)
+    d = _lib.GnoLayer()
+    d.in_chs, d.out_chs, d.aggr, d.act = cin, cout, _lib.AGGR[aggr], _lib.ACT["tanh"]
+    d.h = d.weight = d.bias = dev_ptr
+    d.node_feat, d.node_feat_width = (dev_ptr, ds) if ds else (None, 0)
+    d.edge_feat, d.edge_feat_width = (dev_ptr, de) if de else (None, 0)
+    d.phi.n_layers = len(acts)
+    for l, w in enumerate(dims):
+        d.phi.dims[l] = w
+    for l, a in enumerate(acts):
+        d.phi.act[l] = _lib.ACT[a]
+        d.phi.weight[l] = dev_ptr
+        d.phi.bias[l] = dev_ptr if (b2 or l + 1 < len(acts)) else None
+    return d
+
+
+def query_answers(monkeypatch):
+    """the five queries over the boundary grid under every switch setting, and ngpde_gno_layer_workspace_bytes of every layer case
+    [inference, training] unswitched and under each path switch, as the library answers now.  Yes / no answers as hexbits, groups
+    separated by blanks: apply / message_supported one group per out (over k), gform_supported one per in (over k), gform_preferred
+    per N one group per (E, training) over in x (k, out) with (k, out) = every k x 128 and 64 x every out, gform_splits per N one group
+    per in over k x out.  A table that a switch leaves as it is without it says so instead of repeating it."""
+    lib = _lib.load()
+    digits = lambda vals: "".join(DIGITS[int(v)] for v in vals)
+    ko = [(k, 128) for k in QUERY_KS] + [(64, out) for out in QUERY_OUTS]
+    queries = {}
+    for setting in QUERY_SETTINGS:
+        clear_switches(monkeypatch)
+        if setting:
+            monkeypatch.setenv(*setting)
+        q = {"apply_supported": " ".join(hexbits(lib.ngpde_gno_apply_supported(o, k) for k in QUERY_KS) for o in QUERY_OUTS),
+             "message_supported": " ".join(hexbits(lib.ngpde_gno_message_supported(o, k) for k in QUERY_KS) for o in QUERY_OUTS),
+             "gform_supported": " ".join(hexbits(lib.ngpde_gno_gform_supported(i, k) for k in QUERY_KS) for i in QUERY_INS),
+             "gform_preferred": {f"N={N}": " ".join(hexbits(lib.ngpde_gno_gform_preferred(N, E, i, k, o, tr) for i in QUERY_INS for k, o in ko)
+                                                    for E in query_edge_counts(N) for tr in (0, 1)) for N in QUERY_NS},
+             "gform_splits": {f"N={N}": " ".join(digits(lib.ngpde_gno_gform_splits(N, i, k, o) for k in QUERY_KS for o in QUERY_OUTS) for i in QUERY_INS)
+                              for N in QUERY_NS}}
+        if setting:
+            q = {name: (AS_UNSWITCHED if table == queries[""][name] else table) for name, table in q.items()}
+        queries["=".join(setting) if setting else ""] = q
+    layers = {"=".join(setting) if setting else "": {} for setting in LAYER_SETTINGS}
+    dummy = torch.zeros(16, device=DEV)
+    for case in LAYER_CASES:
+        g, _, ds = layer_graph(case[7], case[8], 31, edata=case[9], node_data=case[10], isolated=0 if case[8] is not None else 3)
+        handle = g.handle()
+        d = gno_descriptor(case, ds, dummy.data_ptr())
+        for setting in LAYER_SETTINGS:
+            clear_switches(monkeypatch)
+            if setting:
+                monkeypatch.setenv(*setting)
+            layers["=".join(setting) if setting else ""][case[0]] = [int(lib.ngpde_gno_layer_workspace_bytes(handle.ptr, C.byref(d), tr)) for tr in (0, 1)]
+    clear_switches(monkeypatch)
+    return {"queries": queries, "layer_workspace_bytes": layers}
+
+
+def test_queries_answer_what_the_build_before_the_forms_header_answered(monkeypatch):
+    # which kernel runs never shows in a float64 comparison; what the ABI queries and the layer's workspace size say about it does.
+    # tests/golden/gno_forms.json holds their answers from the library as it was before the choices moved into csrc/gno_forms.h (the
+    # field "recorded_from" names the commit; tools/record_gno_forms.py wrote it).  No kernel of the family is launched here.
+    want = json.load(open(FORMS_GOLDEN))
+    got = query_answers(monkeypatch)
+    assert set(got["queries"]) == set(want["queries"]) == {""} | {"=".join(s) for s in QUERY_SETTINGS[1:]}
+    for setting, q in got["queries"].items():
+        assert set(q) == set(want["queries"][setting])
+        for name, table in q.items():
+            rec = want["queries"][setting][name]
+            rows, rec_rows = (table, rec) if isinstance(table, dict) and isinstance(rec, dict) else ({"": table}, {"": rec})
+            wrong = [(key, row, rec_rows.get(key)) for key, row in rows.items() if row != rec_rows.get(key)]
+            assert not wrong and len(rows) == len(rec_rows), f"{setting or 'unswitched'} {name} (row, now, recorded): {wrong[:2]}"
+    assert got["layer_workspace_bytes"] == want["layer_workspace_bytes"]
+    sizes = got["layer_workspace_bytes"]
+    assert all(0 < a <= b for per in sizes.values() for a, b in per.values())
+    assert all(sizes[""] != sizes[s] for s in sizes if s)                      # every path switch moves at least one layout
+    # the switches act where they are meant to: each path switch on its own tables, the chunk switch on no query
+    changed = {setting: {name for name, table in q.items() if table != AS_UNSWITCHED} for setting, q in got["queries"].items() if setting}
+    assert changed == {"NGPDE_NO_GNO_MFMA=1": {"message_supported"}, "NGPDE_NO_GNO_GFORM=1": {"gform_supported", "gform_preferred"},
+                       "NGPDE_GNO_MATERIALIZE=1": set(), "NGPDE_GNO_GFORM_CHUNK=16": set(), "NGPDE_GNO_GFORM_CHUNK=32": set(),
+                       "NGPDE_GNO_GFORM_CHUNK=7": set()}
