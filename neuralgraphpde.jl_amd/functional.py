@@ -20,6 +20,44 @@ def _need_cuda(*ts):
                 "the state to the GPU (there is no CPU fallback)")
 
 
+def _vec(b, n, what):
+    """layers.vec_of for the wrappers below: float32 contiguous [n] or DimensionMismatch (the rule at layers.rows_of).  Inside an
+    autograd node's forward the conversion needs no pullback of its own: autograd casts the returned gradient to the input's type"""
+    if b is None:
+        return None
+    from .layers import vec_of
+    return vec_of(b, n, what)
+
+
+def _f32(t):
+    """float32 contiguous, whatever real dtype and strides came in"""
+    if t is None:
+        return None
+    return t.to(torch.float32).contiguous()
+
+
+def _f32a(t):
+    """_f32, and 16-byte aligned: a float32 view that starts in the middle of its storage is copied into a fresh buffer.  For the
+    entries whose launchers read their caller pointers as float4 without testing them, or whose launches were not all traced (the
+    fused GCN kernels, the GAT launches, the one-call edge-function and GNO layers, the device-resident solver plans); the entries
+    that choose a scalar form for such a pointer (Dense, bias_act, the gathers, the fused built-in messages, the segmented
+    reductions, the readouts, the Runge-Kutta combinations) or read one float at a time (propagate_copy_xj, edge_permute, the
+    edge softmax) take _f32"""
+    if t is None:
+        return None
+    t = t.to(torch.float32).contiguous()
+    return t.clone() if (t.data_ptr() & 15) else t
+
+
+def _as(db, shape):
+    """the bias gradient in the shape the bias came in ((out,), (out x 1) or (1 x out)): autograd casts a gradient's type, not its shape"""
+    return db if (db is None or shape is None) else db.reshape(shape)
+
+
+def _shape(b):
+    return None if b is None else tuple(b.shape)
+
+
 def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
@@ -30,14 +68,15 @@ class _GCNConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wt, bias, handle, act, edge_weight=None):
-        lib = _lib.load()
-        _need_cuda(x, wt, bias)
         n, din = x.shape
         dout = wt.shape[1]
         if wt.shape[0] != din:
             raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
                                          f"DimensionMismatch: weight is ({dout} x {wt.shape[0]}), x has {din} features")
-        x, wt = x.contiguous(), wt.contiguous()
+        ctx.bias_shape = _shape(bias)
+        x, wt, bias = _f32a(x), _f32a(wt), _f32a(_vec(bias, dout, "GCNConv: bias"))
+        _need_cuda(x, wt, bias)
+        lib = _lib.load()
         y = torch.empty((n, dout), dtype=torch.float32, device=x.device)
         need_grad = any(ctx.needs_input_grad)
         agg = torch.empty((n, din), dtype=torch.float32, device=x.device) if (need_grad and dout >= din) else None
@@ -57,7 +96,7 @@ class _GCNConvFn(torch.autograd.Function):
         lib = _lib.load()
         x, wt, z, agg, bias = ctx.saved_tensors
         n, din, dout = ctx.dims
-        dy = dy.contiguous()
+        dy = _f32a(dy)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dwt = torch.empty_like(wt)
         db = torch.empty((dout,), dtype=torch.float32, device=x.device) if ctx.has_bias else None
@@ -67,12 +106,12 @@ class _GCNConvFn(torch.autograd.Function):
             _lib.check(lib.ngpde_gcn_backward_ew(ctx.handle.ptr, din, dout, ctx.act, _lib.ptr(x), _lib.ptr(wt), _lib.ptr(bias), _lib.ptr(z),
                                                  _lib.ptr(agg), _lib.ptr(dy), _lib.ptr(dx), _lib.ptr(dwt), _lib.ptr(db), _lib.ptr(dew),
                                                  _lib.ptr(ws), ws.numel(), _lib.current_stream()))
-            return dx, dwt, db, None, None, dew
+            return dx, dwt, _as(db, ctx.bias_shape), None, None, dew
         ws = _ws(lib.ngpde_gcn_workspace_bytes(ctx.handle.ptr, din, dout, 1), x.device)
         _lib.check(lib.ngpde_gcn_backward(ctx.handle.ptr, din, dout, ctx.act, _lib.ptr(x), _lib.ptr(wt), _lib.ptr(z),
                                           _lib.ptr(agg), _lib.ptr(dy), _lib.ptr(dx), _lib.ptr(dwt), _lib.ptr(db),
                                           _lib.ptr(ws), ws.numel(), _lib.current_stream()))
-        return dx, dwt, db, None, None, None
+        return dx, dwt, _as(db, ctx.bias_shape), None, None, None
 
 
 def gcn_conv(x, wt, bias, handle, act, edge_weight=None):
@@ -82,9 +121,11 @@ def gcn_conv(x, wt, bias, handle, act, edge_weight=None):
 
 def propagate_copy_xj(x, handle, aggr="+", edge_weight=None, by_source=False):
     """out[i] = aggr_{e: t_e = i} w_e x[s_e]   (no autograd; forward primitive)."""
-    lib = _lib.load()
+    x = _f32(x)                      # (spmm_generic_kernel reads x and the weights one float at a time: any 4-byte alignment)
+    if edge_weight is not None:      # (the entry reads one float per edge of the handle's graph through this pointer)
+        edge_weight = _vec(edge_weight, handle._n_edges, "edge_weight")
     _need_cuda(x, edge_weight)
-    x = x.contiguous()
+    lib = _lib.load()
     out = torch.empty_like(x)
     _lib.check(lib.ngpde_propagate_copy_xj(handle.ptr, x.shape[1], _lib.AGGR[aggr], int(by_source), _lib.ptr(x),
                                            _lib.ptr(edge_weight), _lib.ptr(out), _lib.current_stream()))
@@ -112,12 +153,12 @@ class _DenseFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, wt, bias, act, row_divs, n, *blocks):
-        lib = _lib.load()
-        _need_cuda(wt, bias, *blocks)
-        blocks = [b.contiguous() for b in blocks]
-        wt = wt.contiguous()
+        blocks = [_f32(b) for b in blocks]
+        wt = _f32(wt)
         widths = [b.shape[1] for b in blocks]
         din, dout = sum(widths), wt.shape[1]
+        ctx.bias_shape = _shape(bias)
+        bias = _vec(bias, dout, "Dense: bias")
         if wt.shape[0] != din:
             raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
                                          f"DimensionMismatch: Dense expects {wt.shape[0]} input features, got {din}")
@@ -125,6 +166,8 @@ class _DenseFn(torch.autograd.Function):
             if b.shape[0] * rd != n and not (rd > 1 and b.shape[0] * rd >= n):
                 raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
                                              f"DimensionMismatch: block with {b.shape[0]} rows (x{rd}) does not cover {n} rows")
+        _need_cuda(wt, bias, *blocks)
+        lib = _lib.load()
         dev = wt.device
         y = torch.empty((n, dout), dtype=torch.float32, device=dev)
         need = any(ctx.needs_input_grad)
@@ -151,7 +194,7 @@ class _DenseFn(torch.autograd.Function):
         _lib.check(lib.ngpde_dense_backward(n, len(blocks), _ptr_array(blocks), _int_array(widths), _int_array(row_divs),
                                             dout, act, _lib.ptr(wt), _lib.ptr(z), _lib.ptr(dy), _ptr_array(dblocks),
                                             _lib.ptr(dwt), _lib.ptr(db), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
-        return (dwt, db, None, None, None, *dblocks)
+        return (dwt, _as(db, ctx.bias_shape), None, None, None, *dblocks)
 
 
 def dense(blocks, wt, bias, act, row_divs=None, n=None):
@@ -167,7 +210,7 @@ class _EdgePermuteFn(torch.autograd.Function):
     def forward(ctx, x, handle, inverse):
         lib = _lib.load()
         _need_cuda(x)
-        x = x.contiguous()
+        x = _f32(x)                  # (edge_permute_kernel moves one float at a time)
         out = torch.empty_like(x)
         _lib.check(lib.ngpde_edge_permute(handle.ptr, x.shape[1], int(inverse), _lib.ptr(x), _lib.ptr(out),
                                           _lib.current_stream()))
@@ -187,9 +230,12 @@ def edge_permute(x, handle, inverse=False):
 class _GatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wx, a, handle, heads, c, slope, n_edges):
-        lib = _lib.load()
+        wx, a = _f32a(wx), _f32a(a)
+        if wx.shape[1] != heads * c or tuple(a.shape) != (heads, 2 * c):
+            raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH, f"DimensionMismatch: GAT: Wx is ({wx.shape[1]} x {wx.shape[0]}) and a is "
+                                         f"{tuple(a.shape)[::-1]}, expected ({heads * c} x N) and ({2 * c}, {heads})")
         _need_cuda(wx, a)
-        wx, a = wx.contiguous(), a.contiguous()
+        lib = _lib.load()
         n = wx.shape[0]
         dev = wx.device
         out = torch.empty_like(wx)
@@ -207,7 +253,7 @@ class _GatFn(torch.autograd.Function):
         lib = _lib.load()
         wx, a, al, ar, alpha = ctx.saved_tensors
         heads, c, slope = ctx.meta
-        dout = dout.contiguous()
+        dout = _f32a(dout)
         dwx, da = torch.empty_like(wx), torch.empty_like(a)
         ws = _ws(lib.ngpde_gat_workspace_bytes(ctx.handle.ptr, heads), wx.device)
         _lib.check(lib.ngpde_gat_backward(ctx.handle.ptr, heads, c, slope, _lib.ptr(wx), _lib.ptr(a), _lib.ptr(al), _lib.ptr(ar),
@@ -225,9 +271,13 @@ class _GatLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wt, a, bias, handle, heads, c, slope, act, n_edges):
-        lib = _lib.load()
+        ctx.bias_shape = _shape(bias)
+        x, wt, a, bias = _f32a(x), _f32a(wt), _f32a(a), _f32a(_vec(bias, heads * c, "GATConv: bias"))
+        if tuple(wt.shape) != (x.shape[1], heads * c) or tuple(a.shape) != (heads, 2 * c):
+            raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH, f"DimensionMismatch: GATConv: weight is {tuple(wt.shape)[::-1]} and a is "
+                                         f"{tuple(a.shape)[::-1]}, expected ({heads * c}, {x.shape[1]}) and ({2 * c}, {heads})")
         _need_cuda(x, wt, a, bias)
-        x, wt, a = x.contiguous(), wt.contiguous(), a.contiguous()
+        lib = _lib.load()
         n, dev = x.shape[0], x.device
         need = any(ctx.needs_input_grad)
         y = torch.empty((n, heads * c), dtype=torch.float32, device=dev)
@@ -244,7 +294,7 @@ class _GatLayerFn(torch.autograd.Function):
         lib = _lib.load()
         x, wt, a, alpha, yz = ctx.saved_tensors
         heads, c, slope, act, has_bias = ctx.meta
-        dy = dy.contiguous()
+        dy = _f32a(dy)
         dev = x.device
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dwt, da = torch.empty_like(wt), torch.empty_like(a)
@@ -254,7 +304,7 @@ class _GatLayerFn(torch.autograd.Function):
                                                 _lib.ptr(a), _lib.ptr(yz), _lib.ptr(alpha), _lib.ptr(dy), _lib.ptr(dx),
                                                 _lib.ptr(dwt), _lib.ptr(da), _lib.ptr(db), _lib.ptr(ws), ws.numel(),
                                                 _lib.current_stream()))
-        return dx, dwt, da, db, None, None, None, None, None, None
+        return dx, dwt, da, _as(db, ctx.bias_shape), None, None, None, None, None, None
 
 
 def gat_layer_supported(handle, din, heads, c):
@@ -271,11 +321,14 @@ class _BiasActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, addend, bias, act):
-        lib = _lib.load()
-        _need_cuda(a, addend, bias)
-        a = a.contiguous()
-        addend = None if addend is None else addend.contiguous()
+        a, addend = _f32(a), _f32(addend)
         n, d = a.shape
+        ctx.bias_shape = _shape(bias)
+        bias = _vec(bias, d, "bias")
+        if addend is not None and addend.shape != a.shape:
+            raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH, f"DimensionMismatch: addend is {tuple(addend.shape)}, expected {tuple(a.shape)}")
+        _need_cuda(a, addend, bias)
+        lib = _lib.load()
         need = any(ctx.needs_input_grad)
         y = torch.empty_like(a)
         z = torch.empty_like(a) if (need and act not in (0, 1)) else None
@@ -300,7 +353,7 @@ class _BiasActFn(torch.autograd.Function):
         # identity: dz aliases dy, the library skips the element-wise pass and only sums the columns
         _lib.check(lib.ngpde_bias_act_backward(n, d, act, _lib.ptr(dy), _lib.ptr(yz), _lib.ptr(dz), _lib.ptr(db), _lib.ptr(ws),
                                                ws.numel() if ws is not None else 0, _lib.current_stream()))
-        return dz, (dz if has_add else None), db, None
+        return dz, (dz if has_add else None), _as(db, ctx.bias_shape), None
 
 
 def bias_act(a, addend, bias, act):
@@ -358,7 +411,7 @@ class _EdgeLayerFn(torch.autograd.Function):
         lib = _lib.load()
         _need_cuda(*[t for t in tensors if t is not None], *[t for t in consts.values() if t is not None])
         n_phi, n_upd = len(phi_acts), len(upd_acts)
-        tensors = [None if t is None else t.contiguous() for t in tensors]
+        tensors = [_f32a(t) for t in tensors]
         state = tensors[:n_state]
         pw = tensors[n_state:n_state + 2 * n_phi]
         uw = tensors[n_state + 2 * n_phi:]
@@ -378,7 +431,7 @@ class _EdgeLayerFn(torch.autograd.Function):
         for name in ("node_feat", "pos", "edge_feat", "theta"):
             t = consts.get(name)
             if t is not None and t.shape[1] > 0:
-                t = t.contiguous()
+                t = _f32a(t)
                 keep.append(t)
                 setattr(d, name, t.data_ptr())
                 setattr(d, name + "_width", t.shape[1])
@@ -411,7 +464,7 @@ class _EdgeLayerFn(torch.autograd.Function):
         it = iter(ctx.saved_tensors)
         tensors = [next(it) if pr else None for pr in ctx.present]
         dev = dy.device
-        dy = dy.contiguous()
+        dy = _f32a(dy)
         grads = [None] * len(tensors)
         dstate = (C.c_void_p * 4)()
         for k in range(n_state):
@@ -452,7 +505,7 @@ class _GnoLayerFn(torch.autograd.Function):
         import ctypes as C
         lib = _lib.load()
         _need_cuda(*[t for t in tensors if t is not None], *[t for t in consts.values() if t is not None])
-        tensors = [None if t is None else t.contiguous() for t in tensors]
+        tensors = [_f32a(t) for t in tensors]
         h, lwt, lb = tensors[:3]
         pw = tensors[3:]
         n_phi = len(phi_acts)
@@ -469,7 +522,7 @@ class _GnoLayerFn(torch.autograd.Function):
         for name in ("node_feat", "edge_feat"):
             t = consts.get(name)
             if t is not None and t.shape[1] > 0:
-                t = t.contiguous()
+                t = _f32a(t)
                 keep.append(t)
                 setattr(d, name, t.data_ptr())
                 setattr(d, name + "_width", t.shape[1])
@@ -494,7 +547,7 @@ class _GnoLayerFn(torch.autograd.Function):
         it = iter(ctx.saved_tensors)
         tensors = [next(it) if pr else None for pr in ctx.present]
         grads = [None] * len(tensors)
-        dy = dy.contiguous()
+        dy = _f32a(dy)
         if ctx.needs_input_grad[8]:
             grads[0] = torch.empty_like(tensors[0])
         grads[1] = torch.empty_like(tensors[1])

@@ -61,7 +61,7 @@ class _Handle:
         out = C.c_void_p()
         self.lib = lib
         self.ptr = None
-        self._targets, self._n_nodes, self._inv_deg = g._t0, g.num_nodes, {}
+        self._targets, self._n_nodes, self._n_edges, self._inv_deg = g._t0, g.num_nodes, g.num_edges, {}
         if os.environ.get("NGPDE_HOST_GRAPH_BUILD") == "1":
             s = np.ascontiguousarray(g._s0, dtype=np.int64)
             t = np.ascontiguousarray(g._t0, dtype=np.int64)
@@ -233,7 +233,10 @@ class GNNGraph:
         # are unchanged and never accumulates handles (each is a full CSR / halo build in HBM).  The entry keeps `w` alive,
         # so data_ptr / id stay unique while it is cached.
         if isinstance(w, torch.Tensor):
-            key = (bool(norm[0]), ("tensor", w.data_ptr(), w._version, tuple(w.shape), str(w.device)), bool(norm[2]))
+            # (strides and dtype belong to the identity: an `expand`ed or strided view shares its first element's address with
+            # the array it was cut from, and so does a reinterpreting view)
+            key = (bool(norm[0]), ("tensor", w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()), str(w.dtype), str(w.device)),
+                   bool(norm[2]))
         else:
             key = (bool(norm[0]), ("object", id(w)), bool(norm[2]))
         lru = self._shared.setdefault("weighted_handles", OrderedDict())

@@ -58,16 +58,89 @@ def _act_code(activation):
     return name, _lib.ACT[name]
 
 
-def rows_of(x):
-    """(D x N) array -> float32 [N][D] contiguous tensor (no copy for column-major inputs)."""
+def _real(x, what):
     if not isinstance(x, torch.Tensor):
         x = torch.as_tensor(x)
+    if x.is_complex():
+        raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, f"{what} is complex ({x.dtype}); the kernels take real arrays")
+    return x
+
+
+def rows_of(x):
+    """(D x N) array -> float32 [N][D] contiguous tensor (no copy for column-major float32 inputs).
+
+    THE RULE for every real-valued array a public callable takes (inputs, parameters, edge weights, node / edge features, loss
+    cotangents), written here once and followed by rows_of (matrices), vec_of (vectors) and the checks built on them:
+
+      conversion  the kernels see float32, contiguous memory of exactly the expected length.  Any real dtype (float64, half,
+                  bfloat16, integers) and any strides (views with steps, `expand`ed arrays, storage offsets, either storage order)
+                  are converted, by `.to(float32)` / `.contiguous()`: differentiable, so a float64 leaf receives a float64
+                  gradient equal to the float32 gradient cast.  Outputs are float32.  Cotangents reach a pullback as float32
+                  (autograd casts them to the output's type) and are made contiguous there.
+      sizes       an array whose size does not fit raises DimensionMismatch naming the array and both sizes -- before the graph
+                  handle is built and before any library entry is called (the entries take pointers: a short array would be
+                  read past its end on the device).  One exception keeps the reference's own error: a wrong number of edge
+                  weights in GCNConv's `edge_weight` argument is an ArgumentError (src/layers.jl:207), raised as early.
+      device      the arrays of one call live on one GPU; a CPU array among GPU arrays raises ArgumentError (functional._need_cuda).
+                  Nothing is moved between devices silently.  Graph data are not arguments in this sense: the features and edge weights
+                  a GNNGraph stores, and GCNConv's `edge_weight` argument when it needs no gradient, may be host arrays; the graph
+                  handle uploads them once (a weight leaf that requires a gradient must be on the GPU).
+      strict      entries that refuse by name keep doing so (cg_solve takes float32 only and says so).
+
+    A float32 view whose memory order already is the kernels' comes out of rows_of / vec_of WITHOUT a copy, also when it starts in
+    the middle of its storage, so its pointer may be 4-byte but not 16-byte aligned.  What happens next depends on the entry: the
+    launchers of Dense, bias_act, the gathers, the fused built-in messages, the segmented reductions, the readouts and the
+    Runge-Kutta combinations test their caller pointers and choose a scalar form, and get the view as it is; propagate_copy_xj, the
+    edge permutation and the edge softmax read one float at a time and get it as it is, too; the fused GCN kernels, the GAT
+    launches, the edge-function and GNO layers and the solver plans read float4 untested (or were not traced through every launch),
+    so their wrappers copy such a view into a fresh buffer (functional._f32a).
+    tests/test_tensor_args_gpu.py lists the finding per entry."""
+    x = _real(x, "the array")
     if x.dim() != 2:
         raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH, f"DimensionMismatch: expected a (D x N) matrix, got shape {tuple(x.shape)}")
     xt = x.T
     if xt.dtype != torch.float32:
         xt = xt.to(torch.float32)
     return xt if xt.is_contiguous() else xt.contiguous()
+
+
+def vec_of(b, n, what, convert=True):
+    """the vector companion of rows_of: a (n x 1), (1 x n) or (n,) array of any real dtype and any strides -> float32 contiguous
+    [n] (no copy when it already is); DimensionMismatch naming `what` and both sizes when it does not hold n entries.  None stays
+    None (a layer without bias).  convert=False: the check alone."""
+    if b is None:
+        return None
+    b = _real(b, what)
+    if b.numel() != n or b.dim() > 2 or (b.dim() == 2 and min(b.shape) > 1):
+        raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
+                                     f"DimensionMismatch: {what} has shape {tuple(b.shape)} ({b.numel()} entries), expected {n}")
+    if not convert:
+        return None
+    v = b.reshape(-1)
+    if v.dtype != torch.float32:
+        v = v.to(torch.float32)
+    return v if v.is_contiguous() else v.contiguous()
+
+
+def mat_of(w, shape, what, convert=True):
+    """rows_of(w) for a parameter matrix whose Julia shape (out x in) must be `shape`; returns the kernels' [in][out] array.
+    convert=False: the check alone."""
+    got = tuple(w.shape) if hasattr(w, "shape") else tuple(_real(w, what).shape)
+    if got != (int(shape[0]), int(shape[1])):
+        raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
+                                     f"DimensionMismatch: {what} is {got}, expected {tuple(int(v) for v in shape)}")
+    return rows_of(w) if convert else None
+
+
+def check_params(layer, ps):
+    """DimensionMismatch unless every parameter of `layer` (and of the layers inside it) has the size the layer was built with:
+    what each layer's own call checks, for callers that run several layers or hand the parameters to a device-resident plan
+    (Chain, NeuralODE).  Shapes only: nothing is converted or copied."""
+    if hasattr(layer, "kernel_params"):
+        layer.kernel_params(ps, convert=False)
+    elif isinstance(layer, Chain):
+        for n, l in zip(layer.names(), layer.chain):
+            check_params(l, ps[n])
 
 
 # ---- Lux layer protocol ----------------------------------------------------------------------------
@@ -175,13 +248,18 @@ class Dense(AbstractExplicitLayer):
     def parameterlength(self):
         return self.out_dims * (self.in_dims + (1 if self.bias else 0))
 
+    def kernel_params(self, ps, convert=True):
+        """(weight [in][out], bias [out] or None) as the kernels take them, sizes checked (the rule at rows_of)"""
+        wt = mat_of(ps["weight"], (self.out_dims, self.in_dims), f"{self!r}: weight", convert)
+        return wt, (vec_of(ps["bias"], self.out_dims, f"{self!r}: bias", convert) if "bias" in ps else None)
+
     def __call__(self, x, ps, st):
         xr = rows_of(x)
         if xr.shape[1] != self.in_dims:
             raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
                                          f"DimensionMismatch: Dense({self.in_dims} => {self.out_dims}) got {xr.shape[1]} rows")
-        b = ps["bias"].reshape(-1) if "bias" in ps else None
-        return F.dense([xr], rows_of(ps["weight"]), b, self.act).T, st
+        wt, b = self.kernel_params(ps)
+        return F.dense([xr], wt, b, self.act).T, st
 
     def __repr__(self):
         return f"Dense({self.in_dims} => {self.out_dims}" + ("" if self.activation == "identity" else f", {self.activation}") + ")"
@@ -205,10 +283,12 @@ class Chain(AbstractExplicitLayer):
     def statelength(self):
         return sum(l.statelength() for l in self.chain)
 
-    def __call__(self, x, ps, st):
+    def __call__(self, x, ps, st, checked=False):
+        if not checked:
+            check_params(self, ps)  # every layer's parameters before the first layer runs (the rule at rows_of: sizes first)
         new_st = {}
-        for n, l in zip(self.names(), self.chain):
-            x, new_st[n] = l(x, ps[n], st[n])
+        for n, l in zip(self.names(), self.chain):      # (a chain inside has been walked by the check above)
+            x, new_st[n] = l(x, ps[n], st[n], checked=True) if isinstance(l, Chain) else l(x, ps[n], st[n])
         return x, new_st
 
 
@@ -253,6 +333,11 @@ class GCNConv(AbstractGNNLayer):
     def parameterlength(self):                         # src/layers.jl:173-175
         return self.out_chs * (self.in_chs + 1) if self.bias else self.out_chs * self.in_chs
 
+    def kernel_params(self, ps, convert=True):
+        """(weight [in][out], bias [out] or None) as the kernels take them, sizes checked (the rule at rows_of)"""
+        wt = mat_of(ps["weight"], (self.out_chs, self.in_chs), f"{self!r}: weight", convert)      # (out x in) column-major -> [in][out]
+        return wt, (vec_of(ps["bias"], self.out_chs, f"{self!r}: bias", convert) if "bias" in ps else None)
+
     def __call__(self, x, ps, st, edge_weight=None):   # src/layers.jl:200-239
         g = st["graph"]
         if edge_weight is not None:
@@ -278,10 +363,11 @@ class GCNConv(AbstractGNNLayer):
         if xr.shape[1] != self.in_chs:
             raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
                                          f"DimensionMismatch: x has {xr.shape[1]} rows, layer expects {self.in_chs}")
-        wt = rows_of(ps["weight"])                     # (out x in) column-major -> [in][out]
-        b = ps["bias"].reshape(-1) if "bias" in ps else None
+        wt, b = self.kernel_params(ps)
         ew_leaf = edge_weight if (isinstance(edge_weight, torch.Tensor) and edge_weight.requires_grad and torch.is_grad_enabled()) else None
         if ew_leaf is not None and not ew_leaf.is_cuda:
             raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, "GCNConv: an edge_weight that requires a gradient must live on the GPU")
+        if ew_leaf is not None:      # its gradient is a float32 [E] array: the conversion's own pullback gives the leaf its shape and type
+            ew_leaf = vec_of(ew_leaf, g.num_edges, "edge_weight")
         y = F.gcn_conv(xr, wt, b, g.handle(norm), self.act, ew_leaf)
         return y.T, st

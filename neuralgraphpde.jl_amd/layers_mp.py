@@ -20,8 +20,8 @@ import torch
 from . import _lib
 from . import functional as F
 from .graphs import EMPTYGRAPH, GNNGraph
-from .layers import (AbstractGNNContainerLayer, AbstractGNNLayer, Chain, Dense, _act_code, glorot_uniform, rows_of,
-                     zeros32)
+from .layers import (AbstractGNNContainerLayer, AbstractGNNLayer, Chain, Dense, _act_code, glorot_uniform, mat_of, rows_of,
+                     vec_of, zeros32)
 from .utils import wrapgraph
 
 
@@ -35,12 +35,23 @@ def _dense_stack(layer, ps, what):
 
 
 def _wt_b(ps):
-    return rows_of(ps["weight"]), (ps["bias"].reshape(-1) if "bias" in ps else None)
+    """(weight [in][out], bias [out] or None) of a Dense's parameters with no layer at hand: the bias is held to the weight's rows"""
+    wt = rows_of(ps["weight"])
+    return wt, (vec_of(ps["bias"], wt.shape[1], "bias") if "bias" in ps else None)
 
 
-def _stack_spec(stack):
-    """[(weight [in][out], bias or None, activation code)] of a Dense stack: what ngpde_edge_layer_* takes"""
-    return [(*_wt_b(ps), layer.act) for layer, ps in stack]
+def _stack_spec(stack, convert=True):
+    """[(weight [in][out], bias or None, activation code)] of a Dense stack: what ngpde_edge_layer_* takes.  Every weight and bias
+    is checked against its Dense (the rule at layers.rows_of): the entries take pointers only"""
+    return [(*layer.kernel_params(ps, convert), layer.act) for layer, ps in stack]
+
+
+class _StackParams:
+    """kernel_params of a container layer: its Dense stacks, each (field name, key of its parameters or None for an un-nested one)"""
+    stacks = ()
+
+    def kernel_params(self, ps, convert=True):
+        return [_stack_spec(_dense_stack(self.sublayer(name), ps if key is None else ps[key], name), convert) for name, key in self.stacks]
 
 
 def _node_data(g, device, exclude=()):
@@ -79,10 +90,11 @@ def _as_named(x):
 # ---- ExplicitEdgeConv ----------------------------------------------------------------------------------
 
 
-class ExplicitEdgeConv(AbstractGNNContainerLayer):
+class ExplicitEdgeConv(_StackParams, AbstractGNNContainerLayer):
     """ExplicitEdgeConv(ϕ; initialgraph, aggr=mean):  h'_i = aggr_j ϕ([h_i; h_j; x_j - x_i])  (src/layers.jl:84-112)"""
 
     layers = ("ϕ",)
+    stacks = (("ϕ", None),)
 
     def __init__(self, ϕ, *, initialgraph=None, aggr="mean"):
         self.ϕ, self.aggr = ϕ, aggr
@@ -94,9 +106,10 @@ class ExplicitEdgeConv(AbstractGNNContainerLayer):
         dev = next(iter(xn.values())).device
         for v in xn.values():
             _check_nodes(v, g)
+        (phi,) = self.kernel_params(ps)
         pos = _node_data(g, dev, exclude=[k for k in g.ndata if k != "x"])        # xi.x
         others = _node_data(g, dev, exclude=["x"])                                # drop(xi, :x) fixed part
-        y = F.edge_layer(g.handle(), _lib.LAYER_EDGECONV, self.aggr, list(xn.values()), _stack_spec(_dense_stack(self.ϕ, ps, "ϕ")),
+        y = F.edge_layer(g.handle(), _lib.LAYER_EDGECONV, self.aggr, list(xn.values()), phi,
                          node_feat=others, pos=pos)                                # propagate(message, g, aggr)  (:111)
         return y.T, st
 
@@ -104,11 +117,12 @@ class ExplicitEdgeConv(AbstractGNNContainerLayer):
 # ---- VMHConv ---------------------------------------------------------------------------------------------
 
 
-class VMHConv(AbstractGNNContainerLayer):
+class VMHConv(_StackParams, AbstractGNNContainerLayer):
     """VMHConv(ϕ, γ; initialgraph, aggr=mean):  m_i = aggr_j ϕ([h_i; h_j - h_i; x_j - x_i]), h' = γ([h_i; m_i])
     (src/layers.jl:295-332)"""
 
     layers = ("ϕ", "γ")
+    stacks = (("ϕ", "ϕ"), ("γ", "γ"))
 
     def __init__(self, ϕ, γ, *, initialgraph=None, aggr="mean"):
         self.ϕ, self.γ, self.aggr = ϕ, γ, aggr
@@ -120,22 +134,23 @@ class VMHConv(AbstractGNNContainerLayer):
         dev = next(iter(xn.values())).device
         for v in xn.values():
             _check_nodes(v, g)
+        phi, gam = self.kernel_params(ps)
         pos = _node_data(g, dev, exclude=[k for k in g.ndata if k != "x"])
         others = _node_data(g, dev, exclude=["x"])
-        y = F.edge_layer(g.handle(), _lib.LAYER_VMH, self.aggr, list(xn.values()), _stack_spec(_dense_stack(self.ϕ, ps["ϕ"], "ϕ")),
-                         _stack_spec(_dense_stack(self.γ, ps["γ"], "γ")), node_feat=others, pos=pos)     # :316-328
+        y = F.edge_layer(g.handle(), _lib.LAYER_VMH, self.aggr, list(xn.values()), phi, gam, node_feat=others, pos=pos)     # :316-328
         return y.T, st
 
 
 # ---- MPPDEConv -------------------------------------------------------------------------------------------
 
 
-class MPPDEConv(AbstractGNNContainerLayer):
+class MPPDEConv(_StackParams, AbstractGNNContainerLayer):
     """MPPDEConv(ϕ, ψ; initialgraph, aggr=mean):  m_i = aggr_j ϕ([h_i; h_j; d_i - d_j; e_ij; θ]),
     h'_i = ψ([h_i; m_i; θ])   (src/layers.jl:377-422).  θ = vcat(g.gdata) per graph; batched graphs must
     share one structure (:359-361) and be stored contiguously (:410, :418)."""
 
     layers = ("ϕ", "ψ")
+    stacks = (("ϕ", "ϕ"), ("ψ", "ψ"))
 
     def __init__(self, ϕ, ψ, *, aggr="mean", initialgraph=None):
         self.ϕ, self.ψ, self.aggr = ϕ, ψ, aggr
@@ -146,9 +161,9 @@ class MPPDEConv(AbstractGNNContainerLayer):
         h = rows_of(x)
         dev = h.device
         _check_nodes(h, g)
+        phi, psi = self.kernel_params(ps)
         handle = g.handle()
-        y = F.edge_layer(handle, _lib.LAYER_MPPDE, self.aggr, [h], _stack_spec(_dense_stack(self.ϕ, ps["ϕ"], "ϕ")),
-                         _stack_spec(_dense_stack(self.ψ, ps["ψ"], "ψ")), node_feat=g.packed("ndata", dev),     # :403-405
+        y = F.edge_layer(handle, _lib.LAYER_MPPDE, self.aggr, [h], phi, psi, node_feat=g.packed("ndata", dev),     # :403-405
                          edge_feat=_edge_data_p(g, handle, dev), theta=g.packed("gdata", dev))                 # :407, :397
         return y.T, st
 
@@ -174,14 +189,18 @@ class GNOConv(AbstractGNNContainerLayer):
         self.linear = Dense(self.in_chs, self.out_chs, activation, init_weight=init_weight, init_bias=init_bias, bias=bias)
         self.initialgraph = wrapgraph(initialgraph if initialgraph is not None else (lambda: EMPTYGRAPH))
 
+    def kernel_params(self, ps, convert=True):
+        """((linear weight [in][out], bias or None), ϕ's stack), sizes checked (the rule at layers.rows_of)"""
+        return self.linear.kernel_params(ps["linear"], convert), _stack_spec(_dense_stack(self.ϕ, ps["ϕ"], "ϕ"), convert)
+
     def __call__(self, x, ps, st):
         g = st["graph"]
         h = rows_of(x)
         dev = h.device
         _check_nodes(h, g)
+        (lwt, lb), phi = self.kernel_params(ps)
         handle = g.handle()
-        lwt, lb = _wt_b(ps["linear"])
-        y = F.gno_layer(handle, self.in_chs, self.out_chs, self.aggr, self.linear.act, h, lwt, lb, _stack_spec(_dense_stack(self.ϕ, ps["ϕ"], "ϕ")),
+        y = F.gno_layer(handle, self.in_chs, self.out_chs, self.aggr, self.linear.act, h, lwt, lb, phi,
                         node_feat=g.packed("ndata", dev), edge_feat=_edge_data_p(g, handle, dev))       # :517-547
         return y.T, st
 
@@ -258,21 +277,31 @@ class GATConv(AbstractGNNLayer):
             g._with_self_loops = sl
         return sl
 
+    def kernel_params(self, ps, convert=True):
+        """(weight [in][heads*c], a [heads][2c], bias or None) as the kernels take them, sizes checked (the rule at layers.rows_of): both
+        paths hand the library pointers, and neither ngpde_gat_layer_forward nor ngpde_gat_forward can see an array's length"""
+        c, h = self.out_chs, self.heads
+        wt = mat_of(ps["weight"], (c * h, self.in_chs), "GATConv: weight", convert)
+        a = mat_of(ps["a"], (2 * c, h), "GATConv: a", convert)
+        return wt, a, (vec_of(ps["bias"], c * h if self.concat else c, "GATConv: bias", convert) if "bias" in ps else None)
+
     def __call__(self, x, ps, st):
         g = st["graph"]
         xr = rows_of(x)
         _check_nodes(xr, g)
+        if xr.shape[1] != self.in_chs:
+            raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH,
+                                         f"DimensionMismatch: x has {xr.shape[1]} rows, GATConv expects {self.in_chs}")
+        wt, a, b = self.kernel_params(ps)
         gs = self._graph(g)
         handle = gs.handle()
         c, h = self.out_chs, self.heads
-        b = ps["bias"].reshape(-1) if "bias" in ps else None
         if self.concat and F.gat_layer_supported(handle, xr.shape[1], h, c):
             # 64 => heads x c = 64 on a graph whose tiles fit the LDS halo (BASELINE config 3): the whole layer is one launch
-            y = F.gat_layer(xr, rows_of(ps["weight"]), rows_of(ps["a"]), b, handle, h, c, self.negative_slope, self.act,
-                            gs.num_edges)
+            y = F.gat_layer(xr, wt, a, b, handle, h, c, self.negative_slope, self.act, gs.num_edges)
             return y.T, st
-        wx = F.dense([xr], rows_of(ps["weight"]), None, 0)                          # Wx = reshape(W x, c, heads, N)
-        out = F.gat_aggregate(wx, rows_of(ps["a"]), handle, h, c, self.negative_slope, gs.num_edges)
+        wx = F.dense([xr], wt, None, 0)                                             # Wx = reshape(W x, c, heads, N)
+        out = F.gat_aggregate(wx, a, handle, h, c, self.negative_slope, gs.num_edges)
         if self.concat:
             y = F.bias_act(out, None, b, self.act)
         else:                                                                       # mean over heads: a genuine linear map

@@ -170,7 +170,7 @@ class _SoftmaxFn(torch.autograd.Function):
     def forward(ctx, e, handle):
         lib = _lib.load()
         F._need_cuda(e)
-        e = e.contiguous()
+        e = F._f32(e)                # (softmax_edge_*_kernel read one float at a time)
         y = torch.empty_like(e)
         _lib.check(lib.ngpde_softmax_edge_neighbors_forward(handle.ptr, e.shape[1], _lib.ptr(e), _lib.ptr(y), _lib.current_stream()))
         ctx.handle = handle
@@ -181,7 +181,7 @@ class _SoftmaxFn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         (y,) = ctx.saved_tensors
-        dy = dy.contiguous()
+        dy = F._f32(dy)
         de = torch.empty_like(y)
         _lib.check(lib.ngpde_softmax_edge_neighbors_backward(ctx.handle.ptr, y.shape[1], _lib.ptr(y), _lib.ptr(dy), _lib.ptr(de),
                                                              _lib.current_stream()))

@@ -22,9 +22,10 @@ import numbers
 import torch
 
 from . import _lib
+from . import functional as F
 from .graphs import GNNGraph
-from .layers import AbstractExplicitLayer, Chain, GCNConv, rows_of
-from .layers_mp import GATConv, VMHConv, _dense_stack, _node_data, _wt_b
+from .layers import AbstractExplicitLayer, Chain, GCNConv, check_params, rows_of
+from .layers_mp import GATConv, VMHConv, _dense_stack, _node_data
 from .batches import _padded_batch, _canonical_batch
 from .plans import _rows_index, _check_plan_shapes, _Plan, _NodeGCN2Fn, _OdePlan, _ode_desc, _NodeOdeFn  # noqa: F401 (tools import _Plan from here)
 from .plans import _PlanPool, _Recent
@@ -733,10 +734,7 @@ class NeuralODE(AbstractExplicitLayer):
             return None
         if not u.is_cuda:
             raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, "NeuralODE: inputs must live on the GPU (no CPU fallback)")
-        p1, p2 = ps["layer_1"], ps["layer_2"]
-        b1 = p1["bias"].reshape(-1) if "bias" in p1 else None
-        b2 = p2["bias"].reshape(-1) if "bias" in p2 else None
-        w1, w2 = rows_of(p1["weight"]), rows_of(p2["weight"])
+        (w1, b1), (w2, b2) = (l.kernel_params(ps[n]) for n, l in zip(self.model.names(), self.model.chain))
         # the plan's entries take no sizes (they walk the handle's rows): what GCNConv.__call__ would have checked
         # (check_num_nodes, the matrix product's own DimensionMismatch) is checked here, before any kernel runs
         d = self.model.chain[0].in_chs
@@ -770,8 +768,7 @@ class NeuralODE(AbstractExplicitLayer):
         make = lambda: _OdePlan(handle, _ode_desc(_lib.RHS_GAT, self.solver, self.n_steps, self.dt, needs_grad, n_members, width=64, act=int(m.act),
                                                   heads=int(m.heads), head_width=int(m.out_chs), negative_slope=float(m.negative_slope)), "gat")
         plan = self._plans.acquire(key, needs_grad, make, self)      # (what the create raises goes to the caller)
-        b = ps["bias"].reshape(-1) if "bias" in ps else None
-        w, a = rows_of(ps["weight"]), rows_of(ps["a"])
+        w, a, b = m.kernel_params(ps)
         _check_plan_shapes("NeuralODE(GATConv)", u, plan.n_nodes * plan.members, 64, [("weight", w, (64, 64))], [("bias", b, 64)])
         if a.numel() != 2 * m.out_chs * m.heads:
             raise _lib.DimensionMismatch(_lib.ERR_DIMENSION_MISMATCH, f"DimensionMismatch: NeuralODE(GATConv): attention vector has "
@@ -801,7 +798,7 @@ class NeuralODE(AbstractExplicitLayer):
         for stack in (phi, gam):
             d, a = [], []
             for layer, p in stack:
-                wt, b = _wt_b(p)
+                wt, b = layer.kernel_params(p)
                 wb += [wt, b]
                 d.append(wt.shape[0])
                 a.append(layer.act)
@@ -896,6 +893,11 @@ class NeuralODE(AbstractExplicitLayer):
 
     def __call__(self, x, ps, st):
         u = rows_of(x)
+        # every parameter against its layer, before a plan, a graph handle or a library entry sees it (the rule at layers.rows_of):
+        # the device-resident plans' entries take pointers only
+        check_params(self.model, ps)
+        if u.is_cuda:      # one device for the call: a plan's entries take pointers, and a host pointer among them is a device fault
+            F._need_cuda(*[p for p in _leaves(ps) if isinstance(p, torch.Tensor)])
         needs_grad = torch.is_grad_enabled() and (u.requires_grad or any(
             isinstance(v, torch.Tensor) and v.requires_grad for v in _leaves(ps)))      # (parameter trees of any depth: VMHConv's phi / gamma chains)
         if not self.adaptive:      # (an adaptive solve's statistics are set by the solve itself)
@@ -911,6 +913,11 @@ class NeuralODE(AbstractExplicitLayer):
         if not u.is_cuda:
             raise _lib.ArgumentError(_lib.ERR_INVALID_ARGUMENT, "NeuralODE: inputs must live on the GPU (no CPU fallback)")
         leaves = _leaves(ps)
+        if any(isinstance(p, torch.Tensor) and p.dtype != torch.float32 for p in leaves):
+            # the stages' cotangents are summed by float32 launches (ngpde_accumulate_many): parameters of another real type enter
+            # the solve through the differentiable conversion, whose pullback casts the sum back to the leaf's type
+            leaves = [p.to(torch.float32) if isinstance(p, torch.Tensor) else p for p in leaves]
+            ps = _rebuild(ps, iter(leaves))
         if self.capture:
             # every GNNGraph leaf of the state tree (a container's graphs sit in st["layer_k"]["graph"]): the captures bake in
             # the addresses of their derived arrays.  The entry keeps `st` -- and with it the graphs -- alive, so an id cannot be

@@ -14,6 +14,7 @@ import weakref
 import torch
 
 from . import _lib
+from . import functional as F
 
 class _Token:
     __slots__ = ("__weakref__",)
@@ -175,7 +176,7 @@ class _NodeGCN2Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, w1t, b1, w2t, b2, plan):
         lib = _lib.load()
-        u, w1t, w2t = u.contiguous(), w1t.contiguous(), w2t.contiguous()
+        u, w1t, w2t, b1, b2 = (F._f32a(t) for t in (u, w1t, w2t, b1, b2))     # (the persistent kernels read float4 through these)
         uT = torch.empty_like(u)
         _lib.check(lib.ngpde_node_gcn2_forward(plan.ptr, _lib.ptr(u), _lib.ptr(w1t), _lib.ptr(b1), _lib.ptr(w2t),
                                                _lib.ptr(b2), _lib.ptr(uT), _lib.current_stream()))
@@ -192,7 +193,7 @@ class _NodeGCN2Fn(torch.autograd.Function):
         us, ws, b1s, b2s = ctx.shapes
         mk = lambda s: None if s is None else torch.empty(s, dtype=torch.float32, device=ctx.dev)
         du0, dw1, dw2, db1, db2 = mk(us), mk(ws), mk(ws), mk(b1s), mk(b2s)
-        duT = duT.contiguous()
+        duT = F._f32a(duT)
         # NGPDE_ERR_STATE if another forward has overwritten this solve's tape (cannot happen through NeuralODE.__call__,
         # which takes a free plan for every outstanding solve; a second backward of the same solve is fine: the tape is kept)
         _lib.check(lib.ngpde_node_expect_generation(ctx.plan.ptr, ctx.generation))
@@ -253,10 +254,10 @@ class _NodeOdeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, plan, save, att, *wb):
         lib = _lib.load()
-        u = u.contiguous()
-        ws = [w.contiguous() for w in wb[0::2]]
-        bs = [None if b is None else b.contiguous() for b in wb[1::2]]
-        att = None if att is None else att.contiguous()
+        u = F._f32a(u)                                  # (the persistent kernels read float4 through these)
+        ws = [F._f32a(w) for w in wb[0::2]]
+        bs = [F._f32a(b) for b in wb[1::2]]
+        att = F._f32a(att)
         nf = plan.n_first if plan.n_first else len(ws)
         prm = _lib.OdeParams()
         for l, (w, b) in enumerate(zip(ws, bs)):
@@ -282,7 +283,7 @@ class _NodeOdeFn(torch.autograd.Function):
         att = saved.pop(0) if ctx.has_att else None
         ws = saved
         dev = ws[0].device
-        dout = dout.contiguous()
+        dout = F._f32a(dout)
         du0 = torch.empty(ctx.ushape, dtype=torch.float32, device=dev)
         dws = [torch.empty_like(w) for w in ws]
         dbs = [torch.empty((w.shape[1],), dtype=torch.float32, device=dev) if hb else None for w, hb in zip(ws, ctx.has_bias)]
