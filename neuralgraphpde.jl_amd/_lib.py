@@ -312,6 +312,18 @@ SIGNATURES = {
     "ngpde_node_gat_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# The second block of the ABI, include/ngpde_interp.h (two-set search and k-NN interpolation): every symbol that header declares,
+# applied by load() next to SIGNATURES.  tests/test_interp_host.py holds this table to what tests/test_abi.py holds SIGNATURES to.
+INTERP_SIGNATURES = {
+    "ngpde_knn_query": (_i32, [_i64, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ngpde_radius_query": (_i32, [_i64, _i64, _i32, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_knn_interp_weights": (_i32, [_i64, _i32, _vp, _vp, _vp]),
+    "ngpde_knn_interp_forward": (_i32, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_knn_interp_transpose_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ngpde_knn_interp_transpose": (_i32, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ngpde_knn_interp_backward": (_i32, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -326,7 +338,7 @@ def load():
             "or `make -C neuralgraphpde.jl_amd/csrc`.  There is no CPU fallback for the hot path.")
     import torch  # noqa: F401  -- makes torch's libamdhip64.so the process's HIP runtime before ours resolves it
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -10,6 +10,25 @@
 // Both hold when (1) the cell edge is >= 1.01 * the largest |p_i - p_j| per coordinate that the float rule can accept,
 // (2) a cell coordinate is wrong by at most 1e-3 cells, and (3) cell and 1 / cell are finite and positive.  (1) fails for
 // a cell of 1.01 r where squares leave the float range, which is what the three rules below are for.
+//
+// Two-set search (ngpde_knn_query / ngpde_radius_query, include/ngpde_interp.h).  The grid is sized over the DATA points alone
+// (their box, their count): a grid over the union would be coarsened by a handful of far queries until the cells of the data no
+// longer separate anything, and the data's grid is the one the one-set entries already prove.  A query may then lie anywhere, and
+// cell_of_query clamps its cell coordinate to the grid.  Covering and the ring bound survive the clamp: let q' be q with every
+// coordinate clamped to the data's [lo, hi].  Every data coordinate lies in [lo, hi], so |p - q'| <= |p - q| per coordinate for
+// every data point p -- a clamped query is at least as far from every point, hence from every cell, as its clamped position is.
+//   the cell   q' lies in the box, and the clamped cell of q is a cell condition (2) allows for q': below lo the float difference
+//              is negative, the cell is 0 and q' = lo has coordinate exactly 0; above hi the float coordinate is monotone in q, so
+//              it is >= the one of q' = hi, and the clamp returns either that cell or the top cell, whose exact lower edge
+//              top <= ext / cell is within the same 1e-3 of hi's coordinate;
+//   covering   a pair (q, p) the float rule accepts has |p - q| <= the bound of (1) per coordinate, so |p - q'| has it too, and
+//              the argument for two points of the box puts p within one cell of q''s cell per dimension;
+//   ring bound a point p in a cell at Chebyshev distance > ring from q's clamped cell is >= (ring - 0.002) cells from q' in one
+//              coordinate, so at least as far from q in that coordinate, and its float d2 (a sum of non-negative terms, each
+//              rounded monotonically) is >= reach^2 as for two points of the box.
+// A far query pays for this in time, not in correctness: its k-th distance exceeds every ring's reach until the walk has seen
+// the whole grid of its graph.  What must hold of the two sets TOGETHER is the span: q - lo is formed in float, so span_is_finite is
+// asked of the union's box.  tests/host/neighbor_query_check.cpp checks covering and the ring bound for clamped queries by brute force.
 #pragma once
 #include <algorithm>
 #include <cfloat>
@@ -46,6 +65,20 @@ NGPDE_GRID_HD void cell_of(const Grid &g, const float *p, int *c) {
     const int x = (int)((p[d] - g.lo[d]) * g.inv);
     const int top = g.nc[d] - 1;
     c[d] = x < 0 ? 0 : (x > top ? top : x);
+  }
+}
+// cell_of for a point of a second set (a query), which may lie anywhere relative to the grid: the same expression, clamped as a
+// float BEFORE the conversion (a coordinate thousands of boxes away, or inf after the product, has no int value).  For a coordinate
+// inside the grid the result is cell_of's.  The header comment says why a clamped cell serves.
+template <int DIM>
+NGPDE_GRID_HD void cell_of_query(const Grid &g, const float *p, int *c) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int d = 0; d < DIM; ++d) {
+    const float x = (p[d] - g.lo[d]) * g.inv;
+    const int top = g.nc[d] - 1;
+    c[d] = x >= (float)top ? top : (x > 0.f ? (int)x : 0);
   }
 }
 template <int DIM>

@@ -23,6 +23,10 @@
 // ranges; counts -> scan -> fill -> per-row sort.  k-NN walks rings of cells until the k-th distance is proven.
 // The grid's sizing, cell_of and the curve quantisation are host code in neighbor_grid.h, checked on the host by
 // tests/host/neighbor_grid_check.cpp.
+// Two-set search (ngpde_knn_query, ngpde_radius_query; include/ngpde_interp.h): the same rule and the same kernels with a point of a
+// SECOND set as the searcher (template parameter QUERY, struct Searcher).  The grid is the data points'; a query's cell is clamped
+// to it (cell_of_query; neighbor_grid.h's header says why covering and the ring bound survive that), results are indexed by the
+// caller's query order, which is also the order the queries are processed in (a regular target grid is already coherent).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -30,6 +34,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "../../include/ngpde_interp.h"
 #include "common.h"
 #include "device_scratch.h"
 #include "neighbor_grid.h"
@@ -148,32 +153,55 @@ __device__ __forceinline__ void for_block(const Grid &g, int graph, const int *c
   }
 }
 
-// FILL = false: deg[i] = number of neighbours; FILL = true: writes them (unsorted) at rowptr[i]
-template <int DIM, bool FILL>
+// Who searches the sorted points.  QUERY = false: one of them, p its sorted position (the one-set graphs).  QUERY = true: point p of a
+// second set, in the caller's order (`from` = the queries, qgid their graph ids or NULL): its cell is clamped to the data's grid,
+// its graph is its own indicator's, and no sorted position is "itself".
+template <int DIM, bool QUERY>
+struct Searcher {
+  float a[DIM];
+  int c[DIM];
+  int graph;
+  int32_t i;   // the row the results belong to: the point's original index, or the query's
+  __device__ __forceinline__ Searcher(int64_t p, const Grid &g, const float *__restrict__ from, const int32_t *__restrict__ sidx,
+                                      const unsigned *__restrict__ key_sorted, const int32_t *__restrict__ qgid, int id_base) {
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) a[d] = from[p * DIM + d];
+    if constexpr (QUERY) {
+      cell_of_query<DIM>(g, a, c);
+      graph = qgid ? qgid[p] - id_base : 0;
+      i = (int32_t)p;
+    } else {
+      cell_of<DIM>(g, a, c);
+      graph = (int)(key_sorted[p] / (unsigned)g.cells);
+      i = sidx[p];
+    }
+  }
+};
+
+// FILL = false: deg[i] = number of neighbours; FILL = true: writes them (unsorted) at rowptr[i].  n = the number of searchers
+// (`from`: the sorted points themselves, or the queries with their graph ids qgid); QUERY rows have no `self` list.
+template <int DIM, bool FILL, bool QUERY>
 __global__ void radius_kernel(int64_t n, Grid g, float r2, int self_loops, int out_base, const float *__restrict__ spts,
                               const int32_t *__restrict__ sidx, const unsigned *__restrict__ key_sorted,
                               const int32_t *__restrict__ start, int32_t *__restrict__ deg, unsigned long long *__restrict__ total,
-                              const int32_t *__restrict__ rowptr, int32_t *__restrict__ nbr, int32_t *__restrict__ self) {
+                              const int32_t *__restrict__ rowptr, int32_t *__restrict__ nbr, int32_t *__restrict__ self,
+                              const float *__restrict__ from, const int32_t *__restrict__ qgid, int id_base) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int cnt = 0;
   if (p < n) {
-    float a[DIM];
-    int c[DIM];
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) a[d] = spts[p * DIM + d];
-    cell_of<DIM>(g, a, c);
-    const int graph = (int)(key_sorted[p] / (unsigned)g.cells);
-    const int32_t i = sidx[p];
+    const Searcher<DIM, QUERY> me(p, g, from, sidx, key_sorted, qgid, id_base);
+    const float *a = me.a;
+    const int32_t i = me.i;
     int32_t w = FILL ? rowptr[i] : 0;
-    for_block<DIM>(g, graph, c, start, [&](int q) {
+    for_block<DIM>(g, me.graph, me.c, start, [&](int q) {
       float b[DIM];
 #pragma unroll
       for (int d = 0; d < DIM; ++d) b[d] = spts[(int64_t)q * DIM + d];
-      const bool hit = dist2<DIM>(a, b) <= r2 && (self_loops || q != (int)p);
+      const bool hit = dist2<DIM>(a, b) <= r2 && (QUERY || self_loops || q != (int)p);
       if (hit) {
         if constexpr (FILL) {
           nbr[w] = sidx[q] + out_base;
-          self[w] = i + out_base;
+          if constexpr (!QUERY) self[w] = i + out_base;
           ++w;
         }
         ++cnt;
@@ -191,30 +219,30 @@ __global__ void radius_kernel(int64_t n, Grid g, float r2, int self_loops, int o
 // k nearest (d2, index) pairs per point; the running list lives in LDS, one column per thread:
 // list entry m of thread l at [m * 64 + l]
 constexpr int kKnnThreads = 64;
-template <int DIM>
+// QUERY = false writes the COO lists s_out / t_out and ORs 1 into *short_rows; QUERY = true writes s_out = idx [n][k] and, where
+// given, d2_out [n][k] (t_out unused) and keeps the smallest graph of a short row in *short_rows (atomicMin).
+template <int DIM, bool QUERY>
 __global__ void knn_kernel(int64_t n, Grid g, int k, int self_loops, int out_base, int dir_out, const float *__restrict__ spts,
                            const int32_t *__restrict__ sidx, const unsigned *__restrict__ key_sorted,
                            const int32_t *__restrict__ start, int32_t *__restrict__ s_out, int32_t *__restrict__ t_out,
-                           int *__restrict__ short_rows) {
+                           int *__restrict__ short_rows, const float *__restrict__ from, const int32_t *__restrict__ qgid, int id_base,
+                           float *__restrict__ d2_out) {
   extern __shared__ float knn_lds[];
   float *ld = knn_lds + threadIdx.x;                        // distances
   int *li = (int *)(knn_lds + (size_t)k * kKnnThreads) + threadIdx.x;   // original indices
   const int64_t p = (int64_t)blockIdx.x * kKnnThreads + threadIdx.x;
   if (p >= n) return;
-  float a[DIM];
-  int c[DIM];
-#pragma unroll
-  for (int d = 0; d < DIM; ++d) a[d] = spts[p * DIM + d];
-  cell_of<DIM>(g, a, c);
-  const int graph = (int)(key_sorted[p] / (unsigned)g.cells);
-  const int base = graph * g.cells;
-  const int32_t i = sidx[p];
+  const Searcher<DIM, QUERY> me(p, g, from, sidx, key_sorted, qgid, id_base);
+  const float *a = me.a;
+  const int *c = me.c;
+  const int base = me.graph * g.cells;
+  const int32_t i = me.i;
   int have = 0;
   int max_ring = 0;
 #pragma unroll
   for (int d = 0; d < DIM; ++d) max_ring = max(max_ring, max(c[d], g.nc[d] - 1 - c[d]));
   auto offer = [&](int q) {
-    if (!self_loops && q == (int)p) return;
+    if (!QUERY && !self_loops && q == (int)p) return;
     float b[DIM];
 #pragma unroll
     for (int d = 0; d < DIM; ++d) b[d] = spts[(int64_t)q * DIM + d];
@@ -298,11 +326,19 @@ __global__ void knn_kernel(int64_t n, Grid g, int k, int self_loops, int out_bas
     // every unvisited point is at least ring * cell away (the point lies inside its home cell)
     if (have == k && ring > 0 && ld[(k - 1) * kKnnThreads] < ring_reach2(g, ring)) break;
   }
-  if (have < k) atomicOr(short_rows, 1);
-  int32_t *nb = dir_out ? t_out : s_out, *me = dir_out ? s_out : t_out;
-  for (int m = 0; m < k; ++m) {
-    nb[(int64_t)i * k + m] = (m < have ? li[m * kKnnThreads] : i) + out_base;
-    me[(int64_t)i * k + m] = i + out_base;
+  if constexpr (QUERY) {
+    if (have < k) atomicMin(short_rows, me.graph);
+    for (int m = 0; m < k; ++m) {
+      s_out[(int64_t)i * k + m] = (m < have ? li[m * kKnnThreads] : 0) + out_base;
+      if (d2_out) d2_out[(int64_t)i * k + m] = m < have ? ld[m * kKnnThreads] : INFINITY;
+    }
+  } else {
+    if (have < k) atomicOr(short_rows, 1);
+    int32_t *nb = dir_out ? t_out : s_out, *own = dir_out ? s_out : t_out;
+    for (int m = 0; m < k; ++m) {
+      nb[(int64_t)i * k + m] = (m < have ? li[m * kKnnThreads] : i) + out_base;
+      own[(int64_t)i * k + m] = i + out_base;
+    }
   }
 }
 
@@ -354,7 +390,7 @@ __global__ void curve_key_kernel(int64_t n, Quant qz, const float *__restrict__ 
 }
 
 int32_t bounding_box(int64_t n, int dim, const float *pts, const int32_t *gid, int id_base, int n_graphs, hipStream_t stream,
-                     Scratch &sc, float *lo, float *hi) {
+                     Scratch &sc, float *lo, float *hi, const char *what = "points", const char *ids = "graph_indicator") {
   unsigned *box = nullptr;
   int *bad = nullptr;
   int32_t st;
@@ -370,15 +406,14 @@ int32_t bounding_box(int64_t n, int dim, const float *pts, const int32_t *gid, i
   NGPDE_HIP_CHECK(hipMemcpyAsync(h, box, sizeof(h), hipMemcpyDeviceToHost, stream));
   NGPDE_HIP_CHECK(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, stream));
   NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
-  NGPDE_REQUIRE(!h_bad, NGPDE_ERR_INVALID_ARGUMENT, "graph_indicator holds an id outside %d:%d", id_base, id_base + n_graphs - 1);
+  NGPDE_REQUIRE(!h_bad, NGPDE_ERR_INVALID_ARGUMENT, "%s holds an id outside %d:%d", ids, id_base, id_base + n_graphs - 1);
   for (int d = 0; d < 3; ++d) {
     lo[d] = d < dim ? from_ordered_bits(h[d]) : 0.f;
     hi[d] = d < dim ? from_ordered_bits(h[3 + d]) : 0.f;
-    NGPDE_REQUIRE(std::isfinite(lo[d]) && std::isfinite(hi[d]), NGPDE_ERR_INVALID_ARGUMENT,
-                  "points hold a non-finite coordinate");
+    NGPDE_REQUIRE(std::isfinite(lo[d]) && std::isfinite(hi[d]), NGPDE_ERR_INVALID_ARGUMENT, "%s hold a non-finite coordinate", what);
   }
-  NGPDE_REQUIRE(span_is_finite(dim, lo, hi), NGPDE_ERR_INVALID_ARGUMENT,
-                "points span more than the largest finite float in a coordinate");
+  NGPDE_REQUIRE(span_is_finite(dim, lo, hi), NGPDE_ERR_INVALID_ARGUMENT, "%s span more than the largest finite float in a coordinate",
+                what);
   return NGPDE_OK;
 }
 
@@ -430,8 +465,9 @@ int32_t radius_graph_impl(int64_t n, const float *pts, float r, const int32_t *g
   NGPDE_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(unsigned long long), stream));
   NGPDE_HIP_CHECK(hipMemsetAsync(deg, 0, ((size_t)n + 1) * sizeof(int32_t), stream));
   const float r2 = r * r;
-  hipLaunchKernelGGL((radius_kernel<DIM, false>), dim3(blocks_for(n)), dim3(kB), 0, stream, n, g, r2, self_loops, out_base, so.pts,
-                     so.idx, so.key, so.start, deg, total, (const int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
+  hipLaunchKernelGGL((radius_kernel<DIM, false, false>), dim3(blocks_for(n)), dim3(kB), 0, stream, n, g, r2, self_loops, out_base, so.pts,
+                     so.idx, so.key, so.start, deg, total, (const int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr,
+                     (const float *)so.pts, (const int32_t *)nullptr, 0);
   NGPDE_LAUNCH_CHECK("radius_kernel(count)");
   unsigned long long h_total = 0;
   NGPDE_HIP_CHECK(hipMemcpyAsync(&h_total, total, sizeof(h_total), hipMemcpyDeviceToHost, stream));
@@ -449,8 +485,9 @@ int32_t radius_graph_impl(int64_t n, const float *pts, float r, const int32_t *g
   int32_t *nbr = nullptr;
   if ((st = sc.get(&nbr, (size_t)h_total))) return st;
   int32_t *nb_out = dir_out ? t : s, *me_out = dir_out ? s : t;
-  hipLaunchKernelGGL((radius_kernel<DIM, true>), dim3(blocks_for(n)), dim3(kB), 0, stream, n, g, r2, self_loops, out_base, so.pts,
-                     so.idx, so.key, so.start, (int32_t *)nullptr, (unsigned long long *)nullptr, (const int32_t *)rowptr, nbr, me_out);
+  hipLaunchKernelGGL((radius_kernel<DIM, true, false>), dim3(blocks_for(n)), dim3(kB), 0, stream, n, g, r2, self_loops, out_base, so.pts,
+                     so.idx, so.key, so.start, (int32_t *)nullptr, (unsigned long long *)nullptr, (const int32_t *)rowptr, nbr, me_out,
+                     (const float *)so.pts, (const int32_t *)nullptr, 0);
   NGPDE_LAUNCH_CHECK("radius_kernel(fill)");
   const unsigned end_bit = bits_for(std::max<int64_t>(n + out_base + 1, 2));
   auto sort = [&](void *tmp, size_t &bytes) {
@@ -476,9 +513,10 @@ int32_t knn_graph_impl(int64_t n, const float *pts, int k, const int32_t *gid, i
   if ((st = sc.get(&short_rows, 1))) return st;
   NGPDE_HIP_CHECK(hipMemsetAsync(short_rows, 0, sizeof(int), stream));
   const size_t lds = (size_t)k * kKnnThreads * 8;
-  NGPDE_HIP_CHECK(hipFuncSetAttribute((const void *)knn_kernel<DIM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(knn_kernel<DIM>, dim3((unsigned)((n + kKnnThreads - 1) / kKnnThreads)), dim3(kKnnThreads), lds, stream, n, g, k,
-                     self_loops, out_base, dir_out, so.pts, so.idx, so.key, so.start, s, t, short_rows);
+  NGPDE_HIP_CHECK(hipFuncSetAttribute((const void *)knn_kernel<DIM, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((knn_kernel<DIM, false>), dim3((unsigned)((n + kKnnThreads - 1) / kKnnThreads)), dim3(kKnnThreads), lds, stream, n, g, k,
+                     self_loops, out_base, dir_out, so.pts, so.idx, so.key, so.start, s, t, short_rows, (const float *)so.pts,
+                     (const int32_t *)nullptr, 0, (float *)nullptr);
   NGPDE_LAUNCH_CHECK("knn_kernel");
   int h_short = 0;
   NGPDE_HIP_CHECK(hipMemcpyAsync(&h_short, short_rows, sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -506,6 +544,120 @@ int32_t spatial_order_impl(int64_t n, const float *pts, const int32_t *gid, int 
   };
   if ((st = with_temp(sc, sort))) return st;
   NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
+  return NGPDE_OK;
+}
+
+// ---- two-set search: the data points are boxed, gridded and sorted as above, the queries are boxed for their checks alone ------
+// boxes of both sets with their id and finiteness checks; the span that must be finite is the union's (q - lo is formed in float)
+int32_t two_boxes(int64_t n, int64_t m, int dim, const float *pts, const float *qs, const int32_t *gid, const int32_t *qgid, int id_base,
+                  int n_graphs, hipStream_t stream, Scratch &sc, float *lo, float *hi) {
+  float qlo[3], qhi[3], ulo[3], uhi[3];
+  int32_t st;
+  if ((st = bounding_box(n, dim, pts, gid, id_base, n_graphs, stream, sc, lo, hi, "points", "point_graph_id")) ||
+      (st = bounding_box(m, dim, qs, qgid, id_base, n_graphs, stream, sc, qlo, qhi, "queries", "query_graph_id")))
+    return st;
+  for (int d = 0; d < 3; ++d) {
+    ulo[d] = std::min(lo[d], qlo[d]);
+    uhi[d] = std::max(hi[d], qhi[d]);
+  }
+  NGPDE_REQUIRE(span_is_finite(dim, ulo, uhi), NGPDE_ERR_INVALID_ARGUMENT,
+                "points and queries together span more than the largest finite float in a coordinate");
+  return NGPDE_OK;
+}
+
+constexpr int kNoShortGraph = 0x7f7f7f7f;   // (what hipMemset writes byte by byte; above every graph number)
+
+template <int DIM>
+int32_t knn_query_impl(int64_t n, int64_t m, const float *pts, const float *qs, int k, const int32_t *gid, const int32_t *qgid,
+                       int n_graphs, int id_base, int out_base, int32_t *idx, float *d2, hipStream_t stream) {
+  Scratch sc;
+  float lo[3], hi[3];
+  int32_t st;
+  if ((st = two_boxes(n, m, DIM, pts, qs, gid, qgid, id_base, n_graphs, stream, sc, lo, hi))) return st;
+  const float want = knn_want(DIM, lo, hi, n, n_graphs, k);
+  const Grid g = make_grid(DIM, lo, hi, want, cell_budget(n), n_graphs);
+  Sorted so;
+  if ((st = sort_into_cells<DIM>(n, g, n_graphs, pts, gid, id_base, stream, sc, so))) return st;
+  int *short_graph = nullptr;
+  if ((st = sc.get(&short_graph, 1))) return st;
+  NGPDE_HIP_CHECK(hipMemsetAsync(short_graph, 0x7f, sizeof(int), stream));
+  const size_t lds = (size_t)k * kKnnThreads * 8;
+  NGPDE_HIP_CHECK(hipFuncSetAttribute((const void *)knn_kernel<DIM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((knn_kernel<DIM, true>), dim3((unsigned)((m + kKnnThreads - 1) / kKnnThreads)), dim3(kKnnThreads), lds, stream, m, g, k,
+                     1, out_base, 0, so.pts, so.idx, so.key, so.start, idx, (int32_t *)nullptr, short_graph, qs, qgid, id_base, d2);
+  NGPDE_LAUNCH_CHECK("knn_kernel(query)");
+  int h_short = kNoShortGraph;
+  NGPDE_HIP_CHECK(hipMemcpyAsync(&h_short, short_graph, sizeof(int), hipMemcpyDeviceToHost, stream));
+  NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
+  if (h_short != kNoShortGraph) {
+    int32_t bounds[2] = {0, 0};   // the graph's points are the sorted positions start[graph * cells] .. start[(graph + 1) * cells]
+    NGPDE_HIP_CHECK(hipMemcpy(&bounds[0], so.start + (size_t)h_short * g.cells, sizeof(int32_t), hipMemcpyDeviceToHost));
+    NGPDE_HIP_CHECK(hipMemcpy(&bounds[1], so.start + ((size_t)h_short + 1) * g.cells, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return fail(NGPDE_ERR_INVALID_ARGUMENT, "knn_query: graph %d has queries and %d points, fewer than k = %d", h_short + id_base,
+                bounds[1] - bounds[0], k);
+  }
+  return NGPDE_OK;
+}
+
+template <int DIM>
+int32_t radius_query_impl(int64_t n, int64_t m, const float *pts, const float *qs, float r, const int32_t *gid, const int32_t *qgid,
+                          int n_graphs, int id_base, int out_base, int64_t capacity, int32_t *ptr, int32_t *nbr_out, int64_t *n_found,
+                          hipStream_t stream) {
+  Scratch sc;
+  float lo[3], hi[3];
+  int32_t st;
+  if ((st = two_boxes(n, m, DIM, pts, qs, gid, qgid, id_base, n_graphs, stream, sc, lo, hi))) return st;
+  const Grid g = make_grid(DIM, lo, hi, radius_want(r), cell_budget(n), n_graphs);
+  Sorted so;
+  if ((st = sort_into_cells<DIM>(n, g, n_graphs, pts, gid, id_base, stream, sc, so))) return st;
+  int32_t *deg = nullptr;
+  unsigned long long *total = nullptr;
+  if ((st = sc.get(&deg, (size_t)m + 1)) || (st = sc.get(&total, 1))) return st;
+  NGPDE_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(unsigned long long), stream));
+  NGPDE_HIP_CHECK(hipMemsetAsync(deg, 0, ((size_t)m + 1) * sizeof(int32_t), stream));
+  const float r2 = r * r;
+  hipLaunchKernelGGL((radius_kernel<DIM, false, true>), dim3(blocks_for(m)), dim3(kB), 0, stream, m, g, r2, 1, out_base, so.pts, so.idx,
+                     so.key, so.start, deg, total, (const int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, qs, qgid, id_base);
+  NGPDE_LAUNCH_CHECK("radius_kernel(query count)");
+  unsigned long long h_total = 0;
+  NGPDE_HIP_CHECK(hipMemcpyAsync(&h_total, total, sizeof(h_total), hipMemcpyDeviceToHost, stream));
+  NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
+  *n_found = (int64_t)h_total;
+  if (!nbr_out) return NGPDE_OK;   // count only
+  NGPDE_REQUIRE(h_total <= 0x7fffffffull, NGPDE_ERR_UNSUPPORTED, "radius_query found %llu pairs: more than int32 positions", h_total);
+  NGPDE_REQUIRE((int64_t)h_total <= capacity, NGPDE_ERR_INVALID_ARGUMENT, "radius_query found %llu pairs, the output array holds %lld",
+                h_total, (long long)capacity);
+  auto scan = [&](void *tmp, size_t &bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, deg, ptr, 0, (size_t)m + 1, rocprim::plus<int32_t>(), stream);
+  };
+  if ((st = with_temp(sc, scan))) return st;
+  if (h_total > 0) {
+    int32_t *nbr = nullptr;
+    if ((st = sc.get(&nbr, (size_t)h_total))) return st;
+    hipLaunchKernelGGL((radius_kernel<DIM, true, true>), dim3(blocks_for(m)), dim3(kB), 0, stream, m, g, r2, 1, out_base, so.pts, so.idx,
+                       so.key, so.start, (int32_t *)nullptr, (unsigned long long *)nullptr, (const int32_t *)ptr, nbr, (int32_t *)nullptr,
+                       qs, qgid, id_base);
+    NGPDE_LAUNCH_CHECK("radius_kernel(query fill)");
+    const unsigned end_bit = bits_for(std::max<int64_t>(n + out_base + 1, 2));
+    auto sort = [&](void *tmp, size_t &bytes) {
+      return rocprim::segmented_radix_sort_keys(tmp, bytes, nbr, nbr_out, (unsigned)h_total, (unsigned)m, ptr, ptr + 1, 0u, end_bit, stream);
+    };
+    if ((st = with_temp(sc, sort))) return st;
+  }
+  NGPDE_HIP_CHECK(hipStreamSynchronize(stream));
+  return NGPDE_OK;
+}
+
+int32_t check_query(const char *fn, int64_t n, int64_t m, int32_t dim, const float *pts, const float *qs, const int32_t *gid,
+                    const int32_t *qgid, int32_t n_graphs) {
+  NGPDE_REQUIRE(n >= 0 && n <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "%s: number of points %lld outside 0:2^31-1", fn, (long long)n);
+  NGPDE_REQUIRE(m >= 0 && m <= 0x7fffffffLL, NGPDE_ERR_INVALID_ARGUMENT, "%s: number of queries %lld outside 0:2^31-1", fn, (long long)m);
+  NGPDE_REQUIRE(dim >= 1 && dim <= 3, NGPDE_ERR_UNSUPPORTED, "%s: neighbour search supports 1, 2 or 3 coordinates, got %d", fn, dim);
+  NGPDE_REQUIRE(n == 0 || pts != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "%s: points is NULL", fn);
+  NGPDE_REQUIRE(m == 0 || qs != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "%s: queries is NULL", fn);
+  NGPDE_REQUIRE(n_graphs >= 1, NGPDE_ERR_INVALID_ARGUMENT, "%s: n_graphs must be >= 1", fn);
+  NGPDE_REQUIRE((gid != nullptr || n == 0) && (qgid != nullptr || m == 0) || n_graphs == 1, NGPDE_ERR_INVALID_ARGUMENT,
+                "%s: n_graphs > 1 needs point_graph_id and query_graph_id", fn);
   return NGPDE_OK;
 }
 
@@ -576,6 +728,52 @@ int32_t ngpde_spatial_order(int64_t n, int32_t dim, const float *points, const i
     case 1: return spatial_order_impl<1>(n, points, graph_id, n_graphs, id_base, order, hs);
     case 2: return spatial_order_impl<2>(n, points, graph_id, n_graphs, id_base, order, hs);
     default: return spatial_order_impl<3>(n, points, graph_id, n_graphs, id_base, order, hs);
+  }
+}
+
+int32_t ngpde_knn_query(int64_t n, int64_t m, int32_t dim, const float *points, const float *queries, int32_t k,
+                        const int32_t *point_graph_id, const int32_t *query_graph_id, int32_t n_graphs, int32_t id_base,
+                        int32_t index_base, int32_t *idx, float *d2, ngpde_stream_t stream) {
+  NGPDE_RANGE();
+  int32_t st = check_query("knn_query", n, m, dim, points, queries, point_graph_id, query_graph_id, n_graphs);
+  if (st) return st;
+  NGPDE_REQUIRE(k >= 0, NGPDE_ERR_INVALID_ARGUMENT, "knn_query: k must be >= 0 (got %d)", k);
+  NGPDE_REQUIRE(k <= NGPDE_KNN_MAX_K, NGPDE_ERR_UNSUPPORTED, "knn_query supports k <= %d, got %d", NGPDE_KNN_MAX_K, k);
+  NGPDE_REQUIRE(m * (int64_t)k <= 0x7fffffffLL, NGPDE_ERR_UNSUPPORTED, "knn_query: more than int32 positions");
+  if (m == 0 || k == 0) return NGPDE_OK;
+  NGPDE_REQUIRE(idx != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "knn_query: idx is NULL");
+  NGPDE_REQUIRE(n >= (int64_t)k, NGPDE_ERR_INVALID_ARGUMENT, "knn_query: %lld points in all, fewer than k = %d", (long long)n, k);
+  hipStream_t hs = (hipStream_t)stream;
+  switch (dim) {
+    case 1: return knn_query_impl<1>(n, m, points, queries, k, point_graph_id, query_graph_id, n_graphs, id_base, index_base, idx, d2, hs);
+    case 2: return knn_query_impl<2>(n, m, points, queries, k, point_graph_id, query_graph_id, n_graphs, id_base, index_base, idx, d2, hs);
+    default: return knn_query_impl<3>(n, m, points, queries, k, point_graph_id, query_graph_id, n_graphs, id_base, index_base, idx, d2, hs);
+  }
+}
+
+int32_t ngpde_radius_query(int64_t n, int64_t m, int32_t dim, const float *points, const float *queries, float r,
+                           const int32_t *point_graph_id, const int32_t *query_graph_id, int32_t n_graphs, int32_t id_base,
+                           int32_t index_base, int64_t capacity, int32_t *ptr, int32_t *nbr, int64_t *n_found, ngpde_stream_t stream) {
+  NGPDE_RANGE();
+  int32_t st = check_query("radius_query", n, m, dim, points, queries, point_graph_id, query_graph_id, n_graphs);
+  if (st) return st;
+  NGPDE_REQUIRE(n_found != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "radius_query: n_found is NULL");
+  NGPDE_REQUIRE(r >= 0.f, NGPDE_ERR_INVALID_ARGUMENT, "radius_query: radius must be >= 0 (got %g)", (double)r);
+  NGPDE_REQUIRE(nbr == nullptr || (ptr != nullptr && capacity >= 0), NGPDE_ERR_INVALID_ARGUMENT,
+                "radius_query: a fill call needs ptr and a capacity >= 0");
+  *n_found = 0;
+  hipStream_t hs = (hipStream_t)stream;
+  if (n == 0 || m == 0) {   // nothing to find: every row is empty
+    if (nbr) {
+      NGPDE_HIP_CHECK(hipMemsetAsync(ptr, 0, ((size_t)m + 1) * sizeof(int32_t), hs));
+      NGPDE_HIP_CHECK(hipStreamSynchronize(hs));
+    }
+    return NGPDE_OK;
+  }
+  switch (dim) {
+    case 1: return radius_query_impl<1>(n, m, points, queries, r, point_graph_id, query_graph_id, n_graphs, id_base, index_base, capacity, ptr, nbr, n_found, hs);
+    case 2: return radius_query_impl<2>(n, m, points, queries, r, point_graph_id, query_graph_id, n_graphs, id_base, index_base, capacity, ptr, nbr, n_found, hs);
+    default: return radius_query_impl<3>(n, m, points, queries, r, point_graph_id, query_graph_id, n_graphs, id_base, index_base, capacity, ptr, nbr, n_found, hs);
   }
 }
 
