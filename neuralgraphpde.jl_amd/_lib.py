@@ -324,6 +324,14 @@ INTERP_SIGNATURES = {
     "ngpde_knn_interp_backward": (_i32, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# The third block of the ABI, include/ngpde_mesh.h (Delaunay graphs and triangles), applied by load() next to the other two.
+# tests/test_mesh_host.py holds this table to what tests/test_abi.py holds SIGNATURES to.
+MESH_SIGNATURES = {
+    "ngpde_delaunay_graph": (_i32, [_i64, _vp, _vp, _i32, _i32, _f32, _i32, _i32, _i64, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_delaunay_triangles": (_i32, [_i64, _vp, _vp, _i32, _i32, _f32, _i32, _i64, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_delaunay_last_passes": (_i32, [C.POINTER(_i64), C.POINTER(_i64)]),
+}
+
 _lib = None
 
 
@@ -338,7 +346,7 @@ def load():
             "or `make -C neuralgraphpde.jl_amd/csrc`.  There is no CPU fallback for the hot path.")
     import torch  # noqa: F401  -- makes torch's libamdhip64.so the process's HIP runtime before ours resolves it
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + list(MESH_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -37,6 +37,7 @@
 #include "../../include/ngpde_interp.h"
 #include "common.h"
 #include "device_scratch.h"
+#include "neighbor_cells.h"
 #include "neighbor_grid.h"
 
 namespace ngpde {
@@ -671,6 +672,25 @@ int32_t check_common(int64_t n, int32_t dim, const float *pts, const int32_t *gi
 }
 
 }  // namespace
+
+// (neighbor_cells.h) the sorted grid for delaunay.hip
+int32_t point_cells_2d(int64_t n, const float *pts, const int32_t *gid, int n_graphs, int id_base, int k, hipStream_t stream,
+                       std::vector<void *> &owned, Grid *g, PointCells *out) {
+  Scratch sc;
+  float lo[3], hi[3];
+  Sorted so;
+  int32_t st = bounding_box(n, 2, pts, gid, id_base, n_graphs, stream, sc, lo, hi);
+  if (!st) {
+    *g = make_grid(2, lo, hi, knn_want(2, lo, hi, n, n_graphs, k), cell_budget(n), n_graphs);
+    st = sort_into_cells<2>(n, *g, n_graphs, pts, gid, id_base, stream, sc, so);
+  }
+  if (st) return st;   // (sc frees what it holds)
+  *out = PointCells{so.key, so.idx, so.pts, so.start};
+  owned.insert(owned.end(), sc.ptrs.begin(), sc.ptrs.end());
+  sc.ptrs.clear();
+  return NGPDE_OK;
+}
+
 }  // namespace ngpde
 
 using namespace ngpde;
