@@ -26,7 +26,7 @@ from .queries import (AdjacencyList, adjacency_list, has_edge, inneighbors, inte
 from .linsolve import CGInfo, cg_solve
 from .traversal import (Components, ShortestPaths, connected_components, hop_distance, is_connected, neighborhood, shortest_paths,
                         split_components)
-from . import dist, optim, synth, interp, mesh
+from . import dist, optim, synth, interp, mesh, coarsen
 
 
 def release_cached_memory():

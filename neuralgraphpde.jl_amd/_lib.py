@@ -332,6 +332,19 @@ MESH_SIGNATURES = {
     "ngpde_delaunay_last_passes": (_i32, [C.POINTER(_i64), C.POINTER(_i64)]),
 }
 
+# The fourth block of the ABI, include/ngpde_coarsen.h (farthest-point sampling, grid clusters, pooling over clusters), applied by
+# load() next to the other three.  tests/test_coarsen_host.py holds this table to what tests/test_abi.py holds SIGNATURES to.
+COARSEN_SIGNATURES = {
+    "ngpde_fps_plan_create": (_i32, [_i32, _vp, _vp, _i32, _i32, _vp, C.POINTER(_vp)]),
+    "ngpde_fps_plan_destroy": (_i32, [_vp]),
+    "ngpde_fps_plan_info": (_i32, [_vp, C.POINTER(_i64)]),
+    "ngpde_fps_workspace_bytes": (_sz, [_vp]),
+    "ngpde_fps": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ngpde_grid_cluster": (_i32, [_i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ngpde_cluster_pool_forward": (_i32, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ngpde_cluster_pool_backward": (_i32, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -346,7 +359,8 @@ def load():
             "or `make -C neuralgraphpde.jl_amd/csrc`.  There is no CPU fallback for the hot path.")
     import torch  # noqa: F401  -- makes torch's libamdhip64.so the process's HIP runtime before ours resolves it
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(INTERP_SIGNATURES.items()) + list(MESH_SIGNATURES.items()):
+    tables = (SIGNATURES, INTERP_SIGNATURES, MESH_SIGNATURES, COARSEN_SIGNATURES)
+    for name, (res, args) in [item for table in tables for item in table.items()]:
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -421,6 +435,6 @@ def flush_destroy():
 
 
 def destroy_later(fn, ptr):
-    """fn: "ngpde_graph_destroy" | "ngpde_node_destroy" | "ngpde_ode_destroy" | "ngpde_readout_destroy"; ptr: the handle"""
+    """fn: "ngpde_graph_destroy" | "ngpde_node_destroy" | "ngpde_ode_destroy" | "ngpde_readout_destroy" | "ngpde_fps_plan_destroy"; ptr: the handle"""
     _pending_destroy.append((fn, ptr))
     flush_destroy()
