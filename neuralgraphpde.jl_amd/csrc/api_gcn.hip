@@ -37,59 +37,12 @@ int32_t check_common(const char *fn, const ngpde_graph_t *g, int32_t din, int32_
   return NGPDE_OK;
 }
 
-// the forward's one region; the fused path needs none.  Any width: the Dense part on the fp32-MFMA kernels of dense_mfma.hip, and
-// the region holds the aggregated input (dout >= din) or the split-K partial products of W x (dout < din)
-float *gcn_fwd_layout(Workspace &w, const ngpde_graph_t *g, int32_t din, int32_t dout) {
-  if (fused_supported(din, dout)) return nullptr;
-  const size_t n = (size_t)g->n_nodes;
-  const size_t parts = dout < din ? (size_t)dense_fwd_split_count(din, dense_fwd_splits((int64_t)n, din, dout)) : 1;
-  return w.take<float>(n * (dout < din ? (size_t)dout * parts : (size_t)std::max(din, dout)));
-}
-
-struct GcnBwdWs {
-  float *slab_dw, *slab_db, *gbuf;   // fused: the weight and bias slabs of the blocks (zeroed as one span), dz W^T
-  float *dz, *tmp, *partial;         // any width: dz, one [N][max] buffer, the weight pullback's slabs
-  float *ew_dx, *ew_xw, *ew_nd;      // behind those when dedge_weight is asked for
-};
-constexpr size_t kGcnSlack = 256;    // what the queries add behind the pullback's own pieces; the ew pieces start after it
-
-void gcn_bwd_layout(Workspace &w, const ngpde_graph_t *g, int32_t din, int32_t dout, bool ew, GcnBwdWs &p) {
-  const size_t n = (size_t)g->n_nodes;
-  p = GcnBwdWs{};
-  if (fused_supported(din, dout)) {
-    const size_t nb = (size_t)fused_num_blocks(g->n_nodes);
-    p.slab_dw = w.take<float>(nb * (size_t)din * dout);
-    p.slab_db = w.take<float>(nb * (size_t)dout);
-    p.gbuf = w.take<float>(n * din);
-  } else {
-    const size_t dmax = (size_t)std::max(din, dout);
-    p.dz = w.take<float>(n * dmax);
-    p.tmp = w.take<float>(n * dmax);
-    // this region serves two users: the weight pullback's slabs (chunks x (din + 1) x dout) and, when dout < din, the two-stage
-    // column sums of the bias gradient (launch_colsum2: kColsumChunks x dout) -- with narrow layers the second is the larger one
-    const size_t slabs = (size_t)dense_weight_chunks((int64_t)n, din, dout) * (din + 1) * dout;
-    p.partial = w.take<float>(std::max(slabs, (size_t)kColsumChunks * dout));
-  }
-  w.take<char>(kGcnSlack);
-  if (!ew) return;
-  // dx (the caller may pass none), x W (Dout < Din: the array that entered the propagation), the per-node degree terms
-  p.ew_dx = w.take<float>(n * din);
-  p.ew_xw = w.take<float>(n * (size_t)std::min(din, dout));
-  p.ew_nd = w.take<float>(n);
-}
-
-size_t gcn_bwd_bytes(const ngpde_graph_t *g, int32_t din, int32_t dout, bool ew) {
-  GcnBwdWs p;
-  return measure(gcn_bwd_layout, g, din, dout, ew, p);
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t ngpde_gcn_workspace_bytes(const ngpde_graph_t *g, int32_t din, int32_t dout, int32_t backward) {
-  if (!g) return 0;
-  return backward ? gcn_bwd_bytes(g, din, dout, false) : measure(gcn_fwd_layout, g, din, dout) + kGcnSlack;
+  return g ? gcn_workspace_bytes(gcn_layer_form(g->n_nodes, din, dout), backward != 0, false) : 0;
 }
 
 int32_t ngpde_gcn_forward(const ngpde_graph_t *g, int32_t din, int32_t dout, int32_t act, const float *x,
@@ -102,25 +55,25 @@ int32_t ngpde_gcn_forward(const ngpde_graph_t *g, int32_t din, int32_t dout, int
   NGPDE_REQUIRE(x && weight && y, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gcn_forward: x/weight/y is NULL");
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t n = g->n_nodes;
-  if (fused_supported(din, dout)) {
+  const GcnLayerForm f = gcn_layer_form(n, din, dout);   // (gcn_forms.h: the kind, the split, the workspace)
+  if (f.fused()) {
     FusedFwdArgs a;
     a.g = g; a.d = din; a.act = act; a.x = x; a.wt = weight; a.bias = bias; a.y = y;
     a.save_agg = save_agg; a.save_z = save_z;
     return launch_fused_fwd(a, stream);
   }
-  if ((st = check_workspace("ngpde_gcn_forward", workspace, workspace_bytes, ngpde_gcn_workspace_bytes(g, din, dout, 0), 1))) return st;
+  if ((st = check_workspace("ngpde_gcn_forward", workspace, workspace_bytes, gcn_workspace_bytes(f, false, false), 1))) return st;
   Workspace w(workspace);
-  float *tmp = gcn_fwd_layout(w, g, din, dout);
-  if (dout >= din) {  // aggregate, then multiply (src/layers.jl:235-237)
+  float *tmp = gcn_fwd_layout(w, f);
+  if (f.aggregate_first()) {  // aggregate, then multiply (src/layers.jl:235-237)
     float *agg = save_agg ? save_agg : tmp;
     if ((st = launch_spmm_generic(g, false, true, din, NGPDE_AGGR_SUM, x, nullptr, agg, stream))) return st;
     return launch_dense_seg_fwd(n, one_seg(agg, din), din, dout, act, weight, bias, y, save_z, stream);
   }
   // multiply first (src/layers.jl:220-223) -- split over the input features when the row tiles alone cannot fill the chip,
   // the partial products summed in slab order --, then ONE launch: aggregation + bias + activation
-  const int nsplit = dense_fwd_splits(n, din, dout);
-  if ((st = launch_dense_seg_fwd_splitk(n, one_seg(x, din), din, dout, weight, tmp, nsplit, stream))) return st;
-  if ((st = launch_sum_partials(n * dout, dense_fwd_split_count(din, nsplit), (size_t)n * dout, tmp, stream))) return st;
+  if ((st = launch_dense_seg_fwd_splitk(n, one_seg(x, din), din, dout, weight, tmp, f.nsplit, stream))) return st;
+  if ((st = launch_sum_partials(n * dout, f.parts, (size_t)n * dout, tmp, stream))) return st;
   return launch_spmm_gcn_tail(g, dout, tmp, bias, act, y, save_z, stream);
 }
 
@@ -141,20 +94,21 @@ int32_t gcn_backward_impl(const char *fn, const ngpde_graph_t *g, int32_t din, i
     return NGPDE_OK;
   }
   NGPDE_REQUIRE(weight && z && dy, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gcn_backward: weight/z/dy is NULL");
-  NGPDE_REQUIRE(dout < din || saved_agg, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gcn_backward: saved_agg is NULL");
-  NGPDE_REQUIRE(dout >= din || x, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gcn_backward: x is NULL");
-  hipStream_t stream = (hipStream_t)stream_;
   const int64_t n = g->n_nodes;
-  if ((st = check_workspace(fn, workspace, workspace_bytes, gcn_bwd_bytes(g, din, dout, dedge_weight != nullptr), 1))) return st;
+  const GcnLayerForm f = gcn_layer_form(n, din, dout);
+  NGPDE_REQUIRE(!f.needs_saved_agg || saved_agg, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gcn_backward: saved_agg is NULL");
+  NGPDE_REQUIRE(!f.needs_x || x, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gcn_backward: x is NULL");
+  hipStream_t stream = (hipStream_t)stream_;
+  if ((st = check_workspace(fn, workspace, workspace_bytes, gcn_workspace_bytes(f, true, dedge_weight != nullptr), 1))) return st;
   Workspace w(workspace);
   GcnBwdWs p;
-  gcn_bwd_layout(w, g, din, dout, dedge_weight != nullptr, p);
+  gcn_bwd_layout(w, f, dedge_weight != nullptr, p);
   float *const ew_xw = p.ew_xw, *const ew_nd = p.ew_nd;
   if (dedge_weight) {
     NGPDE_REQUIRE(x != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gcn_backward_ew: x is NULL");
     if (!dx) dx = p.ew_dx;      // the degree term needs the layer's input gradient
   }
-  if (fused_supported(din, dout)) {
+  if (f.fused()) {
     float *const slab_dw = p.slab_dw, *const slab_db = p.slab_db, *const gbuf = p.gbuf;
     { const int32_t zs = launch_zero(slab_dw, (size_t)((char *)gbuf - (char *)slab_dw), stream); if (zs) return zs; }
     FusedBwdArgs a;
@@ -176,7 +130,7 @@ int32_t gcn_backward_impl(const char *fn, const ngpde_graph_t *g, int32_t din, i
   }
   float *const dz = p.dz, *const tmp = p.tmp, *const partial = p.partial;
   if ((st = launch_act_bwd(n * dout, act, dy, z, dz, stream))) return st;
-  if (dout >= din) {   // y = act(agg W + b): dW = agg^T dz, db = column sums of dz (the weight pullback's bias row), dx = A^T (dz W^T)
+  if (f.aggregate_first()) {   // y = act(agg W + b): dW = agg^T dz, db = column sums of dz (the weight pullback's bias row), dx = A^T (dz W^T)
     if ((st = launch_dense_seg_bwd_weight(n, one_seg(saved_agg, din), din, dout, dz, dweight, dbias, partial, stream))) return st;
     if (dx) {
       if ((st = launch_dense_seg_bwd_input(n, one_grad(tmp, din), din, dout, dz, weight, stream))) return st;
@@ -212,8 +166,7 @@ int32_t ngpde_gcn_backward(const ngpde_graph_t *g, int32_t din, int32_t dout, in
 }
 
 size_t ngpde_gcn_backward_ew_workspace_bytes(const ngpde_graph_t *g, int32_t din, int32_t dout) {
-  if (!g) return 0;
-  return gcn_bwd_bytes(g, din, dout, true);
+  return g ? gcn_workspace_bytes(gcn_layer_form(g->n_nodes, din, dout), true, true) : 0;
 }
 
 int32_t ngpde_gcn_backward_ew(const ngpde_graph_t *g, int32_t din, int32_t dout, int32_t act, const float *x, const float *weight,

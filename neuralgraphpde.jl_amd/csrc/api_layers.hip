@@ -224,7 +224,7 @@ int32_t make_plan(const ngpde_graph *g, const ngpde_edge_layer_t &L, bool traini
   // otherwise: edge_layer_msg_path in edge_mlp_forms.h, asked about the call the layer makes (P, Q and dQ; E iff edge features)
   EdgeMlpDesc msg = edge_mlp_desc(p.h1, p.act1, p.n_tail, p.tail_dout, p.tail_act, p.aggr);
   msg.P = msg.Q = msg.dQ = true; msg.Eterm = p.de > 0;
-  const EdgeMsgPath path = edge_layer_msg_path(edge_tile_geom(g), msg, training);
+  const EdgeMsgPath path = edge_layer_msg_path(tile_geom(g), msg, training);
   p.fused_msg = path.fused_msg; p.fused_bwd = path.fused_bwd;
 
   // ---- forward region

@@ -30,16 +30,6 @@ int32_t check_act(const char *fn, int32_t act) {
   return NGPDE_OK;
 }
 
-// the unfused GAT pullback: the edges' score gradients, the two per-node score gradients
-struct GatBwdWs {
-  float *dscore, *dal, *dar;
-};
-void gat_bwd_layout(Workspace &w, const ngpde_graph_t *g, int32_t heads, GatBwdWs &p) {
-  p.dscore = w.take<float>((size_t)std::max<int64_t>(g->n_edges, 1) * heads);
-  p.dal = w.take<float>((size_t)std::max<int64_t>(g->n_nodes, 1) * heads);
-  p.dar = w.take<float>((size_t)std::max<int64_t>(g->n_nodes, 1) * heads);
-}
-
 }  // namespace
 
 extern "C" {
@@ -365,13 +355,13 @@ int32_t ngpde_gat_forward(const ngpde_graph_t *g, int32_t heads, int32_t c, floa
   hipStream_t stream = (hipStream_t)stream_;
   int32_t st = launch_gat_scores(g->n_nodes, heads, c, wx, a, al, ar, stream);
   if (st) return st;
-  return launch_gat_fwd(g, heads, c, negative_slope, wx, al, ar, out, alpha, stream);
+  return launch_gat_fwd(g, gat_fwd_form(tile_geom(g), heads, c), heads, c, negative_slope, wx, al, ar, out, alpha, stream);
 }
 
 size_t ngpde_gat_workspace_bytes(const ngpde_graph_t *g, int32_t heads) {
   if (!g) return 0;
   GatBwdWs p;
-  return measure(gat_bwd_layout, g, heads, p) + kWsSlack;
+  return measure(gat_bwd_layout, tile_geom(g), heads, p) + kWsSlack;
 }
 
 int32_t ngpde_gat_backward(const ngpde_graph_t *g, int32_t heads, int32_t c, float negative_slope, const float *wx,
@@ -385,18 +375,19 @@ int32_t ngpde_gat_backward(const ngpde_graph_t *g, int32_t heads, int32_t c, flo
   if (int32_t st = check_workspace("ngpde_gat_backward", workspace, workspace_bytes, ngpde_gat_workspace_bytes(g, heads), 1)) return st;
   Workspace w(workspace);
   GatBwdWs p;
-  gat_bwd_layout(w, g, heads, p);
-  return launch_gat_bwd(g, heads, c, negative_slope, wx, a, al, ar, alpha, dout, p.dscore, p.dal, p.dar, dwx, da,
-                        (hipStream_t)stream_);
+  gat_bwd_layout(w, tile_geom(g), heads, p);
+  const bool aligned = ((reinterpret_cast<uintptr_t>(wx) | reinterpret_cast<uintptr_t>(dout)) & 15) == 0;
+  return launch_gat_bwd(g, gat_bwd_form(tile_geom(g), heads, c, aligned), heads, c, negative_slope, wx, a, al, ar, alpha, dout, p.dscore, p.dal, p.dar,
+                        dwx, da, (hipStream_t)stream_);
 }
 
 int32_t ngpde_gat_layer_supported(const ngpde_graph_t *g, int32_t din, int32_t heads, int32_t c) {
-  return gat_layer_fused_supported(g, din, heads, c) ? 1 : 0;
+  return gat_layer_form(tile_geom(g), din, heads, c).supported ? 1 : 0;
 }
 
 size_t ngpde_gat_layer_workspace_bytes(const ngpde_graph_t *g, int32_t heads, int32_t c) {
   (void)c;
-  return g ? gat_layer_workspace_bytes(g, heads) : 0;
+  return gat_layer_workspace_bytes(tile_geom(g), heads);
 }
 
 int32_t ngpde_gat_layer_forward(const ngpde_graph_t *g, int32_t din, int32_t heads, int32_t c, float negative_slope, int32_t act,
@@ -406,12 +397,13 @@ int32_t ngpde_gat_layer_forward(const ngpde_graph_t *g, int32_t din, int32_t hea
   NGPDE_REQUIRE(g != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gat_layer_forward: graph is NULL");
   int32_t st = check_act("ngpde_gat_layer_forward", act);
   if (st) return st;
-  NGPDE_REQUIRE(gat_layer_fused_supported(g, din, heads, c), NGPDE_ERR_UNSUPPORTED,
+  const GatLayer f = gat_layer_form(tile_geom(g), din, heads, c);
+  NGPDE_REQUIRE(f.supported, NGPDE_ERR_UNSUPPORTED,
                 "ngpde_gat_layer_forward: needs din == heads * c == 64, heads in {1, 2, 4} and a graph whose tiles fit the LDS "
                 "halo in both directions (got din = %d, heads = %d, c = %d); compose ngpde_dense_forward + ngpde_gat_forward", din, heads, c);
   if (g->n_nodes == 0) return NGPDE_OK;
   NGPDE_REQUIRE(x && weight && a && y, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gat_layer_forward: NULL argument");
-  return launch_gat_layer_fwd(g, heads, negative_slope, act, x, weight, a, bias, y, save_alpha, save_z, (hipStream_t)stream);
+  return launch_gat_layer_fwd(g, f, negative_slope, act, x, weight, a, bias, y, save_alpha, save_z, (hipStream_t)stream);
 }
 
 int32_t ngpde_gat_layer_backward(const ngpde_graph_t *g, int32_t din, int32_t heads, int32_t c, float negative_slope, int32_t act,
@@ -422,12 +414,13 @@ int32_t ngpde_gat_layer_backward(const ngpde_graph_t *g, int32_t din, int32_t he
   NGPDE_REQUIRE(g != nullptr, NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gat_layer_backward: graph is NULL");
   int32_t st = check_act("ngpde_gat_layer_backward", act);
   if (st) return st;
-  NGPDE_REQUIRE(gat_layer_fused_supported(g, din, heads, c), NGPDE_ERR_UNSUPPORTED,
+  const GatLayer f = gat_layer_form(tile_geom(g), din, heads, c);
+  NGPDE_REQUIRE(f.supported, NGPDE_ERR_UNSUPPORTED,
                 "ngpde_gat_layer_backward: unsupported shape / graph (din = %d, heads = %d, c = %d)", din, heads, c);
   NGPDE_REQUIRE(weight && a && dweight && da && (g->n_nodes == 0 || (x && dy && (save_alpha || g->n_edges == 0))) &&
                     (act == NGPDE_ACT_IDENTITY || y_or_z || g->n_nodes == 0),
                 NGPDE_ERR_INVALID_ARGUMENT, "ngpde_gat_layer_backward: NULL argument");
-  return launch_gat_layer_bwd(g, heads, negative_slope, act, x, weight, a, y_or_z, save_alpha, dy, dx, dweight, da, dbias, workspace,
+  return launch_gat_layer_bwd(g, f, heads, negative_slope, act, x, weight, a, y_or_z, save_alpha, dy, dx, dweight, da, dbias, workspace,
                               workspace_bytes, (hipStream_t)stream);
 }
 
@@ -464,7 +457,7 @@ int32_t ngpde_bias_act_backward(int64_t n, int32_t d, int32_t act, const float *
 
 // The message-MLP entries and queries: edge_mlp_forms.h decides from the graph's tile geometry and the call's description.
 int32_t ngpde_edge_mlp_supported(const ngpde_graph_t *g, int32_t h1, int32_t n_tail, const int32_t *tail_dout) {
-  return edge_mlp_fwd_supported(edge_tile_geom(g), edge_mlp_desc(h1, 0, n_tail, tail_dout, nullptr, 0)) ? 1 : 0;
+  return edge_mlp_fwd_supported(tile_geom(g), edge_mlp_desc(h1, 0, n_tail, tail_dout, nullptr, 0)) ? 1 : 0;
 }
 
 int32_t ngpde_edge_mlp_forward(const ngpde_graph_t *g, int32_t h1, int32_t act1, const float *p_target,
@@ -496,15 +489,15 @@ int32_t ngpde_edge_mlp_forward(const ngpde_graph_t *g, int32_t h1, int32_t act1,
       a.d.save_z = a.d.save_z || save_z[l];
     }
   a.d.P = a.P != nullptr; a.d.Q = a.Q != nullptr; a.d.Eterm = a.Eterm != nullptr;
-  return launch_edge_mlp_fused_fwd(g, edge_mlp_fwd_plan(edge_tile_geom(g), a.d), a, (hipStream_t)stream);
+  return launch_edge_mlp_fused_fwd(g, edge_mlp_fwd_plan(tile_geom(g), a.d), a, (hipStream_t)stream);
 }
 
 int32_t ngpde_edge_mlp_backward_supported(const ngpde_graph_t *g, int32_t h1, int32_t n_tail, const int32_t *tail_dout, int32_t aggr) {
-  return edge_mlp_bwd_plan(edge_tile_geom(g), edge_mlp_desc(h1, 0, n_tail, tail_dout, nullptr, aggr)).supported ? 1 : 0;
+  return edge_mlp_bwd_plan(tile_geom(g), edge_mlp_desc(h1, 0, n_tail, tail_dout, nullptr, aggr)).supported ? 1 : 0;
 }
 
 size_t ngpde_edge_mlp_backward_workspace_bytes(const ngpde_graph_t *g, int32_t h1, int32_t n_tail, const int32_t *tail_dout) {
-  return edge_mlp_bwd_workspace_bytes(edge_tile_geom(g), edge_mlp_desc(h1, 0, n_tail, tail_dout, nullptr, 0));
+  return edge_mlp_bwd_workspace_bytes(tile_geom(g), edge_mlp_desc(h1, 0, n_tail, tail_dout, nullptr, 0));
 }
 
 int32_t ngpde_edge_mlp_backward_needs_edge_buffer(const ngpde_graph_t *g, int32_t h1, int32_t act1, int32_t has_e_term, int32_t n_tail,
@@ -512,7 +505,7 @@ int32_t ngpde_edge_mlp_backward_needs_edge_buffer(const ngpde_graph_t *g, int32_
   EdgeMlpDesc d = edge_mlp_desc(h1, act1, n_tail, tail_dout, tail_act, aggr);   // a call with P, Q and dQ
   d.tails = d.tails && (n_tail <= 0 || tail_act != nullptr);
   d.P = d.Q = d.dQ = true; d.Eterm = has_e_term != 0;
-  return edge_mlp_bwd_plan(edge_tile_geom(g), d).edge_buffer ? 1 : 0;
+  return edge_mlp_bwd_plan(tile_geom(g), d).edge_buffer ? 1 : 0;
 }
 
 int32_t ngpde_edge_mlp_backward(const ngpde_graph_t *g, int32_t h1, int32_t act1, const float *p_target, const float *q_source,
@@ -542,7 +535,7 @@ int32_t ngpde_edge_mlp_backward(const ngpde_graph_t *g, int32_t h1, int32_t act1
   }
   a.dP = dp_target; a.dQ = dq_source; a.dE = de_term; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
   a.d.P = a.P != nullptr; a.d.Q = a.Q != nullptr; a.d.Eterm = a.Eterm != nullptr; a.d.dQ = a.dQ != nullptr; a.d.dE = a.dE != nullptr;
-  const EdgeBwd p = edge_mlp_bwd_plan(edge_tile_geom(g), a.d);
+  const EdgeBwd p = edge_mlp_bwd_plan(tile_geom(g), a.d);
   return p.form == EdgeBwdForm::Deep ? launch_edge_mlp_deep_bwd(g, p, a, (hipStream_t)stream) : launch_edge_mlp_fused_bwd(g, p, a, (hipStream_t)stream);
 }
 

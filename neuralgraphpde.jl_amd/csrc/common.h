@@ -13,6 +13,10 @@
 #include "../../include/ngpde.h"
 #include "dense_forms.h"
 #include "edge_mlp_forms.h"
+#include "gat_forms.h"
+#include "gcn_forms.h"
+#include "pick_int.h"
+#include "tile_geom.h"
 #include "workspace.h"
 
 namespace ngpde {
@@ -81,8 +85,7 @@ struct HaloInverse {
   int stride = 0;
 };
 
-// kTileRows, kHaloCap, kSlotWidth: edge_mlp_forms.h (host only; the message-MLP family decides in them)
-constexpr int kEllWidth = 16;  // entries per row held in the fixed-width block (rows with more spill to the CSR list)
+// kTileRows, kHaloCap, kSlotWidth, kEllWidth: tile_geom.h (host only; the forms headers decide in them)
 
 }  // namespace ngpde
 
@@ -114,14 +117,15 @@ struct ngpde_graph {
 
 namespace ngpde {
 
-// all the message-MLP family's choices read of a handle (edge_mlp_forms.h); NULL: no graph
-inline EdgeTileGeom edge_tile_geom(const ngpde_graph *g) {
-  EdgeTileGeom t;
+// all that the choices of the forms headers read of a handle (tile_geom.h); NULL: no graph
+inline TileGeom tile_geom(const ngpde_graph *g) {
+  TileGeom t;
   if (!g) return t;
-  t.graph = true; t.has_norm = g->has_norm; t.halo_ok = g->by_t.halo_ok; t.max_halo = g->by_t.max_halo;
-  t.n_tiles = (int)(g->n_sched / kTileRows); t.n_nodes = g->n_nodes; t.n_edges = g->n_edges;
+  t.graph = true; t.has_norm = g->has_norm; t.halo_ok = g->by_t.halo_ok; t.halo_ok_s = g->by_s.halo_ok; t.self_loops = g->self_loops != 0;
+  t.max_halo = g->by_t.max_halo; t.n_tiles = (int)(g->n_sched / kTileRows); t.n_nodes = g->n_nodes; t.n_edges = g->n_edges;
   return t;
 }
+inline bool fused_prescaled_supported(const ngpde_graph *g, int d) { return fused_prescaled_supported(tile_geom(g), d); }
 
 // ---- device-side handle construction (graph_device.hip)
 template <class I>
@@ -162,8 +166,7 @@ struct FusedFwdArgs {
   // optional start/stop events attached to the dispatch itself (profiling pass only)
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 };
-bool fused_supported(int din, int dout);
-bool fused_prescaled_supported(const ngpde_graph *g, int d);
+// (fused_supported, fused_prescaled_supported, fused_num_blocks, fused_num_slabs, fused_mask_bytes: gcn_forms.h)
 int32_t launch_fused_fwd(const FusedFwdArgs &a, hipStream_t stream);
 
 struct FusedBwdArgs {
@@ -189,10 +192,6 @@ struct FusedBwdArgs {
   float *slab_db = nullptr;      // [n_blocks][d]   accumulated (+=)
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 };
-int fused_tile_rows();
-int fused_num_blocks(int64_t n_nodes);
-size_t fused_mask_bytes(int64_t n_nodes, int d);   // bytes of one sign-bit mask (FusedFwdArgs::save_mask)
-int fused_num_slabs(int64_t n_nodes, int d);   // <= fused_num_blocks: slabs the backward launches actually write
 int32_t launch_fused_bwd(const FusedBwdArgs &a, hipStream_t stream);
 // ct > 0: dW slabs in MFMA-fragment order (ct = D/16 column tiles) -> row-major [in][out]; ct == 0: plain sum
 int32_t launch_reduce_slabs(const float *slab, int n_slabs, int len, int ct, float *out, hipStream_t stream);
@@ -376,8 +375,8 @@ int32_t launch_vmh_copy_block(const float *src, int sp, float *dst, int dp, int 
 // srcpos[r][kSlotWidth] / srcdeg[r] for every row r of the by-target schedule: the positions (in the by-target edge order) of the out-edges
 // of the row's node -- the by-source gather's addresses, laid out by schedule row so that a tile reads them with one coalesced load
 int32_t launch_vmh_srcpos(const ngpde_graph *g, int *srcpos, int *srcdeg, hipStream_t stream);
-bool gat_fused_supported(const ngpde_graph *g, int heads, int c);
-int32_t launch_gat_fused_fwd(const ngpde_graph *g, int heads, int c, float slope, const float *wx, const float *al, const float *ar,
+// the tiled forward of the GAT aggregation (gat_fwd_form in gat_forms.h says when)
+int32_t launch_gat_fused_fwd(const ngpde_graph *g, int heads, float slope, const float *wx, const float *al, const float *ar,
                              float *out, float *alpha, hipStream_t stream);
 
 // generic (any feature width) building blocks
@@ -465,21 +464,20 @@ int32_t launch_gno_apply_mfma_bwd(const ngpde_graph *g, int cout, int kdim, cons
                                   float *dq = nullptr);
 int32_t launch_gat_scores(int64_t n, int heads, int c, const float *wx, const float *a, float *al, float *ar,
                           hipStream_t stream);
-int32_t launch_gat_fwd(const ngpde_graph *g, int heads, int c, float slope, const float *wx, const float *al, const float *ar,
+// the GAT aggregation and its pullback in the form gat_fwd_form / gat_bwd_form (gat_forms.h) decided
+int32_t launch_gat_fwd(const ngpde_graph *g, const GatFwd &f, int heads, int c, float slope, const float *wx, const float *al, const float *ar,
                        float *out, float *alpha, hipStream_t stream);
-int32_t launch_gat_bwd(const ngpde_graph *g, int heads, int c, float slope, const float *wx, const float *a, const float *al,
+int32_t launch_gat_bwd(const ngpde_graph *g, const GatBwd &f, int heads, int c, float slope, const float *wx, const float *a, const float *al,
                        const float *ar, const float *alpha, const float *dout, float *dscore, float *dal, float *dar,
                        float *dwx, float *da, hipStream_t stream);
 int32_t launch_spectral_weights(int64_t n_edges, float nn, const float *e, float *w, hipStream_t stream);
-// ---- the whole GAT-style layer (gat_fused.hip)
-bool gat_layer_fused_supported(const ngpde_graph *g, int din, int heads, int c);
-size_t gat_layer_workspace_bytes(const ngpde_graph *g, int heads);
-int32_t launch_gat_layer_fwd(const ngpde_graph *g, int heads, float slope, int act, const float *x, const float *wt, const float *a,
+// ---- the whole GAT-style layer (gat_fused.hip): gat_layer_form in gat_forms.h decides, these launch a supported form
+int32_t launch_gat_layer_fwd(const ngpde_graph *g, const GatLayer &f, float slope, int act, const float *x, const float *wt, const float *a,
                              const float *bias, float *y, float *alpha, float *save_z, hipStream_t stream);
-int32_t launch_gat_layer_bwd(const ngpde_graph *g, int heads, float slope, int act, const float *x, const float *wt, const float *a,
+int32_t launch_gat_layer_bwd(const ngpde_graph *g, const GatLayer &f, int heads, float slope, int act, const float *x, const float *wt, const float *a,
                              const float *yz, const float *alpha, const float *dy, float *dx, float *dwt, float *da, float *db,
                              void *workspace, size_t workspace_bytes, hipStream_t stream);
-constexpr int kColsumChunks = 128;
+// two stages through `partial` ([kColsumChunks][d]) where colsum_two_stage(n) (gcn_forms.h) and partial is given
 int32_t launch_colsum2(int64_t n, int d, const float *a, float *partial, float *out, hipStream_t stream);
 // y = act(a + addend + bias) (addend, bias nullable), 16-byte accesses when d % 4 == 0
 int32_t launch_bias_act2(int64_t n, int d, int act, const float *a, const float *addend, const float *bias, float *y, float *save_z,

@@ -619,7 +619,7 @@ int32_t edge64_pair(int act1, int act2, F f) {
 
 int32_t launch_edge_mlp64_fwd(const ngpde_graph *g, const EdgeFwd &p, const EdgeMlpArgs &a, hipStream_t stream) {
   EdgeMlp64K k;
-  fill_tile_args(g, edge_tile_geom(g), k);
+  fill_tile_args(g, tile_geom(g), k);
   k.aggr = a.d.aggr;
   k.P = a.P; k.Q = a.Q; k.wt = a.wt[0]; k.bias = a.bias[0]; k.out = a.out;
   NGPDE_STAMP_SET(k, kStampEdge64, 0);
@@ -643,7 +643,7 @@ __global__ __launch_bounds__(256) void edge64_dq_combine_kernel(int n_listed, co
 
 // ---- pullback launch (launch_edge_mlp_fused_bwd has checked the workspace and the dE rule)
 int32_t launch_edge_mlp64_bwd(const ngpde_graph *g, const EdgeBwd &p, const EdgeMlpBwdArgs &a, hipStream_t stream) {
-  const EdgeTileGeom t = edge_tile_geom(g);
+  const TileGeom t = tile_geom(g);
   EdgeMlp64BwdK k;
   fill_tile_args(g, t, k);
   k.aggr = a.d.aggr;

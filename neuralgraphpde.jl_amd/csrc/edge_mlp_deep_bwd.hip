@@ -206,7 +206,7 @@ int32_t launch_edge_mlp_deep_bwd(const ngpde_graph *g, const EdgeBwd &p, const E
   if (int32_t st = check_workspace("deep fused edge-MLP pullback", a.workspace, a.workspace_bytes, p.workspace_bytes, 1)) return st;
   NGPDE_REQUIRE(!p.dE_missing, NGPDE_ERR_INVALID_ARGUMENT, "deep fused edge-MLP pullback: the [E][h1] buffer dE is required");
   const EdgeMlpDesc &d = a.d;
-  const EdgeTileGeom t = edge_tile_geom(g);
+  const TileGeom t = tile_geom(g);
   DeepBwdK k;
   fill_tile_args(g, t, k);
   k.h1 = d.h1; k.act1 = d.act1; k.aggr = d.aggr; k.n_tail = d.n_tail;

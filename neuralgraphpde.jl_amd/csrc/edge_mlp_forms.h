@@ -1,7 +1,7 @@
 // edge_mlp_forms.h -- which kernels every one-launch message-MLP call runs, decided in one place (host only, plain C++17: no HIP).
 //
 // The family behind ngpde_edge_mlp_* and ngpde_edge_layer_* (ExplicitEdgeConv, VMHConv, MPPDEConv) picks its kernels from the
-// graph's tile geometry (EdgeTileGeom: all any choice reads of a handle), the message MLP and what the caller passes (EdgeMlpDesc:
+// graph's tile geometry (TileGeom: all any choice reads of a handle), the message MLP and what the caller passes (EdgeMlpDesc:
 // widths, activations, aggregation and presence bits for what are pointers in a call).  Every choice is a pure function here that
 // returns a small plain struct -- the decision -- and the launchers (edge_mlp_fused.hip, edge_mlp64.hip, edge_mlp_deep_bwd.hip) and
 // entries (api_mp.hip, api_layers.hip) execute a decision without judging the shape again.  A decision names the kernels it stands
@@ -42,14 +42,10 @@
 #include <vector>
 
 #include "switches.h"
+#include "tile_geom.h"
 #include "workspace.h"
 
 namespace ngpde {
-
-// ---- the tile schedule (every tiled kernel of the library counts in these) ----------------------------------------------------------
-constexpr int kTileRows = 32;   // node rows per workgroup of the fused kernels
-constexpr int kHaloCap = 96;    // unique rows a tile may stage in LDS (24 KB at D = 64), plus one zero row
-constexpr int kSlotWidth = 32;  // slot bytes per row of the LDS-staged aggregation (rows with more: global gather)
 
 // ---- what the message-MLP family measures in (short names: the three kernel files and edge_mlp_tile.h say `using namespace`) ---------
 namespace edge_mlp {
@@ -67,21 +63,16 @@ constexpr int64_t kDeepBwdNodes = 32768;                  // the deep pullback p
 
 using EdgeKernelNames = std::vector<std::string>;
 
-// ---- all a choice reads of a graph handle (edge_tile_geom in edge_mlp_tile.h fills it; NULL handle: the default) ---------------------
-struct EdgeTileGeom {
-  bool graph = false, has_norm = false, halo_ok = false;
-  int max_halo = 0, n_tiles = 0;
-  int64_t n_nodes = 0, n_edges = 0;
-};
-inline bool edge_tiles_ok(const EdgeTileGeom &g) { return g.graph && g.has_norm && g.halo_ok; }
+// ---- the tile schedule as this family reads it (TileGeom, tile_geom.h: the by-target side) ------------------------------------------------
+inline bool edge_tiles_ok(const TileGeom &g) { return g.graph && g.has_norm && g.halo_ok; }
 // LDS rows of the halo region = the largest halo of this graph's tiles
-inline int edge_halo_rows(const EdgeTileGeom &g) { return std::max<int>(kTileRows, std::min<int>(kHaloCap, g.max_halo)); }
+inline int edge_halo_rows(const TileGeom &g) { return std::max<int>(kTileRows, std::min<int>(kHaloCap, g.max_halo)); }
 // Persistent workgroups, at most per_xcd_cap per XCD.  EdgeTileRange splits the tiles into 8 per-XCD ranges and lets gridDim.x / 8
 // workgroups walk each: the grid has to be a multiple of 8, or the workgroups beyond the last multiple walk tiles of their XCD a
 // second time (and add their weight gradients twice).
-inline int edge_persistent_grid(const EdgeTileGeom &g, int per_xcd_cap) { return 8 * std::max(1, std::min(per_xcd_cap, (g.n_tiles + 7) / 8)); }
+inline int edge_persistent_grid(const TileGeom &g, int per_xcd_cap) { return 8 * std::max(1, std::min(per_xcd_cap, (g.n_tiles + 7) / 8)); }
 // the dynamic LDS of a form: the halo region, its zero row and the form's other rows, kTS floats each
-inline size_t edge_lds_bytes(const EdgeTileGeom &g, int other_rows) {
+inline size_t edge_lds_bytes(const TileGeom &g, int other_rows) {
   return (size_t)(edge_halo_rows(g) + 1 + other_rows) * edge_mlp::kTS * sizeof(float);
 }
 inline int edge_per_xcd(size_t lds, size_t slack) { return lds + slack <= edge_mlp::kLdsBudget ? edge_mlp::kPerXcd2 : edge_mlp::kPerXcd1; }
@@ -126,7 +117,7 @@ inline bool edge64_shape(const EdgeMlpDesc &d) {
   return a1 && (d.act[0] == d.act1 || d.act[0] == NGPDE_ACT_IDENTITY);
 }
 // its pullback sums by source inside the launch (no [E][64] array): dQ wanted, every halo within kDqStride rows
-inline bool edge64_dq_halo(const EdgeTileGeom &g, const EdgeMlpDesc &d) {
+inline bool edge64_dq_halo(const TileGeom &g, const EdgeMlpDesc &d) {
   return !switch_on(Switch::Edge64NoDq) && d.dQ && g.halo_ok && g.max_halo <= edge_mlp::kDqStride;
 }
 inline const char *edge_act_name(int act) {
@@ -147,8 +138,8 @@ struct EdgeFwd {
     return {"edge_mlp_fused_fwd_kernel<" + std::to_string(n_tail) + ">"};
   }
 };
-inline bool edge_mlp_fwd_supported(const EdgeTileGeom &g, const EdgeMlpDesc &d) { return edge_tiles_ok(g) && edge_chain_ok(d, 0, edge_mlp::kMaxTail); }
-inline EdgeFwd edge_mlp_fwd_plan(const EdgeTileGeom &g, const EdgeMlpDesc &d) {
+inline bool edge_mlp_fwd_supported(const TileGeom &g, const EdgeMlpDesc &d) { return edge_tiles_ok(g) && edge_chain_ok(d, 0, edge_mlp::kMaxTail); }
+inline EdgeFwd edge_mlp_fwd_plan(const TileGeom &g, const EdgeMlpDesc &d) {
   using namespace edge_mlp;
   EdgeFwd p;
   p.supported = edge_mlp_fwd_supported(g, d);
@@ -179,7 +170,7 @@ struct EdgeBwdWs {
 };
 inline size_t edge_slab_bytes(int grid, int din, int dw) { return (size_t)grid * (din + 1) * dw * sizeof(float); }
 inline int edge_general_dw(const EdgeMlpDesc &d) { return (d.n_tail == 1 && d.tails) ? d.dout[0] : 0; }   // the general pullback's tail width
-inline void edge_mlp_bwd_layout(Workspace &w, const EdgeTileGeom &g, const EdgeMlpDesc &d, EdgeBwdForm form, EdgeBwdWs &p) {
+inline void edge_mlp_bwd_layout(Workspace &w, const TileGeom &g, const EdgeMlpDesc &d, EdgeBwdForm form, EdgeBwdWs &p) {
   using namespace edge_mlp;
   p = EdgeBwdWs();
   if (form == EdgeBwdForm::Edge64) {   // slabs of the larger grid (two workgroups per CU), then the partials
@@ -196,7 +187,7 @@ inline void edge_mlp_bwd_layout(Workspace &w, const EdgeTileGeom &g, const EdgeM
 }
 // what ngpde_edge_mlp_backward_workspace_bytes answers.  n_tail <= 1: the general kernel's slabs start at the base and end unrounded;
 // at 64 => 64 the edge64 layout counts too (whatever the switches and activations: the query knows neither)
-inline size_t edge_mlp_bwd_workspace_bytes(const EdgeTileGeom &g, const EdgeMlpDesc &d) {
+inline size_t edge_mlp_bwd_workspace_bytes(const TileGeom &g, const EdgeMlpDesc &d) {
   using namespace edge_mlp;
   if (!g.graph) return 0;
   EdgeBwdWs p;
@@ -232,7 +223,7 @@ struct EdgeBwd {
     return k;
   }
 };
-inline EdgeBwd edge_mlp_bwd_plan(const EdgeTileGeom &g, const EdgeMlpDesc &d) {
+inline EdgeBwd edge_mlp_bwd_plan(const TileGeom &g, const EdgeMlpDesc &d) {
   using namespace edge_mlp;
   EdgeBwd p;
   p.act1 = d.act1; p.act2 = d.act[0]; p.n_tail = d.n_tail;
@@ -272,7 +263,7 @@ struct EdgeMsgPath {
   bool fused_msg = false, fused_bwd = false, need_dE = false;
   size_t bwd_workspace_bytes = 0;   // fused_bwd: what the fused pullback asks for
 };
-inline EdgeMsgPath edge_layer_msg_path(const EdgeTileGeom &g, const EdgeMlpDesc &d, bool training) {
+inline EdgeMsgPath edge_layer_msg_path(const TileGeom &g, const EdgeMlpDesc &d, bool training) {
   EdgeMsgPath m;
   // max / min / *: with gradients only where the one-launch pullback takes it -- the primitives' pullbacks of those need the per-edge
   // messages, which the fused forward does not keep

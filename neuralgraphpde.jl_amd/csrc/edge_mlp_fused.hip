@@ -469,7 +469,7 @@ int32_t launch_edge_mlp_fused_fwd(const ngpde_graph *g, const EdgeFwd &p, const 
   if (p.form == EdgeFwdForm::Edge64) return launch_edge_mlp64_fwd(g, p, a, stream);
   const EdgeMlpDesc &d = a.d;
   EdgeMlpK k;
-  fill_tile_args(g, edge_tile_geom(g), k);   // (halo region sized by the largest halo of this graph's tiles)
+  fill_tile_args(g, tile_geom(g), k);   // (halo region sized by the largest halo of this graph's tiles)
   k.h1 = d.h1; k.act1 = d.act1; k.aggr = d.aggr;
   k.P = a.P; k.Q = a.Q; k.Eterm = a.Eterm; k.n_tail = d.n_tail;
   for (int l = 0; l < 3; ++l) {
@@ -496,7 +496,7 @@ int32_t launch_edge_mlp_fused_bwd(const ngpde_graph *g, const EdgeBwd &p, const 
   NGPDE_REQUIRE(!p.dE_missing, NGPDE_ERR_INVALID_ARGUMENT, "fused edge-MLP pullback: the [E][h1] buffer dE is required");
   if (p.form == EdgeBwdForm::Edge64) return launch_edge_mlp64_bwd(g, p, a, stream);
   const EdgeMlpDesc &d = a.d;
-  const EdgeTileGeom t = edge_tile_geom(g);
+  const TileGeom t = tile_geom(g);
   EdgeMlpBwdK k;
   fill_tile_args(g, t, k);
   k.h1 = d.h1; k.act1 = d.act1; k.aggr = d.aggr; k.n_tail = d.n_tail;

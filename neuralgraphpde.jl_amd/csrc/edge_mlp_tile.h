@@ -35,7 +35,7 @@ struct EdgeTileArgs {
   int n_tiles, halo_rows;   // halo_rows: LDS rows of the halo region = the largest halo of this graph's tiles
 };
 
-inline void fill_tile_args(const ngpde_graph *g, const EdgeTileGeom &t, EdgeTileArgs &k) {
+inline void fill_tile_args(const ngpde_graph *g, const TileGeom &t, EdgeTileArgs &k) {
   k.sched = g->by_t.sched; k.halo = g->by_t.halo; k.slots = g->by_t.slots;
   k.n_tiles = t.n_tiles;
   k.halo_rows = edge_halo_rows(t);

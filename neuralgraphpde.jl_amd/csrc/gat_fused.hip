@@ -33,10 +33,10 @@ namespace ngpde {
 
 namespace {
 
-constexpr int GD = 64;                 // input width = heads * c
+constexpr int GD = kGatWidth;          // input width = heads * c
 using GG = Geo<GD>;                    // 16 lanes per row, 32 row groups, one row per group
 constexpr int kATS = 4 * GD + 4;       // row stride (floats) of the per-head [32][heads * 64] tiles
-constexpr int kSrcTiles = 2;           // tiles per workgroup of the by-source pullback launch (dW accumulators stay in registers)
+constexpr int kSrcTiles = kGatSrcTiles; // tiles per workgroup of the by-source pullback launch (dW accumulators stay in registers)
 
 // sum / max over the 16 lanes of a DPP row (= one row group): rotate-and-add, every lane ends with the total
 template <int CTRL>
@@ -1293,59 +1293,30 @@ __global__ __launch_bounds__(kThreads, 4) void gat_node_bwd_persistent_kernel(co
                         dbacc, uacc);
 }
 
-inline int src_wgs(const ngpde_graph *g) { return (fused_num_blocks(g->n_nodes) + kSrcTiles - 1) / kSrcTiles; }
-
-struct GatLayerBwdWs {   // the pieces of the caller's pullback workspace
-  float *dz, *dscore, *dal, *slab_db, *slab_dw, *slab_u;
-};
-inline void gat_layer_bwd_layout(Workspace &w, const ngpde_graph *g, int heads, GatLayerBwdWs &p) {
-  p.dz = w.take<float>((size_t)g->n_nodes * GD);
-  p.dscore = w.take<float>((size_t)std::max<int64_t>(g->n_edges, 1) * heads);
-  p.dal = w.take<float>((size_t)g->n_nodes * heads);
-  p.slab_db = w.take<float>((size_t)fused_num_blocks(g->n_nodes) * GD);
-  p.slab_dw = w.take<float>((size_t)src_wgs(g) * GD * GD);
-  p.slab_u = w.take<float>((size_t)src_wgs(g) * 2 * GD);
-}
-
 }  // namespace
 
-bool gat_layer_fused_supported(const ngpde_graph *g, int din, int heads, int c) {
-  return g && g->has_norm && g->n_edges > 0 && g->by_t.halo_ok && g->by_s.halo_ok && din == GD && heads * c == GD &&
-         (heads == 1 || heads == 2 || heads == 4) && (uint64_t)g->n_nodes * GD * 4 < (1ull << 32) && !switch_on(Switch::NoFusedGatLayer);
-}
-
-size_t gat_layer_workspace_bytes(const ngpde_graph *g, int heads) {
-  GatLayerBwdWs p;
-  return g ? measure(gat_layer_bwd_layout, g, heads, p) : 0;
-}
-
-int32_t launch_gat_layer_fwd(const ngpde_graph *g, int heads, float slope, int act, const float *x, const float *wt, const float *a,
+int32_t launch_gat_layer_fwd(const ngpde_graph *g, const GatLayer &f, float slope, int act, const float *x, const float *wt, const float *a,
                              const float *bias, float *y, float *alpha, float *save_z, hipStream_t stream) {
   if (g->n_nodes == 0) return NGPDE_OK;
   GatFwdK k;
   k.x = x; k.wt = wt; k.a = a; k.bias = bias; k.sched = g->by_t.sched; k.halo = g->by_t.halo; k.slots = g->by_t.slots;
   k.tile_info = g->by_t.tile_info;
-  k.n_tiles = fused_num_blocks(g->n_nodes); k.act = act; k.slope = slope; k.y = y; k.alpha = alpha; k.save_z = save_z;
+  k.n_tiles = f.n_tiles; k.act = act; k.slope = slope; k.y = y; k.alpha = alpha; k.save_z = save_z;
   NGPDE_STAMP_SET(k, kStampGat, 0);
-  const dim3 grid(k.n_tiles), block(kThreads);
-  switch (heads) {
-    case 1: hipLaunchKernelGGL(gat_layer_fwd_kernel<1>, grid, block, 0, stream, k); break;
-    case 2: hipLaunchKernelGGL(gat_layer_fwd_kernel<2>, grid, block, 0, stream, k); break;
-    default: hipLaunchKernelGGL(gat_layer_fwd_kernel<4>, grid, block, 0, stream, k); break;
-  }
+  pick_int<1, 2, 4>(f.h, [&](auto h) { hipLaunchKernelGGL(gat_layer_fwd_kernel<decltype(h)::value>, dim3(f.n_tiles), dim3(kThreads), 0, stream, k); });
   NGPDE_LAUNCH_CHECK("gat_layer_fwd_kernel");
   return NGPDE_OK;
 }
 
-int32_t launch_gat_layer_bwd(const ngpde_graph *g, int heads, float slope, int act, const float *x, const float *wt, const float *a,
+int32_t launch_gat_layer_bwd(const ngpde_graph *g, const GatLayer &f, int heads, float slope, int act, const float *x, const float *wt, const float *a,
                              const float *yz, const float *alpha, const float *dy, float *dx, float *dwt, float *da, float *db,
                              void *workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (int32_t st = check_workspace("ngpde_gat_layer_backward", workspace, workspace_bytes, gat_layer_workspace_bytes(g, heads), 1)) return st;
+  if (int32_t st = check_workspace("ngpde_gat_layer_backward", workspace, workspace_bytes, gat_layer_workspace_bytes(tile_geom(g), heads), 1)) return st;
   Workspace w(workspace);
   GatLayerBwdWs p;
-  gat_layer_bwd_layout(w, g, heads, p);
+  gat_layer_bwd_layout(w, tile_geom(g), heads, p);
   float *const dz = p.dz, *const dscore = p.dscore, *const dal = p.dal, *const slab_db = p.slab_db, *const slab_dw = p.slab_dw, *const slab_u = p.slab_u;
-  const int n_tiles = fused_num_blocks(g->n_nodes), n_wg = src_wgs(g);
+  const int n_tiles = f.n_tiles, n_wg = f.src_wgs;
   const bool ident = act == NGPDE_ACT_IDENTITY;
   if (g->n_nodes > 0) {
     GatBwdTK t;
@@ -1360,20 +1331,10 @@ int32_t launch_gat_layer_bwd(const ngpde_graph *g, int heads, float slope, int a
     s.slab_u = slab_u; s.xpad = nullptr;
     NGPDE_STAMP_SET(s, kStampGat, 0);
     const dim3 block(kThreads);
-    switch (heads) {
-      case 1:
-        hipLaunchKernelGGL(gat_layer_bwd_target_kernel<1>, dim3(n_tiles), block, 0, stream, t);
-        hipLaunchKernelGGL(gat_layer_bwd_source_kernel<1>, dim3(n_wg), block, 0, stream, s);
-        break;
-      case 2:
-        hipLaunchKernelGGL(gat_layer_bwd_target_kernel<2>, dim3(n_tiles), block, 0, stream, t);
-        hipLaunchKernelGGL(gat_layer_bwd_source_kernel<2>, dim3(n_wg), block, 0, stream, s);
-        break;
-      default:
-        hipLaunchKernelGGL(gat_layer_bwd_target_kernel<4>, dim3(n_tiles), block, 0, stream, t);
-        hipLaunchKernelGGL(gat_layer_bwd_source_kernel<4>, dim3(n_wg), block, 0, stream, s);
-        break;
-    }
+    pick_int<1, 2, 4>(f.h, [&](auto h) {
+      hipLaunchKernelGGL(gat_layer_bwd_target_kernel<decltype(h)::value>, dim3(n_tiles), block, 0, stream, t);
+      hipLaunchKernelGGL(gat_layer_bwd_source_kernel<decltype(h)::value>, dim3(n_wg), block, 0, stream, s);
+    });
     NGPDE_LAUNCH_CHECK("gat_layer_bwd kernels");
   }
   hipLaunchKernelGGL(gat_layer_reduce_kernel, dim3(67), dim3(1024), 0, stream, slab_dw, g->n_nodes > 0 ? n_wg : 0, slab_db,
@@ -1421,7 +1382,7 @@ auto gat_node_kernel(int heads, bool batch) {
 size_t gat_node_dscore_elems(const ngpde_graph *g) { return (size_t)g->n_sched * kSlotWidth * 4; }
 
 bool gat_node_persistent_supported(const ngpde_graph *g, int heads, int c) {
-  if (switch_on(Switch::NoPersistent) || !gat_layer_fused_supported(g, GD, heads, c)) return false;
+  if (!gat_node_host_supported(tile_geom(g), heads, c)) return false;   // (gat_forms.h: the switch and the layer's support)
   std::vector<const void *> kernels;   // every workgroup spins for its neighbours: all of them must be resident
   for (const bool batch : {false, true}) {
     kernels.push_back(reinterpret_cast<const void *>(gat_node_kernel<true>(heads, batch)));

@@ -846,81 +846,45 @@ CombDev to_dev(const Comb &c) {
   return d;
 }
 
-// paired workgroups for the backward kernels (D <= 64: two 60 KB regions fit the CU's LDS)
-inline bool fused_bwd_pairs(int d) { return d <= 64; }
-
-// activations with a compiled-in fast path; everything else takes the runtime switch (ACT = -1)
-inline int act_template(int act) { return (act == NGPDE_ACT_RELU || act == NGPDE_ACT_IDENTITY) ? act : -1; }
-
 }  // namespace
 
-// the pre-scaled pipeline (rows stored as c .* x, gathered raw by LDS-DMA): every tile staged from LDS in both directions,
-// and c finite and positive (self loops: degree >= 1)
-bool fused_prescaled_supported(const ngpde_graph *g, int d) {
-  return g && g->has_norm && g->self_loops && d <= 128 && fused_supported(d, d) && g->by_t.halo_ok && g->by_s.halo_ok &&
-         !switch_on(Switch::NoHalo);
-}
-bool fused_supported(int din, int dout) { return din == dout && (din == 16 || din == 32 || din == 64 || din == 128); }
-int fused_tile_rows() { return kTM; }
-int fused_num_blocks(int64_t n_nodes) { return (int)((n_nodes + kTM - 1) / kTM); }
-size_t fused_mask_bytes(int64_t n_nodes, int d) {
-  const int lpr = d / 4, groups = kThreads / lpr, r = (kTM + groups - 1) / groups;   // Geo<d>::R
-  return (size_t)fused_num_blocks(n_nodes) * r * kThreads;
-}
-// slabs the backward launches write (paired workgroups share one)
-int fused_num_slabs(int64_t n_nodes, int d) {
-  const int nb = fused_num_blocks(n_nodes);
-  return fused_bwd_pairs(d) ? (nb + 1) / 2 : nb;
-}
-
+// gcn_forms.h decides (gcn_fused_fwd_form / gcn_fused_bwd_form: the template arguments, the grid, every guard); these execute
 int32_t launch_fused_fwd(const FusedFwdArgs &a, hipStream_t stream) {
   const ngpde_graph *g = a.g;
   NGPDE_REQUIRE(g && g->has_norm, NGPDE_ERR_STATE, "GCN normalisation not set (call ngpde_graph_set_gcn_norm)");
-  NGPDE_REQUIRE(fused_supported(a.d, a.d), NGPDE_ERR_UNSUPPORTED, "fused GCN path needs d in {16,32,64,128}, got %d", a.d);
+  const GcnFusedFwd f = gcn_fused_fwd_form(tile_geom(g), a.d, a.act, a.pre, a.of && a.of->slots);
+  NGPDE_REQUIRE(f.supported, NGPDE_ERR_UNSUPPORTED, "fused GCN path needs d in {16,32,64,128}, got %d", a.d);
   if (g->n_nodes == 0) return NGPDE_OK;
-  NGPDE_REQUIRE((uint64_t)g->n_nodes * a.d * 4 < (1ull << 32), NGPDE_ERR_UNSUPPORTED,
+  NGPDE_REQUIRE(f.rows_ok, NGPDE_ERR_UNSUPPORTED,
                 "fused GCN path addresses feature arrays with 32-bit byte offsets: n_nodes * d * 4 must be < 4 GiB");
+  NGPDE_REQUIRE(f.pre_ok, NGPDE_ERR_UNSUPPORTED, "the pre-scaled form needs self loops and tiles that fit the LDS halo in both directions");
   FwdK k;
   k.x = a.x; k.sched = g->by_t.sched; k.ent = g->by_t.ent; k.ell = g->by_t.ell;
   k.halo = g->by_t.halo; k.tile_info = g->by_t.tile_info; k.slots = g->by_t.slots; k.slot_w = g->by_t.slot_w;
-  if (a.of && a.of->slots && g->by_t.halo_ok && !switch_on(Switch::NoHalo)) {   // a solver plan's own-first tables (LDS-staged aggregation only:
-    k.slots = a.of->slots; k.sched = a.of->sched;                   // the same rows in another order, padded lengths in the schedule)
+  if (f.own_first) {   // a solver plan's own-first tables: the same rows in another order, padded lengths in the schedule
+    k.slots = a.of->slots; k.sched = a.of->sched;
     if (k.slot_w) k.slot_w = a.of->slot_w;
   }
-  k.self_loops = g->self_loops; k.n_tiles = fused_num_blocks(g->n_nodes); k.act = a.act;
+  k.self_loops = g->self_loops; k.n_tiles = f.grid; k.act = a.act;
   k.wt = a.wt; k.bias = a.bias; k.y = a.y; k.save_agg = a.save_agg; k.save_z = a.save_z;
   k.has_comb = a.has_comb ? 1 : 0; k.comb = to_dev(a.comb); k.comb_out = a.comb_out;
   k.save_mask = a.save_mask;
   NGPDE_STAMP_SET(k, kStampGcn, (int64_t)k.n_tiles * 16);
-  const bool use_halo = g->by_t.halo_ok && !switch_on(Switch::NoHalo);
-  NGPDE_REQUIRE(!a.pre || fused_prescaled_supported(g, a.d), NGPDE_ERR_UNSUPPORTED,
-                "the pre-scaled form needs self loops and tiles that fit the LDS halo in both directions");
-  const dim3 grid(k.n_tiles), block(kThreads);
-#define NGPDE_FWD_LAUNCH2(DD, AA, HH, PP)                                                                          \
-  if (a.ev_start) hipExtLaunchKernelGGL((gcn_fused_fwd_kernel<DD, AA, HH, PP>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, \
-                                        k.halo, k.slots, k.sched, k.x, k.slot_w, k.n_tiles, k);                       \
-  else hipLaunchKernelGGL((gcn_fused_fwd_kernel<DD, AA, HH, PP>), grid, block, 0, stream, k.halo, k.slots, k.sched, k.x, k.slot_w, k.n_tiles, k);
-#define NGPDE_FWD_LAUNCH(DD, AA)                                                                                   \
-  if (Geo<DD>::HALO && a.pre) { NGPDE_FWD_LAUNCH2(DD, AA, (Geo<DD>::HALO), (Geo<DD>::HALO)) }                      \
-  else if (Geo<DD>::HALO && use_halo) { NGPDE_FWD_LAUNCH2(DD, AA, (Geo<DD>::HALO), false) }                        \
-  else { NGPDE_FWD_LAUNCH2(DD, AA, false, false) }
-#define NGPDE_FWD_CASE(DD)                                                            \
-  case DD:                                                                            \
-    switch (act_template(a.act)) {                                                    \
-      case NGPDE_ACT_RELU: NGPDE_FWD_LAUNCH(DD, NGPDE_ACT_RELU) break;                \
-      case NGPDE_ACT_IDENTITY: NGPDE_FWD_LAUNCH(DD, NGPDE_ACT_IDENTITY) break;        \
-      default: NGPDE_FWD_LAUNCH(DD, -1) break;                                        \
-    }                                                                                 \
-    break;
-  switch (a.d) {
-    NGPDE_FWD_CASE(16)
-    NGPDE_FWD_CASE(32)
-    NGPDE_FWD_CASE(64)
-    NGPDE_FWD_CASE(128)
-  }
-#undef NGPDE_FWD_CASE
-#undef NGPDE_FWD_LAUNCH
-#undef NGPDE_FWD_LAUNCH2
+  const dim3 grid(f.grid), block(f.block);
+  pick_int<16, 32, 64, 128>(f.d, [&](auto d) {
+    pick_int<NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY, -1>(gcn_act_template(f.act), [&](auto act) {
+      pick_int<1, 0>(f.halo, [&](auto halo) {
+        pick_int<1, 0>(f.pre, [&](auto pre) {
+          constexpr bool HALO = decltype(halo)::value != 0, PRE = decltype(pre)::value != 0;
+          if constexpr (HALO || !PRE) {   // (PRE gathers raw rows from LDS: never instantiated without HALO)
+            auto kernel = gcn_fused_fwd_kernel<decltype(d)::value, decltype(act)::value, HALO, PRE>;
+            if (a.ev_start) hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k.halo, k.slots, k.sched, k.x, k.slot_w, k.n_tiles, k);
+            else hipLaunchKernelGGL(kernel, grid, block, 0, stream, k.halo, k.slots, k.sched, k.x, k.slot_w, k.n_tiles, k);
+          }
+        });
+      });
+    });
+  });
   NGPDE_LAUNCH_CHECK("gcn_fused_fwd_kernel");
   return NGPDE_OK;
 }
@@ -928,10 +892,13 @@ int32_t launch_fused_fwd(const FusedFwdArgs &a, hipStream_t stream) {
 int32_t launch_fused_bwd(const FusedBwdArgs &a, hipStream_t stream) {
   const ngpde_graph *g = a.g;
   NGPDE_REQUIRE(g && g->has_norm, NGPDE_ERR_STATE, "GCN normalisation not set (call ngpde_graph_set_gcn_norm)");
-  NGPDE_REQUIRE(fused_supported(a.d, a.d), NGPDE_ERR_UNSUPPORTED, "fused GCN path needs d in {16,32,64,128}, got %d", a.d);
+  const GcnFusedBwd f = gcn_fused_bwd_form(tile_geom(g), a.d, a.act, a.aggregate, a.pre);
+  NGPDE_REQUIRE(f.supported, NGPDE_ERR_UNSUPPORTED, "fused GCN path needs d in {16,32,64,128}, got %d", a.d);
   if (g->n_nodes == 0) return NGPDE_OK;
-  NGPDE_REQUIRE((uint64_t)g->n_nodes * a.d * 4 < (1ull << 32), NGPDE_ERR_UNSUPPORTED,
+  NGPDE_REQUIRE(f.rows_ok, NGPDE_ERR_UNSUPPORTED,
                 "fused GCN path addresses feature arrays with 32-bit byte offsets: n_nodes * d * 4 must be < 4 GiB");
+  NGPDE_REQUIRE(!a.mask || a.act == NGPDE_ACT_RELU, NGPDE_ERR_INVALID_ARGUMENT, "sign-bit masks carry relu' only");
+  NGPDE_REQUIRE(f.pre_ok, NGPDE_ERR_UNSUPPORTED, "the pre-scaled form needs self loops and tiles that fit the LDS halo in both directions");
   BwdK k;
   k.g_in = a.g_in; k.sched = g->by_s.sched; k.ent = g->by_s.ent; k.ell = g->by_s.ell;
   k.halo = g->by_s.halo; k.tile_info = g->by_s.tile_info; k.slots = g->by_s.slots; k.slot_w = g->by_s.slot_w;
@@ -940,57 +907,34 @@ int32_t launch_fused_bwd(const FusedBwdArgs &a, hipStream_t stream) {
   k.store_t = a.store_t; k.store_v = a.store_v; k.v_scale = a.v_scale;
   k.do_dense = a.do_dense ? 1 : 0; k.z = a.z; k.saved_agg = a.saved_agg; k.wt = a.wt;
   k.mask = a.mask;
-  NGPDE_REQUIRE(!a.mask || a.act == NGPDE_ACT_RELU, NGPDE_ERR_INVALID_ARGUMENT, "sign-bit masks carry relu' only");
   k.tape_late = a.has_comb ? 0 : 1;
   k.g_out = a.g_out; k.slab_dw = a.slab_dw; k.slab_db = a.slab_db;
   NGPDE_STAMP_SET(k, kStampGcn, (int64_t)k.n_tiles * 16);
-  const bool use_halo = g->by_s.halo_ok && !switch_on(Switch::NoHalo);
-  NGPDE_REQUIRE(!a.pre || fused_prescaled_supported(g, a.d), NGPDE_ERR_UNSUPPORTED,
-                "the pre-scaled form needs self loops and tiles that fit the LDS halo in both directions");
-  const bool pair = fused_bwd_pairs(a.d);   // (D <= 64: the launches below instantiate the paired kernel only)
-  const dim3 grid(pair ? (k.n_tiles + 1) / 2 : k.n_tiles), block(pair ? 2 * kThreads : kThreads);
-#define NGPDE_BWD_LAUNCH3(DD, AG, AA, HH, PP, SS)                                                                 \
-  if (a.ev_start) hipExtLaunchKernelGGL((gcn_fused_bwd_kernel<DD, AG, AA, HH, PP, SS>), grid, block, 0, stream, a.ev_start, a.ev_stop, 0, \
-                                        k.halo, k.slots, k.sched, k.g_in, k.slot_w, k.n_tiles, k);                    \
-  else hipLaunchKernelGGL((gcn_fused_bwd_kernel<DD, AG, AA, HH, PP, SS>), grid, block, 0, stream, k.halo, k.slots, k.sched, k.g_in, k.slot_w, k.n_tiles, k);
-#define NGPDE_BWD_LAUNCH2(DD, AG, AA, HH, SS) NGPDE_BWD_LAUNCH3(DD, AG, AA, HH, (DD <= 64), SS)
-#define NGPDE_BWD_LAUNCH(DD, AG, AA)                                                                              \
-  if (Geo<DD>::HALO && a.pre) { NGPDE_BWD_LAUNCH2(DD, AG, AA, (AG && Geo<DD>::HALO), (Geo<DD>::HALO)) }            \
-  else if (AG && Geo<DD>::HALO && use_halo) { NGPDE_BWD_LAUNCH2(DD, AG, AA, (AG && Geo<DD>::HALO), false) }        \
-  else { NGPDE_BWD_LAUNCH2(DD, AG, AA, false, false) }
-#define NGPDE_BWD_ACT(DD, AG)                                                         \
-  switch (act_template(a.act)) {                                                      \
-    case NGPDE_ACT_RELU: NGPDE_BWD_LAUNCH(DD, AG, NGPDE_ACT_RELU) break;              \
-    case NGPDE_ACT_IDENTITY: NGPDE_BWD_LAUNCH(DD, AG, NGPDE_ACT_IDENTITY) break;      \
-    default: NGPDE_BWD_LAUNCH(DD, AG, -1) break;                                      \
-  }
-#define NGPDE_BWD_CASE(DD)                                                            \
-  case DD:                                                                            \
-    if (a.aggregate) { NGPDE_BWD_ACT(DD, true) } else { NGPDE_BWD_ACT(DD, false) }    \
-    break;
-  switch (a.d) {
-    NGPDE_BWD_CASE(16)
-    NGPDE_BWD_CASE(32)
-    NGPDE_BWD_CASE(64)
-    NGPDE_BWD_CASE(128)
-  }
-#undef NGPDE_BWD_CASE
-#undef NGPDE_BWD_ACT
-#undef NGPDE_BWD_LAUNCH
-#undef NGPDE_BWD_LAUNCH2
-#undef NGPDE_BWD_LAUNCH3
+  const dim3 grid(f.grid), block(f.block);
+  pick_int<16, 32, 64, 128>(f.d, [&](auto d) {
+    pick_int<1, 0>(f.aggregate, [&](auto agg) {
+      pick_int<NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY, -1>(gcn_act_template(f.act), [&](auto act) {
+        pick_int<1, 0>(f.halo, [&](auto halo) {
+          pick_int<1, 0>(f.pre, [&](auto pre) {
+            constexpr int D = decltype(d)::value;
+            constexpr bool AGG = decltype(agg)::value != 0, HALO = decltype(halo)::value != 0, PRE = decltype(pre)::value != 0;
+            // HALO only where the launch gathers, and with PRE wherever it does; PAIR (two tiles per workgroup) exactly at D <= 64
+            if constexpr (HALO == (AGG && (HALO || PRE))) {
+              auto kernel = gcn_fused_bwd_kernel<D, AGG, decltype(act)::value, HALO, fused_bwd_pairs(D), PRE>;
+              if (a.ev_start) hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, a.ev_start, a.ev_stop, 0, k.halo, k.slots, k.sched, k.g_in, k.slot_w, k.n_tiles, k);
+              else hipLaunchKernelGGL(kernel, grid, block, 0, stream, k.halo, k.slots, k.sched, k.g_in, k.slot_w, k.n_tiles, k);
+            }
+          });
+        });
+      });
+    });
+  });
   NGPDE_LAUNCH_CHECK("gcn_fused_bwd_kernel");
   return NGPDE_OK;
 }
 
-bool gat_fused_supported(const ngpde_graph *g, int heads, int c) {
-  return g && g->has_norm && g->by_t.halo_ok && heads * c == 64 && (heads == 1 || heads == 2 || heads == 4) &&
-         (uint64_t)g->n_nodes * 64 * 4 < (1ull << 32);
-}
-
-int32_t launch_gat_fused_fwd(const ngpde_graph *g, int heads, int c, float slope, const float *wx, const float *al, const float *ar,
-                             float *out, float *alpha, hipStream_t stream) {
-  NGPDE_REQUIRE(gat_fused_supported(g, heads, c), NGPDE_ERR_UNSUPPORTED, "fused GAT aggregation needs heads * c == 64, heads in {1,2,4}, tiles that fit the LDS halo");
+int32_t launch_gat_fused_fwd(const ngpde_graph *g, int heads, float slope, const float *wx, const float *al, const float *ar, float *out,
+                             float *alpha, hipStream_t stream) {
   if (g->n_nodes == 0) return NGPDE_OK;
   GatK k;
   k.wx = wx; k.al = al; k.ar = ar; k.sched = g->by_t.sched; k.halo = g->by_t.halo; k.slots = g->by_t.slots;

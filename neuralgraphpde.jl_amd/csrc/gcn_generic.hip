@@ -104,14 +104,13 @@ __global__ __launch_bounds__(256) void spmm_generic_kernel(const int *__restrict
   }
 }
 
-#define NGPDE_SPMM_LAUNCH(...)                                                                                       \
-  do {                                                                                                               \
-    const dim3 grid_((unsigned)((g->n_nodes + 3) / 4)), block_(256);                                                 \
-    if (d <= 8) hipLaunchKernelGGL(spmm_generic_kernel<8>, grid_, block_, 0, stream, __VA_ARGS__);                   \
-    else if (d <= 16) hipLaunchKernelGGL(spmm_generic_kernel<16>, grid_, block_, 0, stream, __VA_ARGS__);            \
-    else if (d <= 32) hipLaunchKernelGGL(spmm_generic_kernel<32>, grid_, block_, 0, stream, __VA_ARGS__);            \
-    else hipLaunchKernelGGL(spmm_generic_kernel<64>, grid_, block_, 0, stream, __VA_ARGS__);                         \
-  } while (0)
+// spmm_generic_kernel<DP> for the d of the call (gcn_spmm_dp in gcn_forms.h), four rows per workgroup
+template <class... A>
+void launch_spmm(const ngpde_graph *g, int d, hipStream_t stream, A... args) {
+  pick_int<8, 16, 32, 64>(gcn_spmm_dp(d), [&](auto dp) {
+    hipLaunchKernelGGL(spmm_generic_kernel<decltype(dp)::value>, dim3((unsigned)((g->n_nodes + 3) / 4)), dim3(256), 0, stream, args...);
+  });
+}
 
 __global__ void act_bwd_kernel(int64_t count, int act, const float *__restrict__ dy, const float *__restrict__ z,
                                float *__restrict__ dz) {
@@ -190,7 +189,7 @@ int32_t launch_bias_act2(int64_t n, int d, int act, const float *a, const float 
 // column sums of a [n][d] array in two deterministic stages through `partial` ([kColsumChunks][d] floats)
 int32_t launch_colsum2(int64_t n, int d, const float *a, float *partial, float *out, hipStream_t stream) {
   if (d == 0) return NGPDE_OK;
-  if (n <= 4 * kColsumChunks || partial == nullptr) return launch_colsum(n, d, a, out, stream);
+  if (!colsum_two_stage(n) || partial == nullptr) return launch_colsum(n, d, a, out, stream);
   hipLaunchKernelGGL(colsum_partial_kernel, dim3((d + 63) / 64, kColsumChunks), dim3(256), 0, stream, n, d, kColsumChunks, a, partial);
   NGPDE_LAUNCH_CHECK("colsum_partial_kernel");
   return launch_colsum(kColsumChunks, d, partial, out, stream);
@@ -204,8 +203,8 @@ int32_t launch_spmm_generic(const ngpde_graph *g, bool by_source, bool gcn_norm,
                 "aggregation %d not supported by the copy_xj path", aggr);
   if (g->n_nodes == 0 || d == 0) return NGPDE_OK;
   const Csr &c = by_source ? g->by_s : g->by_t;
-  NGPDE_SPMM_LAUNCH(c.rowptr, c.col, c.eid, c.ent, g->c, g->self_loops, gcn_norm ? 1 : 0, aggr == NGPDE_AGGR_MEAN ? 1 : 0, edge_weight,
-                    (int)g->n_nodes, d, x, out, SpmmTail());
+  launch_spmm(g, d, stream, c.rowptr, c.col, c.eid, c.ent, g->c, g->self_loops, gcn_norm ? 1 : 0, aggr == NGPDE_AGGR_MEAN ? 1 : 0, edge_weight,
+              (int)g->n_nodes, d, x, out, SpmmTail());
   NGPDE_LAUNCH_CHECK("spmm_generic_kernel");
   return NGPDE_OK;
 }
@@ -240,7 +239,7 @@ int32_t launch_spmm_gcn_tail(const ngpde_graph *g, int d, const float *x, const 
   const Csr &c = g->by_t;
   SpmmTail t;
   t.bias = bias; t.act = act; t.save_z = save_z;
-  NGPDE_SPMM_LAUNCH(c.rowptr, c.col, c.eid, c.ent, g->c, g->self_loops, 1, 0, (const float *)nullptr, (int)g->n_nodes, d, x, out, t);
+  launch_spmm(g, d, stream, c.rowptr, c.col, c.eid, c.ent, g->c, g->self_loops, 1, 0, (const float *)nullptr, (int)g->n_nodes, d, x, out, t);
   NGPDE_LAUNCH_CHECK("spmm_generic_kernel (tail)");
   return NGPDE_OK;
 }

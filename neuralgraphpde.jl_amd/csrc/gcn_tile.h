@@ -9,7 +9,7 @@
 namespace ngpde {
 namespace {
 
-constexpr int kThreads = 512;
+constexpr int kThreads = kFusedThreads;   // (gcn_forms.h sizes grids and masks with it)
 constexpr int kTM = kTileRows;
 constexpr int kXcds = 8;
 

@@ -62,14 +62,6 @@ constexpr int kGformSplitTile = 128, kGformSplitTargetWgs = 512, kGformSplitMinK
 
 using GnoKernelNames = std::vector<std::string>;
 
-// f(std::integral_constant<int, V>()) for the V of the list that equals v; the last of the list where none does
-template <int V, int... Vs, class F>
-inline void gno_pick(int v, F &&f) {
-  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>());
-  else if (v == V) f(std::integral_constant<int, V>());
-  else gno_pick<Vs...>(v, f);
-}
-
 // ---- the apply kernels ---------------------------------------------------------------------------------------------------------------
 constexpr int gno_pad4(int v) { return (v + 3) & ~3; }
 constexpr int gno_kp_log2(int kdim) {

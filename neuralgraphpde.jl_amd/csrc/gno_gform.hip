@@ -264,9 +264,9 @@ int32_t ngpde_gno_gform_aggregate(const ngpde_graph_t *g, int32_t in_chs, int32_
   a.P = p_target; a.Q = q_source; a.Et = e_term; a.h = h; a.G = gout; a.hsum = hsum; a.z_out = z_out; a.act1 = act1; a.mean = mean ? 1 : 0;
   // in x edges per chunk x act1 (relu and identity instantiated, anything else read at run time: -1)
   const int act_arg = f.act1 == GnoAct1::Relu ? (int)NGPDE_ACT_RELU : f.act1 == GnoAct1::Identity ? (int)NGPDE_ACT_IDENTITY : -1;
-  gno_pick<32, 64, 128>(in_chs, [&](auto cin) {
-    gno_pick<kGformChunkAlt, kGformChunk>(f.chunk, [&](auto chunk) {
-      gno_pick<NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY, -1>(act_arg, [&](auto act) {
+  pick_int<32, 64, 128>(in_chs, [&](auto cin) {
+    pick_int<kGformChunkAlt, kGformChunk>(f.chunk, [&](auto chunk) {
+      pick_int<NGPDE_ACT_RELU, NGPDE_ACT_IDENTITY, -1>(act_arg, [&](auto act) {
         hipLaunchKernelGGL((gno_gform_fwd_kernel<decltype(cin)::value, decltype(chunk)::value, decltype(act)::value>), dim3((unsigned)g->n_nodes),
                            dim3(kGnoThreads), 0, (hipStream_t)stream, a);
       });

@@ -319,7 +319,7 @@ template <bool FUSED>
 int32_t launch_fwd(const ngpde_graph *g, int cout, int kdim, const float *T, const float *Bh, const float *z, float *m, const GnoFuse &fz,
                    hipStream_t stream) {
   if (g->n_edges == 0) return NGPDE_OK;
-  gno_pick<16, 32, 64>(kdim, [&](auto kd) {
+  pick_int<16, 32, 64>(kdim, [&](auto kd) {
     hipLaunchKernelGGL((gno_apply_mfma_fwd_kernel<decltype(kd)::value, FUSED>), dim3((unsigned)g->n_nodes), dim3(kGnoThreads), 0, stream, cout,
                        g->by_s.rowptr, g->by_s.xpos, T, Bh, z, m, fz);
   });
@@ -346,9 +346,9 @@ int32_t launch_gno_apply_mfma_bwd(const ngpde_graph *g, int cout, int kdim, cons
   const GnoApplyForm f = gno_apply_form(cout, kdim);   // NOB and the LDS request (below the default limit: gno_forms.h asserts it)
   NGPDE_REQUIRE(f.kind == GnoApplyKind::Mfma, NGPDE_ERR_UNSUPPORTED, "gno_apply_mfma_bwd_kernel: out = %d, k = %d outside the matrix-pipe kernels", cout, kdim);
   const GnoNodeGrad ng{dagg, g->by_s.col, g->by_t.rowptr, mean, act1, dq};
-  gno_pick<16, 32, 64>(kdim, [&](auto kd) {
-    gno_pick<kGnoMfmaNobSmall, kGnoMfmaNobLarge>(f.nob, [&](auto nob) {
-      gno_pick<1, 0>(dagg ? 1 : 0, [&](auto node) {
+  pick_int<16, 32, 64>(kdim, [&](auto kd) {
+    pick_int<kGnoMfmaNobSmall, kGnoMfmaNobLarge>(f.nob, [&](auto nob) {
+      pick_int<1, 0>(dagg ? 1 : 0, [&](auto node) {
         hipLaunchKernelGGL((gno_apply_mfma_bwd_kernel<decltype(kd)::value, decltype(nob)::value, decltype(node)::value != 0>), dim3((unsigned)g->n_nodes),
                            dim3(kGnoThreads), f.lds_bwd, stream, cout, g->by_s.rowptr, g->by_s.xpos, T, z, dm, dT, dBh, dz, ng);
       });

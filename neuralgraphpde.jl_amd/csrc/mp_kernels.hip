@@ -980,20 +980,16 @@ int32_t launch_gat_scores(int64_t n, int heads, int c, const float *wx, const fl
   return NGPDE_OK;
 }
 
-int32_t launch_gat_fwd(const ngpde_graph *g, int heads, int c, float slope, const float *wx, const float *al, const float *ar,
+int32_t launch_gat_fwd(const ngpde_graph *g, const GatFwd &f, int heads, int c, float slope, const float *wx, const float *al, const float *ar,
                        float *out, float *alpha, hipStream_t stream) {
-  if (g->n_nodes == 0) return NGPDE_OK;
-  if (!switch_on(Switch::NoFusedGat) && gat_fused_supported(g, heads, c)) return launch_gat_fused_fwd(g, heads, c, slope, wx, al, ar, out, alpha, stream);
+  if (!f.launch) return NGPDE_OK;
+  if (f.form == GatForm::Tiled) return launch_gat_fused_fwd(g, heads, slope, wx, al, ar, out, alpha, stream);
   const dim3 grid(rows4(g->n_nodes)), block(256);
   const int n = (int)g->n_nodes;
-  if (heads * c <= 256 && (heads == 1 || heads == 2 || heads == 4 || heads == 8 || heads == 16)) {
-    switch (heads) {
-      case 1: hipLaunchKernelGGL(gat_fwd_blocked_kernel<1>, grid, block, 0, stream, n, c, slope, g->by_t.rowptr, g->by_t.col, wx, al, ar, out, alpha); break;
-      case 2: hipLaunchKernelGGL(gat_fwd_blocked_kernel<2>, grid, block, 0, stream, n, c, slope, g->by_t.rowptr, g->by_t.col, wx, al, ar, out, alpha); break;
-      case 4: hipLaunchKernelGGL(gat_fwd_blocked_kernel<4>, grid, block, 0, stream, n, c, slope, g->by_t.rowptr, g->by_t.col, wx, al, ar, out, alpha); break;
-      case 8: hipLaunchKernelGGL(gat_fwd_blocked_kernel<8>, grid, block, 0, stream, n, c, slope, g->by_t.rowptr, g->by_t.col, wx, al, ar, out, alpha); break;
-      default: hipLaunchKernelGGL(gat_fwd_blocked_kernel<16>, grid, block, 0, stream, n, c, slope, g->by_t.rowptr, g->by_t.col, wx, al, ar, out, alpha); break;
-    }
+  if (f.form == GatForm::Blocked) {
+    pick_int<1, 2, 4, 8, 16>(heads, [&](auto h) {
+      hipLaunchKernelGGL(gat_fwd_blocked_kernel<decltype(h)::value>, grid, block, 0, stream, n, c, slope, g->by_t.rowptr, g->by_t.col, wx, al, ar, out, alpha);
+    });
     NGPDE_LAUNCH_CHECK("gat_fwd_blocked_kernel");
     return NGPDE_OK;
   }
@@ -1002,34 +998,26 @@ int32_t launch_gat_fwd(const ngpde_graph *g, int heads, int c, float slope, cons
   return NGPDE_OK;
 }
 
-int32_t launch_gat_bwd(const ngpde_graph *g, int heads, int c, float slope, const float *wx, const float *a, const float *al,
+int32_t launch_gat_bwd(const ngpde_graph *g, const GatBwd &f, int heads, int c, float slope, const float *wx, const float *a, const float *al,
                        const float *ar, const float *alpha, const float *dout, float *dscore, float *dal, float *dar,
                        float *dwx, float *da, hipStream_t stream) {
-  if (g->n_nodes == 0) return NGPDE_OK;
+  if (!f.launch) return NGPDE_OK;
   const int n = (int)g->n_nodes;
-  const bool blocked = heads * c <= 256 && c % 4 == 0 && (heads == 1 || heads == 2 || heads == 4 || heads == 8 || heads == 16) &&
-                       ((reinterpret_cast<uintptr_t>(wx) | reinterpret_cast<uintptr_t>(dout)) & 15) == 0;
-  if (blocked) {
-#define NGPDE_GAT_BWD(HH)                                                                                                  \
-  hipLaunchKernelGGL(gat_bwd_target_blocked_kernel<HH>, dim3(rows4(n)), dim3(256), 0, stream, n, c, slope, g->by_t.rowptr, \
-                     g->by_t.col, wx, al, ar, alpha, dout, dscore, dal);                                                     \
-  hipLaunchKernelGGL(gat_bwd_source_blocked_kernel<HH>, dim3(rows4(n)), dim3(256), 0, stream, n, c, g->by_s.rowptr,        \
-                     g->by_s.col, g->by_s.xpos, alpha, dout, dscore, dwx, dar);
-    switch (heads) {
-      case 1: NGPDE_GAT_BWD(1) break;
-      case 2: NGPDE_GAT_BWD(2) break;
-      case 4: NGPDE_GAT_BWD(4) break;
-      case 8: NGPDE_GAT_BWD(8) break;
-      default: NGPDE_GAT_BWD(16) break;
-    }
-#undef NGPDE_GAT_BWD
+  const dim3 grid(rows4(n)), block(256);
+  if (f.form == GatForm::Blocked) {
+    pick_int<1, 2, 4, 8, 16>(heads, [&](auto h) {
+      hipLaunchKernelGGL(gat_bwd_target_blocked_kernel<decltype(h)::value>, grid, block, 0, stream, n, c, slope, g->by_t.rowptr, g->by_t.col, wx, al, ar, alpha,
+                         dout, dscore, dal);
+      hipLaunchKernelGGL(gat_bwd_source_blocked_kernel<decltype(h)::value>, grid, block, 0, stream, n, c, g->by_s.rowptr, g->by_s.col, g->by_s.xpos, alpha, dout,
+                         dscore, dwx, dar);
+    });
     NGPDE_LAUNCH_CHECK("gat_bwd_*_blocked_kernel");
   } else {
-    hipLaunchKernelGGL(gat_bwd_target_kernel, dim3(rows4(n)), dim3(256), 0, stream, n, heads, c, slope, g->by_t.rowptr,
-                       g->by_t.col, wx, al, ar, alpha, dout, dscore, dal);
+    hipLaunchKernelGGL(gat_bwd_target_kernel, grid, block, 0, stream, n, heads, c, slope, g->by_t.rowptr, g->by_t.col, wx, al, ar, alpha, dout, dscore,
+                       dal);
     NGPDE_LAUNCH_CHECK("gat_bwd_target_kernel");
-    hipLaunchKernelGGL(gat_bwd_source_kernel, dim3(rows4(n)), dim3(256), 0, stream, n, heads, c, g->by_s.rowptr, g->by_s.col,
-                       g->by_s.xpos, alpha, dout, dscore, dwx, dar);
+    hipLaunchKernelGGL(gat_bwd_source_kernel, grid, block, 0, stream, n, heads, c, g->by_s.rowptr, g->by_s.col, g->by_s.xpos, alpha, dout, dscore, dwx,
+                       dar);
     NGPDE_LAUNCH_CHECK("gat_bwd_source_kernel");
   }
   hipLaunchKernelGGL(gat_scores_bwd_dwx_kernel, dim3(blocks_for((int64_t)n * heads * c)), dim3(256), 0, stream, (int64_t)n,

@@ -43,7 +43,7 @@ int main() {
     int graph = 0, has_norm = 0, halo_ok = 0, tables = 0, bits[6] = {0, 0, 0, 0, 0, 0}, training = 0;
     int h1 = 0, act1 = 0, n_tail = 0, aggr = 0;
     int32_t dout[4] = {0, 0, 0, 0}, act[4] = {0, 0, 0, 0};
-    EdgeTileGeom g;
+    TileGeom g;
     bool ok = static_cast<bool>(in >> entry >> graph >> has_norm >> halo_ok >> g.max_halo >> g.n_tiles >> g.n_nodes >> g.n_edges >> h1 >> act1 >> n_tail >>
                                 tables);
     for (int l = 0; ok && l < 4; ++l) ok = static_cast<bool>(in >> dout[l] >> act[l]);

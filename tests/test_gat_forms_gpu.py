@@ -5,8 +5,8 @@ Three families, each of which picks its layout and grid from the shape and the g
      gat_layer_bwd_source_kernel<H> with kSrcTiles = 2 tiles per workgroup, gat_layer_reduce_kernel over the slabs) at heads 1 / 2 / 4,
      din = heads * c = 64.  It needs every tile to fit kHaloCap = 96 staged rows and kSlotWidth = 32 entries per row in BOTH
      directions (by target: in-degree and foreign sources; by source: out-degree and foreign targets) and at least one edge.
-  B. the aggregation primitives ngpde_gat_forward / ngpde_gat_backward (csrc/mp_kernels.hip launch_gat_fwd / launch_gat_bwd):
-     the tiled forward (gcn_fused.hip gat_fused_fwd_kernel) when heads * c = 64, heads in {1, 2, 4} and the by-target tiles fit;
+  B. the aggregation primitives ngpde_gat_forward / ngpde_gat_backward (csrc/gat_forms.h gat_fwd_form / gat_bwd_form decide,
+     csrc/mp_kernels.hip launches): the tiled forward (gat_fused_fwd_kernel) when heads * c = 64, heads in {1, 2, 4} and the by-target tiles fit;
      the blocked forward <H> when H is a power of two <= 16 and heads * c <= 256 (rows of more than 64 / H edges take several
      blocks); the blocked pullback <H> when in addition c % 4 == 0 and wx, dout are 16-byte aligned; the row-per-wave kernels
      (lanes stride rows in steps of 64 edges) otherwise.
@@ -14,7 +14,8 @@ Three families, each of which picks its layout and grid from the shape and the g
 
 Every case builds its handle with ngpde_graph_create_device and an explicit node order (tiles = consecutive 32-node runs of it), asserts
 its regime first -- both directions' halos and degrees, the tile count, and that the library's support query (or, for the primitives,
-this file's restatement of launch_gat_fwd's / launch_gat_bwd's conditions) agrees -- and then compares every output with a float64
+the restatement of gat_fwd_form's / gat_bwd_form's conditions in tests/gcn_gat_forms_spec.py, which tests/test_gcn_gat_forms_host.py
+holds to the header) agrees -- and then compares every output with a float64
 restatement in torch on the CPU: logits leakyrelu(a_l . Wx_t + a_r . Wx_s), softmax over each target's incoming edges (max-subtracted),
 heads concatenated, bias and activation; gradients by autograd.  test_restatement_matches_the_oracle ties the restatement to
 oracle.ngpde_oracle.gat_conv / gat_conv_backward once.  Outputs the contract says are written start as NaN, and so does the workspace;
@@ -42,11 +43,12 @@ from oracle import ngpde_oracle as O
 from test_mp_gpu import close
 from test_edge_mlp_forms_gpu import (ACTS, HALO_CAP, ROWS, SLOT_WIDTH, TileGraph, _release_graphs, f64, graph,  # noqa: F401
                                      random_degrees, same, spread, tile_geometry, tiled_graph)
+import gcn_gat_forms_spec as F
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-GD = 64
-SWITCHES = ("NGPDE_NO_FUSED_GAT", "NGPDE_NO_FUSED_GAT_LAYER", "NGPDE_NO_PERSISTENT")
+GD = F.GAT_WIDTH
+SWITCHES = (F.NO_FUSED_GAT, F.NO_FUSED_GAT_LAYER, F.NO_PERSISTENT)
 KINKED = ("relu", "leakyrelu", "elu")          # activations with a branch at 0
 SMOOTH = ("identity", "tanh", "sigmoid", "swish", "gelu", "softplus")
 NEAR = 1e-5                                    # no logit / kinked pre-activation within NEAR * max|.| of zero
@@ -76,9 +78,14 @@ def both_ways(g):
     return g.max_halo, g.max_deg, g.halo_s, g.max_out, g.n_tiles
 
 
-def layer_fits(g):
+def geom_of(g):
+    """what the headers' choices read of a handle (csrc/tile_geom.h), from the host geometry"""
     ht, di, hs, do, _ = both_ways(g)
-    return g.E > 0 and ht <= HALO_CAP and di <= SLOT_WIDTH and hs <= HALO_CAP and do <= SLOT_WIDTH
+    return F.geom(g.n, g.E, halo_ok=ht <= HALO_CAP and di <= SLOT_WIDTH, halo_ok_s=hs <= HALO_CAP and do <= SLOT_WIDTH)
+
+
+def layer_fits(g):
+    return F.layer_fits(geom_of(g))
 
 
 def transposed(key, base):
@@ -457,20 +464,21 @@ def test_layer_refuses_tiles_beyond_the_caps(monkeypatch):
 
 # ---- B. the aggregation primitives --------------------------------------------------------------------------------------------------
 
-P2 = (1, 2, 4, 8, 16)
+P2 = F.GAT_BLOCKED_HEADS
 
 
 def fwd_form(g, heads, c, no_fused=False):
-    """launch_gat_fwd's choice, restated"""
-    if not no_fused and heads * c == GD and heads in (1, 2, 4) and g.max_halo <= HALO_CAP and g.max_deg <= SLOT_WIDTH:
-        return "tiled"
-    return "blocked" if heads * c <= 256 and heads in P2 else "row"
+    """gat_fwd_form's choice (csrc/gat_forms.h) by its restatement; no_fused: as under NGPDE_NO_FUSED_GAT=1"""
+    with pytest.MonkeyPatch.context() as mp:
+        mp.delenv(F.NO_FUSED_GAT, raising=False)
+        if no_fused:
+            mp.setenv(F.NO_FUSED_GAT, "1")
+        return F.fwd_form(geom_of(g), heads, c)
 
 
 def bwd_form(heads, c, wx, dout):
-    """launch_gat_bwd's choice, restated"""
-    aligned = (wx.data_ptr() | dout.data_ptr()) % 16 == 0
-    return "blocked" if heads * c <= 256 and c % 4 == 0 and heads in P2 and aligned else "row"
+    """gat_bwd_form's choice by its restatement; the two pointers enter as one alignment bit"""
+    return F.bwd_form(heads, c, (wx.data_ptr() | dout.data_ptr()) % 16 == 0)
 
 
 ROW_DEGREES = (0, 1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 129, 130, 300)

@@ -1,37 +1,39 @@
 """The GCNConv kernels against float64 across gathers, widths and tiles.
 
-ngpde_gcn_forward / ngpde_gcn_backward / ngpde_gcn_backward_ew run one of two families, chosen by the widths:
+ngpde_gcn_forward / ngpde_gcn_backward / ngpde_gcn_backward_ew run one of two families, chosen by the widths (csrc/gcn_forms.h:
+gcn_layer_form; this file takes its thresholds from the restatement tests/gcn_gat_forms_spec.py, which tests/test_gcn_gat_forms_host.py
+holds to the header):
   A. the fused layer (csrc/gcn_fused.hip), din = dout = D in {16, 32, 64, 128} (fused_supported).  A workgroup owns one run of 32
      positions of the handle's node order (a tile); the forward walks the by-target lists, the pullback's aggregation the by-source
      lists.  Each direction picks its gather on its own:
-       forward  (launch_fused_fwd)  LDS-staged rows, gcn_fused_fwd_kernel<D, ACT, HALO=true>, iff by_t.halo_ok and NGPDE_NO_HALO
-                                    is not 1 (`use_halo`, gcn_fused.hip:900); else the per-row gather <D, ACT, false>.
-       backward (launch_fused_bwd)  the dense launch (AGG = false: dz, dW / db slabs, G = dz W^T) never gathers; the dx launch
-                                    (AGG = true) stages rows iff by_s.halo_ok and NGPDE_NO_HALO is not 1 (:952), else the per-row
-                                    gather.  D <= 64 (fused_bwd_pairs, :955): one 1024-thread workgroup per pair of tiles (2 b,
-                                    2 b + 1); an odd tile count's last pair repeats the last tile with every row masked out (:495-500).
+       forward  (gcn_fused_fwd_form)  LDS-staged rows, gcn_fused_fwd_kernel<D, ACT, HALO=true>, iff every by-target tile fits and
+                                    NGPDE_NO_HALO is not 1; else the per-row gather <D, ACT, false>.
+       backward (gcn_fused_bwd_form)  the dense launch (AGG = false: dz, dW / db slabs, G = dz W^T) never gathers; the dx launch
+                                    (AGG = true) stages rows iff every by-source tile fits and NGPDE_NO_HALO is not 1, else the per-row
+                                    gather.  D <= 64 (fused_bwd_pairs): one 1024-thread workgroup per pair of tiles (2 b, 2 b + 1);
+                                    an odd tile count's last pair repeats the last tile with every row masked out.
                                     D = 128: one tile each.
      A tile fits the halo iff every row has at most 32 entries (kSlotWidth) and its 32 rows plus its distinct foreign rows are at
-     most 96 (kHaloCap); halo_ok means every tile of that direction fits (graph_device.hip:138, :211, all_fit_kernel).
-     ACT: RELU and IDENTITY are compiled in, the other seven take the runtime switch (ACT = -1, act_template, gcn_fused.hip:858).
+     most 96 (kHaloCap); halo_ok means every tile of that direction fits (graph_device.hip: all_fit_kernel).
+     ACT: RELU and IDENTITY are compiled in, the other seven take the runtime switch (ACT = -1, gcn_act_class).
      Per-row gather: the first 16 entries of a row come from the position-indexed block when D / 4 <= 16 (Geo::ELL: D <= 64), the
-     rest from the CSR list (gcn_tile.h:22).  coop_long_rows (gcn_fused.hip:130, :161-206): the rows of a tile (a pair half)
+     rest from the CSR list (gcn_tile.h).  coop_long_rows (gcn_fused.hip): the rows of a tile (a pair half)
      with more than kCoopDeg = 48 entries, if there are at most kCoopRows = 4 of them, are walked one at a time by
      min(32, 512 / (D / 4)) lane groups (16 at D = 128); with 5 or more the plain walk serves the whole tile.  In a pair both
      halves run n = max(mine, other) rounds, the idle half with row -1.
-     The slabs (fused_num_slabs, :876: ceil(tiles / 2) for D <= 64, tiles for D = 128) are summed by reduce_slabs_kernel (:805):
-     16 parts per element, four slabs per step while b + 48 < n_slabs (:813), then one at a time; ct = D / 16 re-lays dW out
-     row-major.  Blocks are mapped to tiles by xcd_tile (gcn_tile.h:41: contiguous runs per XCD, the remainder over the first
+     The slabs (fused_num_slabs: ceil(tiles / 2) for D <= 64, tiles for D = 128) are summed by reduce_slabs_kernel:
+     16 parts per element, four slabs per step while b + 48 < n_slabs, then one at a time; ct = D / 16 re-lays dW out
+     row-major.  Blocks are mapped to tiles by xcd_tile (gcn_tile.h: contiguous runs per XCD, the remainder over the first
      tile-count % 8 XCDs).
   B. the any-width path (csrc/gcn_generic.hip + dense_mfma.hip) for every other (din, dout):
-       dout >= din   aggregate first (api_gcn.hip:87): spmm_generic_kernel<DP> (DP = 8 / 16 / 32 / 64 for d <= 8 / 16 / 32 / above,
-                     gcn_generic.hip:110-113; rows walked in batches of 64 entries, the next batch loaded while `base + 64 < re`,
-                     :70), then the Dense forward; save_agg written.
-       dout < din    multiply first (api_gcn.hip:94-97): split-K Dense forward (dense_fwd_splits parts, summed by sum_partials),
+       dout >= din   aggregate first: spmm_generic_kernel<DP> (DP = 8 / 16 / 32 / 64 for d <= 8 / 16 / 32 / above, gcn_spmm_dp;
+                     rows walked in batches of 64 entries, the next batch loaded while `base + 64 < re`), then the Dense forward;
+                     save_agg written.
+       dout < din    multiply first: split-K Dense forward (dense_fwd_splits parts, summed by sum_partials),
                      then spmm_gcn_tail (aggregation + bias + activation in one launch); save_agg is left untouched.  The
-                     pullback's bias gradient is launch_colsum2: two stages iff N > 4 * kColsumChunks = 512 (gcn_generic.hip:193).
+                     pullback's bias gradient is launch_colsum2: two stages iff N > 4 * kColsumChunks = 512 (colsum_two_stage).
   C. the gradient w.r.t. the edge_weight argument (ngpde_gcn_backward_ew): gcn_ew_node_term_kernel + gcn_ew_edge_kernel after
-     either family's pullback; with dx = NULL the degree term's input gradient goes to the workspace's scratch (api_gcn.hip:139).
+     either family's pullback; with dx = NULL the degree term's input gradient goes to the workspace's scratch (gcn_bwd_layout).
 
 Every case builds its handle with ngpde_graph_create_device and an explicit node order, sets the normalisation it names
 (ngpde_graph_set_gcn_norm_device: self loops, edge weights, weighted or unweighted degree), asserts its regime first -- the
@@ -46,8 +48,11 @@ the cotangent dy is zeroed at such entries, so the branch cannot move the gradie
 NGPDE_NO_HALO is read once per process: cases that claim a staged direction skip when it is set.
 """
 import ctypes as C
+import json
 import math
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -60,12 +65,14 @@ from oracle import ngpde_oracle as O
 from test_mp_gpu import close
 from test_edge_mlp_forms_gpu import HALO_CAP, ROWS, SLOT_WIDTH, TileGraph, _release_graphs, graph  # noqa: F401
 from test_gat_forms_gpu import both_ways
+from test_gno_forms_gpu import hexbits
+import gcn_gat_forms_spec as F
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-FUSED = (16, 32, 64, 128)
-COOP_DEG, COOP_ROWS = 48, 4
-COLSUM_TWO_STAGE = 4 * 128                     # launch_colsum2: two stages above this many rows
+FUSED = F.FUSED
+COOP_DEG, COOP_ROWS = 48, 4                    # kernel-internal (gcn_fused.hip: kCoopDeg, kCoopRows)
+COLSUM_TWO_STAGE = F.COLSUM_TWO_STAGE          # colsum_two_stage: two stages above this many rows
 KINKED = ("relu", "leakyrelu", "elu")
 OTHER_ACTS = ("tanh", "sigmoid", "swish", "gelu", "leakyrelu", "elu", "softplus")
 NO_HALO = os.environ.get("NGPDE_NO_HALO", "")[:1] == "1"
@@ -154,7 +161,7 @@ def halo_ok(g, direction):
 
 
 def n_slabs(g, d):
-    return (g.n_tiles + 1) // 2 if d <= 64 else g.n_tiles
+    return F.n_slabs(g.n, d)
 
 
 def assert_regime(g, fwd, bwd, tiles=None):
@@ -184,7 +191,7 @@ LONG_S = {14: 1, 16: 2, 17: 4, 18: 5, 19: 1, 21: 1, 27: 1, 32: 1, 33: 1, 34: 1, 
 REGIMES = {"SS": ("staged", "staged"), "RS": ("row", "staged"), "SR": ("staged", "row"), "RR": ("row", "row")}
 
 
-def hub_graph(kind="RR", loops=True, wmode=None, extra=False):
+def build_hub_graph(kind="RR", loops=True, wmode=None, extra=False):
     """kind: which directions carry hubs (R = per-row gather); extra: repeated edges and explicit self-loop edges"""
     def make():
         pos = lambda hubs: {k * ROWS + r: d for (k, r), d in hubs.items()}
@@ -197,12 +204,16 @@ def hub_graph(kind="RR", loops=True, wmode=None, extra=False):
         if extra:
             assert (g.s == g.t).sum() == 25 and np.unique(np.stack([g.s, g.t]), axis=1).shape[1] < g.E - 25
         return g
-    g = graph(("gcn hub", kind, loops, wmode, extra), make)
+    return graph(("gcn hub", kind, loops, wmode, extra), make)
+
+
+def hub_graph(kind="RR", loops=True, wmode=None, extra=False):
+    g = build_hub_graph(kind, loops, wmode, extra)
     assert_regime(g, *REGIMES[kind], tiles=HUB_TILES)
     return g
 
 
-def tiles_graph(n_tiles, hubs):
+def build_tiles_graph(n_tiles, hubs):
     """n_tiles tiles (the last one ragged); hubs: one long row each way (per-row gather in both directions, coop)"""
     def make():
         ragged = 5 if n_tiles > 1 else 3
@@ -211,7 +222,11 @@ def tiles_graph(n_tiles, hubs):
         s, t, order = layout(n_tiles, ragged, 100 + n_tiles, {mid + 1: deg} if hubs else {},
                              {(n_tiles - 1) * ROWS: deg} if hubs else {}, foreign=3 if n_tiles > 1 else 0)
         return GcnGraph(s, t, n, order)
-    g = graph(("gcn tiles", n_tiles, hubs), make)
+    return graph(("gcn tiles", n_tiles, hubs), make)
+
+
+def tiles_graph(n_tiles, hubs):
+    g = build_tiles_graph(n_tiles, hubs)
     assert_regime(g, *(("row", "row") if hubs else ("staged", "staged")), tiles=n_tiles)
     if hubs:
         assert g.long_rows(0).sum() == 1 and g.long_rows(1).sum() == 1
@@ -553,3 +568,100 @@ def test_replayed_plan_on_per_row_graph(d, tab, act, no_mask, monkeypatch):
     for k, name in enumerate(["layer_1", "layer_2"]):
         close(ps[name]["weight"].grad, acc[k]["weight"], rtol=5e-4, atol=1e-3, what=f"dW{k + 1}")
         close(ps[name]["bias"].grad, acc[k]["bias"], rtol=5e-4, atol=1e-3, what=f"db{k + 1}")
+
+
+# ---- F. the queries' answers, pinned to the build before csrc/gcn_forms.h and csrc/gat_forms.h ----------------------------------------
+
+FORMS_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gcn_gat_forms.json")
+QUERY_SETTINGS = [None] + [(name, "1") for name in F.SWITCHES]
+AS_UNSWITCHED = "as unswitched"
+
+
+def query_graphs():
+    """name -> graph: the tile-count and hub graphs of sections A and B, built without their regime assertions (a process under
+    NGPDE_NO_HALO=1 asks too)"""
+    gs = {f"tiles={k} hubs={int(h)}": build_tiles_graph(k, h) for k in (1, 2, 3) for h in (False, True)}
+    gs.update({f"hub {kind}": build_hub_graph(kind) for kind in REGIMES})
+    assert (min(g.n for g in gs.values()), max(g.n for g in gs.values())) == (29, 1241)
+    return gs
+
+
+def setting_answers():
+    """every query of the two families under the environment of the moment, per handle.  Yes / no answers as hexbits (the GNO file's
+    encoding): gat_layer_supported one group per din over heads x head_widths(heads), node_gat_supported one group over the same
+    at din = 64.  "geometry": what a size or an answer depends on, for the restatement on the CPU.  Sizes as lists: gcn_workspace_bytes [forward, backward, backward_ew] flattened over din x dout; gat_workspace_bytes
+    over heads; gat_layer_workspace_bytes over heads (c does not enter)."""
+    lib = _lib.load()
+    hc = [(h, c) for h in F.HEADS for c in F.head_widths(h)]
+    edgeless = Edgeless(50)
+    handles = dict(query_graphs(), edgeless=edgeless)
+    out = {}
+    try:
+        for name, g in handles.items():
+            ptr = g.ptr
+            out[name] = {
+                "geometry": [g.n, g.E, int(halo_ok(g, 0)), int(halo_ok(g, 1))],   # nodes, edges, halo_ok by target / by source
+                "gat_layer_supported": " ".join(hexbits(lib.ngpde_gat_layer_supported(ptr, din, h, c) for h, c in hc) for din in F.WIDTHS),
+                "node_gat_supported": hexbits(lib.ngpde_node_gat_supported(ptr, F.GAT_WIDTH, h, c) for h, c in hc),
+                "gcn_workspace_bytes": [int(v) for din in F.WIDTHS for dout in F.WIDTHS
+                                        for v in (lib.ngpde_gcn_workspace_bytes(ptr, din, dout, 0), lib.ngpde_gcn_workspace_bytes(ptr, din, dout, 1),
+                                                  lib.ngpde_gcn_backward_ew_workspace_bytes(ptr, din, dout))],
+                "gat_workspace_bytes": [int(lib.ngpde_gat_workspace_bytes(ptr, h)) for h in F.HEADS],
+                "gat_layer_workspace_bytes": [int(lib.ngpde_gat_layer_workspace_bytes(ptr, h, 64 // max(h, 1))) for h in F.HEADS]}
+    finally:
+        _lib.destroy_later("ngpde_graph_destroy", edgeless.ptr)
+    return out
+
+
+def query_answers(monkeypatch):
+    """setting_answers() with no switch set and under each switch of the families alone; a setting the library latches once per process
+    (NGPDE_NO_HALO) is asked of a fresh child process that loads the same library.  A handle's table that a switch leaves as it is
+    without it says so instead of repeating it.  No kernel of the families is launched."""
+    answers = {}
+    for setting in QUERY_SETTINGS:
+        for name in F.SWITCHES:
+            monkeypatch.delenv(name, raising=False)
+        if setting and setting[0] in F.LATCHED:
+            tests = os.path.dirname(os.path.abspath(__file__))
+            code = (f"import sys, json; sys.path[:0] = [{os.path.dirname(tests)!r}, {tests!r}]\n"
+                    f"from ngpde_amd import _lib; _lib.LIB_PATH = {_lib.LIB_PATH!r}\n"
+                    "import test_gcn_forms_gpu as T; print('ANSWERS ' + json.dumps(T.setting_answers()))")
+            r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **{setting[0]: setting[1]}), capture_output=True, text=True, timeout=240)
+            assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+            got = json.loads([l for l in r.stdout.splitlines() if l.startswith("ANSWERS ")][-1][len("ANSWERS "):])
+        else:
+            if setting:
+                monkeypatch.setenv(*setting)
+            got = setting_answers()
+        if setting:
+            got = {h: {q: (AS_UNSWITCHED if table == answers[""][h][q] else table) for q, table in per.items()} for h, per in got.items()}
+        answers["=".join(setting) if setting else ""] = got
+    for name in F.SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    return {"queries": answers}
+
+
+def test_queries_answer_what_the_build_before_the_forms_headers_answered(monkeypatch):
+    # which kernel runs never shows in a float64 comparison; what the support queries and the workspace sizes say about it does.
+    # tests/golden/gcn_gat_forms.json holds their answers from the library as it was before the choices moved into csrc/gcn_forms.h
+    # and csrc/gat_forms.h (the field "recorded_from" names the commit; tools/record_forms.py --family gcn_gat wrote it).  Handles
+    # are built and queries made; no kernel of the families is launched.
+    want = json.load(open(FORMS_GOLDEN))["queries"]
+    got = query_answers(monkeypatch)["queries"]
+    assert set(got) == set(want) == {""} | {"=".join(s) for s in QUERY_SETTINGS[1:]}
+    for setting, per in got.items():
+        assert set(per) == set(want[setting]) and len(per) == 11
+        for handle, tables in per.items():
+            wrong = [q for q, table in tables.items() if table != want[setting][handle].get(q)]
+            assert not wrong and set(tables) == set(want[setting][handle]), (setting or "unswitched", handle, wrong)
+    # the answers are the restatement's too (the host test holds the headers to it; this holds the entries to the headers)
+    for handle, tables in got[""].items():
+        sizes = tables["gcn_workspace_bytes"]
+        assert len(sizes) == 3 * len(F.WIDTHS) ** 2 and all(0 < f and 0 < b <= e for f, b, e in zip(sizes[0::3], sizes[1::3], sizes[2::3])), handle
+    # the switches act where they are meant to: the layer's on both support queries, the solver's on its own, the others on none
+    changed = {setting: {q for tables in per.values() for q, table in tables.items() if table != AS_UNSWITCHED} for setting, per in got.items() if setting}
+    assert changed == {"NGPDE_NO_HALO=1": set(), "NGPDE_NO_FUSED_GAT=1": set(), "NGPDE_NO_FUSED_GAT_LAYER=1": {"gat_layer_supported", "node_gat_supported"},
+                       "NGPDE_NO_PERSISTENT=1": {"node_gat_supported"}}
+    fits = {h for h, tables in got[""].items() if int(tables["gat_layer_supported"].replace(" ", ""), 16)}
+    assert fits == {name for name, g in query_graphs().items() if g.fits_t and g.fits_s} >= {"tiles=3 hubs=0", "hub SS"}   # staged both ways, with edges
+    assert fits.isdisjoint({"edgeless", "hub RS", "hub SR", "hub RR", "tiles=3 hubs=1"})

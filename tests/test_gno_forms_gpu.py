@@ -506,7 +506,7 @@ def query_answers(monkeypatch):
 def test_queries_answer_what_the_build_before_the_forms_header_answered(monkeypatch):
     # which kernel runs never shows in a float64 comparison; what the ABI queries and the layer's workspace size say about it does.
     # tests/golden/gno_forms.json holds their answers from the library as it was before the choices moved into csrc/gno_forms.h (the
-    # field "recorded_from" names the commit; tools/record_gno_forms.py wrote it).  No kernel of the family is launched here.
+    # field "recorded_from" names the commit; tools/record_forms.py --family gno wrote it).  No kernel of the family is launched here.
     want = json.load(open(FORMS_GOLDEN))
     got = query_answers(monkeypatch)
     assert set(got["queries"]) == set(want["queries"]) == {""} | {"=".join(s) for s in QUERY_SETTINGS[1:]}
